@@ -33,6 +33,9 @@ Extra objects on the JSON line:
                split over the processes).
   file_to_tsv  the reference's `Time to count` window (bin/mercat2.py:335-346): the S2 sample as a
                file in the page cache -> TSV closed, through harness.run_sample; plain and .gz.
+
+--dump-outputs DIR writes the table the last timed step exported (keys, counts) as float64 .npy files, so
+that two builds run with the same arguments -- hence the same seeded input -- can be compared output for output.
 """
 import argparse
 import json
@@ -120,6 +123,56 @@ def cpu_baseline(k, c, genome, gseed, rseed, chunk_reads, want_cores=0):
         out["calibration_note"] = "oracle rate / reference find_kmers rate on the same sample, measured in the build " \
                                   "container by tools/calibrate_cpu_ref.py (profiles/round2_calibration.json)"
     return out
+
+
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 64_000_000  # all files of one dump together
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, parts, words, budget=DUMP_BYTES, suffix=""):
+    """Write what the timed step hands its caller -- the sorted (key, count) rows of the table, one
+    (keys, counts, rows) triple of export buffers per GPU in owner order, i.e. ascending key ranges --
+    as float64 .npy files in out_dir:
+      keys.npy    (n, 2 * words): every 64-bit key word as its high and its low 32 bits (exact in float64)
+      counts.npy  (n,)
+      summary.npy [rows, sum of counts] of the whole table
+    n is every row when that fits in `budget` bytes; otherwise a fixed sample of rows (seeded, in table
+    order) and index.npy, their row numbers in the table.  Returns n."""
+    import numpy as np
+    import torch
+    total = sum(r for _, _, r in parts)
+    count_sum = sum(int(c[:r].sum().item()) for _, c, r in parts)
+    room = budget - 1024  # (the summary and the four .npy headers)
+    if total * (2 * words + 1) * 8 <= room:
+        pick = None
+        n = total
+    else:
+        n = room // ((2 * words + 2) * 8)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=n, replace=False))
+    keys, counts, first = [], [], 0
+    for k_dev, c_dev, r in parts:
+        k_rows = k_dev[: r * words].view(r, words)
+        c_rows = c_dev[:r]
+        if pick is not None:
+            lo, hi = np.searchsorted(pick, [first, first + r])
+            idx = torch.from_numpy(pick[lo:hi] - first).to(c_dev.device)
+            k_rows, c_rows = k_rows.index_select(0, idx), c_rows.index_select(0, idx)
+        keys.append(k_rows.cpu().numpy().view(np.uint64))
+        counts.append(c_rows.cpu().numpy())
+        first += r
+    keys = np.concatenate(keys) if keys else np.empty((0, words), dtype=np.uint64)
+    halves = np.empty((keys.shape[0], 2 * words), dtype=np.float64)
+    halves[:, 0::2] = keys >> np.uint64(32)
+    halves[:, 1::2] = keys & np.uint64(0xFFFFFFFF)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "keys%s.npy" % suffix), halves)
+    np.save(os.path.join(out_dir, "counts%s.npy" % suffix),
+            (np.concatenate(counts) if counts else np.empty(0, dtype=np.int64)).astype(np.float64))
+    np.save(os.path.join(out_dir, "summary%s.npy" % suffix), np.array([total, count_sum], dtype=np.float64))
+    if pick is not None:
+        np.save(os.path.join(out_dir, "index%s.npy" % suffix), pick.astype(np.float64))
+    return n
 
 
 # ------------------------------------------------------------------------------ self-launch
@@ -223,10 +276,16 @@ def main():
     ap.add_argument("--contexts", type=int, default=int(os.environ.get("MK_BENCH_CONTEXTS", "0")),
                     help="engine contexts (HIP streams) per GPU; chunks are dealt round-robin and counted "
                          "concurrently, the tables are merged on the device at the end of the step")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the table the last timed step exported as DIR/<name>.npy "
+                         "(float64, at most 64 MB: a seeded sample of the rows of a larger table; see dump_outputs). "
+                         "bench_outputs/ is ignored by git")
     args = ap.parse_args(sys.argv[1:] + os.environ.get("MK_BENCH_EXTRA", "").split())  # (MK_BENCH_EXTRA: more flags, for A/B scripts)
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     single = bool(args.single_process) and args.gpus > 1
     if "RANK" not in os.environ and args.gpus > 1 and not single:
         # no launcher: be one (before torch.cuda / HIP is touched in this process)
@@ -305,6 +364,7 @@ def main():
             self.out = [(torch.empty(cap * self.words, dtype=torch.int64, device="cuda:%d" % d),
                          torch.empty(cap, dtype=torch.int64, device="cuda:%d" % d)) for d in devices]
             self.merge_stats = None
+            self.last_rows = [0] * len(devices)  # rows the last step's export left in self.out, per device
             self.phase = {"count_s": 0.0, "merge_s": 0.0, "export_s": 0.0, "steps": 0}  # this process, summed over steps
 
         def close(self):
@@ -367,9 +427,10 @@ def main():
                     merge_ranks(self.leaders[0], self.key_bits, device=dev)
                 t2 = time.perf_counter()
                 if len(devices) == 1:
-                    rows = export_device(0)
+                    self.last_rows = [export_device(0)]
                 else:
-                    rows = sum(self.pool.map(export_device, range(len(devices))))  # every owner sorts its own range
+                    self.last_rows = list(self.pool.map(export_device, range(len(devices))))  # every owner sorts its own range
+                rows = sum(self.last_rows)
                 t3 = time.perf_counter()
                 ph = self.phase
                 ph["count_s"] += t1 - t0
@@ -484,6 +545,11 @@ def main():
     parts, nchunks, total_bases, gen_s = load_sample(mode, args.reads, args.genome, args.genome_seed, args.read_seed, args.sub_ppm)
     step = eng.make_step(parts)
     dt, total_rows, ranks_seen = timed(eng, step, args.steps, args.warmup, True)
+    if args.dump_outputs:
+        # (every device was synchronised at the end of the timed region: the export buffers hold the last step's rows;
+        # N ranks: every rank writes the rows it owns, files suffixed with its rank, an N-th of the size limit each)
+        dump_outputs(args.dump_outputs, [(eng.out[di][0], eng.out[di][1], r) for di, r in enumerate(eng.last_rows)], eng.words,
+                     DUMP_BYTES // world, "" if world == 1 else "_rank%d" % rank)
     st = sum_stats(eng.all)
     for c in eng.all:
         c.set_profiling(False)
