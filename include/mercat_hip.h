@@ -131,6 +131,26 @@ int mk_clean_stats(mk_ctx* ctx, mk_clean_gpu_t* out);
  * cuts at (lib/mercat2_fasta.py:35-38). */
 int mk_clean_runs(mk_ctx* ctx, uint64_t* starts, uint64_t* ends, size_t cap, size_t* n);
 
+/* FASTQ input as MerCat2 counts it with -skipclean (fq2fa, lib/mercat2_fasta.py:175-198: `sed -n '1~4s/^@/>/p;2~4p'`
+ * read back in universal-newline text mode, written to <base>.fna.gz).  Lines are split on '\n' only and numbered
+ * across the text: line 4i+1 is kept, its '@' made a '>', when it starts with '@' and dropped otherwise; line 4i+2 is
+ * kept as it stands; lines 4i+3 and 4i+4 are dropped; the text read back turns '\r\n' and a lone '\r' into '\n'. */
+typedef struct mk_fastq_stats_t {
+  uint64_t lines;           /* lines of the FASTQ text (a last line without '\n' is one)                 */
+  uint64_t reads;           /* lines 4i+1 kept (header lines of the converted text)                     */
+  uint64_t headers_dropped; /* lines 4i+1 that do not start with '@'                                    */
+  uint64_t fasta_bytes;     /* size of the converted text                                               */
+  uint64_t crlf;            /* '\r\n' pairs of kept lines, each one '\n' in the converted text           */
+} mk_fastq_stats_t;
+/* With on != 0 every chunk fed from now on (mk_chunk_feed / mk_chunk_feed_device) is raw FASTQ text, a file of its own
+ * that starts at line 1, and is counted exactly as find_kmers counts the text fq2fa makes of it.  The chunk is rewritten
+ * in place before the parser (dropped lines become line ends, the kept '@' a '>'), so text already on the device is
+ * refused by mk_count_device (MK_ERR_STATE), and so is mk_count_file.  Nucleotide alphabet only; not together with clean
+ * mode (MK_ERR_ARG).  mk_reset keeps the mode and zeroes the stats. */
+int mk_set_fastq(mk_ctx* ctx, int on);
+/* The conversion's figures summed over the chunks counted in FASTQ mode since mk_reset (mk_fq2fa's for the same text). */
+int mk_fastq_stats(mk_ctx* ctx, mk_fastq_stats_t* out);
+
 /* ---- one chunk = one find_kmers call (lib/mercat2_kmers.py:32-78) ------------------------ */
 int mk_chunk_begin(mk_ctx* ctx);
 /* Append raw FASTA bytes (host memory) of the current chunk; may be called repeatedly, the
@@ -385,6 +405,12 @@ typedef struct mk_clean_stats_t {
   int64_t unsupported_record; /* -1, or the index of the first record this function does not rewrite */
 } mk_clean_stats_t;
 int mk_remove_n(const uint8_t* text, size_t n, int toupper, uint8_t** out, size_t* out_len, mk_clean_stats_t* st);
+/* fq2fa (see mk_set_fastq) on a whole FASTQ text held in memory: *out receives the converted text exactly as it stands,
+ * uncompressed, in MerCat2's <base>.fna.gz (malloc'ed: release it with mk_free), st its figures.  A byte >= 0x80 in a
+ * line of the converted text that is not a header line is MK_ERR_NON_ASCII (*out stays NULL), as in the counting
+ * calls; header lines may hold any bytes.  (The reference decodes the text as UTF-8 and raises UnicodeDecodeError on
+ * invalid UTF-8 in a kept line; this function does not check that.) */
+int mk_fq2fa(const uint8_t* text, size_t n, uint8_t** out, size_t* out_len, mk_fastq_stats_t* st);
 void mk_free(void* p);
 /* textwrap.wrap(text, width) of CPython 3.10 for ASCII text, as mk_remove_n applies it to the pieces of a split
  * sequence: the lines, each followed by '\n', in a malloc'ed buffer (mk_free).  A self-check for tests. */

@@ -4,10 +4,13 @@
 The count phase and what stands directly in front of and behind it: inputs are
 FASTA (nucleotide or protein; plain or .gz); nucleotide inputs go through removeN first unless
 -skipclean is given (bin/mercat2.py:239-244), exactly as in the reference; the combined tables are
-written after counting.  FASTQ conversion and QC, ORF calling (-prod / -fgs), reports, PCA and plots
-belong to the reference's other layers: their flags are accepted where they change nothing here
-(-lowmem, -pca, -debug, -category_file) and refused with a clear message where the run would need
-that layer's output (-prod, -fgs, FASTQ input).
+written after counting.  FASTQ input (.fq, .fastq, plain or .gz) is taken with -skipclean: MerCat2 then
+converts it with fq2fa only (lib/mercat2_fasta.py:175-198) into clean/<base>.fna.gz and counts that as a
+nucleotide sample; here the GPU counts the raw reads the same way while the file is written.  Without
+-skipclean MerCat2 trims the reads with fastp first, a tool this engine does not run: refused.  FASTQ QC,
+ORF calling (-prod / -fgs), reports, PCA and plots belong to the reference's other layers: their flags are
+accepted where they change nothing here (-lowmem, -pca, -debug, -category_file) and refused with a clear
+message where the run would need that layer's output (-prod, -fgs).
 """
 from __future__ import annotations
 
@@ -19,9 +22,9 @@ import timeit
 from pathlib import Path
 
 from . import __version__
-from .fasta import removeN_background, removeN_text
+from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_background, removeN_text
 from .kmers import read_fasta_bytes
-from .harness import run_raw_clean, run_sample, run_text
+from .harness import run_raw_clean, run_raw_fastq, run_sample, run_text
 from .report import merge_counters, merge_counters_T
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
@@ -77,8 +80,21 @@ def parseargs(argv=None):
     return args, p
 
 
-def classify(path: Path):
-    """(type, basename) by the reference's extension tables (bin/mercat2.py:26-28, 264-283)."""
+def fastq_ext(path: Path) -> str:
+    """The FASTQ extension of the name ('' for none), the longest that matches, as the reference picks it."""
+    suffixes = path.suffixes
+    ext = ""
+    for i in reversed(range(len(suffixes))):
+        cand = "".join(suffixes[i:])
+        if cand in FILE_EXT_FASTQ:
+            ext = cand
+    return ext
+
+
+def classify(path: Path, skipclean: bool = False):
+    """(type, basename) by the reference's extension tables (bin/mercat2.py:26-28, 264-283).  A FASTQ name is a
+    nucleotide sample with ``skipclean`` (MerCat2 converts it with fq2fa and counts that); without it MerCat2 trims the
+    reads with fastp first, which this engine does not run: SystemExit."""
     suffixes = path.suffixes
     ext = ""
     for i in reversed(range(len(suffixes))):
@@ -86,13 +102,60 @@ def classify(path: Path):
         if cand in FILE_EXT_NUCLEOTIDE + FILE_EXT_PROTEIN:
             ext = cand
     if not ext:
-        for i in reversed(range(len(suffixes))):
-            if "".join(suffixes[i:]) in FILE_EXT_FASTQ:
-                raise SystemExit(f"'{path.name}': FASTQ input needs MerCat2's fastq_to_fasta layer (fastp / fastqc), which is "
-                                 "not part of this engine; convert it to FASTA first")
+        fq = fastq_ext(path)
+        if fq and skipclean:
+            return "nucleotide", path.name[: -len(fq)]
+        if fq:
+            raise SystemExit(f"'{path.name}': without -skipclean MerCat2 trims FASTQ reads with fastp, which is not part of "
+                             "this engine; -skipclean counts the reads untrimmed (fq2fa only), as MerCat2 does with "
+                             "-skipclean or when fastp is not installed")
         return None, None
     base = path.name[: -len(ext)]
     return ("protein" if ext in FILE_EXT_PROTEIN else "nucleotide"), base
+
+
+def count_converted(base: str, holder: dict, fut, tsv: Path, args, devices, home: int, lines: list, tables: dict, t: dict) -> None:
+    """The table of a sample whose text a background job rewrites (removeN) or converts (fq2fa) and writes as a level-9
+    .gz, counted from the text in memory: the reference cuts the REWRITTEN file, and its size on disk decides
+    (bin/mercat2.py:101) -- without waiting for the whole gzip: a DEFLATE stream only grows, so "chunked" is known the
+    moment its bytes pass -s MiB.  Until that is known, both tables are counted (milliseconds each) and the size picks one."""
+    limit = args.s * 1024 * 1024
+    holder["ready"].wait()
+    if "text" not in holder:
+        fut.result()  # (the rewrite failed: its exception surfaces here, as it would in MerCat2)
+    text = holder.pop("text")
+    decision = holder["decision"]
+    kw = dict(device=home, streams=args.streams, canonical=args.canonical, timings=t)
+    # the .gz cannot be larger than the text plus the stored-block overhead zlib falls back to
+    certain_whole = args.s <= 0 or len(text) + len(text) // 1000 + 4096 < limit
+    chunked = False if certain_whole else decision.wait(0)
+    if chunked is not None:
+        run_text(base, text, tsv, args.k, args.c, args.s, chunked, devices=devices if chunked else None,
+                 report=lines.append, keep=tables, **kw)
+        return
+    # not known yet: count BOTH tables now, publish the one the size selects
+    t_wait = timeit.default_timer()
+    cand = {}
+    for name, ch in (("whole", False), ("chunked", True)):
+        lc, kc = [], {}
+        run_text(base, text, str(tsv) + "." + name, args.k, args.c, args.s, ch, devices=devices if ch else None,
+                 report=lc.append, keep=kc, **kw)
+        cand[ch] = (str(tsv) + "." + name, lc, kc)
+    del text
+    chunked = decision.wait()
+    if chunked is None:
+        fut.result()  # (the gzip writer failed)
+    t["decide_s"] = timeit.default_timer() - t_wait
+    path_, lc, kc = cand[bool(chunked)]
+    if os.path.exists(path_):
+        os.replace(path_, tsv)
+    lines.extend(lc)
+    tables.update(kc)
+    other_path, _, other_keep = cand[not chunked]
+    if os.path.exists(other_path):
+        os.unlink(other_path)
+    for ctx_ in other_keep.values():
+        ctx_.close()
 
 
 def main(argv=None) -> int:
@@ -124,21 +187,28 @@ def main(argv=None) -> int:
         folder = Path(os.path.abspath(os.path.expanduser(args.f)))
         files += [folder / name for name in sorted(os.listdir(folder)) if (folder / name).is_file()]
     samples = {"nucleotide": {}, "protein": {}}
+    fastq = set()  # nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)
     for f in files:
-        kind, base = classify(f.expanduser().absolute())
+        kind, base = classify(f.expanduser().absolute(), args.skipclean)
         if kind:
             samples[kind][base] = f
+            if fastq_ext(f):
+                fastq.add(base)
+            else:
+                fastq.discard(base)
 
     from concurrent.futures import ThreadPoolExecutor
-    # ---- "Loading files" (bin/mercat2.py:229-298): nucleotide FASTA goes through removeN unless -skipclean.  The text
-    # rewrite is native and fast; the level-9 gzip of <base>_clean.fna.gz is not (~1.5 MB/s), so the files are written
-    # by background threads while the counting below already runs on the cleaned text in memory.
+    # ---- "Loading files" (bin/mercat2.py:229-298): nucleotide FASTA goes through removeN unless -skipclean, FASTQ
+    # through fq2fa.  The text rewrite is native and fast; the level-9 gzip of clean/<base>_clean.fna.gz or
+    # clean/<base>.fna.gz is not (~1.5 MB/s), so the files are written by background threads while the counting below
+    # already runs on the text in memory.
     print("Loading files")
     load_start = timeit.default_timer()
     clean = not args.skipclean
     cleaned = {}  # base -> [clean file, raw bytes (until counted), future of (.gz size, stats), holder of the cleaned text, timings]
     gz_writers = ThreadPoolExecutor(max(1, min(int(args.n), 16)))
-    if clean and samples["nucleotide"]:
+    to_load = {b: f for b, f in samples["nucleotide"].items() if clean or b in fastq}
+    if to_load:
         import threading
         budget = [8 << 30]  # bytes of input held in memory between loading and counting; samples beyond it are read when counted
         budget_lock = threading.Lock()
@@ -154,11 +224,14 @@ def main(argv=None) -> int:
             t0 = timeit.default_timer()
             raw = read_fasta_bytes(f)
             t["read_s"] = timeit.default_timer() - t0
-            path, fut, holder = removeN_background(f, raw, out / "clean", args.toupper, gz_writers, timings=t,
-                                                   limit=args.s * 1024 * 1024)
+            if base in fastq:
+                path, fut, holder = fq2fa_background(f, raw, out / "clean", base, gz_writers, timings=t, limit=args.s * 1024 * 1024)
+            else:
+                path, fut, holder = removeN_background(f, raw, out / "clean", args.toupper, gz_writers, timings=t,
+                                                       limit=args.s * 1024 * 1024)
             return base, [path, raw, fut, holder, t]
-        with ThreadPoolExecutor(max(1, min(int(args.n), 8, len(samples["nucleotide"])))) as pool:
-            for base, job in pool.map(load, samples["nucleotide"].items()):
+        with ThreadPoolExecutor(max(1, min(int(args.n), 8, len(to_load)))) as pool:
+            for base, job in pool.map(load, to_load.items()):
                 cleaned[base] = job
     print(f"Time to load {len(samples['nucleotide']) + len(samples['protein'])} files: {round(timeit.default_timer() - load_start, 2)} seconds")
 
@@ -187,7 +260,29 @@ def main(argv=None) -> int:
             t = {}
             t0 = timeit.default_timer()
             tsv = tsv_dir / f"{base}_counts.tsv"
-            if kind == "nucleotide" and clean:
+            if kind == "nucleotide" and base in fastq:
+                limit = args.s * 1024 * 1024
+                if cleaned[base] is None:  # (not loaded up front: the conversion, its file, then the count)
+                    text, _ = fq2fa_text(read_fasta_bytes(f))
+                    os.makedirs(out / "clean", exist_ok=True)
+                    size = _write_clean_gz(out / "clean" / f"{base}.fna.gz", text, t)
+                    chunked = args.s > 0 and size >= limit
+                    run_text(base, text, tsv, args.k, args.c, args.s, chunked, device=home, devices=devices if chunked else None,
+                             streams=args.streams, canonical=args.canonical, report=lines.append, keep=tables, timings=t)
+                    del text
+                else:
+                    clean_file, raw, fut, holder, t_load = cleaned[base]
+                    # the table straight from the raw reads, counted as fq2fa leaves them (rewritten in place on the GPU),
+                    # while the conversion and the level-9 gzip of clean/<base>.fna.gz run in the background
+                    done = run_raw_fastq(base, raw, tsv, args.k, args.c, limit, device=home, canonical=args.canonical,
+                                         report=lines.append, keep=tables, timings=t)
+                    cleaned[base][1] = raw = None
+                    if done is not None:
+                        holder["drop"]()
+                    else:  # the sample may be chunked: count the converted text
+                        count_converted(base, holder, fut, tsv, args, devices, home, lines, tables, t)
+                    t.update(t_load)
+            elif kind == "nucleotide" and clean:
                 limit = args.s * 1024 * 1024
                 if cleaned[base] is None:  # (not loaded up front: the rewrite, its file, then the count, one after the other)
                     clean_file, _gc, text = removeN_text(f, out / "clean", args.toupper, timings=t)
@@ -206,46 +301,9 @@ def main(argv=None) -> int:
                     if done is not None:
                         holder["drop"]()
                     else:
-                        # the sample may be chunked (the reference cuts the CLEANED file, and its size on disk decides,
-                        # bin/mercat2.py:101, 243), or holds text whose rewrite the GPU does not reproduce: count the text
-                        # the host rewrite produced (native, memory speed) -- without waiting for the level-9 gzip of the
-                        # clean file: a DEFLATE stream only grows, so "chunked" is known the moment its bytes pass -s MiB.
-                        holder["ready"].wait()
-                        if "text" not in holder:
-                            fut.result()  # (the rewrite failed: its exception surfaces here, as it would in MerCat2)
-                        text = holder.pop("text")
-                        decision = holder["decision"]
-                        kw = dict(device=home, streams=args.streams, canonical=args.canonical, timings=t)
-                        # the .gz cannot be larger than the text plus the stored-block overhead zlib falls back to
-                        certain_whole = args.s <= 0 or len(text) + len(text) // 1000 + 4096 < limit
-                        chunked = False if certain_whole else decision.wait(0)
-                        if chunked is not None:
-                            run_text(base, text, tsv, args.k, args.c, args.s, chunked, devices=devices if chunked else None,
-                                     report=lines.append, keep=tables, **kw)
-                        else:
-                            # not known yet: count BOTH tables now (milliseconds each), publish the one the size selects
-                            t_wait = timeit.default_timer()
-                            cand = {}
-                            for name, ch in (("whole", False), ("chunked", True)):
-                                lc, kc = [], {}
-                                run_text(base, text, str(tsv) + "." + name, args.k, args.c, args.s, ch, devices=devices if ch else None,
-                                         report=lc.append, keep=kc, **kw)
-                                cand[ch] = (str(tsv) + "." + name, lc, kc)
-                            chunked = decision.wait()
-                            if chunked is None:
-                                fut.result()  # (the gzip writer failed)
-                            t["decide_s"] = timeit.default_timer() - t_wait
-                            path_, lc, kc = cand[bool(chunked)]
-                            if os.path.exists(path_):
-                                os.replace(path_, tsv)
-                            lines.extend(lc)
-                            tables.update(kc)
-                            other_path, _, other_keep = cand[not chunked]
-                            if os.path.exists(other_path):
-                                os.unlink(other_path)
-                            for ctx_ in other_keep.values():
-                                ctx_.close()
-                        del text
+                        # the sample may be chunked (the reference cuts the CLEANED file, bin/mercat2.py:101, 243), or holds
+                        # text whose rewrite the GPU does not reproduce: count the text the host rewrite produced
+                        count_converted(base, holder, fut, tsv, args, devices, home, lines, tables, t)
                 t.update(t_load)
             else:
                 run_sample(base, f, tsv, args.k, args.c, args.s, device=home,

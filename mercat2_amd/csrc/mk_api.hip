@@ -106,7 +106,7 @@ static void prof_collect(mk_ctx* c) {
 // ----------------------------------------------------------------------------- lifetime
 // "mercat_hip <abi>.<minor> (gfx950)": the ABI number changes whenever a struct or a signature of include/mercat_hip.h does
 // (native.py checks it against its own MK_ABI before it trusts the struct layouts)
-extern "C" const char* mk_version(void) { return "mercat_hip 4.0 (gfx950)"; }
+extern "C" const char* mk_version(void) { return "mercat_hip 4.1 (gfx950)"; }
 
 extern "C" int mk_device_count(void) {
   int n = 0;
@@ -230,7 +230,7 @@ extern "C" void mk_destroy(mk_ctx* c) {
   for (auto& e : c->event_pool) (void)hipEventDestroy(e);
   MkDevBuf* all[] = {&c->raw, &c->seq, &c->codes, &c->bad, &c->tile_maps, &c->info, &c->ctab, &c->rtab_chunk, &c->run,
                      &c->run_ref, &c->arena, &c->run128, &c->ex128, &c->ex128_out, &c->ex_keys, &c->ex_cnts, &c->ex_keys2, &c->ex_cnts2, &c->ex_tmp, &c->part, &c->part_meta, &c->surv_keys, &c->surv_cnts, &c->surv_keys2,
-                     &c->xfer_out, &c->xfer_in, &c->xfer_meta, &c->clean_meta, &c->clean_runs};
+                     &c->xfer_out, &c->xfer_in, &c->xfer_meta, &c->clean_meta, &c->clean_runs, &c->fastq_stats, &c->fastq_tiles};
   for (auto* b : all) buf_free(*b);
   if (c->h_info) (void)hipHostFree(c->h_info);
   if (c->ingest_ring) (void)hipHostFree(c->ingest_ring);
@@ -279,6 +279,10 @@ static int reset_impl(mk_ctx* c, size_t expect_rows) {
   // guess leaves no room for.  Only a new context has no guess and hands its first chunk's survivors over through regions.)
   c->fuse_cap = 0;
   c->clean_n_runs = c->clean_n_bytes = c->clean_gc = c->clean_symbols = c->clean_raw = c->clean_headers = c->clean_last_runs = 0;
+  if (c->fastq_stats.p) {
+    int rc = mk_fastq_clear(c);
+    if (rc) return rc;
+  }
   MK_HIP(hipStreamSynchronize(c->stream));
   return MK_OK;
 }
@@ -307,9 +311,40 @@ extern "C" int mk_set_canonical(mk_ctx* c, int on) {
 extern "C" int mk_set_clean(mk_ctx* c, int on, int toupper) {
   if (!c) return MK_ERR_ARG;
   if (on && c->alphabet != MK_ALPHABET_NT2) { c->err = "mk_set_clean: removeN applies to nucleotide FASTA (bin/mercat2.py:276)"; return MK_ERR_ARG; }
+  if (on && c->fastq_mode) { c->err = "mk_set_clean: FASTQ mode is on (MerCat2 does not run removeN on converted FASTQ)"; return MK_ERR_ARG; }
   if (c->in_chunk) { c->err = "mk_set_clean: a chunk is open"; return MK_ERR_STATE; }
   c->clean_mode = on ? 1 : 0;
   c->clean_upper = (on && toupper) ? 1 : 0;
+  return MK_OK;
+}
+
+extern "C" int mk_set_fastq(mk_ctx* c, int on) {
+  if (!c) return MK_ERR_ARG;
+  if (on && c->alphabet != MK_ALPHABET_NT2) { c->err = "mk_set_fastq: FASTQ is counted as a nucleotide sample (bin/mercat2.py:290-293)"; return MK_ERR_ARG; }
+  if (on && c->clean_mode) { c->err = "mk_set_fastq: clean mode is on (MerCat2 does not run removeN on converted FASTQ)"; return MK_ERR_ARG; }
+  if (c->in_chunk) { c->err = "mk_set_fastq: a chunk is open"; return MK_ERR_STATE; }
+  MK_HIP(hipSetDevice(c->device));
+  if (on && !c->fastq_stats.p) {
+    int rc = mk_fastq_clear(c);
+    if (rc) return rc;
+  }
+  c->fastq_mode = on ? 1 : 0;
+  return MK_OK;
+}
+
+extern "C" int mk_fastq_stats(mk_ctx* c, mk_fastq_stats_t* out) {
+  if (!c || !out) return MK_ERR_ARG;
+  u64 w[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lines | kept headers | dropped headers | kept bytes | '\r\n' pairs (mk_fastq.hip)
+  if (c->fastq_stats.p) {
+    MK_HIP(hipSetDevice(c->device));
+    MK_HIP(hipMemcpyAsync(w, c->fastq_stats.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+  }
+  out->lines = w[0];
+  out->reads = w[1];
+  out->headers_dropped = w[2];
+  out->fasta_bytes = w[3] - w[4];
+  out->crlf = w[4];
   return MK_OK;
 }
 
@@ -712,6 +747,11 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
     MK_HIP(hipSetDevice(c->device));
     if ((rc = mk_launch_clean_pre(c, (uint8_t*)c->raw.p, n)) != MK_OK) return rc;
   }
+  if (c->fastq_mode) {  // (in place, before the parser: everything after it -- the speculative lane included -- reads FASTA)
+    if (d_raw != (const uint8_t*)c->raw.p) { c->err = "FASTQ mode rewrites the text in place: feed it (mk_chunk_feed), do not pass caller memory"; return MK_ERR_STATE; }
+    MK_HIP(hipSetDevice(c->device));
+    if ((rc = mk_launch_fastq_pre(c, (uint8_t*)c->raw.p, n)) != MK_OK) return rc;
+  }
   if (!c->clean_mode && c->use_speculation && c->use_fast_parse && c->alphabet == MK_ALPHABET_NT2 && n && n < 0xFE000000ull &&
       ((c->mode == MK_MODE_HASH64 && c->use_partition && c->use_superkmer && c->k >= c->sk_min_k && c->k <= 32) ||
        (c->mode == MK_MODE_HASH128 && c->use_superkmer2))) {
@@ -920,6 +960,7 @@ extern "C" int mk_count_device(mk_ctx* c, const uint8_t* d_text, size_t n, uint6
   if (!c) return MK_ERR_ARG;
   if (c->in_chunk) { c->err = "mk_count_device: a chunk is open"; return MK_ERR_STATE; }
   if (n && !d_text) { c->err = "mk_count_device: d_text is NULL"; return MK_ERR_ARG; }
+  if (c->fastq_mode) { c->err = "mk_count_device: FASTQ mode rewrites the text in place: feed it (mk_chunk_feed_device)"; return MK_ERR_STATE; }
   if (!c->clean_mode && (((uintptr_t)d_text & 15) == 0 || c->use_fast_parse)) return process_chunk(c, d_text, n, min_count);
   int rc = mk_chunk_begin(c);
   if (!rc) rc = mk_chunk_feed_device(c, d_text, n);

@@ -199,6 +199,11 @@ struct mk_ctx {
   unsigned long long clean_n_runs = 0, clean_n_bytes = 0, clean_gc = 0, clean_symbols = 0, clean_raw = 0, clean_headers = 0;
   unsigned long long clean_last_runs = 0;  // runs of the last chunk (listed in clean_runs up to its capacity)
 
+  // FASTQ mode (mk_fastq.hip): every chunk is raw FASTQ, counted as fq2fa leaves it
+  int fastq_mode = 0;
+  MkDevBuf fastq_stats;  // 8 words summed over the chunks since mk_reset (mk_fastq.hip)
+  MkDevBuf fastq_tiles;  // per 4 KiB tile: entering line number and class | summary
+
   // multi-GPU merge staging (mk_multi.hip): rows grouped by owner going out, rows received from the peers,
   // owner bounds + histogram + cursors
   MkDevBuf xfer_out, xfer_in, xfer_meta;
@@ -307,6 +312,9 @@ int mk_launch_import_rows(mk_ctx* c, const uint64_t* d_rows, size_t rows);
 // mk_clean.hip
 int mk_launch_clean_pre(mk_ctx* c, uint8_t* d_raw, size_t n);
 int mk_launch_clean_post(mk_ctx* c, size_t seq_cap);
+// mk_fastq.hip
+int mk_fastq_clear(mk_ctx* c);
+int mk_launch_fastq_pre(mk_ctx* c, uint8_t* d_raw, size_t n);
 
 void mk_prof_begin(mk_ctx* c, int id);
 void mk_prof_end(mk_ctx* c);

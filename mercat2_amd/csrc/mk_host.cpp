@@ -606,6 +606,75 @@ extern "C" int mk_textwrap(const uint8_t* text, size_t n, size_t width, uint8_t*
   return MK_OK;
 }
 
+// fq2fa: a memchr walk over the lines (sed's, split on '\n' only), the kept ones copied whole; the universal-newline
+// translation only runs over lines that hold a '\r', and the non-ASCII check only when the converted text holds a byte
+// >= 0x80 (both are found with one memchr / one word-wise pass first)
+extern "C" int mk_fq2fa(const uint8_t* text, size_t n, uint8_t** out, size_t* out_len, mk_fastq_stats_t* st) {
+  if (!out || !out_len || !st || (n && !text)) return MK_ERR_ARG;
+  *out = nullptr;
+  *out_len = 0;
+  memset(st, 0, sizeof *st);
+  uint8_t* o = (uint8_t*)malloc(n ? n : 1);  // (the converted text is never longer than the FASTQ text)
+  if (!o) return MK_ERR_NOMEM;
+  const bool any_cr = n && memchr(text, '\r', n) != nullptr;
+  size_t w = 0, a = 0;
+  uint64_t line = 0;
+  while (a < n) {
+    const uint8_t* q = (const uint8_t*)memchr(text + a, '\n', n - a);
+    const size_t e = q ? (size_t)(q - text) + 1 : n;  // the line with its '\n'
+    const unsigned ph = (unsigned)(line++ & 3);
+    size_t from = a;
+    if (ph == 0) {
+      if (text[a] != '@') {
+        st->headers_dropped += 1;
+        a = e;
+        continue;
+      }
+      st->reads += 1;
+      o[w++] = '>';
+      from = a + 1;
+    } else if (ph != 1) {
+      a = e;
+      continue;
+    }
+    if (any_cr && memchr(text + from, '\r', e - from)) {
+      for (size_t i = from; i < e; ++i) {
+        if (text[i] == '\r' && i + 1 < e && text[i + 1] == '\n') { st->crlf += 1; continue; }
+        o[w++] = text[i] == '\r' ? (uint8_t)'\n' : text[i];
+      }
+    } else {
+      memcpy(o + w, text + from, e - from);
+      w += e - from;
+    }
+    a = e;
+  }
+  st->lines = line;
+  st->fasta_bytes = w;
+  uint64_t hi = 0;  // any byte >= 0x80?
+  size_t i = 0;
+  for (; i + 8 <= w; i += 8) {
+    uint64_t v;
+    memcpy(&v, o + i, 8);
+    hi |= v;
+  }
+  for (; i < w; ++i) hi |= o[i];
+  if (hi & 0x8080808080808080ull) {
+    LineReader rd(o, w);
+    size_t la = 0, lb = 0;
+    while (rd.next(la, lb)) {
+      if (la < lb && o[la] == '>') continue;
+      for (size_t j = la; j < lb; ++j)
+        if (o[j] >= 0x80) {  // non-ASCII sequence text: refused here as the counting engine refuses it
+          free(o);
+          return MK_ERR_NON_ASCII;
+        }
+    }
+  }
+  *out = o;
+  *out_len = w;
+  return MK_OK;
+}
+
 extern "C" void mk_free(void* p) { free(p); }
 
 // ---- planning helpers of the multi-GPU path (no GPU needed) -------------------------------------------------

@@ -382,6 +382,7 @@ extern "C" int mk_count_file(mk_ctx* const* ctxs, int nctx, const char* path, ui
   for (int j = 0; j < nctx; ++j) {
     if (!ctxs[j]) { c0->err = "mk_count_file: a context is NULL"; return MK_ERR_ARG; }
     if (ctxs[j]->in_chunk) { c0->err = "mk_count_file: a chunk is open"; return MK_ERR_STATE; }
+    if (ctxs[j]->fastq_mode) { c0->err = "mk_count_file: FASTQ mode is on (the file's chunks would be cut as FASTA)"; return MK_ERR_STATE; }
     if (ctxs[j]->alphabet != c0->alphabet || ctxs[j]->k != c0->k || ctxs[j]->canonical != c0->canonical) {
       c0->err = "mk_count_file: contexts differ in alphabet, k or canonical mode";
       return MK_ERR_ARG;

@@ -1,11 +1,15 @@
 """Drop-in for the part of MerCat2's ``mercat2_fasta`` module that stands in front of the counting path:
-``removeN`` (lib/mercat2_fasta.py:53-119) with its helper ``split_sequenceN`` (:21-49).
+``removeN`` (lib/mercat2_fasta.py:53-119) with its helper ``split_sequenceN`` (:21-49), and ``fq2fa`` (:175-198).
 
 The reference runs removeN on every nucleotide FASTA before counting (bin/mercat2.py:239-244, 276) unless
 ``-skipclean`` is given: sequences are cut at runs of 'N' into ``>{name}_{i} {info}`` records re-wrapped at 80
 columns, and the result is written as ``<outpath>/<base>_clean.fna.gz``.  Here the rewrite is native host code
 behind the C ABI (``mk_remove_n``, csrc/mk_host.cpp); the cleaned text can be handed to the counting engine
 straight from memory (``clean_text``) instead of being read back from the ``.gz``.
+
+FASTQ input is converted by ``fq2fa`` -- ``sed -n '1~4s/^@/>/p;2~4p'`` read back in universal-newline text mode --
+into ``<outpath>/<f_name>.fna.gz``, which then is the sample (its size decides about chunking).  The conversion is
+native host code too (``mk_fq2fa``); the GPU counts raw FASTQ the same way (``native.Counter.set_fastq``).
 """
 from __future__ import annotations
 
@@ -116,10 +120,16 @@ def removeN_background(fasta: Path, raw, outpath: Path, toupper: bool, writers, 
     called ``holder["drop"]()`` (it did not need them: no reason to keep a second copy of the sample in memory).
     ``holder["ready"]`` is set when the rewrite is done (the text is there, or the job has failed); ``holder["decision"]``
     is the GzDecision of the file against ``limit`` bytes (0: no limit: "not chunked" once the file is complete)."""
-    import threading
     os.makedirs(outpath, exist_ok=True)
     basename = Path(fasta).stem.split(".")[0]
     out_fasta = Path(outpath, f"{basename}_clean.fna.gz")
+    return _convert_background(out_fasta, lambda: clean_text(raw, toupper), "clean_s", writers, timings, limit)
+
+
+def _convert_background(out_fasta: Path, convert, key: str, writers, timings: Optional[dict], limit: int):
+    """``convert()`` -> (text, stats), then the text written to ``out_fasta`` (_write_clean_gz), on ``writers``:
+    the job of removeN_background and fq2fa_background (the time of ``convert`` goes to ``timings[key]``)."""
+    import threading
     lock = threading.Lock()
     holder = {"dropped": False, "ready": threading.Event(), "decision": GzDecision(limit)}
 
@@ -133,13 +143,13 @@ def removeN_background(fasta: Path, raw, outpath: Path, toupper: bool, writers, 
         import timeit
         t0 = timeit.default_timer()
         try:
-            cleaned, stats = clean_text(raw, toupper)
+            cleaned, stats = convert()
         except BaseException:
             holder["ready"].set()
             holder["decision"]._failed()
             raise
         if timings is not None:
-            timings["clean_s"] = timeit.default_timer() - t0
+            timings[key] = timeit.default_timer() - t0
         with lock:
             if not holder["dropped"]:
                 holder["text"] = cleaned
@@ -193,3 +203,35 @@ def removeN(fasta: Path, outpath: Path, toupper: bool):
     the sample is chunked, bin/mercat2.py:101 -- is the same."""
     path, stats, _ = removeN_text(fasta, outpath, toupper)
     return path, stats
+
+
+def fq2fa_text(raw) -> Tuple[bytes, dict]:
+    """fq2fa on FASTQ bytes already in memory (decompressed): (the text MerCat2 writes into ``<f_name>.fna.gz``, the
+    conversion's figures).  Lines are split on '\n' only and numbered across the text: line 4i+1 is kept with its '@'
+    made a '>' when it starts with '@' (dropped otherwise), line 4i+2 is kept, the others are dropped, and '\r\n' and
+    a lone '\r' become '\n'.  A byte >= 0x80 in a kept line that is not a header line raises native.NonAsciiInput
+    (the reference raises UnicodeDecodeError only for invalid UTF-8; the counting engine refuses any such byte)."""
+    return native.fq2fa(raw)
+
+
+def fq2fa_background(fq_file: Path, raw, outpath: Path, f_name: str, writers, timings: Optional[dict] = None, limit: int = 0):
+    """fq2fa -- conversion and ``<outpath>/<f_name>.fna.gz`` -- on the executor ``writers`` from the file's bytes ``raw``
+    already in memory, as removeN_background does it for removeN: returns ``(path, future, holder)``, ``future.result()``
+    is ``(size of the finished .gz, stats)``, the converted text is left in ``holder["text"]`` unless
+    ``holder["drop"]()`` was called, ``holder["ready"]`` and ``holder["decision"]`` (a GzDecision against ``limit``)."""
+    os.makedirs(outpath, exist_ok=True)
+    out_fasta = Path(outpath, f"{f_name}.fna.gz")
+    return _convert_background(out_fasta, lambda: fq2fa_text(raw), "fq2fa_s", writers, timings, limit)
+
+
+def fq2fa(fq_file, outpath, f_name: str) -> str:
+    """Converts a FASTQ file (plain, or gzip iff the name ends in '.gz') to ``<outpath>/<f_name>.fna.gz``
+    (lib/mercat2_fasta.py:175-198: same arguments, same result -- the absolute path of that file --, same file content,
+    written at level 9 by the same text-mode writer, so that its size, which decides whether the sample is chunked,
+    is the same)."""
+    os.makedirs(outpath, exist_ok=True)
+    out_fasta = Path(outpath, f"{f_name}.fna.gz")
+    raw = gzip.open(fq_file, "rb").read() if os.fspath(fq_file).endswith(".gz") else Path(fq_file).read_bytes()
+    text, _ = fq2fa_text(raw)
+    _write_clean_gz(out_fasta, text)
+    return os.path.abspath(out_fasta)

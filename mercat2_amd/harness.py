@@ -259,6 +259,64 @@ def run_raw_clean(basename: str, raw, out_file, kmer: int, min_count: int, toupp
             _give_back(ctx, key, size)
 
 
+# the largest raw FASTQ text run_raw_fastq counts as one chunk (the speculative lane of the parser and the 32-bit record
+# indices of the partition stop below 4 GiB)
+FASTQ_CHUNK_MAX = 0xF0000000
+
+
+def run_raw_fastq(basename: str, raw, out_file, kmer: int, min_count: int, limit_bytes: int = 0,
+                  *, device: int = 0, canonical: bool = False, report=print, keep: Optional[dict] = None,
+                  timings: Optional[dict] = None) -> Optional[Tuple[str, Optional[os.PathLike]]]:
+    """The table of a FASTQ sample straight from its RAW text (decompressed), counted as MerCat2 counts the
+    ``<base>.fna.gz`` its fq2fa writes (mk_set_fastq: the text is rewritten in place on the GPU before the parser) --
+    without waiting for the host's conversion and the gzip of that file.  Only for a sample that is ONE chunk:
+    ``limit_bytes`` (the -s size, 0 = never chunked) is compared with the converted text's size, which the GPU counts,
+    plus the most a level-9 DEFLATE stream can add to it.  Returns None -- nothing counted, nothing written -- when the
+    sample may be chunked; the caller then counts the text fq2fa produced."""
+    import timeit
+    mv = memoryview(raw)
+    # (the converted text is about half the FASTQ text: far beyond the limit it cannot be one chunk)
+    if (limit_bytes and len(mv) >= 4 * limit_bytes) or len(mv) > FASTQ_CHUNK_MAX:
+        return None
+    canon = bool(canonical)
+    key = (kmer, native.ALPHABET_NT2, device, canon)
+    ctx = _take_context(*key)
+    size = 1 << 62
+    t0 = timeit.default_timer()
+    try:
+        ctx.set_fastq(True)
+        ctx.count_chunk(mv, min_count)
+        st = ctx.fastq_stats()
+        fb = st["fasta_bytes"]
+        # the .gz cannot be larger than the text plus the stored-block overhead zlib falls back to
+        if limit_bytes and fb + fb // 1000 + 4096 >= limit_bytes:
+            ctx.reset()
+            size = len(mv)
+            return None
+        t1 = timeit.default_timer()
+        result = _finish(ctx, basename, out_file, report)
+        size = len(mv)
+        if timings is not None:
+            timings.update(count_s=t1 - t0, tsv_s=timeit.default_timer() - t1, chunks=1, contexts=1, devices=1, gpu_fastq=1,
+                           reads=st["reads"], fasta_bytes=fb)
+        if keep is not None and result[1] is not None:
+            ctx.set_fastq(False)
+            ctx.trim()
+            keep[basename] = ctx
+            ctx = None
+        return result
+    except BaseException:
+        size = 1 << 62
+        raise
+    finally:
+        if ctx is not None:
+            try:
+                ctx.set_fastq(False)  # (a pooled context must not count the next sample as FASTQ)
+            except native.MercatHipError:
+                size = 1 << 62
+            _give_back(ctx, key, size)
+
+
 # a file that is ONE filter unit is only spread over several GPUs from this size on (mk_count_file: MK_SPLIT_MIN)
 SPLIT_MIN_BYTES = 64 << 20
 

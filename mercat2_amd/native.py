@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "mk_owner_bounds", "mk_plan_contexts", "mk_bucket_rows_device", "mk_import_rows_device", "mk_merge_devices",
     "mk_export_size_multi", "mk_export_multi", "mk_write_tsv_multi", "mk_record_cuts", "mk_sample_keys", "mk_dense_bins_device",
     "mk_device_count", "mk_reset_for", "mk_textwrap", "mk_set_clean", "mk_clean_stats", "mk_clean_runs",
-    "mk_export_stats", "mk_share_table",
+    "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa",
 ]
 MK_ABI = 4  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -91,6 +91,11 @@ class CleanGpu(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("raw_bytes", "symbols", "gc_count", "n_bytes", "n_runs", "header_lines", "last_runs")]
 
 
+class FastqStats(C.Structure):
+    """mk_fastq_stats_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "reads", "headers_dropped", "fasta_bytes", "crlf")]
+
+
 class MergeStats(C.Structure):
     """mk_merge_stats_t (include/mercat_hip.h)."""
     _fields_ = ([(n, C.c_uint64) for n in ("rows_in", "rows_out", "rows_moved", "bytes_moved", "max_owned")] +
@@ -141,6 +146,9 @@ def lib() -> C.CDLL:
         "mk_set_clean": (C.c_int, [vp, C.c_int, C.c_int]),
         "mk_clean_stats": (C.c_int, [vp, C.POINTER(CleanGpu)]),
         "mk_clean_runs": (C.c_int, [vp, u64p, u64p, C.c_size_t, szp]),
+        "mk_set_fastq": (C.c_int, [vp, C.c_int]),
+        "mk_fastq_stats": (C.c_int, [vp, C.POINTER(FastqStats)]),
+        "mk_fq2fa": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_void_p), szp, C.POINTER(FastqStats)]),
         "mk_chunk_begin": (C.c_int, [vp]),
         "mk_chunk_feed": (C.c_int, [vp, u8p, C.c_size_t]),
         "mk_chunk_feed_device": (C.c_int, [vp, u8p, C.c_size_t]),
@@ -262,6 +270,25 @@ def remove_n(text, toupper: bool = False) -> Tuple[bytes, dict]:
         raise MercatHipError(rc, "mk_remove_n")
     try:
         data = C.string_at(out, out_len.value) if out.value else b""
+    finally:
+        if out.value:
+            L.mk_free(out)
+    return data, {n_: int(getattr(st, n_)) for n_, _ in st._fields_}
+
+
+def fq2fa(raw) -> Tuple[bytes, dict]:
+    """mk_fq2fa: (the text MerCat2's fq2fa writes into <base>.fna.gz, uncompressed; mk_fastq_stats_t fields) of a whole
+    FASTQ text.  NonAsciiInput for a byte >= 0x80 in a line of the converted text that is not a header line."""
+    L = lib()
+    addr, n, keep = _buf_ptr(raw)
+    out, out_len, st = C.c_void_p(), C.c_size_t(0), FastqStats()
+    rc = L.mk_fq2fa(addr, n, C.byref(out), C.byref(out_len), C.byref(st))
+    if rc == -5:
+        raise NonAsciiInput(rc, "the converted FASTQ text holds sequence byte(s) >= 0x80 (non-ASCII sequence text is not supported)")
+    if rc:
+        raise MercatHipError(rc, "mk_fq2fa")
+    try:
+        data = C.string_at(out, out_len.value) if out_len.value else b""
     finally:
         if out.value:
             L.mk_free(out)
@@ -548,6 +575,17 @@ class Counter:
         if n.value:
             self._check(self._L.mk_clean_runs(self._h, a.ctypes.data, b.ctypes.data, n.value, C.byref(n)))
         return a, b
+
+    def set_fastq(self, on: bool):
+        """Count every chunk fed from now on as raw FASTQ, as MerCat2's fq2fa leaves it (mk_set_fastq): one file per
+        chunk, rewritten in place on the GPU before the parser.  Nucleotide alphabet; not with clean mode."""
+        self._check(self._L.mk_set_fastq(self._h, 1 if on else 0))
+
+    def fastq_stats(self) -> dict:
+        """mk_fastq_stats_t fields summed over the chunks counted in FASTQ mode since the last reset."""
+        st = FastqStats()
+        self._check(self._L.mk_fastq_stats(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
 
     def reset(self, expect_rows: int = 0):
         """Forget the running table; with ``expect_rows`` also size it for about that many keys if that is less than
