@@ -175,15 +175,9 @@ extern "C" int mk_create(int device, int alphabet, int k, mk_ctx** out) {
   const long kb = (long)k * c->bits;
   c->mode = (c->bits == 0) ? MK_MODE_BYREF : (kb <= 15 ? MK_MODE_DENSE : (kb <= 64 ? MK_MODE_HASH64 : MK_MODE_BYREF));
   if (alphabet == MK_ALPHABET_NT2 && k >= 33 && k <= 64) c->mode = MK_MODE_HASH128;  // packed by-reference
-  // amino acids, 13 <= k <= 25: 5 k <= 125 bits, the same two-word tables (mk_count_ref128aa_k); MK_NO_AA128 = by bytes, as before round 3
-  if (alphabet == MK_ALPHABET_AA5 && k >= 13 && k <= 25 && !getenv("MK_NO_AA128")) c->mode = MK_MODE_HASH128;
+  // amino acids, 13 <= k <= 25: 5 k <= 125 bits, the same two-word tables (mk_count_ref128aa_k)
+  if (alphabet == MK_ALPHABET_AA5 && k >= 13 && k <= 25) c->mode = MK_MODE_HASH128;
   c->st.mode = c->mode;
-  c->use_partition = getenv("MK_NO_PARTITION") ? 0 : 1;
-  c->use_fast_parse = getenv("MK_NO_FAST_PARSE") ? 0 : 1;
-  c->use_superkmer = getenv("MK_NO_SUPERKMER") ? 0 : 1;
-  c->use_superkmer2 = getenv("MK_NO_SUPERKMER2") ? 0 : 1;
-  c->run_bucket_major = (getenv("MK_BUCKET_MAJOR") && alphabet == MK_ALPHABET_NT2 && c->mode == MK_MODE_HASH64 && k >= 12 && k <= 32) ? 1 : 0;
-  if (const char* e = getenv("MK_SK_MIN_K")) { const int v = atoi(e); if (v >= 12 && v <= 33) c->sk_min_k = v; }
   int rc = MK_OK;
   auto fail = [&](int code, const std::string& msg) {
     g_err = msg;
@@ -193,9 +187,6 @@ extern "C" int mk_create(int device, int alphabet, int k, mk_ctx** out) {
   if ((e = hipSetDevice(device)) != hipSuccess) return fail(MK_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
     return fail(MK_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  c->use_speculation = getenv("MK_NO_SPECULATION") ? 0 : 1;
-  c->use_reuse = getenv("MK_NO_REUSE") ? 0 : 1;
-  c->use_fused = getenv("MK_NO_FUSE") ? 0 : 1;
   // What a new context assumes about its first chunk (later chunks go by the chunk before): two windows per distinct key,
   // five per record.  The count kernels plan their sub-range passes from it; a bucket that does not fit is split anyway.
   // (1 and 8 -- every window a new key, full records -- made the first chunk of a read set take eight passes per bucket,
@@ -293,7 +284,7 @@ extern "C" int mk_set_canonical(mk_ctx* c, int on) {
   if (!c) return MK_ERR_ARG;
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (on && c->alphabet != MK_ALPHABET_NT2) { c->err = "mk_set_canonical: only the nucleotide alphabet has a reverse complement"; return MK_ERR_ARG; }
-  if (on && c->mode != MK_MODE_DENSE && c->mode != MK_MODE_HASH64 && !(c->mode == MK_MODE_HASH128 && c->use_superkmer2)) {
+  if (on && c->mode != MK_MODE_DENSE && c->mode != MK_MODE_HASH64 && c->mode != MK_MODE_HASH128) {
     c->err = "mk_set_canonical: canonical counting is implemented for nucleotide k <= 64 (two-word keys: on the partitioned path only)";
     return MK_ERR_ARG;
   }
@@ -475,12 +466,9 @@ extern "C" int mk_chunk_feed_device(mk_ctx* c, const uint8_t* d_text, size_t n) 
 
 // ------------------------------------------------------------------------ running tables
 // Slots of a running table that has to take need_rows rows: the next power of two above 2.5 x (load 20-40 % after a
-// growth, 50 % before the next; MK_GROW_X4=1: above 4 x, as in rounds 1-2).  Compaction, table-to-table sums and
-// clears scan the slots, so a table twice as sparse costs every sample ~0.15 ms.
-static size_t run_slots_for(size_t need_rows) {
-  static const bool x4 = getenv("MK_GROW_X4") != nullptr;
-  return pow2_at_least(x4 ? 4 * need_rows : need_rows * 5 / 2);
-}
+// growth, 50 % before the next; rounds 1-2 took 4 x).  Compaction, table-to-table sums and clears scan the slots, so a
+// table twice as sparse costs every sample ~0.15 ms.
+static size_t run_slots_for(size_t need_rows) { return pow2_at_least(need_rows * 5 / 2); }
 
 static int grow_run64_body(mk_ctx* c, size_t need_rows);
 // (a table other contexts launch into -- mk_share_table -- is only replaced under its lock, with their streams drained)
@@ -575,8 +563,7 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   if ((rc = mk_buf_reserve(c, c->codes, (2 * bad_words + 8) * 8)) != MK_OK) return rc;
   // (the parsed stream itself is not written: only the by-reference kernel reads it, and that runs only when the chunk
   // holds characters outside the alphabet -- the chunk is then parsed once more with the stream, below)
-  static const bool always_seq = getenv("MK_ALWAYS_SEQ") != nullptr;
-  if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/true, /*write_seq=*/always_seq)) != MK_OK) return rc;
+  if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/true, /*write_seq=*/false)) != MK_OK) return rc;
   const bool two = c->mode == MK_MODE_HASH128;
   c->rtab_chunk_slots = 0;
   c->surv_regions = 0;
@@ -585,9 +572,8 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   // table itself -- no import kernel, no waiting for their number.  The table is sized HERE for what the chunk before
   // kept, twice over; the kernel spills what a table that fills up all the same cannot take, and that is imported below.
   c->fuse_cap = 0;
-  if (!two && c->use_fused && min_count >= 2 && c->surv_hint_ok && !c->run_bucket_major) {
-    static const bool cores = getenv("MK_CORES") != nullptr;  // (half-sized buckets: half the survivors per bucket, half the list)
-    const unsigned long long per_bucket = (c->surv_hint >> 13) * (cores ? 2 : 1);  // (8192 buckets on chunks of this size; smaller chunks: fewer of both)
+  if (!two && min_count >= 2 && c->surv_hint_ok && !mk_env_set("MK_NO_FUSE")) {
+    const unsigned long long per_bucket = c->surv_hint >> 13;  // (8192 buckets on chunks of this size; smaller chunks: fewer of both)
     const int cap = per_bucket <= 110 ? 512 : (per_bucket <= 360 ? 1024 : 0);
     if (cap) {
       if ((rc = settle(c)) != MK_OK) return rc;  // (run_rows must be what the table holds)
@@ -597,8 +583,7 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
       mk_ctx* t = table_of_ctx(c);
       // (what this chunk is expected to add: the last full chunk's survivors -- late in a sample most of them are keys
       // the table already holds; the spill list takes what a bad guess leaves no room for)
-      static const bool roomy = getenv("MK_FUSE_ROOMY") != nullptr;  // (A/B: twice the survivors, as first built)
-      const size_t expect = (roomy ? 2 * (size_t)c->surv_hint : (size_t)c->surv_hint) + 4096;
+      const size_t expect = (size_t)c->surv_hint + 4096;
       if (t != c) {
         std::shared_lock<std::shared_mutex> rd(t->table_mu);
         size_t rows_now;
@@ -634,15 +619,13 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   }
   const size_t seq_len = (size_t)h->seq_len;
   if (h->bad_symbols) {  // windows holding a symbol outside the alphabet: by reference, now
-    if (!always_seq) {
-      // the by-reference kernel reads the parsed stream, which the first parse did not write: parse again (the raw text
-      // is still there), this time for the stream only -- the packed words, the bitmap and the chunk's counters stand
-      // (the second parse adds to the chunk's counters again -- kept bytes >= 0x80 -- so they are set aside and put back)
-      if ((rc = mk_buf_reserve(c, c->ex_tmp, sizeof(MkChunkInfo) + 64)) != MK_OK) return rc;
-      MK_HIP(hipMemcpyAsync(c->ex_tmp.p, c->info.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
-      if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/false, /*write_seq=*/true)) != MK_OK) return rc;
-      MK_HIP(hipMemcpyAsync(c->info.p, c->ex_tmp.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
-    }
+    // the by-reference kernel reads the parsed stream, which the first parse did not write: parse again (the raw text
+    // is still there), this time for the stream only -- the packed words, the bitmap and the chunk's counters stand
+    // (the second parse adds to the chunk's counters again -- kept bytes >= 0x80 -- so they are set aside and put back)
+    if ((rc = mk_buf_reserve(c, c->ex_tmp, sizeof(MkChunkInfo) + 64)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(c->ex_tmp.p, c->info.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/false, /*write_seq=*/true)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(c->info.p, c->ex_tmp.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
     const u64 bound = std::min<u64>((u64)seq_len, h->bad_symbols * (u64)c->k);
     c->rtab_chunk_slots = pow2_at_least(2 * (size_t)bound);
     if ((rc = mk_buf_reserve(c, c->rtab_chunk, c->rtab_chunk_slots * sizeof(MkSlot))) != MK_OK) return rc;
@@ -653,7 +636,7 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   }
   if (h->part_overflow) {  // (see process_chunk: partition again from the exact histogram)
     if (!c->part_sampled) { c->err = "partition overflow without sampling (internal error)"; return MK_ERR_STATE; }
-    if (getenv("MK_VERBOSE")) fprintf(stderr, "[mk] sampled partition too small (where=%llu): exact pass\n", h->part_overflow);
+    if (mk_env_set("MK_VERBOSE")) fprintf(stderr, "[mk] sampled partition too small (where=%llu): exact pass\n", h->part_overflow);
     h->windows = h->records = h->distinct = h->survivors = h->side = h->errors = h->part_overflow = 0;
     MK_HIP(hipMemcpyAsync(c->info.p, h, sizeof(MkChunkInfo), hipMemcpyHostToDevice, c->stream));
     c->st.part_retries += 1;
@@ -719,7 +702,7 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   if (!two && (full_chunk || !c->surv_hint_ok)) { c->surv_hint = h->survivors; c->surv_hint_ok = true; }
   if (h->distinct && full_chunk) { c->dup_hint = (double)h->windows / (double)h->distinct; c->dup_known = true; }
   if (h->records) { c->nk_hint = (double)(h->windows + h->exotic) / (double)h->records; c->items_hint = (double)h->records * 32.0 / (double)(seq_len ? seq_len : 1); }
-  if (getenv("MK_VERBOSE"))
+  if (mk_env_set("MK_VERBOSE"))
     fprintf(stderr, "[mk] chunk (one read-back): raw=%zu seq=%zu windows=%llu records=%llu distinct=%llu survivors=%llu p1=2^%d dup=%.2f nk=%.2f fused=%d spilled=%llu rows=%zu slots=%zu\n",
             n, seq_len, (unsigned long long)h->windows, (unsigned long long)h->records, (unsigned long long)h->distinct,
             (unsigned long long)h->survivors, c->p1_log2, c->dup_hint, c->nk_hint, fused_done ? 1 : 0, (unsigned long long)h->spilled,
@@ -742,7 +725,6 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
   int rc;
   bool known_blank = false;
   if (c->clean_mode) {  // (one read-back more than the speculative lane: the chunk must be known to be reproducible BEFORE it is merged)
-    if (!c->use_fast_parse) { c->err = "clean mode needs the fast parser (MK_NO_FAST_PARSE is set)"; return MK_ERR_UNSUPPORTED; }
     if (d_raw != (const uint8_t*)c->raw.p) { c->err = "clean mode rewrites the text in place: feed it (mk_chunk_feed), do not pass caller memory"; return MK_ERR_STATE; }
     MK_HIP(hipSetDevice(c->device));
     if ((rc = mk_launch_clean_pre(c, (uint8_t*)c->raw.p, n)) != MK_OK) return rc;
@@ -752,9 +734,8 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
     MK_HIP(hipSetDevice(c->device));
     if ((rc = mk_launch_fastq_pre(c, (uint8_t*)c->raw.p, n)) != MK_OK) return rc;
   }
-  if (!c->clean_mode && c->use_speculation && c->use_fast_parse && c->alphabet == MK_ALPHABET_NT2 && n && n < 0xFE000000ull &&
-      ((c->mode == MK_MODE_HASH64 && c->use_partition && c->use_superkmer && c->k >= c->sk_min_k && c->k <= 32) ||
-       (c->mode == MK_MODE_HASH128 && c->use_superkmer2))) {
+  if (!c->clean_mode && c->alphabet == MK_ALPHABET_NT2 && n && n < 0xFE000000ull &&
+      ((c->mode == MK_MODE_HASH64 && c->k >= MK_SK_MIN_K && c->k <= 32) || c->mode == MK_MODE_HASH128)) {
     rc = process_chunk_fast(c, d_raw, n, min_count);
     if (rc != MK_RETRY_GENERAL) return rc;
     known_blank = true;  // (the fast parser has just said so: straight to the general one)
@@ -773,7 +754,7 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
     if ((rc = mk_buf_reserve(c, c->codes, (code_words + 8) * 8)) != MK_OK) return rc;
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
-    const bool fast = c->use_fast_parse && attempt == 0 && !known_blank;
+    const bool fast = attempt == 0 && !known_blank;
     const bool fused = fast && packed && c->alphabet == MK_ALPHABET_NT2;  // the nt pack rides on the parser's LDS image
     if (!fast && begin) {  // aligned copy for the general transducer
       if ((rc = mk_buf_reserve(c, c->raw, n + 64)) != MK_OK) return rc;
@@ -820,16 +801,11 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
 
   // chunk tables
   c->rtab_chunk_slots = 0;
-  const bool partitioned = c->mode == MK_MODE_HASH64 && c->use_partition;
+  const bool partitioned = c->mode == MK_MODE_HASH64;
   c->surv_regions = 0;
   c->ctab_slots = c->mode == MK_MODE_DENSE ? c->ctab_slots : 0;
-  if (c->mode == MK_MODE_HASH64 && !partitioned) {
-    c->ctab_slots = pow2_at_least(2 * seq_len);
-    if ((rc = mk_buf_reserve(c, c->ctab, c->ctab_slots * sizeof(MkSlot))) != MK_OK) return rc;
-    if ((rc = mk_launch_clear_slots(c, (MkSlot*)c->ctab.p, c->ctab_slots)) != MK_OK) return rc;
-  }
   // partitioned path: no global chunk table (32-bit record indices in the scatter's LDS: chunks below 4 G symbols)
-  const bool sk2 = c->mode == MK_MODE_HASH128 && c->alphabet == MK_ALPHABET_NT2 && c->use_superkmer2 && seq_len < 0xFFFFFF00ull;
+  const bool sk2 = c->mode == MK_MODE_HASH128 && c->alphabet == MK_ALPHABET_NT2 && seq_len < 0xFFFFFF00ull;
   if (c->mode == MK_MODE_HASH128 && c->canonical && !sk2) {
     c->err = "canonical counting of 33..64-mers needs the partitioned path (chunk of 4 G symbols or more)";
     return MK_ERR_RANGE;
@@ -850,13 +826,12 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
   if (c->mode == MK_MODE_DENSE) rc = mk_launch_count_dense(c, seq_len);
   else if (partitioned) {
     // (the super-k-mer scatter keeps 32-bit record indices in LDS)
-    const bool sk = c->use_superkmer && c->alphabet == MK_ALPHABET_NT2 && c->k >= c->sk_min_k && c->k <= 32 && seq_len < 0xFE000000ull;
+    const bool sk = c->alphabet == MK_ALPHABET_NT2 && c->k >= MK_SK_MIN_K && c->k <= 32 && seq_len < 0xFE000000ull;
     // (keys of 16..26 bits -- nucleotide 8 <= k <= 11, protein k = 4, 5 -- are counted by direct index: mk_bin.hip)
     const bool binned = !sk && mk_binned_takes(c) && seq_len < 0xFFFFFF00ull;
     rc = sk ? mk_launch_count_superkmer(c, seq_len, min_count)
             : (binned ? mk_launch_count_binned(c, seq_len, min_count) : mk_launch_count_partitioned(c, seq_len, min_count));
   }
-  else if (c->mode == MK_MODE_HASH64) rc = mk_launch_count_hash64(c, seq_len);
   else if (c->mode == MK_MODE_HASH128) rc = sk2 ? mk_launch_count_superkmer2(c, seq_len, min_count) : mk_launch_count_ref128(c, seq_len);
   if (rc) return rc;
   // by reference, byte-wise: every window (raw mode) or only those holding a symbol outside the alphabet
@@ -871,7 +846,7 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
     // short of writing past it; partition and count again from the exact histogram
     if (!c->part_sampled) { c->err = "partition overflow without sampling (internal error)"; return MK_ERR_STATE; }
     MkChunkInfo* h = c->h_info;
-    if (getenv("MK_VERBOSE")) fprintf(stderr, "[mk] sampled partition too small (where=%llu: 1 records total, 2 survivors total, 4 a bucket, 8 a survivor region): exact pass\n", h->part_overflow);
+    if (mk_env_set("MK_VERBOSE")) fprintf(stderr, "[mk] sampled partition too small (where=%llu: 1 records total, 2 survivors total, 4 a bucket, 8 a survivor region): exact pass\n", h->part_overflow);
     // (the fields the partitioned kernels own; what the by-reference kernel added for odd windows stays)
     h->windows = h->records = h->distinct = h->survivors = h->side = h->errors = h->part_overflow = 0;
     MK_HIP(hipMemcpyAsync(c->info.p, h, sizeof(MkChunkInfo), hipMemcpyHostToDevice, c->stream));
@@ -931,7 +906,7 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
     c->items_hint = (double)c->h_info->records * 32.0 / (double)(seq_len ? seq_len : 1);
   }
 
-  if (getenv("MK_VERBOSE"))
+  if (mk_env_set("MK_VERBOSE"))
     fprintf(stderr, "[mk] chunk: raw=%zu seq=%zu windows=%llu records=%llu distinct=%llu survivors=%llu new_rows=%llu p1=2^%d dup=%.2f nk=%.2f\n", n, seq_len,
             (unsigned long long)c->h_info->windows, (unsigned long long)c->h_info->records, (unsigned long long)c->h_info->distinct,
             (unsigned long long)c->h_info->survivors, (unsigned long long)c->h_info->new_rows, c->p1_log2, c->dup_hint, c->nk_hint);
@@ -961,7 +936,7 @@ extern "C" int mk_count_device(mk_ctx* c, const uint8_t* d_text, size_t n, uint6
   if (c->in_chunk) { c->err = "mk_count_device: a chunk is open"; return MK_ERR_STATE; }
   if (n && !d_text) { c->err = "mk_count_device: d_text is NULL"; return MK_ERR_ARG; }
   if (c->fastq_mode) { c->err = "mk_count_device: FASTQ mode rewrites the text in place: feed it (mk_chunk_feed_device)"; return MK_ERR_STATE; }
-  if (!c->clean_mode && (((uintptr_t)d_text & 15) == 0 || c->use_fast_parse)) return process_chunk(c, d_text, n, min_count);
+  if (!c->clean_mode) return process_chunk(c, d_text, n, min_count);
   int rc = mk_chunk_begin(c);
   if (!rc) rc = mk_chunk_feed_device(c, d_text, n);
   if (rc) { c->in_chunk = false; return rc; }
@@ -1348,8 +1323,7 @@ static int write_tsv_from_device(mk_ctx* c, const char* path, const char* basena
 extern "C" int mk_write_tsv(mk_ctx* c, const char* path, const char* basename, size_t* rows_out) {
   if (!c || !path || !basename) return MK_ERR_ARG;
   { int rc_ = settle(c); if (rc_) return rc_; }
-  static const bool host_only = getenv("MK_TSV_HOST") != nullptr;  // (A/B and tests: the host formatter for every table)
-  if (!host_only && c->mode != MK_MODE_BYREF && c->run_ref_rows == 0 && c->bits != 0)
+  if (c->mode != MK_MODE_BYREF && c->run_ref_rows == 0 && c->bits != 0)
     return write_tsv_from_device(c, path, basename, rows_out);
   ExportView v;
   int rc = build_view(c, v);

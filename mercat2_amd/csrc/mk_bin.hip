@@ -251,9 +251,8 @@ __global__ __launch_bounds__(BINC_THREADS) void mk_bin_count_k(const unsigned sh
 
 // key bits this path takes (the caller checks the alphabet and that no longer path is faster)
 bool mk_binned_takes(const mk_ctx* c) {
-  static const bool off = getenv("MK_NO_BINNED") != nullptr;
   const int kb = c->bits * c->k;
-  return !off && c->mode == MK_MODE_HASH64 && kb >= 16 && kb <= 26;
+  return c->mode == MK_MODE_HASH64 && kb >= 16 && kb <= 26;
 }
 
 int mk_launch_count_binned(mk_ctx* c, size_t seq_len, uint64_t min_count) {

@@ -8,6 +8,7 @@
 #include <shared_mutex>
 #include <vector>
 #include "../../include/mercat_hip.h"
+#include "mk_env.h"
 
 // ------------------------------------------------------------------------------------------
 // Device data layout (all in HBM, owned by the context)
@@ -26,10 +27,8 @@
 
 // Smallest nucleotide k that takes the super-k-mer partition (mk_skmer.hip): k - 10 minimizer candidates per window.
 // Round 3: 12 (measured on an S2 chunk, Gbases/s against the 8-byte-key partition: k = 12 50 / 42, 14 74 / 47, 16 90 / 46,
-// 17 96 / 21); the environment variable MK_SK_MIN_K (tests / A-B runs) may raise it back to 18, the round-2 threshold.
-#ifndef MK_SK_MIN_K
+// 17 96 / 21; round 2 started at 18).
 #define MK_SK_MIN_K 12
-#endif
 #define MK_SEP 0x0Au
 #define MK_EMPTY 0xFFFFFFFFFFFFFFFFull
 
@@ -125,7 +124,6 @@ struct mk_ctx {
   MkChunkInfo* h_info = nullptr;  // pinned host copy (two structs: [1] receives the read-back that is not waited for)
   bool pending_rows = false;      // h_info[1] holds (or will hold, once the stream has passed the copy) the row totals
                                   // of the last chunk's merge, not yet added to run_rows / run128_rows / run_ref_rows
-  int use_speculation = 1;        // one read-back per chunk on the partitioned paths (mk_api.hip: process_chunk_fast)
 
   // chunk tables
   MkDevBuf ctab;        // MkSlot[] (hash64) / MkSlot128[] (hash128) / u64 bins (dense)
@@ -152,16 +150,10 @@ struct mk_ctx {
   MkDevBuf part_meta;   // u64 hist[P1] | start[P1+1] | cursor[P1]
   MkDevBuf surv_keys, surv_cnts;  // (key,count) survivors of the chunk
   MkDevBuf surv_keys2;            // second key word of the survivors (33..64-mers)
-  int use_superkmer2 = 1;
   int p1_log2 = 10;
   double dup_hint = 1.0;  // windows per distinct key seen in the previous chunk
   bool dup_known = false; // ... of THIS sample (mk_reset forgets it)
-  int use_partition = 1;
-  int use_fast_parse = 1;
   int canonical = 0;      // opt-in: count min(kmer, revcomp) (nt only)
-  int use_superkmer = 1;
-  int run_bucket_major = 0;  // one-word running table addressed bucket-major (mk_table.hip: RunAddr; experiment, MK_BUCKET_MAJOR=1)
-  int sk_min_k = MK_SK_MIN_K;  // nucleotide k from which the super-k-mer partition is used (below: 8-byte-key partition)
   bool part_sampled = false;  // the last super-k-mer partition sized its buckets from a sample
   // bucket regions of the previous chunk kept for the next one (mk_skmer.hip): same size, same min_count, no overflow
   bool part_reuse_ok = false;
@@ -171,12 +163,10 @@ struct mk_ctx {
   int part_nseg = 1;            // regions per bucket of the last one-word partition (1, or 8: one per XCD)
   unsigned long long part_prev_minc = 0;
   int part_cooldown = 0;      // chunks that size their buckets afresh after a chunk overflowed inherited regions
-  int use_reuse = 1;
   int surv_regions = 0;   // survivors of the last chunk are laid out per bucket (kstart/nsurv in part_meta)
   double nk_hint = 8.0;   // windows per super-k-mer record seen in the previous chunk
   double items_hint = 0;  // records per analysis thread (32 positions) seen in the previous chunk; 0 = not known yet
   // fused upsert (mk_skcount.hip): the count kernel puts a chunk's survivors into the running table itself
-  int use_fused = 1;                  // MK_NO_FUSE=1 turns it off
   int fuse_cap = 0;                   // list entries per sweep the NEXT count launch may use (0: survivors go to their regions)
   bool fused_last = false;            // the last count launch was a fused one
   unsigned long long surv_hint = 0;   // survivors of the previous chunk of this sample
@@ -241,7 +231,6 @@ int mk_launch_fparse(mk_ctx* c, const uint8_t* d_raw, size_t begin, size_t len, 
 int mk_launch_pack(mk_ctx* c, size_t seq_cap);
 // counting
 int mk_launch_count_dense(mk_ctx* c, size_t seq_cap);
-int mk_launch_count_hash64(mk_ctx* c, size_t seq_cap);
 int mk_launch_count_byref(mk_ctx* c, size_t seq_cap, bool exotic_only);
 // nt 33..64-mers without bad symbols: by reference with packed hashing/compare (mode MK_MODE_HASH128)
 int mk_launch_count_ref128(mk_ctx* c, size_t seq_len);
@@ -257,10 +246,7 @@ void mk_launch_sk_scan(mk_ctx* c, const unsigned long long* hist, const unsigned
                        int nseg);  // nseg: regions per bucket (1, or 8: one per XCD, mk_skmer.hip)
 // mk_skcount.hip: the count kernel of the one-word super-k-mer path over the bucket regions the scatter filled
 int mk_launch_sk_count(mk_ctx* c, const unsigned long long* start, unsigned* cursor, const unsigned long long* kstart,
-                       unsigned long long* nsurv, uint64_t min_count, int nkmax, size_t p1, bool exact, int nseg);
-// mk_skcount_small.hip: the same with 512-thread workgroups and 4096-slot tables (experiment MK_CORES)
-int mk_launch_sk_count_small(mk_ctx* c, const unsigned long long* start, unsigned* cursor, const unsigned long long* kstart,
-                             unsigned long long* nsurv, uint64_t min_count, int nkmax, size_t p1, bool exact, int nseg);
+                       unsigned long long* nsurv, uint64_t min_count, size_t p1, int nseg);
 // nt 33 <= k <= 64, two-word keys: mk_skmer2.hip; survivors {hi,lo,count} per bucket region
 int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bool exact = false);
 int mk_launch_import_ref128_regions(mk_ctx* c, const uint64_t* hi, const uint64_t* lo, const uint64_t* cnts,

@@ -2,12 +2,11 @@
 //
 // Replaces the reference's inner loop (lib/mercat2_kmers.py:56-60, 65-69)
 //     for i in range(len(seq)-k+1): kmerlist[seq[i:i+k]] += 1
-// with three GPU forms that together count *every* window exactly:
+// with GPU forms that together count *every* window exactly (packed keys of 16..64 bits are counted by
+// the partitioned paths: mk_bin.hip, mk_part.hip, mk_skmer.hip):
 //   dense   k*BITS <= 15: direct-index histogram, private to the workgroup in LDS
 //           (replicated per lane group when the bin count is small), one global add per
 //           non-zero bin per workgroup;
-//   hash64  k*BITS <= 64: packed key, open-addressed table of 16-byte {key,count} slots in
-//           HBM, linear probing, claim by atomicCAS, count by no-return atomicAdd;
 //   byref   any k, any character: the table stores the *position* of the first occurrence
 //           (plus a hash tag); equality is a k-byte compare in the parsed stream. It takes
 //           (a) every window when there is no packed form for (alphabet,k) and (b) in the
@@ -20,65 +19,6 @@
 __device__ __forceinline__ void add_windows(MkChunkInfo* info, unsigned mine, bool exotic) {
   for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(exotic ? &info->exotic : &info->windows, (u64)mine);
-}
-
-// ------------------------------------------------------------------------------ hash64
-__device__ __forceinline__ void insert64(MkSlot* __restrict__ table, u64 mask, u64 key, u64 add) {
-  u64 slot = mk_mix64(key) & mask;
-  for (;;) {
-    u64 cur = table[slot].key;
-    if (cur == MK_EMPTY) {
-      cur = atomicCAS(&table[slot].key, MK_EMPTY, key);
-      if (cur == MK_EMPTY) cur = key;
-    }
-    if (cur == key) {
-      atomicAdd(&table[slot].cnt, add);
-      return;
-    }
-    slot = (slot + 1) & mask;
-  }
-}
-
-template <int BITS, int SPW, int WPT>
-__global__ __launch_bounds__(256) void mk_count_hash64_k(const u64* __restrict__ codes, const u64* __restrict__ bad,
-                                                         MkChunkInfo* __restrict__ info, MkSlot* __restrict__ table,
-                                                         u64 mask, int k, int canon) {
-  constexpr int R = SPW * WPT;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t p0 = t * R;
-  unsigned mine = 0;
-  if (p0 < info->seq_len) {
-    u64 w[WPT + 1];
-#pragma unroll
-    for (int i = 0; i <= WPT; ++i) w[i] = codes[t * WPT + i];
-    const u64 badw = bad_window(bad, p0);
-    const u64 kmask = (k >= 64) ? ~0ull : ((1ull << k) - 1);
-    if ((badw & ((R + k - 1 >= 64) ? ~0ull : ((1ull << (R + k - 1)) - 1))) == 0) {
-      // fast path: no bad symbol anywhere in this thread's span
-#pragma unroll
-      for (int i = 0; i < WPT; ++i) {
-#pragma unroll
-        for (int s = 0; s < SPW; ++s) {
-          u64 key = mk_canon2(window_key<BITS, SPW>(w[i], w[i + 1], s, k), k, BITS == 2 && canon);
-          if (key == MK_EMPTY) atomicAdd(&info->side, 1ull); else insert64(table, mask, key, 1);
-        }
-      }
-      mine = R;
-    } else {
-#pragma unroll
-      for (int i = 0; i < WPT; ++i) {
-#pragma unroll
-        for (int s = 0; s < SPW; ++s) {
-          if (((badw >> (i * SPW + s)) & kmask) == 0) {
-            u64 key = mk_canon2(window_key<BITS, SPW>(w[i], w[i + 1], s, k), k, BITS == 2 && canon);
-            if (key == MK_EMPTY) atomicAdd(&info->side, 1ull); else insert64(table, mask, key, 1);
-            ++mine;
-          }
-        }
-      }
-    }
-  }
-  add_windows(info, mine, false);
 }
 
 // ------------------------------------------------------------------------------- dense
@@ -386,25 +326,6 @@ int mk_launch_count_ref128(mk_ctx* c, size_t seq_len) {
 
 // ------------------------------------------------------------------------------ launchers
 static size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
-
-int mk_launch_count_hash64(mk_ctx* c, size_t seq_len) {
-  if (seq_len == 0) return MK_OK;
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  const u64 mask = c->ctab_slots - 1;
-  mk_prof_begin(c, MK_K_COUNT);
-  if (c->alphabet == MK_ALPHABET_NT2) {
-    const size_t threads = div_up(seq_len, 32);
-    hipLaunchKernelGGL((mk_count_hash64_k<2, 32, 1>), dim3((unsigned)div_up(threads, 256)), dim3(256), 0, c->stream,
-                       (const u64*)c->codes.p, (const u64*)c->bad.p, info, (MkSlot*)c->ctab.p, mask, c->k, c->canonical);
-  } else {
-    const size_t threads = div_up(seq_len, 36);
-    hipLaunchKernelGGL((mk_count_hash64_k<5, 12, 3>), dim3((unsigned)div_up(threads, 256)), dim3(256), 0, c->stream,
-                       (const u64*)c->codes.p, (const u64*)c->bad.p, info, (MkSlot*)c->ctab.p, mask, c->k, c->canonical);
-  }
-  mk_prof_end(c);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
 
 int mk_launch_count_dense(mk_ctx* c, size_t seq_len) {
   if (seq_len == 0) return MK_OK;

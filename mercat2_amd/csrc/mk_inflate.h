@@ -257,9 +257,6 @@ class MkInflateT {
   // Where two literal codes fit into one primary index, let the entry deliver both (FASTA text is mostly
   // literals with 2..4-bit codes: half the lookups).
   void pair_literals() {
-#ifdef MK_INFLATE_NO_PAIRS
-    return;
-#endif
     for (unsigned i = 0; i < (1u << LBITS); ++i) {
       const uint32_t e1 = lt_[i];
       if ((e1 & (F_LIT | F_SUB | F_DBL)) != F_LIT) continue;

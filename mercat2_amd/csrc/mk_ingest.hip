@@ -208,7 +208,7 @@ static void gz_parallel_reader(Ring* R, const uint8_t* file, size_t file_len, co
     });
   }
   if (copier.joinable()) copier.join();
-  if (getenv("MK_VERBOSE"))
+  if (mk_env_set("MK_VERBOSE"))
     fprintf(stderr, "[mk] parallel gunzip: find %.3f s, decode %.3f s, stitch %.3f s, copy+wait %.3f s (overlapped); pieces %zu started, %zu kept\n",
             rd.engine().s_find, rd.engine().s_decode, rd.engine().s_stitch, s_copy, rd.engine().pieces_started, rd.engine().pieces_kept);
   *members_out = rd.members();
@@ -404,7 +404,7 @@ extern "C" int mk_count_file(mk_ctx* const* ctxs, int nctx, const char* path, ui
   // the GPUs the contexts are on, in order of first appearance
   // (MK_DEVICE_PER_CONTEXT=1, for tests on a one-GPU box: every context counts as a GPU of its own, so the several-GPU
   // code path -- per-GPU leaders, mk_merge_devices, the split of a single filter unit -- runs with device list [0, 0, ..])
-  const bool each_own = getenv("MK_DEVICE_PER_CONTEXT") != nullptr;
+  const bool each_own = mk_env_set("MK_DEVICE_PER_CONTEXT");
   auto group_of = [&](int j) { return each_own ? -1 - j : ctxs[j]->device; };
   std::vector<int> devs;
   for (int j = 0; j < nctx; ++j)
@@ -420,7 +420,7 @@ extern "C" int mk_count_file(mk_ctx* const* ctxs, int nctx, const char* path, ui
       text_guess = std::max<uint64_t>(isize, disk);
     }
   }
-  const uint64_t split_min = getenv("MK_SPLIT_MIN") ? (uint64_t)atoll(getenv("MK_SPLIT_MIN")) : ((uint64_t)64 << 20);
+  const uint64_t split_min = (uint64_t)mk_env_int("MK_SPLIT_MIN", (long long)64 << 20);
   const bool split = !chunked && devs.size() > 1 && text_guess >= split_min && c0->mode != MK_MODE_BYREF;
   const uint64_t piece_bytes = split ? std::max<uint64_t>((text_guess + (uint64_t)nctx - 1) / (uint64_t)nctx, std::min<uint64_t>(split_min, (uint64_t)8 << 20)) : 0;
   const int lanes_n = (chunked || split) ? nctx : 1;
@@ -431,9 +431,9 @@ extern "C" int mk_count_file(mk_ctx* const* ctxs, int nctx, const char* path, ui
 
   Ring R;
   {
-    const char* e = getenv("MK_INGEST_BLOCK");  // (tests shrink the blocks to put every boundary case in reach)
-    R.block = e && atoll(e) > 0 ? (size_t)atoll(e) : ((size_t)4 << 20);
-    if (!(e && atoll(e) > 0)) {
+    const long long want = mk_env_int("MK_INGEST_BLOCK", 0);  // (tests shrink the blocks to put every boundary case in reach)
+    R.block = want > 0 ? (size_t)want : ((size_t)4 << 20);
+    if (want <= 0) {
       // small samples: pinning the ring costs ~0.4 ms per MiB, more than reading the file -- size it to the text
       const uint64_t text_guess = gz ? disk * 6 : disk;
       while (R.block > ((size_t)64 << 10) && (uint64_t)R.block * 2 > text_guess + R.block / 2) R.block >>= 1;
@@ -454,7 +454,7 @@ extern "C" int mk_count_file(mk_ctx* const* ctxs, int nctx, const char* path, ui
     // (decoding scales further than reading: measured 1.1 s with 8 threads, 0.75 s with 16 on the 1.6 GB S2 file)
     if (auto_threads) threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
     if (bgzf.empty()) {
-      gz_parallel = threads > 1 && disk >= ((size_t)16 << 20) && !getenv("MK_GZ_SERIAL");
+      gz_parallel = threads > 1 && disk >= ((size_t)16 << 20) && !mk_env_set("MK_GZ_SERIAL");
       if (!gz_parallel) threads = 1;
     }
   }

@@ -745,7 +745,7 @@ extern "C" int mk_merge_devices(mk_ctx* const* ctxs, int n, int flags, mk_merge_
     S.max_owned = std::max<uint64_t>(S.max_owned, r);
   }
   S.s_total = secs(t_begin);
-  if (getenv("MK_VERBOSE"))
+  if (mk_env_set("MK_VERBOSE"))
     fprintf(stderr, "[mk] merge_devices: bounds %.0f us, bucket %.0f, reset+reserve %.0f, copies+import %.0f, text rows %.0f, total %.0f us\n",
             s_bounds * 1e6, S.s_bucket * 1e6, s_prepare * 1e6, S.s_copy * 1e6, S.s_import * 1e6, S.s_total * 1e6);
   if (st) *st = S;

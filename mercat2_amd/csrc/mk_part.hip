@@ -119,7 +119,7 @@ template <int BITS, int SPW, int WPT>
 __global__ __launch_bounds__(SCAT_THREADS) void mk_part_scatter_k(const u64* __restrict__ codes, const u64* __restrict__ bad,
                                                                   const MkChunkInfo* __restrict__ info,
                                                                   u64* __restrict__ cursor, u64* __restrict__ part,
-                                                                  int p1_log2, int k, size_t ntiles, int dbg, int canon) {
+                                                                  int p1_log2, int k, size_t ntiles, int canon) {
   __shared__ unsigned lh[PART_MAX_P1];
   __shared__ u64 gbase[PART_MAX_P1];
   constexpr int R = SPW * WPT;
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void mk_part_scatter_k(const u64* __r
 #pragma unroll
       for (int i = 0; i < NB; ++i) {
         const unsigned b = threadIdx.x + i * SCAT_THREADS;
-        r[i] = (v[i] && !(dbg & 2)) ? atomicAdd(&cursor[b], (u64)v[i]) : (u64)b * 16;
+        r[i] = v[i] ? atomicAdd(&cursor[b], (u64)v[i]) : (u64)b * 16;
       }
 #pragma unroll
       for (int i = 0; i < NB; ++i) {
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void mk_part_scatter_k(const u64* __r
             if (key != MK_EMPTY) {
               const unsigned b = (unsigned)(mk_mix64(key) >> hshift);
               const u64 at = gbase[b] + atomicAdd(&lh[b], 1u);
-              if (!(dbg & 1)) part[at] = key;
+              part[at] = key;
             }
           }
         }
@@ -230,7 +230,7 @@ __device__ __forceinline__ void lds_insert_slow(u64* tkey, unsigned* tcnt, unsig
 __global__ __launch_bounds__(CNT_THREADS) void mk_part_count_k(const u64* __restrict__ part, const u64* __restrict__ start,
                                                                MkChunkInfo* __restrict__ info, u64 min_count,
                                                                u64* __restrict__ out_keys, u64* __restrict__ out_cnts,
-                                                               int p1_log2, double dup_hint, int dbg) {
+                                                               int p1_log2, double dup_hint) {
   __shared__ u64 tkey[CNT_SLOTS];
   __shared__ unsigned tcnt[CNT_SLOTS];
   __shared__ unsigned s_distinct, s_overflow, s_emit;
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(CNT_THREADS) void mk_part_count_k(const u64* __rest
       __syncthreads();
       if (threadIdx.x == 0) {
         const unsigned tot = s_emit;
-        s_base = (tot && !(dbg & 4)) ? atomicAdd(&info->survivors, (u64)tot) : 0ull;
+        s_base = tot ? atomicAdd(&info->survivors, (u64)tot) : 0ull;
         s_emit = 0;
       }
       __syncthreads();
@@ -366,9 +366,7 @@ int mk_launch_count_partitioned(mk_ctx* c, size_t seq_len, uint64_t min_count) {
   // bucket count: aim at ~8K keys per bucket, between 256 and PART_MAX_P1
   int p1_log2 = 8;
   while (p1_log2 < 13 && (seq_len >> p1_log2) > 8192) ++p1_log2;
-  if (const char* e = getenv("MK_P1_LOG2")) { int v = atoi(e); if (v >= 4 && v <= 13) p1_log2 = v; }
   c->p1_log2 = p1_log2;
-  const int dbg = getenv("MK_DBG") ? atoi(getenv("MK_DBG")) : 0;
   const size_t p1 = (size_t)1 << p1_log2;
   int rc;
   if ((rc = mk_buf_reserve(c, c->part_meta, (3 * p1 + 8) * sizeof(u64))) != MK_OK) return rc;
@@ -389,7 +387,7 @@ int mk_launch_count_partitioned(mk_ctx* c, size_t seq_len, uint64_t min_count) {
     hipLaunchKernelGGL(mk_part_scan_k, dim3(1), dim3(1024), 0, c->stream, (const u64*)hist, start, cursor, p1_log2, (u64)1);
     hipLaunchKernelGGL((mk_part_scatter_k<2, 32, 1>), dim3((unsigned)(stiles < 4096 ? stiles : 4096)), dim3(SCAT_THREADS), 0,
                        c->stream, (const u64*)c->codes.p, (const u64*)c->bad.p, info, cursor, (u64*)c->part.p, p1_log2,
-                       c->k, stiles, dbg, c->canonical);
+                       c->k, stiles, c->canonical);
   } else {
     const size_t threads = div_up(seq_len, 36), tiles = div_up(threads, PART_THREADS);
     const size_t stiles = div_up(threads, (size_t)SCAT_THREADS * SCAT_SUBT);
@@ -399,13 +397,13 @@ int mk_launch_count_partitioned(mk_ctx* c, size_t seq_len, uint64_t min_count) {
     hipLaunchKernelGGL(mk_part_scan_k, dim3(1), dim3(1024), 0, c->stream, (const u64*)hist, start, cursor, p1_log2, (u64)1);
     hipLaunchKernelGGL((mk_part_scatter_k<5, 12, 3>), dim3((unsigned)(stiles < 4096 ? stiles : 4096)), dim3(SCAT_THREADS), 0,
                        c->stream, (const u64*)c->codes.p, (const u64*)c->bad.p, info, cursor, (u64*)c->part.p, p1_log2,
-                       c->k, stiles, dbg, c->canonical);
+                       c->k, stiles, c->canonical);
   }
   mk_prof_end(c);
   mk_prof_begin(c, MK_K_COUNT);
   hipLaunchKernelGGL(mk_part_count_k, dim3((unsigned)p1), dim3(CNT_THREADS), 0, c->stream, (const u64*)c->part.p,
                      (const u64*)start, info, (u64)min_count, (u64*)c->surv_keys.p, (u64*)c->surv_cnts.p, p1_log2,
-                     c->dup_hint, dbg);
+                     c->dup_hint);
   mk_prof_end(c);
   MK_HIP(hipGetLastError());
   return MK_OK;

@@ -32,28 +32,24 @@
 #include <emmintrin.h>
 
 #include "mk_crc32.h"
+#include "mk_env.h"
 #include "mk_inflate.h"
 
 // Big blocks of the decoder outlive the file they were used for: a block of 1 MiB or more goes to a process-wide
 // pool instead of back to the allocator, and the next file's decoder takes it from there.  Decoding a 0.55 GB .gz takes
 // ~1.3 GB of these buffers; giving them back was 90 ms of munmap at the end of every file (the reader thread's exit,
 // inside the window that is timed) and taking fresh ones a page fault per 4 KiB in the decoding threads.  The pool
-// keeps at most MK_POOL_BYTES (default 4 GiB) and 96 blocks; MK_NO_BUF_POOL=1 turns it off.
+// keeps at most MK_POOL_BYTES (default 4 GiB, read once, when the pool is built) and 96 blocks.
 struct MkBlockPool {
   struct Block { void* p; size_t bytes; };
   std::mutex mu;
   std::vector<Block> free_;
-  size_t held = 0, limit = (size_t)4 << 30;
-  bool off = false;
-  MkBlockPool() {
-    off = getenv("MK_NO_BUF_POOL") != nullptr;
-    if (const char* e = getenv("MK_POOL_BYTES")) limit = (size_t)strtoull(e, nullptr, 10);
-  }
+  size_t held = 0, limit = (size_t)mk_env_int("MK_POOL_BYTES", (long long)4 << 30);
   // (never destroyed: buffers may be given back while the process winds down; its blocks go with the process)
   static MkBlockPool& get() { static MkBlockPool* g = new MkBlockPool; return *g; }
   // the smallest pooled block of at least `bytes` (not more than four times as much), or nullptr
   void* take(size_t bytes, size_t* got) {
-    if (off || bytes < ((size_t)1 << 20)) return nullptr;
+    if (bytes < ((size_t)1 << 20)) return nullptr;
     std::lock_guard<std::mutex> g(mu);
     size_t best = free_.size();
     for (size_t i = 0; i < free_.size(); ++i)
@@ -70,7 +66,7 @@ struct MkBlockPool {
     if (!p) return;
     {
       std::lock_guard<std::mutex> g(mu);
-      if (!off && bytes >= ((size_t)1 << 20) && free_.size() < 96 && held + bytes <= limit) {
+      if (bytes >= ((size_t)1 << 20) && free_.size() < 96 && held + bytes <= limit) {
         free_.push_back({p, bytes});
         held += bytes;
         return;
@@ -116,7 +112,7 @@ class MkParallelInflate {
   size_t pieces_started = 0, pieces_kept = 0;
 
   MkParallelInflate(int threads, size_t piece_bytes) : threads_(threads < 1 ? 1 : threads), piece_(piece_bytes < 4096 ? 4096 : piece_bytes) {
-    if (const char* e = getenv("MK_PGUNZIP_FAIL_ROUND")) fail_round_ = atoi(e);  // (tests: make that round give up)
+    fail_round_ = (int)mk_env_int("MK_PGUNZIP_FAIL_ROUND", fail_round_);  // (tests: make that round give up)
   }
 
   // Decode from bit `start_bit` of [base, end) -- a verified block header -- whose preceding text ends

@@ -9,17 +9,8 @@
 #include <vector>
 #include <type_traits>
 
-#ifdef SKC_SMALL  // (mk_skcount_small.hip: this file once more with 512 threads / 4096 slots, under names of its own)
-#define mk_sk_count_k mk_sk_count_small_k
-#define mk_sk_countp_k mk_sk_countp_small_k
-#define mk_launch_sk_count mk_launch_sk_count_small
-#define mk_dbg_ptr mk_dbg_ptr_small
-#define SKC_FCAP_A 256   // list entries per sweep of the fused upsert: the short and the long list
-#define SKC_FCAP_B 512
-#else
-#define SKC_FCAP_A 512
+#define SKC_FCAP_A 512   // list entries per sweep of the fused upsert: the short and the long list
 #define SKC_FCAP_B 1024
-#endif
 
 #ifndef SKC_SLOTS
 #define SKC_SLOTS 8192          // LDS table slots of one workgroup (12 bytes each)
@@ -81,36 +72,15 @@ __device__ __forceinline__ unsigned skc_step(unsigned slot, unsigned d) {
   else return slot >= SKC_SLOTS ? slot - SKC_SLOTS : slot;
 }
 
-// Which record of a load round a thread takes: batch h, record h * SKC_THREADS + ..; odd batches hand the 64-record
-// groups to the waves in reverse order, so that when a bucket's records come sorted by length (longest first) every
-// wave gets a long group and a short one
-#ifdef SKC_DYN
-#define SKC_JMAP(h) ((u64)(h) * SKC_THREADS + (((h) & 1) ? (unsigned)(SKC_THREADS - 64 - (threadIdx.x & ~63u)) + (threadIdx.x & 63u) : threadIdx.x))
-#else
+// Which record of a load round a thread takes: batch h, record h * SKC_THREADS + ..
 #define SKC_JMAP(h) ((u64)(h) * SKC_THREADS + threadIdx.x)
-#endif
-// A bucket's records are read once, front to back: loaded past the L2's replacement order (SKC_NT_LOAD), so that the
-// 243 MB a chunk's count kernel streams do not push the open lines of the OTHER context's scatter out of the L2s.
-__device__ __forceinline__ ulonglong2 skc_ldrec(const ulonglong2* __restrict__ p) {
-#ifdef SKC_NT_LOAD
-  typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-  const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t*>(p));
-  return make_ulonglong2(v.x, v.y);
-#else
-  return *p;
-#endif
-}
 // The next bucket's first records, asked for before the sweep of this one, are taken in (waited for) BEFORE the fused
 // upsert's claims go out after the sweep: the loop head then has no load to wait for -- a wait there is vmcnt(0), which
 // also waits for the claims just issued, a trip to the running table in HBM per bucket (7 % of the kernel by the stamps).
-#ifdef SKC_NO_TAKE_IN
-#define SKC_TAKE_IN(pre)
-#else
 #define SKC_TAKE_IN(pre)                                                                       \
   do {                                                                                         \
     _Pragma("unroll") for (int h_ = 0; h_ < SKC_PRE; ++h_) asm volatile("" ::"v"((pre)[h_].x), "v"((pre)[h_].y)); \
   } while (0)
-#endif
 #define SKC_B 8          // k-mers of a record expanded and probed together
 #define SKC_WAVES (SKC_THREADS / 64)
 #ifndef SKC_PUSH
@@ -137,16 +107,8 @@ __device__ __forceinline__ void skc_drain(u64* tkey, unsigned* tcnt, const u64* 
     bool placed = false;
 #pragma unroll 1
     for (int probe = 0; probe < SKC_MAX_PROBE; ++probe) {
-#ifdef SKC_DRAIN_READ_FIRST  // (A/B: look before claiming -- two trips through the LDS for a free slot)
-      u64 cur = tkey[slot];
-      if (cur == MK_EMPTY) {
-        cur = atomicCAS(&tkey[slot], MK_EMPTY, key);
-        if (cur == MK_EMPTY) cur = key;
-      }
-#else
       u64 cur = atomicCAS(&tkey[slot], MK_EMPTY, key);  // claim-or-compare in one trip, as in the insert round
       if (cur == MK_EMPTY) cur = key;
-#endif
       if (cur == key) {
         atomicAdd(&tcnt[slot], 1u);
         placed = true;
@@ -205,17 +167,12 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
                                                              MkChunkInfo* __restrict__ info, u64 min_count,
                                                              u64* __restrict__ out_keys, u64* __restrict__ out_cnts,
                                                              int k, unsigned p1, double dup_hint, double nk_hint, u64* __restrict__ dbg,
-                                                             int dflags, MkSlot* __restrict__ run, u64 run_mask, unsigned max_probe,
-                                                             int nseg) {
+                                                             MkSlot* __restrict__ run, u64 run_mask, unsigned max_probe, int nseg) {
   constexpr bool FUSED = FCAP > 0;
   // (the longer list takes its LDS from the deferred-key stacks: two slots pushed at a time instead of four, measured 1 % slower)
   constexpr int PUSH = FCAP > SKC_FCAP_A ? 2 : SKC_PUSH;
   constexpr int QCAP = 64 + 64 * PUSH;
-#ifdef SKC_UNCOND
-  __shared__ __attribute__((aligned(16))) u64 tkey[SKC_SLOTS + 64];  // (+ a word per lane for the swaps of lanes without a key)
-#else
   __shared__ __attribute__((aligned(16))) u64 tkey[SKC_SLOTS];
-#endif
   __shared__ __attribute__((aligned(16))) unsigned tcnt[SKC_SLOTS];
   __shared__ __attribute__((aligned(16))) u64 wq[SKC_WAVES][QCAP];  // deferred keys, one stack per wave
   // survivors on their way into the running table: two lists (one being resolved, one being filled)
@@ -286,7 +243,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
 #pragma unroll
     for (int h = 0; h < SKC_PRE; ++h) {
       const unsigned j = (unsigned)SKC_JMAP(h);
-      if (j < n_n) pre[h] = skc_ldrec(part + skc_seg_at(s_seg[0], j, nseg));
+      if (j < n_n) pre[h] = part[skc_seg_at(s_seg[0], j, nseg)];
     }
     SKC_TAKE_IN(pre);
   }
@@ -320,7 +277,6 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
         // here, and 2^s0 passes over them took 30 s for 2 Mbases of poly-A.  Start no deeper than 8 sub-ranges;
         // a sub-range that overflows is split further anyway, and its pass stops at the first overflow.
         if (s0 > SKC_S0_MAX) s0 = SKC_S0_MAX;
-        if (dflags & 16) s0 = 0;  // (timing experiments only)
       }
       int s = s0;
       unsigned idx = 0;
@@ -345,7 +301,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
 #pragma unroll
             for (int h = 0; h < SKC_PRE; ++h) {
               const u64 j = rb2 + SKC_JMAP(h);
-              recs2[h] = j < n ? skc_ldrec(part + skc_seg_at(seg, (unsigned)j, nseg)) : make_ulonglong2(0, 0);
+              recs2[h] = j < n ? part[skc_seg_at(seg, (unsigned)j, nseg)] : make_ulonglong2(0, 0);
             }
             SKC_TAKE_IN(recs2);  // (waited for on this path, so that the join with the path above has nothing to wait for)
           }
@@ -361,65 +317,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
             u64 x = rec.x, y = rec.y;
             // (the whole wave walks the loop together -- lanes without a record or with a short one just have
             // no live slots -- because the deferred-key stack below is the wave's: every lane takes part)
-            // One round = up to NB consecutive k-mers of every lane's record.  NB is a compile-time constant of the
-            // body; with SKC_DYN the wave picks the body that fits its LONGEST record (4, 6 or 8 slots: scalar
-            // branch, no per-slot tests), which pays when the records a wave holds are about equally long.
-#ifdef SKC_OLD_ROUND
-            auto round = [&](auto nb_tag, auto, int base) {  // (A/B: the round as it was up to round 3)
-              constexpr int NB = decltype(nb_tag)::value;
-              u64 kk[NB], cur[NB];
-              unsigned hh[NB];
-              unsigned live = 0;  // bit u: slot u holds a key of this pass
-              // every key's compare-and-swap is issued as soon as its slot is known, so that the hashing of the
-              // later keys runs while the earlier ones are on their way through the LDS
-              // canonical keys: the reverse complement ROLLS with the window -- the base that enters the key on the
-              // right enters its reverse complement, complemented, on the left -- one full reversal per round
-              u64 rcv = CANON ? mk_revcomp2(x >> kshift, k) : 0ull;
-#pragma unroll
-              for (int u = 0; u < NB; ++u) {
-                const u64 fw = x >> kshift;
-                kk[u] = (CANON && rcv < fw) ? rcv : fw;
-                x = (x << 2) | (y >> 62);
-                y <<= 2;
-                if (CANON) rcv = (rcv >> 2) | ((((x >> kshift) & 3ull) ^ 3ull) << (2 * k - 2));
-                hh[u] = skc_hash(kk[u]);
-                bool on = base + u < nk;
-                if (K32 && on && kk[u] == MK_EMPTY) {
-                  side_pass += side_done ? 0 : 1;
-                  on = false;
-                }
-                if (s && ((hh[u] & ((1u << SKC_SUB_BITS) - 1)) >> sel_shift) != idx) on = false;
-                live |= on ? (1u << u) : 0u;
-                if (on) cur[u] = atomicCAS(&tkey[skc_home(hh[u])], MK_EMPTY, kk[u]);
-#ifdef SKC_SCHED_FENCE
-                __builtin_amdgcn_sched_barrier(0);
-#endif
-              }
-              unsigned fail = 0;
-#pragma unroll
-              for (int u = 0; u < NB; ++u)
-                if ((live >> u) & 1u) {
-                  if (cur[u] == MK_EMPTY || cur[u] == kk[u]) atomicAdd(&tcnt[skc_home(hh[u])], 1u);
-                  else fail |= 1u << u;
-                }
-              // deferred keys -> the wave's stack (positions from ballots: no atomic), four slots at a time
-              // so that the stack never holds more than SKC_QCAP; full groups of 64 are probed right away
-#pragma unroll
-              for (int half = 0; half < NB; half += PUSH) {
-#pragma unroll
-                for (int u = half; u < half + PUSH && u < NB; ++u) {
-                  const bool f = (fail >> u) & 1u;
-                  const u64 m = __ballot(f);
-                  if (m) {
-                    if (f) myq[qcount + skc_lane_rank(m)] = kk[u];
-                    qcount += (unsigned)__popcll(m);
-                  }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                while (qcount >= 64) skc_drain(tkey, tcnt, myq, qcount, 64u, ovf);
-              }
-            };
-#else
+            // One round = up to NB consecutive k-mers of every lane's record (NB: a compile-time constant of the body).
             auto round = [&](auto nb_tag, auto sub_tag, int base) {
               constexpr int NB = decltype(nb_tag)::value;
               constexpr bool SUB = decltype(sub_tag)::value;  // a sub-range pass (s > 0): keys are selected by hash bits
@@ -454,24 +352,13 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
                 if (SUB && ((hv & ((1u << SKC_SUB_BITS) - 1)) >> sel_shift) != idx) o = false;
                 on[u] = o;
                 sl[u] = skc_home(hv);
-#ifdef SKC_UNCOND  // (A/B: no exec masking at all -- lanes without a key swap on a word of their own behind the table)
-                cur[u] = atomicCAS(&tkey[o ? sl[u] : SKC_SLOTS + (unsigned)lane], MK_EMPTY, kk[u]);
-#else
                 if (o) cur[u] = atomicCAS(&tkey[sl[u]], MK_EMPTY, kk[u]);
-#endif
-#ifdef SKC_SCHED_FENCE
-                __builtin_amdgcn_sched_barrier(0);
-#endif
               }
 #pragma unroll
               for (int u = 0; u < NB; ++u) {
                 const bool ok = on[u] && (cur[u] == MK_EMPTY || cur[u] == kk[u]);
-#ifdef SKC_UNCOND
-                atomicAdd(&tcnt[sl[u]], ok ? 1u : 0u);
-#else
 #ifndef SKC_ABL_NOADD  // (timing ablation only, counts are wrong: 306 -> 274 us per S2 chunk)
                 if (ok) atomicAdd(&tcnt[sl[u]], 1u);
-#endif
 #endif
 #ifdef SKC_ABL_NODEFER  // (timing ablation only, keys that miss their home slot are dropped: 306 -> 212 us -- the stack
                 on[u] = false;   // and the probing loop are a third of the kernel; trying the next slot inside the round as well
@@ -496,24 +383,11 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
                 while (qcount >= 64) skc_drain(tkey, tcnt, myq, qcount, 64u, ovf);
               }
             };
-#endif
             auto round_any = [&](auto nb_tag, int base) {
               if (s) round(nb_tag, std::true_type{}, base);
               else round(nb_tag, std::false_type{}, base);
             };
-#ifdef SKC_DYN
-            int wmax = nk;  // the wave's longest record (wave-uniform)
-            for (int d = 32; d > 0; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
-            wmax = __builtin_amdgcn_readfirstlane(wmax);
-            for (int base = 0; base < wmax;) {
-              const int left = wmax - base;
-              if (left <= 4) { round_any(std::integral_constant<int, 4>{}, base); base += 4; }
-              else if (left <= 6) { round_any(std::integral_constant<int, 6>{}, base); base += 6; }
-              else { round_any(std::integral_constant<int, SKC_B>{}, base); base += SKC_B; }
-            }
-#else
             for (int base = 0; __any(base < nk); base += SKC_B) round_any(std::integral_constant<int, SKC_B>{}, base);
-#endif
           }
           STAMP_ADD(tC, t0);
           // hint only; decided after the barrier below (an LDS read: a volatile access through the generic pointer was a
@@ -569,7 +443,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
 #pragma unroll
           for (int h = 0; h < SKC_PRE; ++h) {
             const unsigned j = (unsigned)SKC_JMAP(h);
-            pre[h] = j < n_n ? skc_ldrec(part + skc_seg_at(s_seg[bp ^ 1], j, nseg)) : make_ulonglong2(0, 0);
+            pre[h] = j < n_n ? part[skc_seg_at(s_seg[bp ^ 1], j, nseg)] : make_ulonglong2(0, 0);
           }
         }
         // ---- emit (when complete) into the bucket's own region, and clear.  The sweep reads the COUNTS only
@@ -693,7 +567,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
 #pragma unroll
         for (int h = 0; h < SKC_PRE; ++h) {
           const unsigned j = (unsigned)SKC_JMAP(h);
-          pre[h] = j < n_n ? skc_ldrec(part + skc_seg_at(s_seg[bp ^ 1], j, nseg)) : make_ulonglong2(0, 0);
+          pre[h] = j < n_n ? part[skc_seg_at(s_seg[bp ^ 1], j, nseg)] : make_ulonglong2(0, 0);
         }
         SKC_TAKE_IN(pre);
       }
@@ -731,333 +605,6 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
   if (K32) wave_add(&info->side, side);
 }
 
-// ------------------------------------------------------------------- count with a counting pre-filter
-// With -c well above the mean count of a key (S2: 75 M windows over 19.6 M distinct keys per chunk, -c 10) nearly every
-// insert of the kernel above -- compare-and-swap of the 64-bit key, add, deferred-key stack -- feeds a slot that the
-// emit sweep throws away.  Here every bucket is walked twice (as in mk_skmer2.hip, where the case is made at length):
-//   P  every key adds 1 to one of 16 384 32-bit counters in LDS (a count-min row): never below the count of a key that
-//      maps to it;
-//   Q  keys whose counter reached min_count (every key that can survive, plus the few that share a counter) are
-//      inserted into a small exact table, every occurrence of them; the rest costs one LDS read.
-// `distinct` = counters in use (a lower bound).
-// MEASURED (round 3, S2 chunk, k = 31, -c 10): 437 us against the exact kernel's 300 -- for one-word keys the tuned
-// single pass (compare-and-swap as soon as a slot is known, deferred-key stacks, the next bucket's records prefetched)
-// beats two plain passes; it is the two-word kernel, with its lock / write / publish protocol and its sub-range passes,
-// that the pre-filter more than halves (mk_skmer2.hip).  So this kernel is NOT the default: MK_FORCE_PREFILTER=1 selects
-// it (tests keep it exact: tests/test_gpu_parity.py::test_counting_prefilter_kernels_are_exact).
-#define SKP_CNT 16384
-#define SKP_SLOTS 2048
-#define SKP_MAX_PROBE 64
-#define SKP_QCAP 128  // candidates a wave can hold: < 64 left over + one slot x 64 lanes
-
-__device__ __forceinline__ void skp_insert(u64* tkey, unsigned* tcnt, unsigned* ovf, u64 key, unsigned h) {
-  unsigned slot = h >> (32 - 11);  // SKP_SLOTS = 2^11
-  bool done = false;
-#pragma unroll 1
-  for (int probe = 0; probe < SKP_MAX_PROBE && !done; ++probe) {
-    u64 cur = tkey[slot];
-    if (cur == MK_EMPTY) {
-      cur = atomicCAS(&tkey[slot], MK_EMPTY, key);
-      if (cur == MK_EMPTY) cur = key;
-    }
-    if (cur == key) {
-      atomicAdd(&tcnt[slot], 1u);
-      done = true;
-    } else {
-      slot = (slot + 1) & (SKP_SLOTS - 1);
-    }
-  }
-  if (!done) atomicOr(ovf, 1u);
-}
-
-template <bool CANON, bool K32>
-__global__ __launch_bounds__(SKC_THREADS) void mk_sk_countp_k(const ulonglong2* __restrict__ part, const u64* __restrict__ start,
-                                                              SkCursor* __restrict__ cursor, const u64* __restrict__ kstart,
-                                                              u64* __restrict__ nsurv, MkChunkInfo* __restrict__ info, u64 min_count,
-                                                              u64* __restrict__ out_keys, u64* __restrict__ out_cnts, int k, unsigned p1) {
-  __shared__ unsigned cnt32[SKP_CNT];
-  __shared__ __attribute__((aligned(16))) u64 tkey[SKP_SLOTS];
-  __shared__ unsigned tcnt[SKP_SLOTS];
-  __shared__ __attribute__((aligned(16))) u64 cq[SKC_WAVES][SKP_QCAP];  // candidates, one stack per wave (positions from ballots)
-  __shared__ unsigned s_distinct[2], s_overflow[2], s_emit[2];
-  __shared__ unsigned long long s_windows;
-  __shared__ unsigned s_abort;
-  if (threadIdx.x == 0) { s_abort = info->part_overflow != 0; s_windows = 0; }
-  __syncthreads();
-  if (s_abort) return;
-  for (unsigned i = threadIdx.x; i < SKP_CNT; i += blockDim.x) cnt32[i] = 0;
-  for (unsigned i = threadIdx.x; i < SKP_SLOTS; i += blockDim.x) { tkey[i] = MK_EMPTY; tcnt[i] = 0; }
-  if (threadIdx.x < 2) { s_distinct[threadIdx.x] = 0; s_overflow[threadIdx.x] = 0; s_emit[threadIdx.x] = 0; }
-  __syncthreads();
-  unsigned par = 0;
-  const int kshift = 64 - 2 * k;
-  const int lane = threadIdx.x & 63;
-  const unsigned need = min_count > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)min_count;
-  u64 distinct_total = 0, side = 0, survivors_total = 0, nerr = 0, windows = 0, records_total = 0;
-  // as in mk_sk_count_k: the next bucket's bounds and its first records are loaded while this one is swept, and a
-  // bucket's first SKC_PRE x 1024 records (nearly always all of them) stay in registers from P to Q
-  unsigned bn = blockIdx.x;
-  u64 lo_n = 0, hi_n = 0, ks_n = 0, ke_n = 0;
-  ulonglong2 pre[SKC_PRE];
-#pragma unroll
-  for (int h = 0; h < SKC_PRE; ++h) pre[h] = make_ulonglong2(0, 0);
-  if (bn < p1) {
-    lo_n = start[bn];
-    hi_n = cursor[bn];
-    ks_n = kstart[bn];
-    ke_n = kstart[bn + 1];
-#pragma unroll
-    for (int h = 0; h < SKC_PRE; ++h) {
-      const u64 j = (u64)h * SKC_THREADS + threadIdx.x;
-      if (j < hi_n - lo_n) pre[h] = part[lo_n + j];
-    }
-  }
-  for (unsigned b = blockIdx.x; b < p1; b += gridDim.x) {
-    const u64 lo = lo_n, n = hi_n - lo_n;
-    u64* __restrict__ my_keys = out_keys + ks_n;
-    u64* __restrict__ my_cnts = out_cnts + ks_n;
-    const u64 region = ke_n - ks_n;
-    ulonglong2 first[SKC_PRE];
-#pragma unroll
-    for (int h = 0; h < SKC_PRE; ++h) first[h] = pre[h];
-    bn = b + gridDim.x;
-    if (bn < p1) {
-      lo_n = start[bn];
-      hi_n = cursor[bn];
-      ks_n = kstart[bn];
-      ke_n = kstart[bn + 1];
-    }
-    unsigned emitted = 0;
-    bool counted = false;
-    bool fetched = false;  // the next bucket's records are in pre[]
-    records_total += n;
-    if (n >> 27) {  // 2^27 records x 31 k-mers would overflow the 32-bit LDS counters
-      ++nerr;
-    } else if (n) {
-      int s = 0;
-      unsigned idx = 0;
-      const ulonglong2* __restrict__ src = part + lo;
-      for (;;) {
-        const unsigned sel_shift = 32 - s;
-        unsigned* const ovf = &s_overflow[par];
-        u64 win_pass = 0, side_pass = 0;
-        // ---- P: eight fire-and-forget LDS adds per record, nothing waits for an answer.  The hashes (and which slots
-        //      are live) of the records that stay in registers are kept for Q: that pass then costs a read and a compare
-        //      per key, and the key itself is rebuilt only for the rare candidate
-        unsigned hs[SKC_PRE][SKC_B], lives[SKC_PRE];
-        for (u64 rb2 = 0; rb2 < n; rb2 += SKC_PRE * SKC_THREADS) {
-#pragma unroll
-          for (int h = 0; h < SKC_PRE; ++h) {
-            ulonglong2 rec;
-            if (rb2 == 0) rec = first[h];
-            else {
-              const u64 j = rb2 + (u64)h * SKC_THREADS + threadIdx.x;
-              rec = j < n ? src[j] : make_ulonglong2(0, 0);
-            }
-            const int nk = (int)(rec.y & 63);
-            win_pass += counted ? 0 : (u64)nk;
-            u64 x = rec.x, y = rec.y;
-            u64 rcv = CANON ? mk_revcomp2(x >> kshift, k) : 0ull;
-            unsigned live = 0;
-#pragma unroll
-            for (int u = 0; u < SKC_B; ++u) {
-              const u64 fw = x >> kshift;
-              const u64 key = (CANON && rcv < fw) ? rcv : fw;
-              x = (x << 2) | (y >> 62);
-              y <<= 2;
-              if (CANON) rcv = (rcv >> 2) | ((((x >> kshift) & 3ull) ^ 3ull) << (2 * k - 2));
-              const unsigned hv = skc_hash(key);
-              bool on = u < nk && (!s || (hv >> sel_shift) == idx);
-              if (K32 && on && key == MK_EMPTY) {
-                side_pass += counted ? 0 : 1;
-                on = false;
-              }
-              if (on) atomicAdd(&cnt32[hv & (SKP_CNT - 1)], 1u);
-              live |= on ? (1u << u) : 0u;
-              if (rb2 == 0) hs[h][u] = hv;
-            }
-            if (rb2 == 0) lives[h] = live;
-          }
-        }
-        __syncthreads();
-        // ---- Q: eight independent LDS reads per record; the rare candidate goes onto the wave's stack, and the wave
-        //      inserts 64 of them at a time with every lane busy (one by one in the lane that found them, the inserts'
-        //      LDS round trips ran one after the other: that alone made the kernel slower than the exact one)
-        u64* const myq = cq[threadIdx.x >> 6];
-        unsigned qcount = 0;
-        for (u64 rb2 = 0; rb2 < n; rb2 += SKC_PRE * SKC_THREADS) {
-#pragma unroll
-          for (int h = 0; h < SKC_PRE; ++h) {
-            ulonglong2 rec;
-            if (rb2 == 0) rec = first[h];
-            else {
-              const u64 j = rb2 + (u64)h * SKC_THREADS + threadIdx.x;
-              rec = j < n ? src[j] : make_ulonglong2(0, 0);
-            }
-            unsigned hh[SKC_B], cv[SKC_B];
-            unsigned live = 0;
-            if (rb2 == 0) {
-              live = lives[h];
-#pragma unroll
-              for (int u = 0; u < SKC_B; ++u) hh[u] = hs[h][u];
-            } else {
-              const int nk = (int)(rec.y & 63);
-              u64 x = rec.x, y = rec.y;
-              u64 rcv = CANON ? mk_revcomp2(x >> kshift, k) : 0ull;
-#pragma unroll
-              for (int u = 0; u < SKC_B; ++u) {
-                const u64 fw = x >> kshift;
-                const u64 key = (CANON && rcv < fw) ? rcv : fw;
-                x = (x << 2) | (y >> 62);
-                y <<= 2;
-                if (CANON) rcv = (rcv >> 2) | ((((x >> kshift) & 3ull) ^ 3ull) << (2 * k - 2));
-                hh[u] = skc_hash(key);
-                bool on = u < nk && (!s || (hh[u] >> sel_shift) == idx);
-                if (K32 && key == MK_EMPTY) on = false;
-                live |= on ? (1u << u) : 0u;
-              }
-            }
-#pragma unroll
-            for (int u = 0; u < SKC_B; ++u) cv[u] = ((live >> u) & 1u) ? cnt32[hh[u] & (SKP_CNT - 1)] : 0u;
-            unsigned cand = 0;
-#pragma unroll
-            for (int u = 0; u < SKC_B; ++u) cand |= (cv[u] >= need && cv[u]) ? (1u << u) : 0u;
-            if (__any(cand != 0)) {
-#pragma unroll
-              for (int u = 0; u < SKC_B; ++u) {
-                const bool f = (cand >> u) & 1u;
-                const u64 m = __ballot(f);
-                if (m) {
-                  if (f) {  // window u of the record: its 2k bits start 2u bits into (x : y)
-                    const u64 sx = u ? ((rec.x << (2 * u)) | (rec.y >> (64 - 2 * u))) : rec.x;
-                    myq[qcount + skc_lane_rank(m)] = mk_canon2(sx >> kshift, k, CANON);
-                  }
-                  qcount += (unsigned)__popcll(m);
-                  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                  if (qcount >= 64) {
-                    qcount -= 64;
-                    const u64 key = myq[qcount + lane];
-                    skp_insert(tkey, tcnt, ovf, key, skc_hash(key) * 0x9E3779B1u);
-                  }
-                }
-              }
-            }
-          }
-        }
-        if (qcount) {  // (< 64 left)
-          if ((unsigned)lane < qcount) {
-            const u64 key = myq[lane];
-            skp_insert(tkey, tcnt, ovf, key, skc_hash(key) * 0x9E3779B1u);
-          }
-          qcount = 0;
-        }
-        __syncthreads();  // A
-        if (threadIdx.x == 0) cursor[b] = lo;
-        const bool over = s_overflow[par] != 0;
-        if (threadIdx.x == 0) { s_distinct[par ^ 1] = 0; s_overflow[par ^ 1] = 0; s_emit[par ^ 1] = 0; }
-        // the bucket's last pass? then the next bucket's records start loading now
-        if (!over && !fetched) {
-          int s2 = s;
-          unsigned i2 = idx;
-          while (s2 > 0 && (i2 & 1u)) { i2 >>= 1; --s2; }
-          if (s2 == 0) {
-            fetched = true;
-            if (bn < p1) {
-#pragma unroll
-              for (int h = 0; h < SKC_PRE; ++h) {
-                const u64 j = (u64)h * SKC_THREADS + threadIdx.x;
-                pre[h] = (j < hi_n - lo_n) ? part[lo_n + j] : make_ulonglong2(0, 0);
-              }
-            }
-          }
-        }
-        {
-          unsigned occ = 0;
-#pragma unroll
-          for (int q = 0; q < SKP_CNT / SKC_THREADS; q += 4) {
-            const unsigned i = (q * SKC_THREADS + 4 * threadIdx.x);
-            const uint4 c4 = *reinterpret_cast<const uint4*>(&cnt32[i]);
-            occ += (c4.x != 0) + (c4.y != 0) + (c4.z != 0) + (c4.w != 0);
-            *reinterpret_cast<uint4*>(&cnt32[i]) = make_uint4(0u, 0u, 0u, 0u);
-          }
-          occ = mk_wave_sum(occ);
-          if (lane == 0 && occ && !over) atomicAdd(&s_distinct[par], occ);
-          constexpr int PER = SKP_SLOTS / SKC_THREADS;
-          unsigned ec[PER];
-          unsigned mine = 0;
-#pragma unroll
-          for (int q = 0; q < PER; ++q) {
-            const unsigned i = q * SKC_THREADS + threadIdx.x;
-            ec[q] = tcnt[i];
-            if (over || (u64)ec[q] < min_count) ec[q] = 0;
-            mine += ec[q] != 0;
-          }
-          if (mine) {
-            const unsigned at = emitted + atomicAdd(&s_emit[par], mine);
-            unsigned o = 0;
-            if ((u64)at + mine > region) {
-              atomicOr(&info->part_overflow, 8ull);
-              mine = 0;
-            }
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-              if (mine && ec[q]) {
-                my_keys[at + o] = tkey[q * SKC_THREADS + threadIdx.x];
-                my_cnts[at + o] = ec[q];
-                ++o;
-              }
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < PER; ++q) {
-            const unsigned i = q * SKC_THREADS + threadIdx.x;
-            tkey[i] = MK_EMPTY;
-            tcnt[i] = 0;
-          }
-        }
-        __syncthreads();  // B
-        emitted += s_emit[par];
-        distinct_total += s_distinct[par];
-        par ^= 1;
-        if (over) {
-          if (s >= 16) { ++nerr; break; }
-          s += 1;
-          idx <<= 1;
-        } else {
-          windows += win_pass;
-          side += side_pass;
-          counted = true;
-          while (s > 0 && (idx & 1u)) { idx >>= 1; --s; }
-          if (s == 0) break;
-          ++idx;
-        }
-      }
-    }
-    if (!fetched && bn < p1) {  // (an empty or refused bucket: nothing was prefetched by a last pass)
-#pragma unroll
-      for (int h = 0; h < SKC_PRE; ++h) {
-        const u64 j = (u64)h * SKC_THREADS + threadIdx.x;
-        pre[h] = (j < hi_n - lo_n) ? part[lo_n + j] : make_ulonglong2(0, 0);
-      }
-    }
-    if (threadIdx.x == 0) nsurv[b] = emitted;
-    survivors_total += emitted;
-  }
-  {
-    for (int d = 32; d > 0; d >>= 1) windows += __shfl_down(windows, d);
-    if (lane == 0 && windows) atomicAdd(&s_windows, (unsigned long long)windows);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (s_windows) atomicAdd(&info->windows, (u64)s_windows);
-    if (records_total) atomicAdd(&info->records, records_total);
-    if (distinct_total) atomicAdd(&info->distinct, distinct_total);
-    if (survivors_total) atomicAdd(&info->survivors, survivors_total);
-    if (nerr) atomicAdd(&info->errors, nerr);
-  }
-  if (K32) wave_add(&info->side, side);
-}
-
 // ------------------------------------------------------------------------------ launcher
 #ifdef MK_STAMP
 u64* mk_dbg_ptr = nullptr;
@@ -1065,8 +612,8 @@ u64* mk_dbg_ptr = nullptr;
 
 // The count kernel over the p1 bucket regions the scatter has filled (start / cursor: records, kstart: survivor regions,
 // nsurv: survivors per bucket, written here).  Called by mk_launch_count_superkmer (mk_skmer.hip).
-int mk_launch_sk_count(mk_ctx* c, const u64* start, SkCursor* cursor, const u64* kstart, u64* nsurv, uint64_t min_count, int nkmax,
-                       size_t p1, bool exact, int nseg) {
+int mk_launch_sk_count(mk_ctx* c, const u64* start, SkCursor* cursor, const u64* kstart, u64* nsurv, uint64_t min_count,
+                       size_t p1, int nseg) {
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
   const int k = c->k;
   mk_prof_begin(c, MK_K_COUNT);
@@ -1079,24 +626,10 @@ int mk_launch_sk_count(mk_ctx* c, const u64* start, SkCursor* cursor, const u64*
     if (!mk_dbg_ptr) (void)hipMalloc((void**)&mk_dbg_ptr, 8 * 8 * 1024);
     dbgbuf = mk_dbg_ptr;
 #endif
-    const int dflags = getenv("MK_DBG") ? atoi(getenv("MK_DBG")) : 0;
-    static const bool no_pre = getenv("MK_NO_PREFILTER") != nullptr;
-    static const bool force_pre = getenv("MK_FORCE_PREFILTER") != nullptr;
-    const bool pre = !no_pre && !exact && min_count >= 2 && nkmax <= SKC_B && force_pre;  // (opt-in only: see mk_sk_countp_k)
-    if (pre) c->fused_last = false;
-    if (pre && nseg != 1) { c->err = "mk_launch_sk_count: the pre-filter kernel reads one region per bucket"; return MK_ERR_ARG; }
-#define SKP_LAUNCH(CANON, K32)                                                                                          \
-  hipLaunchKernelGGL((mk_sk_countp_k<CANON, K32>), dim3(grid), dim3(SKC_THREADS), 0, c->stream, (const ulonglong2*)c->part.p, \
-                     (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count,                        \
-                     (u64*)c->surv_keys.p, (u64*)c->surv_cnts.p, k, (unsigned)p1)
-    if (pre) {
-      if (c->canonical) { if (k == 32) SKP_LAUNCH(true, true); else SKP_LAUNCH(true, false); }
-      else { if (k == 32) SKP_LAUNCH(false, true); else SKP_LAUNCH(false, false); }
-    } else {
 #define SKC_LAUNCH(CANON, K32, FCAP)                                                                                    \
   hipLaunchKernelGGL((mk_sk_count_k<CANON, K32, FCAP>), dim3(grid), dim3(SKC_THREADS), 0, c->stream, (const ulonglong2*)c->part.p, \
                      (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count,                        \
-                     (u64*)c->surv_keys.p, (u64*)c->surv_cnts.p, k, (unsigned)p1, c->dup_hint, c->nk_hint, dbgbuf, dflags, \
+                     (u64*)c->surv_keys.p, (u64*)c->surv_cnts.p, k, (unsigned)p1, c->dup_hint, c->nk_hint, dbgbuf,     \
                      (MkSlot*)tab->run.p, (u64)(tab->run_slots ? tab->run_slots - 1 : 0), max_probe, nseg)
 #define SKC_LAUNCH2(CANON, K32)                                                                                         \
   do {                                                                                                                  \
@@ -1105,7 +638,7 @@ int mk_launch_sk_count(mk_ctx* c, const u64* start, SkCursor* cursor, const u64*
     else SKC_LAUNCH(CANON, K32, 0);                                                                                     \
   } while (0)
     // (fused: the survivors go straight into the running table, which process_chunk_fast has sized for them)
-    const unsigned max_probe = getenv("MK_FUSE_MAX_PROBE") ? (unsigned)atoi(getenv("MK_FUSE_MAX_PROBE")) : (unsigned)SKF_MAX_PROBE;
+    const unsigned max_probe = (unsigned)mk_env_int("MK_FUSE_MAX_PROBE", SKF_MAX_PROBE);
     mk_ctx* tab = (c->fuse_cap > 0 && c->fuse_target) ? c->fuse_target : c;  // (mk_share_table: the caller holds that table's lock)
     const int fcap = (c->fuse_cap > 0 && tab->run_slots >= 1024 && tab->run_slots <= ((size_t)1 << 32)) ? c->fuse_cap : 0;
     c->fused_last = fcap > 0;
@@ -1113,8 +646,6 @@ int mk_launch_sk_count(mk_ctx* c, const u64* start, SkCursor* cursor, const u64*
     else { if (k == 32) SKC_LAUNCH2(false, true); else SKC_LAUNCH2(false, false); }
 #undef SKC_LAUNCH2
 #undef SKC_LAUNCH
-    }
-#undef SKP_LAUNCH
   }
   mk_prof_end(c);
 #ifdef MK_STAMP

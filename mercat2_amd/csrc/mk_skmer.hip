@@ -16,8 +16,8 @@
 //                    thread in eight only (a sample)
 //   2 mk_sk_scan     bucket regions of the record buffer and of the survivor buffer in one pass; sampled
 //                    counts become capacities with room for the sampling error
-//   3 mk_sk_scatter  same walk over tiles of 2 x 1024 threads (the first sub-tile's analysis parked in
-//                    LDS); rank of each record inside its (tile,bucket) run from an LDS counter, one sweep
+//   3 mk_sk_scatterq same analysis over tiles of 2 or 3 x 512 threads, the records listed in per-wave queues in
+//                    LDS; rank of each record inside its (tile,bucket) run from an LDS counter, one sweep
 //                    of cursor atomics per tile checked against the region ends, 16-byte record stores
 //   4 mk_sk_count    (mk_skcount.hip) persistent, one workgroup per CU walks the buckets: expands the records into k-mers
 //                    and counts them in an LDS open-addressing table (claim-or-compare with one
@@ -38,21 +38,11 @@
 #ifndef SK_HIST_GRID
 #define SK_HIST_GRID 512
 #endif
-#ifndef SK_SCAT_THREADS
-#define SK_SCAT_THREADS 1024
-#endif
 #ifndef SK_SCAT_GRID
 #define SK_SCAT_GRID 4096
 #endif
-#ifndef SK_SCAT_SUBT
-#define SK_SCAT_SUBT 2
-#endif
-#ifndef SK_MAX_P1_LOG2
-#define SK_MAX_P1_LOG2 14       // most buckets a chunk is cut into (2^13 by default: the launcher's choice; 2^14 with MK_CORES)
-#endif
-#define SK_MAX_P1 (1 << SK_MAX_P1_LOG2)
-#define SK_LH_LOG2 13           // bucket counters the queue scatter keeps in LDS at a time: with more buckets than that a tile
-#define SK_LH (1 << SK_LH_LOG2) // is worked off in rounds of 2^13 buckets (the LDS stays at 72-80 KB: two workgroups per CU)
+#define SK_MAX_P1_LOG2 13       // most buckets a chunk is cut into: the scatter keeps a counter per bucket in LDS (72-80 KB
+#define SK_MAX_P1 (1 << SK_MAX_P1_LOG2)  // with its queues: two workgroups per CU)
 #ifndef SK_BUCKET_SYMS
 #define SK_BUCKET_SYMS 8192     // symbols of the chunk per bucket the bucket count aims at (~1.2K records, ~10K windows)
 #endif
@@ -222,124 +212,7 @@ __global__ __launch_bounds__(1024) void mk_sk_scan_k(const u64* __restrict__ his
 #endif
 
 // --------------------------------------------------------------------------- 3 scatter
-template <int W, bool CANON>
-__global__ __launch_bounds__(1024) void mk_sk_scatter_k(const u64* __restrict__ codes, const u64* __restrict__ bad,
-                                                                   MkChunkInfo* __restrict__ info, const u64* __restrict__ start,
-                                                                   SkCursor* __restrict__ cursor, ulonglong2* __restrict__ part,
-                                                                   int p1_log2, int k, int nkmax, size_t ntiles, int canon) {
-  // lh[b]: pass 1 counts the tile's records of bucket b; after the reservation it holds the record index at which
-  // the tile's run in that bucket starts (the launcher keeps indices below SK_NOFIT) and pass 2's atomic add hands
-  // out base + rank in one step -- one array instead of two, which is what lets a tile park a second analysis
-  __shared__ unsigned lh[SK_MAX_P1];
-  constexpr int PK = SK_SCAT_SUBT > 1 ? SK_SCAT_SUBT - 1 : 1;  // parked analyses (56 bytes per thread each)
-  __shared__ uint2 pk_mask[PK][SK_SCAT_THREADS];
-  __shared__ ulonglong2 pk_w[PK][SK_SCAT_THREADS];
-  __shared__ ulonglong2 pk_pos[PK][2][SK_SCAT_THREADS];
-  __shared__ unsigned s_abort;  // (read once per workgroup: other workgroups of this launch may set the flag meanwhile)
-  if (threadIdx.x == 0) s_abort = info->part_overflow != 0;
-  __syncthreads();
-  if (s_abort) return;  // the regions do not fit the buffers: nothing may be written
-  unsigned spilled = 0;
-  constexpr int NB = SK_MAX_P1 / SK_SCAT_THREADS;
-  const unsigned p1 = 1u << p1_log2;
-  const size_t seq_len = info->seq_len;
-  for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) lh[i] = 0;
-  __syncthreads();
-  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    // pass 1: analyse every sub-tile once and size the runs. The analysis of the last sub-tile stays
-    // in registers for pass 2, that of the others is parked in LDS (a second register copy spills):
-    // twice the records per tile halves the cursor atomics per record, which run at the L2's limit.
-    SkRuns runs;
-    u64 ww0 = 0, ww1 = 0;
-#pragma unroll
-    for (int st = 0; st < SK_SCAT_SUBT; ++st) {
-      const size_t t = (tile * SK_SCAT_SUBT + st) * SK_SCAT_THREADS + threadIdx.x;
-      const size_t p0 = t * SK_R;
-      runs.valid = 0;
-      runs.starts = 0;
-      runs.pos[0] = runs.pos[1] = runs.pos[2] = runs.pos[3] = 0;
-      ww0 = ww1 = 0;
-      if (p0 < seq_len) {
-        ww0 = codes[t];
-        ww1 = codes[t + 1];
-        runs = sk_analyse<W>(ww0, ww1, sk_valid32(bad_window(bad, p0), k), CANON);
-        sk_walk(runs, ww0, ww1, nkmax, CANON,
-                [&](int, int, unsigned mm) { atomicAdd(&lh[sk_bucket(mm, p1_log2)], 1u); });
-      }
-      if (st + 1 < SK_SCAT_SUBT) {
-        pk_mask[st][threadIdx.x] = make_uint2(runs.valid, runs.starts);
-        pk_w[st][threadIdx.x] = make_ulonglong2(ww0, ww1);
-        pk_pos[st][0][threadIdx.x] = make_ulonglong2(runs.pos[0], runs.pos[1]);
-        pk_pos[st][1][threadIdx.x] = make_ulonglong2(runs.pos[2], runs.pos[3]);
-      }
-    }
-    __syncthreads();
-    {
-      unsigned v[NB];
-      u64 r[NB];
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const unsigned b = threadIdx.x + i * SK_SCAT_THREADS;
-        v[i] = b < p1 ? lh[b] : 0u;
-      }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const unsigned b = threadIdx.x + i * SK_SCAT_THREADS;
-#ifdef SK_ABL_NOCURSOR  // (timing ablation only: no reservation, runs land on top of each other)
-        r[i] = v[i] ? start[b] : 0ull;
-#elif defined(SK_ABL_WGSCOPE)  // (timing ablation only: the add is performed in this XCD's L2 -- not coherent across XCDs)
-        r[i] = v[i] ? __hip_atomic_fetch_add(&cursor[b], (u64)v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0ull;
-#else
-        r[i] = v[i] ? atomicAdd(&cursor[b], (u64)v[i]) : 0ull;
-#endif
-      }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const unsigned b = threadIdx.x + i * SK_SCAT_THREADS;
-        if (b < p1) {
-          // a run that would cross the end of its bucket's region (sampled sizes only) is not written
-          const bool fits = v[i] == 0 || r[i] + v[i] <= start[b + 1];
-          spilled |= fits ? 0u : 1u;
-          lh[b] = fits ? (unsigned)r[i] : SK_NOFIT;
-        }
-      }
-    }
-    __syncthreads();
-    // pass 2: rank of every record inside its run, store (registers first, then the parked sub-tiles)
-#pragma unroll
-    for (int st = SK_SCAT_SUBT - 1; st >= 0; --st) {
-      if (st + 1 < SK_SCAT_SUBT) {
-        const uint2 m = pk_mask[st][threadIdx.x];
-        const ulonglong2 w = pk_w[st][threadIdx.x], pa = pk_pos[st][0][threadIdx.x], pb = pk_pos[st][1][threadIdx.x];
-        runs.valid = m.x;
-        runs.starts = m.y;
-        runs.pos[0] = pa.x; runs.pos[1] = pa.y; runs.pos[2] = pb.x; runs.pos[3] = pb.y;
-        ww0 = w.x;
-        ww1 = w.y;
-      }
-      const u64 w0 = ww0, w1 = ww1;
-      (void)canon;
-      sk_walk(runs, w0, w1, nkmax, CANON, [&](int jstart, int nk, unsigned mm) {
-        const unsigned b = sk_bucket(mm, p1_log2);
-        const unsigned at = atomicAdd(&lh[b], 1u);  // base + rank
-        // (the record is built while the LDS answers: pinned here, or the compiler sinks it behind the test of `at`)
-        ulonglong2 rec = sk_make_record(w0, w1, jstart, nk, k);
-        asm volatile("" : "+v"(rec.x), "+v"(rec.y));
-#ifdef SK_ABL_NOSTORE   // (timing ablation only: the record is built and dropped)
-        if (at == 0xFFFFFFFFu) part[(size_t)at] = rec;
-#else
-        if (at < SK_NOFIT) part[(size_t)at] = rec;
-#endif
-      });
-    }
-    __syncthreads();
-    for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) lh[i] = 0;
-    __syncthreads();
-  }
-  if (spilled) atomicOr(&info->part_overflow, 4ull);
-}
-
-// The same scatter with the walks FLATTENED.  In the kernel above every lane walks its own runs, and a loop over
+// The scatter with the walks FLATTENED.  When every lane walks its own runs (the first version, removed), a loop over
 // runs lasts as long as the lane with the most of them: 4.9 runs per thread on average, about 10 for the slowest of
 // 64 lanes, so the two walks (two thirds of the kernel's instructions) run half empty.  Here a lane only LISTS its
 // runs -- one 32-bit item {lane, first window, windows, minimizer position} per record, written into the wave's
@@ -385,7 +258,10 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     cursor += seg << p1_log2;
     start += seg << p1_log2;
   }
-  __shared__ unsigned lh[SK_LH];  // as above: counts, then base + rank -- of the 2^13 buckets of the current round
+  // lh[b]: pass 1 counts the tile's records of bucket b; after the reservation it holds the record index at which the
+  // tile's run in that bucket starts (the launcher keeps indices below SK_NOFIT) and pass 2's atomic add hands out
+  // base + rank in one step
+  __shared__ unsigned lh[SK_MAX_P1];
   // every thread's first word; its second is the next lane's first, and a wave keeps the second word of its last lane
   // itself (pass 1 runs between wave barriers only: a wave must not read what another wave writes)
   __shared__ u64 pk_x[SKQ_SUBT][SKQ_WAVES][65];
@@ -395,10 +271,8 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   __syncthreads();
   if (s_abort) return;  // the regions do not fit the buffers: nothing may be written
   unsigned spilled = 0;
-  constexpr int NB = SK_LH / SKQ_THREADS;
+  constexpr int NB = SK_MAX_P1 / SKQ_THREADS;
   const unsigned p1 = 1u << p1_log2;
-  const unsigned lhn = p1 < (unsigned)SK_LH ? p1 : (unsigned)SK_LH;  // counters in use
-  const unsigned nround = p1 / lhn;                                  // 1, or 2 with 2^14 buckets
   const size_t seq_len = info->seq_len;
   const int lane = threadIdx.x & 63;
   // (the wave's number, computed again at every use from an empty asm: kept in a register -- with the queue and word-row
@@ -406,7 +280,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   // and loaded back once per sub-tile)
 #define wv sk_wave_id()
   auto sk_wave_id = [&]() { int w = (int)threadIdx.x; asm volatile("" : "+v"(w)); return w >> 6; };
-  for (unsigned i = threadIdx.x; i < lhn; i += blockDim.x) lh[i] = 0;
+  for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) lh[i] = 0;
   __syncthreads();
   u64 tA = 0, tB = 0, tC = 0, tD = 0, tE = 0, tF = 0, t0 = 0, ntile = 0;
   (void)tA; (void)tB; (void)tC; (void)tD; (void)tE; (void)tF; (void)t0; (void)ntile;
@@ -462,7 +336,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
 #else
             const unsigned b = sk_bucket(mm, p1_log2);
 #endif
-            if ((b >> SK_LH_LOG2) == 0) atomicAdd(&lh[b & (SK_LH - 1)], 1u);  // (round 0's buckets: counted as they are found)
+            atomicAdd(&lh[b], 1u);
             myq[i] = (it & 0xFFFFu) | (b << 16);
           }
         }
@@ -470,50 +344,24 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
       } else {
         if (p0 < seq_len)
           sk_walk(runs, ww0, ww1, nkmax, CANON, [&](int, int, unsigned mm) {
-            const unsigned b = sk_bucket(mm, p1_log2);
-            if ((b >> SK_LH_LOG2) == 0) atomicAdd(&lh[b & (SK_LH - 1)], 1u);
+            atomicAdd(&lh[sk_bucket(mm, p1_log2)], 1u);
           });
         qn[st] = SKQ_WALKED;
-      }
-    }
-    // A tile's records are placed in rounds of 2^13 buckets (one round unless the chunk is cut into 2^14): count the
-    // round's records per bucket (round 0: done above), reserve their runs, store them, clear the counters.
-#pragma unroll 1
-    for (unsigned round = 0; round < nround; ++round) {
-    SkCursor* const rcursor = cursor + (size_t)round * SK_LH;
-    const u64* const rstart = start + (size_t)round * SK_LH;
-    if (round) {
-#pragma unroll
-      for (int st = 0; st < SKQ_SUBT; ++st) {
-        if (qn[st] != SKQ_WALKED) {
-          const unsigned total = qn[st];
-          const unsigned* const myq = queue[st][wv];
-          for (unsigned base = 0; base < total; base += 64) {
-            const unsigned i = base + lane;
-            if (i < total) {
-              const unsigned b = myq[i] >> 16;
-              if ((b >> SK_LH_LOG2) == round) atomicAdd(&lh[b & (SK_LH - 1)], 1u);
-            }
-          }
-        } else {
-          const size_t t = (tile * SKQ_SUBT + st) * SKQ_THREADS + threadIdx.x;
-          const size_t p0 = t * SK_R;
-          if (p0 < seq_len) {
-            const ulonglong2 w = make_ulonglong2(pk_x[st][wv][lane], pk_x[st][wv][lane + 1]);
-            const SkRuns runs = sk_analyse<W>(w.x, w.y, sk_valid32(bad_window(bad, p0), k), CANON);
-            sk_walk(runs, w.x, w.y, nkmax, CANON, [&](int, int, unsigned mm) {
-              const unsigned b = sk_bucket(mm, p1_log2);
-              if ((b >> SK_LH_LOG2) == round) atomicAdd(&lh[b & (SK_LH - 1)], 1u);
-            });
-          }
-        }
       }
     }
     STAMP_ADD(tA, t0);
     __syncthreads();
     STAMP_ADD(tB, t0);
+    // (the regions are addressed from an offset that passes an empty asm once per tile -- zero: otherwise the compiler
+    // computes the reservations' addresses ahead of the tile loop and spills them under the kernel's 128 registers)
+    unsigned roff = 0;
+    asm volatile("" : "+s"(roff));
+    SkCursor* const rcursor = cursor + roff;
+    const u64* const rstart = start + roff;
+    SkCursor* const rshared_cursor = shared_cursor + roff;
+    const u64* const rshared_start = shared_start + roff;
 #ifndef SK_PLAIN_CURSORS
-    if (lhn == SK_LH) {  // (8192 buckets, 8 per thread: all reservations in flight together, mk_skmer_dev.h)
+    if (p1 == SK_MAX_P1) {  // (8192 buckets, 8 per thread: all reservations in flight together, mk_skmer_dev.h)
       static_assert(NB % 8 == 0, "sk_reserve8");
 #pragma unroll
       for (int h = 0; h < NB; h += 8) {  // (512 threads: buckets 0..4095, then 4096..8191)
@@ -535,8 +383,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
               for (unsigned q = 0; q < pad; ++q) part[end - pad + q] = make_ulonglong2(0, 0);
             }
           }
-          nofit = sk_reserve8<SKQ_THREADS>(v2, shared_cursor + (size_t)round * SK_LH + h * SKQ_THREADS,
-                                           shared_start + (size_t)round * SK_LH + h * SKQ_THREADS, SK_NOFIT, at2);
+          nofit = sk_reserve8<SKQ_THREADS>(v2, rshared_cursor + h * SKQ_THREADS, rshared_start + h * SKQ_THREADS, SK_NOFIT, at2);
 #pragma unroll
           for (int i = 0; i < 8; ++i) at[i] = v2[i] ? at2[i] : at[i];
         }
@@ -547,7 +394,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     } else
 #endif
     {  // (fewer buckets than the most -- small chunks: a plain loop, one bucket at a time)
-      for (unsigned b = threadIdx.x; b < lhn; b += SKQ_THREADS) {
+      for (unsigned b = threadIdx.x; b < p1; b += SKQ_THREADS) {
         const unsigned v = lh[b];
         u64 r = v ? (u64)atomicAdd(&rcursor[b], v) : 0ull;
 #ifdef SK_ABL_COARSE
@@ -556,8 +403,8 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
         bool fits = v == 0 || r + v <= rstart[b + 1];
         if (!fits && nseg > 1) {  // (the bucket's shared region; what was free at the end of the XCD's: empty records, as above)
           for (u64 q = r; q < rstart[b + 1]; ++q) part[q] = make_ulonglong2(0, 0);
-          r = (u64)atomicAdd(&shared_cursor[b], v);
-          fits = r + v <= shared_start[b + 1];
+          r = (u64)atomicAdd(&rshared_cursor[b], v);
+          fits = r + v <= rshared_start[b + 1];
         }
 #endif
         spilled |= fits ? 0u : 1u;
@@ -574,18 +421,13 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
         const unsigned* const myq = queue[st][wv];
         for (unsigned base = 0; base < total; base += 64) {
           const unsigned i = base + lane;
-          if (i < total && ((myq[i] >> 16) >> SK_LH_LOG2) == round) {
+          if (i < total) {
             const unsigned it = myq[i];
-            const unsigned at = atomicAdd(&lh[(it >> 16) & (SK_LH - 1)], 1u);  // base + rank
+            const unsigned at = atomicAdd(&lh[it >> 16], 1u);  // base + rank
             const u64* const wp = &pk_x[st][wv][it & 63u];
             ulonglong2 rec = sk_make_record(wp[0], wp[1], (int)((it >> 6) & 31u), (int)((it >> 11) & 31u), k);
             asm volatile("" : "+v"(rec.x), "+v"(rec.y));  // (built while the LDS answers)
-#ifdef SK_NT_STORE  // (timing experiment: streaming stores -- no L2 allocation for the record lines)
-            typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-            if (at < SK_NOFIT) __builtin_nontemporal_store(u64x2_t{rec.x, rec.y}, (u64x2_t*)&part[(size_t)at]);
-#else
             if (at < SK_NOFIT) part[(size_t)at] = rec;
-#endif
           }
         }
       } else {
@@ -595,9 +437,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
           const ulonglong2 w = make_ulonglong2(pk_x[st][wv][lane], pk_x[st][wv][lane + 1]);
           const SkRuns runs = sk_analyse<W>(w.x, w.y, sk_valid32(bad_window(bad, p0), k), CANON);
           sk_walk(runs, w.x, w.y, nkmax, CANON, [&](int jstart, int nk, unsigned mm) {
-            const unsigned b = sk_bucket(mm, p1_log2);
-            if ((b >> SK_LH_LOG2) != round) return;
-            const unsigned at = atomicAdd(&lh[b & (SK_LH - 1)], 1u);
+            const unsigned at = atomicAdd(&lh[sk_bucket(mm, p1_log2)], 1u);
             if (at < SK_NOFIT) part[(size_t)at] = sk_make_record(w.x, w.y, jstart, nk, k);
           });
         }
@@ -605,10 +445,9 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     }
     STAMP_ADD(tE, t0);
     __syncthreads();
-    for (unsigned i = threadIdx.x; i < lhn; i += blockDim.x) lh[i] = 0;
+    for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) lh[i] = 0;
     __syncthreads();
     STAMP_ADD(tF, t0);
-    }  // rounds of 2^13 buckets
   }
 #ifdef MK_STAMP
   if (threadIdx.x == 0 && blockIdx.x < 1024) { u64* d = skq_dbg + (size_t)blockIdx.x * 8; d[0] = tA; d[1] = tB; d[2] = tC; d[3] = tD; d[4] = tE; d[5] = tF; d[6] = ntile; }
@@ -616,40 +455,6 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   if (spilled) atomicOr(&info->part_overflow, 4ull);
 }
 #undef wv
-
-#ifdef SK_EXP_SORT
-// EXPERIMENT (timing only, not in the product build): the records of every bucket sorted by their number of windows,
-// longest first (classes = 8: every length its own class; classes = 2: five windows or more first) -- what a scatter
-// that files records by length class would hand the count kernel.  One workgroup per bucket, counting sort through LDS.
-__global__ __launch_bounds__(256) void mk_sk_expsort_k(ulonglong2* __restrict__ part, const u64* __restrict__ start,
-                                                       const SkCursor* __restrict__ cursor, unsigned p1, int classes) {
-  __shared__ ulonglong2 buf[6144];
-  __shared__ unsigned cnt[64], base[64];
-  for (unsigned b = blockIdx.x; b < p1; b += gridDim.x) {
-    const u64 lo = start[b], n = cursor[b] - start[b];
-    if (n == 0 || n > 6144) continue;
-    if (threadIdx.x < 64) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (u64 i = threadIdx.x; i < n; i += blockDim.x) {
-      const ulonglong2 r = part[lo + i];
-      buf[i] = r;
-      const int nk = (int)(r.y & 63);
-      const int cls = classes == 2 ? (nk >= 5 ? 0 : 1) : (32 - nk);
-      atomicAdd(&cnt[cls], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) { unsigned a = 0; for (int q = 0; q < 64; ++q) { base[q] = a; a += cnt[q]; } }
-    __syncthreads();
-    for (u64 i = threadIdx.x; i < n; i += blockDim.x) {
-      const ulonglong2 r = buf[i];
-      const int nk = (int)(r.y & 63);
-      const int cls = classes == 2 ? (nk >= 5 ? 0 : 1) : (32 - nk);
-      part[lo + atomicAdd(&base[cls], 1u)] = r;
-    }
-    __syncthreads();
-  }
-}
-#endif
 
 // ------------------------------------------------------------------------------ launcher
 
@@ -666,14 +471,13 @@ template <int W, bool CANON>
 static void launch_wc(mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sample_log2, u64 surv_div, u64 part_cap, u64 surv_cap,
                      u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg) {
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  float sigmas = 6.0f;  // MK_SAMPLE_SIGMAS=0 makes the sampled sizes too small on purpose (tests of the exact second pass)
-  if (const char* e = getenv("MK_SAMPLE_SIGMAS")) sigmas = (float)atof(e);
   const size_t threads = div_up(seq_len, SK_R);
   const size_t tiles = div_up(div_up(threads, (size_t)1 << sample_log2), SK_HIST_THREADS);
-  const size_t stiles = div_up(threads, (size_t)SK_SCAT_THREADS * SK_SCAT_SUBT);
   // few, long-lived workgroups: each one flushes 2 x p1 global atomics at its end (fewer still for a sample)
   const size_t hist_grid = sample_log2 ? SK_HIST_GRID / 2 : SK_HIST_GRID;
   if (!reuse) {  // (reuse: the regions of the previous chunk stand as they are, cursors back at their starts)
+    // MK_SAMPLE_SIGMAS=0 makes the sampled sizes too small on purpose (tests of the exact second pass)
+    const float sigmas = (float)mk_env_double("MK_SAMPLE_SIGMAS", 6.0);
     hipLaunchKernelGGL((mk_sk_hist_k<W, CANON>), dim3((unsigned)(tiles < hist_grid ? tiles : hist_grid)), dim3(SK_HIST_THREADS),
                        2 * sizeof(unsigned) << p1_log2, c->stream,
                        (const u64*)c->codes.p, (const u64*)c->bad.p, info, hist, khist, p1_log2, c->k, nkmax, threads, c->canonical,
@@ -681,32 +485,24 @@ static void launch_wc(mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sam
     mk_launch_sk_scan(c, (const u64*)hist, (const u64*)khist, start, cursor, kstart, p1_log2, sample_log2, nkmax, surv_div, part_cap,
                       surv_cap, sigmas, nseg);
   }
-  static const bool walked = getenv("MK_SCATTER_WALK") != nullptr;  // (the per-lane walks of the first version, for A/B runs)
   // three sub-tiles when the lanes of the chunk before listed few enough records for the shorter queues (mean + 3 sigma
   // of a wave's total under 376: sigma ~ 2 per lane); MK_SKQ_SUBT=2|3 forces a shape
-  const int force_subt = getenv("MK_SKQ_SUBT") ? atoi(getenv("MK_SKQ_SUBT")) : 0;
+  const long long force_subt = mk_env_int("MK_SKQ_SUBT", 0);
   const bool three = force_subt == 3 || (force_subt != 2 && c->items_hint > 0 && c->items_hint * 64.0 + 48.0 < 376.0);
   unsigned qcap = three ? 376u : 512u;
-  if (const char* e = getenv("MK_SKQ_CAP")) { const int v = atoi(e); if (v >= 0 && (unsigned)v < qcap) qcap = (unsigned)v; }
-  if (walked)
-    hipLaunchKernelGGL((mk_sk_scatter_k<W, CANON>), dim3((unsigned)(stiles < SK_SCAT_GRID ? stiles : SK_SCAT_GRID)), dim3(SK_SCAT_THREADS), 0,
-                       c->stream, (const u64*)c->codes.p, (const u64*)c->bad.p, info, (const u64*)start, cursor,
-                       (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, stiles, c->canonical);
-  else {
-    const size_t qtiles = div_up(threads, (size_t)SKQ_THREADS * (three ? 3 : 2));
-    const dim3 qgrid((unsigned)(qtiles < SK_SCAT_GRID ? qtiles : SK_SCAT_GRID));
-    if (three)
-      hipLaunchKernelGGL((mk_sk_scatterq_k<W, CANON, 3, 376>), qgrid, dim3(SKQ_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                         (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg);
-    else
-      hipLaunchKernelGGL((mk_sk_scatterq_k<W, CANON, 2, 512>), qgrid, dim3(SKQ_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                         (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg);
-  }
+  { const long long v = mk_env_int("MK_SKQ_CAP", -1); if (v >= 0 && (unsigned long long)v < qcap) qcap = (unsigned)v; }
+  const size_t qtiles = div_up(threads, (size_t)SKQ_THREADS * (three ? 3 : 2));
+  const dim3 qgrid((unsigned)(qtiles < SK_SCAT_GRID ? qtiles : SK_SCAT_GRID));
+  if (three)
+    hipLaunchKernelGGL((mk_sk_scatterq_k<W, CANON, 3, 376>), qgrid, dim3(SKQ_THREADS), 0, c->stream, (const u64*)c->codes.p,
+                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg);
+  else
+    hipLaunchKernelGGL((mk_sk_scatterq_k<W, CANON, 2, 512>), qgrid, dim3(SKQ_THREADS), 0, c->stream, (const u64*)c->codes.p,
+                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg);
 #ifdef MK_STAMP
-  if (!walked) {
+  {
     (void)hipStreamSynchronize(c->stream);
-    const size_t qtiles = div_up(threads, (size_t)SKQ_THREADS * (three ? 3 : 2));
-    const unsigned g = (unsigned)(qtiles < SK_SCAT_GRID ? qtiles : SK_SCAT_GRID);
+    const unsigned g = qgrid.x;
     std::vector<u64> h(8 * 1024);
     (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(skq_dbg), h.size() * 8);
     double a[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -750,9 +546,10 @@ bool mk_sk_partition_canon(int W, mk_ctx* c, size_t seq_len, int p1_log2, int nk
 // size their buckets afresh.  Called once per partition launch (both key widths); true = inherit.
 bool mk_part_inherit(mk_ctx* c, size_t seq_len, int p1_log2, uint64_t min_count, bool sampled, bool exact) {
   if (c->part_cooldown > 0 && !exact) c->part_cooldown -= 1;
-  const bool reuse = c->use_reuse && !exact && sampled && c->part_reuse_ok && !c->part_dirty && c->part_cooldown == 0 &&
+  const bool reuse = !exact && sampled && c->part_reuse_ok && !c->part_dirty && c->part_cooldown == 0 &&
                      p1_log2 == c->part_prev_p1 && (unsigned long long)min_count == c->part_prev_minc &&
-                     seq_len <= c->part_prev_len + c->part_prev_len / 100 && seq_len >= c->part_prev_len - c->part_prev_len / 50;
+                     seq_len <= c->part_prev_len + c->part_prev_len / 100 && seq_len >= c->part_prev_len - c->part_prev_len / 50 &&
+                     !mk_env_set("MK_NO_REUSE");
   if (reuse) c->st.part_reused += 1;
   c->part_dirty = true;  // (until the caller has read the chunk's flags back: process_chunk, process_chunk_fast)
   if (exact) { c->part_reuse_ok = false; c->part_cooldown = 4; }
@@ -767,18 +564,10 @@ bool mk_part_inherit(mk_ctx* c, size_t seq_len, int p1_log2, uint64_t min_count,
 
 int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, bool exact) {
   if (seq_len == 0) return MK_OK;
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
   const int k = c->k;
   // ~1.2K records (~10K windows) per bucket, between 256 and SK_MAX_P1 buckets
-  // MK_CORES=1 (experiment, round 4): half-sized buckets -- up to 2^14 of them -- counted by 512-thread workgroups with
-  // 4096-slot tables (mk_skcount_small.hip: 68-76 KB of LDS, so that two of them, or one and a scatter workgroup of the
-  // other context, share a CU)
-  static const bool cores = getenv("MK_CORES") != nullptr;
-  const int max_log2 = cores ? SK_MAX_P1_LOG2 : SK_LH_LOG2;
-  const size_t bucket_syms = cores ? SK_BUCKET_SYMS / 2 : SK_BUCKET_SYMS;
   int p1_log2 = 8;
-  while (p1_log2 < max_log2 && (seq_len >> p1_log2) > bucket_syms) ++p1_log2;
-  if (const char* e = getenv("MK_P1_LOG2")) { int v = atoi(e); if (v >= 4 && v <= SK_MAX_P1_LOG2) p1_log2 = v; }
+  while (p1_log2 < SK_MAX_P1_LOG2 && (seq_len >> p1_log2) > SK_BUCKET_SYMS) ++p1_log2;
   c->p1_log2 = p1_log2;
   const size_t p1 = (size_t)1 << p1_log2;
   // Runs are cut into records of at most SK_NKMAX windows: the count kernel expands one record per
@@ -786,28 +575,16 @@ int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, boo
   // 8 trades 1.5x more records for 2.7x fewer expansion rounds).
   int nkmax = 62 - k;
   if (nkmax > SK_NKMAX) nkmax = SK_NKMAX;
-  if (const char* e = getenv("MK_NKMAX")) { int v = atoi(e); if (v >= 1 && v <= 31 && v <= 62 - k) nkmax = v; }
+  { const long long v = mk_env_int("MK_NKMAX", 0); if (v >= 1 && v <= 31 && v <= 62 - k) nkmax = (int)v; }
   // Bucket sizes from a 1-in-2^s sample of the analysis threads (big chunks only: the exact histogram
-  // costs as much as the scatter's own analysis). MK_SAMPLE_LOG2=0 turns it off, MK_SAMPLE_MIN moves
-  // the size threshold (tests).
-  int sample_log2 = 0;
-  {
-    int want = 3;
-    size_t min_len = (size_t)8 << 20;
-    if (const char* e = getenv("MK_SAMPLE_LOG2")) { int v = atoi(e); if (v >= 0 && v <= 6) want = v; }
-    if (const char* e = getenv("MK_SAMPLE_MIN")) min_len = (size_t)atoll(e);
-    if (!exact && seq_len >= min_len) sample_log2 = want;
-  }
+  // costs as much as the scatter's own analysis). MK_SAMPLE_MIN moves the size threshold (tests).
+  const int sample_log2 = !exact && seq_len >= (size_t)mk_env_int("MK_SAMPLE_MIN", (long long)8 << 20) ? 3 : 0;
   c->part_sampled = sample_log2 != 0;
   // regions per bucket: one per XCD when the sizes come from a sample (the exact partition keeps one: a bucket's exact
   // size says nothing exact about its eighths); MK_XSEG=0 keeps one everywhere (A/B runs, tests)
-  const bool xseg_on = !(getenv("MK_XSEG") && atoi(getenv("MK_XSEG")) == 0);
-  static const bool walked_env = getenv("MK_SCATTER_WALK") != nullptr;
-  static const bool force_pre = getenv("MK_FORCE_PREFILTER") != nullptr;  // (that count kernel reads one region per bucket)
   // (chunks of up to 1 GiB: the nine regions take room for two records per window, 32 bytes per byte of text -- a sample
   // counted unchunked, -s 0, keeps the single region and its 16)
-  const int nseg = (xseg_on && sample_log2 != 0 && !walked_env && !force_pre && p1_log2 <= SK_LH_LOG2 &&
-                    seq_len <= ((size_t)1 << 30)) ? 9 : 1;
+  const int nseg = (sample_log2 != 0 && seq_len <= ((size_t)1 << 30) && mk_env_int("MK_XSEG", 1) != 0) ? 9 : 1;
   if (nseg != c->part_nseg) c->part_reuse_ok = false;  // (regions of the other layout cannot be inherited)
   c->part_nseg = nseg;
   const bool reuse = mk_part_inherit(c, seq_len, p1_log2, min_count, sample_log2 != 0, exact);
@@ -853,16 +630,7 @@ int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, boo
     return MK_ERR_ARG;
   }
   mk_prof_end(c);
-#ifdef SK_EXP_SORT
-  if (const char* e = getenv("MK_EXP_SORT"))
-    hipLaunchKernelGGL(mk_sk_expsort_k, dim3(2048), dim3(256), 0, c->stream, (ulonglong2*)c->part.p, (const u64*)start, (const SkCursor*)cursor,
-                       (unsigned)p1, atoi(e));
-#endif
-  {
-    const int rc_count = cores ? mk_launch_sk_count_small(c, (const u64*)start, cursor, (const u64*)kstart, nsurv, min_count, nkmax, p1, exact, nseg)
-                               : mk_launch_sk_count(c, (const u64*)start, cursor, (const u64*)kstart, nsurv, min_count, nkmax, p1, exact, nseg);
-    if (rc_count) return rc_count;
-  }
+  if ((rc = mk_launch_sk_count(c, (const u64*)start, cursor, (const u64*)kstart, nsurv, min_count, p1, nseg)) != MK_OK) return rc;
   MK_HIP(hipGetLastError());
   c->surv_regions = 1;
   return MK_OK;

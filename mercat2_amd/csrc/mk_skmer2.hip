@@ -986,20 +986,10 @@ int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bo
   const int k = c->k;
   int p1_log2 = 8;
   while (p1_log2 < SK2_MAX_P1_LOG2 && (seq_len >> p1_log2) > 8192) ++p1_log2;
-  if (const char* e = getenv("MK_P1_LOG2")) { int v = atoi(e); if (v >= 4 && v <= SK2_MAX_P1_LOG2) p1_log2 = v; }
   c->p1_log2 = p1_log2;
   const size_t p1 = (size_t)1 << p1_log2;
   // bucket sizes from a 1-in-8 sample of the analysis threads for big chunks (see mk_skmer.hip)
-  int sample_log2 = 0;
-  float sigmas = 6.0f;
-  {
-    int want = 3;
-    size_t min_len = (size_t)8 << 20;
-    if (const char* e = getenv("MK_SAMPLE_LOG2")) { int v = atoi(e); if (v >= 0 && v <= 6) want = v; }
-    if (const char* e = getenv("MK_SAMPLE_MIN")) min_len = (size_t)atoll(e);
-    if (const char* e = getenv("MK_SAMPLE_SIGMAS")) sigmas = (float)atof(e);
-    if (!exact && seq_len >= min_len) sample_log2 = want;
-  }
+  const int sample_log2 = !exact && seq_len >= (size_t)mk_env_int("MK_SAMPLE_MIN", (long long)8 << 20) ? 3 : 0;
   c->part_sampled = sample_log2 != 0;
   const bool reuse = mk_part_inherit(c, seq_len, p1_log2, min_count, sample_log2 != 0, exact);
   int rc;
@@ -1040,18 +1030,18 @@ int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bo
                        (const u64*)c->bad.p, info, hist, khist, p1_log2, k, threads, sample_log2);
   if (!reuse)
     mk_launch_sk_scan(c, hist, khist, start, cursor, kstart, p1_log2, sample_log2, SK2_NKMAX, surv_div, (u64)part_cap,
-                      (u64)surv_cap, sigmas, 1);
+                      (u64)surv_cap, (float)mk_env_double("MK_SAMPLE_SIGMAS", 6.0), 1);
   if (c->canonical)
     hipLaunchKernelGGL(mk_sk2_scatter_k<true>, sgrid, dim3(SK2_SCAT_THREADS), 0, c->stream, (const u64*)c->codes.p,
                        (const u64*)c->bad.p, info, (const u64*)start, cursor, (Sk2Rec*)c->part.p, p1_log2, k, stiles);
-  else if (getenv("MK_SCATTER_WALK") || part_cap >= SK2_NOFIT)
+  else if (part_cap >= SK2_NOFIT || mk_env_set("MK_SCATTER_WALK"))
     hipLaunchKernelGGL(mk_sk2_scatter_k<false>, sgrid, dim3(SK2_SCAT_THREADS), 0, c->stream, (const u64*)c->codes.p,
                        (const u64*)c->bad.p, info, (const u64*)start, cursor, (Sk2Rec*)c->part.p, p1_log2, k, stiles);
   else {
-    const int force_subt = getenv("MK_SKQ_SUBT") ? atoi(getenv("MK_SKQ_SUBT")) : 0;
+    const long long force_subt = mk_env_int("MK_SKQ_SUBT", 0);
     const bool three = force_subt == 3 || (force_subt != 2 && c->items_hint > 0 && c->items_hint * 64.0 + 48.0 < 376.0);
     unsigned qcap = three ? 376u : 512u;
-    if (const char* e = getenv("MK_SKQ_CAP")) { const int v = atoi(e); if (v >= 0 && (unsigned)v < qcap) qcap = (unsigned)v; }
+    { const long long v = mk_env_int("MK_SKQ_CAP", -1); if (v >= 0 && (unsigned long long)v < qcap) qcap = (unsigned)v; }
     const size_t qtiles = div_up(threads, (size_t)SK2Q_THREADS * (three ? 3 : 2));
     const dim3 qgrid((unsigned)(qtiles < 8192 ? qtiles : 8192));
     if (three)
@@ -1069,9 +1059,9 @@ int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bo
     const unsigned grid = (unsigned)((size_t)ncu < p1 ? (size_t)ncu : p1);
     // the counting pre-filter pays when few keys can reach min_count: min_count well above the mean count of a key,
     // which the chunk before has measured (windows / distinct keys); a sample's first chunk takes the exact kernel
-    static const bool no_pre = getenv("MK_NO_PREFILTER") != nullptr;
-    static const bool force_pre = getenv("MK_FORCE_PREFILTER") != nullptr;
-    const bool pre = !no_pre && min_count >= 2 && (force_pre || (min_count >= 4 && c->dup_known && c->dup_hint * 2.5 < (double)min_count));
+    // (MK_FORCE_PREFILTER: whenever min_count >= 2)
+    const bool pre = min_count >= 2 && ((min_count >= 4 && c->dup_known && c->dup_hint * 2.5 < (double)min_count) ||
+                                        mk_env_set("MK_FORCE_PREFILTER"));
     if (pre && c->canonical)
       hipLaunchKernelGGL(mk_sk2_countp_k<true>, dim3(grid), dim3(SK2C_THREADS), 0, c->stream, (const Sk2Rec*)c->part.p,
                          (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count, (u64*)c->surv_keys.p,

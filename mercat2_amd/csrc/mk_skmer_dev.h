@@ -137,21 +137,11 @@ __device__ __forceinline__ SkRuns sk_analyse(u64 w0, u64 w1, unsigned valid, boo
       // (the hash's low 22 bits on top, bits 6..9 zero.  The register constraint keeps the shift out of the multiply:
       // folded, the multiplier no longer fits 24 bits and the multiply-add becomes a quarter-rate v_mul_lo_u32 + add)
       unsigned h = sk_order_raw(sk_canon_mmer(mm, canon));
-#ifndef SK_MIN_DOUBLING
       asm("" : "+v"(h));
-#endif
       ord[q] = (h << 10) | (unsigned)q;
     }
   }
-#ifdef SK_MIN_DOUBLING  // (A/B: the round-2 form -- two-input minima, widths 1, 2, 4, 8, 16 -- and the folded multiply)
-  constexpr int WB = (W >= 16) ? 16 : (W >= 8) ? 8 : (W >= 4) ? 4 : (W >= 2) ? 2 : 1;
-#pragma unroll
-  for (int step = 1; step < WB; step <<= 1) {
-#pragma unroll
-    for (int q = 0; q + step < NQ; ++q) ord[q] = min(ord[q], ord[q + step]);
-  }
-#else
-  // Sliding minimum over W candidates with three-input minima: the width covered triples (offsets 0, w, 2w) while
+  // Sliding minimum over W candidates with three-input minima (round 2 took two-input minima over widths 1, 2, 4, 8, 16): the width covered triples (offsets 0, w, 2w) while
   // 3w <= W; the last step, in the loop below, closes to exactly W (W <= 22: two rounds at most).
   constexpr int WA = W >= 3 ? 3 : 1, WB = W >= 9 ? 9 : WA;
   if constexpr (W >= 3) {
@@ -163,7 +153,6 @@ __device__ __forceinline__ SkRuns sk_analyse(u64 w0, u64 w1, unsigned valid, boo
     for (int q = 0; q + 8 < NQ; ++q) ord[q] = min(min(ord[q], ord[q + 3]), ord[q + 6]);
   }
   static_assert(W <= 3 * WB, "a third round of minima would be needed");
-#endif
   // static, branch-free: minimizer positions and run starts (first valid window, minimizer
   // moved, or previous window invalid)
   SkRuns r;

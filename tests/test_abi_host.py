@@ -29,6 +29,34 @@ def test_header_and_binding_agree():
     assert declared_functions() == sorted(native.ABI_SYMBOLS)
 
 
+CSRC = ROOT / "mercat2_amd" / "csrc"
+
+
+def _native_sources():
+    return {p.name: p.read_text() for p in sorted(CSRC.iterdir()) if p.suffix in (".hip", ".h", ".cpp")}
+
+
+def test_environment_switches_are_the_documented_list():
+    """Every MK_* name the native sources read from the environment is listed in DESIGN section 8e, and nothing else
+    is; every read names its switch literally (through mk_env.h, or getenv for the one string)."""
+    read = set()
+    for name, text in _native_sources().items():
+        read |= set(re.findall(r'\b(?:getenv|mk_env_set|mk_env_int|mk_env_double)\("(MK_[A-Z0-9_]+)"', text))
+        if name != "mk_env.h":
+            assert not re.findall(r'\bgetenv\((?!"MK_)', text), name
+    design = (ROOT / "DESIGN.md").read_text()
+    section = design.split("### 8e.")[1].split("\n### ")[0]
+    assert read == set(re.findall(r"`(MK_[A-Z0-9_]+)`", section))
+
+
+def test_no_environment_read_is_cached_in_a_static():
+    """Tests set the switches between calls of one process: a static initialised from the environment would keep the
+    value of the first call.  (The gz decoder's block pool reads MK_POOL_BYTES in its constructor, once per process.)"""
+    for name, text in _native_sources().items():
+        for m in re.finditer(r"\bstatic\b[^;{}()]*=[^;]*;", text):
+            assert not re.search(r"\b(?:getenv|mk_env_\w+)\s*\(", m.group(0)), (name, m.group(0))
+
+
 def test_library_exports_every_declared_symbol():
     lib = native.lib()
     for name in declared_functions():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/ab_env.sh <rounds> "<bench args>" "ENV=1" ...   (GPU box) -- like ab_interleaved.sh, but the variants are
-# environment settings of the product library ("-" = none), e.g. tools/ab_env.sh 4 "--steps 10" - MK_SCATTER_WALK=1
+# environment settings of the product library ("-" = none), e.g. tools/ab_env.sh 4 "--steps 10" - MK_XSEG=0
 rounds=$1; args=$2; shift 2
 declare -A best
 for ((r = 0; r < rounds; ++r)); do

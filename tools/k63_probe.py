@@ -1,5 +1,5 @@
 """Per-kernel-family HIP-event times of one context over S3-shaped chunks (100 MiB of 150-bp reads from a 50 Mbp genome,
-k=63, -c 10): partition and count kernel of the two-word path; MK_NO_PREFILTER=1 / MK_FORCE_PREFILTER=1 for A/B runs.
+k=63, -c 10): partition and count kernel of the two-word path; MK_FORCE_PREFILTER=1 for A/B runs.
 python tools/k63_probe.py [chunks] [genome] [min_count]"""
 import sys
 from pathlib import Path
