@@ -252,6 +252,17 @@ int mk_write_merged_tsv_as_reference(mk_ctx* const* ctxs, int n, const char* con
  * "sample\t<k-mer>\t...\n", then "<names[s]>\t<count>...\n" per sample.  The reference orders the k-mer columns
  * as a Python set iterates (not reproducible); here they are in sorted(str) order.  *rows = k-mer columns. */
 int mk_write_merged_tsv_t(mk_ctx* const* ctxs, int n, const char* const* names, const char* path, size_t* rows);
+/* ---- sample PCA (MerCat2 -pca, lib/mercat2_figures.py:206-291): the exact Gram matrix the host centres and
+ *      decomposes (mercat2_amd/pca.py) ------------------------------------------------------------------------ */
+/* Exact Gram matrix of n samples' count columns over the union of their k-mers (X X^T, X = the table
+ * mk_merged_export gives without as_reference).  gram: n*n pairs of uint64 {lo, hi} (128-bit), row-major.
+ * Same k, alphabet and canonical mode; contexts on any devices (joined on ctxs[0]'s device); 1 <= n <= 4096.
+ * slab_rows: cap on the union rows held on the device at once (0 = pick from free memory).
+ * *rows = union rows (n_features). */
+int mk_gram(mk_ctx* const* ctxs, int n, size_t slab_rows, uint64_t* gram, size_t* rows);
+/* The same for a dense rows x n uint64 matrix in host memory (row-major, as mk_merged_export returns it).
+ * Errors: mk_last_error(NULL). */
+int mk_gram_matrix(int device, const uint64_t* matrix, size_t rows, int n, uint64_t* gram);
 /* ---- alpha diversity of a sample: the moments of its count column (lib/mercat2_diversity.py:13-53
  *      computes nine scikit-bio metrics from exactly these), reduced on the GPU ------------------ */
 typedef struct mk_alpha_t {

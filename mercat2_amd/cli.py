@@ -7,9 +7,11 @@ FASTA (nucleotide or protein; plain or .gz); nucleotide inputs go through remove
 written after counting.  FASTQ input (.fq, .fastq, plain or .gz) is taken with -skipclean: MerCat2 then
 converts it with fq2fa only (lib/mercat2_fasta.py:175-198) into clean/<base>.fna.gz and counts that as a
 nucleotide sample; here the GPU counts the raw reads the same way while the file is written.  Without
--skipclean MerCat2 trims the reads with fastp first, a tool this engine does not run: refused.  FASTQ QC,
-ORF calling (-prod / -fgs), reports, PCA and plots belong to the reference's other layers: their flags are
-accepted where they change nothing here (-lowmem, -pca, -debug, -category_file) and refused with a clear
+-skipclean MerCat2 trims the reads with fastp first, a tool this engine does not run: refused.  With -pca and
+more than three samples of a type, pca_<type>/pca.tsv is computed from the tables still on the GPU
+(bin/mercat2.py:170-181, lib/mercat2_figures.py:206-291; mercat2_amd/pca.py): exact PCA, no plots.  FASTQ QC,
+ORF calling (-prod / -fgs), reports and plots belong to the reference's other layers: their flags are
+accepted where they change nothing here (-lowmem, -debug, -category_file) and refused with a clear
 message where the run would need that layer's output (-prod, -fgs).
 """
 from __future__ import annotations
@@ -49,8 +51,12 @@ def parseargs(argv=None):
     # flags of the reference's other layers (bin/mercat2.py:45-58)
     p.add_argument("-prod", action="store_true", help="(MerCat2: ORF calling with prodigal) not part of this engine")
     p.add_argument("-fgs", action="store_true", help="(MerCat2: ORF calling with FragGeneScanRs) not part of this engine")
-    p.add_argument("-lowmem", action="store_true", help="(MerCat2: incremental PCA) accepted, no effect: no PCA here")
-    p.add_argument("-pca", action="store_true", help="(MerCat2: PCA plots) accepted, no effect")
+    p.add_argument("-lowmem", action="store_true",
+                   help="(MerCat2: incremental PCA beyond 1000 samples) accepted, no effect: the PCA here is exact, and is not "
+                        "computed for more than 1000 samples")
+    p.add_argument("-pca", action="store_true",
+                   help="write pca_<type>/pca.tsv (three principal components per sample, exact PCA) for every sample type "
+                        "with more than 3 samples; no plots")
     p.add_argument("-debug", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("-category_file", type=str, required=False, help=argparse.SUPPRESS)
     p.add_argument("-gpus", type=int, default=None,
@@ -333,6 +339,9 @@ def main(argv=None) -> int:
                     print(f"Note: {stem}.tsv has {rows} rows, the samples hold {union_rows} different k-mers: MerCat2's merge_tsv "
                           f"leaves out or misplaces k-mers that not all samples share; {stem}_T.tsv is the full table, and "
                           f"-union writes {stem}.tsv that way too")
+                if args.pca:  # bin/mercat2.py:170-181, from the tables still on the GPU
+                    from .pca import cli_pca
+                    cli_pca(tables, out, "Nucleotide" if kind == "nucleotide" else "protein")
         finally:
             for t in tables.values():
                 t.close()

@@ -115,6 +115,7 @@ extern "C" int mk_device_count(void) {
 }
 
 extern "C" const char* mk_last_error(const mk_ctx* c) { return c ? c->err.c_str() : g_err.c_str(); }
+void mk_set_global_error(const std::string& msg) { g_err = msg; }  // (mk_gram.hip: calls without a context)
 
 extern "C" int mk_words_per_key(const mk_ctx* c) { return c ? (c->mode == MK_MODE_HASH128 ? 2 : 1) : 0; }
 

@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "mk_owner_bounds", "mk_plan_contexts", "mk_bucket_rows_device", "mk_import_rows_device", "mk_merge_devices",
     "mk_export_size_multi", "mk_export_multi", "mk_write_tsv_multi", "mk_record_cuts", "mk_sample_keys", "mk_dense_bins_device",
     "mk_device_count", "mk_reset_for", "mk_textwrap", "mk_set_clean", "mk_clean_stats", "mk_clean_runs",
-    "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa",
+    "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
 ]
 MK_ABI = 4  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -200,6 +200,8 @@ def lib() -> C.CDLL:
         "mk_export_size_multi": (C.c_int, [C.POINTER(vp), C.c_int, szp]),
         "mk_export_multi": (C.c_int, [C.POINTER(vp), C.c_int, u8p, u64p, C.c_size_t]),
         "mk_write_tsv_multi": (C.c_int, [C.POINTER(vp), C.c_int, C.c_char_p, C.c_char_p, szp]),
+        "mk_gram": (C.c_int, [C.POINTER(vp), C.c_int, C.c_size_t, u64p, szp]),
+        "mk_gram_matrix": (C.c_int, [C.c_int, u64p, C.c_size_t, C.c_int, u64p]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -494,6 +496,39 @@ def write_merged_tsv_T(ctxs: Sequence["Counter"], names: Sequence[str], path) ->
     rows = C.c_size_t(0)
     ctxs[0]._check(L.mk_write_merged_tsv_t(arr, len(ctxs), cn, os.fsencode(str(path)), C.byref(rows)))
     return rows.value
+
+
+def _gram_ints(g: np.ndarray, n: int) -> list:
+    """n x n nested lists of Python ints from n*n {lo, hi} uint64 pairs."""
+    g = g.reshape(n, n, 2)
+    return [[int(g[i, j, 0]) | (int(g[i, j, 1]) << 64) for j in range(n)] for i in range(n)]
+
+
+def gram(ctxs: Sequence["Counter"], slab_rows: int = 0) -> Tuple[list, int]:
+    """mk_gram: (G, rows): the exact Gram matrix X X^T (n x n nested lists of Python ints) of the samples' count
+    columns over the union of their k-mers (X = merged_export's matrix, transposed), and the number of union rows.
+    ``slab_rows`` caps the union rows held on the device at once (0: from free memory)."""
+    n = len(ctxs)
+    g = np.zeros(2 * n * n, dtype=np.uint64)
+    rows = C.c_size_t(0)
+    rc = lib().mk_gram(_ctx_array(ctxs), n, int(slab_rows), g.ctypes.data, C.byref(rows))
+    if rc:
+        ctxs[0]._check(rc)
+    return _gram_ints(g, n), rows.value
+
+
+def gram_matrix(matrix: np.ndarray, device: int = 0) -> list:
+    """mk_gram_matrix: the exact X^T X (n x n nested lists of Python ints) of a dense rows x n count matrix."""
+    m = np.ascontiguousarray(matrix, dtype=np.uint64)
+    if m.ndim != 2 or m.shape[1] < 1:
+        raise ValueError("gram_matrix: a rows x n matrix with n >= 1 is needed")
+    n = m.shape[1]
+    g = np.zeros(2 * n * n, dtype=np.uint64)
+    L = lib()
+    rc = L.mk_gram_matrix(int(device), m.ctypes.data if m.size else None, m.shape[0], n, g.ctypes.data)
+    if rc:
+        raise MercatHipError(rc, (L.mk_last_error(None) or b"").decode())
+    return _gram_ints(g, n)
 
 
 def synth_reads(genome_len: int, genome_seed: int, reads: int, read_len: int, read_seed: int,
