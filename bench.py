@@ -16,10 +16,16 @@ bin/mercat2.py:119-127,336-339):
                    indices), then the ranks merge their tables;
   --scaling strong the 16 chunks of the ONE S2 sample are dealt chunk i -> rank i mod N,
                    every rank filters its own chunks, then the ranks merge.
-  The other mode is timed after the main region and reported under "also".
+  With --full, the other mode is timed after the main region and reported under "also".
   Launched by torch.distributed.run (RANK/WORLD_SIZE in the environment) or by itself: with
   --gpus N > 1 and no RANK set, this process starts N children (before anything here touches the
   GPU) and prints rank 0's line.  "ranks_seen" is an all_reduce of ones, "rccl" says the backend.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line; every figure on
+it comes from the timed steps.  --full then runs everything else the benchmark measures or checks: the
+comparison with the reference's table (verified_rows / _sum / _digest, exit 1 on a mismatch),
+roofline.one_context and roofline.measured_stream_copy, "also", "configs", file_to_tsv, cpu_baseline
+and, for N > 1 ranks, "also_single_process".
 
 Extra objects on the JSON line:
   roofline     dominant kernel = the LDS count kernel; achieved = algorithmic bytes per launch
@@ -28,10 +34,10 @@ Extra objects on the JSON line:
                measured with HIP events on the engine's stream; peak = 8 TB/s HBM3E.  `stage_*`
                repeat the calculation for the whole counting stage (partition + count kernels, + the
                0.25 B per symbol packed read).
-  cpu_baseline the CPU oracle (Python restatement of the reference, oracle/cpu_ref.py) timed on
+  cpu_baseline (--full) the CPU oracle (Python restatement of the reference, oracle/cpu_ref.py) timed on
                this box's host cores on a bounded sample of the same reads (one real S2 chunk
                split over the processes).
-  file_to_tsv  the reference's `Time to count` window (bin/mercat2.py:335-346): the S2 sample as a
+  file_to_tsv  (--full) the reference's `Time to count` window (bin/mercat2.py:335-346): the S2 sample as a
                file in the page cache -> TSV closed, through harness.run_sample; plain and .gz.
 
 --dump-outputs DIR writes the table the last timed step exported (keys, counts) as float64 .npy files, so
@@ -263,13 +269,16 @@ def main():
     ap.add_argument("--no-share", action="store_true",
                     help="every context sums its chunks' survivors into a table of its own (as up to round 3) instead of the "
                          "contexts of a GPU sharing the first one's (mk_share_table)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need (see the module docstring); "
+                         "the --no-* options below skip parts of it")
     ap.add_argument("--no-single-leg", action="store_true",
-                    help="N > 1, one process per GPU: do not run the one-process product path (mk_merge_devices) in a fresh child afterwards")
+                    help="--full, N > 1, one process per GPU: do not run the one-process product path (mk_merge_devices) in a fresh child afterwards")
     ap.add_argument("--cpu-cores", type=int, default=0, help="processes of the cpu_baseline leg (default: the physical cores available)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short runs of the other BASELINE configs after the main region")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-file-leg", action="store_true", help="skip the file-to-TSV leg")
-    ap.add_argument("--no-also", action="store_true", help="N > 1: do not time the other scaling mode after the main region")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the short runs of the other BASELINE configs after the main region")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-file-leg", action="store_true", help="--full: skip the file-to-TSV leg")
+    ap.add_argument("--no-also", action="store_true", help="--full, N > 1: do not time the other scaling mode after the main region")
     ap.add_argument("--canonical", action="store_true",
                     help="count min(kmer, reverse complement) (BASELINE config 3 names it; an opt-in extension, not the "
                          "reference's forward-strand behaviour -- the default run keeps that)")
@@ -505,7 +514,7 @@ def main():
     # from the reference's own Chunker + find_kmers): rows, sum of counts, sha256 of the concatenated keys and of the counts
     golden = {}
     try:
-        gj = json.loads((ROOT / "tests" / "golden" / "expected_s2.json").read_text())
+        gj = json.loads((ROOT / "tests" / "golden" / "expected_s2.json").read_text()) if args.full else {}
         for name, wl in (("S2|k31|c10|s100", (READS, GENOME, K, GENOME_SEED, READ_SEED)),
                          ("S1|k21|c10|s100", (1_000_000, 1_000_000, 21, 1, 2)),
                          ("S3|k63|c10|s100", (50_000_000, 50_000_000, 63, 6, 7))):
@@ -568,15 +577,18 @@ def main():
         per_rank = [None] * world
         with torch.cuda.device(dev):
             dist.all_gather_object(per_rank, mine)
-    verified = verify_rows(total_rows, mode, args.reads, args.genome, k, args.sub_ppm, canonical, args.genome_seed, args.read_seed)
-    verified_table = verify_table(eng, mode, args.reads, args.genome, k, args.sub_ppm, canonical, args.genome_seed, args.read_seed) if rank == 0 else None
-    if verified_table is not None and not all(verified_table.values()):
-        verified = False
+    # ---- --full only from here to the line: checks and measurements the headline figure does not need
+    verified, verified_table = None, None
+    if args.full:
+        verified = verify_rows(total_rows, mode, args.reads, args.genome, k, args.sub_ppm, canonical, args.genome_seed, args.read_seed)
+        verified_table = verify_table(eng, mode, args.reads, args.genome, k, args.sub_ppm, canonical, args.genome_seed, args.read_seed) if rank == 0 else None
+        if verified_table is not None and not all(verified_table.values()):
+            verified = False
 
     # After the timed region: the same kernels alone on the GPU (one context, one pass), so that the
     # dominant kernel's duration can also be read without the other stream's kernels on its CUs.
     solo = None
-    if nctx > 1 and rank == 0:
+    if args.full and nctx > 1 and rank == 0:
         c = eng.all[0]
         c.reset()
         c.reset_stats()
@@ -589,7 +601,7 @@ def main():
 
     # the other scaling mode, timed after the main region (N > 1 only)
     also = None
-    if ngpu > 1 and not args.no_also:
+    if args.full and ngpu > 1 and not args.no_also:
         other_mode = "strong" if mode == "weak" else "weak"
         del parts
         parts2, nchunks2, total2, _ = load_sample(other_mode, args.reads, args.genome, args.genome_seed, args.read_seed, args.sub_ppm)
@@ -606,7 +618,7 @@ def main():
     # config 3 as worded (canonical keys), config 2 (S1: 1 M reads, k=21) and config 5 (S3: 50 M reads, k=63)
     configs = None
     default_run = (args.reads, args.genome, k, args.sub_ppm, canonical) == (READS, GENOME, K, 0, False)
-    if ngpu == 1 and rank == 0 and default_run and not args.no_configs:
+    if args.full and ngpu == 1 and rank == 0 and default_run and not args.no_configs:
         configs = {}
         # (the main engine's contexts go first: HIP spreads a process's streams over a few hardware queues, and with the
         # main engine's two streams still alive the two streams of a leg's engine landed on ONE queue -- their kernels ran
@@ -699,11 +711,6 @@ def main():
             "distinct_kmers_per_s": total_rows * args.steps / dt,
             "distinct_prefilter_per_s": st["distinct"] * world / dt,  # distinct keys per chunk, before the -c filter
             "rows": total_rows,
-            # the rows the REFERENCE gets for this sample (tests/golden/expected_s2.json); null when the run is not that sample
-            "verified_rows": verified,
-            # the table of the last timed step exported once more and compared with the reference's sum and sha256 digests
-            "verified_sum": None if verified_table is None else verified_table["sum"],
-            "verified_digest": None if verified_table is None else verified_table["digest"],
             "kernel_ms_per_step": {n: st["ms_" + n] / args.steps for n in ("parse", "pack", "part", "count", "exotic", "filter", "export")},
             # chunks whose count kernel merged its survivors into the running table itself (no import kernel), and what those set aside
             "fused_chunks_per_step": st["fused_chunks"] / args.steps, "fuse_spilled": st["fuse_spilled"],
@@ -716,7 +723,15 @@ def main():
                          "stage_ms_per_launch": stage_ms, "stage_achieved": stage_achieved,
                          "stage_frac": stage_achieved / HBM_PEAK_GBS},
             "input_gen_s": gen_s,
+            "full": bool(args.full),
         }
+        if args.full:
+            line.update({
+                # the rows the REFERENCE gets for this sample (tests/golden/expected_s2.json); null when the run is not that sample
+                "verified_rows": verified,
+                # the table of the last timed step exported once more and compared with the reference's sum and sha256 digests
+                "verified_sum": None if verified_table is None else verified_table["sum"],
+                "verified_digest": None if verified_table is None else verified_table["digest"]})
         if main_merge_stats:
             line["merge_devices"] = main_merge_stats  # (of the last timed step)
         if also:
@@ -729,28 +744,29 @@ def main():
             # (not `achieved`: that one is measured inside the timed region, where two contexts share the GPU)
             line["roofline"]["one_context"] = {"ms_per_launch": solo_ms, "achieved": solo_ach, "frac": solo_ach / HBM_PEAK_GBS,
                                                "note": "same kernel, untimed extra pass with one context"}
-        # the box's own stream-copy rate beside the nominal peak (1 GiB device-to-device copy, read + write
-        # bytes / time, best of 5, after the timed region)
-        try:
-            src = torch.empty(1 << 28, dtype=torch.int32, device=dev)
-            dst = torch.empty_like(src)
-            best = None
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                dst.copy_(src)
-                e1.record()
-                e1.synchronize()
-                ms = e0.elapsed_time(e1)
-                best = ms if best is None or ms < best else best
-            line["roofline"]["measured_stream_copy"] = 2 * src.numel() * 4 / (best * 1e-3) / 1e9
-            line["roofline"]["frac_of_measured_copy"] = achieved / line["roofline"]["measured_stream_copy"]
-            del src, dst
-        except Exception:  # (a probe, not the product: never fail the bench line over it)
-            line["roofline"]["measured_stream_copy"] = None
-        if ngpu == 1 and not args.no_file_leg:
+        if args.full:
+            # the box's own stream-copy rate beside the nominal peak (1 GiB device-to-device copy, read + write
+            # bytes / time, best of 5, after the timed region)
+            try:
+                src = torch.empty(1 << 28, dtype=torch.int32, device=dev)
+                dst = torch.empty_like(src)
+                best = None
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    dst.copy_(src)
+                    e1.record()
+                    e1.synchronize()
+                    ms = e0.elapsed_time(e1)
+                    best = ms if best is None or ms < best else best
+                line["roofline"]["measured_stream_copy"] = 2 * src.numel() * 4 / (best * 1e-3) / 1e9
+                line["roofline"]["frac_of_measured_copy"] = achieved / line["roofline"]["measured_stream_copy"]
+                del src, dst
+            except Exception:  # (a probe, not the product: never fail the bench line over it)
+                line["roofline"]["measured_stream_copy"] = None
+        if args.full and ngpu == 1 and not args.no_file_leg:
             line["file_to_tsv"] = file_to_tsv_leg(args, k, canonical)
-        if not args.no_cpu and ngpu == 1:
+        if args.full and not args.no_cpu and ngpu == 1:
             chunk_reads = max(1, args.reads // max(1, nchunks))
             line["cpu_baseline"] = cpu_baseline(k, MIN_COUNT, args.genome, args.genome_seed, args.read_seed, chunk_reads, args.cpu_cores)
             line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
@@ -766,7 +782,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not args.no_single_leg:
+        if args.full and world > 1 and not args.no_single_leg:
             # every rank has closed its contexts: the GPUs are idle.  The product's own N-GPU path -- ONE process, chunks
             # dealt to the GPUs through the C ABI, mk_merge_devices -- timed in a fresh child process of this one (never
             # an exec of this process), its line folded in here
@@ -785,7 +801,7 @@ def single_process_leg(args, backend):
     cmd = [sys.executable, str(Path(__file__).resolve()), "--gpus", str(args.gpus), "--single-process", "--steps", str(args.steps),
            "--warmup", "1", "--scaling", args.scaling, "--reads", str(args.reads), "--k", str(args.k), "--genome", str(args.genome),
            "--genome-seed", str(args.genome_seed), "--read-seed", str(args.read_seed), "--sub-ppm", str(args.sub_ppm),
-           "--no-also", "--no-configs", "--no-cpu", "--no-file-leg"]
+           "--full", "--no-also", "--no-configs", "--no-cpu", "--no-file-leg"]
     if args.canonical:
         cmd.append("--canonical")
     if args.contexts > 0:

@@ -82,6 +82,8 @@ def test_bench_dumps_the_table_of_its_last_step(tmp_path):
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["steps"] == 3 and line["ms_per_step"] > 0
+    # a plain run (no --full) measures nothing after its timed steps
+    assert line["full"] is False and "verified_rows" not in line and "measured_stream_copy" not in line["roofline"]
     data = native.synth_reads(genome, bench.GENOME_SEED, reads, bench.READ_LEN, bench.READ_SEED).tobytes()
     with native.Counter(bench.K, native.ALPHABET_NT2, device=0) as ctx:
         ctx.count_chunk(data, bench.MIN_COUNT)

@@ -184,7 +184,7 @@ def test_bench_launches_ranks_and_strong_rows_match(tmp_path):
     import subprocess
     import sys
     from conftest import ROOT
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu", "--no-file-leg", "--reads", "2000000", "--genome", "1000000"]
+    common = ["--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--no-file-leg", "--reads", "2000000", "--genome", "1000000"]
     env = dict(os.environ, MK_BENCH_BACKEND="gloo")
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
@@ -220,7 +220,7 @@ def test_bench_single_process_drives_several_gpus(tmp_path):
     import subprocess
     import sys
     from conftest import ROOT
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu", "--no-file-leg", "--no-configs", "--reads", "2000000", "--genome", "1000000"]
+    common = ["--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--no-file-leg", "--no-configs", "--reads", "2000000", "--genome", "1000000"]
     env = dict(os.environ, MK_BENCH_SHARE_DEVICE="1")
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
