@@ -217,7 +217,9 @@ extern "C" void mk_destroy(mk_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->share_owner) (void)mk_share_table(c, nullptr);
-  for (mk_ctx* s : std::vector<mk_ctx*>(c->sharers)) (void)mk_share_table(s, nullptr);  // (their rows in this table go with it)
+  std::vector<mk_ctx*> sharers;
+  { std::shared_lock<std::shared_mutex> rd(c->table_mu); sharers = c->sharers; }
+  for (mk_ctx* s : sharers) (void)mk_share_table(s, nullptr);  // (their rows in this table go with it)
   for (auto& p : c->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto& e : c->event_pool) (void)hipEventDestroy(e);
   MkDevBuf* all[] = {&c->raw, &c->seq, &c->codes, &c->bad, &c->tile_maps, &c->info, &c->ctab, &c->rtab_chunk, &c->run,
@@ -240,8 +242,8 @@ static int reset_impl(mk_ctx* c, size_t expect_rows) {
   if (c->pending_rows) { MK_HIP(hipStreamSynchronize(c->stream)); c->pending_rows = false; }
   // (a table other contexts launch into: nobody launches while it is cleared, and what was launched has finished.  The
   // ORDER of a sharer's chunks against this reset is the caller's: reset the owner before the sharers count the next sample)
-  std::unique_lock<std::shared_mutex> table_lock(c->table_mu, std::defer_lock);
-  if (!c->sharers.empty()) { table_lock.lock(); drain_table_users(c); }
+  std::unique_lock<std::shared_mutex> table_lock(c->table_mu);
+  if (!c->sharers.empty()) drain_table_users(c);
   if (expect_rows && c->mode != MK_MODE_DENSE) {
     const size_t want = pow2_at_least(4 * expect_rows);
     if (c->run_slots > want) c->run_slots = want;
@@ -404,18 +406,24 @@ extern "C" int mk_share_table(mk_ctx* c, mk_ctx* owner) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     old->sharers.erase(std::remove(old->sharers.begin(), old->sharers.end(), c), old->sharers.end());
+    old->n_sharers = old->sharers.size();
     c->share_owner = nullptr;
     c->fuse_target = nullptr;
   }
   if (!owner) return MK_OK;
-  if (owner->share_owner || !c->sharers.empty()) { c->err = "mk_share_table: tables are shared one level deep (the owner must own its table, a sharer cannot be an owner)"; return MK_ERR_ARG; }
+  if (owner->share_owner || c->n_sharers) { c->err = "mk_share_table: tables are shared one level deep (the owner must own its table, a sharer cannot be an owner)"; return MK_ERR_ARG; }
   if (owner->device != c->device || owner->alphabet != c->alphabet || owner->k != c->k || owner->canonical != c->canonical || owner->mode != c->mode) {
     c->err = "mk_share_table: contexts differ in device, alphabet, k or canonical mode";
     return MK_ERR_ARG;
   }
   if (c->mode != MK_MODE_HASH64) { c->err = "mk_share_table: only one-word hashed tables are shared"; return MK_ERR_ARG; }
+  // (the owner may have plain-store imports in flight, chosen while it had no sharers: they finish before this context
+  // can launch into the table -- mk_launch_import_regions / mk_launch_import_pairs choose under the shared lock)
   std::unique_lock<std::shared_mutex> wr(owner->table_mu);
+  (void)hipSetDevice(owner->device);
+  drain_table_users(owner);
   owner->sharers.push_back(c);
+  owner->n_sharers = owner->sharers.size();
   c->share_owner = owner;
   return MK_OK;
 }
@@ -472,12 +480,12 @@ extern "C" int mk_chunk_feed_device(mk_ctx* c, const uint8_t* d_text, size_t n) 
 static size_t run_slots_for(size_t need_rows) { return pow2_at_least(need_rows * 5 / 2); }
 
 static int grow_run64_body(mk_ctx* c, size_t need_rows);
-// (a table other contexts launch into -- mk_share_table -- is only replaced under its lock, with their streams drained)
+// (the table is only replaced under its lock -- a sharer may attach at any time, mk_share_table -- and with the streams
+// of the contexts that launch into it drained)
 static int grow_run64(mk_ctx* c, size_t need_rows) {
-  if (c->sharers.empty()) return grow_run64_body(c, need_rows);
   std::unique_lock<std::shared_mutex> wr(c->table_mu);
   if (2 * need_rows <= c->run_slots) return MK_OK;
-  drain_table_users(c);
+  if (!c->sharers.empty()) drain_table_users(c);
   return grow_run64_body(c, need_rows);
 }
 static int grow_run64_body(mk_ctx* c, size_t need_rows) {
@@ -587,15 +595,9 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
       const size_t expect = (size_t)c->surv_hint + 4096;
       if (t != c) {
         std::shared_lock<std::shared_mutex> rd(t->table_mu);
-        size_t rows_now;
-        { std::lock_guard<std::mutex> g(t->rows_mu); rows_now = t->run_rows; }
-        if (t->run_slots < 1024 || 2 * (rows_now + expect) > t->run_slots) t = c;
+        if (t->run_slots < 1024 || 2 * (t->run_rows + expect) > t->run_slots) t = c;
       }
-      if (t == c) {
-        size_t rows_now;
-        { std::lock_guard<std::mutex> g(c->rows_mu); rows_now = c->run_rows; }
-        if ((rc = grow_run64(c, rows_now + expect * (1 + c->sharers.size()))) != MK_OK) return rc;
-      }
+      if (t == c && (rc = grow_run64(c, c->run_rows + expect * (1 + c->n_sharers))) != MK_OK) return rc;
       c->fuse_target = t;
       c->fuse_cap = cap;
     }
@@ -655,11 +657,8 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   c->part_dirty = false;  // the count kernel ran to its end: every cursor is back at its region's start
   const bool fused_done = !two && c->fused_last;  // (of the launch that counted: the exact pass is never fused)
   if (fused_done) {
-    {
-      mk_ctx* t = c->fuse_target ? c->fuse_target : c;  // (counted by the kernel, in the same read-back; the table may be another context's)
-      std::lock_guard<std::mutex> g(t->rows_mu);
-      t->run_rows += (size_t)h->new_rows;
-    }
+    mk_ctx* t = c->fuse_target ? c->fuse_target : c;  // (counted by the kernel, in the same read-back; the table may be another context's)
+    t->run_rows += (size_t)h->new_rows;
     h->new_rows = 0;
     c->st.fused_chunks += 1;
     c->st.fuse_spilled += h->spilled;
@@ -707,7 +706,7 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
     fprintf(stderr, "[mk] chunk (one read-back): raw=%zu seq=%zu windows=%llu records=%llu distinct=%llu survivors=%llu p1=2^%d dup=%.2f nk=%.2f fused=%d spilled=%llu rows=%zu slots=%zu\n",
             n, seq_len, (unsigned long long)h->windows, (unsigned long long)h->records, (unsigned long long)h->distinct,
             (unsigned long long)h->survivors, c->p1_log2, c->dup_hint, c->nk_hint, fused_done ? 1 : 0, (unsigned long long)h->spilled,
-            c->run_rows, c->run_slots);
+            (size_t)c->run_rows, c->run_slots);
   c->st.table_slots = c->rtab_chunk_slots;
   c->st.raw_bytes += n;
   c->st.symbols += h->symbols;

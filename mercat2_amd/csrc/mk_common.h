@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
+#include <atomic>
 #include <mutex>
 #include <shared_mutex>
 #include <vector>
@@ -134,7 +135,8 @@ struct mk_ctx {
   // running (merged) tables
   MkDevBuf run;         // same layout as ctab (dense: u64 bins)
   size_t run_slots = 0;
-  size_t run_rows = 0;
+  // (run_rows / run128_rows are atomic: an owner's count is added to by its sharers' host threads -- mk_share_table)
+  std::atomic<size_t> run_rows{0};
   unsigned long long run_side = 0;  // count of the MK_EMPTY-valued key
   MkDevBuf run_ref;     // by-reference running table MkSlot[] (key = tag|arena index)
   size_t run_ref_slots = 0;
@@ -143,7 +145,7 @@ struct mk_ctx {
   size_t arena_rows_cap = 0;
   MkDevBuf run128;      // MkSlot128[]: packed two-word keys (mode MK_MODE_HASH128), u64 counts
   size_t run128_slots = 0;
-  size_t run128_rows = 0;
+  std::atomic<size_t> run128_rows{0};
 
   // partitioned counting (hash64): keys bucketed by hash, counted per bucket in LDS
   MkDevBuf part;        // u64 keys, bucket after bucket
@@ -174,9 +176,9 @@ struct mk_ctx {
   // one table for several contexts of a device (mk_share_table): the fused launches of this context upsert into the owner's
   mk_ctx* share_owner = nullptr;
   mk_ctx* fuse_target = nullptr;      // the context whose table the NEXT / last fused launch of this one upserts into (this or share_owner)
-  std::vector<mk_ctx*> sharers;       // contexts whose fused launches upsert into THIS context's table
+  std::vector<mk_ctx*> sharers;       // contexts whose fused launches upsert into THIS context's table (changed under table_mu)
+  std::atomic<size_t> n_sharers{0};   // sharers.size(), for readers that do not hold table_mu
   std::shared_mutex table_mu;         // shared: a launch reads run.p / run_slots; exclusive: the table is replaced (grown) or cleared
-  std::mutex rows_mu;                 // run_rows of an owner is added to by its sharers' host threads
 
   // export scratch
   MkDevBuf ex_keys, ex_cnts, ex_keys2, ex_cnts2, ex_tmp;

@@ -165,7 +165,10 @@ int mk_launch_import_regions(mk_ctx* c, const uint64_t* d_keys, const uint64_t* 
   // Many survivors per bucket (-c 1, canonical keys: a bucket keeps a thousand keys, each upsert is two dependent
   // round trips to HBM): every bucket gets its own wave at once -- the kernel is bound by requests in flight.
   const unsigned cap = survivors > 64 * p1 ? 4096u : 512u;
-  if (!c->sharers.empty())
+  // (the plain-store form is chosen and enqueued under the table's lock, shared: a context that attaches as a sharer
+  // meanwhile -- mk_share_table, the lock exclusive -- drains this stream before its first launch into the table)
+  std::shared_lock<std::shared_mutex> rd(c->table_mu);
+  if (c->n_sharers)
     hipLaunchKernelGGL(mk_import_regions_k<true>, dim3(grid_for(p1 * 64, 256, cap)), dim3(256), 0, c->stream, (const u64*)d_keys,
                        (const u64*)d_counts, (const u64*)kstart, (const u64*)nsurv, p1, (MkSlot*)c->run.p,
                        (u64)(c->run_slots - 1), &info->new_rows);
@@ -622,7 +625,8 @@ int mk_launch_accumulate(mk_ctx* c, uint64_t min_count) {
 int mk_launch_import_pairs(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows, bool distinct) {
   if (!rows) return MK_OK;
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  if (distinct && c->mode == MK_MODE_HASH64 && c->sharers.empty()) {
+  std::shared_lock<std::shared_mutex> rd(c->table_mu);  // (the plain-store form: see mk_launch_import_regions)
+  if (distinct && c->mode == MK_MODE_HASH64 && !c->n_sharers) {
     hipLaunchKernelGGL(mk_import_pairs_distinct_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, (const u64*)d_keys,
                        (const u64*)d_counts, rows, (MkSlot*)c->run.p, (u64)(c->run_slots - 1), &info->new_rows, &info->side);
     MK_HIP(hipGetLastError());
