@@ -74,6 +74,8 @@ typedef struct mk_stats_t {
   uint64_t fused_chunks; /* chunks whose count kernel put the survivors into the running table itself (ABI 4)        */
   uint64_t fuse_spilled; /* ... survivors of those it set aside instead (table filling up), imported afterwards        */
   uint64_t parse_retries; /* chunks parsed a second time by the general parser (a blank inside a sequence line)           */
+  uint64_t split_exhausted; /* sub-ranges of the LDS count kernels that reached the last split level (every hash bit used):
+                               counted by probing the whole table (ABI 5)                                                     */
 } mk_stats_t;
 
 /* ---- lifetime ------------------------------------------------------------------------- */

@@ -106,7 +106,7 @@ static void prof_collect(mk_ctx* c) {
 // ----------------------------------------------------------------------------- lifetime
 // "mercat_hip <abi>.<minor> (gfx950)": the ABI number changes whenever a struct or a signature of include/mercat_hip.h does
 // (native.py checks it against its own MK_ABI before it trusts the struct layouts)
-extern "C" const char* mk_version(void) { return "mercat_hip 4.1 (gfx950)"; }
+extern "C" const char* mk_version(void) { return "mercat_hip 5.0 (gfx950)"; }
 
 extern "C" int mk_device_count(void) {
   int n = 0;
@@ -264,6 +264,7 @@ static int reset_impl(mk_ctx* c, size_t expect_rows) {
   c->run_ref_rows = 0;
   c->run128_rows = 0;
   c->run_side = 0;
+  c->spoiled = false;
   c->in_chunk = false;
   c->raw_len = 0;
   c->part_reuse_ok = false;  // (a new sample sizes its own bucket regions: nothing is inherited across samples)
@@ -398,6 +399,8 @@ static void drain_table_users(mk_ctx* t) {  // (t->table_mu is held exclusively:
 
 extern "C" int mk_share_table(mk_ctx* c, mk_ctx* owner) {
   if (!c || c == owner) return MK_ERR_ARG;
+  if (owner) { const int rs_ = mk_refuse_spoiled(owner, "mk_share_table"); if (rs_) { c->err = owner->err; return rs_; } }
+  { const int rs_ = mk_refuse_spoiled(c, "mk_share_table"); if (rs_) return rs_; }
   if (c->in_chunk) { c->err = "mk_share_table: a chunk is open"; return MK_ERR_STATE; }
   if (c->share_owner == owner) return MK_OK;
   if (c->share_owner) {  // leave the table it launched into
@@ -431,6 +434,7 @@ extern "C" int mk_share_table(mk_ctx* c, mk_ctx* owner) {
 // ----------------------------------------------------------------------------- chunk feed
 extern "C" int mk_chunk_begin(mk_ctx* c) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_chunk_begin"); if (rs_) return rs_; }
   if (c->in_chunk) { c->err = "mk_chunk_begin: a chunk is already open"; return MK_ERR_STATE; }
   c->in_chunk = true;
   c->raw_len = 0;
@@ -560,6 +564,34 @@ int mk_launch_count_binned(mk_ctx* c, size_t seq_len, uint64_t min_count);
 // (otherwise MK_RETRY_GENERAL), whether symbols outside the alphabet need the by-reference kernel (then it runs
 // now: one more read-back, rare), and how many rows survive; the merge is launched and its row totals are copied
 // back without waiting -- they are added up when the next read-back (or settle()) has passed them.
+// The two-word pre-filter (mk_skmer2.hip mk_sk2_countp_k) met a bucket whose keys share every bit of its hash, which no
+// split tells apart: the chunk is counted again by the exact kernel (as a partition that overflowed is: the fields the
+// partitioned kernels own start from zero; split_exhausted keeps what the pre-filter met).
+static int recount_pre_void(mk_ctx* c, MkChunkInfo* h, size_t seq_len, u64 min_count) {
+  if (!h->pre_void) return MK_OK;
+  if (mk_env_set("MK_VERBOSE")) fprintf(stderr, "[mk] pre-filter could not split %llu bucket(s): exact count\n", h->pre_void);
+  h->windows = h->records = h->distinct = h->survivors = h->side = h->errors = h->part_overflow = h->pre_void = 0;
+  MK_HIP(hipMemcpyAsync(c->info.p, h, sizeof(MkChunkInfo), hipMemcpyHostToDevice, c->stream));
+  int rc = mk_launch_count_superkmer2(c, seq_len, min_count, /*exact=*/true);
+  if (rc) return rc;
+  if ((rc = pull_info(c)) != MK_OK) return rc;
+  if (h->part_overflow || h->pre_void) { c->err = "exact count after the pre-filter overflowed (internal error: nothing was counted)"; return MK_ERR_STATE; }
+  return MK_OK;
+}
+
+// A fused count kernel has upserted part of a chunk that is then refused: that cannot be taken back, so the context (and
+// the table's owner, when the launch went into a shared table) refuses everything but a reset until it gets one.
+static void spoil(mk_ctx* c, mk_ctx* t) {
+  c->spoiled = true;
+  t->spoiled = true;
+  c->err += " -- the running table holds part of the refused chunk: mk_reset before anything else";
+}
+int mk_refuse_spoiled(mk_ctx* c, const char* what) {
+  if (!c->spoiled) return MK_OK;
+  c->err = std::string(what) + ": the running table holds part of a refused chunk (mk_reset first)";
+  return MK_ERR_STATE;
+}
+
 static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_count) {
   int rc;
   const size_t begin = (size_t)((uintptr_t)d_raw & 15);
@@ -650,8 +682,11 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
     if ((rc = pull_info(c)) != MK_OK) return rc;
     if (h->part_overflow) { c->err = "partition overflow after the exact pass (internal error: nothing was counted)"; return MK_ERR_STATE; }
   }
+  if (two && (rc = recount_pre_void(c, h, seq_len, min_count)) != MK_OK) return rc;
+  c->st.split_exhausted += h->split_exhausted;
   if (h->errors) {
     c->err = "counting kernel reported " + std::to_string(h->errors) + " unrecoverable condition(s) (bucket too large to split)";
+    if (!two && c->fused_last) spoil(c, c->fuse_target ? c->fuse_target : c);
     return MK_ERR_RANGE;
   }
   c->part_dirty = false;  // the count kernel ran to its end: every cursor is back at its region's start
@@ -857,6 +892,8 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
     if ((rc = pull_info(c)) != MK_OK) return rc;
     if (c->h_info->part_overflow) { c->err = "partition overflow after the exact pass (internal error: nothing was counted)"; return MK_ERR_STATE; }
   }
+  if (sk2 && (rc = recount_pre_void(c, c->h_info, seq_len, min_count)) != MK_OK) return rc;
+  c->st.split_exhausted += c->h_info->split_exhausted;
   if (c->h_info->errors) {
     c->err = "counting kernel reported " + std::to_string(c->h_info->errors) + " unrecoverable condition(s) (bucket too large to split)";
     return MK_ERR_RANGE;
@@ -933,6 +970,7 @@ extern "C" int mk_chunk_end(mk_ctx* c, uint64_t min_count) {
 
 extern "C" int mk_count_device(mk_ctx* c, const uint8_t* d_text, size_t n, uint64_t min_count) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_count_device"); if (rs_) return rs_; }
   if (c->in_chunk) { c->err = "mk_count_device: a chunk is open"; return MK_ERR_STATE; }
   if (n && !d_text) { c->err = "mk_count_device: d_text is NULL"; return MK_ERR_ARG; }
   if (c->fastq_mode) { c->err = "mk_count_device: FASTQ mode rewrites the text in place: feed it (mk_chunk_feed_device)"; return MK_ERR_STATE; }
@@ -1182,6 +1220,7 @@ extern "C" int mk_export_stats(mk_ctx* c, mk_export_stats_t* out) {
 
 extern "C" int mk_export_size(mk_ctx* c, size_t* rows) {
   if (!c || !rows) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_export_size"); if (rs_) return rs_; }
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (c->mode == MK_MODE_DENSE) {
     ExportView v;
@@ -1198,6 +1237,7 @@ extern "C" int mk_export_size(mk_ctx* c, size_t* rows) {
 
 extern "C" int mk_export(mk_ctx* c, uint8_t* kmers, uint64_t* counts, size_t rows_cap) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_export"); if (rs_) return rs_; }
   ExportView v;
   int rc = build_view(c, v);
   if (rc) return rc;
@@ -1322,6 +1362,7 @@ static int write_tsv_from_device(mk_ctx* c, const char* path, const char* basena
 
 extern "C" int mk_write_tsv(mk_ctx* c, const char* path, const char* basename, size_t* rows_out) {
   if (!c || !path || !basename) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_write_tsv"); if (rs_) return rs_; }
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (c->mode != MK_MODE_BYREF && c->run_ref_rows == 0 && c->bits != 0)
     return write_tsv_from_device(c, path, basename, rows_out);
@@ -1383,6 +1424,7 @@ static int write_view_tsv(mk_ctx* c, const ExportView& v, const char* path, cons
 // the few rows kept as text into them.
 static int build_view_multi(mk_ctx* const* ctxs, int n, ExportView& all) {
   if (!ctxs || n < 1 || !ctxs[0]) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "multi export: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c0 = ctxs[0];
   for (int j = 0; j < n; ++j) {
     if (!ctxs[j]) { c0->err = "multi export: a context is NULL"; return MK_ERR_ARG; }
@@ -1445,6 +1487,7 @@ static int build_view_multi(mk_ctx* const* ctxs, int n, ExportView& all) {
 
 extern "C" int mk_export_size_multi(mk_ctx* const* ctxs, int n, size_t* rows) {
   if (!ctxs || n < 1 || !rows) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { if (ctxs[0]) ctxs[0]->err = "mk_export_size_multi: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   size_t total = 0;
   for (int j = 0; j < n; ++j) {
     size_t r = 0;
@@ -1575,6 +1618,7 @@ int merged_samples(mk_ctx* const* ctxs, int n, F&& f, bool as_reference = false)
 
 extern "C" int mk_merged_export(mk_ctx* const* ctxs, int n, uint8_t* kmers, uint64_t* matrix, size_t rows_cap, size_t* rows) {
   if (!rows) return MK_ERR_ARG;
+  for (int j_ = 0; ctxs && j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "merged table: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   size_t at = 0;
   bool short_cap = false;
   const size_t k = ctxs && ctxs[0] ? (size_t)ctxs[0]->k : 0;
@@ -1606,6 +1650,7 @@ extern "C" int mk_write_merged_tsv_as_reference(mk_ctx* const* ctxs, int n, cons
 static int write_merged(mk_ctx* const* ctxs, int n, const char* const* names, const char* first_column, const char* path,
                         size_t* rows_out, bool as_reference) {
   if (!ctxs || n < 1 || !ctxs[0] || !names || !first_column || !path) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "merged table: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c = ctxs[0];
   FILE* f = fopen(path, "wb");
   if (!f) { c->err = std::string("mk_write_merged_tsv: cannot open ") + path; return MK_ERR_IO; }
@@ -1658,6 +1703,7 @@ static int write_merged(mk_ctx* const* ctxs, int n, const char* const* names, co
 // every process); here they are sorted.  Consumers address columns by label (bin/mercat2.py:354-355).
 extern "C" int mk_write_merged_tsv_t(mk_ctx* const* ctxs, int n, const char* const* names, const char* path, size_t* rows_out) {
   if (!ctxs || n < 1 || !ctxs[0] || !names || !path) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "merged table: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c = ctxs[0];
   const size_t k = (size_t)c->k;
   std::vector<uint8_t> kmers;
@@ -1716,6 +1762,7 @@ extern "C" int mk_write_merged_tsv_t(mk_ctx* const* ctxs, int n, const char* con
 // ------------------------------------------------------------------------ alpha diversity
 extern "C" int mk_alpha_stats(mk_ctx* c, mk_alpha_t* out) {
   if (!c || !out) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_alpha_stats"); if (rs_) return rs_; }
   if (c->in_chunk) { c->err = "mk_alpha_stats: a chunk is open"; return MK_ERR_STATE; }
   MK_HIP(hipSetDevice(c->device));
   int rc;
@@ -1746,6 +1793,7 @@ extern "C" int mk_alpha_stats(mk_ctx* c, mk_alpha_t* out) {
 // buffers come back on the next chunk.
 extern "C" int mk_trim(mk_ctx* c) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_trim"); if (rs_) return rs_; }
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (c->in_chunk) { c->err = "mk_trim: a chunk is open"; return MK_ERR_STATE; }
   MK_HIP(hipSetDevice(c->device));
@@ -1765,6 +1813,7 @@ extern "C" int mk_trim(mk_ctx* c) {
 // ------------------------------------------------------------------- multi-GPU plumbing
 extern "C" int mk_export_pairs_device(mk_ctx* c, uint64_t* d_keys, uint64_t* d_counts, size_t cap, size_t* rows) {
   if (!c || !rows) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_export_pairs_device"); if (rs_) return rs_; }
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (c->mode == MK_MODE_BYREF) { *rows = 0; return MK_OK; }  // rows travel as text (mk_export_exotic)
   MK_HIP(hipSetDevice(c->device));
@@ -1774,6 +1823,7 @@ extern "C" int mk_export_pairs_device(mk_ctx* c, uint64_t* d_keys, uint64_t* d_c
 
 extern "C" int mk_import_pairs_device(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_import_pairs_device"); if (rs_) return rs_; }
   if (!rows) return MK_OK;
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (c->mode == MK_MODE_BYREF) { c->err = "mk_import_pairs_device: context has no packed table"; return MK_ERR_STATE; }
@@ -1798,6 +1848,7 @@ extern "C" int mk_import_pairs_device(mk_ctx* c, const uint64_t* d_keys, const u
 
 extern "C" int mk_export_exotic(mk_ctx* c, uint8_t* kmers, uint64_t* counts, size_t cap, size_t* rows) {
   if (!c || !rows) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_export_exotic"); if (rs_) return rs_; }
   MK_HIP(hipSetDevice(c->device));
   { int rc_ = settle(c); if (rc_) return rc_; }
   ExportView v;
@@ -1816,6 +1867,7 @@ extern "C" int mk_export_exotic(mk_ctx* c, uint8_t* kmers, uint64_t* counts, siz
 
 extern "C" int mk_import_exotic(mk_ctx* c, const uint8_t* kmers, const uint64_t* counts, size_t rows) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_import_exotic"); if (rs_) return rs_; }
   if (!rows) return MK_OK;
   if (!kmers || !counts) return MK_ERR_ARG;
   MK_HIP(hipSetDevice(c->device));
@@ -1839,6 +1891,7 @@ extern "C" int mk_import_exotic(mk_ctx* c, const uint8_t* kmers, const uint64_t*
 // (lib/mercat2_kmers.py:73-76 applies it once per file).
 extern "C" int mk_filter_min(mk_ctx* c, uint64_t min_count) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_filter_min"); if (rs_) return rs_; }
   { int rc_ = settle(c); if (rc_) return rc_; }
   if (c->in_chunk) { c->err = "mk_filter_min: a chunk is open"; return MK_ERR_STATE; }
   if (min_count <= 1) return MK_OK;
@@ -1893,6 +1946,8 @@ extern "C" int mk_filter_min(mk_ctx* c, uint64_t min_count) {
 
 extern "C" int mk_merge_from(mk_ctx* dst, mk_ctx* src) {
   if (!dst || !src || dst == src) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(dst, "mk_merge_from"); if (rs_) return rs_; }
+  if (src->spoiled) { dst->err = "mk_merge_from: the source context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c = dst;
   if (dst->device != src->device || dst->alphabet != src->alphabet || dst->k != src->k || dst->canonical != src->canonical) {
     c->err = "mk_merge_from: contexts differ in device, alphabet, k or canonical mode";

@@ -68,6 +68,8 @@ struct MkChunkInfo {
   unsigned long long records;       // super-k-mer records written (partitioned nt path)
   unsigned long long part_overflow; // a bucket region sized from a sampled histogram was too small: partition again, exactly
   unsigned long long spilled;       // fused upsert (mk_skcount.hip): survivors written to the spill list instead of the running table
+  unsigned long long split_exhausted; // sub-ranges counted (or found void) with every split bit used: the whole LDS table probed
+  unsigned long long pre_void;      // two-word pre-filter (mk_skmer2.hip): buckets it could not split far enough (count them exactly)
 };
 
 enum MkMode { MK_MODE_DENSE = 0, MK_MODE_HASH64 = 1, MK_MODE_HASH128 = 2, MK_MODE_BYREF = 3 };
@@ -98,6 +100,8 @@ int mk_buf_reserve(mk_ctx* c, MkDevBuf& b, size_t bytes, bool keep = false);
 // (the source must stay untouched until the context's stream has passed it) unless wait is set
 int mk_feed_host_async(mk_ctx* c, const uint8_t* p, size_t n, bool wait);
 int mk_reserve_raw(mk_ctx* c, size_t bytes);
+// mk_api.hip: MK_ERR_STATE (and the message) when the context holds part of a refused chunk (mk_ctx::spoiled), else MK_OK
+int mk_refuse_spoiled(mk_ctx* c, const char* what);
 
 struct MkEventPair {
   hipEvent_t a, b;
@@ -114,6 +118,9 @@ struct mk_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   bool in_chunk = false;
+  // a fused count kernel upserted part of a chunk that was then refused: the running table holds part of it, and every
+  // call but mk_reset / mk_reset_for / mk_destroy is refused until a reset clears it
+  std::atomic<bool> spoiled{false};
   bool profile = false;
 
   // chunk staging

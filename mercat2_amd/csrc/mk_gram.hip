@@ -346,6 +346,7 @@ extern "C" int mk_gram_matrix(int device, const uint64_t* matrix, size_t rows, i
 
 extern "C" int mk_gram(mk_ctx* const* ctxs, int n, size_t slab_rows, uint64_t* gram, size_t* rows_out) {
   if (!ctxs || n < 1 || !ctxs[0] || !gram || !rows_out) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "mk_gram: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c = ctxs[0];
   if (n > kMaxN) { c->err = "mk_gram: at most 4096 samples"; return MK_ERR_ARG; }
   for (int s = 0; s < n; ++s) {

@@ -377,6 +377,7 @@ struct Dispatcher : MkCutSink {
 extern "C" int mk_count_file(mk_ctx* const* ctxs, int nctx, const char* path, uint64_t chunk_bytes, uint64_t min_count,
                              int threads, mk_file_stats_t* st) {
   if (!ctxs || nctx < 1 || !ctxs[0]) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < nctx; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "mk_count_file: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c0 = ctxs[0];
   if (!path) { c0->err = "mk_count_file: path is NULL"; return MK_ERR_ARG; }
   for (int j = 0; j < nctx; ++j) {

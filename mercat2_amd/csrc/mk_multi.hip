@@ -387,6 +387,7 @@ static int on_every(int n, F&& f) {
 
 extern "C" int mk_bucket_rows_device(mk_ctx* c, const uint64_t* bounds, int n, uint64_t* d_rows, size_t cap_rows, uint64_t* counts) {
   if (!c || !counts || n < 1 || (n > 1 && !bounds)) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_bucket_rows_device"); if (rs_) return rs_; }
   if (n > MK_MAX_OWNERS) { c->err = "mk_bucket_rows_device: at most 64 owners"; return MK_ERR_ARG; }
   if (c->in_chunk) { c->err = "mk_bucket_rows_device: a chunk is open"; return MK_ERR_STATE; }
   for (int j = 1; j + 1 < n; ++j)
@@ -396,6 +397,7 @@ extern "C" int mk_bucket_rows_device(mk_ctx* c, const uint64_t* bounds, int n, u
 
 extern "C" int mk_import_rows_device(mk_ctx* c, const uint64_t* d_rows, size_t rows) {
   if (!c) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_import_rows_device"); if (rs_) return rs_; }
   if (!rows) return MK_OK;
   if (!d_rows) return MK_ERR_ARG;
   if (c->mode == MK_MODE_BYREF) { c->err = "mk_import_rows_device: context has no packed table"; return MK_ERR_STATE; }
@@ -413,6 +415,7 @@ extern "C" int mk_import_rows_device(mk_ctx* c, const uint64_t* d_rows, size_t r
 
 extern "C" int mk_sample_keys(mk_ctx* c, size_t stride, uint64_t* out, size_t cap, size_t* n) {
   if (!c || !n || (cap && !out)) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_sample_keys"); if (rs_) return rs_; }
   if (c->in_chunk) { c->err = "mk_sample_keys: a chunk is open"; return MK_ERR_STATE; }
   std::vector<u64> got;
   int rc = sample_keys(c, stride ? stride : 1, got);
@@ -426,6 +429,7 @@ extern "C" int mk_sample_keys(mk_ctx* c, size_t stride, uint64_t* out, size_t ca
 // sum their bins with one reduce ("dense bins: ncclAllReduce / ncclReduce of u64 bins").
 extern "C" int mk_dense_bins_device(mk_ctx* c, uint64_t* d_bins, size_t nbins, int store) {
   if (!c || !d_bins) return MK_ERR_ARG;
+  { const int rs_ = mk_refuse_spoiled(c, "mk_dense_bins_device"); if (rs_) return rs_; }
   if (c->mode != MK_MODE_DENSE) { c->err = "mk_dense_bins_device: the context does not count into dense bins"; return MK_ERR_STATE; }
   if (c->in_chunk) { c->err = "mk_dense_bins_device: a chunk is open"; return MK_ERR_STATE; }
   if (nbins != c->run_slots) { c->err = "mk_dense_bins_device: the table has " + std::to_string(c->run_slots) + " bins"; return MK_ERR_RANGE; }
@@ -440,6 +444,7 @@ extern "C" int mk_dense_bins_device(mk_ctx* c, uint64_t* d_bins, size_t nbins, i
 
 extern "C" int mk_merge_devices(mk_ctx* const* ctxs, int n, int flags, mk_merge_stats_t* st) {
   if (!ctxs || n < 1 || !ctxs[0]) return MK_ERR_ARG;
+  for (int j_ = 0; j_ < n; ++j_) if (ctxs[j_] && ctxs[j_]->spoiled) { ctxs[0]->err = "mk_merge_devices: a context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
   mk_ctx* c0 = ctxs[0];
   if (n > MK_MAX_OWNERS) { c0->err = "mk_merge_devices: at most 64 contexts"; return MK_ERR_ARG; }
   for (int i = 0; i < n; ++i) {

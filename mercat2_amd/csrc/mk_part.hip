@@ -16,7 +16,10 @@
 //                      ds_add_u32), emit the entries with count >= min_count, clear, next
 //                      sub-range. A bucket holding more distinct keys than the LDS table takes
 //                      is split by further hash bits (the bucket is re-read, from L2), and a
-//                      sub-range that still overflows is halved again -- any input works.
+//                      sub-range that still overflows is halved again.  At the last split level
+//                      (all SUB_BITS used) a key probes the whole table: a sub-range of up to
+//                      CNT_SLOTS distinct keys always counts; more distinct keys sharing the bucket
+//                      and every split bit are refused (MK_ERR_RANGE).
 //   5 (mk_table.hip)   survivors -> running table.
 //
 // All counting atomics are LDS atomics; HBM sees the packed symbols once or twice, each key
@@ -212,10 +215,11 @@ __global__ __launch_bounds__(SCAT_THREADS) void mk_part_scatter_k(const u64* __r
 #define CNT_U 4  // keys per thread in flight
 
 #define CNT_MAX_PROBE 48  // longer chains mean the table is too full for this sub-range: split it
+// (max_probe: CNT_MAX_PROBE, or CNT_SLOTS at the last split level, where no further split can shorten a chain)
 __device__ __forceinline__ void lds_insert_slow(u64* tkey, unsigned* tcnt, unsigned* s_overflow, u64 key, unsigned slot,
-                                                u64 cur) {
+                                                u64 cur, int max_probe) {
 #pragma unroll 1  // (unrolled 48 times and inlined at every call site this loop was most of the kernel's 23 KB of code)
-  for (int probe = 0; probe < CNT_MAX_PROBE; ++probe) {
+  for (int probe = 0; probe < max_probe; ++probe) {
     if (cur == MK_EMPTY) {
       cur = atomicCAS(&tkey[slot], MK_EMPTY, key);
       if (cur == MK_EMPTY) cur = key;
@@ -262,6 +266,7 @@ __global__ __launch_bounds__(CNT_THREADS) void mk_part_count_k(const u64* __rest
     // ---- fill the table with the keys of sub-range (s, idx): CNT_U loads in flight per thread,
     //      first probe of all of them issued together, the rare collisions take the slow path
     const unsigned sel_shift = SUB_BITS - s;
+    const int max_probe = s >= SUB_BITS ? CNT_SLOTS : CNT_MAX_PROBE;
     for (u64 base = 0; base < n; base += (u64)CNT_THREADS * CNT_U) {
       u64 kk[CNT_U];
 #pragma unroll
@@ -283,7 +288,7 @@ __global__ __launch_bounds__(CNT_THREADS) void mk_part_count_k(const u64* __rest
       for (int u = 0; u < CNT_U; ++u) {
         if (kk[u] == MK_EMPTY) continue;
         if (cur[u] == kk[u]) atomicAdd(&tcnt[slot[u]], 1u);
-        else lds_insert_slow(tkey, tcnt, &s_overflow, kk[u], slot[u], cur[u]);
+        else lds_insert_slow(tkey, tcnt, &s_overflow, kk[u], slot[u], cur[u], max_probe);
       }
       if (*(volatile unsigned*)&s_overflow) break;  // the table filled up: this attempt is void
     }
@@ -335,6 +340,7 @@ __global__ __launch_bounds__(CNT_THREADS) void mk_part_count_k(const u64* __rest
     if (threadIdx.x == 0) { s_distinct = 0; s_overflow = 0; s_emit = 0; }
     __syncthreads();
     // ---- next sub-range (uniform across the workgroup)
+    if (s >= SUB_BITS && threadIdx.x == 0) atomicAdd(&info->split_exhausted, 1ull);
     if (over) {
       if (s >= SUB_BITS) {  // cannot split further: report, never give a wrong count silently
         if (threadIdx.x == 0) atomicAdd(&info->errors, 1ull);

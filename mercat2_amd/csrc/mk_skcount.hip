@@ -93,9 +93,10 @@ __device__ __forceinline__ unsigned skc_lane_rank(u64 mask) {  // set bits of ma
 }
 
 // The top n (<= 64) deferred keys of this wave's stack: linear probing from the slot after the home slot
-// (the home slot is known to hold another key), one key per lane.
+// (the home slot is known to hold another key), one key per lane, for at most max_probe slots: SKC_MAX_PROBE, or the
+// whole table at the last split level (no further split can shorten a chain there: DESIGN.md section 8h).
 __device__ __forceinline__ void skc_drain(u64* tkey, unsigned* tcnt, const u64* q, unsigned& qcount, unsigned n,
-                                              unsigned* s_overflow) {
+                                              unsigned* s_overflow, int max_probe) {
   const unsigned lane = threadIdx.x & 63;
   qcount -= n;
 #ifdef SKC_ABL_NODRAIN  // (timing ablation only: the deferred keys are pushed and then dropped)
@@ -106,7 +107,7 @@ __device__ __forceinline__ void skc_drain(u64* tkey, unsigned* tcnt, const u64* 
     unsigned slot = skc_step(skc_home(skc_hash(key)), 1);
     bool placed = false;
 #pragma unroll 1
-    for (int probe = 0; probe < SKC_MAX_PROBE; ++probe) {
+    for (int probe = 0; probe < max_probe; ++probe) {
       u64 cur = atomicCAS(&tkey[slot], MK_EMPTY, key);  // claim-or-compare in one trip, as in the insert round
       if (cur == MK_EMPTY) cur = key;
       if (cur == key) {
@@ -287,6 +288,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
       bool first_pass = true;
       for (;;) {
         const unsigned sel_shift = SKC_SUB_BITS - s;
+        const int max_probe = s >= SKC_SUB_BITS ? SKC_SLOTS : SKC_MAX_PROBE;
         side_pass = 0;  // the all-ones key (32 x 'T') is counted aside, once per bucket
         win_pass = 0;
         bool over = false;
@@ -380,7 +382,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
                   }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                while (qcount >= 64) skc_drain(tkey, tcnt, myq, qcount, 64u, ovf);
+                while (qcount >= 64) skc_drain(tkey, tcnt, myq, qcount, 64u, ovf, max_probe);
               }
             };
             auto round_any = [&](auto nb_tag, int base) {
@@ -395,7 +397,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
           if (__hip_atomic_load(&s_overflow[par], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) over = true;
         }
         STAMP_ADD(tA, t0);
-        if (qcount) skc_drain(tkey, tcnt, myq, qcount, qcount, ovf);  // (< 64 left)
+        if (qcount) skc_drain(tkey, tcnt, myq, qcount, qcount, ovf, max_probe);  // (< 64 left)
         if (first_pass && seg_lane && bn < p1) skc_seg_publish(s_seg[bp ^ 1], seg_lo, seg_hi, seg_end, nseg);  // the next bucket's table
         first_pass = false;
         STAMP_ADD(tB, t0);
@@ -539,6 +541,7 @@ __global__ __launch_bounds__(SKC_LB) void mk_sk_count_k(const ulonglong2* __rest
           if (threadIdx.x < f_n) f_old = atomicCAS(&run[pend_slot[f_cur][threadIdx.x]].key, MK_EMPTY, pend_key[f_cur][threadIdx.x]);
         }
         STAMP_ADD(tD, t0);
+        if (s >= SKC_SUB_BITS && threadIdx.x == 0) atomicAdd(&info->split_exhausted, 1ull);
         if (over) {
           if (s >= SKC_SUB_BITS) { ++nerr; break; }
           s += 1;

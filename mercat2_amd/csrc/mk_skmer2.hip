@@ -479,11 +479,13 @@ __device__ __forceinline__ unsigned sk2c_lane_rank(u64 mask) {  // set bits of m
 // Insert one 128-bit key, probing from its home slot (see the protocol in the header).  The lane that wins a slot
 // writes the key and publishes inside the loop iteration in which it won.  tkey holds {hi, lo} side by side: one
 // 16-byte LDS access per key.
-__device__ __forceinline__ void sk2c_insert(ulonglong2* tkey, unsigned* tcnt, unsigned* ovf, u64 hi, u64 lo, unsigned h) {
+// At most max_probe slots: SK2C_MAX_PROBE, or the whole table at the last split level.
+__device__ __forceinline__ void sk2c_insert(ulonglong2* tkey, unsigned* tcnt, unsigned* ovf, u64 hi, u64 lo, unsigned h,
+                                            int max_probe) {
   unsigned slot = sk2c_home(h);
   bool done = false;
 #pragma unroll 1
-  for (int probe = 0; probe < SK2C_MAX_PROBE && !done;) {
+  for (int probe = 0; probe < max_probe && !done;) {
     unsigned c = __hip_atomic_load(&tcnt[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (c == 0) {
       c = atomicCAS(&tcnt[slot], 0u, SK2C_LOCK);
@@ -511,12 +513,12 @@ __device__ __forceinline__ void sk2c_insert(ulonglong2* tkey, unsigned* tcnt, un
 
 // The top n (<= 64) deferred keys of this wave's stack, one per lane, through the general insert.
 __device__ __forceinline__ void sk2c_drain(ulonglong2* tkey, unsigned* tcnt, const ulonglong2* q, unsigned& qcount, unsigned n,
-                                           unsigned* ovf) {
+                                           unsigned* ovf, int max_probe) {
   const unsigned lane = threadIdx.x & 63;
   qcount -= n;
   if (lane < n) {
     const ulonglong2 key = q[qcount + lane];
-    sk2c_insert(tkey, tcnt, ovf, key.x, key.y, sk2c_hash(key.x, key.y));
+    sk2c_insert(tkey, tcnt, ovf, key.x, key.y, sk2c_hash(key.x, key.y), max_probe);
   }
 }
 
@@ -568,6 +570,7 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_count_k(const Sk2Rec* __r
       const Sk2Rec* __restrict__ src = part + lo_r;
       for (;;) {
         const unsigned sel_shift = SK2C_SUB_BITS - s;
+        const int max_probe = s >= SK2C_SUB_BITS ? SK2C_SLOTS : SK2C_MAX_PROBE;
         unsigned* const ovf = &s_overflow[par];
         u64 win_pass = 0;
         ulonglong2* const myq = wq[threadIdx.x >> 6];
@@ -638,12 +641,12 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_count_k(const Sk2Rec* __r
               if (f) myq[qcount + sk2c_lane_rank(m)] = make_ulonglong2(khi[u], klo[u]);
               qcount += (unsigned)__popcll(m);
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-              if (qcount >= 64) sk2c_drain(tkey, tcnt, myq, qcount, 64u, ovf);
+              if (qcount >= 64) sk2c_drain(tkey, tcnt, myq, qcount, 64u, ovf, max_probe);
             }
           }
           if (__hip_atomic_load(ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
         }
-        if (qcount) sk2c_drain(tkey, tcnt, myq, qcount, qcount, ovf);  // (< 64 left)
+        if (qcount) sk2c_drain(tkey, tcnt, myq, qcount, qcount, ovf, max_probe);  // (< 64 left)
         __syncthreads();  // A
         if (threadIdx.x == 0) cursor[b] = lo_r;  // back to the region's start: the next chunk may inherit the regions (mk_skmer.hip)
         const bool over = s_overflow[par] != 0;
@@ -687,6 +690,7 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_count_k(const Sk2Rec* __r
         emitted += s_emit[par];
         distinct_total += s_distinct[par];
         par ^= 1;
+        if (s >= SK2C_SUB_BITS && threadIdx.x == 0) atomicAdd(&info->split_exhausted, 1ull);
         if (over) {
           if (s >= SK2C_SUB_BITS) { ++nerr; break; }
           s += 1;
@@ -804,7 +808,7 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
   const int lane = threadIdx.x & 63;
   const u64 lomask = (k >= 64) ? ~0ull : (~0ull << (128 - 2 * k));
   const unsigned need = min_count > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)min_count;
-  u64 distinct_total = 0, survivors_total = 0, nerr = 0, windows = 0, records_total = 0;
+  u64 distinct_total = 0, survivors_total = 0, nerr = 0, windows = 0, records_total = 0, npre_void = 0;
   for (unsigned b = blockIdx.x; b < p1; b += gridDim.x) {
     const u64 lo_r = start[b], n = cursor[b] - lo_r;
     u64* __restrict__ my_hi = out_hi + kstart[b];
@@ -949,8 +953,11 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
         emitted += s_emit[par];
         distinct_total += s_distinct[par];
         par ^= 1;
+        if (s >= 16 && threadIdx.x == 0) atomicAdd(&info->split_exhausted, 1ull);
         if (over) {  // thousands of candidates: split the hash range and take the halves one after the other
-          if (s >= 16) { ++nerr; break; }
+          // (keys that share every bit of sk2p_hash cannot be split apart: the host counts the chunk again with the
+          // exact kernel above, whose hash tells them apart -- never a reason to refuse the chunk)
+          if (s >= 16) { ++npre_void; break; }
           s += 1;
           idx <<= 1;
         } else {
@@ -976,6 +983,7 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
     if (distinct_total) atomicAdd(&info->distinct, distinct_total);
     if (survivors_total) atomicAdd(&info->survivors, survivors_total);
     if (nerr) atomicAdd(&info->errors, nerr);
+    if (npre_void) atomicAdd(&info->pre_void, npre_void);
   }
 }
 
@@ -1060,7 +1068,9 @@ int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bo
     // the counting pre-filter pays when few keys can reach min_count: min_count well above the mean count of a key,
     // which the chunk before has measured (windows / distinct keys); a sample's first chunk takes the exact kernel
     // (MK_FORCE_PREFILTER: whenever min_count >= 2)
-    const bool pre = min_count >= 2 && ((min_count >= 4 && c->dup_known && c->dup_hint * 2.5 < (double)min_count) ||
+    // (never on the exact pass: that counts a chunk again whose pre-filter could not split a bucket, or whose sampled
+    // partition was too small -- the exact kernel takes both)
+    const bool pre = !exact && min_count >= 2 && ((min_count >= 4 && c->dup_known && c->dup_hint * 2.5 < (double)min_count) ||
                                         mk_env_set("MK_FORCE_PREFILTER"));
     if (pre && c->canonical)
       hipLaunchKernelGGL(mk_sk2_countp_k<true>, dim3(grid), dim3(SK2C_THREADS), 0, c->stream, (const Sk2Rec*)c->part.p,

@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "mk_device_count", "mk_reset_for", "mk_textwrap", "mk_set_clean", "mk_clean_stats", "mk_clean_runs",
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
 ]
-MK_ABI = 4  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
+MK_ABI = 5  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
 
 
@@ -60,7 +60,8 @@ class Stats(C.Structure):
                [(n, C.c_double) for n in ("ms_parse", "ms_pack", "ms_count", "ms_exotic", "ms_filter", "ms_export")] + \
                [(n, C.c_uint64) for n in ("n_parse", "n_pack", "n_count", "n_exotic", "n_filter", "n_export")] + \
                [("ms_part", C.c_double), ("n_part", C.c_uint64), ("records", C.c_uint64), ("distinct", C.c_uint64),
-                ("part_retries", C.c_uint64), ("part_reused", C.c_uint64), ("fused_chunks", C.c_uint64), ("fuse_spilled", C.c_uint64), ("parse_retries", C.c_uint64)]
+                ("part_retries", C.c_uint64), ("part_reused", C.c_uint64), ("fused_chunks", C.c_uint64), ("fuse_spilled", C.c_uint64), ("parse_retries", C.c_uint64),
+                ("split_exhausted", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -226,3 +226,208 @@ def count_sample_c1(texts: Sequence[bytes], k: int) -> Tuple[List[np.ndarray], n
 def as_text(keys: Sequence[np.ndarray], k: int) -> np.ndarray:
     """(rows, k) uint8 text of packed nucleotide keys, in the key order given."""
     return decode64(keys[0], k) if len(keys) == 1 else decode128(keys[0], keys[1], k)
+
+
+# ------------------------------------------------------------------------------------ hostile keys for the LDS tables
+# Restatements of the slot hashes of the per-chunk LDS count kernels, and solvers that return distinct keys sharing a
+# kernel's bucket, its home slot and every split bit (DESIGN.md section 8h).  All arithmetic is on uint64 arrays.
+M32 = 0xFFFFFFFF
+M24 = 0xFFFFFF
+SK_M = 11                                   # minimizer length (mk_skmer_dev.h)
+SK_ORDER_MUL, SK_ORDER_ADD = 0x9277B5, 0x2C5A3D
+# the one 11-mer whose minimizer order (the low 22 bits of sk_order_raw) is 0: every window that holds it is filed under it
+M_STAR = (-SK_ORDER_ADD * pow(SK_ORDER_MUL, -1, 1 << 22)) % (1 << 22)
+CNT_SLOTS, SKC_SLOTS, SK2C_SLOTS, SK2P_SLOTS = 8192, 8192, 6144, 2048
+
+
+def umul24(a, b) -> np.ndarray:
+    """__umul24: the low 32 bits of the product of the low 24 bits of each operand."""
+    with np.errstate(over="ignore"):
+        return ((_u(a) & U64(M24)) * (_u(b) & U64(M24))) & U64(M32)
+
+
+def sk_order_raw(mm) -> np.ndarray:
+    """mk_skmer_dev.h sk_order_raw (32 bits; minimizers are compared on the low 22)."""
+    return (umul24(mm, SK_ORDER_MUL) + U64(SK_ORDER_ADD)) & U64(M32)
+
+
+def sk_bucket(mm, p1_log2: int) -> np.ndarray:
+    with np.errstate(over="ignore"):
+        return ((_u(mm) * U64(0xC2B2AE3D)) & U64(M32)) >> U64(32 - p1_log2)
+
+
+def _three(w) -> np.ndarray:
+    """The three 24-bit multiplies of skc_hash over one 64-bit word."""
+    w = _u(w)
+    return umul24(w & U64(M32), 0x9E3779) ^ umul24((w >> U64(24)) & U64(M32), 0x85EBCB) ^ umul24(w >> U64(48), 0xC2B2AF)
+
+
+def skc_hash(key) -> np.ndarray:
+    """mk_skcount.hip skc_hash: bits 31..19 pick the slot (8192 slots), bits 15..0 the sub-range."""
+    return _three(key)
+
+
+def skc_home(h) -> np.ndarray:
+    return _u(h) >> U64(19)
+
+
+def _sk2_pre(hi, lo) -> np.ndarray:
+    hi, lo = _u(hi), _u(lo)
+    return (_three(hi) ^ umul24(lo & U64(M32), 0x27D4EB) ^ umul24((lo >> U64(24)) & U64(M32), 0x165667) ^
+            umul24(lo >> U64(48), 0x2C1B3D))
+
+
+def sk2c_hash(hi, lo) -> np.ndarray:
+    """mk_skmer2.hip sk2c_hash."""
+    h = _sk2_pre(hi, lo)
+    return h ^ (h >> U64(15))
+
+
+def sk2c_home(h) -> np.ndarray:
+    return (_u(h) * U64(SK2C_SLOTS)) >> U64(32)
+
+
+def rotr64(x, r: int) -> np.ndarray:
+    x = _u(x)
+    return (x >> U64(r)) | (x << U64(64 - r))
+
+
+def sk2p_hash(hi, lo) -> np.ndarray:
+    """mk_skmer2.hip sk2p_hash: the 128 key bits folded to 64 (hi ^ rotr(lo, 23)), then skc_hash's multiplies."""
+    h = _three(_u(hi) ^ rotr64(lo, 23))
+    return h ^ (h >> U64(15))
+
+
+def part_hash_fields(key, p1_log2: int):
+    """mk_part.hip: (bucket, 24-bit split field, home slot) of a one-word key."""
+    h = mix64(key)
+    return h >> U64(64 - p1_log2), (h >> U64(64 - p1_log2 - 24)) & U64(M24), h & U64(CNT_SLOTS - 1)
+
+
+def _deposit(i: np.ndarray, positions: Sequence[int]) -> np.ndarray:
+    """The bits of i (t = 0, 1, ..) placed at positions[t] of a 64-bit word."""
+    out = np.zeros(i.size, dtype=U64)
+    for t, p in enumerate(positions):
+        out |= ((i >> U64(t)) & U64(1)) << U64(p)
+    return out
+
+
+def _free_positions(fixed_mask: int, skip: int) -> List[int]:
+    return [b for b in range(64) if not (fixed_mask >> b) & 1 and not (skip >> b) & 1]
+
+
+def skc_hostile(k: int, n: int, offset: int = 0, same_home: bool = True, seed: int = 1) -> np.ndarray:
+    """Up to n distinct one-word k-mer keys (12 <= k <= 32) with M_STAR at bases offset..offset+10 -- one minimizer, so
+    one bucket at any p1 -- and equal skc_hash bits 15..0 (the sub-range at every split level); with same_home also
+    equal bits 31..19 (the home slot).  Bits 24..39 of the key (bases k-20..k-13) must be free: they are solved for."""
+    assert 12 <= k <= 32 and 0 <= offset <= k - SK_M
+    mshift = 2 * (k - SK_M - offset)
+    fixed = ((1 << 22) - 1) << mshift
+    base = M_STAR << mshift
+    solve = 0xFFFF << 24
+    assert not fixed & solve, "M_STAR would cover the solved bits"
+    keymask = (1 << (2 * k)) - 1
+    free = [b for b in _free_positions(fixed | ~keymask & ((1 << 64) - 1), solve)]
+    rng = np.random.default_rng(seed)
+    target = int(rng.integers(0, 1 << 32))
+    binv = pow(0x85EBCB, -1, 1 << 16)
+    got, total = [], 0
+    step = 1 << 22
+    for start in range(0, 1 << len(free), step):
+        i = np.arange(start, min(start + step, 1 << len(free)), dtype=U64)
+        key = _deposit(i, free) | U64(base)
+        with np.errstate(over="ignore"):
+            x = (((skc_hash(key) ^ U64(target)) & U64(0xFFFF)) * U64(binv)) & U64(0xFFFF)
+        key = key | (x << U64(24))
+        h = skc_hash(key)
+        ok = (h & U64(0xFFFF)) == U64(target & 0xFFFF)
+        if same_home:
+            ok &= (h >> U64(19)) == U64(target >> 19)
+        got.append(key[ok])
+        total += int(ok.sum())
+        if total >= n:
+            break
+    keys = np.unique(np.concatenate(got))
+    return keys[:n]
+
+
+def sk2c_hostile(k: int, n: int, seed: int = 2) -> Tuple[np.ndarray, np.ndarray]:
+    """Up to n distinct two-word keys (33 <= k <= 64) with M_STAR at bases 0..10 and one value of sk2c_hash: one
+    bucket, one home slot, one sub-range at every split level.  Bits 0..23 of hi are enumerated, bits 24..41 solved,
+    the rest of the key (lo) drawn once."""
+    assert 33 <= k <= 64
+    rng = np.random.default_rng(seed)
+    lo_bits = 2 * (k - 32)
+    lo = U64((int.from_bytes(rng.bytes(8), "little") >> (64 - lo_bits)) << (64 - lo_bits))
+    hi_base = U64(M_STAR << 42)
+    target = int(rng.integers(0, 1 << 32))
+    binv = pow(0x85EBCB, -1, 1 << 18)
+    got, total = [], 0
+    step = 1 << 22
+    for start in range(0, 1 << 24, step):
+        h0 = np.arange(start, start + step, dtype=U64)
+        hi = hi_base | h0
+        # pre-mix value without the middle piece's product: the product must make up the rest
+        rest = _sk2_pre(hi, np.full(hi.size, lo)) ^ umul24((hi >> U64(24)) & U64(M32), 0x85EBCB)
+        with np.errstate(over="ignore"):
+            need = rest ^ U64(target)
+            # middle piece = hi bits 24..47: bits 42..47 are M_STAR's, bits 24..41 (x) are solved from the low 18 bits
+            top = (hi >> U64(24)) & U64(0xFC0000)
+            x = (((need - umul24(top, 0x85EBCB)) & U64((1 << 18) - 1)) * U64(binv)) & U64((1 << 18) - 1)
+        hi = hi | (x << U64(24))
+        ok = _sk2_pre(hi, np.full(hi.size, lo)) == U64(target)
+        got.append(hi[ok])
+        total += int(ok.sum())
+        if total >= n:
+            break
+    his = np.unique(np.concatenate(got))[:n]
+    return his, np.full(his.size, lo)
+
+
+def sk2p_hostile(k: int, n: int, seed: int = 3) -> Tuple[np.ndarray, np.ndarray]:
+    """n distinct two-word keys (33 <= k <= 64) with one value of sk2p_hash and M_STAR at bases 0..10:
+    (hi ^ rotr(d, 23), lo ^ d) for d on lo bits that the key uses and that rotr moves below hi bit 42."""
+    assert 33 <= k <= 64
+    rng = np.random.default_rng(seed)
+    lo_low = max(23, 128 - 2 * k)  # (d below bit 23 would rotate into M_STAR's bits of hi)
+    width = 64 - lo_low
+    assert (1 << width) >= n
+    hi0 = U64((M_STAR << 42) | int(rng.integers(0, 1 << 42)))
+    lo0 = U64((int.from_bytes(rng.bytes(8), "little") >> (128 - 2 * k)) << (128 - 2 * k))
+    d = rng.choice(1 << min(width, 40), size=n, replace=False).astype(U64) << U64(lo_low)
+    return np.full(n, hi0) ^ rotr64(d, 23), np.full(n, lo0) ^ d
+
+
+def part_hostile(k: int, n: int, fixed_top: int = 37, same_home: bool = True, seed: int = 4) -> np.ndarray:
+    """Up to n distinct protein keys (5-bit codes A..Z, 6 <= k <= 12) whose mk_mix64 shares its top fixed_top bits
+    (the bucket and split field at p1_log2 <= fixed_top - 24) and, with same_home, its low 13 bits (the LDS home slot
+    of mk_part_count_k): keys are unmix64 of the values with the other bits free, kept when they are valid k-mers."""
+    assert 6 <= k <= 12
+    rng = np.random.default_rng(seed)
+    top = int(rng.integers(0, 1 << fixed_top)) << (64 - fixed_top)
+    low = int(rng.integers(0, CNT_SLOTS)) if same_home else 0
+    free = list(range(13 if same_home else 0, 64 - fixed_top))
+    got, total = [], 0
+    step = 1 << 22
+    for start in range(0, 1 << len(free), step):
+        i = np.arange(start, min(start + step, 1 << len(free)), dtype=U64)
+        key = unmix64(_deposit(i, free) | U64(top | low))
+        ok = key < U64(1 << (5 * k))
+        for j in range(k):
+            ok &= ((key >> U64(5 * j)) & U64(31)) <= U64(25)
+        got.append(key[ok])
+        total += int(ok.sum())
+        if total >= n:
+            break
+    return np.unique(np.concatenate(got))[:n]
+
+
+def hostile_fasta(rows: np.ndarray, reps: Sequence[int], background: bytes = b"", tag: str = "h") -> bytes:
+    """One record per occurrence: key i ((rows, k) uint8 text) written reps[i] times, each as a record of its own, the
+    background records (FASTA text) between them."""
+    recs = []
+    for i, r in enumerate(reps):
+        line = b">%s%d\n%s\n" % (tag.encode(), i, rows[i].tobytes())
+        recs.append(line * int(r))
+    half = len(recs) // 2
+    return b"".join(recs[:half]) + background + b"".join(recs[half:])

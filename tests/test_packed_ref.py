@@ -125,3 +125,87 @@ def test_packed_counter_canonical_is_the_folded_oracle(k):
         keys, counts = pr.count_sample(chunks, k, c, canonical=True)
         got = dict(zip((r.tobytes().decode() for r in pr.as_text(keys, k)), counts.tolist()))
         assert got == want, (k, c)
+
+
+# ------------------------------------------------------------------------- hostile keys for the per-chunk LDS tables
+def test_m_star_has_minimizer_order_zero():
+    assert int(pr.sk_order_raw(pr.M_STAR)) & ((1 << 22) - 1) == 0
+    orders = pr.sk_order_raw(np.arange(1 << 22, dtype=np.uint64)) & np.uint64((1 << 22) - 1)
+    assert np.unique(orders).size == 1 << 22  # a bijection on 11-mers: M_STAR is the only minimizer of order 0
+
+
+def test_umul24_takes_the_low_24_bits_of_each_operand():
+    a, b = 0xAB123456, 0xCD654321
+    assert int(pr.umul24(a, b)) == ((a & 0xFFFFFF) * (b & 0xFFFFFF)) & 0xFFFFFFFF
+
+
+def _mmer_at(keys, k, q):
+    return (np.asarray(keys, np.uint64) >> np.uint64(2 * (k - pr.SK_M - q))) & np.uint64((1 << 22) - 1)
+
+
+@pytest.mark.parametrize("k", [31, 32])
+def test_skc_hostile_keys_share_bucket_home_and_every_split_bit(k):
+    keys = pr.skc_hostile(k, 300)
+    assert keys.size == 300 and np.unique(keys).size == 300
+    assert np.all(keys < np.uint64(1 << (2 * k)) if k < 32 else True)
+    assert np.all(_mmer_at(keys, k, 0) == np.uint64(pr.M_STAR))  # the window's minimizer, so one bucket at any p1
+    for p1_log2 in (8, 13):
+        assert np.unique(pr.sk_bucket(_mmer_at(keys, k, 0), p1_log2)).size == 1
+    h = pr.skc_hash(keys)
+    assert np.unique(pr.skc_home(h)).size == 1 and np.unique(h & np.uint64(0xFFFF)).size == 1
+
+
+def test_skc_hostile_largest_set_at_k31_is_over_two_thousand():
+    keys = pr.skc_hostile(31, 1 << 20)
+    assert keys.size > 2_000 and np.unique(keys).size == keys.size
+    h = pr.skc_hash(keys)
+    assert np.unique(pr.skc_home(h)).size == 1 and np.unique(h & np.uint64(0xFFFF)).size == 1
+
+
+def test_skc_over_capacity_set_shares_the_sub_range_only():
+    keys = pr.skc_hostile(31, 9_000, same_home=False)
+    assert keys.size == 9_000 and np.unique(keys).size == 9_000
+    assert np.unique(pr.skc_hash(keys) & np.uint64(0xFFFF)).size == 1
+    assert np.all(_mmer_at(keys, 31, 0) == np.uint64(pr.M_STAR))
+
+
+@pytest.mark.parametrize("k", [33, 64])
+def test_sk2c_hostile_keys_share_one_hash(k):
+    hi, lo = pr.sk2c_hostile(k, 200)
+    assert hi.size == 200 and np.unique(hi).size == 200
+    assert np.all((hi >> np.uint64(42)) == np.uint64(pr.M_STAR))
+    if k < 64:
+        assert np.all(lo & np.uint64((1 << (128 - 2 * k)) - 1) == 0)  # unused low bits of lo stay clear
+    h = pr.sk2c_hash(hi, lo)
+    assert np.unique(h).size == 1 and np.unique(pr.sk2c_home(h)).size == 1
+    assert int(pr.sk2c_home(h[0])) < pr.SK2C_SLOTS
+
+
+def test_sk2p_hostile_keys_share_one_prefilter_hash():
+    k = 48
+    hi, lo = pr.sk2p_hostile(k, 2_500)
+    pairs = set(zip(hi.tolist(), lo.tolist()))
+    assert len(pairs) == 2_500
+    assert np.all((hi >> np.uint64(42)) == np.uint64(pr.M_STAR))
+    assert np.all(lo & np.uint64((1 << (128 - 2 * k)) - 1) == 0)
+    assert np.unique(pr.sk2p_hash(hi, lo)).size == 1
+    assert np.unique(pr.sk2c_hash(hi, lo)).size > 2_000  # the exact kernel's hash tells them apart
+
+
+def test_part_hostile_keys_are_protein_kmers_on_one_chain():
+    keys = pr.part_hostile(12, 1 << 20)
+    assert keys.size > 48 and np.unique(keys).size == keys.size
+    assert np.all(keys < np.uint64(1 << 60))
+    text = pr.decode64(keys, 12, bits=5)
+    assert np.all((text >= ord("A")) & (text <= ord("Z")))
+    for p1_log2 in (8, 13):
+        b, f, slot = pr.part_hash_fields(keys, p1_log2)
+        assert np.unique(b).size == 1 and np.unique(f).size == 1 and np.unique(slot).size == 1
+
+
+def test_hostile_fasta_counts_are_the_repeats():
+    keys = pr.skc_hostile(31, 60)
+    rows = pr.decode64(keys, 31)
+    text = pr.hostile_fasta(rows, [1 + i % 3 for i in range(60)], b">bg\nACGT\n")
+    got = cpu_ref.count_text(text, 31, 1)
+    assert got == {rows[i].tobytes().decode(): 1 + i % 3 for i in range(60)}
