@@ -267,8 +267,6 @@ struct PairAcc {
 
 }  // namespace
 
-void mk_set_global_error(const std::string& msg);  // mk_api.hip: mk_last_error(NULL)
-
 extern "C" int mk_pair_stats_matrix(int device, const uint64_t* matrix, size_t rows, int n, mk_pair_t* out, uint64_t* sums,
                                     uint64_t* flags) {
   Sink sink;

@@ -93,8 +93,9 @@ struct MkDevBuf {
   size_t cap = 0;
 };
 
-// Simple growable device buffer helpers (implemented in mk_api.cpp)
 struct mk_ctx;
+// ---- host plumbing shared by the host-only files (mk_api / mk_chunk / mk_export / mk_combine / mk_tableops / mk_multi) ----
+// mk_api.hip: growable device buffers
 int mk_buf_reserve(mk_ctx* c, MkDevBuf& b, size_t bytes, bool keep = false);
 // mk_api.hip, for mk_ingest.hip: append host bytes to the open chunk without waiting for the copy
 // (the source must stay untouched until the context's stream has passed it) unless wait is set
@@ -102,6 +103,16 @@ int mk_feed_host_async(mk_ctx* c, const uint8_t* p, size_t n, bool wait);
 int mk_reserve_raw(mk_ctx* c, size_t bytes);
 // mk_api.hip: MK_ERR_STATE (and the message) when the context holds part of a refused chunk (mk_ctx::spoiled), else MK_OK
 int mk_refuse_spoiled(mk_ctx* c, const char* what);
+// mk_api.hip: mk_last_error(NULL), for calls that have no context
+void mk_set_global_error(const std::string& msg);
+// mk_api.hip: row totals and the chunk's scalars
+int mk_settle(mk_ctx* c);     // fold row totals that were read back without waiting; before anything reads run_rows & co.
+int mk_pull_info(mk_ctx* c);  // MkChunkInfo -> h_info, stream idle afterwards
+// mk_api.hip: room in a running table for need_rows keys in all (mk_grow_run: for more_rows further packed keys)
+int mk_grow_run64(mk_ctx* c, size_t need_rows);
+int mk_grow_run128(mk_ctx* c, size_t need_rows);
+int mk_grow_run_ref(mk_ctx* c, size_t need_rows);
+int mk_grow_run(mk_ctx* c, size_t more_rows);
 
 struct MkEventPair {
   hipEvent_t a, b;
@@ -231,6 +242,43 @@ struct mk_ctx {
     }                                                                                        \
   } while (0)
 
+// How an ABI entry point opens: refuse a spoiled context, fold pending row totals.  Both return from the caller.
+#define MK_REFUSE_SPOILED(c, what)                                                           \
+  do {                                                                                       \
+    const int rs__ = mk_refuse_spoiled((c), (what));                                         \
+    if (rs__) return rs__;                                                                   \
+  } while (0)
+#define MK_SETTLE(c)                                                                         \
+  do {                                                                                       \
+    const int rc__ = mk_settle(c);                                                           \
+    if (rc__) return rc__;                                                                   \
+  } while (0)
+
+static inline size_t pow2_at_least(size_t v) {
+  size_t p = 1024;
+  while (p < v) p <<= 1;
+  return p;
+}
+static inline void buf_free(MkDevBuf& b) {
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+}
+// the context whose running table the fused launches of c upsert into (mk_share_table)
+static inline mk_ctx* table_of_ctx(mk_ctx* c) { return c->share_owner ? c->share_owner : c; }
+
+// A sample's rows on the host (mk_export.hip), for mk_combine.hip
+struct ExportView {
+  std::vector<unsigned long long> pkeys, pcnts;  // packed rows, sorted by key (two-word keys: pkeys holds {hi, lo} pairs)
+  int words = 1;                                 // 64-bit words per packed key
+  size_t packed_rows() const { return pcnts.size(); }
+  std::vector<uint8_t> rstr;                     // by-reference rows: k bytes each, arena order
+  std::vector<unsigned long long> rcnt;          // counts in arena order
+  std::vector<unsigned long long> rorder;        // arena rows sorted by string
+};
+int mk_build_view(mk_ctx* c, ExportView& v);  // every row of c's running tables, sorted (settles first; fills c->ex_st)
+void mk_decode_row(const mk_ctx* c, const ExportView& v, size_t i, uint8_t* out);  // packed row i -> its k characters
+
 // ---- kernel launchers (each in its own translation unit) ---------------------------------
 // parse: raw[n] -> seq, info (seq_len, symbols, non_ascii)
 int mk_launch_parse(mk_ctx* c, const uint8_t* d_raw, size_t n);
@@ -297,13 +345,15 @@ int mk_launch_compact(mk_ctx* c, const MkSlot* t, size_t slots, uint64_t* d_keys
 int mk_sort_pairs(mk_ctx* c, const uint64_t* keys_in, const uint64_t* vals_in, uint64_t* keys_out, uint64_t* vals_out,
                   size_t n, int key_bits);
 
-// mk_api.hip, for mk_multi.hip
-int mk_settle(mk_ctx* c);                      // fold row totals that were read back without waiting
-int mk_pull_info(mk_ctx* c);                   // MkChunkInfo -> h_info, stream idle afterwards
-int mk_grow_run(mk_ctx* c, size_t more_rows);  // room in the packed running table for more_rows further keys
 // mk_table.hip: interleaved rows {key word(s), count} -> running table (dense: {bin, count})
 int mk_launch_import_rows(mk_ctx* c, const uint64_t* d_rows, size_t rows);
 
+// mk_bin.hip: keys of 16..26 bits counted by direct index
+bool mk_binned_takes(const mk_ctx* c);
+int mk_launch_count_binned(mk_ctx* c, size_t seq_len, uint64_t min_count);
+// mk_tsv.hip: sorted device rows -> TSV text in c->seq
+int mk_launch_tsv_format(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_cnts, size_t rows, int words, uint64_t* d_len,
+                         uint64_t* d_off, size_t* text_bytes);
 // mk_clean.hip
 int mk_launch_clean_pre(mk_ctx* c, uint8_t* d_raw, size_t n);
 int mk_launch_clean_post(mk_ctx* c, size_t seq_cap);

@@ -186,8 +186,6 @@ struct GramAcc {
 
 }  // namespace
 
-void mk_set_global_error(const std::string& msg);  // mk_api.hip: mk_last_error(NULL)
-
 extern "C" int mk_gram_matrix(int device, const uint64_t* matrix, size_t rows, int n, uint64_t* gram) {
   Sink sink;
   Sink* c = &sink;

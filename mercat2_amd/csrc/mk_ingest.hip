@@ -7,7 +7,7 @@
 // streaming Chunker rule over the blocks (mk_cutscan.h) and copies each byte range straight into
 // the raw buffer of the context that owns the current chunk (hipMemcpyAsync on that context's
 // stream), and one worker thread per context runs mk_chunk_end while the next chunk is being read.
-// Host code only; all GPU work is behind the per-context calls of mk_api.hip.
+// Host code only; all GPU work is behind the per-context calls of mk_api.hip (feed) and mk_chunk.hip (count).
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>

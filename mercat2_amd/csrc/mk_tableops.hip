@@ -1,0 +1,164 @@
+// mk_tableops.hip -- rows going INTO a running table from outside a chunk, and table-to-table operations: the imports
+// of the multi-GPU merge (mk_import_pairs_device, mk_import_exotic; their exports are in mk_export.hip), mk_filter_min,
+// mk_merge_from.  Host code only.
+#include "mk_common.h"
+#include <cstring>
+
+typedef unsigned long long u64;
+
+extern "C" int mk_import_pairs_device(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows) {
+  if (!c) return MK_ERR_ARG;
+  MK_REFUSE_SPOILED(c, "mk_import_pairs_device");
+  if (!rows) return MK_OK;
+  MK_SETTLE(c);
+  if (c->mode == MK_MODE_BYREF) { c->err = "mk_import_pairs_device: context has no packed table"; return MK_ERR_STATE; }
+  MK_HIP(hipSetDevice(c->device));
+  int rc;
+  MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
+  if (c->mode == MK_MODE_HASH128) {  // d_keys: {hi, lo} per row
+    if ((rc = mk_grow_run128(c, c->run128_rows + rows)) != MK_OK) return rc;
+    if ((rc = mk_launch_import128_pairs(c, d_keys, d_counts, rows)) != MK_OK) return rc;
+    if ((rc = mk_pull_info(c)) != MK_OK) return rc;
+    c->run128_rows += (size_t)c->h_info->new_rows;
+    return MK_OK;
+  }
+  // (the all-ones key travels as an ordinary pair, anywhere in the rows: the kernel sets it aside)
+  if (c->mode == MK_MODE_HASH64 && (rc = mk_grow_run64(c, c->run_rows + rows)) != MK_OK) return rc;
+  if ((rc = mk_launch_import_pairs(c, d_keys, d_counts, rows)) != MK_OK) return rc;
+  if ((rc = mk_pull_info(c)) != MK_OK) return rc;
+  c->run_rows += (size_t)c->h_info->new_rows;
+  if (c->mode == MK_MODE_HASH64) c->run_side += c->h_info->side;
+  return MK_OK;
+}
+
+extern "C" int mk_import_exotic(mk_ctx* c, const uint8_t* kmers, const uint64_t* counts, size_t rows) {
+  if (!c) return MK_ERR_ARG;
+  MK_REFUSE_SPOILED(c, "mk_import_exotic");
+  if (!rows) return MK_OK;
+  if (!kmers || !counts) return MK_ERR_ARG;
+  MK_HIP(hipSetDevice(c->device));
+  MK_SETTLE(c);
+  int rc;
+  const size_t k = (size_t)c->k;
+  if ((rc = mk_buf_reserve(c, c->ex_keys2, rows * k + 64)) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, c->ex_cnts2, rows * 8 + 64)) != MK_OK) return rc;
+  MK_HIP(hipMemcpyAsync(c->ex_keys2.p, kmers, rows * k, hipMemcpyHostToDevice, c->stream));
+  MK_HIP(hipMemcpyAsync(c->ex_cnts2.p, counts, rows * 8, hipMemcpyHostToDevice, c->stream));
+  MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
+  if ((rc = mk_grow_run_ref(c, c->run_ref_rows + rows)) != MK_OK) return rc;
+  if ((rc = mk_launch_import_ref(c, (const uint8_t*)c->ex_keys2.p, (const uint64_t*)c->ex_cnts2.p, rows)) != MK_OK) return rc;
+  if ((rc = mk_pull_info(c)) != MK_OK) return rc;
+  c->run_ref_rows += (size_t)c->h_info->new_rows_ref;
+  return MK_OK;
+}
+
+// Drop every row of the running table whose count is below min_count: the filter of a sample that is ONE
+// chunk but was counted in pieces (record ranges on several GPUs, unfiltered) and merged
+// (lib/mercat2_kmers.py:73-76 applies it once per file).
+extern "C" int mk_filter_min(mk_ctx* c, uint64_t min_count) {
+  if (!c) return MK_ERR_ARG;
+  MK_REFUSE_SPOILED(c, "mk_filter_min");
+  MK_SETTLE(c);
+  if (c->in_chunk) { c->err = "mk_filter_min: a chunk is open"; return MK_ERR_STATE; }
+  if (min_count <= 1) return MK_OK;
+  MK_HIP(hipSetDevice(c->device));
+  int rc;
+  u64* d_kept = (u64*)((char*)c->info.p + sizeof(MkChunkInfo));
+  u64 kept = 0;
+  if (c->mode == MK_MODE_DENSE) {
+    if ((rc = mk_launch_refilter_dense(c, (uint64_t*)c->run.p, c->run_slots, min_count)) != MK_OK) return rc;
+  } else if (c->mode == MK_MODE_HASH64 && c->run_slots) {
+    MkDevBuf nb;
+    if ((rc = mk_buf_reserve(c, nb, c->run_slots * sizeof(MkSlot))) != MK_OK) return rc;
+    if ((rc = mk_launch_clear_slots(c, (MkSlot*)nb.p, c->run_slots)) != MK_OK) return rc;
+    MK_HIP(hipMemsetAsync(d_kept, 0, 8, c->stream));
+    if ((rc = mk_launch_refilter64(c, (const MkSlot*)c->run.p, (MkSlot*)nb.p, c->run_slots, min_count, (uint64_t*)d_kept)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(&kept, d_kept, 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    buf_free(c->run);
+    c->run = nb;
+    c->run_rows = (size_t)kept;
+    if (c->run_side < min_count) c->run_side = 0;
+  } else if (c->mode == MK_MODE_HASH128 && c->run128_slots) {
+    MkDevBuf nb;
+    if ((rc = mk_buf_reserve(c, nb, c->run128_slots * sizeof(MkSlot128))) != MK_OK) return rc;
+    MK_HIP(hipMemsetAsync(nb.p, 0, c->run128_slots * sizeof(MkSlot128), c->stream));
+    MK_HIP(hipMemsetAsync(d_kept, 0, 8, c->stream));
+    if ((rc = mk_launch_refilter128(c, (const MkSlot128*)c->run128.p, (MkSlot128*)nb.p, c->run128_slots, min_count, (uint64_t*)d_kept)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(&kept, d_kept, 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    buf_free(c->run128);
+    c->run128 = nb;
+    c->run128_rows = (size_t)kept;
+  }
+  if (c->run_ref_rows) {  // rows kept as text (few): through the host
+    size_t n = 0;
+    if ((rc = mk_export_exotic(c, nullptr, nullptr, 0, &n)) != MK_OK) return rc;
+    std::vector<uint8_t> km(n * (size_t)c->k + 1), km2;
+    std::vector<uint64_t> cn(n + 1), cn2;
+    if ((rc = mk_export_exotic(c, km.data(), cn.data(), n, &n)) != MK_OK) return rc;
+    for (size_t i = 0; i < n; ++i)
+      if (cn[i] >= min_count) {
+        km2.insert(km2.end(), km.begin() + i * (size_t)c->k, km.begin() + (i + 1) * (size_t)c->k);
+        cn2.push_back(cn[i]);
+      }
+    if ((rc = mk_launch_clear_slots(c, (MkSlot*)c->run_ref.p, c->run_ref_slots)) != MK_OK) return rc;
+    c->run_ref_rows = 0;
+    if (!cn2.empty() && (rc = mk_import_exotic(c, km2.data(), cn2.data(), cn2.size())) != MK_OK) return rc;
+  }
+  MK_HIP(hipStreamSynchronize(c->stream));
+  return MK_OK;
+}
+
+extern "C" int mk_merge_from(mk_ctx* dst, mk_ctx* src) {
+  if (!dst || !src || dst == src) return MK_ERR_ARG;
+  MK_REFUSE_SPOILED(dst, "mk_merge_from");
+  if (src->spoiled) { dst->err = "mk_merge_from: the source context holds part of a refused chunk (mk_reset it first)"; return MK_ERR_STATE; }
+  mk_ctx* c = dst;
+  if (dst->device != src->device || dst->alphabet != src->alphabet || dst->k != src->k || dst->canonical != src->canonical) {
+    c->err = "mk_merge_from: contexts differ in device, alphabet, k or canonical mode";
+    return MK_ERR_ARG;
+  }
+  if (dst->in_chunk || src->in_chunk) { c->err = "mk_merge_from: a chunk is open"; return MK_ERR_STATE; }
+  MK_HIP(hipSetDevice(dst->device));
+  int rc;
+  // both streams idle before one context's kernels touch the other's buffers (whatever the mode: the export of src
+  // writes into dst's survivor buffers, which dst's own merge kernels may still be reading)
+  if ((rc = mk_settle(src)) != MK_OK) { dst->err = src->err; return rc; }
+  if ((rc = mk_settle(dst)) != MK_OK) return rc;
+  MK_HIP(hipStreamSynchronize(src->stream));
+  MK_HIP(hipStreamSynchronize(dst->stream));
+  if (src->mode == MK_MODE_HASH64) {
+    // table to table, on the device: no compaction, no sort (the rows' order does not matter for a sum)
+    if (src->run_rows) {
+      if ((rc = mk_grow_run64(dst, dst->run_rows + src->run_rows)) != MK_OK) return rc;
+      MK_HIP(hipMemsetAsync(dst->info.p, 0, sizeof(MkChunkInfo), dst->stream));
+      if ((rc = mk_launch_merge_table64(dst, (const MkSlot*)src->run.p, src->run_slots)) != MK_OK) return rc;
+      if ((rc = mk_pull_info(dst)) != MK_OK) return rc;
+      dst->run_rows += (size_t)dst->h_info->new_rows;
+    }
+    dst->run_side += src->run_side;
+  } else if (src->mode == MK_MODE_DENSE || src->mode == MK_MODE_HASH128) {
+    size_t cap = 0;
+    if ((rc = mk_export_size(src, &cap)) != MK_OK) { dst->err = src->err; return rc; }
+    cap += 1;
+    if ((rc = mk_buf_reserve(dst, dst->surv_keys, cap * 8 * (size_t)mk_words_per_key(src) + 64)) != MK_OK) return rc;
+    if ((rc = mk_buf_reserve(dst, dst->surv_cnts, cap * 8 + 64)) != MK_OK) return rc;
+    size_t rows = 0;
+    if ((rc = mk_export_pairs_device(src, (uint64_t*)dst->surv_keys.p, (uint64_t*)dst->surv_cnts.p, cap, &rows)) != MK_OK) {
+      dst->err = src->err;
+      return rc;
+    }
+    if (rows && (rc = mk_import_pairs_device(dst, (const uint64_t*)dst->surv_keys.p, (const uint64_t*)dst->surv_cnts.p, rows)) != MK_OK)
+      return rc;
+  }
+  if (src->run_ref_rows) {
+    size_t n = 0;
+    if ((rc = mk_export_exotic(src, nullptr, nullptr, 0, &n)) != MK_OK) { dst->err = src->err; return rc; }
+    std::vector<uint8_t> km(n * (size_t)src->k + 1);
+    std::vector<uint64_t> cn(n + 1);
+    if ((rc = mk_export_exotic(src, km.data(), cn.data(), n, &n)) != MK_OK) { dst->err = src->err; return rc; }
+    if ((rc = mk_import_exotic(dst, km.data(), cn.data(), n)) != MK_OK) return rc;
+  }
+  return MK_OK;
+}

@@ -1,4 +1,4 @@
-"""The running hash table (mk_table.hip upserts, mk_api.hip sizing and growth) against a numpy reduction of the same
+"""The running hash table (mk_table.hip upserts, mk_chunk.hip sizing, mk_api.hip growth) against a numpy reduction of the same
 packed keys, where hash tables break: growth from empty over many batches, long probe chains on one home slot and
 probing that wraps past the last slot, many lanes adding to a few keys at once, the key kept beside the table, rows
 of count 0, sums past 2^32, and TSV counts of 1 to 20 digits.

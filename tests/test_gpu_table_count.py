@@ -1,5 +1,5 @@
 """Counting runs that push the running table where the host's sizing guess is wrong: a sample whose chunks alternate
-between low and high diversity, so that the table sized before a fused launch (mk_api.hip process_chunk_fast, from the
+between low and high diversity, so that the table sized before a fused launch (mk_chunk.hip process_chunk_fast, from the
 chunk before) fills up during it and the count kernel spills (mk_skcount.hip) -- without MK_FUSE_MAX_PROBE -- and the
 same chunks over one table shared by several contexts, each driven by its own thread; and S2e at full chunk size
 (100 MiB chunks with 1 % substitutions at -c 1: the non-fused region import, buckets that overflow the count kernels'
