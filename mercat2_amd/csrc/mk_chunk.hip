@@ -104,17 +104,15 @@ static int grow_for_survivors(mk_ctx* c, size_t packed, size_t by_ref) {
   return MK_OK;
 }
 
-// part_meta of the super-k-mer paths: hist[p1] | start[p1 + 1] | cursor[p1] | khist[p1] | kstart[p1 + 1] | kcursor[p1] | nsurv[p1]
-static const uint64_t* meta_kstart(const mk_ctx* c, size_t p1) { return (const uint64_t*)c->part_meta.p + 4 * p1 + 1; }
-static const uint64_t* meta_nsurv(const mk_ctx* c, size_t p1) { return (const uint64_t*)c->part_meta.p + 6 * p1 + 2; }
-
 // The chunk's survivors, laid out per bucket region by the count kernel, into the running table.
 static int import_survivor_regions(mk_ctx* c, bool two) {
   const size_t p1 = (size_t)1 << c->p1_log2;
   const uint64_t *keys = (const uint64_t*)c->surv_keys.p, *cnts = (const uint64_t*)c->surv_cnts.p;
+  const SkMeta m = sk_meta(c->part_meta.p, p1, 1);  // (kstart and nsurv lie where they do whatever the regions per bucket)
+  const uint64_t *kstart = (const uint64_t*)m.kstart, *nsurv = (const uint64_t*)m.nsurv;
   mk_prof_begin(c, MK_K_FILTER);
-  const int rc = two ? mk_launch_import128_regions(c, keys, (const uint64_t*)c->surv_keys2.p, cnts, meta_kstart(c, p1), meta_nsurv(c, p1), p1)
-                     : mk_launch_import_regions(c, keys, cnts, meta_kstart(c, p1), meta_nsurv(c, p1), p1, (size_t)c->h_info->survivors);
+  const int rc = two ? mk_launch_import128_regions(c, keys, (const uint64_t*)c->surv_keys2.p, cnts, kstart, nsurv, p1)
+                     : mk_launch_import_regions(c, keys, cnts, kstart, nsurv, p1, (size_t)c->h_info->survivors);
   mk_prof_end(c);
   return rc;
 }

@@ -297,6 +297,38 @@ int mk_launch_count_partitioned(mk_ctx* c, size_t seq_len, uint64_t min_count);
 int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, bool exact = false);
 // mk_skmer.hip: bucket regions (records and survivors) from an exact or sampled histogram, in one kernel
 bool mk_part_inherit(mk_ctx* c, size_t seq_len, int p1_log2, uint64_t min_count, bool sampled, bool exact);  // mk_skmer.hip
+// part_meta of the super-k-mer paths, in 64-bit words: hist[p1] | start[p1 + 1] | cursor[p1] (packed 32-bit record indices in
+// the space of p1 words) | khist[p1] | kstart[p1 + 1] | [p1] (a cursor array the 8-byte-key path uses) | nsurv[p1], padded
+// to 7 p1 + 16; with nine regions per bucket (nseg > 1, one-word keys) start[9 p1 + 1] and cursor[9 p1] follow there
+// and the two single-region arrays stay unused.
+struct SkMeta {
+  unsigned long long *hist, *start;
+  unsigned* cursor;
+  unsigned long long *khist, *kstart, *nsurv;
+};
+inline size_t sk_meta_words(size_t p1, int nseg) { return 7 * p1 + 16 + (nseg > 1 ? 14 * p1 + 8 : 0); }
+inline size_t sk_meta_cleared_words(size_t p1) { return 7 * p1 + 8; }  // what a fresh partition zeroes: the scan writes the regions
+inline SkMeta sk_meta(void* part_meta, size_t p1, int nseg) {
+  SkMeta m;
+  m.hist = (unsigned long long*)part_meta;
+  m.start = m.hist + p1;
+  m.cursor = (unsigned*)(m.start + p1 + 1);
+  m.khist = m.start + p1 + 1 + p1;
+  m.kstart = m.khist + p1;
+  m.nsurv = m.kstart + p1 + 1 + p1;
+  if (nseg > 1) {
+    m.start = m.hist + sk_meta_words(p1, 1);
+    m.cursor = (unsigned*)(m.start + 9 * p1 + 8);
+  }
+  return m;
+}
+// what both super-k-mer launchers plan a chunk with (mk_skmer.hip)
+int sk_p1_log2(size_t seq_len, int max_log2, size_t bucket_syms);  // buckets: 256 .. 2^max_log2, about bucket_syms symbols each
+int sk_sample_log2(size_t seq_len, bool exact);                    // bucket sizes from one analysis thread in 2^this
+unsigned long long sk_surv_div(uint64_t min_count);                // a bucket of m k-mers has <= ceil(m / this) survivors
+size_t sk_surv_cap(size_t seq_len, size_t p1, unsigned long long surv_div, int sample_log2);  // survivor buffer, in entries
+struct SkQueueShape { bool three; unsigned qcap; };  // sub-tiles per tile of the queue scatters (2 or 3), items per wave queue
+SkQueueShape sk_queue_shape(const mk_ctx* c);
 void mk_launch_sk_scan(mk_ctx* c, const unsigned long long* hist, const unsigned long long* khist, unsigned long long* start,
                        unsigned* cursor, unsigned long long* kstart, int p1_log2, int sample_log2, int nkmax,
                        unsigned long long surv_div, unsigned long long part_cap, unsigned long long surv_cap, float sigmas,

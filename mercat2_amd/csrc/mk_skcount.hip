@@ -154,7 +154,7 @@ __device__ __forceinline__ void skf_finish(MkSlot* __restrict__ run, u64 mask, u
   }
 }
 
-// (the region table of a bucket -- skc_seg_at, skc_seg_publish -- is in mk_skmer_dev.h: the two-word kernels use it too)
+// (the region table of a bucket -- skc_seg_at, skc_seg_publish -- is in mk_skmer_dev.h)
 // Persistent: gridDim.x workgroups (one per CU) walk the buckets b = blockIdx.x, +gridDim.x, ...
 // The next bucket's bounds and its first two record batches are loaded while the current
 // bucket is being emitted, so no global-memory latency sits on the critical path.

@@ -69,45 +69,19 @@ __device__ __forceinline__ ulonglong2 sk_make_record(u64 w0, u64 w1, int jstart,
 }
 
 // ------------------------------------------------------------------------------ 1 hist
-// Records and k-mers per bucket.  With sample_log2 = s > 0 only one analysis thread of every 2^s
-// (a pseudo-random member of each group, so that no period of the text can hide from the sample)
-// is looked at: the scan below turns the sampled counts into capacities with room for the sampling
-// error, the scatter checks every reservation against them, and a chunk whose estimate was too
-// small anywhere is partitioned again with s = 0 (exact).
+// Records and k-mers per bucket (sk_hist_body, mk_skmer_dev.h, which also says what sample_log2 does).
 template <int W, bool CANON>
 __global__ __launch_bounds__(SK_HIST_THREADS) void mk_sk_hist_k(const u64* __restrict__ codes, const u64* __restrict__ bad,
                                                                 const MkChunkInfo* __restrict__ info, u64* __restrict__ hist,
                                                                 u64* __restrict__ khist, int p1_log2, int k, int nkmax,
                                                                 size_t nthreads_total, int canon, int sample_log2) {
   extern __shared__ unsigned sk_hist_lds[];  // 2 x p1 words (launcher): records per bucket, then k-mers per bucket
-  const unsigned p1 = 1u << p1_log2;
-  unsigned* const lh = sk_hist_lds;        // records per bucket
-  unsigned* const lk = sk_hist_lds + p1;   // k-mers per bucket (bounds the bucket's survivors)
-  for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) { lh[i] = 0; lk[i] = 0; }
-  __syncthreads();
-  const size_t seq_len = info->seq_len;
-  const size_t ngroups = (nthreads_total + ((size_t)1 << sample_log2) - 1) >> sample_log2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * blockDim.x) {
-    size_t t = g;
-    if (sample_log2) t = (g << sample_log2) + (((unsigned)g * 0x9E3779B1u >> 7) & ((1u << sample_log2) - 1));
-    const size_t p0 = t * SK_R;
-    if (t >= nthreads_total || p0 >= seq_len) continue;
-    const u64 w0 = codes[t], w1 = codes[t + 1];
-    const u64 badw = bad_window(bad, p0);
-    (void)canon;
-    sk_for_each_record<W>(w0, w1, badw, k, nkmax, CANON, [&](int, int nk, unsigned mm) {
-      const unsigned b = sk_bucket(mm, p1_log2);
-      atomicAdd(&lh[b], 1u);
-      atomicAdd(&lk[b], (unsigned)nk);
-    });
-  }
-  __syncthreads();
-  for (unsigned b = threadIdx.x; b < p1; b += blockDim.x) {
-    const unsigned v = lh[b];
-    // one global add per bucket: records in the low word, k-mers in the high word (a chunk holds fewer than 2^32
-    // symbols, so neither half can carry) -- the per-workgroup flush is most of this kernel's HBM traffic
-    if (v) atomicAdd(&hist[b], (u64)v | ((u64)lk[b] << 32));
-  }
+  (void)canon;
+  // records per bucket, k-mers per bucket (bounds the bucket's survivors)
+  sk_hist_body(sk_hist_lds, sk_hist_lds + (1u << p1_log2), info, hist, p1_log2, nthreads_total, sample_log2,
+               [&](size_t t, size_t p0, auto&& tally) {
+                 sk_for_each_record<W>(codes[t], codes[t + 1], bad_window(bad, p0), k, nkmax, CANON, tally);
+               });
 }
 
 // ------------------------------------------------------------------------------ 2 scan
@@ -485,12 +459,9 @@ static void launch_wc(mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sam
     mk_launch_sk_scan(c, (const u64*)hist, (const u64*)khist, start, cursor, kstart, p1_log2, sample_log2, nkmax, surv_div, part_cap,
                       surv_cap, sigmas, nseg);
   }
-  // three sub-tiles when the lanes of the chunk before listed few enough records for the shorter queues (mean + 3 sigma
-  // of a wave's total under 376: sigma ~ 2 per lane); MK_SKQ_SUBT=2|3 forces a shape
-  const long long force_subt = mk_env_int("MK_SKQ_SUBT", 0);
-  const bool three = force_subt == 3 || (force_subt != 2 && c->items_hint > 0 && c->items_hint * 64.0 + 48.0 < 376.0);
-  unsigned qcap = three ? 376u : 512u;
-  { const long long v = mk_env_int("MK_SKQ_CAP", -1); if (v >= 0 && (unsigned long long)v < qcap) qcap = (unsigned)v; }
+  const SkQueueShape shape = sk_queue_shape(c);
+  const bool three = shape.three;
+  const unsigned qcap = shape.qcap;
   const size_t qtiles = div_up(threads, (size_t)SKQ_THREADS * (three ? 3 : 2));
   const dim3 qgrid((unsigned)(qtiles < SK_SCAT_GRID ? qtiles : SK_SCAT_GRID));
   if (three)
@@ -562,12 +533,43 @@ bool mk_part_inherit(mk_ctx* c, size_t seq_len, int p1_log2, uint64_t min_count,
   return reuse;
 }
 
+// ---- what both launchers (this one and mk_launch_count_superkmer2) plan a chunk with
+int sk_p1_log2(size_t seq_len, int max_log2, size_t bucket_syms) {
+  int p1_log2 = 8;
+  while (p1_log2 < max_log2 && (seq_len >> p1_log2) > bucket_syms) ++p1_log2;
+  return p1_log2;
+}
+// Bucket sizes from a 1-in-2^s sample of the analysis threads (big chunks only: the exact histogram
+// costs as much as the scatter's own analysis). MK_SAMPLE_MIN moves the size threshold (tests).
+int sk_sample_log2(size_t seq_len, bool exact) {
+  return !exact && seq_len >= (size_t)mk_env_int("MK_SAMPLE_MIN", (long long)8 << 20) ? 3 : 0;
+}
+// a bucket with m k-mers has at most ceil(m / min_count) survivors: that bounds its region
+u64 sk_surv_div(uint64_t min_count) { return min_count > 1 ? (u64)min_count : 1; }
+// (regions sized from a sample carry its error margin: half as much room again plus the per-bucket floor)
+size_t sk_surv_cap(size_t seq_len, size_t p1, u64 surv_div, int sample_log2) {
+  if (!sample_log2) return seq_len / surv_div + p1 + 64;
+  // sum over the buckets of (estimate + 6 sigma + floor) <= 1.25 L + 6 sqrt(p1 * S * SK_R * 1.25 L) + floor * p1
+  // (Cauchy-Schwarz on the sum of square roots; L = seq_len bounds the k-mers)
+  const double L = 1.25 * (double)seq_len, S = (double)(1u << sample_log2), w = (double)SK_R;
+  return (size_t)((L + 6.0 * sqrt((double)p1 * S * w * L) + 16.0 * w * (double)p1) / (double)surv_div) + 2 * p1 + 64;
+}
+// three sub-tiles when the lanes of the chunk before listed few enough records for the shorter queues (mean + 3 sigma
+// of a wave's total under 376: sigma ~ 2 per lane); MK_SKQ_SUBT=2|3 forces a shape, MK_SKQ_CAP shortens the queues
+SkQueueShape sk_queue_shape(const mk_ctx* c) {
+  const long long force_subt = mk_env_int("MK_SKQ_SUBT", 0);
+  SkQueueShape q;
+  q.three = force_subt == 3 || (force_subt != 2 && c->items_hint > 0 && c->items_hint * 64.0 + 48.0 < 376.0);
+  q.qcap = q.three ? 376u : 512u;
+  { const long long v = mk_env_int("MK_SKQ_CAP", -1); if (v >= 0 && (unsigned long long)v < q.qcap) q.qcap = (unsigned)v; }
+  return q;
+}
+
 int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, bool exact) {
   if (seq_len == 0) return MK_OK;
   const int k = c->k;
   // ~1.2K records (~10K windows) per bucket, between 256 and SK_MAX_P1 buckets
-  int p1_log2 = 8;
-  while (p1_log2 < SK_MAX_P1_LOG2 && (seq_len >> p1_log2) > SK_BUCKET_SYMS) ++p1_log2;
+  const int p1_log2 = sk_p1_log2(seq_len, SK_MAX_P1_LOG2, SK_BUCKET_SYMS);
   c->p1_log2 = p1_log2;
   const size_t p1 = (size_t)1 << p1_log2;
   // Runs are cut into records of at most SK_NKMAX windows: the count kernel expands one record per
@@ -576,9 +578,7 @@ int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, boo
   int nkmax = 62 - k;
   if (nkmax > SK_NKMAX) nkmax = SK_NKMAX;
   { const long long v = mk_env_int("MK_NKMAX", 0); if (v >= 1 && v <= 31 && v <= 62 - k) nkmax = (int)v; }
-  // Bucket sizes from a 1-in-2^s sample of the analysis threads (big chunks only: the exact histogram
-  // costs as much as the scatter's own analysis). MK_SAMPLE_MIN moves the size threshold (tests).
-  const int sample_log2 = !exact && seq_len >= (size_t)mk_env_int("MK_SAMPLE_MIN", (long long)8 << 20) ? 3 : 0;
+  const int sample_log2 = sk_sample_log2(seq_len, exact);
   c->part_sampled = sample_log2 != 0;
   // regions per bucket: one per XCD when the sizes come from a sample (the exact partition keeps one: a bucket's exact
   // size says nothing exact about its eighths); MK_XSEG=0 keeps one everywhere (A/B runs, tests)
@@ -589,48 +589,31 @@ int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, boo
   c->part_nseg = nseg;
   const bool reuse = mk_part_inherit(c, seq_len, p1_log2, min_count, sample_log2 != 0, exact);
   int rc;
-  // hist p1 | start p1 + 1 | cursor (p1 words) | khist p1 | kstart p1 + 1 | (p1) | nsurv p1 | start of the 9 p1 regions + 1 | their cursors
-  if ((rc = mk_buf_reserve(c, c->part_meta, (7 * p1 + 16 + 14 * p1 + 8) * sizeof(u64))) != MK_OK) return rc;
+  // (room for the nine-region layout whichever this chunk uses)
+  if ((rc = mk_buf_reserve(c, c->part_meta, sk_meta_words(p1, SKC_SEG_MAX) * sizeof(u64))) != MK_OK) return rc;
   // worst case one record per window (nine regions per bucket: the shared ones alone have that much, the eight others as
   // much again -- untouched memory for the most part)
   const size_t part_cap = nseg > 1 ? 2 * seq_len + 64 : seq_len + 64;
   if ((rc = mk_buf_reserve(c, c->part, part_cap * sizeof(ulonglong2))) != MK_OK) return rc;
-  // a bucket with m k-mers has at most ceil(m / min_count) survivors: that bounds its region
-  // (regions sized from a sample carry its error margin: half as much room again plus the per-bucket floor)
-  const u64 surv_div = min_count > 1 ? (u64)min_count : 1;
-  size_t surv_cap = seq_len / surv_div + p1 + 64;
-  if (sample_log2) {
-    // sum over the buckets of (estimate + 6 sigma + floor) <= 1.25 L + 6 sqrt(p1 * S * SK_R * 1.25 L) + floor * p1
-    // (Cauchy-Schwarz on the sum of square roots; L = seq_len bounds the k-mers)
-    const double L = 1.25 * (double)seq_len, S = (double)(1u << sample_log2), w = (double)SK_R;
-    surv_cap = (size_t)((L + 6.0 * sqrt((double)p1 * S * w * L) + 16.0 * w * (double)p1) / (double)surv_div) + 2 * p1 + 64;
-  }
+  const u64 surv_div = sk_surv_div(min_count);
+  const size_t surv_cap = sk_surv_cap(seq_len, p1, surv_div, sample_log2);
   if ((rc = mk_buf_reserve(c, c->surv_keys, surv_cap * sizeof(u64))) != MK_OK) return rc;
   if ((rc = mk_buf_reserve(c, c->surv_cnts, surv_cap * sizeof(u64))) != MK_OK) return rc;
-  u64* hist = (u64*)c->part_meta.p;
-  u64* start = hist + p1;
-  SkCursor* cursor = (SkCursor*)(start + p1 + 1);  // (packed 32-bit, in the space of p1 64-bit words)
-  u64* khist = start + p1 + 1 + p1;
-  u64* kstart = khist + p1;
-  u64* nsurv = kstart + p1 + 1 + p1;  // (the p1 words in between: a cursor array the 8-byte-key path uses)
-  if (nseg > 1) {
-    start = hist + 7 * p1 + 16;
-    cursor = (SkCursor*)(start + 9 * p1 + 8);
-  }
-  if (!reuse) MK_HIP(hipMemsetAsync(hist, 0, (7 * p1 + 8) * sizeof(u64), c->stream));
+  const SkMeta m = sk_meta(c->part_meta.p, p1, nseg);
+  if (!reuse) MK_HIP(hipMemsetAsync(m.hist, 0, sk_meta_cleared_words(p1) * sizeof(u64), c->stream));
   mk_prof_begin(c, MK_K_PART);
   // (the canonical instances live in a translation unit of their own, mk_skmer_canon.hip: half the compile time each)
   if (c->canonical) {
-    if (!mk_sk_partition_canon(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, hist, start, cursor, khist, kstart, reuse, nseg)) {
+    if (!mk_sk_partition_canon(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, m.hist, m.start, m.cursor, m.khist, m.kstart, reuse, nseg)) {
       c->err = "mk_launch_count_superkmer: k out of range";
       return MK_ERR_ARG;
     }
-  } else if (!sk_partition<false>(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, hist, start, cursor, khist, kstart, reuse, nseg)) {
+  } else if (!sk_partition<false>(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, m.hist, m.start, m.cursor, m.khist, m.kstart, reuse, nseg)) {
     c->err = "mk_launch_count_superkmer: k out of range";
     return MK_ERR_ARG;
   }
   mk_prof_end(c);
-  if ((rc = mk_launch_sk_count(c, (const u64*)start, cursor, (const u64*)kstart, nsurv, min_count, p1, nseg)) != MK_OK) return rc;
+  if ((rc = mk_launch_sk_count(c, (const u64*)m.start, m.cursor, (const u64*)m.kstart, m.nsurv, min_count, p1, nseg)) != MK_OK) return rc;
   MK_HIP(hipGetLastError());
   c->surv_regions = 1;
   return MK_OK;

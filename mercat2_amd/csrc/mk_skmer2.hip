@@ -19,7 +19,6 @@
 #include "mk_skmer_dev.h"
 #include <cstdlib>
 
-#define SK2_R SK_R
 #define SK2_HIST_THREADS 1024   // (two 64 KB LDS histograms per workgroup: one workgroup per CU)
 #define SK2_SCAT_THREADS 1024
 #ifndef SK2_MAX_P1_LOG2
@@ -30,9 +29,9 @@
 #ifndef SK2C_SLOTS
 #define SK2C_SLOTS 6144   // 20 bytes each: 120 KB of LDS, + 32 KB of deferred-key stacks (4096: 25 % slower at k = 63, twice the sub-range passes)
 #endif
+#define SK2C_THREADS 1024
 #define SK2C_WAVES (SK2C_THREADS / 64)
 #define SK2C_QCAP 128     // deferred keys a wave can hold: < 64 left over + one slot x 64 lanes pushed at once
-#define SK2C_THREADS 1024
 #ifndef SK2C_TARGET
 #define SK2C_TARGET (SK2C_SLOTS * 6 / 10)
 #endif
@@ -152,7 +151,7 @@ __device__ __forceinline__ unsigned sk2_valid32(const u64* __restrict__ bad, siz
   const u64 kmask = (k >= 64) ? ~0ull : ((1ull << k) - 1);
   unsigned v = 0;
 #pragma unroll
-  for (int j = 0; j < SK2_R; ++j) {
+  for (int j = 0; j < SK_R; ++j) {
     const u64 win = (b_lo >> j) | (j ? (b_hi << (64 - j)) : 0ull);  // bad bits j .. j+63
     v |= ((win & kmask) == 0) ? (1u << j) : 0u;
   }
@@ -177,7 +176,7 @@ __device__ __forceinline__ Sk2Rec sk2_make_record(u64 w0, u64 w1, u64 w2, u64 w3
 }
 
 // ------------------------------------------------------------------------------ hist / scatter
-// (sample_log2 > 0: one pseudo-randomly chosen analysis thread of every 2^sample_log2, as in mk_skmer.hip)
+// (the histogram's body, and what sample_log2 does: sk_hist_body, mk_skmer_dev.h)
 template <bool CANON>
 __global__ __launch_bounds__(SK2_HIST_THREADS) void mk_sk2_hist_k(const u64* __restrict__ codes, const u64* __restrict__ bad,
                                                                   const MkChunkInfo* __restrict__ info, u64* __restrict__ hist,
@@ -185,22 +184,8 @@ __global__ __launch_bounds__(SK2_HIST_THREADS) void mk_sk2_hist_k(const u64* __r
                                                                   size_t nthreads_total, int sample_log2) {
   __shared__ unsigned lh[SK2_MAX_P1];
   __shared__ unsigned lk[SK2_MAX_P1];
-  const unsigned p1 = 1u << p1_log2;
-  for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) { lh[i] = 0; lk[i] = 0; }
-  __syncthreads();
-  const size_t seq_len = info->seq_len;
-  const size_t ngroups = (nthreads_total + ((size_t)1 << sample_log2) - 1) >> sample_log2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * blockDim.x) {
-    size_t t = g;
-    if (sample_log2) t = (g << sample_log2) + (((unsigned)g * 0x9E3779B1u >> 7) & ((1u << sample_log2) - 1));
-    const size_t p0 = t * SK2_R;
-    if (t >= nthreads_total || p0 >= seq_len) continue;
+  sk_hist_body(lh, lk, info, hist, p1_log2, nthreads_total, sample_log2, [&](size_t t, size_t p0, auto&& tally) {
     const u64 w0 = codes[t], w1 = codes[t + 1];
-    auto tally = [&](int, int nk, unsigned mm) {
-      const unsigned b = sk2_bucket(mm, p1_log2);
-      atomicAdd(&lh[b], 1u);
-      atomicAdd(&lk[b], (unsigned)nk);
-    };
     if constexpr (CANON) {
       const Sk2CRuns r = sk2c_analyse(w0, w1, codes[t + 2], sk2_valid32(bad, p0, k), k);
       sk2c_walk(r, tally);
@@ -208,14 +193,7 @@ __global__ __launch_bounds__(SK2_HIST_THREADS) void mk_sk2_hist_k(const u64* __r
       const Sk2Runs r = sk2_analyse(w0, w1, sk2_valid32(bad, p0, k));
       sk2_walk(r, w0, w1, tally);
     }
-  }
-  __syncthreads();
-  for (unsigned b = threadIdx.x; b < p1; b += blockDim.x) {
-    const unsigned v = lh[b];
-    // one global add per bucket: records in the low word, k-mers in the high word (a chunk holds fewer than 2^32
-    // symbols, so neither half can carry) -- the per-workgroup flush is most of this kernel's HBM traffic
-    if (v) atomicAdd(&hist[b], (u64)v | ((u64)lk[b] << 32));
-  }
+  });
 }
 
 template <bool CANON>
@@ -230,14 +208,13 @@ __global__ __launch_bounds__(SK2_SCAT_THREADS) void mk_sk2_scatter_k(const u64* 
   __syncthreads();
   if (s_abort) return;  // the regions do not fit the buffers: nothing may be written
   unsigned spilled = 0;
-  constexpr int NB = SK2_MAX_P1 / SK2_SCAT_THREADS;
   const unsigned p1 = 1u << p1_log2;
   const size_t seq_len = info->seq_len;
   for (unsigned i = threadIdx.x; i < p1; i += blockDim.x) lh[i] = 0;
   __syncthreads();
   for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const size_t t = tile * SK2_SCAT_THREADS + threadIdx.x;
-    const size_t p0 = t * SK2_R;
+    const size_t p0 = t * SK_R;
     Sk2Runs runs;
     Sk2CRuns cruns;  // (canonical mode)
     runs.valid = 0;
@@ -258,31 +235,7 @@ __global__ __launch_bounds__(SK2_SCAT_THREADS) void mk_sk2_scatter_k(const u64* 
       }
     }
     __syncthreads();
-#ifndef SK_PLAIN_CURSORS
-    if (p1 == SK2_MAX_P1) {  // (8192 buckets, 8 per thread: all reservations in flight together, mk_skmer_dev.h)
-      static_assert(NB == 8 && SK2_SCAT_THREADS == 1024, "sk_reserve8");
-      unsigned v[NB], at[NB];
-#pragma unroll
-      for (int i = 0; i < NB; ++i) v[i] = lh[threadIdx.x + i * SK2_SCAT_THREADS];
-      spilled |= sk_reserve8<SK2_SCAT_THREADS>(v, cursor, start, ~0u, at);
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        gbase[threadIdx.x + i * SK2_SCAT_THREADS] = at[i];
-        lh[threadIdx.x + i * SK2_SCAT_THREADS] = 0;
-      }
-    } else
-#endif
-    {  // (small chunks, fewer buckets: one at a time)
-      for (unsigned b = threadIdx.x; b < p1; b += SK2_SCAT_THREADS) {
-        const unsigned v = lh[b];
-        const u64 r = v ? (u64)atomicAdd(&cursor[b], v) : 0ull;
-        // a run that would cross the end of its bucket's region (sampled sizes only) is not written
-        const bool fits = v == 0 || r + v <= start[b + 1];
-        spilled |= fits ? 0u : 1u;
-        gbase[b] = fits ? (unsigned)r : ~0u;
-        lh[b] = 0;
-      }
-    }
+    sk_reserve_tile<SK2_SCAT_THREADS, SK2_MAX_P1>(lh, gbase, cursor, start, p1, ~0u, spilled);
     __syncthreads();
     if (CANON ? cruns.starts : runs.starts) {
       const u64 w2 = codes[t + 2], w3 = codes[t + 3];
@@ -331,7 +284,6 @@ __global__ __launch_bounds__(SK2Q_THREADS) __attribute__((amdgpu_waves_per_eu(4,
   __syncthreads();
   if (s_abort) return;
   unsigned spilled = 0;
-  constexpr int NB = SK2_MAX_P1 / SK2Q_THREADS;
   const unsigned p1 = 1u << p1_log2;
   const size_t seq_len = info->seq_len;
   const int lane = threadIdx.x & 63;
@@ -344,7 +296,7 @@ __global__ __launch_bounds__(SK2Q_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 #pragma unroll
     for (int st = 0; st < SK2Q_SUBT; ++st) {
       const size_t t = (tile * SK2Q_SUBT + st) * SK2Q_THREADS + threadIdx.x;
-      const size_t p0 = t * SK2_R;
+      const size_t p0 = t * SK_R;
       Sk2Runs runs;
       runs.valid = 0;
       runs.starts = 0;
@@ -372,7 +324,7 @@ __global__ __launch_bounds__(SK2Q_THREADS) __attribute__((amdgpu_waves_per_eu(4,
           const int j = __ffs(todo) - 1;
           todo &= todo - 1;
           const unsigned stop = (s2 | ~runs.valid) & ~((2u << j) - 1);
-          const int nk = (stop ? (__ffs(stop) - 1) : SK2_R) - j;
+          const int nk = (stop ? (__ffs(stop) - 1) : SK_R) - j;
           const u64 pw = j < 10 ? runs.pos[0] : (j < 20 ? runs.pos[1] : (j < 30 ? runs.pos[2] : runs.pos[3]));
           const unsigned best = (unsigned)(pw >> (6 * (j % 10))) & 63u;
           myq[at++] = (unsigned)lane | ((unsigned)j << 6) | ((unsigned)nk << 11) | (best << 16);
@@ -397,29 +349,7 @@ __global__ __launch_bounds__(SK2Q_THREADS) __attribute__((amdgpu_waves_per_eu(4,
       }
     }
     __syncthreads();
-#ifndef SK_PLAIN_CURSORS
-    if (p1 == SK2_MAX_P1) {
-      static_assert(NB % 8 == 0, "sk_reserve8");
-#pragma unroll
-      for (int h = 0; h < NB; h += 8) {
-        unsigned v[8], at[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = lh[threadIdx.x + (h + i) * SK2Q_THREADS];
-        spilled |= sk_reserve8<SK2Q_THREADS>(v, cursor + h * SK2Q_THREADS, start + h * SK2Q_THREADS, SK2_NOFIT, at);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lh[threadIdx.x + (h + i) * SK2Q_THREADS] = at[i];
-      }
-    } else
-#endif
-    {  // (small chunks, fewer buckets: one at a time)
-      for (unsigned b = threadIdx.x; b < p1; b += SK2Q_THREADS) {
-        const unsigned v = lh[b];
-        const u64 r = v ? (u64)atomicAdd(&cursor[b], v) : 0ull;
-        const bool fits = v == 0 || r + v <= start[b + 1];
-        spilled |= fits ? 0u : 1u;
-        lh[b] = fits ? (unsigned)r : SK2_NOFIT;
-      }
-    }
+    sk_reserve_tile<SK2Q_THREADS, SK2_MAX_P1>(lh, lh, cursor, start, p1, SK2_NOFIT, spilled);
     __syncthreads();
 #pragma unroll
     for (int st = 0; st < SK2Q_SUBT; ++st) {
@@ -438,7 +368,7 @@ __global__ __launch_bounds__(SK2Q_THREADS) __attribute__((amdgpu_waves_per_eu(4,
         }
       } else {
         const size_t t = (tile * SK2Q_SUBT + st) * SK2Q_THREADS + threadIdx.x;
-        const size_t p0 = t * SK2_R;
+        const size_t p0 = t * SK_R;
         if (p0 < seq_len) {
           const u64* const wp = &pk_x[st][wv][lane];
           const ulonglong2 wa = make_ulonglong2(wp[0], wp[1]);
@@ -469,20 +399,24 @@ __device__ __forceinline__ unsigned sk2c_hash(u64 hi, u64 lo) {
   return h ^ (h >> 15);
 }
 
-// Home slot of a hash (any table size).
-__device__ __forceinline__ unsigned sk2c_home(unsigned h) { return (unsigned)(((u64)h * SK2C_SLOTS) >> 32); }
+// Home slot of a hash in a table of SLOTS slots (any table size).
+template <int SLOTS>
+__device__ __forceinline__ unsigned sk2_home(unsigned h) { return (unsigned)(((u64)h * SLOTS) >> 32); }
+__device__ __forceinline__ unsigned sk2c_home(unsigned h) { return sk2_home<SK2C_SLOTS>(h); }
 
 __device__ __forceinline__ unsigned sk2c_lane_rank(u64 mask) {  // set bits of mask below this lane
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
-// Insert one 128-bit key, probing from its home slot (see the protocol in the header).  The lane that wins a slot
-// writes the key and publishes inside the loop iteration in which it won.  tkey holds {hi, lo} side by side: one
-// 16-byte LDS access per key.
-// At most max_probe slots: SK2C_MAX_PROBE, or the whole table at the last split level.
-__device__ __forceinline__ void sk2c_insert(ulonglong2* tkey, unsigned* tcnt, unsigned* ovf, u64 hi, u64 lo, unsigned h,
-                                            int max_probe) {
-  unsigned slot = sk2c_home(h);
+// Insert one 128-bit key into a table of SLOTS slots, probing from its home slot (see the protocol in the header).
+// The lane that wins a slot writes the key and publishes inside the loop iteration in which it won.  tkey holds
+// {hi, lo} side by side: one 16-byte LDS access per key.
+// At most max_probe slots: SK2C_MAX_PROBE / SK2P_MAX_PROBE, or the whole table at the exact kernel's last split level
+// (DESIGN.md section 8h).
+template <int SLOTS>
+__device__ __forceinline__ void sk2_insert(ulonglong2* tkey, unsigned* tcnt, unsigned* ovf, u64 hi, u64 lo, unsigned h,
+                                           int max_probe) {
+  unsigned slot = sk2_home<SLOTS>(h);
   bool done = false;
 #pragma unroll 1
   for (int probe = 0; probe < max_probe && !done;) {
@@ -503,7 +437,7 @@ __device__ __forceinline__ void sk2c_insert(ulonglong2* tkey, unsigned* tcnt, un
         atomicAdd(&tcnt[slot], 1u);
         done = true;
       } else {
-        slot = slot + 1 == SK2C_SLOTS ? 0u : slot + 1;
+        slot = slot + 1 == SLOTS ? 0u : slot + 1;
         ++probe;
       }
     }
@@ -511,14 +445,116 @@ __device__ __forceinline__ void sk2c_insert(ulonglong2* tkey, unsigned* tcnt, un
   if (!done) atomicOr(ovf, 1u);
 }
 
-// The top n (<= 64) deferred keys of this wave's stack, one per lane, through the general insert.
-__device__ __forceinline__ void sk2c_drain(ulonglong2* tkey, unsigned* tcnt, const ulonglong2* q, unsigned& qcount, unsigned n,
-                                           unsigned* ovf, int max_probe) {
+// The top n (<= 64) keys of this wave's stack, one per lane, through the general insert.
+template <int SLOTS>
+__device__ __forceinline__ void sk2_drain(ulonglong2* tkey, unsigned* tcnt, const ulonglong2* q, unsigned& qcount, unsigned n,
+                                          unsigned* ovf, int max_probe) {
   const unsigned lane = threadIdx.x & 63;
   qcount -= n;
   if (lane < n) {
     const ulonglong2 key = q[qcount + lane];
-    sk2c_insert(tkey, tcnt, ovf, key.x, key.y, sk2c_hash(key.x, key.y), max_probe);
+    sk2_insert<SLOTS>(tkey, tcnt, ovf, key.x, key.y, sk2c_hash(key.x, key.y), max_probe);
+  }
+}
+
+// The keys u of `flags` (this lane's share of khi / klo) onto the wave's stack q, their places from ballots: the
+// whole wave is here.  Whenever the stack holds 64 keys they are inserted, every lane busy.
+template <int SLOTS>
+__device__ __forceinline__ void sk2_push_keys(ulonglong2* tkey, unsigned* tcnt, ulonglong2* q, unsigned& qcount, unsigned flags,
+                                              const u64 (&khi)[SK2_NKMAX], const u64 (&klo)[SK2_NKMAX], unsigned* ovf,
+                                              int max_probe) {
+#pragma unroll
+  for (int u = 0; u < SK2_NKMAX; ++u) {
+    const bool f = (flags >> u) & 1u;
+    const u64 m = __ballot(f);
+    if (m) {
+      if (f) q[qcount + sk2c_lane_rank(m)] = make_ulonglong2(khi[u], klo[u]);
+      qcount += (unsigned)__popcll(m);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      if (qcount >= 64) sk2_drain<SLOTS>(tkey, tcnt, q, qcount, 64u, ovf, max_probe);
+    }
+  }
+}
+
+// Record j of a bucket's n, or an empty one (the whole wave walks the record loop together).
+__device__ __forceinline__ Sk2Rec sk2_load_record(const Sk2Rec* __restrict__ src, u64 j, u64 n) {
+  Sk2Rec rec;
+  rec.r0 = rec.r1 = rec.r2 = rec.nk = 0;
+  if (j < n) rec = src[j];
+  return rec;
+}
+
+// f(u, hi, lo) for the SK2_NKMAX keys a record can hold (u >= rec.nk: not keys of the record; the caller masks them).
+template <bool CANON, class F>
+__device__ __forceinline__ void sk2_for_each_key(const Sk2Rec& rec, u64 lomask, int k, F&& f) {
+  u64 x0 = rec.r0, x1 = rec.r1, x2 = rec.r2;
+#pragma unroll
+  for (int u = 0; u < SK2_NKMAX; ++u) {
+    u64 hi = x0, lo = x1 & lomask;
+    if constexpr (CANON) sk2_canon128(hi, lo, k);
+    x0 = (x0 << 2) | (x1 >> 62);
+    x1 = (x1 << 2) | (x2 >> 62);
+    x2 <<= 2;
+    f(u, hi, lo);
+  }
+}
+
+// The emit sweep between barriers A and B of a pass: every slot's count is read and cleared; the entries that reached
+// min_count (none of a pass that overflowed) go to the bucket's survivor region as {hi, lo, count}, their places
+// reserved through s_emit.  The sweep reads the counts only; a slot's key only when its count reaches min_count.
+// occupied(n) is called between the two halves with the thread's number of slots in use.
+template <int SLOTS, class F>
+__device__ __forceinline__ void sk2_emit_sweep(const ulonglong2* tkey, unsigned* tcnt, bool over, u64 min_count, unsigned emitted,
+                                               unsigned* s_emit, u64 region, MkChunkInfo* info, u64* __restrict__ my_hi,
+                                               u64* __restrict__ my_lo, u64* __restrict__ my_cnt, F&& occupied) {
+  constexpr int PER = SLOTS / SK2C_THREADS;
+  unsigned ec[PER];
+  unsigned mine = 0, occ = 0;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const unsigned i = q * SK2C_THREADS + threadIdx.x;
+    ec[q] = tcnt[i];
+    tcnt[i] = 0;
+    occ += ec[q] != 0;
+    if (over || (u64)ec[q] < min_count) ec[q] = 0;
+    mine += ec[q] != 0;
+  }
+  occupied(occ);
+  if (mine) {
+    const unsigned at = emitted + atomicAdd(s_emit, mine);
+    unsigned o = 0;
+    if ((u64)at + mine > region) {  // only a region sized from a sampled histogram can be too small
+      atomicOr(&info->part_overflow, 8ull);
+      mine = 0;
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      if (mine && ec[q]) {
+        const ulonglong2 key = tkey[q * SK2C_THREADS + threadIdx.x];
+        my_hi[at + o] = key.x;
+        my_lo[at + o] = key.y;
+        my_cnt[at + o] = ec[q];
+        ++o;
+      }
+    }
+  }
+}
+
+// The end of a count kernel: one global add per workgroup and total.
+// windows / survivors of THIS kernel go to the fields the one-word path uses; the caller folds them into the
+// by-reference totals once the chunk is known to be complete (they may have to be discarded)
+__device__ __forceinline__ void sk2_finish_kernel(MkChunkInfo* info, unsigned long long* s_windows, u64 windows, u64 records_total,
+                                                  u64 distinct_total, u64 survivors_total, u64 nerr, u64 npre_void) {
+  for (int d = 32; d > 0; d >>= 1) windows += __shfl_down(windows, d);
+  if ((threadIdx.x & 63) == 0 && windows) atomicAdd(s_windows, (unsigned long long)windows);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (*s_windows) atomicAdd(&info->windows, (u64)*s_windows);
+    if (records_total) atomicAdd(&info->records, records_total);
+    if (distinct_total) atomicAdd(&info->distinct, distinct_total);
+    if (survivors_total) atomicAdd(&info->survivors, survivors_total);
+    if (nerr) atomicAdd(&info->errors, nerr);
+    if (npre_void) atomicAdd(&info->pre_void, npre_void);
   }
 }
 
@@ -578,29 +614,19 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_count_k(const Sk2Rec* __r
         // (the whole wave walks the record loop together: lanes past the end hold an empty record)
         for (u64 jb = 0; jb < n; jb += SK2C_THREADS) {
           const u64 j = jb + threadIdx.x;
-          Sk2Rec rec;
-          rec.r0 = rec.r1 = rec.r2 = rec.nk = 0;
-          if (j < n) rec = src[j];
+          const Sk2Rec rec = sk2_load_record(src, j, n);
           const int nk = (int)rec.nk;  // <= SK2_NKMAX
           win_pass += counted ? 0 : (u64)nk;
           u64 khi[SK2_NKMAX], klo[SK2_NKMAX];
           unsigned hh[SK2_NKMAX], st[SK2_NKMAX];
           unsigned alive = 0;
-          {
-            u64 x0 = rec.r0, x1 = rec.r1, x2 = rec.r2;
-#pragma unroll
-            for (int u = 0; u < SK2_NKMAX; ++u) {
-              khi[u] = x0;
-              klo[u] = x1 & lomask;
-              if constexpr (CANON) sk2_canon128(khi[u], klo[u], k);
-              x0 = (x0 << 2) | (x1 >> 62);
-              x1 = (x1 << 2) | (x2 >> 62);
-              x2 <<= 2;
-              hh[u] = sk2c_hash(khi[u], klo[u]);
-              const bool mine = u < nk && (!s || ((hh[u] & ((1u << SK2C_SUB_BITS) - 1)) >> sel_shift) == idx);
-              alive |= mine ? (1u << u) : 0u;
-            }
-          }
+          sk2_for_each_key<CANON>(rec, lomask, k, [&](int u, u64 hi, u64 lo) {
+            khi[u] = hi;
+            klo[u] = lo;
+            hh[u] = sk2c_hash(hi, lo);
+            const bool mine = u < nk && (!s || ((hh[u] & ((1u << SK2C_SUB_BITS) - 1)) >> sel_shift) == idx);
+            alive |= mine ? (1u << u) : 0u;
+          });
           // batched first probe, compare-and-swap first: a free home slot (most keys of a read set at 33 <= k <= 64 are
           // new) is claimed by the very first LDS operation, the key goes in with one 16-byte write and the count is
           // published; a slot that holds a count has its key read (one 16-byte read) and compared.  Whatever does not
@@ -633,59 +659,18 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_count_k(const Sk2Rec* __r
             if (!(st[u] & SK2C_LOCK) && ok[u].x == khi[u] && ok[u].y == klo[u]) atomicAdd(&tcnt[sk2c_home(hh[u])], 1u);
             else defer |= 1u << u;
           }
-#pragma unroll
-          for (int u = 0; u < SK2_NKMAX; ++u) {
-            const bool f = (defer >> u) & 1u;
-            const u64 m = __ballot(f);
-            if (m) {
-              if (f) myq[qcount + sk2c_lane_rank(m)] = make_ulonglong2(khi[u], klo[u]);
-              qcount += (unsigned)__popcll(m);
-              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-              if (qcount >= 64) sk2c_drain(tkey, tcnt, myq, qcount, 64u, ovf, max_probe);
-            }
-          }
+          sk2_push_keys<SK2C_SLOTS>(tkey, tcnt, myq, qcount, defer, khi, klo, ovf, max_probe);
           if (__hip_atomic_load(ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
         }
-        if (qcount) sk2c_drain(tkey, tcnt, myq, qcount, qcount, ovf, max_probe);  // (< 64 left)
+        if (qcount) sk2_drain<SK2C_SLOTS>(tkey, tcnt, myq, qcount, qcount, ovf, max_probe);  // (< 64 left)
         __syncthreads();  // A
         if (threadIdx.x == 0) cursor[b] = lo_r;  // back to the region's start: the next chunk may inherit the regions (mk_skmer.hip)
         const bool over = s_overflow[par] != 0;
         if (threadIdx.x == 0) { s_distinct[par ^ 1] = 0; s_overflow[par ^ 1] = 0; s_emit[par ^ 1] = 0; }
-        {
-          // the sweep reads the counts only; a slot's key only when its count reaches min_count
-          constexpr int PER = SK2C_SLOTS / SK2C_THREADS;
-          unsigned ec[PER];
-          unsigned mine = 0, occ = 0;
-#pragma unroll
-          for (int q = 0; q < PER; ++q) {
-            const unsigned i = q * SK2C_THREADS + threadIdx.x;
-            ec[q] = tcnt[i];
-            tcnt[i] = 0;
-            occ += ec[q] != 0;
-            if (over || (u64)ec[q] < min_count) ec[q] = 0;
-            mine += ec[q] != 0;
-          }
+        sk2_emit_sweep<SK2C_SLOTS>(tkey, tcnt, over, min_count, emitted, &s_emit[par], region, info, my_hi, my_lo, my_cnt, [&](unsigned occ) {
           occ = mk_wave_sum(occ);
           if (lane == 0 && occ && !over) atomicAdd(&s_distinct[par], occ);
-          if (mine) {
-            const unsigned at = emitted + atomicAdd(&s_emit[par], mine);
-            unsigned o = 0;
-            if ((u64)at + mine > region) {  // only a region sized from a sampled histogram can be too small
-              atomicOr(&info->part_overflow, 8ull);
-              mine = 0;
-            }
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-              if (mine && ec[q]) {
-                const ulonglong2 key = tkey[q * SK2C_THREADS + threadIdx.x];
-                my_hi[at + o] = key.x;
-                my_lo[at + o] = key.y;
-                my_cnt[at + o] = ec[q];
-                ++o;
-              }
-            }
-          }
-        }
+        });
         __syncthreads();  // B
         emitted += s_emit[par];
         distinct_total += s_distinct[par];
@@ -711,20 +696,7 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_count_k(const Sk2Rec* __r
     if (threadIdx.x == 0) nsurv[b] = emitted;
     survivors_total += emitted;
   }
-  {  // one global add per workgroup
-    for (int d = 32; d > 0; d >>= 1) windows += __shfl_down(windows, d);
-    if (lane == 0 && windows) atomicAdd(&s_windows, (unsigned long long)windows);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    // windows / survivors of THIS kernel go to the fields the one-word path uses; the caller folds them into
-    // the by-reference totals once the chunk is known to be complete (they may have to be discarded)
-    if (s_windows) atomicAdd(&info->windows, (u64)s_windows);
-    if (records_total) atomicAdd(&info->records, records_total);
-    if (distinct_total) atomicAdd(&info->distinct, distinct_total);
-    if (survivors_total) atomicAdd(&info->survivors, survivors_total);
-    if (nerr) atomicAdd(&info->errors, nerr);
-  }
+  sk2_finish_kernel(info, &s_windows, windows, records_total, distinct_total, survivors_total, nerr, 0ull);
 }
 
 // ------------------------------------------------------------------- count with a counting pre-filter
@@ -751,36 +723,6 @@ __device__ __forceinline__ unsigned sk2p_hash(u64 hi, u64 lo) {
   const unsigned a = (unsigned)f, b = (unsigned)(f >> 32);
   unsigned h = __umul24(a, 0x9E3779u) ^ __umul24(__funnelshift_r(a, b, 24), 0x85EBCBu) ^ __umul24(b >> 16, 0xC2B2AFu);
   return h ^ (h >> 15);
-}
-
-__device__ __forceinline__ void sk2p_insert(ulonglong2* tkey, unsigned* tcnt, unsigned* ovf, u64 hi, u64 lo, unsigned h) {
-  unsigned slot = (unsigned)(((u64)h * SK2P_SLOTS) >> 32);
-  bool done = false;
-#pragma unroll 1
-  for (int probe = 0; probe < SK2P_MAX_PROBE && !done;) {
-    unsigned c = __hip_atomic_load(&tcnt[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (c == 0) {
-      c = atomicCAS(&tcnt[slot], 0u, SK2C_LOCK);
-      if (c == 0) {
-        tkey[slot] = make_ulonglong2(hi, lo);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        atomicAdd(&tcnt[slot], 1u - SK2C_LOCK);
-        done = true;
-      }
-    }
-    if (!done && !(c & SK2C_LOCK)) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      const ulonglong2 o = tkey[slot];
-      if (o.x == hi && o.y == lo) {
-        atomicAdd(&tcnt[slot], 1u);
-        done = true;
-      } else {
-        slot = slot + 1 == SK2P_SLOTS ? 0u : slot + 1;
-        ++probe;
-      }
-    }
-  }
-  if (!done) atomicOr(ovf, 1u);
 }
 
 template <bool CANON>
@@ -831,22 +773,13 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
         // ---- P: count every key of the sub-range into its counter
         for (u64 jb = 0; jb < n; jb += SK2C_THREADS) {
           const u64 j = jb + threadIdx.x;
-          Sk2Rec rec;
-          rec.r0 = rec.r1 = rec.r2 = rec.nk = 0;
-          if (j < n) rec = src[j];
+          const Sk2Rec rec = sk2_load_record(src, j, n);
           const int nk = (int)rec.nk;
           win_pass += counted ? 0 : (u64)nk;
-          u64 x0 = rec.r0, x1 = rec.r1, x2 = rec.r2;
-#pragma unroll
-          for (int u = 0; u < SK2_NKMAX; ++u) {
-            u64 khi = x0, klo = x1 & lomask;
-            if constexpr (CANON) sk2_canon128(khi, klo, k);
-            x0 = (x0 << 2) | (x1 >> 62);
-            x1 = (x1 << 2) | (x2 >> 62);
-            x2 <<= 2;
+          sk2_for_each_key<CANON>(rec, lomask, k, [&](int u, u64 khi, u64 klo) {
             const unsigned h = sk2p_hash(khi, klo);
             if (u < nk && (!s || (h >> sel_shift) == idx)) atomicAdd(&cnt32[h & (SK2P_CNT - 1)], 1u);
-          }
+          });
         }
         __syncthreads();  // P done: the counters are final
         // ---- Q: the candidates into the exact table -- via the wave's stack (positions from ballots), 64 at a time with
@@ -855,53 +788,23 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
         unsigned qcount = 0;
         for (u64 jb = 0; jb < n; jb += SK2C_THREADS) {
           const u64 j = jb + threadIdx.x;
-          Sk2Rec rec;
-          rec.r0 = rec.r1 = rec.r2 = rec.nk = 0;
-          if (j < n) rec = src[j];
+          const Sk2Rec rec = sk2_load_record(src, j, n);
           const int nk = (int)rec.nk;
-          u64 x0 = rec.r0, x1 = rec.r1, x2 = rec.r2;
           unsigned cv[SK2_NKMAX];
           u64 khi[SK2_NKMAX], klo[SK2_NKMAX];
           unsigned cand = 0;
-#pragma unroll
-          for (int u = 0; u < SK2_NKMAX; ++u) {
-            khi[u] = x0;
-            klo[u] = x1 & lomask;
-            if constexpr (CANON) sk2_canon128(khi[u], klo[u], k);
-            x0 = (x0 << 2) | (x1 >> 62);
-            x1 = (x1 << 2) | (x2 >> 62);
-            x2 <<= 2;
-            const unsigned h = sk2p_hash(khi[u], klo[u]);
+          sk2_for_each_key<CANON>(rec, lomask, k, [&](int u, u64 hi, u64 lo) {
+            khi[u] = hi;
+            klo[u] = lo;
+            const unsigned h = sk2p_hash(hi, lo);
             const bool mine = u < nk && (!s || (h >> sel_shift) == idx);
             cv[u] = mine ? cnt32[h & (SK2P_CNT - 1)] : 0u;
-          }
+          });
 #pragma unroll
           for (int u = 0; u < SK2_NKMAX; ++u) cand |= (cv[u] >= need && cv[u]) ? (1u << u) : 0u;
-          if (__any(cand != 0)) {
-#pragma unroll
-            for (int u = 0; u < SK2_NKMAX; ++u) {
-              const bool f = (cand >> u) & 1u;
-              const u64 m = __ballot(f);
-              if (m) {
-                if (f) myq[qcount + sk2c_lane_rank(m)] = make_ulonglong2(khi[u], klo[u]);
-                qcount += (unsigned)__popcll(m);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                if (qcount >= 64) {
-                  qcount -= 64;
-                  const ulonglong2 key = myq[qcount + lane];
-                  sk2p_insert(tkey, tcnt, ovf, key.x, key.y, sk2c_hash(key.x, key.y));
-                }
-              }
-            }
-          }
+          if (__any(cand != 0)) sk2_push_keys<SK2P_SLOTS>(tkey, tcnt, myq, qcount, cand, khi, klo, ovf, SK2P_MAX_PROBE);
         }
-        if (qcount) {  // (< 64 left)
-          if ((unsigned)lane < qcount) {
-            const ulonglong2 key = myq[lane];
-            sk2p_insert(tkey, tcnt, ovf, key.x, key.y, sk2c_hash(key.x, key.y));
-          }
-          qcount = 0;
-        }
+        if (qcount) sk2_drain<SK2P_SLOTS>(tkey, tcnt, myq, qcount, qcount, ovf, SK2P_MAX_PROBE);  // (< 64 left)
         __syncthreads();  // A: every insert of the pass is in the table
         if (threadIdx.x == 0) cursor[b] = lo_r;  // back to the region's start: the next chunk may inherit the regions
         const bool over = s_overflow[par] != 0;
@@ -918,37 +821,9 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
           }
           occ = mk_wave_sum(occ);
           if (lane == 0 && occ && !over) atomicAdd(&s_distinct[par], occ);
-          // exact table: emit what reached min_count, clear
-          constexpr int PER = SK2P_SLOTS / SK2C_THREADS;
-          unsigned ec[PER];
-          unsigned mine = 0;
-#pragma unroll
-          for (int q = 0; q < PER; ++q) {
-            const unsigned i = q * SK2C_THREADS + threadIdx.x;
-            ec[q] = tcnt[i];
-            tcnt[i] = 0;
-            if (over || (u64)ec[q] < min_count) ec[q] = 0;
-            mine += ec[q] != 0;
-          }
-          if (mine) {
-            const unsigned at = emitted + atomicAdd(&s_emit[par], mine);
-            unsigned o = 0;
-            if ((u64)at + mine > region) {
-              atomicOr(&info->part_overflow, 8ull);
-              mine = 0;
-            }
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-              if (mine && ec[q]) {
-                const ulonglong2 key = tkey[q * SK2C_THREADS + threadIdx.x];
-                my_hi[at + o] = key.x;
-                my_lo[at + o] = key.y;
-                my_cnt[at + o] = ec[q];
-                ++o;
-              }
-            }
-          }
         }
+        // exact table: emit what reached min_count, clear
+        sk2_emit_sweep<SK2P_SLOTS>(tkey, tcnt, over, min_count, emitted, &s_emit[par], region, info, my_hi, my_lo, my_cnt, [](unsigned) {});
         __syncthreads();  // B
         emitted += s_emit[par];
         distinct_total += s_distinct[par];
@@ -972,19 +847,7 @@ __global__ __launch_bounds__(SK2C_THREADS) void mk_sk2_countp_k(const Sk2Rec* __
     if (threadIdx.x == 0) nsurv[b] = emitted;
     survivors_total += emitted;
   }
-  {
-    for (int d = 32; d > 0; d >>= 1) windows += __shfl_down(windows, d);
-    if (lane == 0 && windows) atomicAdd(&s_windows, (unsigned long long)windows);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (s_windows) atomicAdd(&info->windows, (u64)s_windows);
-    if (records_total) atomicAdd(&info->records, records_total);
-    if (distinct_total) atomicAdd(&info->distinct, distinct_total);
-    if (survivors_total) atomicAdd(&info->survivors, survivors_total);
-    if (nerr) atomicAdd(&info->errors, nerr);
-    if (npre_void) atomicAdd(&info->pre_void, npre_void);
-  }
+  sk2_finish_kernel(info, &s_windows, windows, records_total, distinct_total, survivors_total, nerr, npre_void);
 }
 
 // ------------------------------------------------------------------------------------ launcher
@@ -992,79 +855,56 @@ int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bo
   if (seq_len == 0) return MK_OK;
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
   const int k = c->k;
-  int p1_log2 = 8;
-  while (p1_log2 < SK2_MAX_P1_LOG2 && (seq_len >> p1_log2) > 8192) ++p1_log2;
+  const int p1_log2 = sk_p1_log2(seq_len, SK2_MAX_P1_LOG2, 8192);
   c->p1_log2 = p1_log2;
   const size_t p1 = (size_t)1 << p1_log2;
-  // bucket sizes from a 1-in-8 sample of the analysis threads for big chunks (see mk_skmer.hip)
-  const int sample_log2 = !exact && seq_len >= (size_t)mk_env_int("MK_SAMPLE_MIN", (long long)8 << 20) ? 3 : 0;
+  const int sample_log2 = sk_sample_log2(seq_len, exact);
   c->part_sampled = sample_log2 != 0;
   const bool reuse = mk_part_inherit(c, seq_len, p1_log2, min_count, sample_log2 != 0, exact);
   int rc;
-  if ((rc = mk_buf_reserve(c, c->part_meta, (7 * p1 + 16) * sizeof(u64))) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, c->part_meta, sk_meta_words(p1, 1) * sizeof(u64))) != MK_OK) return rc;
   const size_t part_cap = seq_len + 64;
   if ((rc = mk_buf_reserve(c, c->part, part_cap * sizeof(Sk2Rec))) != MK_OK) return rc;
-  const u64 surv_div = min_count > 1 ? (u64)min_count : 1;  // <= ceil(m / min_count) survivors among m k-mers
-  size_t surv_cap = seq_len / surv_div + p1 + 64;
-  if (sample_log2) {  // room for the sampling error of every bucket (bound as in mk_skmer.hip)
-    const double L = 1.25 * (double)seq_len, S = (double)(1u << sample_log2), w = (double)SK2_R;
-    surv_cap = (size_t)((L + 6.0 * sqrt((double)p1 * S * w * L) + 16.0 * w * (double)p1) / (double)surv_div) + 2 * p1 + 64;
-  }
+  const u64 surv_div = sk_surv_div(min_count);
+  const size_t surv_cap = sk_surv_cap(seq_len, p1, surv_div, sample_log2);
   if ((rc = mk_buf_reserve(c, c->surv_keys, surv_cap * sizeof(u64))) != MK_OK) return rc;
   if ((rc = mk_buf_reserve(c, c->surv_keys2, surv_cap * sizeof(u64))) != MK_OK) return rc;
   if ((rc = mk_buf_reserve(c, c->surv_cnts, surv_cap * sizeof(u64))) != MK_OK) return rc;
-  u64* hist = (u64*)c->part_meta.p;
-  u64* start = hist + p1;
-  SkCursor* cursor = (SkCursor*)(start + p1 + 1);  // (packed 32-bit, in the space of p1 64-bit words)
-  u64* khist = start + p1 + 1 + p1;
-  u64* kstart = khist + p1;
-  u64* kcursor = kstart + p1 + 1;
-  u64* nsurv = kcursor + p1;
-  if (!reuse) MK_HIP(hipMemsetAsync(hist, 0, (7 * p1 + 8) * sizeof(u64), c->stream));
-  const size_t threads = div_up(seq_len, SK2_R);
+  const SkMeta m = sk_meta(c->part_meta.p, p1, 1);
+  if (!reuse) MK_HIP(hipMemsetAsync(m.hist, 0, sk_meta_cleared_words(p1) * sizeof(u64), c->stream));
+  const size_t threads = div_up(seq_len, SK_R);
   const size_t tiles = div_up(div_up(threads, (size_t)1 << sample_log2), SK2_HIST_THREADS);
   const size_t stiles = div_up(threads, SK2_SCAT_THREADS);
   const size_t hist_grid = sample_log2 ? 128 : 256;
-  (void)kcursor;
+  const bool canon = c->canonical;  // (every kernel below comes in both forms: the form is picked here, the arguments are written once)
+  const u64 *codes = (const u64*)c->codes.p, *bad = (const u64*)c->bad.p;
+  Sk2Rec* part = (Sk2Rec*)c->part.p;
   mk_prof_begin(c, MK_K_PART);
-  const dim3 hgrid((unsigned)(tiles < hist_grid ? tiles : hist_grid)), sgrid((unsigned)(stiles < 4096 ? stiles : 4096));
-  if (reuse) {
-    // the regions of the chunk before stand as they are, every cursor back at its start
-  } else if (c->canonical)
-    hipLaunchKernelGGL(mk_sk2_hist_k<true>, hgrid, dim3(SK2_HIST_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                       (const u64*)c->bad.p, info, hist, khist, p1_log2, k, threads, sample_log2);
-  else
-    hipLaunchKernelGGL(mk_sk2_hist_k<false>, hgrid, dim3(SK2_HIST_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                       (const u64*)c->bad.p, info, hist, khist, p1_log2, k, threads, sample_log2);
-  if (!reuse)
-    mk_launch_sk_scan(c, hist, khist, start, cursor, kstart, p1_log2, sample_log2, SK2_NKMAX, surv_div, (u64)part_cap,
+  if (!reuse) {  // (reuse: the regions of the chunk before stand as they are, every cursor back at its start)
+    const dim3 hgrid((unsigned)(tiles < hist_grid ? tiles : hist_grid));
+    hipLaunchKernelGGL(canon ? mk_sk2_hist_k<true> : mk_sk2_hist_k<false>, hgrid, dim3(SK2_HIST_THREADS), 0, c->stream, codes, bad,
+                       info, m.hist, m.khist, p1_log2, k, threads, sample_log2);
+    mk_launch_sk_scan(c, m.hist, m.khist, m.start, m.cursor, m.kstart, p1_log2, sample_log2, SK2_NKMAX, surv_div, (u64)part_cap,
                       (u64)surv_cap, (float)mk_env_double("MK_SAMPLE_SIGMAS", 6.0), 1);
-  if (c->canonical)
-    hipLaunchKernelGGL(mk_sk2_scatter_k<true>, sgrid, dim3(SK2_SCAT_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (Sk2Rec*)c->part.p, p1_log2, k, stiles);
-  else if (part_cap >= SK2_NOFIT || mk_env_set("MK_SCATTER_WALK"))
-    hipLaunchKernelGGL(mk_sk2_scatter_k<false>, sgrid, dim3(SK2_SCAT_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (Sk2Rec*)c->part.p, p1_log2, k, stiles);
-  else {
-    const long long force_subt = mk_env_int("MK_SKQ_SUBT", 0);
-    const bool three = force_subt == 3 || (force_subt != 2 && c->items_hint > 0 && c->items_hint * 64.0 + 48.0 < 376.0);
-    unsigned qcap = three ? 376u : 512u;
-    { const long long v = mk_env_int("MK_SKQ_CAP", -1); if (v >= 0 && (unsigned long long)v < qcap) qcap = (unsigned)v; }
-    const size_t qtiles = div_up(threads, (size_t)SK2Q_THREADS * (three ? 3 : 2));
+  }
+  if (canon || part_cap >= SK2_NOFIT || mk_env_set("MK_SCATTER_WALK")) {
+    const dim3 sgrid((unsigned)(stiles < 4096 ? stiles : 4096));
+    hipLaunchKernelGGL(canon ? mk_sk2_scatter_k<true> : mk_sk2_scatter_k<false>, sgrid, dim3(SK2_SCAT_THREADS), 0, c->stream, codes,
+                       bad, info, (const u64*)m.start, m.cursor, part, p1_log2, k, stiles);
+  } else {
+    const SkQueueShape shape = sk_queue_shape(c);
+    const size_t qtiles = div_up(threads, (size_t)SK2Q_THREADS * (shape.three ? 3 : 2));
     const dim3 qgrid((unsigned)(qtiles < 8192 ? qtiles : 8192));
-    if (three)
-      hipLaunchKernelGGL((mk_sk2_scatterq_k<3, 376>), qgrid, dim3(SK2Q_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                         (const u64*)c->bad.p, info, (const u64*)start, cursor, (Sk2Rec*)c->part.p, p1_log2, k, qtiles, qcap);
-    else
-      hipLaunchKernelGGL((mk_sk2_scatterq_k<2, 512>), qgrid, dim3(SK2Q_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                         (const u64*)c->bad.p, info, (const u64*)start, cursor, (Sk2Rec*)c->part.p, p1_log2, k, qtiles, qcap);
+    hipLaunchKernelGGL((shape.three ? mk_sk2_scatterq_k<3, 376> : mk_sk2_scatterq_k<2, 512>), qgrid, dim3(SK2Q_THREADS), 0, c->stream,
+                       codes, bad, info, (const u64*)m.start, m.cursor, part, p1_log2, k, qtiles, shape.qcap);
   }
   mk_prof_end(c);
   mk_prof_begin(c, MK_K_COUNT);
   {
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-    const unsigned grid = (unsigned)((size_t)ncu < p1 ? (size_t)ncu : p1);
+    const dim3 grid((unsigned)((size_t)ncu < p1 ? (size_t)ncu : p1));
+    u64 *out_hi = (u64*)c->surv_keys.p, *out_lo = (u64*)c->surv_keys2.p, *out_cnt = (u64*)c->surv_cnts.p;
     // the counting pre-filter pays when few keys can reach min_count: min_count well above the mean count of a key,
     // which the chunk before has measured (windows / distinct keys); a sample's first chunk takes the exact kernel
     // (MK_FORCE_PREFILTER: whenever min_count >= 2)
@@ -1072,22 +912,14 @@ int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bo
     // partition was too small -- the exact kernel takes both)
     const bool pre = !exact && min_count >= 2 && ((min_count >= 4 && c->dup_known && c->dup_hint * 2.5 < (double)min_count) ||
                                         mk_env_set("MK_FORCE_PREFILTER"));
-    if (pre && c->canonical)
-      hipLaunchKernelGGL(mk_sk2_countp_k<true>, dim3(grid), dim3(SK2C_THREADS), 0, c->stream, (const Sk2Rec*)c->part.p,
-                         (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count, (u64*)c->surv_keys.p,
-                         (u64*)c->surv_keys2.p, (u64*)c->surv_cnts.p, k, (unsigned)p1);
-    else if (pre)
-      hipLaunchKernelGGL(mk_sk2_countp_k<false>, dim3(grid), dim3(SK2C_THREADS), 0, c->stream, (const Sk2Rec*)c->part.p,
-                         (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count, (u64*)c->surv_keys.p,
-                         (u64*)c->surv_keys2.p, (u64*)c->surv_cnts.p, k, (unsigned)p1);
-    else if (c->canonical)
-      hipLaunchKernelGGL(mk_sk2_count_k<true>, dim3(grid), dim3(SK2C_THREADS), 0, c->stream, (const Sk2Rec*)c->part.p,
-                         (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count, (u64*)c->surv_keys.p,
-                         (u64*)c->surv_keys2.p, (u64*)c->surv_cnts.p, k, (unsigned)p1, c->dup_hint, c->nk_hint);
+    if (pre)
+      hipLaunchKernelGGL(canon ? mk_sk2_countp_k<true> : mk_sk2_countp_k<false>, grid, dim3(SK2C_THREADS), 0, c->stream,
+                         (const Sk2Rec*)part, (const u64*)m.start, m.cursor, (const u64*)m.kstart, m.nsurv, info, (u64)min_count,
+                         out_hi, out_lo, out_cnt, k, (unsigned)p1);
     else
-      hipLaunchKernelGGL(mk_sk2_count_k<false>, dim3(grid), dim3(SK2C_THREADS), 0, c->stream, (const Sk2Rec*)c->part.p,
-                         (const u64*)start, cursor, (const u64*)kstart, nsurv, info, (u64)min_count, (u64*)c->surv_keys.p,
-                         (u64*)c->surv_keys2.p, (u64*)c->surv_cnts.p, k, (unsigned)p1, c->dup_hint, c->nk_hint);
+      hipLaunchKernelGGL(canon ? mk_sk2_count_k<true> : mk_sk2_count_k<false>, grid, dim3(SK2C_THREADS), 0, c->stream,
+                         (const Sk2Rec*)part, (const u64*)m.start, m.cursor, (const u64*)m.kstart, m.nsurv, info, (u64)min_count,
+                         out_hi, out_lo, out_cnt, k, (unsigned)p1, c->dup_hint, c->nk_hint);
   }
   mk_prof_end(c);
   MK_HIP(hipGetLastError());

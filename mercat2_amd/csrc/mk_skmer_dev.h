@@ -1,6 +1,6 @@
 // mk_skmer_dev.h -- device code shared by the super-k-mer partitioners (mk_skmer.hip: one-word keys, 18 <= k <= 32;
 // mk_skmer2.hip: two-word keys, 33 <= k <= 64): the minimizer order, the analysis of a thread's 32 windows into runs
-// that share their minimizer, and the walk over those runs.
+// that share their minimizer, the walk over those runs, the histogram kernels' body and the scatters' bucket reservations.
 #pragma once
 #include "mk_common.h"
 #include "mk_device.h"
@@ -96,6 +96,44 @@ __device__ __forceinline__ unsigned sk_reserve8(const unsigned (&count)[8], SkCu
   return spilled;
 }
 #endif
+
+// A tile's reservations in the two-word scatters (mk_skmer2.hip): count[b] records in every bucket b < p1; base[b]
+// becomes the run's first record, or `nofit` for a run that would cross the end of its bucket's region (sampled sizes
+// only: it is not written).  base may be count itself; where it is not, count[] is left cleared.  MAX_P1 buckets go
+// through sk_reserve8, eight per thread and all reservations in flight together; fewer buckets (small chunks) one at
+// a time.  `spilled` becomes 1 when a run does not fit.
+template <int THREADS, int MAX_P1>
+__device__ __forceinline__ void sk_reserve_tile(unsigned* count, unsigned* base, SkCursor* cursor, const u64* start, unsigned p1,
+                                                unsigned nofit, unsigned& spilled) {
+#ifndef SK_PLAIN_CURSORS
+  if (p1 == MAX_P1) {
+    constexpr int NB = MAX_P1 / THREADS;
+    static_assert(NB % 8 == 0, "sk_reserve8");
+#pragma unroll
+    for (int h = 0; h < NB; h += 8) {
+      unsigned v[8], at[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = count[threadIdx.x + (h + i) * THREADS];
+      spilled |= sk_reserve8<THREADS>(v, cursor + h * THREADS, start + h * THREADS, nofit, at);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        base[threadIdx.x + (h + i) * THREADS] = at[i];
+        if (base != count) count[threadIdx.x + (h + i) * THREADS] = 0;
+      }
+    }
+  } else
+#endif
+  {
+    for (unsigned b = threadIdx.x; b < p1; b += THREADS) {
+      const unsigned v = count[b];
+      const u64 r = v ? (u64)atomicAdd(&cursor[b], v) : 0ull;
+      const bool fits = v == 0 || r + v <= start[b + 1];
+      spilled |= fits ? 0u : 1u;
+      base[b] = fits ? (unsigned)r : nofit;
+      if (base != count) count[b] = 0;
+    }
+  }
+}
 
 // Result of analysing a thread's 32 windows: which are valid, where runs start, and the 6-bit
 // minimizer position of every window (packed 10 per word).
@@ -212,7 +250,43 @@ __device__ __forceinline__ unsigned sk_cut_starts(unsigned starts, unsigned vali
   return s2;
 }
 
-// ---- regions of a bucket, as the count kernels see them (mk_skcount.hip, mk_skmer2.hip)
+// The histogram kernels' body (mk_sk_hist_k, mk_sk2_hist_k): records and k-mers per bucket, counted in the LDS arrays
+// lh / lk (2^p1_log2 words each) and flushed to hist.  analyse(t, p0, tally) walks the records of analysis thread t,
+// whose first base is p0, and calls tally(first window, windows, minimizer) for each.
+// With sample_log2 = s > 0 only one analysis thread of every 2^s (a pseudo-random member of each group, so that no
+// period of the text can hide from the sample) is looked at: the scan turns the sampled counts into capacities with
+// room for the sampling error, the scatter checks every reservation against them, and a chunk whose estimate was too
+// small anywhere is partitioned again with s = 0 (exact).
+template <class A>
+__device__ __forceinline__ void sk_hist_body(unsigned* lh, unsigned* lk, const MkChunkInfo* __restrict__ info, u64* __restrict__ hist,
+                                             int p1_log2, size_t nthreads_total, int sample_log2, A&& analyse) {
+  // (blockDim.x once: read at each use, the inlined body loaded it again from the dispatch packet on every trip of the loop)
+  const unsigned p1 = 1u << p1_log2, nthr = blockDim.x;
+  for (unsigned i = threadIdx.x; i < p1; i += nthr) { lh[i] = 0; lk[i] = 0; }
+  __syncthreads();
+  const size_t seq_len = info->seq_len;
+  const size_t ngroups = (nthreads_total + ((size_t)1 << sample_log2) - 1) >> sample_log2;
+  for (size_t g = (size_t)blockIdx.x * nthr + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * nthr) {
+    size_t t = g;
+    if (sample_log2) t = (g << sample_log2) + (((unsigned)g * 0x9E3779B1u >> 7) & ((1u << sample_log2) - 1));
+    const size_t p0 = t * SK_R;
+    if (t >= nthreads_total || p0 >= seq_len) continue;
+    analyse(t, p0, [&](int, int nk, unsigned mm) {
+      const unsigned b = sk_bucket(mm, p1_log2);
+      atomicAdd(&lh[b], 1u);
+      atomicAdd(&lk[b], (unsigned)nk);
+    });
+  }
+  __syncthreads();
+  for (unsigned b = threadIdx.x; b < p1; b += nthr) {
+    const unsigned v = lh[b];
+    // one global add per bucket: records in the low word, k-mers in the high word (a chunk holds fewer than 2^32
+    // symbols, so neither half can carry) -- the per-workgroup flush is most of this kernel's HBM traffic
+    if (v) atomicAdd(&hist[b], (u64)v | ((u64)lk[b] << 32));
+  }
+}
+
+// ---- regions of a bucket, as the one-word count kernel sees them (mk_skcount.hip)
 // A bucket's records lie in nseg regions (1, or 9: one per XCD and a shared one, see mk_sk_scatterq_k / mk_sk_scan_k) --
 // region x of bucket b is [start[x * p1 + b], cursor[x * p1 + b]) -- and the kernel numbers them through, region after
 // region.  The table of a bucket: words 0..8 the number of records before region x, word 9 their total, words 10..18 region
