@@ -106,8 +106,7 @@ extern "C" int mk_words_per_key(const mk_ctx* c) { return c ? (c->mode == MK_MOD
 static void fold_pending(mk_ctx* c) {
   if (!c->pending_rows) return;
   const MkChunkInfo* p = c->h_info + 1;
-  if (c->mode == MK_MODE_HASH128) c->run128_rows += (size_t)p->new_rows;
-  else c->run_rows += (size_t)p->new_rows;
+  mk_add_packed_rows(c, (size_t)p->new_rows);
   c->run_ref_rows += (size_t)p->new_rows_ref;
   c->pending_rows = false;
 }
@@ -241,17 +240,10 @@ static int reset_impl(mk_ctx* c, size_t expect_rows) {
     if (c->run_slots > want) c->run_slots = want;
     if (c->run128_slots > want) c->run128_slots = want;
   }
-  if (c->mode == MK_MODE_DENSE) {
-    MK_HIP(hipMemsetAsync(c->run.p, 0, c->run_slots * sizeof(u64), c->stream));
-  } else if (c->run_slots) {
-    int rc = mk_launch_clear_slots(c, (MkSlot*)c->run.p, c->run_slots);
-    if (rc) return rc;
-  }
-  if (c->run_ref_slots) {
-    int rc = mk_launch_clear_slots(c, (MkSlot*)c->run_ref.p, c->run_ref_slots);
-    if (rc) return rc;
-  }
-  if (c->run128_slots) MK_HIP(hipMemsetAsync(c->run128.p, 0, c->run128_slots * sizeof(MkSlot128), c->stream));
+  int rc;
+  if ((rc = mk_clear_table(c, c->mode == MK_MODE_DENSE ? MK_TABLE_DENSE : MK_TABLE_ONE, c->run.p, c->run_slots)) != MK_OK) return rc;
+  if ((rc = mk_clear_table(c, MK_TABLE_REF, c->run_ref.p, c->run_ref_slots)) != MK_OK) return rc;
+  if ((rc = mk_clear_table(c, MK_TABLE_TWO, c->run128.p, c->run128_slots)) != MK_OK) return rc;
   c->run_rows = 0;
   c->run_ref_rows = 0;
   c->run128_rows = 0;
@@ -266,10 +258,7 @@ static int reset_impl(mk_ctx* c, size_t expect_rows) {
   // guess leaves no room for.  Only a new context has no guess and hands its first chunk's survivors over through regions.)
   c->fuse_cap = 0;
   c->clean_n_runs = c->clean_n_bytes = c->clean_gc = c->clean_symbols = c->clean_raw = c->clean_headers = c->clean_last_runs = 0;
-  if (c->fastq_stats.p) {
-    int rc = mk_fastq_clear(c);
-    if (rc) return rc;
-  }
+  if (c->fastq_stats.p && (rc = mk_fastq_clear(c)) != MK_OK) return rc;
   MK_HIP(hipStreamSynchronize(c->stream));
   return MK_OK;
 }
@@ -466,60 +455,51 @@ extern "C" int mk_chunk_feed_device(mk_ctx* c, const uint8_t* d_text, size_t n) 
 // table twice as sparse costs every sample ~0.15 ms.
 static size_t run_slots_for(size_t need_rows) { return pow2_at_least(need_rows * 5 / 2); }
 
-// (the table is only replaced under its lock -- a sharer may attach at any time, mk_share_table -- and with the streams
-// of the contexts that launch into it drained)
+// The running table of one kind replaced by a fresh one of `slots` slots that holds its rows (all of them, or with kept
+// those that pass min_count).  Whoever may launch into the old table has been dealt with by the caller.
+int mk_rebuild_table(mk_ctx* c, int kind, size_t slots, uint64_t min_count, size_t* kept) {
+  MkDevBuf& run = kind == MK_TABLE_TWO ? c->run128 : kind == MK_TABLE_REF ? c->run_ref : c->run;
+  size_t& run_slots = kind == MK_TABLE_TWO ? c->run128_slots : kind == MK_TABLE_REF ? c->run_ref_slots : c->run_slots;
+  u64* d_kept = kept ? (u64*)((char*)c->info.p + sizeof(MkChunkInfo)) : nullptr;
+  u64 h_kept = 0;
+  MkDevBuf nb;
+  int rc = mk_buf_reserve(c, nb, slots * (kind == MK_TABLE_TWO ? sizeof(MkSlot128) : sizeof(MkSlot)));
+  if (rc) return rc;
+  if ((rc = mk_clear_table(c, kind, nb.p, slots)) != MK_OK) return rc;
+  if (kept) MK_HIP(hipMemsetAsync(d_kept, 0, 8, c->stream));
+  if ((rc = mk_launch_rebuild(c, kind, run.p, run_slots, nb.p, slots, min_count, (uint64_t*)d_kept)) != MK_OK) return rc;
+  if (kept) MK_HIP(hipMemcpyAsync(&h_kept, d_kept, 8, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  buf_free(run);
+  run = nb;
+  run_slots = slots;
+  if (kept) *kept = (size_t)h_kept;
+  return MK_OK;
+}
+
+// (the shared table is only replaced under its lock -- a sharer may attach at any time, mk_share_table -- and with the
+// streams of the contexts that launch into it drained; the other two tables are never shared)
 int mk_grow_run64(mk_ctx* c, size_t need_rows) {
   std::unique_lock<std::shared_mutex> wr(c->table_mu);
   if (2 * need_rows <= c->run_slots) return MK_OK;
   if (!c->sharers.empty()) drain_table_users(c);
-  const size_t slots = run_slots_for(need_rows);
-  MkDevBuf nb;
-  int rc = mk_buf_reserve(c, nb, slots * sizeof(MkSlot));
-  if (rc) return rc;
-  if ((rc = mk_launch_clear_slots(c, (MkSlot*)nb.p, slots)) != MK_OK) return rc;
-  if (c->run_slots && (rc = mk_launch_rehash64(c, (const MkSlot*)c->run.p, c->run_slots, (MkSlot*)nb.p, slots)) != MK_OK) return rc;
-  MK_HIP(hipStreamSynchronize(c->stream));
-  buf_free(c->run);
-  c->run = nb;
-  c->run_slots = slots;
-  return MK_OK;
+  return mk_rebuild_table(c, MK_TABLE_ONE, run_slots_for(need_rows));
 }
 
 int mk_grow_run128(mk_ctx* c, size_t need_rows) {
   if (2 * need_rows <= c->run128_slots) return MK_OK;
-  const size_t slots = pow2_at_least(4 * need_rows);
-  MkDevBuf nb;
-  int rc = mk_buf_reserve(c, nb, slots * sizeof(MkSlot128));
-  if (rc) return rc;
-  MK_HIP(hipMemsetAsync(nb.p, 0, slots * sizeof(MkSlot128), c->stream));
-  if (c->run128_slots && (rc = mk_launch_rehash128(c, (const MkSlot128*)c->run128.p, c->run128_slots, (MkSlot128*)nb.p, slots)) != MK_OK) return rc;
-  MK_HIP(hipStreamSynchronize(c->stream));
-  buf_free(c->run128);
-  c->run128 = nb;
-  c->run128_slots = slots;
-  return MK_OK;
+  return mk_rebuild_table(c, MK_TABLE_TWO, pow2_at_least(4 * need_rows));
 }
 
 int mk_grow_run_ref(mk_ctx* c, size_t need_rows) {
-  int rc;
   if (need_rows > c->arena_rows_cap) {
     const size_t rows = std::max(need_rows, c->arena_rows_cap * 2);
-    if ((rc = mk_buf_reserve(c, c->arena, rows * (size_t)c->k + 64, true)) != MK_OK) return rc;
+    const int rc = mk_buf_reserve(c, c->arena, rows * (size_t)c->k + 64, true);
+    if (rc) return rc;
     c->arena_rows_cap = rows;
   }
   if (2 * need_rows <= c->run_ref_slots) return MK_OK;
-  const size_t slots = pow2_at_least(4 * need_rows);
-  MkDevBuf nb;
-  if ((rc = mk_buf_reserve(c, nb, slots * sizeof(MkSlot))) != MK_OK) return rc;
-  if ((rc = mk_launch_clear_slots(c, (MkSlot*)nb.p, slots)) != MK_OK) return rc;
-  if (c->run_ref_slots &&
-      (rc = mk_launch_rehash_ref(c, (const MkSlot*)c->run_ref.p, c->run_ref_slots, (MkSlot*)nb.p, slots)) != MK_OK)
-    return rc;
-  MK_HIP(hipStreamSynchronize(c->stream));
-  buf_free(c->run_ref);
-  c->run_ref = nb;
-  c->run_ref_slots = slots;
-  return MK_OK;
+  return mk_rebuild_table(c, MK_TABLE_REF, pow2_at_least(4 * need_rows));
 }
 
 int mk_grow_run(mk_ctx* c, size_t more_rows) {
@@ -594,7 +574,7 @@ extern "C" int mk_get_stats(mk_ctx* c, mk_stats_t* out) {
   (void)hipSetDevice(c->device);
   prof_collect(c);
   c->st.mode = c->mode;
-  if (c->mode != MK_MODE_DENSE) c->st.rows = c->run_rows + (c->run_side ? 1 : 0) + c->run_ref_rows + c->run128_rows;
+  if (c->mode != MK_MODE_DENSE) c->st.rows = mk_total_rows(c);
   *out = c->st;
   return MK_OK;
 }

@@ -24,7 +24,6 @@
 #define BIN_SC_NB 2048    // buckets at most: 1024, or 2048 for keys of 26 bits
 #define BIN_MAX_LOW 15    // bins per bucket 2^low <= 32768 (128 KB of 32-bit counters in the count kernel's LDS)
 
-static size_t bin_div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
 // f(key) for every clean window of the R = SPW * WPT symbols thread t owns
 template <int BITS, int SPW, int WPT, class F>
@@ -279,9 +278,9 @@ int mk_launch_count_binned(mk_ctx* c, size_t seq_len, uint64_t min_count) {
   mk_prof_begin(c, MK_K_PART);
 #define BIN_LAUNCH(BITS, SPW, WPT)                                                                                          \
   do {                                                                                                                      \
-    const size_t threads = bin_div_up(seq_len, (size_t)(SPW) * (WPT));                                                      \
-    const size_t tiles = bin_div_up(threads, (size_t)BIN_THREADS);                                                          \
-    const unsigned hgrid = (unsigned)std::min<size_t>(bin_div_up(threads, BIN_THREADS), (size_t)ncu * 4);                   \
+    const size_t threads = div_up(seq_len, (size_t)(SPW) * (WPT));                                                          \
+    const size_t tiles = div_up(threads, (size_t)BIN_THREADS);                                                              \
+    const unsigned hgrid = (unsigned)std::min<size_t>(div_up(threads, BIN_THREADS), (size_t)ncu * 4);                   \
     hipLaunchKernelGGL((mk_bin_hist_k<BITS, SPW, WPT>), dim3(hgrid), dim3(BIN_THREADS), 0, c->stream, (const u64*)c->codes.p, \
                        (const u64*)c->bad.p, info, hist, low, nb, c->k, threads, c->canonical);                             \
     hipLaunchKernelGGL(mk_bin_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)hist, start, cursor, nb);         \

@@ -212,7 +212,7 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
     const u64 bound = std::min<u64>((u64)seq_len, h->bad_symbols * (u64)c->k);
     c->rtab_chunk_slots = pow2_at_least(2 * (size_t)bound);
     if ((rc = mk_buf_reserve(c, c->rtab_chunk, c->rtab_chunk_slots * sizeof(MkSlot))) != MK_OK) return rc;
-    if ((rc = mk_launch_clear_slots(c, (MkSlot*)c->rtab_chunk.p, c->rtab_chunk_slots)) != MK_OK) return rc;
+    if ((rc = mk_clear_table(c, MK_TABLE_REF, c->rtab_chunk.p, c->rtab_chunk_slots)) != MK_OK) return rc;
     if ((rc = mk_launch_count_byref(c, seq_len, true)) != MK_OK) return rc;
     if ((rc = mk_launch_count_survivors(c, min_count)) != MK_OK) return rc;
     if ((rc = mk_pull_info(c)) != MK_OK) return rc;
@@ -356,7 +356,7 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
   }
   if (c->rtab_chunk_slots) {
     if ((rc = mk_buf_reserve(c, c->rtab_chunk, c->rtab_chunk_slots * sizeof(MkSlot))) != MK_OK) return rc;
-    if ((rc = mk_launch_clear_slots(c, (MkSlot*)c->rtab_chunk.p, c->rtab_chunk_slots)) != MK_OK) return rc;
+    if ((rc = mk_clear_table(c, MK_TABLE_REF, c->rtab_chunk.p, c->rtab_chunk_slots)) != MK_OK) return rc;
   }
   c->st.table_slots = (c->mode == MK_MODE_BYREF || c->mode == MK_MODE_HASH128) ? c->rtab_chunk_slots : c->ctab_slots;
 
@@ -394,8 +394,7 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
   }
   if ((rc = mk_launch_accumulate(c, min_count)) != MK_OK) return rc;
   if ((rc = mk_pull_info(c)) != MK_OK) return rc;
-  if (c->mode == MK_MODE_HASH128) c->run128_rows += (size_t)h->new_rows;
-  else c->run_rows += (size_t)h->new_rows;
+  mk_add_packed_rows(c, (size_t)h->new_rows);
   c->run_ref_rows += (size_t)h->new_rows_ref;
   if (h->side && h->side >= min_count) c->run_side += h->side;
   if (partitioned || sk2) note_hints(c, seq_len, /*full_chunk=*/true);  // (this lane takes dup_hint from every chunk)

@@ -108,6 +108,9 @@ void mk_set_global_error(const std::string& msg);
 // mk_api.hip: row totals and the chunk's scalars
 int mk_settle(mk_ctx* c);     // fold row totals that were read back without waiting; before anything reads run_rows & co.
 int mk_pull_info(mk_ctx* c);  // MkChunkInfo -> h_info, stream idle afterwards
+// mk_api.hip: the running table of this kind (MkTableKind) replaced by one of `slots` slots that holds its rows -- with
+// kept, only the rows with count >= min_count, *kept of them.  The caller holds whatever lock the table needs.
+int mk_rebuild_table(mk_ctx* c, int kind, size_t slots, uint64_t min_count = 0, size_t* kept = nullptr);
 // mk_api.hip: room in a running table for need_rows keys in all (mk_grow_run: for more_rows further packed keys)
 int mk_grow_run64(mk_ctx* c, size_t need_rows);
 int mk_grow_run128(mk_ctx* c, size_t need_rows);
@@ -254,6 +257,13 @@ struct mk_ctx {
     if (rc__) return rc__;                                                                   \
   } while (0)
 
+static inline size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
+static inline unsigned grid_for(size_t items, unsigned per_block = 256, unsigned cap = 1u << 20) {
+  size_t g = div_up(items, per_block);
+  if (g > cap) g = cap;
+  if (g == 0) g = 1;
+  return (unsigned)g;
+}
 static inline size_t pow2_at_least(size_t v) {
   size_t p = 1024;
   while (p < v) p <<= 1;
@@ -266,6 +276,27 @@ static inline void buf_free(MkDevBuf& b) {
 }
 // the context whose running table the fused launches of c upsert into (mk_share_table)
 static inline mk_ctx* table_of_ctx(mk_ctx* c) { return c->share_owner ? c->share_owner : c; }
+
+// The packed running table of a context.  (MK_TABLE_REF, the by-reference table beside it, is never what table_of names.)
+enum MkTableKind { MK_TABLE_NONE = 0, MK_TABLE_ONE = 1, MK_TABLE_TWO = 2, MK_TABLE_DENSE = 3, MK_TABLE_REF = 4 };
+struct TableRef {
+  int kind = MK_TABLE_NONE;
+  const void* p = nullptr;
+  size_t slots = 0;
+  size_t rows = 0;  // rows the host knows of (dense: unknown, bins)
+};
+static inline TableRef table_of(const mk_ctx* c) {
+  TableRef t;
+  if (c->mode == MK_MODE_HASH64 && c->run_slots) { t.kind = MK_TABLE_ONE; t.p = c->run.p; t.slots = c->run_slots; t.rows = c->run_rows; }
+  else if (c->mode == MK_MODE_HASH128 && c->run128_slots) { t.kind = MK_TABLE_TWO; t.p = c->run128.p; t.slots = c->run128_slots; t.rows = c->run128_rows; }
+  else if (c->mode == MK_MODE_DENSE) { t.kind = MK_TABLE_DENSE; t.p = c->run.p; t.slots = c->run_slots; t.rows = c->run_slots; }
+  return t;
+}
+// n keys were new to the packed table (dense bins have no new keys: their kernels leave n at 0)
+static inline void mk_add_packed_rows(mk_ctx* c, size_t n) { (c->mode == MK_MODE_HASH128 ? c->run128_rows : c->run_rows) += n; }
+// rows of the hashed tables: the packed ones (with the one key kept beside the one-word table), and all of them
+static inline size_t mk_packed_rows(const mk_ctx* c) { return c->run_rows + (c->run_side ? 1 : 0) + c->run128_rows; }
+static inline size_t mk_total_rows(const mk_ctx* c) { return mk_packed_rows(c) + c->run_ref_rows; }
 
 // A sample's rows on the host (mk_export.hip), for mk_combine.hip
 struct ExportView {
@@ -338,34 +369,30 @@ int mk_launch_sk_count(mk_ctx* c, const unsigned long long* start, unsigned* cur
                        unsigned long long* nsurv, uint64_t min_count, size_t p1, int nseg);
 // nt 33 <= k <= 64, two-word keys: mk_skmer2.hip; survivors {hi,lo,count} per bucket region
 int mk_launch_count_superkmer2(mk_ctx* c, size_t seq_len, uint64_t min_count, bool exact = false);
-int mk_launch_import_ref128_regions(mk_ctx* c, const uint64_t* hi, const uint64_t* lo, const uint64_t* cnts,
-                                    const uint64_t* kstart, const uint64_t* nsurv, size_t p1);
-// tables
-int mk_launch_clear_slots(mk_ctx* c, MkSlot* t, size_t slots);
+// tables (mk_table.hip); kind: MkTableKind
+int mk_clear_table(mk_ctx* c, int kind, void* t, size_t slots);  // every slot free (MK_TABLE_DENSE: every bin zero)
 int mk_launch_count_survivors(mk_ctx* c, uint64_t min_count);
 // mk_sort.hip: arena rows (k bytes each) in byte order; *d_order = row indices, sorted (lives in c->ex_cnts2)
 int mk_sort_rows(mk_ctx* c, const uint8_t* d_arena, size_t rows, int k, uint64_t** d_order);
 int mk_launch_rows_by_slot(mk_ctx* c, const uint64_t* slot_keys, const uint64_t* slot_cnts, size_t rows, uint64_t* cnt_by_row, uint64_t* d_bad);
 int mk_launch_rows_gather(mk_ctx* c, const uint8_t* arena, const uint64_t* order, const uint64_t* cnt_by_row, size_t rows, int k,
                           uint8_t* out_rows, uint64_t* out_cnts);
-int mk_launch_alpha(mk_ctx* c, unsigned long long* d_out);  // 16 words: see mk_alpha_k
+int mk_launch_alpha(mk_ctx* c, unsigned long long* d_out);  // 16 words: see mk_alpha_k<View>
 int mk_launch_accumulate(mk_ctx* c, uint64_t min_count);
 // every row of another one-word table (same device) added into c's running table; *new_rows counts the new keys
 int mk_launch_merge_table64(mk_ctx* c, const MkSlot* from, size_t from_slots);
-int mk_launch_rehash64(mk_ctx* c, const MkSlot* from, size_t from_slots, MkSlot* to, size_t to_slots);
-int mk_launch_rehash_ref(mk_ctx* c, const MkSlot* from, size_t from_slots, MkSlot* to, size_t to_slots);
+// the rows of one table into a fresh one (mk_rebuild_k); d_kept: only rows with count >= min_count, counted there
+int mk_launch_rebuild(mk_ctx* c, int kind, const void* from, size_t from_slots, void* to, size_t to_slots, uint64_t min_count,
+                      uint64_t* d_kept);
+// rows as columns (two-word keys: {hi, lo} interleaved) -> the packed table; distinct: a chunk's survivors, each key once
 int mk_launch_import_pairs(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows, bool distinct = false);
 int mk_launch_import_regions(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* kstart,
                              const uint64_t* nsurv, size_t p1, size_t survivors);
 int mk_launch_import_ref(mk_ctx* c, const uint8_t* d_kmers, const uint64_t* d_counts, size_t rows);
-// two-word keys (mk_table.hip): survivors {hi, lo, count} per bucket region / rows {hi, lo} interleaved -> run128
+// two-word keys: survivors {hi, lo, count} per bucket region -> run128
 int mk_launch_import128_regions(mk_ctx* c, const uint64_t* hi, const uint64_t* lo, const uint64_t* cnts, const uint64_t* kstart,
                                 const uint64_t* nsurv, size_t p1);
-int mk_launch_import128_pairs(mk_ctx* c, const uint64_t* d_keys2, const uint64_t* d_counts, size_t rows);
-int mk_launch_refilter64(mk_ctx* c, const MkSlot* from, MkSlot* to, size_t slots, uint64_t min_count, uint64_t* d_kept);
-int mk_launch_refilter128(mk_ctx* c, const MkSlot128* from, MkSlot128* to, size_t slots, uint64_t min_count, uint64_t* d_kept);
 int mk_launch_refilter_dense(mk_ctx* c, uint64_t* bins, size_t nbins, uint64_t min_count);
-int mk_launch_rehash128(mk_ctx* c, const MkSlot128* from, size_t from_slots, MkSlot128* to, size_t to_slots);
 int mk_launch_compact128(mk_ctx* c, const MkSlot128* t, size_t slots, uint64_t* hi, uint64_t* lo, uint64_t* cnts, size_t cap,
                          uint64_t* d_cursor);
 // mk_sort.hip: rows {hi[i], lo[i], cnt[i]} -> sorted by (hi, lo): keys2_out = {hi, lo} interleaved, cnts_out; scratch = 4 * n words

@@ -325,7 +325,6 @@ int mk_launch_count_ref128(mk_ctx* c, size_t seq_len) {
 }
 
 // ------------------------------------------------------------------------------ launchers
-static size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
 int mk_launch_count_dense(mk_ctx* c, size_t seq_len) {
   if (seq_len == 0) return MK_OK;

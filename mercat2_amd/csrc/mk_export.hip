@@ -37,42 +37,53 @@ static int gather_packed(mk_ctx* c, ExportView& v, u64* d_keys_out, u64* d_cnts_
         MK_HIP(hipStreamSynchronize(c->stream));
       }
     }
-  } else if (c->mode == MK_MODE_HASH64) {
-    rows = c->run_rows;
-    const size_t side = c->run_side ? 1 : 0;
+  } else if (c->mode == MK_MODE_HASH64 || c->mode == MK_MODE_HASH128) {
+    const bool two = c->mode == MK_MODE_HASH128;
+    const size_t w = two ? 2 : 1;  // words per key
+    v.words = (int)w;
+    rows = two ? c->run128_rows : c->run_rows;
+    const size_t side = !two && c->run_side ? 1 : 0;
     if (!to_host && rows + side > cap) { c->err = "export: device buffers too small"; return MK_ERR_RANGE; }
     if (rows) {
       mk_prof_begin(c, MK_K_EXPORT);
-      if ((rc = mk_buf_reserve(c, c->ex_keys, rows * 8 + 64)) != MK_OK) return rc;
-      if ((rc = mk_buf_reserve(c, c->ex_cnts, rows * 8 + 64)) != MK_OK) return rc;
+      // compacted rows: one-word keys | counts; two-word hi | lo | count + 4 n words of sort scratch
+      if ((rc = two ? mk_buf_reserve(c, c->ex128, 7 * rows * 8 + 64) : mk_buf_reserve(c, c->ex_keys, rows * 8 + 64)) != MK_OK) return rc;
+      if (!two && (rc = mk_buf_reserve(c, c->ex_cnts, rows * 8 + 64)) != MK_OK) return rc;
+      u64* k0 = (u64*)(two ? c->ex128.p : c->ex_keys.p);
+      u64* cn = two ? k0 + 2 * rows : (u64*)c->ex_cnts.p;
       u64* d_cursor = (u64*)((char*)c->info.p + sizeof(MkChunkInfo));
       MK_HIP(hipMemsetAsync(d_cursor, 0, 8, c->stream));
-      if ((rc = mk_launch_compact(c, (const MkSlot*)c->run.p, c->run_slots, (uint64_t*)c->ex_keys.p,
-                                  (uint64_t*)c->ex_cnts.p, rows, (uint64_t*)d_cursor)) != MK_OK) return rc;
+      if ((rc = two ? mk_launch_compact128(c, (const MkSlot128*)c->run128.p, c->run128_slots, (uint64_t*)k0, (uint64_t*)(k0 + rows),
+                                           (uint64_t*)cn, rows, (uint64_t*)d_cursor)
+                    : mk_launch_compact(c, (const MkSlot*)c->run.p, c->run_slots, (uint64_t*)k0, (uint64_t*)cn, rows,
+                                        (uint64_t*)d_cursor)) != MK_OK) return rc;
       u64* ok = d_keys_out;
       u64* oc = d_cnts_out;
-      if (to_host) {
-        if ((rc = mk_buf_reserve(c, c->ex_keys2, rows * 8 + 64)) != MK_OK) return rc;
-        if ((rc = mk_buf_reserve(c, c->ex_cnts2, rows * 8 + 64)) != MK_OK) return rc;
-        ok = (u64*)c->ex_keys2.p;
-        oc = (u64*)c->ex_cnts2.p;
+      if (to_host) {  // sorted rows for the host: keys, then counts
+        MkDevBuf& kb = two ? c->ex128_out : c->ex_keys2;
+        if ((rc = mk_buf_reserve(c, kb, (two ? 3 : 1) * rows * 8 + 64)) != MK_OK) return rc;
+        if (!two && (rc = mk_buf_reserve(c, c->ex_cnts2, rows * 8 + 64)) != MK_OK) return rc;
+        ok = (u64*)kb.p;
+        oc = two ? ok + 2 * rows : (u64*)c->ex_cnts2.p;
       }
-      if ((rc = mk_sort_pairs(c, (const uint64_t*)c->ex_keys.p, (const uint64_t*)c->ex_cnts.p, (uint64_t*)ok,
-                              (uint64_t*)oc, rows, c->bits * c->k)) != MK_OK) return rc;
+      if ((rc = two ? mk_sort_pairs128(c, (const uint64_t*)k0, (const uint64_t*)(k0 + rows), (const uint64_t*)cn, rows,
+                                       2 * (c->k - 32), (uint64_t*)(cn + rows), (uint64_t*)ok, (uint64_t*)oc)
+                    : mk_sort_pairs(c, (const uint64_t*)k0, (const uint64_t*)cn, (uint64_t*)ok, (uint64_t*)oc, rows,
+                                    c->bits * c->k)) != MK_OK) return rc;
       mk_prof_end(c);
       if (to_host) {
         MK_HIP(hipStreamSynchronize(c->stream));  // (so that sort and copy are timed apart: ~10 us)
         c->ex_st.s_sort += since(t_gather);
-        v.pkeys.resize(rows);
+        v.pkeys.resize(w * rows);
         v.pcnts.resize(rows);
-        MK_HIP(hipMemcpyAsync(v.pkeys.data(), ok, rows * 8, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipMemcpyAsync(v.pkeys.data(), ok, w * rows * 8, hipMemcpyDeviceToHost, c->stream));
         MK_HIP(hipMemcpyAsync(v.pcnts.data(), oc, rows * 8, hipMemcpyDeviceToHost, c->stream));
       }
       u64 got = 0;
       MK_HIP(hipMemcpyAsync(&got, d_cursor, 8, hipMemcpyDeviceToHost, c->stream));
       MK_HIP(hipStreamSynchronize(c->stream));
       if (got != rows) {
-        c->err = "export: table holds " + std::to_string(got) + " rows, expected " + std::to_string(rows);
+        c->err = std::string("export: ") + (two ? "two-word table" : "table") + " holds " + std::to_string(got) + " rows, expected " + std::to_string(rows);
         return MK_ERR_STATE;
       }
     }
@@ -85,49 +96,6 @@ static int gather_packed(mk_ctx* c, ExportView& v, u64* d_keys_out, u64* d_cnts_
         MK_HIP(hipStreamSynchronize(c->stream));
       }
       rows += 1;
-    }
-  }
-  else if (c->mode == MK_MODE_HASH128) {
-    v.words = 2;
-    rows = c->run128_rows;
-    if (!to_host && rows > cap) { c->err = "export: device buffers too small"; return MK_ERR_RANGE; }
-    if (rows) {
-      mk_prof_begin(c, MK_K_EXPORT);
-      // compacted {hi | lo | count} + 4 n words of sort scratch
-      if ((rc = mk_buf_reserve(c, c->ex128, 7 * rows * 8 + 64)) != MK_OK) return rc;
-      u64* hi = (u64*)c->ex128.p;
-      u64* lo = hi + rows;
-      u64* cn = lo + rows;
-      u64* scratch = cn + rows;
-      u64* d_cursor = (u64*)((char*)c->info.p + sizeof(MkChunkInfo));
-      MK_HIP(hipMemsetAsync(d_cursor, 0, 8, c->stream));
-      if ((rc = mk_launch_compact128(c, (const MkSlot128*)c->run128.p, c->run128_slots, (uint64_t*)hi, (uint64_t*)lo,
-                                     (uint64_t*)cn, rows, (uint64_t*)d_cursor)) != MK_OK) return rc;
-      u64* ok = d_keys_out;
-      u64* oc = d_cnts_out;
-      if (to_host) {
-        if ((rc = mk_buf_reserve(c, c->ex128_out, 3 * rows * 8 + 64)) != MK_OK) return rc;
-        ok = (u64*)c->ex128_out.p;
-        oc = ok + 2 * rows;
-      }
-      if ((rc = mk_sort_pairs128(c, (const uint64_t*)hi, (const uint64_t*)lo, (const uint64_t*)cn, rows, 2 * (c->k - 32),
-                                 (uint64_t*)scratch, (uint64_t*)ok, (uint64_t*)oc)) != MK_OK) return rc;
-      mk_prof_end(c);
-      if (to_host) {
-        MK_HIP(hipStreamSynchronize(c->stream));
-        c->ex_st.s_sort += since(t_gather);
-        v.pkeys.resize(2 * rows);
-        v.pcnts.resize(rows);
-        MK_HIP(hipMemcpyAsync(v.pkeys.data(), ok, 2 * rows * 8, hipMemcpyDeviceToHost, c->stream));
-        MK_HIP(hipMemcpyAsync(v.pcnts.data(), oc, rows * 8, hipMemcpyDeviceToHost, c->stream));
-      }
-      u64 got = 0;
-      MK_HIP(hipMemcpyAsync(&got, d_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-      MK_HIP(hipStreamSynchronize(c->stream));
-      if (got != rows) {
-        c->err = "export: two-word table holds " + std::to_string(got) + " rows, expected " + std::to_string(rows);
-        return MK_ERR_STATE;
-      }
     }
   }
   if (rows_out) *rows_out = rows;
@@ -252,7 +220,7 @@ extern "C" int mk_export_size(mk_ctx* c, size_t* rows) {
     if (rc) return rc;
     *rows = v.packed_rows() + c->run_ref_rows;
   } else {
-    *rows = c->run_rows + (c->run_side ? 1 : 0) + c->run_ref_rows + c->run128_rows;
+    *rows = mk_total_rows(c);
   }
   c->st.rows = *rows;
   return MK_OK;

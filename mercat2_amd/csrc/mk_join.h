@@ -179,7 +179,7 @@ int join_union(mk_ctx* const* ctxs, int n, size_t slab_rows, Acc& g, size_t* row
     const int w = mk_words_per_key(o);
     if (words && w != words) { c->err = W + ": contexts differ in key width"; return MK_ERR_ARG; }
     words = w;
-    const size_t cap = o->mode == MK_MODE_DENSE ? o->run_slots : o->run_rows + (o->run_side ? 1 : 0) + o->run128_rows;
+    const size_t cap = o->mode == MK_MODE_DENSE ? o->run_slots : mk_packed_rows(o);
     if (!cap) continue;
     DevBuf k_, c_;
     if ((rc = dev_alloc(c, k_, o->device, cap * 8 * (size_t)w)) != MK_OK) return rc;

@@ -13,7 +13,7 @@
 // The same two device primitives serve one-process-per-GPU callers (mercat2_amd/dist.py over RCCL) through
 // mk_bucket_rows_device / mk_import_rows_device.
 #include "mk_common.h"
-#include "mk_device.h"
+#include "mk_tableview.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -33,34 +33,6 @@ namespace {
 using Clock = std::chrono::steady_clock;
 static double secs(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
-// ---- the three packed running tables seen as "slot i -> (occupied, key word(s), count)" ------------------------
-struct View64 {
-  const MkSlot* t;
-  static constexpr int W = 1;
-  __device__ __forceinline__ bool get(size_t i, u64& a, u64& b, u64& c) const {
-    const ulonglong2 s = reinterpret_cast<const ulonglong2*>(t)[i];
-    a = s.x; b = 0; c = s.y;
-    return s.x != MK_EMPTY && s.y != 0;
-  }
-};
-struct View128 {
-  const MkSlot128* t;
-  static constexpr int W = 2;
-  __device__ __forceinline__ bool get(size_t i, u64& a, u64& b, u64& c) const {
-    const ulonglong4 s = reinterpret_cast<const ulonglong4*>(t)[i];
-    a = s.x; b = s.y; c = s.z;
-    return s.z != 0;
-  }
-};
-struct ViewDense {
-  const u64* bins;
-  static constexpr int W = 1;
-  __device__ __forceinline__ bool get(size_t i, u64& a, u64& b, u64& c) const {
-    a = (u64)i; b = 0; c = bins[i];
-    return c != 0;
-  }
-};
-
 __device__ __forceinline__ int owner_of(const u64* __restrict__ s_bounds, int n, u64 key) {
   int o = 0;
   for (int j = 0; j + 1 < n; ++j) o += key >= s_bounds[j] ? 1 : 0;
@@ -77,10 +49,10 @@ __global__ __launch_bounds__(256) void mk_owner_hist_k(V v, size_t slots, const 
     s_bounds[threadIdx.x] = (int)threadIdx.x + 1 < n ? bounds[threadIdx.x] : ~0ull;
   }
   __syncthreads();
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
+  mk_for_each(slots, [&](size_t i) {
     u64 a, b, c;
     if (v.get(i, a, b, c)) atomicAdd(&s_cnt[owner_of(s_bounds, n, a)], 1u);
-  }
+  });
   __syncthreads();
   if ((int)threadIdx.x < n && s_cnt[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (u64)s_cnt[threadIdx.x]);
 }
@@ -140,37 +112,16 @@ __global__ void mk_owner_prefix_k(const u64* __restrict__ hist, u64* __restrict_
   }
 }
 
-// first key words of the rows in every stride-th slot (the table is hashed: a uniform sample of its rows)
+// first key words of the rows in every stride-th slot, n slots in all (the table is hashed: a uniform sample of its rows)
 template <class V>
-__global__ void mk_sample_keys_k(V v, size_t slots, size_t stride, u64* __restrict__ out, u64 cap, u64* __restrict__ cursor) {
-  for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j * stride < slots; j += (size_t)gridDim.x * blockDim.x) {
+__global__ void mk_sample_keys_k(V v, size_t n, size_t stride, u64* __restrict__ out, u64 cap, u64* __restrict__ cursor) {
+  mk_for_each(n, [&](size_t j) {
     u64 a, b, c;
     if (v.get(j * stride, a, b, c)) {
       const u64 pos = atomicAdd(cursor, 1ull);
       if (pos < cap) out[pos] = a;
     }
-  }
-}
-
-static unsigned grid_for(size_t items, unsigned per_block, unsigned cap) {
-  size_t g = (items + per_block - 1) / per_block;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return (unsigned)g;
-}
-
-struct TableRef {
-  int kind = 0;  // 0 none, 1 one-word, 2 two-word, 3 dense
-  const void* p = nullptr;
-  size_t slots = 0;
-  size_t rows = 0;  // rows the host knows of (dense: unknown, bins)
-};
-static TableRef table_of(const mk_ctx* c) {
-  TableRef t;
-  if (c->mode == MK_MODE_HASH64 && c->run_slots) { t.kind = 1; t.p = c->run.p; t.slots = c->run_slots; t.rows = c->run_rows; }
-  else if (c->mode == MK_MODE_HASH128 && c->run128_slots) { t.kind = 2; t.p = c->run128.p; t.slots = c->run128_slots; t.rows = c->run128_rows; }
-  else if (c->mode == MK_MODE_DENSE) { t.kind = 3; t.p = c->run.p; t.slots = c->run_slots; t.rows = c->run_slots; }
-  return t;
+  });
 }
 
 // meta buffer: bounds[64] | hist[64] | cursor[64]
@@ -196,13 +147,13 @@ static int bucket_rows(mk_ctx* c, const u64* bounds, int n, u64* d_rows, size_t 
     MK_HIP(hipMemcpyAsync(d_bounds, hb, sizeof hb, hipMemcpyHostToDevice, c->stream));
     MK_HIP(hipMemsetAsync(d_hist, 0, MK_MAX_OWNERS * sizeof(u64), c->stream));
     const unsigned grid = grid_for(t.slots, 256 * 16, 2048);
-    if (t.kind == 1) hipLaunchKernelGGL(mk_owner_hist_k<View64>, dim3(grid), dim3(256), 0, c->stream, View64{(const MkSlot*)t.p}, t.slots, (const u64*)d_bounds, n, d_hist);
-    else if (t.kind == 2) hipLaunchKernelGGL(mk_owner_hist_k<View128>, dim3(grid), dim3(256), 0, c->stream, View128{(const MkSlot128*)t.p}, t.slots, (const u64*)d_bounds, n, d_hist);
+    if (t.kind == MK_TABLE_ONE) hipLaunchKernelGGL(mk_owner_hist_k<View64>, dim3(grid), dim3(256), 0, c->stream, View64{(const MkSlot*)t.p}, t.slots, (const u64*)d_bounds, n, d_hist);
+    else if (t.kind == MK_TABLE_TWO) hipLaunchKernelGGL(mk_owner_hist_k<View128>, dim3(grid), dim3(256), 0, c->stream, View128{(const MkSlot128*)t.p}, t.slots, (const u64*)d_bounds, n, d_hist);
     else hipLaunchKernelGGL(mk_owner_hist_k<ViewDense>, dim3(grid), dim3(256), 0, c->stream, ViewDense{(const u64*)t.p}, t.slots, (const u64*)d_bounds, n, d_hist);
     if (d_rows) {  // (the scatter never writes past cap_rows; whether everything fitted is checked below)
       hipLaunchKernelGGL(mk_owner_prefix_k, dim3(1), dim3(64), 0, c->stream, (const u64*)d_hist, d_cursor, n);
-      if (t.kind == 1) hipLaunchKernelGGL(mk_owner_scatter_k<View64>, dim3(grid), dim3(256), 0, c->stream, View64{(const MkSlot*)t.p}, t.slots, (const u64*)d_bounds, n, d_cursor, d_rows, (u64)cap_rows);
-      else if (t.kind == 2) hipLaunchKernelGGL(mk_owner_scatter_k<View128>, dim3(grid), dim3(256), 0, c->stream, View128{(const MkSlot128*)t.p}, t.slots, (const u64*)d_bounds, n, d_cursor, d_rows, (u64)cap_rows);
+      if (t.kind == MK_TABLE_ONE) hipLaunchKernelGGL(mk_owner_scatter_k<View64>, dim3(grid), dim3(256), 0, c->stream, View64{(const MkSlot*)t.p}, t.slots, (const u64*)d_bounds, n, d_cursor, d_rows, (u64)cap_rows);
+      else if (t.kind == MK_TABLE_TWO) hipLaunchKernelGGL(mk_owner_scatter_k<View128>, dim3(grid), dim3(256), 0, c->stream, View128{(const MkSlot128*)t.p}, t.slots, (const u64*)d_bounds, n, d_cursor, d_rows, (u64)cap_rows);
       else hipLaunchKernelGGL(mk_owner_scatter_k<ViewDense>, dim3(grid), dim3(256), 0, c->stream, ViewDense{(const u64*)t.p}, t.slots, (const u64*)d_bounds, n, d_cursor, d_rows, (u64)cap_rows);
     }
     MK_HIP(hipGetLastError());
@@ -239,15 +190,15 @@ static int sample_keys(mk_ctx* c, size_t stride, std::vector<u64>& out) {
   MK_HIP(hipSetDevice(c->device));
   if ((rc = mk_settle(c)) != MK_OK) return rc;
   const TableRef t = table_of(c);
-  if (!(t.kind == 1 || t.kind == 2) || !t.rows) return MK_OK;
+  if (!(t.kind == MK_TABLE_ONE || t.kind == MK_TABLE_TWO) || !t.rows) return MK_OK;
   const size_t cap = 2 * (t.rows / stride) + 1024;
   if ((rc = mk_buf_reserve(c, c->xfer_in, (cap + 8) * sizeof(u64))) != MK_OK) return rc;
   u64* d_cursor = (u64*)c->xfer_in.p;
   u64* d_out = d_cursor + 8;
   MK_HIP(hipMemsetAsync(d_cursor, 0, 8, c->stream));
   const unsigned grid = grid_for(t.slots / stride + 1, 256, 1024);
-  if (t.kind == 1) hipLaunchKernelGGL(mk_sample_keys_k<View64>, dim3(grid), dim3(256), 0, c->stream, View64{(const MkSlot*)t.p}, t.slots, stride, d_out, (u64)cap, d_cursor);
-  else hipLaunchKernelGGL(mk_sample_keys_k<View128>, dim3(grid), dim3(256), 0, c->stream, View128{(const MkSlot128*)t.p}, t.slots, stride, d_out, (u64)cap, d_cursor);
+  if (t.kind == MK_TABLE_ONE) hipLaunchKernelGGL(mk_sample_keys_k<View64>, dim3(grid), dim3(256), 0, c->stream, View64{(const MkSlot*)t.p}, div_up(t.slots, stride), stride, d_out, (u64)cap, d_cursor);
+  else hipLaunchKernelGGL(mk_sample_keys_k<View128>, dim3(grid), dim3(256), 0, c->stream, View128{(const MkSlot128*)t.p}, div_up(t.slots, stride), stride, d_out, (u64)cap, d_cursor);
   MK_HIP(hipGetLastError());
   u64 got = 0;
   MK_HIP(hipMemcpyAsync(&got, d_cursor, 8, hipMemcpyDeviceToHost, c->stream));
@@ -408,8 +359,8 @@ extern "C" int mk_import_rows_device(mk_ctx* c, const uint64_t* d_rows, size_t r
   if ((rc = mk_grow_run(c, rows)) != MK_OK) return rc;
   if ((rc = mk_launch_import_rows(c, d_rows, rows)) != MK_OK) return rc;
   if ((rc = mk_pull_info(c)) != MK_OK) return rc;
-  if (c->mode == MK_MODE_HASH128) c->run128_rows += (size_t)c->h_info->new_rows;
-  else if (c->mode == MK_MODE_HASH64) { c->run_rows += (size_t)c->h_info->new_rows; c->run_side += c->h_info->side; }
+  mk_add_packed_rows(c, (size_t)c->h_info->new_rows);
+  if (c->mode == MK_MODE_HASH64) c->run_side += c->h_info->side;
   return MK_OK;
 }
 
@@ -528,7 +479,7 @@ extern "C" int mk_merge_devices(mk_ctx* const* ctxs, int n, int flags, mk_merge_
       mk_ctx* c = ctxs[i];
       int r;
       if ((r = mk_settle(c)) != MK_OK) { bad = i; return r; }
-      if (table_of(c).kind == 3) {  // dense bins: the rows are the bins that are not zero (tiny: counted on the host)
+      if (table_of(c).kind == MK_TABLE_DENSE) {  // dense bins: the rows are the bins that are not zero (tiny: counted on the host)
         size_t r0 = 0;
         if ((r = mk_export_size(c, &r0)) != MK_OK) { bad = i; return r; }
         rows_before[i] = r0 - c->run_ref_rows;
@@ -546,7 +497,7 @@ extern "C" int mk_merge_devices(mk_ctx* const* ctxs, int n, int flags, mk_merge_
       }
       if (!packed) return MK_OK;
       const TableRef t = table_of(c);
-      const size_t cap = (t.kind == 3 ? t.slots : t.rows) + 1;  // (the rows the host knows of, + the one key kept beside the table)
+      const size_t cap = (t.kind == MK_TABLE_DENSE ? t.slots : t.rows) + 1;  // (the rows the host knows of, + the one key kept beside the table)
       if (hipSetDevice(c->device) != hipSuccess) { bad = i; c->err = "hipSetDevice failed"; return MK_ERR_HIP; }
       if ((r = mk_buf_reserve(c, c->xfer_out, cap * rw * sizeof(u64) + 64)) != MK_OK) { bad = i; return r; }
       if ((r = bucket_rows(c, bounds, m, (u64*)c->xfer_out.p, cap, counts[i].data(), m - 1)) != MK_OK) { bad = i; return r; }
@@ -722,8 +673,8 @@ extern "C" int mk_merge_devices(mk_ctx* const* ctxs, int n, int flags, mk_merge_
         }
         if (recv[j] && (r = mk_launch_import_rows(c, (const uint64_t*)c->xfer_in.p, (size_t)recv[j])) != MK_OK) { bad = j; return r; }
         if ((r = mk_pull_info(c)) != MK_OK) { bad = j; return r; }
-        if (c->mode == MK_MODE_HASH128) c->run128_rows += (size_t)c->h_info->new_rows;
-        else if (c->mode == MK_MODE_HASH64) { c->run_rows += (size_t)c->h_info->new_rows; c->run_side += c->h_info->side; }
+        mk_add_packed_rows(c, (size_t)c->h_info->new_rows);
+        if (c->mode == MK_MODE_HASH64) c->run_side += c->h_info->side;
       } else {
         if (hipStreamSynchronize(c->stream) != hipSuccess) { bad = j; c->err = "hipStreamSynchronize failed"; return MK_ERR_HIP; }
       }

@@ -36,7 +36,6 @@
 #define CNT_THREADS 1024
 #define SUB_BITS 24                         // hash bits available for splitting a bucket
 
-static size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
 // --------------------------------------------------------------------------- 1 histogram
 template <int BITS, int SPW, int WPT>

@@ -47,7 +47,6 @@
 #define SK_BUCKET_SYMS 8192     // symbols of the chunk per bucket the bucket count aims at (~1.2K records, ~10K windows)
 #endif
 #define SK_NOFIT 0xFF000000u    // lh[] value of a (tile, bucket) run that does not fit its region: nothing is stored
-static size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
 template <int W, class F>
 __device__ __forceinline__ void sk_for_each_record(u64 w0, u64 w1, u64 badw, int k, int nkmax, bool canon, F&& emit) {

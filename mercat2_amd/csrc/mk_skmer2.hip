@@ -42,7 +42,6 @@
 #define SK2C_MAX_PROBE 64
 #define SK2C_LOCK 0x80000000u
 
-static size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
 // The minimizer of a window is taken over the 22 candidate 11-mers of its FIRST 32 bases: the analysis is the
 // k = 32 instantiation of mk_skmer_dev.h's.

@@ -6,50 +6,50 @@
 // before the merge -- there is no post-merge filter in the reference (SURVEY.md trap T2).
 #include "mk_common.h"
 #include "mk_device.h"
+#include "mk_tableview.h"
+#include <type_traits>
 
-typedef unsigned long long u64;
 #define REF_POS_BITS 40
 #define REF_POS_MASK ((1ull << REF_POS_BITS) - 1)
 
-static size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
-static unsigned grid_for(size_t items, unsigned per_block = 256, unsigned cap = 1u << 20) {
-  size_t g = div_up(items, per_block);
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return (unsigned)g;
+// Every kernel of this file is launched like this: 256 threads a workgroup, on the context's stream.
+template <class... A>
+static int launch(mk_ctx* c, void (*kernel)(A...), unsigned grid, std::common_type_t<A>... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, c->stream, args...);
+  MK_HIP(hipGetLastError());
+  return MK_OK;
 }
 
 // ----------------------------------------------------------------------------------- clear
 __global__ void mk_clear_slots_k(MkSlot* __restrict__ t, size_t slots) {
   const ulonglong2 e = make_ulonglong2(MK_EMPTY, 0ull);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x)
-    reinterpret_cast<ulonglong2*>(t)[i] = e;
+  mk_for_each(slots, [&](size_t i) { reinterpret_cast<ulonglong2*>(t)[i] = e; });
 }
 
-int mk_launch_clear_slots(mk_ctx* c, MkSlot* t, size_t slots) {
+// A free MkSlot holds the key MK_EMPTY; a free MkSlot128 and an empty bin are all zero bits.
+int mk_clear_table(mk_ctx* c, int kind, void* t, size_t slots) {
   if (!slots) return MK_OK;
-  hipLaunchKernelGGL(mk_clear_slots_k, dim3(grid_for(slots, 256, 16384)), dim3(256), 0, c->stream, t, slots);
-  MK_HIP(hipGetLastError());
+  if (kind == MK_TABLE_TWO) MK_HIP(hipMemsetAsync(t, 0, slots * sizeof(MkSlot128), c->stream));
+  else if (kind == MK_TABLE_DENSE) MK_HIP(hipMemsetAsync(t, 0, slots * sizeof(u64), c->stream));
+  else return launch(c, mk_clear_slots_k, grid_for(slots, 256, 16384), (MkSlot*)t, slots);
   return MK_OK;
 }
 
 // ------------------------------------------------------------------------------ survivors
 __global__ void mk_count_survivors_k(const MkSlot* __restrict__ t, size_t slots, u64 min_count, u64* __restrict__ out) {
   u64 mine = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
+  mk_for_each(slots, [&](size_t i) {
     ulonglong2 s = reinterpret_cast<const ulonglong2*>(t)[i];
-    mine += (s.x != MK_EMPTY && s.y >= min_count) ? 1 : 0;
-  }
+    mine += ((s.x != MK_EMPTY) & (s.y >= min_count)) ? 1 : 0;  // (no short cut: the slot stays one 16-byte load)
+  });
   block_add(out, mine);
 }
 
 int mk_launch_count_survivors(mk_ctx* c, uint64_t min_count) {
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  if (c->rtab_chunk_slots)
-    hipLaunchKernelGGL(mk_count_survivors_k, dim3(grid_for(c->rtab_chunk_slots, 256, 8192)), dim3(256), 0, c->stream,
-                       (const MkSlot*)c->rtab_chunk.p, c->rtab_chunk_slots, (u64)min_count, &info->survivors_ref);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  if (!c->rtab_chunk_slots) return MK_OK;
+  return launch(c, mk_count_survivors_k, grid_for(c->rtab_chunk_slots, 256, 8192), (const MkSlot*)c->rtab_chunk.p,
+                c->rtab_chunk_slots, min_count, &info->survivors_ref);
 }
 
 // ------------------------------------------------------------------- running table: hash64
@@ -70,31 +70,6 @@ __device__ __forceinline__ bool upsert64(MkSlot* __restrict__ table, u64 mask, u
     }
     slot = (slot + 1) & mask;
   }
-}
-
-__global__ void mk_accumulate64_k(const MkSlot* __restrict__ from, size_t slots, u64 min_count, MkSlot* __restrict__ run,
-                                  u64 run_mask, u64* __restrict__ new_rows) {
-  u64 fresh = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
-    ulonglong2 s = reinterpret_cast<const ulonglong2*>(from)[i];
-    if (s.x != MK_EMPTY && s.y >= min_count && s.y != 0) fresh += upsert64(run, run_mask, s.x, s.y) ? 1 : 0;
-  }
-  block_add(new_rows, fresh);
-}
-
-// The all-ones key (32 x 'T') cannot live in the table (it is the free-slot mark): wherever it stands in
-// the rows -- rows received from several peers are a concatenation of sorted segments -- its count goes
-// to *side (the context keeps that one key beside the table).
-__global__ void mk_import_pairs_k(const u64* __restrict__ keys, const u64* __restrict__ cnts, size_t rows,
-                                  MkSlot* __restrict__ run, u64 run_mask, u64* __restrict__ new_rows, u64* __restrict__ side) {
-  u64 fresh = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-    const u64 key = keys[i], cnt = cnts[i];
-    if (!cnt) continue;
-    if (key == MK_EMPTY) atomicAdd(side, cnt);
-    else fresh += upsert64(run, run_mask, key, cnt) ? 1 : 0;
-  }
-  block_add(new_rows, fresh);
 }
 
 // The same for keys that are DISTINCT within the launch and that no other launch adds to at the same time -- the
@@ -124,66 +99,6 @@ __device__ __forceinline__ bool upsert64_distinct(MkSlot* __restrict__ table, u6
     }
     slot = (slot + 1) & mask;
   }
-}
-
-// Survivors laid out per bucket: bucket b holds nsurv[b] pairs from kstart[b] on. One wave per bucket.
-// ATOMIC: the counts are added with atomics -- for a table that other contexts' count kernels upsert into at the same
-// time (mk_share_table); otherwise the plain-store form above.
-template <bool ATOMIC>
-__global__ void mk_import_regions_k(const u64* __restrict__ keys, const u64* __restrict__ cnts, const u64* __restrict__ kstart,
-                                    const u64* __restrict__ nsurv, size_t p1, MkSlot* __restrict__ run, u64 run_mask,
-                                    u64* __restrict__ new_rows) {
-  u64 fresh = 0;
-  const int lane = threadIdx.x & 63;
-  for (size_t b = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); b < p1; b += (size_t)gridDim.x * (blockDim.x >> 6)) {
-    const u64 base = kstart[b], n = nsurv[b];
-    if (ATOMIC) { for (u64 i = lane; i < n; i += 64) fresh += upsert64(run, run_mask, keys[base + i], cnts[base + i]) ? 1 : 0; }
-    else { for (u64 i = lane; i < n; i += 64) fresh += upsert64_distinct(run, run_mask, keys[base + i], cnts[base + i]) ? 1 : 0; }
-  }
-  block_add(new_rows, fresh);
-}
-
-// Pairs that are DISTINCT within the launch (a chunk's survivors from the direct-index and the 8-byte-key paths: every
-// key is counted in one bucket) into a table nobody else writes meanwhile: the plain-store upsert above.
-__global__ void mk_import_pairs_distinct_k(const u64* __restrict__ keys, const u64* __restrict__ cnts, size_t rows,
-                                           MkSlot* __restrict__ run, u64 run_mask, u64* __restrict__ new_rows, u64* __restrict__ side) {
-  u64 fresh = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-    const u64 key = keys[i], cnt = cnts[i];
-    if (!cnt) continue;
-    if (key == MK_EMPTY) atomicAdd(side, cnt);
-    else fresh += upsert64_distinct(run, run_mask, key, cnt) ? 1 : 0;
-  }
-  block_add(new_rows, fresh);
-}
-
-int mk_launch_import_regions(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* kstart,
-                             const uint64_t* nsurv, size_t p1, size_t survivors) {
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  // (few workgroups, each wave walking several buckets: every workgroup ends with one add to the same counter, and
-  // adds to one address are serialised by the L2 at ~4 ns each)
-  // Many survivors per bucket (-c 1, canonical keys: a bucket keeps a thousand keys, each upsert is two dependent
-  // round trips to HBM): every bucket gets its own wave at once -- the kernel is bound by requests in flight.
-  const unsigned cap = survivors > 64 * p1 ? 4096u : 512u;
-  // (the plain-store form is chosen and enqueued under the table's lock, shared: a context that attaches as a sharer
-  // meanwhile -- mk_share_table, the lock exclusive -- drains this stream before its first launch into the table)
-  std::shared_lock<std::shared_mutex> rd(c->table_mu);
-  if (c->n_sharers)
-    hipLaunchKernelGGL(mk_import_regions_k<true>, dim3(grid_for(p1 * 64, 256, cap)), dim3(256), 0, c->stream, (const u64*)d_keys,
-                       (const u64*)d_counts, (const u64*)kstart, (const u64*)nsurv, p1, (MkSlot*)c->run.p,
-                       (u64)(c->run_slots - 1), &info->new_rows);
-  else
-    hipLaunchKernelGGL(mk_import_regions_k<false>, dim3(grid_for(p1 * 64, 256, cap)), dim3(256), 0, c->stream, (const u64*)d_keys,
-                       (const u64*)d_counts, (const u64*)kstart, (const u64*)nsurv, p1, (MkSlot*)c->run.p,
-                       (u64)(c->run_slots - 1), &info->new_rows);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-__global__ void mk_import_bins_k(const u64* __restrict__ keys, const u64* __restrict__ cnts, size_t rows,
-                                 u64* __restrict__ bins, size_t nbins) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x)
-    if (keys[i] < nbins) atomicAdd(&bins[keys[i]], cnts[i]);
 }
 
 // ------------------------------------------------------------- running table: two-word keys
@@ -244,110 +159,153 @@ __device__ __forceinline__ bool upsert128(MkSlot128* __restrict__ t, u64 mask, u
   return fresh;
 }
 
-// Survivors of the partitioned 33..64-mer path: {hi, lo, count} per bucket region. One wave per bucket.
-__global__ void mk_import128_regions_k(const u64* __restrict__ hi, const u64* __restrict__ lo, const u64* __restrict__ cnts,
-                                       const u64* __restrict__ kstart, const u64* __restrict__ nsurv, size_t p1,
-                                       MkSlot128* __restrict__ run, u64 run_mask, u64* __restrict__ new_rows) {
+// ---- where rows go: put(a, b, count) -> the key was new to the table ---------------------------------------------
+// The all-ones key (32 x 'T') cannot live in the one-word table (it is the free-slot mark): wherever it stands in
+// the rows -- rows received from several peers are a concatenation of sorted segments -- its count goes
+// to *side (the context keeps that one key beside the table).
+// DISTINCT: the plain-store upsert, for keys that are distinct within the launch (a chunk's survivors: every key is
+// counted in one bucket) into a table nobody else writes meanwhile.
+template <bool DISTINCT>
+struct Sink64 {
+  MkSlot* run;
+  u64 mask;
+  u64* side;
+  static constexpr int W = 1;
+  static constexpr bool COUNTS = true;
+  __device__ __forceinline__ bool put(u64 key, u64, u64 cnt) const {
+    if (key == MK_EMPTY) { atomicAdd(side, cnt); return false; }
+    return DISTINCT ? upsert64_distinct(run, mask, key, cnt) : upsert64(run, mask, key, cnt);
+  }
+};
+struct Sink128 {
+  MkSlot128* run;
+  u64 mask;
+  static constexpr int W = 2;
+  static constexpr bool COUNTS = true;
+  __device__ __forceinline__ bool put(u64 hi, u64 lo, u64 cnt) const { return upsert128(run, mask, hi, lo, cnt); }
+};
+struct SinkBins {  // (a bin is never new: these instances count no rows)
+  u64* bins;
+  size_t nbins;
+  static constexpr int W = 1;
+  static constexpr bool COUNTS = false;
+  __device__ __forceinline__ bool put(u64 bin, u64, u64 cnt) const {
+    if (bin < nbins) atomicAdd(&bins[bin], cnt);
+    return false;
+  }
+};
+
+// Every row of a source (mk_tableview.h: columns, interleaved rows, another table's slots) into a sink.
+template <class Source, class Sink>
+__global__ void mk_import_k(Source src, size_t rows, Sink sink, u64* __restrict__ new_rows) {
+  u64 fresh = 0;
+  mk_for_each(rows, [&](size_t i) {
+    u64 a, b, cnt;
+    if (src.get(i, a, b, cnt)) fresh += sink.put(a, b, cnt) ? 1 : 0;
+  });
+  if constexpr (Sink::COUNTS) block_add(new_rows, fresh);
+}
+
+// Survivors laid out per bucket: bucket b holds nsurv[b] rows {ka, (kb,) cnts} from kstart[b] on. One wave per bucket.
+template <class Sink>
+__global__ void mk_import_regions_k(const u64* __restrict__ ka, const u64* __restrict__ kb, const u64* __restrict__ cnts,
+                                    const u64* __restrict__ kstart, const u64* __restrict__ nsurv, size_t p1, Sink sink,
+                                    u64* __restrict__ new_rows) {
   u64 fresh = 0;
   const int lane = threadIdx.x & 63;
   for (size_t b = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); b < p1; b += (size_t)gridDim.x * (blockDim.x >> 6)) {
     const u64 base = kstart[b], n = nsurv[b];
-    for (u64 i = lane; i < n; i += 64) fresh += upsert128(run, run_mask, hi[base + i], lo[base + i], cnts[base + i]) ? 1 : 0;
+    for (u64 i = lane; i < n; i += 64) fresh += sink.put(ka[base + i], Sink::W == 2 ? kb[base + i] : 0, cnts[base + i]) ? 1 : 0;
   }
   block_add(new_rows, fresh);
 }
 
+static Sink128 sink128(mk_ctx* c) { return Sink128{(MkSlot128*)c->run128.p, (u64)(c->run128_slots - 1)}; }
+template <bool DISTINCT>
+static Sink64<DISTINCT> sink64(mk_ctx* c) {
+  return Sink64<DISTINCT>{(MkSlot*)c->run.p, (u64)(c->run_slots - 1), &((MkChunkInfo*)c->info.p)->side};
+}
+static SinkBins sink_bins(mk_ctx* c) { return SinkBins{(u64*)c->run.p, (size_t)1 << (c->bits * c->k)}; }
+
+int mk_launch_import_regions(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* kstart,
+                             const uint64_t* nsurv, size_t p1, size_t survivors) {
+  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
+  // (few workgroups, each wave walking several buckets: every workgroup ends with one add to the same counter, and
+  // adds to one address are serialised by the L2 at ~4 ns each)
+  // Many survivors per bucket (-c 1, canonical keys: a bucket keeps a thousand keys, each upsert is two dependent
+  // round trips to HBM): every bucket gets its own wave at once -- the kernel is bound by requests in flight.
+  const unsigned cap = survivors > 64 * p1 ? 4096u : 512u;
+  // (the plain-store form is chosen and enqueued under the table's lock, shared: a context that attaches as a sharer
+  // meanwhile -- mk_share_table, the lock exclusive -- drains this stream before its first launch into the table)
+  std::shared_lock<std::shared_mutex> rd(c->table_mu);
+  const u64 *keys = (const u64*)d_keys, *cnts = (const u64*)d_counts, *ks = (const u64*)kstart, *ns = (const u64*)nsurv;
+  // (with sharers the counts are added with atomics: other contexts' count kernels upsert into the table at the same time)
+  if (c->n_sharers)
+    return launch(c, mk_import_regions_k<Sink64<false>>, grid_for(p1 * 64, 256, cap), keys, nullptr, cnts, ks, ns, p1,
+                  sink64<false>(c), &info->new_rows);
+  return launch(c, mk_import_regions_k<Sink64<true>>, grid_for(p1 * 64, 256, cap), keys, nullptr, cnts, ks, ns, p1,
+                sink64<true>(c), &info->new_rows);
+}
+
+// Survivors of the partitioned 33..64-mer path: {hi, lo, count} per bucket region.
 int mk_launch_import128_regions(mk_ctx* c, const uint64_t* hi, const uint64_t* lo, const uint64_t* cnts, const uint64_t* kstart,
                                 const uint64_t* nsurv, size_t p1) {
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  hipLaunchKernelGGL(mk_import128_regions_k, dim3(grid_for(p1 * 64, 256, 512)), dim3(256), 0, c->stream, (const u64*)hi,
-                     (const u64*)lo, (const u64*)cnts, (const u64*)kstart, (const u64*)nsurv, p1, (MkSlot128*)c->run128.p,
-                     (u64)(c->run128_slots - 1), &info->new_rows);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  return launch(c, mk_import_regions_k<Sink128>, grid_for(p1 * 64, 256, 512), (const u64*)hi, (const u64*)lo, (const u64*)cnts,
+                (const u64*)kstart, (const u64*)nsurv, p1, sink128(c), &info->new_rows);
 }
 
-// Rows {hi, lo} interleaved + counts (another context's or rank's table; the same key may come more than once).
-__global__ void mk_import128_pairs_k(const u64* __restrict__ keys2, const u64* __restrict__ cnts, size_t rows,
-                                     MkSlot128* __restrict__ run, u64 run_mask, u64* __restrict__ new_rows) {
-  u64 fresh = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x)
-    if (cnts[i]) fresh += upsert128(run, run_mask, keys2[2 * i], keys2[2 * i + 1], cnts[i]) ? 1 : 0;
-  block_add(new_rows, fresh);
-}
-
-int mk_launch_import128_pairs(mk_ctx* c, const uint64_t* d_keys2, const uint64_t* d_counts, size_t rows) {
+// Rows as columns: keys (two-word keys: {hi, lo} interleaved) + counts.  Another context's or rank's table, where the
+// same key may come more than once, or (distinct) a chunk's survivors from the direct-index and the 8-byte-key paths.
+int mk_launch_import_pairs(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows, bool distinct) {
   if (!rows) return MK_OK;
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  hipLaunchKernelGGL(mk_import128_pairs_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, (const u64*)d_keys2,
-                     (const u64*)d_counts, rows, (MkSlot128*)c->run128.p, (u64)(c->run128_slots - 1), &info->new_rows);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  u64* new_rows = &((MkChunkInfo*)c->info.p)->new_rows;
+  const Cols64 cols{(const u64*)d_keys, (const u64*)d_counts};
+  if (c->mode == MK_MODE_HASH128)
+    return launch(c, mk_import_k<Cols128, Sink128>, grid_for(rows, 256, 8192), Cols128{cols.keys, cols.cnts}, rows, sink128(c), new_rows);
+  if (c->mode == MK_MODE_DENSE) return launch(c, mk_import_k<Cols64, SinkBins>, grid_for(rows), cols, rows, sink_bins(c), new_rows);
+  std::shared_lock<std::shared_mutex> rd(c->table_mu);  // (the plain-store form: see mk_launch_import_regions)
+  if (distinct && c->mode == MK_MODE_HASH64 && !c->n_sharers)
+    return launch(c, mk_import_k<Cols64, Sink64<true>>, grid_for(rows, 256, 8192), cols, rows, sink64<true>(c), new_rows);
+  return launch(c, mk_import_k<Cols64, Sink64<false>>, grid_for(rows, 256, 8192), cols, rows, sink64<false>(c), new_rows);
 }
 
-// Re-insert after growth: rows are distinct and final -> claim the first free slot.
-__global__ void mk_rehash128_k(const MkSlot128* __restrict__ from, size_t slots, MkSlot128* __restrict__ to, u64 to_mask) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
-    const ulonglong4 s = reinterpret_cast<const ulonglong4*>(from)[i];
-    if (s.z == 0) continue;
-    u64 slot = home128(s.x, s.y, to_mask);
-    for (;;) {
-      if (atomicCAS(&to[slot].cnt, 0ull, s.z) == 0ull) {
-        to[slot].hi = s.x;
-        to[slot].lo = s.y;
-        break;
-      }
-      slot = (slot + 1) & to_mask;
-    }
-  }
+// Interleaved rows {key word(s), count} (dense: {bin, count}).
+int mk_launch_import_rows(mk_ctx* c, const uint64_t* d_rows, size_t rows) {
+  if (!rows) return MK_OK;
+  u64* new_rows = &((MkChunkInfo*)c->info.p)->new_rows;
+  const Rows64 rows2{(const ulonglong2*)d_rows};
+  if (c->mode == MK_MODE_DENSE) return launch(c, mk_import_k<Rows64, SinkBins>, grid_for(rows), rows2, rows, sink_bins(c), new_rows);
+  if (c->mode == MK_MODE_HASH64)
+    return launch(c, mk_import_k<Rows64, Sink64<false>>, grid_for(rows, 256, 8192), rows2, rows, sink64<false>(c), new_rows);
+  if (c->mode == MK_MODE_HASH128)
+    return launch(c, mk_import_k<Rows128, Sink128>, grid_for(rows, 256, 8192), Rows128{(const u64*)d_rows}, rows, sink128(c), new_rows);
+  c->err = "import of packed rows: the context has no packed table";
+  return MK_ERR_STATE;
 }
 
-int mk_launch_rehash128(mk_ctx* c, const MkSlot128* from, size_t from_slots, MkSlot128* to, size_t to_slots) {
+// Every row of another one-word table (same device) summed into c's.
+int mk_launch_merge_table64(mk_ctx* c, const MkSlot* from, size_t from_slots) {
   if (!from_slots) return MK_OK;
-  hipLaunchKernelGGL(mk_rehash128_k, dim3(grid_for(from_slots, 256, 8192)), dim3(256), 0, c->stream, from, from_slots, to,
-                     (u64)(to_slots - 1));
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-// Occupied slots -> {hi, lo, count} in arbitrary order; *cursor counts them (wave-aggregated cursor).
-__global__ __launch_bounds__(256) void mk_compact128_k(const MkSlot128* __restrict__ t, size_t slots, u64* __restrict__ hi,
-                                                       u64* __restrict__ lo, u64* __restrict__ cnts, size_t cap,
-                                                       u64* __restrict__ cursor) {
-  const int lane = threadIdx.x & 63;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t rounds = (slots + stride - 1) / stride;
-  for (size_t r = 0; r < rounds; ++r) {
-    const size_t i = r * stride + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    ulonglong4 s = make_ulonglong4(0, 0, 0, 0);
-    if (i < slots) s = reinterpret_cast<const ulonglong4*>(t)[i];
-    const bool keep = s.z != 0;
-    const u64 m = __ballot(keep);
-    if (m) {
-      u64 at = 0;
-      if (lane == 0) at = atomicAdd(cursor, (u64)__popcll(m));
-      const u64 pos = __shfl(at, 0) + __popcll(m & ((1ull << lane) - 1));
-      if (keep && pos < cap) { hi[pos] = s.x; lo[pos] = s.y; cnts[pos] = s.z; }
-    }
-  }
-}
-
-int mk_launch_compact128(mk_ctx* c, const MkSlot128* t, size_t slots, uint64_t* hi, uint64_t* lo, uint64_t* cnts, size_t cap,
-                         uint64_t* d_cursor) {
-  if (!slots) return MK_OK;
-  hipLaunchKernelGGL(mk_compact128_k, dim3(grid_for(slots, 256, 4096)), dim3(256), 0, c->stream, t, slots, (u64*)hi, (u64*)lo,
-                     (u64*)cnts, cap, (u64*)d_cursor);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  return launch(c, mk_import_k<View64, Sink64<false>>, grid_for(from_slots, 256, 2048), View64{from}, from_slots, sink64<false>(c),
+                &((MkChunkInfo*)c->info.p)->new_rows);
 }
 
 // ------------------------------------------------------------------- running table: dense
 __global__ void mk_accumulate_dense_k(u64* __restrict__ chunk, size_t nbins, u64 min_count, u64* __restrict__ run) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbins; i += (size_t)gridDim.x * blockDim.x) {
+  mk_for_each(nbins, [&](size_t i) {
     u64 v = chunk[i];
     if (v >= min_count && v) run[i] += v;
     chunk[i] = 0;
-  }
+  });
+}
+__global__ void mk_refilter_dense_k(u64* __restrict__ bins, size_t nbins, u64 min_count) {
+  mk_for_each(nbins, [&](size_t i) {
+    if (bins[i] < min_count) bins[i] = 0;
+  });
+}
+int mk_launch_refilter_dense(mk_ctx* c, uint64_t* bins, size_t nbins, uint64_t min_count) {
+  return launch(c, mk_refilter_dense_k, grid_for(nbins), (u64*)bins, nbins, min_count);
 }
 
 // --------------------------------------------------------------- running table: by reference
@@ -441,7 +399,7 @@ __global__ void mk_accumulate_ref_k(const MkSlot* __restrict__ from, size_t slot
                                     uint8_t* __restrict__ arena, u64 arena_base, u64* __restrict__ new_rows,
                                     MkSlot128* __restrict__ run128, u64 run128_mask, u64* __restrict__ new_rows128, int aa) {
   u64 fresh128 = 0;  // (one add per workgroup at the end: a counter every new row adds to is serialised by the L2, ~4 ns a row)
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
+  mk_for_each(slots, [&](size_t i) {
     ulonglong2 s = reinterpret_cast<const ulonglong2*>(from)[i];
     if (s.x != MK_EMPTY && s.y >= min_count && s.y != 0) {
       const uint8_t* str = seq + (s.x & REF_POS_MASK);
@@ -468,7 +426,7 @@ __global__ void mk_accumulate_ref_k(const MkSlot* __restrict__ from, size_t slot
       if (packed) fresh128 += upsert128(run128, run128_mask, hi, lo, s.y) ? 1 : 0;
       else upsert_ref(run, run_mask, arena, str, k, s.y, arena_base, new_rows);
     }
-  }
+  });
   if (run128) block_add(new_rows128, fresh128);
 }
 
@@ -477,230 +435,108 @@ __global__ void mk_accumulate_ref_k(const MkSlot* __restrict__ from, size_t slot
 __global__ void mk_import_ref_k(const uint8_t* __restrict__ strs, const u64* __restrict__ cnts, size_t rows, int k,
                                 MkSlot* __restrict__ run, u64 run_mask, uint8_t* __restrict__ arena, u64 arena_base,
                                 u64* __restrict__ new_rows) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x)
+  mk_for_each(rows, [&](size_t i) {
     if (cnts[i]) upsert_ref(run, run_mask, arena, strs + i * (size_t)k, k, cnts[i], arena_base, new_rows);
-}
-
-// Re-insert after growth: rows are distinct and their bytes are final -> only find a free slot.
-__global__ void mk_rehash_ref_k(const MkSlot* __restrict__ from, size_t slots, MkSlot* __restrict__ to, u64 to_mask,
-                                const uint8_t* __restrict__ arena, int k) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
-    ulonglong2 s = reinterpret_cast<const ulonglong2*>(from)[i];
-    if (s.x == MK_EMPTY) continue;
-    const u64 h = poly_hash(arena + (s.x & REF_POS_MASK) * (u64)k, k);
-    u64 slot = h & to_mask;
-    for (;;) {
-      if (atomicCAS(&to[slot].key, MK_EMPTY, s.x) == MK_EMPTY) {
-        to[slot].cnt = s.y;
-        break;
-      }
-      slot = (slot + 1) & to_mask;
-    }
-  }
-}
-
-__global__ void mk_rehash64_k(const MkSlot* __restrict__ from, size_t slots, MkSlot* __restrict__ to, u64 to_mask) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
-    ulonglong2 s = reinterpret_cast<const ulonglong2*>(from)[i];
-    if (s.x == MK_EMPTY) continue;
-    u64 slot = mk_mix64(s.x) & to_mask;
-    for (;;) {
-      if (atomicCAS(&to[slot].key, MK_EMPTY, s.x) == MK_EMPTY) {
-        to[slot].cnt = s.y;
-        break;
-      }
-      slot = (slot + 1) & to_mask;
-    }
-  }
-}
-
-// Rebuild keeping only rows with count >= min_count (the post-merge filter of a single-chunk sample split
-// over several ranks); *kept counts them.
-__global__ void mk_refilter64_k(const MkSlot* __restrict__ from, size_t slots, MkSlot* __restrict__ to, u64 to_mask, u64 min_count,
-                                u64* __restrict__ kept) {
-  u64 mine = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
-    ulonglong2 s = reinterpret_cast<const ulonglong2*>(from)[i];
-    if (s.x == MK_EMPTY || s.y < min_count || s.y == 0) continue;
-    ++mine;
-    u64 slot = mk_mix64(s.x) & to_mask;
-    for (;;) {
-      if (atomicCAS(&to[slot].key, MK_EMPTY, s.x) == MK_EMPTY) {
-        to[slot].cnt = s.y;
-        break;
-      }
-      slot = (slot + 1) & to_mask;
-    }
-  }
-  block_add(kept, mine);
-}
-__global__ void mk_refilter128_k(const MkSlot128* __restrict__ from, size_t slots, MkSlot128* __restrict__ to, u64 to_mask,
-                                 u64 min_count, u64* __restrict__ kept) {
-  u64 mine = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
-    const ulonglong4 s = reinterpret_cast<const ulonglong4*>(from)[i];
-    if (s.z == 0 || s.z < min_count) continue;
-    ++mine;
-    u64 slot = home128(s.x, s.y, to_mask);
-    for (;;) {
-      if (atomicCAS(&to[slot].cnt, 0ull, s.z) == 0ull) {
-        to[slot].hi = s.x;
-        to[slot].lo = s.y;
-        break;
-      }
-      slot = (slot + 1) & to_mask;
-    }
-  }
-  block_add(kept, mine);
-}
-__global__ void mk_refilter_dense_k(u64* __restrict__ bins, size_t nbins, u64 min_count) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbins; i += (size_t)gridDim.x * blockDim.x)
-    if (bins[i] < min_count) bins[i] = 0;
-}
-int mk_launch_refilter64(mk_ctx* c, const MkSlot* from, MkSlot* to, size_t slots, uint64_t min_count, uint64_t* d_kept) {
-  hipLaunchKernelGGL(mk_refilter64_k, dim3(grid_for(slots, 256, 8192)), dim3(256), 0, c->stream, from, slots, to, (u64)(slots - 1),
-                     (u64)min_count, (u64*)d_kept);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-int mk_launch_refilter128(mk_ctx* c, const MkSlot128* from, MkSlot128* to, size_t slots, uint64_t min_count, uint64_t* d_kept) {
-  hipLaunchKernelGGL(mk_refilter128_k, dim3(grid_for(slots, 256, 8192)), dim3(256), 0, c->stream, from, slots, to, (u64)(slots - 1),
-                     (u64)min_count, (u64*)d_kept);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-int mk_launch_refilter_dense(mk_ctx* c, uint64_t* bins, size_t nbins, uint64_t min_count) {
-  hipLaunchKernelGGL(mk_refilter_dense_k, dim3(grid_for(nbins)), dim3(256), 0, c->stream, (u64*)bins, nbins, (u64)min_count);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-int mk_launch_merge_table64(mk_ctx* c, const MkSlot* from, size_t from_slots) {
-  if (!from_slots) return MK_OK;
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  hipLaunchKernelGGL(mk_accumulate64_k, dim3(grid_for(from_slots, 256, 2048)), dim3(256), 0, c->stream, from, from_slots, (u64)0,
-                     (MkSlot*)c->run.p, (u64)(c->run_slots - 1), &info->new_rows);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-int mk_launch_rehash64(mk_ctx* c, const MkSlot* from, size_t from_slots, MkSlot* to, size_t to_slots) {
-  if (!from_slots) return MK_OK;
-  hipLaunchKernelGGL(mk_rehash64_k, dim3(grid_for(from_slots, 256, 8192)), dim3(256), 0, c->stream, from, from_slots, to,
-                     (u64)(to_slots - 1));
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-int mk_launch_rehash_ref(mk_ctx* c, const MkSlot* from, size_t from_slots, MkSlot* to, size_t to_slots) {
-  if (!from_slots) return MK_OK;
-  hipLaunchKernelGGL(mk_rehash_ref_k, dim3(grid_for(from_slots, 256, 8192)), dim3(256), 0, c->stream, from, from_slots,
-                     to, (u64)(to_slots - 1), (const uint8_t*)c->arena.p, c->k);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-// Filter + merge of the chunk tables into the running tables (capacities already ensured).
-int mk_launch_accumulate(mk_ctx* c, uint64_t min_count) {
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  mk_prof_begin(c, MK_K_FILTER);
-  if (c->mode == MK_MODE_DENSE) {
-    const size_t nbins = (size_t)1 << (c->bits * c->k);
-    hipLaunchKernelGGL(mk_accumulate_dense_k, dim3(grid_for(nbins)), dim3(256), 0, c->stream, (u64*)c->ctab.p, nbins,
-                       (u64)min_count, (u64*)c->run.p);
-  }
-  if (c->rtab_chunk_slots && c->h_info->survivors_ref) {
-    hipLaunchKernelGGL(mk_accumulate_ref_k, dim3(grid_for(c->rtab_chunk_slots, 256, 8192)), dim3(256), 0, c->stream,
-                       (const MkSlot*)c->rtab_chunk.p, c->rtab_chunk_slots, (u64)min_count, (const uint8_t*)c->seq.p,
-                       c->k, (MkSlot*)c->run_ref.p, (u64)(c->run_ref_slots - 1), (uint8_t*)c->arena.p,
-                       (u64)c->run_ref_rows, &info->new_rows_ref,
-                       c->mode == MK_MODE_HASH128 ? (MkSlot128*)c->run128.p : (MkSlot128*)nullptr,
-                       (u64)(c->run128_slots ? c->run128_slots - 1 : 0), &info->new_rows, c->alphabet == MK_ALPHABET_AA5 ? 1 : 0);
-  }
-  mk_prof_end(c);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-int mk_launch_import_pairs(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows, bool distinct) {
-  if (!rows) return MK_OK;
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  std::shared_lock<std::shared_mutex> rd(c->table_mu);  // (the plain-store form: see mk_launch_import_regions)
-  if (distinct && c->mode == MK_MODE_HASH64 && !c->n_sharers) {
-    hipLaunchKernelGGL(mk_import_pairs_distinct_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, (const u64*)d_keys,
-                       (const u64*)d_counts, rows, (MkSlot*)c->run.p, (u64)(c->run_slots - 1), &info->new_rows, &info->side);
-    MK_HIP(hipGetLastError());
-    return MK_OK;
-  }
-  if (c->mode == MK_MODE_DENSE) {
-    const size_t nbins = (size_t)1 << (c->bits * c->k);
-    hipLaunchKernelGGL(mk_import_bins_k, dim3(grid_for(rows)), dim3(256), 0, c->stream, (const u64*)d_keys,
-                       (const u64*)d_counts, rows, (u64*)c->run.p, nbins);
-  } else {
-    hipLaunchKernelGGL(mk_import_pairs_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, (const u64*)d_keys,
-                       (const u64*)d_counts, rows, (MkSlot*)c->run.p, (u64)(c->run_slots - 1), &info->new_rows, &info->side);
-  }
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-// Interleaved rows {key, count} / {hi, lo, count} / {bin, count}: the layout rows travel in between GPUs
-// (mk_multi.hip, mercat2_amd/dist.py), so that a row's words move side by side and are read with one access.
-__global__ void mk_import_rows64_k(const ulonglong2* __restrict__ rows2, size_t rows, MkSlot* __restrict__ run, u64 run_mask,
-                                   u64* __restrict__ new_rows, u64* __restrict__ side) {
-  u64 fresh = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-    const ulonglong2 r = rows2[i];
-    if (!r.y) continue;
-    if (r.x == MK_EMPTY) atomicAdd(side, r.y);
-    else fresh += upsert64(run, run_mask, r.x, r.y) ? 1 : 0;
-  }
-  block_add(new_rows, fresh);
-}
-__global__ void mk_import_rows128_k(const u64* __restrict__ rows3, size_t rows, MkSlot128* __restrict__ run, u64 run_mask,
-                                    u64* __restrict__ new_rows) {
-  u64 fresh = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-    const u64 hi = rows3[3 * i], lo = rows3[3 * i + 1], cnt = rows3[3 * i + 2];
-    if (cnt) fresh += upsert128(run, run_mask, hi, lo, cnt) ? 1 : 0;
-  }
-  block_add(new_rows, fresh);
-}
-__global__ void mk_import_rows_bins_k(const ulonglong2* __restrict__ rows2, size_t rows, u64* __restrict__ bins, size_t nbins) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-    const ulonglong2 r = rows2[i];
-    if (r.x < nbins && r.y) atomicAdd(&bins[r.x], r.y);
-  }
-}
-
-int mk_launch_import_rows(mk_ctx* c, const uint64_t* d_rows, size_t rows) {
-  if (!rows) return MK_OK;
-  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  if (c->mode == MK_MODE_DENSE) {
-    hipLaunchKernelGGL(mk_import_rows_bins_k, dim3(grid_for(rows)), dim3(256), 0, c->stream, (const ulonglong2*)d_rows, rows,
-                       (u64*)c->run.p, (size_t)1 << (c->bits * c->k));
-  } else if (c->mode == MK_MODE_HASH64) {
-    hipLaunchKernelGGL(mk_import_rows64_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, (const ulonglong2*)d_rows,
-                       rows, (MkSlot*)c->run.p, (u64)(c->run_slots - 1), &info->new_rows, &info->side);
-  } else if (c->mode == MK_MODE_HASH128) {
-    hipLaunchKernelGGL(mk_import_rows128_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, (const u64*)d_rows, rows,
-                       (MkSlot128*)c->run128.p, (u64)(c->run128_slots - 1), &info->new_rows);
-  } else {
-    c->err = "import of packed rows: the context has no packed table";
-    return MK_ERR_STATE;
-  }
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  });
 }
 
 int mk_launch_import_ref(mk_ctx* c, const uint8_t* d_kmers, const uint64_t* d_counts, size_t rows) {
   if (!rows) return MK_OK;
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
-  hipLaunchKernelGGL(mk_import_ref_k, dim3(grid_for(rows, 256, 8192)), dim3(256), 0, c->stream, d_kmers,
-                     (const u64*)d_counts, rows, c->k, (MkSlot*)c->run_ref.p, (u64)(c->run_ref_slots - 1),
-                     (uint8_t*)c->arena.p, (u64)c->run_ref_rows, &info->new_rows_ref);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  return launch(c, mk_import_ref_k, grid_for(rows, 256, 8192), d_kmers, (const u64*)d_counts, rows, c->k, (MkSlot*)c->run_ref.p,
+                (u64)(c->run_ref_slots - 1), (uint8_t*)c->arena.p, (u64)c->run_ref_rows, &info->new_rows_ref);
+}
+
+// Filter + merge of the chunk tables into the running tables (capacities already ensured).
+int mk_launch_accumulate(mk_ctx* c, uint64_t min_count) {
+  MkChunkInfo* info = (MkChunkInfo*)c->info.p;
+  int rc = MK_OK;
+  mk_prof_begin(c, MK_K_FILTER);
+  if (c->mode == MK_MODE_DENSE) {
+    const size_t nbins = (size_t)1 << (c->bits * c->k);
+    rc = launch(c, mk_accumulate_dense_k, grid_for(nbins), (u64*)c->ctab.p, nbins, min_count, (u64*)c->run.p);
+  }
+  if (rc == MK_OK && c->rtab_chunk_slots && c->h_info->survivors_ref)
+    rc = launch(c, mk_accumulate_ref_k, grid_for(c->rtab_chunk_slots, 256, 8192), (const MkSlot*)c->rtab_chunk.p,
+                c->rtab_chunk_slots, min_count, (const uint8_t*)c->seq.p, c->k, (MkSlot*)c->run_ref.p,
+                (u64)(c->run_ref_slots - 1), (uint8_t*)c->arena.p, (u64)c->run_ref_rows, &info->new_rows_ref,
+                c->mode == MK_MODE_HASH128 ? (MkSlot128*)c->run128.p : (MkSlot128*)nullptr,
+                (u64)(c->run128_slots ? c->run128_slots - 1 : 0), &info->new_rows, c->alphabet == MK_ALPHABET_AA5 ? 1 : 0);
+  mk_prof_end(c);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------- rebuild
+// A row that is final into a fresh table where it is not yet: claim the first free slot from its home on.
+__device__ __forceinline__ void place(MkSlot* __restrict__ to, u64 to_mask, u64 slot, u64 key, u64, u64 cnt) {
+  for (;;) {
+    if (atomicCAS(&to[slot].key, MK_EMPTY, key) == MK_EMPTY) {
+      to[slot].cnt = cnt;
+      break;
+    }
+    slot = (slot + 1) & to_mask;
+  }
+}
+__device__ __forceinline__ void place(MkSlot128* __restrict__ to, u64 to_mask, u64 slot, u64 hi, u64 lo, u64 cnt) {
+  for (;;) {
+    if (atomicCAS(&to[slot].cnt, 0ull, cnt) == 0ull) {
+      to[slot].hi = hi;
+      to[slot].lo = lo;
+      break;
+    }
+    slot = (slot + 1) & to_mask;
+  }
+}
+// Home slot of a row, by table: the key's hash; by reference, the hash of the arena row the key names.
+struct Home64 {
+  __device__ __forceinline__ u64 operator()(u64 key, u64, u64 mask) const { return mk_mix64(key) & mask; }
+};
+struct Home128 {
+  __device__ __forceinline__ u64 operator()(u64 hi, u64 lo, u64 mask) const { return home128(hi, lo, mask); }
+};
+struct HomeRef {
+  const uint8_t* arena;
+  int k;
+  __device__ __forceinline__ u64 operator()(u64 key, u64, u64 mask) const {
+    return poly_hash(arena + (key & REF_POS_MASK) * (u64)k, k) & mask;
+  }
+};
+
+// The rows of a table into a fresh one.  Re-insert after growth: every slot that holds a key (the rows are distinct and,
+// by reference, their bytes final).  FILTER: only the rows with count >= min_count (the post-merge filter of a
+// single-chunk sample split over several ranks); *kept counts them.
+template <class View, class Slot, class Home, bool FILTER>
+__global__ void mk_rebuild_k(View from, size_t slots, Slot* __restrict__ to, u64 to_mask, Home home, u64 min_count,
+                             u64* __restrict__ kept) {
+  u64 mine = 0;
+  mk_for_each(slots, [&](size_t i) {
+    u64 a, b, cnt;
+    if (!(FILTER ? from.get(i, a, b, cnt) && cnt >= min_count : from.keyed(i, a, b, cnt))) return;
+    ++mine;
+    place(to, to_mask, home(a, b, to_mask), a, b, cnt);
+  });
+  if constexpr (FILTER) block_add(kept, mine);
+}
+
+template <bool FILTER, class View, class Slot, class Home>
+static int launch_rebuild(mk_ctx* c, View from, size_t from_slots, Slot* to, size_t to_slots, Home home, uint64_t min_count,
+                          uint64_t* d_kept) {
+  return launch(c, mk_rebuild_k<View, Slot, Home, FILTER>, grid_for(from_slots, 256, 8192), from, from_slots, to, to_slots - 1, home,
+                min_count, (u64*)d_kept);
+}
+// d_kept != nullptr: keep the rows with count >= min_count and count them there; else every keyed slot.
+int mk_launch_rebuild(mk_ctx* c, int kind, const void* from, size_t from_slots, void* to, size_t to_slots, uint64_t min_count,
+                      uint64_t* d_kept) {
+  if (!from_slots) return MK_OK;
+  const View64 v1{(const MkSlot*)from};
+  const View128 v2{(const MkSlot128*)from};
+  if (kind == MK_TABLE_REF)  // (only ever grown: mk_filter_min filters the rows kept as text on the host)
+    return launch_rebuild<false>(c, v1, from_slots, (MkSlot*)to, to_slots, HomeRef{(const uint8_t*)c->arena.p, c->k}, 0, nullptr);
+  if (kind == MK_TABLE_TWO)
+    return d_kept ? launch_rebuild<true>(c, v2, from_slots, (MkSlot128*)to, to_slots, Home128{}, min_count, d_kept)
+                  : launch_rebuild<false>(c, v2, from_slots, (MkSlot128*)to, to_slots, Home128{}, 0, nullptr);
+  return d_kept ? launch_rebuild<true>(c, v1, from_slots, (MkSlot*)to, to_slots, Home64{}, min_count, d_kept)
+                : launch_rebuild<false>(c, v1, from_slots, (MkSlot*)to, to_slots, Home64{}, 0, nullptr);
 }
 
 // --------------------------------------------------------------------------------- compact
@@ -748,10 +584,35 @@ __global__ __launch_bounds__(256) void mk_compact_k(const MkSlot* __restrict__ t
 int mk_launch_compact(mk_ctx* c, const MkSlot* t, size_t slots, uint64_t* d_keys, uint64_t* d_counts, size_t cap,
                       uint64_t* d_cursor) {
   if (!slots) return MK_OK;
-  hipLaunchKernelGGL(mk_compact_k, dim3(grid_for(slots, 256, 8192)), dim3(256), 0, c->stream, t, slots, (u64*)d_keys,
-                     (u64*)d_counts, cap, (u64*)d_cursor);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  return launch(c, mk_compact_k, grid_for(slots, 256, 8192), t, slots, (u64*)d_keys, (u64*)d_counts, cap, (u64*)d_cursor);
+}
+
+// Two-word keys: occupied slots -> {hi, lo, count} in arbitrary order; *cursor counts them (wave-aggregated cursor).
+__global__ __launch_bounds__(256) void mk_compact128_k(const MkSlot128* __restrict__ t, size_t slots, u64* __restrict__ hi,
+                                                       u64* __restrict__ lo, u64* __restrict__ cnts, size_t cap,
+                                                       u64* __restrict__ cursor) {
+  const int lane = threadIdx.x & 63;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t rounds = (slots + stride - 1) / stride;
+  for (size_t r = 0; r < rounds; ++r) {
+    const size_t i = r * stride + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    ulonglong4 s = make_ulonglong4(0, 0, 0, 0);
+    if (i < slots) s = reinterpret_cast<const ulonglong4*>(t)[i];
+    const bool keep = s.z != 0;
+    const u64 m = __ballot(keep);
+    if (m) {
+      u64 at = 0;
+      if (lane == 0) at = atomicAdd(cursor, (u64)__popcll(m));
+      const u64 pos = __shfl(at, 0) + __popcll(m & ((1ull << lane) - 1));
+      if (keep && pos < cap) { hi[pos] = s.x; lo[pos] = s.y; cnts[pos] = s.z; }
+    }
+  }
+}
+
+int mk_launch_compact128(mk_ctx* c, const MkSlot128* t, size_t slots, uint64_t* hi, uint64_t* lo, uint64_t* cnts, size_t cap,
+                         uint64_t* d_cursor) {
+  if (!slots) return MK_OK;
+  return launch(c, mk_compact128_k, grid_for(slots, 256, 4096), t, slots, (u64*)hi, (u64*)lo, (u64*)cnts, cap, (u64*)d_cursor);
 }
 
 // ------------------------------------------------------------------- alpha-diversity moments
@@ -767,8 +628,8 @@ __device__ __forceinline__ void alpha_take(u64 c, u64& rows, u64& total, double&
   clnc += d * log(d);
   if (c <= 10) atomicAdd(&s_freq[c], 1u);
 }
-__global__ __launch_bounds__(256) void mk_alpha_k(const MkSlot* __restrict__ slots, size_t nslots, const u64* __restrict__ bins,
-                                                  size_t nbins, u64* __restrict__ out) {
+template <class View>
+__global__ __launch_bounds__(256) void mk_alpha_k(View v, size_t n, u64* __restrict__ out) {
   __shared__ unsigned s_freq[11];
   __shared__ unsigned long long s_rows, s_total;
   __shared__ double s_sq, s_clnc;
@@ -777,45 +638,10 @@ __global__ __launch_bounds__(256) void mk_alpha_k(const MkSlot* __restrict__ slo
   __syncthreads();
   u64 rows = 0, total = 0;
   double sq = 0, clnc = 0;
-  const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (size_t i = first; i < nslots; i += stride) {
-    const ulonglong2 s = reinterpret_cast<const ulonglong2*>(slots)[i];
-    if (s.x != MK_EMPTY) alpha_take(s.y, rows, total, sq, clnc, s_freq);
-  }
-  for (size_t i = first; i < nbins; i += stride) alpha_take(bins[i], rows, total, sq, clnc, s_freq);
-  for (int d = 32; d > 0; d >>= 1) {
-    rows += __shfl_down(rows, d);
-    total += __shfl_down(total, d);
-    sq += __shfl_down(sq, d);
-    clnc += __shfl_down(clnc, d);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&s_rows, (unsigned long long)rows);
-    atomicAdd(&s_total, (unsigned long long)total);
-    atomicAdd(&s_sq, sq);
-    atomicAdd(&s_clnc, clnc);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_rows) atomicAdd(&out[0], (u64)s_rows);
-    if (s_total) atomicAdd(&out[1], (u64)s_total);
-    if (s_sq != 0) atomicAdd(reinterpret_cast<double*>(&out[13]), s_sq);
-    if (s_clnc != 0) atomicAdd(reinterpret_cast<double*>(&out[14]), s_clnc);
-  }
-  if (threadIdx.x < 11 && s_freq[threadIdx.x]) atomicAdd(&out[2 + threadIdx.x], (u64)s_freq[threadIdx.x]);
-}
-
-__global__ __launch_bounds__(256) void mk_alpha128_k(const MkSlot128* __restrict__ slots, size_t nslots, u64* __restrict__ out) {
-  __shared__ unsigned s_freq[11];
-  __shared__ unsigned long long s_rows, s_total;
-  __shared__ double s_sq, s_clnc;
-  if (threadIdx.x < 11) s_freq[threadIdx.x] = 0;
-  if (threadIdx.x == 0) { s_rows = 0; s_total = 0; s_sq = 0; s_clnc = 0; }
-  __syncthreads();
-  u64 rows = 0, total = 0;
-  double sq = 0, clnc = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (size_t)gridDim.x * blockDim.x)
-    alpha_take(slots[i].cnt, rows, total, sq, clnc, s_freq);
+  mk_for_each(n, [&](size_t i) {  // (every thread adds its slots in ascending order)
+    u64 a, b, cnt;
+    if (v.keyed(i, a, b, cnt)) alpha_take(cnt, rows, total, sq, clnc, s_freq);
+  });
   for (int d = 32; d > 0; d >>= 1) {
     rows += __shfl_down(rows, d);
     total += __shfl_down(total, d);
@@ -840,19 +666,14 @@ __global__ __launch_bounds__(256) void mk_alpha128_k(const MkSlot128* __restrict
 
 int mk_launch_alpha(mk_ctx* c, u64* d_out) {
   MK_HIP(hipMemsetAsync(d_out, 0, 16 * sizeof(u64), c->stream));
-  if (c->mode == MK_MODE_DENSE) {
-    hipLaunchKernelGGL(mk_alpha_k, dim3(grid_for(c->run_slots, 256, 1024)), dim3(256), 0, c->stream, (const MkSlot*)nullptr,
-                       (size_t)0, (const u64*)c->run.p, c->run_slots, d_out);
-  } else if (c->run_slots) {
-    hipLaunchKernelGGL(mk_alpha_k, dim3(grid_for(c->run_slots, 256, 1024)), dim3(256), 0, c->stream, (const MkSlot*)c->run.p,
-                       c->run_slots, (const u64*)nullptr, (size_t)0, d_out);
-  }
-  if (c->run_ref_slots)
-    hipLaunchKernelGGL(mk_alpha_k, dim3(grid_for(c->run_ref_slots, 256, 1024)), dim3(256), 0, c->stream,
-                       (const MkSlot*)c->run_ref.p, c->run_ref_slots, (const u64*)nullptr, (size_t)0, d_out);
-  if (c->run128_slots)
-    hipLaunchKernelGGL(mk_alpha128_k, dim3(grid_for(c->run128_slots, 256, 1024)), dim3(256), 0, c->stream,
-                       (const MkSlot128*)c->run128.p, c->run128_slots, d_out);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
+  int rc = MK_OK;
+  if (c->mode == MK_MODE_DENSE)
+    rc = launch(c, mk_alpha_k<ViewDense>, grid_for(c->run_slots, 256, 1024), ViewDense{(const u64*)c->run.p}, c->run_slots, d_out);
+  else if (c->run_slots)
+    rc = launch(c, mk_alpha_k<View64>, grid_for(c->run_slots, 256, 1024), View64{(const MkSlot*)c->run.p}, c->run_slots, d_out);
+  if (rc == MK_OK && c->run_ref_slots)
+    rc = launch(c, mk_alpha_k<View64>, grid_for(c->run_ref_slots, 256, 1024), View64{(const MkSlot*)c->run_ref.p}, c->run_ref_slots, d_out);
+  if (rc == MK_OK && c->run128_slots)
+    rc = launch(c, mk_alpha_k<View128>, grid_for(c->run128_slots, 256, 1024), View128{(const MkSlot128*)c->run128.p}, c->run128_slots, d_out);
+  return rc;
 }

@@ -15,18 +15,12 @@ extern "C" int mk_import_pairs_device(mk_ctx* c, const uint64_t* d_keys, const u
   MK_HIP(hipSetDevice(c->device));
   int rc;
   MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
-  if (c->mode == MK_MODE_HASH128) {  // d_keys: {hi, lo} per row
-    if ((rc = mk_grow_run128(c, c->run128_rows + rows)) != MK_OK) return rc;
-    if ((rc = mk_launch_import128_pairs(c, d_keys, d_counts, rows)) != MK_OK) return rc;
-    if ((rc = mk_pull_info(c)) != MK_OK) return rc;
-    c->run128_rows += (size_t)c->h_info->new_rows;
-    return MK_OK;
-  }
-  // (the all-ones key travels as an ordinary pair, anywhere in the rows: the kernel sets it aside)
-  if (c->mode == MK_MODE_HASH64 && (rc = mk_grow_run64(c, c->run_rows + rows)) != MK_OK) return rc;
+  // (two-word keys: d_keys holds {hi, lo} per row; one-word keys: the all-ones key travels as an ordinary pair, anywhere
+  // in the rows: the kernel sets it aside)
+  if ((rc = mk_grow_run(c, rows)) != MK_OK) return rc;
   if ((rc = mk_launch_import_pairs(c, d_keys, d_counts, rows)) != MK_OK) return rc;
   if ((rc = mk_pull_info(c)) != MK_OK) return rc;
-  c->run_rows += (size_t)c->h_info->new_rows;
+  mk_add_packed_rows(c, (size_t)c->h_info->new_rows);
   if (c->mode == MK_MODE_HASH64) c->run_side += c->h_info->side;
   return MK_OK;
 }
@@ -63,33 +57,16 @@ extern "C" int mk_filter_min(mk_ctx* c, uint64_t min_count) {
   if (min_count <= 1) return MK_OK;
   MK_HIP(hipSetDevice(c->device));
   int rc;
-  u64* d_kept = (u64*)((char*)c->info.p + sizeof(MkChunkInfo));
-  u64 kept = 0;
+  size_t kept = 0;
   if (c->mode == MK_MODE_DENSE) {
     if ((rc = mk_launch_refilter_dense(c, (uint64_t*)c->run.p, c->run_slots, min_count)) != MK_OK) return rc;
   } else if (c->mode == MK_MODE_HASH64 && c->run_slots) {
-    MkDevBuf nb;
-    if ((rc = mk_buf_reserve(c, nb, c->run_slots * sizeof(MkSlot))) != MK_OK) return rc;
-    if ((rc = mk_launch_clear_slots(c, (MkSlot*)nb.p, c->run_slots)) != MK_OK) return rc;
-    MK_HIP(hipMemsetAsync(d_kept, 0, 8, c->stream));
-    if ((rc = mk_launch_refilter64(c, (const MkSlot*)c->run.p, (MkSlot*)nb.p, c->run_slots, min_count, (uint64_t*)d_kept)) != MK_OK) return rc;
-    MK_HIP(hipMemcpyAsync(&kept, d_kept, 8, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    buf_free(c->run);
-    c->run = nb;
-    c->run_rows = (size_t)kept;
+    if ((rc = mk_rebuild_table(c, MK_TABLE_ONE, c->run_slots, min_count, &kept)) != MK_OK) return rc;
+    c->run_rows = kept;
     if (c->run_side < min_count) c->run_side = 0;
   } else if (c->mode == MK_MODE_HASH128 && c->run128_slots) {
-    MkDevBuf nb;
-    if ((rc = mk_buf_reserve(c, nb, c->run128_slots * sizeof(MkSlot128))) != MK_OK) return rc;
-    MK_HIP(hipMemsetAsync(nb.p, 0, c->run128_slots * sizeof(MkSlot128), c->stream));
-    MK_HIP(hipMemsetAsync(d_kept, 0, 8, c->stream));
-    if ((rc = mk_launch_refilter128(c, (const MkSlot128*)c->run128.p, (MkSlot128*)nb.p, c->run128_slots, min_count, (uint64_t*)d_kept)) != MK_OK) return rc;
-    MK_HIP(hipMemcpyAsync(&kept, d_kept, 8, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    buf_free(c->run128);
-    c->run128 = nb;
-    c->run128_rows = (size_t)kept;
+    if ((rc = mk_rebuild_table(c, MK_TABLE_TWO, c->run128_slots, min_count, &kept)) != MK_OK) return rc;
+    c->run128_rows = kept;
   }
   if (c->run_ref_rows) {  // rows kept as text (few): through the host
     size_t n = 0;
@@ -102,7 +79,7 @@ extern "C" int mk_filter_min(mk_ctx* c, uint64_t min_count) {
         km2.insert(km2.end(), km.begin() + i * (size_t)c->k, km.begin() + (i + 1) * (size_t)c->k);
         cn2.push_back(cn[i]);
       }
-    if ((rc = mk_launch_clear_slots(c, (MkSlot*)c->run_ref.p, c->run_ref_slots)) != MK_OK) return rc;
+    if ((rc = mk_clear_table(c, MK_TABLE_REF, c->run_ref.p, c->run_ref_slots)) != MK_OK) return rc;
     c->run_ref_rows = 0;
     if (!cn2.empty() && (rc = mk_import_exotic(c, km2.data(), cn2.data(), cn2.size())) != MK_OK) return rc;
   }
