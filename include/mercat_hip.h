@@ -233,6 +233,51 @@ typedef struct mk_export_stats_t {
 } mk_export_stats_t;
 int mk_export_stats(mk_ctx* ctx, mk_export_stats_t* out);
 
+/* ---- a count table in text form back into the running table: the inverse of mk_write_tsv (ABI 6) ------------
+ * The tsv_<type>/<sample>_counts.tsv files are what MerCat2 users keep; loaded, they feed every call below that works
+ * from tables (mk_write_merged_tsv*, mk_gram, mk_pair_stats, mk_alpha_stats) without counting the reads again.
+ * Lines end in '\n' (the last one may lack it).  A data row is exactly k key bytes (k of the context; any ASCII byte but
+ * '\n': the reference counts any character, and a key it wrote may hold a '\t' -- with k known the row is still
+ * unambiguous), '\t', 1..20 decimal digits whose value fits 64 bits.  Line 1 is a
+ * header iff it is not a data row, so "k-mer\t<name>_Count" files and the header-less "kmer\tcount" dumps of Jellyfish
+ * and KMC both load; column receives the header's second field ("" without a header; column may be NULL).  Rows need
+ * not be sorted.  A byte >= 0x80 anywhere behind the header: MK_ERR_NON_ASCII.  Anything else malformed -- a key of
+ * another length, no tab, an empty count, a non-digit, a count above 2^64 - 1, '\r', an empty line (bytes after the
+ * last '\n' are a line; nothing after it is none) -- MK_ERR_RANGE; mk_last_error names the 1-based line.
+ * The load is an insert-add: a key listed twice, or a second text loaded into the same context, adds up (counts wrap
+ * at 2^64 like every sum of the tables).  Keys are taken AS THEY STAND: a canonical context (mk_set_canonical) does not
+ * fold a loaded key onto its reverse complement -- a table written by a canonical context holds canonical keys already.
+ * Rows with count 0 are skipped.  Keys inside the context's alphabet go to its packed table (dense bins, one- or
+ * two-word keys; the 32 x 'T' key beside the one-word table), the others -- in a by-reference context all -- are kept as
+ * text, exactly where counting puts them.
+ * The text travels to the device in pieces of piece_bytes (0: pick; at least two rows, at most 1 GiB), cut at line
+ * ends, through a pinned double buffer: memory is bounded whatever the file's size.  A piece is validated completely
+ * before any of its rows is imported: a text that fits one piece and is refused leaves the context as it was.  A
+ * refusal in a later piece leaves the pieces before in the table: the context then refuses every call with
+ * MK_ERR_STATE until mk_reset, as after a refused chunk. */
+typedef struct mk_tsv_load_t {
+  uint64_t bytes, lines;      /* text consumed, lines seen (header included)              */
+  uint64_t rows;              /* data rows parsed                                          */
+  uint64_t packed_rows;       /* ... that went to the packed table (or dense bins)         */
+  uint64_t text_rows;         /* ... kept as text (a byte outside the alphabet; by-reference contexts: all) */
+  uint64_t zero_rows;         /* rows with count 0: skipped, never inserted                */
+  uint64_t new_rows;          /* distinct keys the table gained                            */
+  int32_t header;             /* 1: the first line was a header                            */
+  int32_t pieces;             /* pieces the text was loaded in                             */
+  /* seconds: host time reading (copying) the text into the pinned buffer; device time of the line-start and row
+   * kernels; device time of table growth and the import kernels; wall time of the call */
+  double s_read, s_parse, s_import, s_total;
+} mk_tsv_load_t;
+int mk_load_tsv(mk_ctx* ctx, const char* path, size_t piece_bytes, char* column, size_t column_cap, mk_tsv_load_t* st);
+int mk_load_tsv_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, char* column, size_t column_cap,
+                     mk_tsv_load_t* st);
+/* Host helper, no GPU: what a table in text form looks like, for choosing the context to load it into.  *k = key
+ * length of the first data row, up to the line's last tab (0: no data row), *header = 1 when line 1 is not a data row of any key length, column
+ * = its second field, *alphabet_hint = MK_ALPHABET_NT2 when every key among the first 4096 rows is ACGT only, else
+ * MK_ALPHABET_AA5 when they are 'A'..'Z' only, else MK_ALPHABET_RAW.  Only a hint: any table loads into any context of
+ * its k, keys outside the alphabet are kept as text.  Errors: mk_last_error(NULL). */
+int mk_tsv_shape(const char* path, int* k, int* header, int* alphabet_hint, char* column, size_t column_cap);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

@@ -4,7 +4,9 @@
 The count phase and what stands directly in front of and behind it: inputs are
 FASTA (nucleotide or protein; plain or .gz); nucleotide inputs go through removeN first unless
 -skipclean is given (bin/mercat2.py:239-244), exactly as in the reference; the combined tables are
-written after counting.  FASTQ input (.fq, .fastq, plain or .gz) is taken with -skipclean: MerCat2 then
+written after counting.  -tsv DIR takes the samples of an earlier output folder (its
+tsv_<type>/<sample>_counts.tsv files) as they are: their tables are loaded onto the GPU instead of being counted, so a
+cohort grows by one sample, or gets its -pca / -union reports, without recounting.  FASTQ input (.fq, .fastq, plain or .gz) is taken with -skipclean: MerCat2 then
 converts it with fq2fa only (lib/mercat2_fasta.py:175-198) into clean/<base>.fna.gz and counts that as a
 nucleotide sample; here the GPU counts the raw reads the same way while the file is written.  Without
 -skipclean MerCat2 trims the reads with fastp first, a tool this engine does not run: refused.  With -pca and
@@ -29,7 +31,7 @@ from pathlib import Path
 from . import __version__
 from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_background, removeN_text
 from .kmers import read_fasta_bytes
-from .harness import run_raw_clean, run_raw_fastq, run_sample, run_text
+from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_text
 from .report import merge_counters, merge_counters_T
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
@@ -42,6 +44,10 @@ def parseargs(argv=None):
     p = argparse.ArgumentParser(description="MerCat2 k-mer counting on MI355X (count phase only)")
     p.add_argument("-i", required=False, default=list(), help="path to input file", nargs="+")
     p.add_argument("-f", type=str, required=False, help="path to folder containing input files")
+    p.add_argument("-tsv", default=list(), nargs="+", metavar="DIR",
+                   help="earlier output folder(s), or tsv_nucleotide / tsv_protein folders themselves: every <sample>_counts.tsv "
+                        "in them is a sample whose table is loaded as it is, not counted again (-c does not apply to it); "
+                        "-k must be the tables' k-mer length")
     p.add_argument("-k", type=int, required=True, help="kmer length")
     p.add_argument("-n", type=int, default=os.cpu_count() or 1,
                    help="no of cores [auto detect]: samples read (inflated) and counted concurrently, at most 8")
@@ -76,17 +82,44 @@ def parseargs(argv=None):
                    help="EXTENSION (not MerCat2 behaviour): count min(kmer, reverse complement) for nucleotide input")
     p.add_argument("--version", "-v", action="version", version=f"mercat2_amd {__version__}")
     args = p.parse_args(argv)
-    if not args.i and not args.f:
+    if not args.i and not args.f and not args.tsv:
         p.error("Please provide either an input file (-i) or an input folder (-f)")
     for filename in args.i:
         if not os.path.isfile(filename):
             p.error(f"file '{filename}' is not valid.\n")
     if args.f and not os.path.isdir(args.f):
         p.error(f"folder {args.f} is not valid.\n")
+    args.loaded = {"nucleotide": {}, "protein": {}}  # sample -> its count table, per type (-tsv)
+    for d in args.tsv:
+        if not os.path.isdir(d):
+            p.error(f"folder {d} is not valid.\n")
+        found = loaded_tables(Path(d))
+        for kind in found:
+            args.loaded[kind].update(found[kind])
+    for kind in args.loaded:
+        for base, path in args.loaded[kind].items():
+            from . import native
+            k = native.tsv_shape(path)["k"]
+            if k and k != args.k:
+                p.error(f"-k {args.k}: '{path}' holds {k}-mers")
     if args.prod or args.fgs:
         p.error("-prod / -fgs call ORFs with prodigal / FragGeneScanRs before counting amino-acid k-mers; that layer is "
                 "not part of this engine: run the ORF caller and pass its .faa output with -i / -f")
     return args, p
+
+
+def loaded_tables(folder: Path) -> dict:
+    """{"nucleotide": {sample: path}, "protein": {...}}: the <sample>_counts.tsv files of an output folder's
+    tsv_nucleotide / tsv_protein, or of such a folder itself."""
+    found = {"nucleotide": {}, "protein": {}}
+    folder = Path(os.path.abspath(os.path.expanduser(folder)))
+    for kind in found:
+        sub = folder if folder.name == f"tsv_{kind}" else folder / f"tsv_{kind}"
+        if sub.is_dir():
+            for name in sorted(os.listdir(sub)):
+                if name.endswith("_counts.tsv") and (sub / name).is_file():
+                    found[kind][name[: -len("_counts.tsv")]] = sub / name
+    return found
 
 
 def write_diversity(tables, out: Path, kind: str) -> None:
@@ -223,6 +256,11 @@ def main(argv=None) -> int:
             else:
                 fastq.discard(base)
 
+    for kind in samples:
+        both = sorted(set(samples[kind]) & set(args.loaded[kind]))
+        if both:
+            parser.error(f"sample '{both[0]}' is given both as an input file and as a table to load (-tsv)")
+
     from concurrent.futures import ThreadPoolExecutor
     # ---- "Loading files" (bin/mercat2.py:229-298): nucleotide FASTA goes through removeN unless -skipclean, FASTQ
     # through fq2fa.  The text rewrite is native and fast; the level-9 gzip of clean/<base>_clean.fna.gz or
@@ -262,7 +300,7 @@ def main(argv=None) -> int:
     print(f"Time to load {len(samples['nucleotide']) + len(samples['protein'])} files: {round(timeit.default_timer() - load_start, 2)} seconds")
 
     for kind in ("nucleotide", "protein"):
-        if not samples[kind]:
+        if not samples[kind] and not args.loaded[kind]:
             continue
         print("Processing Nucleotides" if kind == "nucleotide" else "Processing protein")
         tsv_dir = out / f"tsv_{kind}"
@@ -348,6 +386,17 @@ def main(argv=None) -> int:
             for line in lines:
                 print(line)
         print(f"Time to count {args.k}-mers: {round(timeit.default_timer() - start, 2)} seconds")
+        # -tsv: tables of an earlier run, loaded as they are; they take the GPUs in turn like small counted samples, and are
+        # written to this run's tsv_<type>/ too, so that the output is a complete result folder
+        if args.loaded[kind]:
+            start = timeit.default_timer()
+            print(f"Loading {len(args.loaded[kind])} count table(s): they are already filtered, -c {args.c} is not applied to them")
+            alphabet = native.ALPHABET_NT2 if kind == "nucleotide" else native.ALPHABET_AA5
+            for idx, (base, path) in enumerate(args.loaded[kind].items(), len(samples[kind])):
+                load_table(base, path, args.k, alphabet, devices[idx % len(devices)], tables, canonical=args.canonical)
+                if base in tables:
+                    tables[base].write_tsv(tsv_dir / f"{base}_counts.tsv", base)
+            print(f"Time to load {len(args.loaded[kind])} tables: {round(timeit.default_timer() - start, 2)} seconds")
         # combined_<type>.tsv: what createFigures writes first (bin/mercat2.py:146-150, merge_tsv), here
         # straight from the tables; samples without significant k-mers are left out, as there
         try:

@@ -25,7 +25,6 @@ from typing import Callable, Dict, Optional, Union
 import numpy as np
 
 from . import native
-from .report import _load_tsv
 
 METRICS = ["shannon", "simpson", "simpson_e", "goods_coverage", "fisher_alpha", "dominance", "chao1", "chao1_ci", "ace"]
 Z = 1.96            # chao1_ci: scikit-bio's default z-score
@@ -120,9 +119,8 @@ def compute_alpha_diversity(basename: str, counts, out_file, *, device: int = 0)
     if isinstance(counts, native.Counter):
         table = alpha_from_stats(counts.alpha_stats())
     else:
-        _, kmers, values = _load_tsv(counts)
-        with native.Counter(max(1, kmers.shape[1] if kmers.size else 1), native.ALPHABET_RAW, device) as ctx:
-            ctx.import_exotic(kmers, values)
+        ctx, _ = native.counter_from_tsv(counts, device=device)  # (parsed and inserted on the GPU)
+        with ctx:
             table = alpha_from_stats(ctx.alpha_stats())
     with open(out_file, "w") as w:
         w.write("Metric\t%s\n" % basename)

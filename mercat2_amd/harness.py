@@ -136,6 +136,39 @@ def _finish(ctx: native.Counter, basename: str, out_file, report=print, timings:
     return basename, None
 
 
+def load_table(basename: str, tsv, kmer: int, alphabet: int, device: int = 0, keep: Optional[dict] = None,
+               report=print, *, canonical: bool = False) -> Tuple[str, Optional[os.PathLike]]:
+    """The loaded-sample counterpart of ``_finish``: the count table ``tsv`` (an earlier run's
+    ``tsv_<type>/<basename>_counts.tsv``) goes into a context of (``alphabet``, ``kmer``) without counting anything
+    (``Counter.load_tsv``).  ``report`` receives ``Loaded <n> rows`` in the place of ``Significant k-mers: N``; with a
+    dict as ``keep`` the table stays on the GPU (``keep[basename]`` = its Counter) when it has rows, as after
+    ``run_sample``.  ``canonical`` only marks the context (so that it can stand beside samples counted with
+    -canonical): loaded keys are taken as they stand.  ValueError when the table's keys are not ``kmer`` bytes long."""
+    shape = native.tsv_shape(tsv)
+    if shape["k"] and shape["k"] != kmer:
+        raise ValueError(f"'{tsv}' holds {shape['k']}-mers, not {kmer}-mers")
+    key = (kmer, alphabet, int(device), bool(canonical and alphabet == native.ALPHABET_NT2))
+    ctx = _take_context(*key)
+    size = 1 << 62
+    try:
+        rows = 0
+        if shape["k"]:
+            ctx.load_tsv(tsv)
+            rows = ctx.rows()
+        size = 0
+        if rows:
+            report(f"Loaded {rows} rows")
+            if keep is not None:
+                keep[basename] = ctx
+                ctx = None
+            return basename, tsv
+        report("No significant k-mers found")
+        return basename, None
+    finally:
+        if ctx is not None:
+            _give_back(ctx, key, size)
+
+
 def run_mercat2(basename: str, files: Sequence, out_file, kmer: int, min_count: int, num_cores: int = 1,
                 *, device: int = 0) -> Tuple[str, Optional[os.PathLike]]:
     """bin/mercat2.py:115-137: count every file (chunk) with its own min_count filter, sum the

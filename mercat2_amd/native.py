@@ -33,9 +33,9 @@ ABI_SYMBOLS = [
     "mk_export_size_multi", "mk_export_multi", "mk_write_tsv_multi", "mk_record_cuts", "mk_sample_keys", "mk_dense_bins_device",
     "mk_device_count", "mk_reset_for", "mk_textwrap", "mk_set_clean", "mk_clean_stats", "mk_clean_runs",
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
-    "mk_pair_stats", "mk_pair_stats_matrix",
+    "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
 ]
-MK_ABI = 5  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
+MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
 
 
@@ -83,6 +83,16 @@ class ExportStats(C.Structure):
     """mk_export_stats_t (include/mercat_hip.h)."""
     _fields_ = ([(n, C.c_uint64) for n in ("rows", "bytes")] +
                 [(n, C.c_double) for n in ("s_sort", "s_d2h", "s_format", "s_write", "s_total")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TsvLoad(C.Structure):
+    """mk_tsv_load_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("bytes", "lines", "rows", "packed_rows", "text_rows", "zero_rows", "new_rows")] +
+                [("header", C.c_int32), ("pieces", C.c_int32)] +
+                [(n, C.c_double) for n in ("s_read", "s_parse", "s_import", "s_total")])
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -206,6 +216,9 @@ def lib() -> C.CDLL:
         "mk_gram_matrix": (C.c_int, [C.c_int, u64p, C.c_size_t, C.c_int, u64p]),
         "mk_pair_stats": (C.c_int, [C.POINTER(vp), C.c_int, C.c_size_t, C.c_void_p, u64p, szp, u64p]),
         "mk_pair_stats_matrix": (C.c_int, [C.c_int, u64p, C.c_size_t, C.c_int, C.c_void_p, u64p, u64p]),
+        "mk_load_tsv": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(TsvLoad)]),
+        "mk_load_tsv_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(TsvLoad)]),
+        "mk_tsv_shape": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -315,6 +328,38 @@ def textwrap_lines(text, width: int = 80) -> list:
         if out.value:
             L.mk_free(out)
     return data.split(b"\n")[:-1] if data else []
+
+
+_COLUMN_CAP = 4096  # bytes kept for a count table's column title
+
+
+def tsv_shape(path) -> dict:
+    """mk_tsv_shape: {"k": key length of the first data row (0: none), "header": line 1 is not a data row, "column": its
+    second field, "alphabet": ALPHABET_NT2 / ALPHABET_AA5 / ALPHABET_RAW by the keys of the first 4096 rows} of a count
+    table in text form.  No GPU is touched."""
+    L = lib()
+    k, header, hint = C.c_int(0), C.c_int(0), C.c_int(0)
+    column = C.create_string_buffer(_COLUMN_CAP)
+    rc = L.mk_tsv_shape(os.fsencode(str(path)), C.byref(k), C.byref(header), C.byref(hint), column, _COLUMN_CAP)
+    if rc:
+        raise MercatHipError(rc, (L.mk_last_error(None) or b"").decode())
+    return {"k": k.value, "header": bool(header.value), "column": column.value.decode("utf-8", "replace"), "alphabet": hint.value}
+
+
+def counter_from_tsv(path, alphabet: Optional[int] = None, device: int = 0, canonical: bool = False) -> Tuple["Counter", dict]:
+    """(Counter, info): a new context of the table's key length holding the rows of the count table at ``path``
+    (Counter.load_tsv); ``info`` is load_tsv's result.  ``alphabet`` None: the hint of tsv_shape.  A table without a
+    data row gives an empty context of k = 1.  The caller closes the Counter."""
+    shape = tsv_shape(path)
+    if alphabet is None:
+        alphabet = shape["alphabet"]
+    ctx = Counter(max(1, shape["k"]), alphabet, device, canonical=canonical and alphabet == ALPHABET_NT2)
+    try:
+        info = ctx.load_tsv(path) if shape["k"] else dict(TsvLoad().as_dict(), column=shape["column"])
+    except BaseException:
+        ctx.close()
+        raise
+    return ctx, info
 
 
 def default_streams(k: int, alphabet: int) -> int:
@@ -699,6 +744,23 @@ class Counter:
     def count_device(self, ptr: int, nbytes: int, min_count: int):
         """Count FASTA bytes already resident in this GPU's memory (ptr = device address)."""
         self._check(self._L.mk_count_device(self._h, ptr, int(nbytes), int(min_count)))
+
+    def load_tsv(self, path_or_bytes, piece_bytes: int = 0) -> dict:
+        """Insert-add a count table in text form -- a path, or the text itself as bytes -- into the running table
+        (mk_load_tsv / mk_load_tsv_text): "<k key bytes>\\t<count>" rows, with or without a header line.  Returns the
+        mk_tsv_load_t fields plus "column", the header's second field.  MercatHipError (MK_ERR_RANGE, the message names
+        the line) for a malformed row, NonAsciiInput for a byte >= 0x80."""
+        st = TsvLoad()
+        column = C.create_string_buffer(_COLUMN_CAP)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            rc = self._L.mk_load_tsv(self._h, os.fsencode(str(path_or_bytes)), int(piece_bytes), column, _COLUMN_CAP, C.byref(st))
+        else:
+            addr, n, keep = _buf_ptr(path_or_bytes)
+            rc = self._L.mk_load_tsv_text(self._h, addr, n, int(piece_bytes), column, _COLUMN_CAP, C.byref(st))
+        self._check(rc)
+        d = st.as_dict()
+        d["column"] = column.value.decode("utf-8", "replace")
+        return d
 
     # -- results
     def rows(self) -> int:

@@ -4,7 +4,7 @@ and PCA, and its transpose that beta diversity reads.
 
 ``merge_counters`` builds it straight from the samples' tables on the GPU (no TSV re-read);
 ``merge_tsv`` keeps the reference's signature (a dict of TSV paths) by loading the files into engine
-tables first.  Header ``<first column>\\t<sorted names>``, then one row per k-mer.
+tables first (``Counter.load_tsv``: parsed and inserted on the GPU).  Header ``<first column>\\t<sorted names>``, then one row per k-mer.
 
 Which rows: the reference's streaming merge looks for the next k-mer only among the samples that advanced in
 the current step and writes a sample's pending count under the k-mer at hand whenever its own key is not
@@ -18,8 +18,6 @@ from __future__ import annotations
 
 import os
 from typing import Dict, Optional
-
-import numpy as np
 
 from . import native
 
@@ -42,20 +40,12 @@ def merge_counters_T(counters: Dict[str, "native.Counter"], out_file) -> int:
     return native.write_merged_tsv_T([counters[n] for n in names], names, out_file)
 
 
-def _load_tsv(path) -> tuple:
-    """(first header field, kmers (rows, k) uint8, counts uint64) of a count table."""
+def _first_header_field(path, shape: dict) -> Optional[str]:
+    """The first field of a count table's header line (the combined table's first column title); None without one."""
+    if not shape["header"]:
+        return None
     with open(path, "rb") as fh:
-        head = fh.readline().decode().split("\t")[0]
-        body = fh.read()
-    if not body.strip():
-        return head, np.zeros((0, 0), np.uint8), np.zeros(0, np.uint64)
-    lines = body.split(b"\n")
-    if not lines[-1]:
-        lines.pop()
-    k = lines[0].index(b"\t")
-    flat = np.frombuffer(b"".join(l[:k] for l in lines), dtype=np.uint8).reshape(len(lines), k)
-    counts = np.array([int(l[k + 1:]) for l in lines], dtype=np.uint64)
-    return head, flat, counts
+        return fh.readline().decode().split("\t")[0]
 
 
 def merge_tsv_T(tsv_list: Dict[str, os.PathLike], out_file: os.PathLike, *, device: int = 0) -> None:
@@ -74,17 +64,17 @@ def _merge_files(tsv_list, out_file, device: int, transposed: bool) -> None:
     header: Optional[str] = None
     ctxs = []
     try:
-        loaded = []
-        for name in names:
-            head, kmers, counts = _load_tsv(tsv_list[name])
-            if header is None:
-                header = head
-            loaded.append((kmers, counts))
-        k = next((km.shape[1] for km, _ in loaded if km.size), 1)
-        for kmers, counts in loaded:
-            c = native.Counter(k, native.ALPHABET_RAW, device)
+        # one alphabet and one k for all tables of the call: those of the first file that has rows
+        shapes = [native.tsv_shape(tsv_list[name]) for name in names]
+        first = next((s for s in shapes if s["k"]), None)
+        k, alphabet = (first["k"], first["alphabet"]) if first else (1, native.ALPHABET_RAW)
+        if names:
+            header = _first_header_field(tsv_list[names[0]], shapes[0])
+        for name, shape in zip(names, shapes):
+            c = native.Counter(k, alphabet, device)
             ctxs.append(c)
-            c.import_exotic(kmers, counts)
+            if shape["k"]:
+                c.load_tsv(tsv_list[name])
         if transposed:
             native.write_merged_tsv_T(ctxs, names, out_file)
         else:
