@@ -278,6 +278,52 @@ int mk_load_tsv_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_by
  * its k, keys outside the alphabet are kept as text.  Errors: mk_last_error(NULL). */
 int mk_tsv_shape(const char* path, int* k, int* header, int* alphabet_hint, char* column, size_t column_cap);
 
+/* ---- keys in, counts out: how often does this k-mer, or this panel of marker k-mers, occur in the sample whose table
+ *      the context holds (what Jellyfish calls `query`), answered on the GPU without exporting the table (ABI 6.1) ----
+ * counts[i] is the count of key i in the running table, 0 when the table lacks it, in the order asked; a key asked
+ * twice is answered twice.
+ * The table is only READ: mk_export_size, the export and every later call give what they gave before the lookup.  The
+ * call first makes the table final as mk_export_size does (pending row totals folded, read-backs landed) and drains
+ * the context's stream; the caller must not count into the table meanwhile.  A sharer (mk_share_table) looks in its
+ * OWN table.  A context that holds part of a refused chunk answers MK_ERR_STATE.
+ * Where a key is probed is decided by the key alone, exactly as counting and mk_load_tsv place it: a key inside the
+ * context's alphabet in the packed table (dense bins by index; the one-word table, with the 32 x 'T' key kept beside
+ * it; the two-word tables of nucleotide 33..64-mers and protein 13..25-mers), any other key -- and every key of an
+ * MK_ALPHABET_RAW context, or of one whose k is beyond the packed tables -- in the by-reference table.  An
+ * in-alphabet key is never searched among the rows kept as text.
+ * Key bytes may be any ASCII byte (in the text form: any but '\n'; a '\t' too); a byte >= 0x80 is MK_ERR_NON_ASCII.
+ * MK_LOOKUP_FOLD: an ACGT-only key is looked up under min(key, reverse complement), the key a canonical context
+ * (mk_set_canonical) files it under; keys holding other bytes are never folded.  Only for a canonical nucleotide context
+ * with k <= 64, MK_ERR_ARG anywhere else.  Without the flag keys are taken as they stand, as mk_load_tsv takes them.
+ * mk_lookup: rows * k key bytes in host memory; mk_lookup_device: keys and counts in DEVICE memory of the context's GPU.
+ * mk_lookup_text / mk_lookup_file: a panel in text form (a plain file, not .gz).  Lines end in '\n' (the last may lack
+ * it).  A row is exactly k key bytes, then the end of the line or '\t' and 1..20 decimal digits that fit 64 bits, which
+ * are ignored: a counts TSV, or a Jellyfish / KMC dump, is a panel as it stands.  Line 1 is a header iff it is neither
+ * form; it is skipped (st->header).  Anything else malformed -- a key of another length, '\r', an empty line, bytes
+ * behind the key that are not a tab and digits -- is MK_ERR_RANGE, mk_last_error names the 1-based line.  counts[i]
+ * belongs to data row i (the header not counted), *rows = data rows.  With cap too small: MK_ERR_RANGE, the needed size
+ * in *rows, nothing written past cap.  The text travels in pieces of piece_bytes through a pinned double buffer, with
+ * the defaults and limits of mk_load_tsv: memory is bounded whatever the panel's size. */
+#define MK_LOOKUP_FOLD 1u   /* look an ACGT-only key up under min(key, reverse complement) */
+typedef struct mk_lookup_t {
+  uint64_t bytes, lines;     /* text consumed / lines seen (0 for the non-text calls)            */
+  uint64_t keys;             /* keys looked up                                                    */
+  uint64_t found;            /* ... with a count above zero                                       */
+  uint64_t packed_keys;      /* ... that were probed in the packed table / dense bins             */
+  uint64_t text_keys;        /* ... probed in the by-reference table (a byte outside the alphabet) */
+  uint64_t folded;           /* keys replaced by their reverse complement (MK_LOOKUP_FOLD)        */
+  int32_t header, pieces;
+  /* seconds: host time moving the keys towards the device (the text form: filling the pinned halves); HIP-event time of
+   * the kernels; wall time of the call */
+  double s_read, s_probe, s_total;
+} mk_lookup_t;
+int mk_lookup(mk_ctx* ctx, const uint8_t* kmers, size_t rows, unsigned flags, uint64_t* counts, mk_lookup_t* st);
+int mk_lookup_device(mk_ctx* ctx, const uint8_t* d_kmers, size_t rows, unsigned flags, uint64_t* d_counts, mk_lookup_t* st);
+int mk_lookup_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, uint64_t* counts,
+                   size_t cap, size_t* rows, mk_lookup_t* st);
+int mk_lookup_file(mk_ctx* ctx, const char* path, size_t piece_bytes, unsigned flags, uint64_t* counts, size_t cap,
+                   size_t* rows, mk_lookup_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

@@ -15,7 +15,8 @@ more than three samples of a type, pca_<type>/pca.tsv is computed from the table
 reports are written from the tables on the GPU too (mercat2_amd/diversity.py): the 21 beta-diversity matrices per
 sample type (report/diversity/<metric>-Nucleotide.tsv, report/beta_diversity/<metric>-protein.tsv; no heatmaps;
 skipped beyond 4096 samples), each sample's alpha metrics (report/diversity/<type>-<sample>.tsv) and, with two or
-more samples, report/diversity-<type>.tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
+more samples, report/diversity-<type>.tsv.  -query FILE writes query_<type>.tsv: the count of every k-mer of a panel in every
+sample, looked up in those tables (mk_lookup_file).  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -32,7 +33,7 @@ from . import __version__
 from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_background, removeN_text
 from .kmers import read_fasta_bytes
 from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_text
-from .report import merge_counters, merge_counters_T
+from .report import merge_counters, merge_counters_T, write_query_tsv
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
 
@@ -48,6 +49,11 @@ def parseargs(argv=None):
                    help="earlier output folder(s), or tsv_nucleotide / tsv_protein folders themselves: every <sample>_counts.tsv "
                         "in them is a sample whose table is loaded as it is, not counted again (-c does not apply to it); "
                         "-k must be the tables' k-mer length")
+    p.add_argument("-query", type=str, required=False, metavar="FILE",
+                   help="a panel of k-mers, one a line (a '\\t<count>' behind a key is ignored: a counts TSV or a Jellyfish / KMC "
+                        "dump is a panel): for every sample type, query_<type>.tsv with the count of every panel k-mer in "
+                        "every sample, looked up in the tables on the GPU; with -canonical a k-mer is looked up under "
+                        "min(k-mer, reverse complement)")
     p.add_argument("-k", type=int, required=True, help="kmer length")
     p.add_argument("-n", type=int, default=os.cpu_count() or 1,
                    help="no of cores [auto detect]: samples read (inflated) and counted concurrently, at most 8")
@@ -89,6 +95,8 @@ def parseargs(argv=None):
             p.error(f"file '{filename}' is not valid.\n")
     if args.f and not os.path.isdir(args.f):
         p.error(f"folder {args.f} is not valid.\n")
+    if args.query and not os.path.isfile(args.query):
+        p.error(f"file '{args.query}' is not valid.\n")
     args.loaded = {"nucleotide": {}, "protein": {}}  # sample -> its count table, per type (-tsv)
     for d in args.tsv:
         if not os.path.isdir(d):
@@ -241,6 +249,12 @@ def main(argv=None) -> int:
         devices = list(range(want))
     print(f"\nStarting mercat2_amd v{__version__} with k-mer {args.k} on GPU{'s' if len(devices) > 1 else ''} "
           f"{','.join(str(d) for d in devices)}\n")
+    if args.query:  # a malformed panel ends the run here, not after the counting: looked up once in an empty table
+        try:
+            with native.Counter(args.k, native.ALPHABET_NT2, device=devices[0]) as empty:
+                empty.lookup_text(args.query)
+        except native.MercatHipError as e:
+            raise SystemExit(f"-query {args.query}: {e}")
     files = [Path(f) for f in args.i]
     if args.f:
         folder = Path(os.path.abspath(os.path.expanduser(args.f)))
@@ -412,6 +426,13 @@ def main(argv=None) -> int:
                     from .pca import cli_pca
                     cli_pca(tables, out, "Nucleotide" if kind == "nucleotide" else "protein")
                 write_diversity(tables, out, kind)
+                if args.query:  # from the tables still on the GPU
+                    try:
+                        n = write_query_tsv(tables, args.query, out / ("query_" + stem[len("combined_"):] + ".tsv"),
+                                            fold=args.canonical and kind == "nucleotide")
+                    except native.MercatHipError as e:
+                        raise SystemExit(f"-query {args.query}: {e}")
+                    print(f"query_{stem[len('combined_'):]}.tsv: {n} panel k-mers in {len(tables)} sample(s)")
         finally:
             for t in tables.values():
                 t.close()

@@ -88,7 +88,7 @@ static void prof_collect(mk_ctx* c) {
 // ----------------------------------------------------------------------------- lifetime
 // "mercat_hip <abi>.<minor> (gfx950)": the ABI number changes whenever a struct or a signature of include/mercat_hip.h does
 // (native.py checks it against its own MK_ABI before it trusts the struct layouts)
-extern "C" const char* mk_version(void) { return "mercat_hip 6.0 (gfx950)"; }
+extern "C" const char* mk_version(void) { return "mercat_hip 6.1 (gfx950)"; }
 
 extern "C" int mk_device_count(void) {
   int n = 0;

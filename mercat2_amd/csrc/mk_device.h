@@ -71,3 +71,20 @@ __device__ __forceinline__ u64 mk_canon2(u64 key, int k, bool canonical) {
   const u64 rc = mk_revcomp2(key, k);
   return rc < key ? rc : key;
 }
+
+// min(key, reverse complement) of a two-word key: k bases left-aligned in {hi, lo}.  Returns whether the reverse
+// complement was the smaller one and took the key's place.
+__device__ __forceinline__ u64 mk_revpairs(u64 x) {  // the 32 two-bit groups of x in reverse order
+  const u64 y = __brevll(x);
+  return ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
+}
+__device__ __forceinline__ bool mk_canon128(u64& hi, u64& lo, int k) {
+  // complement, reverse all 64 groups (the 64 - k padding groups, now 'T', come first), shift the k bases back up
+  const u64 a = mk_revpairs(~lo), b = mk_revpairs(~hi);
+  const int s = 128 - 2 * k;  // 0 .. 62
+  const u64 nh = s ? ((a << s) | (b >> (64 - s))) : a;
+  const u64 nl = b << s;
+  const bool smaller = nh < hi || (nh == hi && nl < lo);
+  if (smaller) { hi = nh; lo = nl; }
+  return smaller;
+}

@@ -120,20 +120,6 @@ __device__ __forceinline__ void sk2c_walk(const Sk2CRuns& r, F&& emit) {
   }
 }
 
-// min(key, reverse complement) of a two-word key: k bases left-aligned in {hi, lo}.
-__device__ __forceinline__ u64 sk2_revpairs(u64 x) {  // the 32 two-bit groups of x in reverse order
-  const u64 y = __brevll(x);
-  return ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
-}
-__device__ __forceinline__ void sk2_canon128(u64& hi, u64& lo, int k) {
-  // complement, reverse all 64 groups (the 64 - k padding groups, now 'T', come first), shift the k bases back up
-  const u64 a = sk2_revpairs(~lo), b = sk2_revpairs(~hi);
-  const int s = 128 - 2 * k;  // 0 .. 62
-  const u64 nh = s ? ((a << s) | (b >> (64 - s))) : a;
-  const u64 nl = b << s;
-  if (nh < hi || (nh == hi && nl < lo)) { hi = nh; lo = nl; }
-}
-
 // Windows j = 0..31 whose k (<= 64) bases are clean; p0 is a multiple of 32.
 __device__ __forceinline__ unsigned sk2_valid32(const u64* __restrict__ bad, size_t p0, int k) {
   const size_t bi = p0 >> 6;
@@ -490,7 +476,7 @@ __device__ __forceinline__ void sk2_for_each_key(const Sk2Rec& rec, u64 lomask, 
 #pragma unroll
   for (int u = 0; u < SK2_NKMAX; ++u) {
     u64 hi = x0, lo = x1 & lomask;
-    if constexpr (CANON) sk2_canon128(hi, lo, k);
+    if constexpr (CANON) mk_canon128(hi, lo, k);
     x0 = (x0 << 2) | (x1 >> 62);
     x1 = (x1 << 2) | (x2 >> 62);
     x2 <<= 2;

@@ -9,9 +9,6 @@
 #include "mk_tableview.h"
 #include <type_traits>
 
-#define REF_POS_BITS 40
-#define REF_POS_MASK ((1ull << REF_POS_BITS) - 1)
-
 // Every kernel of this file is launched like this: 256 threads a workgroup, on the context's stream.
 template <class... A>
 static int launch(mk_ctx* c, void (*kernel)(A...), unsigned grid, std::common_type_t<A>... args) {
@@ -54,7 +51,7 @@ int mk_launch_count_survivors(mk_ctx* c, uint64_t min_count) {
 
 // ------------------------------------------------------------------- running table: hash64
 // A key's probe sequence starts at a mixing hash of the key (mask = slots - 1, a power of two).
-// Returns true when the key was new to the table.
+// Returns true when the key was new to the table.  (Its read-only counterpart: find64, mk_tableview.h.)
 __device__ __forceinline__ bool upsert64(MkSlot* __restrict__ table, u64 mask, u64 key, u64 add) {
   u64 slot = mk_mix64(key) & mask;
   for (;;) {
@@ -104,8 +101,8 @@ __device__ __forceinline__ bool upsert64_distinct(MkSlot* __restrict__ table, u6
 // ------------------------------------------------------------- running table: two-word keys
 // Insert-add of one {hi, lo} key (protocol: MkSlot128 in mk_common.h).  A lane that claims a slot writes the
 // key words and publishes the count inside the loop iteration in which it won, so lanes of the same wave that
-// meet MK_LOCK128 and look again cannot starve it.  Returns true when the key was new.
-__device__ __forceinline__ u64 home128(u64 hi, u64 lo, u64 mask) { return mk_mix64(hi ^ mk_mix64(lo + MK_POLY_B)) & mask; }
+// meet MK_LOCK128 and look again cannot starve it.  Returns true when the key was new.  (home128 and the read-only
+// counterpart, find128: mk_tableview.h.)
 
 // Ordering without cache maintenance: every access to a slot's words is an agent-scope atomic (sc1: performed at the
 // device's point of coherence, per-location coherent across the XCDs' L2s by themselves).  The claimer's two key stores
@@ -317,11 +314,8 @@ __device__ __forceinline__ unsigned ld_u8_agent(const uint8_t* p) {
 }
 
 // The k-mer text comes through an accessor get(i) -> byte i, so the same code serves text held in
-// memory (chunk stream, staging buffer) and text decoded on the fly from packed keys.
-struct BytesAt {
-  const uint8_t* p;
-  __device__ __forceinline__ unsigned operator()(int i) const { return p[i]; }
-};
+// memory (chunk stream, staging buffer: BytesAt, mk_tableview.h) and text decoded on the fly from packed keys.
+// (poly_hash_of and the read-only counterpart of upsert_ref_of, find_ref: mk_tableview.h.)
 struct Key128Text {  // 2-bit packed, left-aligned {hi, lo}: base i of the k-mer
   u64 hi, lo;
   __device__ __forceinline__ unsigned operator()(int i) const {
@@ -329,13 +323,6 @@ struct Key128Text {  // 2-bit packed, left-aligned {hi, lo}: base i of the k-mer
     return (unsigned)"ACGT"[code];
   }
 };
-
-template <class Get>
-__device__ __forceinline__ u64 poly_hash_of(const Get& get, int k) {
-  u64 h = 0;
-  for (int i = 0; i < k; ++i) h = h * MK_POLY_B + get(i);
-  return mk_mix64(h);
-}
 
 __device__ __forceinline__ u64 poly_hash(const uint8_t* __restrict__ s, int k) { return poly_hash_of(BytesAt{s}, k); }
 

@@ -80,3 +80,75 @@ struct Rows128 {
     return c != 0;
   }
 };
+
+// ---- where a key's probe sequence starts, per table (the upserts of mk_table.hip and the probes below) ----------
+// one-word keys: mk_mix64(key) & mask.  Two-word keys:
+__device__ __forceinline__ u64 home128(u64 hi, u64 lo, u64 mask) { return mk_mix64(hi ^ mk_mix64(lo + MK_POLY_B)) & mask; }
+// By reference: running slot key = (tag << 40) | arena row, home and tag from the polynomial hash of the k bytes,
+// which come through an accessor get(i) -> byte i.
+#define REF_POS_BITS 40
+#define REF_POS_MASK ((1ull << REF_POS_BITS) - 1)
+struct BytesAt {
+  const uint8_t* p;
+  __device__ __forceinline__ unsigned operator()(int i) const { return p[i]; }
+};
+template <class Get>
+__device__ __forceinline__ u64 poly_hash_of(const Get& get, int k) {
+  u64 h = 0;
+  for (int i = 0; i < k; ++i) h = h * MK_POLY_B + get(i);
+  return mk_mix64(h);
+}
+
+// ---- read-only probes of a QUIESCENT running table: the home slot and probe order of the upserts, loads only, ending
+// at the key (its count) or at a free slot (0).  Nothing writes the table meanwhile, so plain loads will do.
+// One-word table: the slot is one 16-byte load.  `first` is the home slot, already loaded (find64_home: so that a lane
+// can have the loads of several keys in flight before it compares any).
+__device__ __forceinline__ ulonglong2 find64_home(const MkSlot* __restrict__ t, u64 mask, u64 key) {
+  return reinterpret_cast<const ulonglong2*>(t)[mk_mix64(key) & mask];
+}
+__device__ __forceinline__ u64 find64_from(const MkSlot* __restrict__ t, u64 mask, u64 key, ulonglong2 first) {
+  u64 slot = mk_mix64(key) & mask;
+  ulonglong2 s = first;
+  for (;;) {  // (the table is never full: a free slot is met)
+    if (s.x == key) return s.y;
+    if (s.x == MK_EMPTY) return 0;
+    slot = (slot + 1) & mask;
+    s = reinterpret_cast<const ulonglong2*>(t)[slot];
+  }
+}
+__device__ __forceinline__ u64 find64(const MkSlot* __restrict__ t, u64 mask, u64 key) {
+  return find64_from(t, mask, key, find64_home(t, mask, key));
+}
+// Two-word table: the count word is the slot's state, 0 = free.  MK_LOCK128 cannot be met on a quiescent table:
+// *locked is set and the probe ends (a state error for the caller, not a spin).
+__device__ __forceinline__ u64 find128(const MkSlot128* __restrict__ t, u64 mask, u64 hi, u64 lo, bool* locked) {
+  u64 slot = home128(hi, lo, mask);
+  for (;;) {
+    const ulonglong4 s = reinterpret_cast<const ulonglong4*>(t)[slot];
+    if (s.z == 0) return 0;
+    if (s.z == MK_LOCK128) { *locked = true; return 0; }
+    if (s.x == hi && s.y == lo) return s.z;
+    slot = (slot + 1) & mask;
+  }
+}
+// By-reference table: the tag first, the arena bytes only on a tag match.
+template <class Get>
+__device__ __forceinline__ u64 find_ref_of(const MkSlot* __restrict__ run, u64 mask, const uint8_t* __restrict__ arena,
+                                           const Get& get, int k) {
+  const u64 h = poly_hash_of(get, k);
+  const u64 tag = (h >> 41) << REF_POS_BITS;
+  u64 slot = h & mask;
+  for (;;) {
+    const ulonglong2 s = reinterpret_cast<const ulonglong2*>(run)[slot];
+    if (s.x == MK_EMPTY) return 0;
+    if ((s.x & ~REF_POS_MASK) == tag) {
+      const uint8_t* other = arena + (s.x & REF_POS_MASK) * (u64)k;
+      bool same = true;
+      for (int i = 0; i < k && same; ++i) same = other[i] == get(i);
+      if (same) return s.y;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+// Dense bins: one indexed load.
+__device__ __forceinline__ u64 find_dense(const u64* __restrict__ bins, size_t nbins, u64 bin) { return bin < nbins ? bins[bin] : 0; }

@@ -11,8 +11,7 @@
 //   3. once the host has seen that the WHOLE piece is well formed: mk_launch_import_pairs / mk_launch_import_ref.
 // The host reads (or copies) piece p+1 into the other half of a pinned double buffer and a second stream copies it to
 // the device while the kernels of piece p run.
-#include "mk_common.h"
-#include "mk_device.h"
+#include "mk_tsvpieces.h"
 #include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cerrno>
@@ -21,21 +20,6 @@
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
-
-#define TL_TILE 4096u           // bytes per workgroup of the line-start passes: 256 lanes x 16 bytes
-#define TL_NONE 0xFFFFFFFFu
-#define TL_MAX_PIECE ((size_t)1 << 30)  // positions inside a piece are 32-bit
-#define TL_DEFAULT_PIECE ((size_t)16 << 20)
-
-// what the kernels of one piece tell the host (device memory, copied back once per piece)
-struct TlStatus {
-  u64 bad_line;  // smallest index of a malformed line in the piece (all ones: none)
-  u64 bad_byte;  // smallest offset of a byte >= 0x80 (all ones: none)
-  u64 lines, packed, text, zero;
-  u64 pad[2];
-};
-
-enum TlKeys { TL_ONE_WORD = 0, TL_TWO_WORD_NT = 1, TL_TWO_WORD_AA = 2, TL_TEXT_ONLY = 3 };
 
 // ---------------------------------------------------------------------------------------- line starts
 // The 16 bytes of this lane (zero beyond the end of the text: neither a newline nor >= 0x80).
@@ -126,27 +110,10 @@ __global__ void __launch_bounds__(256) tl_parse_k(const uint8_t* __restrict__ te
       s = line_start[i];
       const unsigned len = line_start[i + 1] - 1 - s;  // without the '\n'
       bool ok = len >= (unsigned)k + 2 && len <= (unsigned)k + 21 && text[s + k] == '\t';
-      bool in_alphabet = KEYS != TL_TEXT_ONLY;
+      bool in_alphabet = false;
       if (ok) {
-        unsigned __int128 wide = 0;
-        for (int j = 0; j < k; ++j) {
-          const unsigned ch = text[s + j];
-          unsigned code;
-          if (KEYS == TL_TEXT_ONLY) continue;
-          if (bits == 2) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 99u;
-          else code = (ch >= 'A' && ch <= 'Z') ? ch - 'A' : 99u;
-          if (code == 99u) { in_alphabet = false; continue; }
-          if (KEYS == TL_ONE_WORD) a = (a << bits) | code;
-          else if (KEYS == TL_TWO_WORD_AA) wide = (wide << 5) | code;
-          else if (j < 32) a |= (u64)code << (62 - 2 * j);
-          else b |= (u64)code << (62 - 2 * (j - 32));
-        }
-        if (KEYS == TL_TWO_WORD_AA) { a = (u64)(wide >> 64); b = (u64)wide; }
-        for (unsigned j = (unsigned)k + 1; j < len && ok; ++j) {
-          const unsigned d = (unsigned)text[s + j] - '0';
-          if (d > 9u || cnt > (~0ull - d) / 10ull) ok = false;
-          else cnt = cnt * 10ull + d;
-        }
+        in_alphabet = tl_pack_key<KEYS>(text + s, k, bits, a, b);
+        ok = tl_count_field(text + s + k + 1, len - (unsigned)k - 1, cnt);
       }
       if (!ok) atomicMin(&st->bad_line, (u64)i);  // (rare: the file is refused)
       else if (cnt == 0) ++zeros;
@@ -208,13 +175,14 @@ static double tl_since(TlClk::time_point t0) { return std::chrono::duration<doub
 
 // Is [p, p + n) (a line without its '\n') a data row?  k >= 0: of exactly k key bytes; k < 0: with a key of any length
 // >= 1 that ends at the line's LAST tab (a key may hold tabs, a count cannot; *key_len receives the length).
-// why: what is wrong with it, for the message.
-static bool tl_row_ok(const uint8_t* p, size_t n, long k, size_t* key_len, const char** why) {
+// count_optional (k >= 0): the k key bytes alone are a row too.  why: what is wrong with it, for the message.
+static bool tl_row_ok(const uint8_t* p, size_t n, long k, size_t* key_len, const char** why, bool count_optional = false) {
   const char* dummy;
   if (!why) why = &dummy;
   if (!n) { *why = "empty line"; return false; }
+  if (count_optional && k >= 0 && n == (size_t)k) return true;
   const uint8_t* tab = (const uint8_t*)memrchr(p, '\t', n);
-  if (!tab) { *why = "no tab"; return false; }
+  if (!tab) { *why = count_optional ? "the key is not k bytes long" : "no tab"; return false; }
   const size_t kl = k >= 0 ? (size_t)k : (size_t)(tab - p);
   if (key_len) *key_len = kl;
   if (kl < 1 || n < kl + 1 || p[kl] != '\t') { *why = "the key is not k bytes long"; return false; }
@@ -242,243 +210,268 @@ static std::string tl_second_field(const uint8_t* p, size_t n) {
   return std::string((const char*)from, (size_t)((end ? end : p + n) - from));
 }
 
-struct TlSource {  // a file, or text in host memory
-  int fd = -1;
-  const uint8_t* mem = nullptr;
-  size_t n = 0, at = 0;
-  // up to `want` bytes into dst; less only at the end; -1: read error
-  ssize_t read(uint8_t* dst, size_t want) {
-    if (fd < 0) {
-      const size_t m = std::min(want, n - at);
-      if (m) memcpy(dst, mem + at, m);
-      at += m;
-      return (ssize_t)m;
-    }
-    size_t got = 0;
-    while (got < want) {
-      const ssize_t r = ::read(fd, dst + got, want - got);
-      if (r < 0) return -1;
-      if (r == 0) break;
-      got += (size_t)r;
-    }
-    return (ssize_t)got;
+ssize_t TlSource::read(uint8_t* dst, size_t want) {
+  if (fd < 0) {
+    const size_t m = std::min(want, n - at);
+    if (m) memcpy(dst, mem + at, m);
+    at += m;
+    return (ssize_t)m;
   }
-};
+  size_t got = 0;
+  while (got < want) {
+    const ssize_t r = ::read(fd, dst + got, want - got);
+    if (r < 0) return -1;
+    if (r == 0) break;
+    got += (size_t)r;
+  }
+  return (ssize_t)got;
+}
 
-struct TlSnap {  // pinned: the read-back of one piece
-  TlStatus st;
-  MkChunkInfo info;  // the context's counters after the imports of the pieces before
-};
+int tl_open(mk_ctx* c, const char* what, const char* path, TlSource* src, size_t* hint) {
+  src->fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  if (src->fd < 0) { c->err = std::string(what) + ": " + path + ": " + strerror(errno); return MK_ERR_IO; }
+  struct stat sb;
+  *hint = (fstat(src->fd, &sb) == 0 && sb.st_size > 0) ? (size_t)sb.st_size : 0;
+  return MK_OK;
+}
 
-struct TlLoad {
-  mk_ctx* c;
-  TlSource src;
+// ---- the pieces of a text (mk_tsvpieces.h)
+TlPieces::~TlPieces() {
+  (void)hipSetDevice(c->device);
+  if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+  (void)hipStreamSynchronize(c->stream);
+  for (auto e : ev_copy) if (e) (void)hipEventDestroy(e);
+  for (auto e : ev) if (e) (void)hipEventDestroy(e);
+  if (pinned) (void)hipHostFree(pinned);
+  MkDevBuf* all[] = {&dtext[0], &dtext[1], &tiles, &lines, &scan_tmp, &status};
+  for (auto* b : all) buf_free(*b);
+  for (auto& b : held) buf_free(b);
+  if (src.fd >= 0) ::close(src.fd);
+}
+
+int TlPieces::fail(int code, const std::string& msg) {
+  c->err = std::string(what) + ": " + msg;
+  return code;
+}
+
+int TlPieces::setup(size_t piece_bytes, size_t total_hint) {
+  const size_t k = (size_t)c->k;
+  piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(total_hint + 2, 4096));
+  piece = std::min(std::max(piece, 2 * (k + 24)), TL_MAX_PIECE);
+  if (2 * (k + 24) > TL_MAX_PIECE) return fail(MK_ERR_ARG, "k is too large for a table in text form");
+  cap_rows = (piece + 64) / min_row() + 2;  // (a last line without its '\n' gets one: a piece may be one byte longer)
+  MK_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+  for (auto& e : ev_copy) MK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : ev) MK_HIP(hipEventCreate(&e));
+  const size_t half = (piece + 64 + 255) & ~(size_t)255;
+  MK_HIP(hipHostMalloc((void**)&pinned, 2 * half + sizeof(TlSnap), hipHostMallocDefault));
+  hbuf[0] = pinned;
+  hbuf[1] = pinned + half;
+  snap = (TlSnap*)(pinned + 2 * half);
+  max_tiles = div_up(piece + 64, TL_TILE) + 1;
+  int rc;
+  for (auto& d : dtext)
+    if ((rc = mk_buf_reserve(c, d, half)) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, tiles, 2 * max_tiles * sizeof(unsigned))) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, lines, (cap_rows + 1) * sizeof(unsigned))) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, status, sizeof(TlStatus))) != MK_OK) return rc;
+  if ((rc = reserve()) != MK_OK) return rc;
+  MK_HIP(rocprim::exclusive_scan((void*)nullptr, scan_tmp_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, 0u, max_tiles,
+                                 rocprim::plus<unsigned>(), c->stream));
+  return mk_buf_reserve(c, scan_tmp, scan_tmp_bytes ? scan_tmp_bytes : 16);
+}
+
+// Read the next piece into half b: the carried bytes, then the source up to the piece size; cut at the last '\n'.
+// On piece 0 the header line (line 1, if it is not a data row) is taken off.  Returns > 0 when there was nothing left.
+int TlPieces::fill(int b) {
+  const auto t0 = TlClk::now();
+  if (copy_used[b]) MK_HIP(hipEventSynchronize(ev_copy[b]));  // (the copy that last read this half)
+  uint8_t* h = hbuf[b];
+  size_t have = carry.size();
+  if (have) memcpy(h, carry.data(), have);
+  carry.clear();
+  if (!eof) {
+    const ssize_t got = src.read(h + have, piece - have);
+    if (got < 0) return fail(MK_ERR_IO, std::string("read: ") + strerror(errno));
+    eof = (size_t)got < piece - have;
+    have += (size_t)got;
+    bytes += (u64)got;
+  }
+  s_read += tl_since(t0);
+  if (!have) return 1;
+  size_t plen;
+  if (eof) {
+    if (h[have - 1] != '\n') h[have++] = '\n';  // (the last line may lack it; the buffer has the room)
+    plen = have;
+  } else {
+    size_t cut = have;
+    while (cut && h[cut - 1] != '\n') --cut;  // (a row is short: a few bytes are looked at)
+    if (!cut || have - cut > (size_t)c->k + 22) {  // (the lines of the piece in flight are not counted yet: run() names the line)
+      long_line_at = (u64)std::count(h, h + cut, (uint8_t)'\n');
+      return 2;
+    }
+    carry.assign(h + cut, h + have);
+    plen = cut;
+  }
+  skip[b] = 0;
+  if (pieces == 0) {
+    const uint8_t* nl = (const uint8_t*)memchr(h, '\n', plen);
+    const size_t l1 = (size_t)(nl - h);
+    if (!tl_row_ok(h, l1, c->k, nullptr, nullptr, count_optional)) {
+      header = 1;
+      column = tl_second_field(h, l1);
+      skip[b] = l1 + 1;
+      lines_seen = 1;
+    }
+  }
+  len[b] = plen - skip[b];
+  ++pieces;
+  return MK_OK;
+}
+
+int TlPieces::enqueue_copy(int b) {
+  if (!len[b]) return MK_OK;
+  MK_HIP(hipMemcpyAsync(dtext[b].p, hbuf[b] + skip[b], len[b], hipMemcpyHostToDevice, copy_stream));
+  MK_HIP(hipEventRecord(ev_copy[b], copy_stream));
+  copy_used[b] = true;
+  return MK_OK;
+}
+
+int TlPieces::enqueue_parse(int b) {
+  const size_t n = len[b];
+  TlStatus* st = (TlStatus*)status.p;
+  MK_HIP(hipMemsetAsync(st, 0xFF, 16, c->stream));
+  MK_HIP(hipMemsetAsync((char*)st + 16, 0, sizeof(TlStatus) - 16, c->stream));
+  if (n) {
+    const unsigned ntiles = (unsigned)div_up(n, TL_TILE);
+    const unsigned cap = (unsigned)(n / min_row() + 1);  // <= cap_rows
+    unsigned* tile_nl = (unsigned*)tiles.p;
+    unsigned* tile_off = tile_nl + max_tiles;
+    const uint8_t* text = (const uint8_t*)dtext[b].p;
+    MK_HIP(hipStreamWaitEvent(c->stream, ev_copy[b], 0));
+    MK_HIP(hipEventRecord(ev[0], c->stream));
+    MK_HIP(hipMemsetAsync(tile_nl + ntiles, 0, sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(tl_count_k, dim3(ntiles), dim3(256), 0, c->stream, text, n, tile_nl, st);
+    MK_HIP(rocprim::exclusive_scan(scan_tmp.p, scan_tmp_bytes, (const unsigned*)tile_nl, tile_off, 0u, (size_t)ntiles + 1,
+                                   rocprim::plus<unsigned>(), c->stream));
+    hipLaunchKernelGGL(tl_emit_k, dim3(ntiles), dim3(256), 0, c->stream, text, n, (const unsigned*)tile_off, ntiles,
+                       (unsigned*)lines.p, cap, st);
+    const int rc = enqueue_rows(b, text, (const unsigned*)lines.p, cap, st);
+    if (rc != MK_OK) return rc;
+    MK_HIP(hipGetLastError());
+    MK_HIP(hipEventRecord(ev[1], c->stream));
+  }
+  MK_HIP(hipMemcpyAsync(&snap->st, st, sizeof(TlStatus), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&snap->info, c->info.p, sizeof(MkChunkInfo), hipMemcpyDeviceToHost, c->stream));
+  return MK_OK;
+}
+
+// 1-based number, in the whole text, of line `index` of the piece in half b, and the line itself
+void TlPieces::locate(int b, u64 index, const uint8_t** p, size_t* n) const {
+  const uint8_t* at = hbuf[b] + skip[b];
+  const uint8_t* end = at + len[b];
+  for (u64 i = 0; i < index && at < end; ++i) at = (const uint8_t*)memchr(at, '\n', (size_t)(end - at)) + 1;
+  const uint8_t* nl = at < end ? (const uint8_t*)memchr(at, '\n', (size_t)(end - at)) : nullptr;
+  *p = at;
+  *n = nl ? (size_t)(nl - at) : 0;
+}
+
+void TlPieces::add_elapsed(double& to, hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, a, b) == hipSuccess) to += ms * 1e-3;
+}
+
+// Wait for the piece in half b, refuse it or hand its rows on.
+int TlPieces::finish(int b) {
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if (len[b]) add_elapsed(s_parse, ev[0], ev[1]);
+  const TlStatus st = snap->st;
+  const MkChunkInfo before = snap->info;
+  const u64 none = ~0ull;
+  u64 ascii_line = none;
+  if (st.bad_byte != none)
+    ascii_line = (u64)std::count(hbuf[b] + skip[b], hbuf[b] + skip[b] + st.bad_byte, (uint8_t)'\n');
+  if (ascii_line != none && ascii_line <= st.bad_line)
+    return fail(MK_ERR_NON_ASCII, "line " + std::to_string(lines_seen + ascii_line + 1) + ": byte >= 0x80 (only ASCII keys are counted)");
+  if (st.bad_line != none) {
+    const uint8_t* p;
+    size_t n;
+    const char* why = "malformed row";
+    locate(b, st.bad_line, &p, &n);
+    (void)tl_row_ok(p, n, c->k, nullptr, &why, count_optional);
+    return fail(MK_ERR_RANGE, "line " + std::to_string(lines_seen + st.bad_line + 1) + ": " + why + " (a row is " +
+                                  std::to_string(c->k) + (count_optional ? " key bytes, then nothing or a tab and a decimal count)"
+                                                                         : " key bytes, a tab, a decimal count)"));
+  }
+  const int rc = accept(b, st, before);
+  if (rc == MK_OK) lines_seen += st.lines;
+  return rc;
+}
+
+int TlPieces::too_long() {
+  return fail(MK_ERR_RANGE, "line " + std::to_string(lines_seen + long_line_at + 1) + ": longer than a data row of this k");
+}
+
+int TlPieces::run() {
+  int rc, cur = 0;
+  if ((rc = fill(0)) < 0) return rc;
+  if (rc == 2) return too_long();
+  if (rc > 0) return MK_OK;  // an empty text: no lines
+  if ((rc = enqueue_copy(0)) != MK_OK || (rc = enqueue_parse(0)) != MK_OK) return rc;
+  for (;;) {
+    const int nxt = cur ^ 1;
+    rc = (eof && carry.empty()) ? 1 : fill(nxt);  // (the host reads while the device parses)
+    if (rc < 0) return rc;
+    if (rc == 2) return (rc = finish(cur)) != MK_OK ? rc : too_long();  // (a refusal in the piece before comes first)
+    const bool more = rc == 0;
+    if (more && (rc = enqueue_copy(nxt)) != MK_OK) return rc;  // ... and the copy runs beside the kernels
+    if ((rc = finish(cur)) != MK_OK) return rc;
+    if (!more) return MK_OK;
+    if ((rc = enqueue_parse(nxt)) != MK_OK) return rc;
+    cur = nxt;
+  }
+}
+
+// ---- the loader: a piece's rows are parsed into lists and, once the whole piece is known to be well formed, imported
+struct TlLoad : TlPieces {
   mk_tsv_load_t out{};
-  std::string column;
-  size_t piece = 0, cap_rows = 0, max_tiles = 0;
   int words = 1, keys = TL_TEXT_ONLY;
-  // resources of the call
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint8_t* pinned = nullptr;
-  uint8_t* hbuf[2] = {nullptr, nullptr};
-  TlSnap* snap = nullptr;
-  MkDevBuf dtext[2], tiles, lines, pk_keys, pk_cnts, tx_keys, tx_cnts, fold, scan_tmp, status;
-  size_t scan_tmp_bytes = 0;
-  // the piece in each half of the double buffer
-  size_t skip[2] = {0, 0}, len[2] = {0, 0};
-  std::vector<uint8_t> carry;  // the unfinished line behind the last '\n' of the piece read before
-  bool eof = false, copy_used[2] = {false, false}, import_timed = false;
+  MkDevBuf &pk_keys = hold(), &pk_cnts = hold(), &tx_keys = hold(), &tx_cnts = hold(), &fold = hold();
+  bool import_timed = false;
   bool imported = false;       // the running table holds rows of this call
-  u64 lines_seen = 0;
-  int pieces = 0;
-  u64 long_line_at = 0;  // fill() == 2: lines of its piece in front of a line longer than any data row
+  TlLoad(mk_ctx* c_, TlSource src_) : TlPieces(c_, src_, "mk_load_tsv", false) {}
 
-  ~TlLoad() {
-    (void)hipSetDevice(c->device);
-    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
-    (void)hipStreamSynchronize(c->stream);
-    for (auto e : ev_copy) if (e) (void)hipEventDestroy(e);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    if (pinned) (void)hipHostFree(pinned);
-    MkDevBuf* all[] = {&dtext[0], &dtext[1], &tiles, &lines, &pk_keys, &pk_cnts, &tx_keys, &tx_cnts, &fold, &scan_tmp, &status};
-    for (auto* b : all) buf_free(*b);
-    if (src.fd >= 0) ::close(src.fd);
-  }
-
-  int fail(int code, const std::string& msg) {
-    c->err = "mk_load_tsv: " + msg;
-    return code;
-  }
-
-  int setup(size_t piece_bytes, size_t total_hint) {
+  int reserve() override {
     const size_t k = (size_t)c->k;
-    piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(total_hint + 2, 4096));
-    piece = std::min(std::max(piece, 2 * (k + 24)), TL_MAX_PIECE);
-    if (2 * (k + 24) > TL_MAX_PIECE) return fail(MK_ERR_ARG, "k is too large for a table in text form");
-    cap_rows = (piece + 64) / (k + 3) + 2;  // (a last line without its '\n' gets one: a piece may be one byte longer)
-    keys = c->mode == MK_MODE_BYREF ? TL_TEXT_ONLY
-           : c->mode != MK_MODE_HASH128 ? TL_ONE_WORD
-           : c->alphabet == MK_ALPHABET_NT2 ? TL_TWO_WORD_NT : TL_TWO_WORD_AA;
+    keys = tl_keys_of(c);
     words = c->mode == MK_MODE_HASH128 ? 2 : 1;
-    MK_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-    for (auto& e : ev_copy) MK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : ev) MK_HIP(hipEventCreate(&e));
-    const size_t half = (piece + 64 + 255) & ~(size_t)255;
-    MK_HIP(hipHostMalloc((void**)&pinned, 2 * half + sizeof(TlSnap), hipHostMallocDefault));
-    hbuf[0] = pinned;
-    hbuf[1] = pinned + half;
-    snap = (TlSnap*)(pinned + 2 * half);
-    max_tiles = div_up(piece + 64, TL_TILE) + 1;
     int rc;
-    for (auto& d : dtext)
-      if ((rc = mk_buf_reserve(c, d, half)) != MK_OK) return rc;
-    if ((rc = mk_buf_reserve(c, tiles, 2 * max_tiles * sizeof(unsigned))) != MK_OK) return rc;
-    if ((rc = mk_buf_reserve(c, lines, (cap_rows + 1) * sizeof(unsigned))) != MK_OK) return rc;
     if (keys != TL_TEXT_ONLY) {
       if ((rc = mk_buf_reserve(c, pk_keys, cap_rows * 8 * (size_t)words)) != MK_OK) return rc;
       if ((rc = mk_buf_reserve(c, pk_cnts, cap_rows * 8)) != MK_OK) return rc;
     }
     if ((rc = mk_buf_reserve(c, tx_keys, cap_rows * k + 64)) != MK_OK) return rc;
-    if ((rc = mk_buf_reserve(c, tx_cnts, cap_rows * 8)) != MK_OK) return rc;
-    if ((rc = mk_buf_reserve(c, status, sizeof(TlStatus))) != MK_OK) return rc;
-    MK_HIP(rocprim::exclusive_scan((void*)nullptr, scan_tmp_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, 0u, max_tiles,
-                                   rocprim::plus<unsigned>(), c->stream));
-    return mk_buf_reserve(c, scan_tmp, scan_tmp_bytes ? scan_tmp_bytes : 16);
+    return mk_buf_reserve(c, tx_cnts, cap_rows * 8);
   }
 
-  // Read the next piece into half b: the carried bytes, then the source up to the piece size; cut at the last '\n'.
-  // On piece 0 the header line (line 1, if it is not a data row) is taken off.  Returns > 0 when there was nothing left.
-  int fill(int b) {
-    const auto t0 = TlClk::now();
-    if (copy_used[b]) MK_HIP(hipEventSynchronize(ev_copy[b]));  // (the copy that last read this half)
-    uint8_t* h = hbuf[b];
-    size_t have = carry.size();
-    if (have) memcpy(h, carry.data(), have);
-    carry.clear();
-    if (!eof) {
-      const ssize_t got = src.read(h + have, piece - have);
-      if (got < 0) return fail(MK_ERR_IO, std::string("read: ") + strerror(errno));
-      eof = (size_t)got < piece - have;
-      have += (size_t)got;
-      out.bytes += (u64)got;
-    }
-    out.s_read += tl_since(t0);
-    if (!have) return 1;
-    size_t plen;
-    if (eof) {
-      if (h[have - 1] != '\n') h[have++] = '\n';  // (the last line may lack it; the buffer has the room)
-      plen = have;
-    } else {
-      size_t cut = have;
-      while (cut && h[cut - 1] != '\n') --cut;  // (a row is short: a few bytes are looked at)
-      if (!cut || have - cut > (size_t)c->k + 22) {  // (the lines of the piece in flight are not counted yet: run() names the line)
-        long_line_at = (u64)std::count(h, h + cut, (uint8_t)'\n');
-        return 2;
-      }
-      carry.assign(h + cut, h + have);
-      plen = cut;
-    }
-    skip[b] = 0;
-    if (pieces == 0) {
-      const uint8_t* nl = (const uint8_t*)memchr(h, '\n', plen);
-      const size_t l1 = (size_t)(nl - h);
-      if (!tl_row_ok(h, l1, c->k, nullptr, nullptr)) {
-        out.header = 1;
-        column = tl_second_field(h, l1);
-        skip[b] = l1 + 1;
-        lines_seen = 1;
-      }
-    }
-    len[b] = plen - skip[b];
-    ++pieces;
-    return MK_OK;
-  }
-
-  int enqueue_copy(int b) {
-    if (!len[b]) return MK_OK;
-    MK_HIP(hipMemcpyAsync(dtext[b].p, hbuf[b] + skip[b], len[b], hipMemcpyHostToDevice, copy_stream));
-    MK_HIP(hipEventRecord(ev_copy[b], copy_stream));
-    copy_used[b] = true;
-    return MK_OK;
-  }
-
-  int enqueue_parse(int b) {
-    const size_t n = len[b];
-    TlStatus* st = (TlStatus*)status.p;
-    MK_HIP(hipMemsetAsync(st, 0xFF, 16, c->stream));
-    MK_HIP(hipMemsetAsync((char*)st + 16, 0, sizeof(TlStatus) - 16, c->stream));
-    if (n) {
-      const unsigned ntiles = (unsigned)div_up(n, TL_TILE);
-      const unsigned cap = (unsigned)(n / ((size_t)c->k + 3) + 1);  // <= cap_rows
-      unsigned* tile_nl = (unsigned*)tiles.p;
-      unsigned* tile_off = tile_nl + max_tiles;
-      const uint8_t* text = (const uint8_t*)dtext[b].p;
-      MK_HIP(hipStreamWaitEvent(c->stream, ev_copy[b], 0));
-      MK_HIP(hipEventRecord(ev[0], c->stream));
-      MK_HIP(hipMemsetAsync(tile_nl + ntiles, 0, sizeof(unsigned), c->stream));
-      hipLaunchKernelGGL(tl_count_k, dim3(ntiles), dim3(256), 0, c->stream, text, n, tile_nl, st);
-      MK_HIP(rocprim::exclusive_scan(scan_tmp.p, scan_tmp_bytes, (const unsigned*)tile_nl, tile_off, 0u, (size_t)ntiles + 1,
-                                     rocprim::plus<unsigned>(), c->stream));
-      hipLaunchKernelGGL(tl_emit_k, dim3(ntiles), dim3(256), 0, c->stream, text, n, (const unsigned*)tile_off, ntiles,
-                         (unsigned*)lines.p, cap, st);
-      const unsigned grid = grid_for(cap, 256, 8192);
-#define TL_PARSE(K) hipLaunchKernelGGL((tl_parse_k<K>), dim3(grid), dim3(256), 0, c->stream, text, (const unsigned*)lines.p, cap, c->k, \
+  int enqueue_rows(int, const uint8_t* text, const unsigned* line_start, unsigned cap, TlStatus* st) override {
+    const unsigned grid = grid_for(cap, 256, 8192);
+#define TL_PARSE(K) hipLaunchKernelGGL((tl_parse_k<K>), dim3(grid), dim3(256), 0, c->stream, text, line_start, cap, c->k, \
                                        c->bits, (u64*)pk_keys.p, (u64*)pk_cnts.p, (uint8_t*)tx_keys.p, (u64*)tx_cnts.p, st)
-      if (keys == TL_ONE_WORD) TL_PARSE(TL_ONE_WORD);
-      else if (keys == TL_TWO_WORD_NT) TL_PARSE(TL_TWO_WORD_NT);
-      else if (keys == TL_TWO_WORD_AA) TL_PARSE(TL_TWO_WORD_AA);
-      else TL_PARSE(TL_TEXT_ONLY);
+    if (keys == TL_ONE_WORD) TL_PARSE(TL_ONE_WORD);
+    else if (keys == TL_TWO_WORD_NT) TL_PARSE(TL_TWO_WORD_NT);
+    else if (keys == TL_TWO_WORD_AA) TL_PARSE(TL_TWO_WORD_AA);
+    else TL_PARSE(TL_TEXT_ONLY);
 #undef TL_PARSE
-      MK_HIP(hipGetLastError());
-      MK_HIP(hipEventRecord(ev[1], c->stream));
-    }
-    MK_HIP(hipMemcpyAsync(&snap->st, st, sizeof(TlStatus), hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipMemcpyAsync(&snap->info, c->info.p, sizeof(MkChunkInfo), hipMemcpyDeviceToHost, c->stream));
     return MK_OK;
   }
 
-  // 1-based number, in the whole text, of line `index` of the piece in half b, and the line itself
-  void locate(int b, u64 index, const uint8_t** p, size_t* n) const {
-    const uint8_t* at = hbuf[b] + skip[b];
-    const uint8_t* end = at + len[b];
-    for (u64 i = 0; i < index && at < end; ++i) at = (const uint8_t*)memchr(at, '\n', (size_t)(end - at)) + 1;
-    const uint8_t* nl = at < end ? (const uint8_t*)memchr(at, '\n', (size_t)(end - at)) : nullptr;
-    *p = at;
-    *n = nl ? (size_t)(nl - at) : 0;
-  }
-
-  void add_elapsed(double& to, hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) to += ms * 1e-3;
-  }
-
-  // Wait for the piece in half b, refuse it or hand its rows to the import kernels.
-  int finish(int b) {
-    MK_HIP(hipStreamSynchronize(c->stream));
+  // Hand the rows of a well formed piece to the import kernels.
+  int accept(int, const TlStatus& st, const MkChunkInfo& before) override {
     if (import_timed) { add_elapsed(out.s_import, ev[2], ev[3]); import_timed = false; }
-    if (len[b]) add_elapsed(out.s_parse, ev[0], ev[1]);
-    const TlStatus st = snap->st;
-    const MkChunkInfo before = snap->info;
-    const u64 none = ~0ull;
-    u64 ascii_line = none;
-    if (st.bad_byte != none)
-      ascii_line = (u64)std::count(hbuf[b] + skip[b], hbuf[b] + skip[b] + st.bad_byte, (uint8_t)'\n');
-    if (ascii_line != none && ascii_line <= st.bad_line)
-      return fail(MK_ERR_NON_ASCII, "line " + std::to_string(lines_seen + ascii_line + 1) + ": byte >= 0x80 (only ASCII keys are counted)");
-    if (st.bad_line != none) {
-      const uint8_t* p;
-      size_t n;
-      const char* why = "malformed row";
-      locate(b, st.bad_line, &p, &n);
-      (void)tl_row_ok(p, n, c->k, nullptr, &why);
-      return fail(MK_ERR_RANGE, "line " + std::to_string(lines_seen + st.bad_line + 1) + ": " + why + " (a row is " +
-                                    std::to_string(c->k) + " key bytes, a tab, a decimal count)");
-    }
     if (st.lines != st.packed + st.text + st.zero)
       return fail(MK_ERR_STATE, "the parse kernels lost rows (" + std::to_string(st.lines) + " lines, " +
                                     std::to_string(st.packed + st.text + st.zero) + " rows)");
-    lines_seen += st.lines;
     out.rows += st.lines;
     out.packed_rows += st.packed;
     out.text_rows += st.text;
@@ -527,29 +520,11 @@ struct TlLoad {
     return MK_OK;
   }
 
-  int too_long() {
-    return fail(MK_ERR_RANGE, "line " + std::to_string(lines_seen + long_line_at + 1) + ": longer than a data row of this k");
-  }
-
-  int run() {
-    int rc, cur = 0;
+  int load(size_t piece_bytes, size_t total_hint) {
+    int rc = setup(piece_bytes, total_hint);
+    if (rc != MK_OK) return rc;
     MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
-    if ((rc = fill(0)) < 0) return rc;
-    if (rc == 2) return too_long();
-    if (rc > 0) return MK_OK;  // an empty text: no lines
-    if ((rc = enqueue_copy(0)) != MK_OK || (rc = enqueue_parse(0)) != MK_OK) return rc;
-    for (;;) {
-      const int nxt = cur ^ 1;
-      rc = (eof && carry.empty()) ? 1 : fill(nxt);  // (the host reads while the device parses)
-      if (rc < 0) return rc;
-      if (rc == 2) return (rc = finish(cur)) != MK_OK ? rc : too_long();  // (a refusal in the piece before comes first)
-      const bool more = rc == 0;
-      if (more && (rc = enqueue_copy(nxt)) != MK_OK) return rc;  // ... and the copy runs beside the kernels
-      if ((rc = finish(cur)) != MK_OK) return rc;
-      if (!more) return MK_OK;
-      if ((rc = enqueue_parse(nxt)) != MK_OK) return rc;
-      cur = nxt;
-    }
+    return run();
   }
 };
 
@@ -563,7 +538,7 @@ static int tl_load(mk_ctx* c, TlSource src, size_t total_hint, size_t piece_byte
   size_t dense_before = 0, dense_after = 0;
   int rc;
   if (c->mode == MK_MODE_DENSE && (rc = mk_export_size(c, &dense_before)) != MK_OK) return rc;
-  if ((rc = L.setup(piece_bytes, total_hint)) == MK_OK) rc = L.run();
+  rc = L.load(piece_bytes, total_hint);
   if (rc == MK_OK && column_cap && L.column.size() + 1 > column_cap && !L.imported)
     rc = L.fail(MK_ERR_RANGE, "the column name needs " + std::to_string(L.column.size() + 1) + " bytes");
   const std::string msg = c->err;
@@ -588,6 +563,10 @@ static int tl_load(mk_ctx* c, TlSource src, size_t total_hint, size_t piece_byte
     memcpy(column, L.column.data(), m);
     column[m] = 0;
   }
+  L.out.bytes = L.bytes;
+  L.out.header = L.header;
+  L.out.s_read = L.s_read;
+  L.out.s_parse = L.s_parse;
   L.out.lines = L.lines_seen;
   L.out.pieces = L.pieces;
   L.out.s_total = tl_since(t0);
@@ -609,10 +588,9 @@ extern "C" int mk_load_tsv(mk_ctx* c, const char* path, size_t piece_bytes, char
   if (!c) return MK_ERR_ARG;
   if (!path) { c->err = "mk_load_tsv: path is NULL"; return MK_ERR_ARG; }
   TlSource src;
-  src.fd = ::open(path, O_RDONLY | O_CLOEXEC);
-  if (src.fd < 0) { c->err = std::string("mk_load_tsv: ") + path + ": " + strerror(errno); return MK_ERR_IO; }
-  struct stat sb;
-  const size_t hint = (fstat(src.fd, &sb) == 0 && sb.st_size > 0) ? (size_t)sb.st_size : 0;
+  size_t hint = 0;
+  const int rc = tl_open(c, "mk_load_tsv", path, &src, &hint);
+  if (rc != MK_OK) return rc;
   return tl_load(c, src, hint, piece_bytes, column, column_cap, st);
 }
 

@@ -92,3 +92,10 @@ def find_kmers(file: Path, kmer: int, min_count: int, *, device: int = 0, alphab
     with native.Counter(kmer, alphabet, device) as ctx:
         native.count_file([ctx], file, 0, min_count)  # the whole file is one chunk
         return ctx.to_dict()
+
+
+def lookup_kmers(table: "native.Counter", kmers) -> Dict[str, int]:
+    """{k-mer: count} of the given k-mers (str, each of the table's k) in a table that is still on the GPU -- 0 for a
+    k-mer it lacks -- without exporting it: what ``find_kmers(...)[kmer]`` answers, for a handful of keys."""
+    kmers = list(kmers)
+    return dict(zip(kmers, table.lookup(kmers).tolist()))

@@ -34,9 +34,11 @@ ABI_SYMBOLS = [
     "mk_device_count", "mk_reset_for", "mk_textwrap", "mk_set_clean", "mk_clean_stats", "mk_clean_runs",
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
+    "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
+LOOKUP_FOLD = 1
 
 
 class MercatHipError(RuntimeError):
@@ -93,6 +95,16 @@ class TsvLoad(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in ("bytes", "lines", "rows", "packed_rows", "text_rows", "zero_rows", "new_rows")] +
                 [("header", C.c_int32), ("pieces", C.c_int32)] +
                 [(n, C.c_double) for n in ("s_read", "s_parse", "s_import", "s_total")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class Lookup(C.Structure):
+    """mk_lookup_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("bytes", "lines", "keys", "found", "packed_keys", "text_keys", "folded")] +
+                [("header", C.c_int32), ("pieces", C.c_int32)] +
+                [(n, C.c_double) for n in ("s_read", "s_probe", "s_total")])
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -219,6 +231,10 @@ def lib() -> C.CDLL:
         "mk_load_tsv": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(TsvLoad)]),
         "mk_load_tsv_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(TsvLoad)]),
         "mk_tsv_shape": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+        "mk_lookup": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, u64p, C.POINTER(Lookup)]),
+        "mk_lookup_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, u64p, C.POINTER(Lookup)]),
+        "mk_lookup_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, u64p, C.c_size_t, szp, C.POINTER(Lookup)]),
+        "mk_lookup_file": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_uint, u64p, C.c_size_t, szp, C.POINTER(Lookup)]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -629,6 +645,16 @@ def pair_stats_matrix(matrix: np.ndarray, device: int = 0) -> dict:
     return _pair_result(out, sums, n, m.shape[0], int(flags[0]))
 
 
+def lookup_multi(ctxs: Sequence["Counter"], keys, fold: Optional[bool] = None) -> np.ndarray:
+    """The counts of ``keys`` in a table spread over ``ctxs`` by key range (after merge_devices with MERGE_RANGES): every
+    key has one owner there, so the answer is the sum of the contexts' lookups."""
+    total = None
+    for c in ctxs:
+        got = c.lookup(keys, fold)
+        total = got if total is None else total + got
+    return total if total is not None else np.zeros(0, dtype=np.uint64)
+
+
 def synth_reads(genome_len: int, genome_seed: int, reads: int, read_len: int, read_seed: int,
                 sub_ppm: int = 0, first_index: int = 0) -> np.ndarray:
     """Deterministic synthetic FASTA reads as a uint8 array."""
@@ -657,6 +683,7 @@ class Counter:
         if rc:
             msg = self._L.mk_last_error(None)
             raise MercatHipError(rc, msg.decode() if msg else "mk_create")
+        self.canonical = False
         if canonical:
             self.set_canonical(True)
 
@@ -688,6 +715,7 @@ class Counter:
     def set_canonical(self, on: bool):
         """Opt-in extension (not reference behaviour): count min(kmer, reverse complement)."""
         self._check(self._L.mk_set_canonical(self._h, 1 if on else 0))
+        self.canonical = bool(on)
 
     def set_clean(self, on: bool, toupper: bool = False):
         """Count RAW nucleotide FASTA as removeN would leave it (mk_set_clean): N runs cut records, text in front of the
@@ -761,6 +789,72 @@ class Counter:
         d = st.as_dict()
         d["column"] = column.value.decode("utf-8", "replace")
         return d
+
+    # -- lookups: keys in, counts out (0 = absent), in the order asked; the table is only read
+    def _fold_flag(self, fold: Optional[bool]) -> int:
+        """fold None: fold iff the context is canonical."""
+        if fold is None:
+            fold = self.canonical
+        return LOOKUP_FOLD if fold else 0
+
+    def _key_rows(self, keys) -> np.ndarray:
+        """(rows, k) uint8 from a list of str / bytes of length k, or a (rows, k) / flat uint8 array."""
+        if isinstance(keys, np.ndarray):
+            if keys.dtype == np.dtype("S%d" % self.k):
+                keys = np.ascontiguousarray(keys).view(np.uint8)
+            if keys.dtype != np.uint8:  # (no silent cast: an int64 array would wrap into bytes nobody meant)
+                raise TypeError("lookup: a key array is uint8 or S%d, not %s" % (self.k, keys.dtype))
+            a = np.ascontiguousarray(keys).reshape(-1)
+        else:
+            items = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in keys]
+            if any(len(x) != self.k for x in items):
+                raise ValueError("lookup: every key must be %d bytes long" % self.k)
+            a = np.frombuffer(b"".join(items), dtype=np.uint8)
+        if a.size % self.k:
+            raise ValueError("lookup: the keys are not a multiple of %d bytes" % self.k)
+        return a.reshape(-1, self.k)
+
+    def lookup(self, keys, fold: Optional[bool] = None, info: Optional[dict] = None) -> np.ndarray:
+        """mk_lookup: the count of every key in the running table (uint64, 0 = absent), in the order asked.  ``keys``: a
+        list of str / bytes of length k, or a (rows, k) / flat uint8 array.  ``fold`` None: fold iff the context is
+        canonical (MK_LOOKUP_FOLD).  ``info``, if given, receives the mk_lookup_t fields."""
+        a = self._key_rows(keys)
+        counts = np.zeros(a.shape[0], dtype=np.uint64)
+        st = Lookup()
+        self._check(self._L.mk_lookup(self._h, a.ctypes.data if a.size else None, a.shape[0], self._fold_flag(fold),
+                                      counts.ctypes.data if a.size else None, C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return counts
+
+    def lookup_device(self, ptr: int, rows: int, out_ptr: int, fold: Optional[bool] = None) -> dict:
+        """mk_lookup_device: ``rows`` keys of k bytes at device address ``ptr`` -> uint64 counts at device address
+        ``out_ptr`` (both on this context's GPU).  Returns the mk_lookup_t fields."""
+        st = Lookup()
+        self._check(self._L.mk_lookup_device(self._h, ptr, int(rows), self._fold_flag(fold), out_ptr, C.byref(st)))
+        return st.as_dict()
+
+    def lookup_text(self, path_or_bytes, piece_bytes: int = 0, fold: Optional[bool] = None) -> Tuple[np.ndarray, dict]:
+        """mk_lookup_file / mk_lookup_text: (counts, info) of a panel in text form -- a path, or the text itself as bytes
+        -- one key a line, a "\t<count>" behind it ignored, so a counts TSV is a panel as it stands.  info: the
+        mk_lookup_t fields.  MercatHipError (MK_ERR_RANGE, the message names the line) for a malformed row."""
+        is_path = isinstance(path_or_bytes, (str, os.PathLike))
+        if is_path:
+            size = os.stat(path_or_bytes).st_size
+        else:
+            addr, size, keep = _buf_ptr(path_or_bytes)
+        cap = size // (self.k + 1) + 1  # (a row is at least k bytes and a line end)
+        counts = np.zeros(cap, dtype=np.uint64)
+        rows, st = C.c_size_t(0), Lookup()
+        flags = self._fold_flag(fold)
+        if is_path:
+            rc = self._L.mk_lookup_file(self._h, os.fsencode(str(path_or_bytes)), int(piece_bytes), flags, counts.ctypes.data,
+                                        cap, C.byref(rows), C.byref(st))
+        else:
+            rc = self._L.mk_lookup_text(self._h, addr, size, int(piece_bytes), flags, counts.ctypes.data, cap, C.byref(rows),
+                                        C.byref(st))
+        self._check(rc)
+        return counts[: rows.value], st.as_dict()
 
     # -- results
     def rows(self) -> int:

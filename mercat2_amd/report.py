@@ -17,7 +17,7 @@ over genomes, the reference's committed runs -- the two are the same.  ``merge_t
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 from . import native
 
@@ -38,6 +38,46 @@ def merge_counters_T(counters: Dict[str, "native.Counter"], out_file) -> int:
     if not names:
         raise ValueError("merge_counters_T: no samples")
     return native.write_merged_tsv_T([counters[n] for n in names], names, out_file)
+
+
+def format_query_tsv(names: Sequence[str], keys: Sequence[bytes], columns: Sequence[Sequence[int]]) -> bytes:
+    """The text of a query table: ``k-mer\t<name>...`` then one ``<key>\t<count>...`` line per panel row, in panel order,
+    duplicates kept, ``\n`` line ends.  ``columns[j][i]`` is the count of ``keys[i]`` in sample ``names[j]``; the key
+    bytes are written as they stand (a key may hold a tab or a blank)."""
+    out = [b"k-mer\t" + "\t".join(names).encode() + b"\n"]
+    for i, key in enumerate(keys):
+        out.append(bytes(key) + b"".join(b"\t%d" % int(col[i]) for col in columns) + b"\n")
+    return b"".join(out)
+
+
+def panel_keys(panel_path, k: int, header: bool) -> list:
+    """The keys of a panel in text form (mk_lookup_file's row rules: k key bytes a line, whatever follows them is a
+    tab and a count), line 1 left out when it is a header."""
+    with open(panel_path, "rb") as fh:
+        lines = fh.read().split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    return [line[:k] for line in lines[1 if header else 0:]]
+
+
+def write_query_tsv(counters: Dict[str, "native.Counter"], panel_path, out_path, fold: bool = False) -> int:
+    """How often every k-mer of the panel at ``panel_path`` occurs in each sample of ``{sample name: Counter}``: the panel
+    is looked up once per sample in the table on the GPU (``Counter.lookup_text``), the table written to ``out_path`` with
+    the names sorted as the combined table sorts them.  Returns the number of panel rows.  MercatHipError (the message
+    names the line) for a malformed panel row."""
+    names = sorted(counters.keys())
+    if not names:
+        raise ValueError("write_query_tsv: no samples")
+    columns, info = [], None
+    for name in names:
+        counts, info = counters[name].lookup_text(panel_path, fold=fold)
+        columns.append(counts)
+    keys = panel_keys(panel_path, counters[names[0]].k, bool(info["header"]))
+    if any(len(col) != len(keys) for col in columns):
+        raise RuntimeError("write_query_tsv: the panel changed while it was looked up")
+    with open(out_path, "wb") as fh:
+        fh.write(format_query_tsv(names, keys, columns))
+    return len(keys)
 
 
 def _first_header_field(path, shape: dict) -> Optional[str]:
