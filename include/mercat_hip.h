@@ -324,6 +324,31 @@ int mk_lookup_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_byte
 int mk_lookup_file(mk_ctx* ctx, const char* path, size_t piece_bytes, unsigned flags, uint64_t* counts, size_t cap,
                    size_t* rows, mk_lookup_t* st);
 
+/* ---- the abundance spectrum of a table: how many distinct k-mers occur once, twice, ... (what Jellyfish calls `histo`,
+ *      KMC its histogram), reduced on the GPU in one pass over the table, without exporting it ----
+ * bins has high + 2 words: bins[c] = rows whose count is c, for 1 <= c <= high; bins[high + 1] = rows whose count is
+ * above high (Jellyfish's rule for -h); bins[0] stays 0, so that bins[i] is abundance i.  1 <= high <= 2^20, MK_ERR_ARG
+ * otherwise.  A row is a key whose count is not zero: a dense bin never hit, or a keyed slot that counts 0, is none.
+ * Counts are 64-bit and every step is an integer add: the answer is exact whatever the order (a count of 2^64 - 1 lands
+ * in the overflow bin); total and over_total are sums modulo 2^64, as mk_alpha_stats' total is.
+ * The contract is that of mk_lookup: the table is only READ and a repeated call gives the same answer; the call first
+ * makes the table final (pending row totals folded) and works on the context's stream, which is idle when it returns;
+ * a context that holds part of a refused chunk, or an open chunk, answers MK_ERR_STATE; an empty table gives all-zero
+ * bins and MK_OK.  A sharer (mk_share_table) answers as it does for mk_alpha_stats and mk_lookup: for its OWN tables,
+ * not the owner's -- the rows its chunks put into the owner's table are in the owner's histogram.
+ * mk_histo: bins in host memory; mk_histo_device: bins in DEVICE memory of the context's GPU.  st may be NULL. */
+typedef struct mk_histo_t {
+  uint64_t distinct;    /* rows: the sum of the bins                                            */
+  uint64_t total;       /* sum of the counts                                                    */
+  uint64_t max_count;   /* the largest count (0: no rows)                                       */
+  uint64_t over_rows;   /* rows whose count is above high: bins[high + 1]                       */
+  uint64_t over_total;  /* sum of their counts                                                  */
+  uint64_t slots;       /* table slots (dense bins) read                                        */
+  double s_scan, s_total; /* seconds: HIP-event time of the kernel(s); wall time of the call   */
+} mk_histo_t;
+int mk_histo(mk_ctx* ctx, uint64_t high, uint64_t* bins, mk_histo_t* st);
+int mk_histo_device(mk_ctx* ctx, uint64_t high, uint64_t* d_bins, mk_histo_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

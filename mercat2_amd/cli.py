@@ -16,7 +16,8 @@ reports are written from the tables on the GPU too (mercat2_amd/diversity.py): t
 sample type (report/diversity/<metric>-Nucleotide.tsv, report/beta_diversity/<metric>-protein.tsv; no heatmaps;
 skipped beyond 4096 samples), each sample's alpha metrics (report/diversity/<type>-<sample>.tsv) and, with two or
 more samples, report/diversity-<type>.tsv.  -query FILE writes query_<type>.tsv: the count of every k-mer of a panel in every
-sample, looked up in those tables (mk_lookup_file).  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
+sample, looked up in those tables (mk_lookup_file).  -histo [HIGH] writes every sample's abundance histogram
+(histo_<type>/<sample>_histo.txt, histo_<type>.tsv), reduced in those tables (mk_histo).  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -33,7 +34,7 @@ from . import __version__
 from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_background, removeN_text
 from .kmers import read_fasta_bytes
 from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_text
-from .report import merge_counters, merge_counters_T, write_query_tsv
+from .report import merge_counters, merge_counters_T, write_histo_files, write_histo_tsv, write_query_tsv
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
 
@@ -54,6 +55,12 @@ def parseargs(argv=None):
                         "dump is a panel): for every sample type, query_<type>.tsv with the count of every panel k-mer in "
                         "every sample, looked up in the tables on the GPU; with -canonical a k-mer is looked up under "
                         "min(k-mer, reverse complement)")
+    p.add_argument("-histo", type=int, nargs="?", const=10000, default=None, metavar="HIGH",
+                   help="the abundance histogram of every sample (what Jellyfish calls histo), reduced in the tables on the "
+                        "GPU: histo_<type>/<sample>_histo.txt, one '<abundance> <k-mers>' line per abundance that occurs, "
+                        "k-mers counted more than HIGH times [10000, at most 1048576] together under HIGH + 1, and "
+                        "histo_<type>.tsv with all samples side by side.  It describes the tables the run ends with: with "
+                        "-c 10 the bins below 10 are empty by construction -- a spectrum for choosing -c is made with -c 1")
     p.add_argument("-k", type=int, required=True, help="kmer length")
     p.add_argument("-n", type=int, default=os.cpu_count() or 1,
                    help="no of cores [auto detect]: samples read (inflated) and counted concurrently, at most 8")
@@ -97,6 +104,8 @@ def parseargs(argv=None):
         p.error(f"folder {args.f} is not valid.\n")
     if args.query and not os.path.isfile(args.query):
         p.error(f"file '{args.query}' is not valid.\n")
+    if args.histo is not None and not 1 <= args.histo <= 1 << 20:
+        p.error(f"-histo {args.histo}: HIGH must lie in 1..{1 << 20}")
     args.loaded = {"nucleotide": {}, "protein": {}}  # sample -> its count table, per type (-tsv)
     for d in args.tsv:
         if not os.path.isdir(d):
@@ -433,6 +442,11 @@ def main(argv=None) -> int:
                     except native.MercatHipError as e:
                         raise SystemExit(f"-query {args.query}: {e}")
                     print(f"query_{stem[len('combined_'):]}.tsv: {n} panel k-mers in {len(tables)} sample(s)")
+                if args.histo is not None:  # from the tables still on the GPU
+                    ordered = {base: tables[base] for base in sorted(tables)}
+                    bins = write_histo_files(ordered, out / f"histo_{kind}", args.histo)
+                    n = write_histo_tsv(ordered, out / f"histo_{kind}.tsv", args.histo, bins=bins)
+                    print(f"histo_{kind}.tsv: {n} abundances up to {args.histo} (and above) in {len(tables)} sample(s)")
         finally:
             for t in tables.values():
                 t.close()

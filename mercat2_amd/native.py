@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "mk_device_count", "mk_reset_for", "mk_textwrap", "mk_set_clean", "mk_clean_stats", "mk_clean_runs",
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
-    "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file",
+    "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -105,6 +105,15 @@ class Lookup(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in ("bytes", "lines", "keys", "found", "packed_keys", "text_keys", "folded")] +
                 [("header", C.c_int32), ("pieces", C.c_int32)] +
                 [(n, C.c_double) for n in ("s_read", "s_probe", "s_total")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class Histo(C.Structure):
+    """mk_histo_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("distinct", "total", "max_count", "over_rows", "over_total", "slots")] +
+                [(n, C.c_double) for n in ("s_scan", "s_total")])
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -235,6 +244,8 @@ def lib() -> C.CDLL:
         "mk_lookup_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, u64p, C.POINTER(Lookup)]),
         "mk_lookup_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, u64p, C.c_size_t, szp, C.POINTER(Lookup)]),
         "mk_lookup_file": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_uint, u64p, C.c_size_t, szp, C.POINTER(Lookup)]),
+        "mk_histo": (C.c_int, [vp, C.c_uint64, u64p, C.POINTER(Histo)]),
+        "mk_histo_device": (C.c_int, [vp, C.c_uint64, u64p, C.POINTER(Histo)]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -655,6 +666,16 @@ def lookup_multi(ctxs: Sequence["Counter"], keys, fold: Optional[bool] = None) -
     return total if total is not None else np.zeros(0, dtype=np.uint64)
 
 
+def histo_multi(ctxs: Sequence["Counter"], high: int = 10000) -> np.ndarray:
+    """The abundance histogram (Counter.histo) of a table spread over ``ctxs`` by key range (after merge_devices with
+    MERGE_RANGES): every key has one owner there, so the sum of the contexts' histograms is the table's.  Wrong for
+    contexts whose key sets overlap: a key two of them hold is two rows here, each under its own partial count."""
+    total = np.zeros(int(high) + 2, dtype=np.uint64)
+    for c in ctxs:
+        total += c.histo(high)
+    return total
+
+
 def synth_reads(genome_len: int, genome_seed: int, reads: int, read_len: int, read_seed: int,
                 sub_ppm: int = 0, first_index: int = 0) -> np.ndarray:
     """Deterministic synthetic FASTA reads as a uint8 array."""
@@ -855,6 +876,25 @@ class Counter:
                                         C.byref(st))
         self._check(rc)
         return counts[: rows.value], st.as_dict()
+
+    # -- the abundance spectrum: bins[i] = distinct k-mers that occur i times; the table is only read
+    def histo(self, high: int = 10000, info: Optional[dict] = None) -> np.ndarray:
+        """mk_histo: uint64 array of ``high + 2`` bins -- bins[c] = rows whose count is c (1 <= c <= high), bins[high + 1] =
+        rows whose count is above ``high``, bins[0] = 0.  ``info``, if given, receives the mk_histo_t fields (distinct,
+        total, max_count, over_rows, over_total, slots, s_scan, s_total)."""
+        bins = np.zeros(max(0, int(high)) + 2, dtype=np.uint64)
+        st = Histo()
+        self._check(self._L.mk_histo(self._h, int(high), bins.ctypes.data, C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return bins
+
+    def histo_device(self, high: int, out_ptr: int) -> dict:
+        """mk_histo_device: the same ``high + 2`` uint64 bins written at device address ``out_ptr`` (on this context's
+        GPU).  Returns the mk_histo_t fields."""
+        st = Histo()
+        self._check(self._L.mk_histo_device(self._h, int(high), out_ptr, C.byref(st)))
+        return st.as_dict()
 
     # -- results
     def rows(self) -> int:

@@ -80,6 +80,51 @@ def write_query_tsv(counters: Dict[str, "native.Counter"], panel_path, out_path,
     return len(keys)
 
 
+def format_histo(bins, full: bool = False) -> bytes:
+    """The text of an abundance histogram (``Counter.histo``): one ``<abundance> <k-mers>`` line per bin, a single blank
+    between the two, ascending, ``\n`` line ends -- the layout ``jellyfish histo -h HIGH`` documents.  bins[i] is the
+    number of distinct k-mers that occur i times, the last bin (abundance high + 1) those that occur more often.  Bins
+    that are zero are left out unless ``full`` (bin 0 is never written: no row has count 0)."""
+    return b"".join(b"%d %d\n" % (i, int(n)) for i, n in enumerate(bins) if i and (full or int(n)))
+
+
+def write_histo_files(counters: Dict[str, "native.Counter"], folder, high: int = 10000) -> Dict[str, object]:
+    """``<folder>/<name>_histo.txt`` (``format_histo``) for every sample of ``{sample name: Counter}``, each histogram
+    reduced in the table on the GPU (``Counter.histo``).  Returns ``{name: bins}``."""
+    os.makedirs(folder, exist_ok=True)
+    out = {}
+    for name in counters:
+        out[name] = counters[name].histo(high)
+        with open(os.path.join(folder, f"{name}_histo.txt"), "wb") as fh:
+            fh.write(format_histo(out[name]))
+    return out
+
+
+def format_histo_tsv(names: Sequence[str], columns: Sequence[Sequence[int]]) -> bytes:
+    """The cohort's histograms side by side: ``count\t<name>...``, then one tab-separated row per abundance at which any
+    sample's bin is not zero, ascending, the overflow row (abundance high + 1) last.  ``columns[j]`` are the bins of
+    ``names[j]``, all of one length."""
+    out = [b"count\t" + "\t".join(names).encode() + b"\n"]
+    for i in range(1, len(columns[0]) if columns else 0):
+        if any(int(col[i]) for col in columns):
+            out.append(b"%d" % i + b"".join(b"\t%d" % int(col[i]) for col in columns) + b"\n")
+    return b"".join(out)
+
+
+def write_histo_tsv(counters: Dict[str, "native.Counter"], out_file, high: int = 10000, bins: Optional[dict] = None) -> int:
+    """The histograms of ``{sample name: Counter}`` as one table (``format_histo_tsv``), the names in the order given.
+    ``bins``: histograms already at hand (``write_histo_files``' result), else they are computed.  Returns the number
+    of rows written."""
+    names = list(counters.keys())
+    if not names:
+        raise ValueError("write_histo_tsv: no samples")
+    columns = [bins[name] if bins is not None else counters[name].histo(high) for name in names]
+    text = format_histo_tsv(names, columns)
+    with open(out_file, "wb") as fh:
+        fh.write(text)
+    return text.count(b"\n") - 1
+
+
 def _first_header_field(path, shape: dict) -> Optional[str]:
     """The first field of a count table's header line (the combined table's first column title); None without one."""
     if not shape["header"]:
