@@ -349,6 +349,54 @@ typedef struct mk_histo_t {
 int mk_histo(mk_ctx* ctx, uint64_t high, uint64_t* bins, mk_histo_t* st);
 int mk_histo_device(mk_ctx* ctx, uint64_t high, uint64_t* d_bins, mk_histo_t* st);
 
+/* ---- sequences in, per-record k-mer hits and abundance out: how many of this read's k-mers are in the table, and how
+ *      abundant are they (Jellyfish `query -s`, BBDuk-style screening, abundance filtering), answered on the GPU from
+ *      the text itself: one byte per base travels, not k ----
+ * The text is FASTA and is read exactly as counting reads it (the general parser: strip(), universal newlines, '*'
+ * removed, wrapped lines joined, any ASCII character kept); a byte >= 0x80 in a sequence line is MK_ERR_NON_ASCII, header
+ * lines may hold any bytes.  Clean mode and FASTQ mode of the context do NOT apply: they rewrite chunks on their way into
+ * the count and this call never enters that path -- the text is read as FASTA as it stands (convert FASTQ with mk_fq2fa).
+ * Records are the stretches of kept characters between header lines: one row per header line, in text order, a header
+ * without sequence included (windows = 0); one leading row when kept characters stand in front of the first header
+ * (st->headless = 1).  *nrows = records.  With cap too small: MK_ERR_RANGE, the needed size in *nrows, nothing written
+ * past cap.
+ * A record of L kept characters has max(0, L - k + 1) windows; no window spans two records.  Each window is probed where
+ * mk_lookup would probe the same k bytes: inside the alphabet in the packed table (dense bins, the one-word table with
+ * the 32 x 'T' key beside it, the two-word tables), any other window -- every window of an MK_ALPHABET_RAW context or of
+ * a k beyond the packed tables -- in the by-reference table.  MK_SCREEN_FOLD has the meaning and the restriction of
+ * MK_LOOKUP_FOLD.  at_least >= 1 (0: MK_ERR_ARG).  All sums are integer adds: the rows are exact whatever the order.
+ * The table is only READ, under mk_lookup's rules: it is made final first, an open chunk or a context that holds part of
+ * a refused chunk is MK_ERR_STATE, a sharer screens against its OWN table, the stream is idle afterwards; the export,
+ * mk_export_stats and the counting figures of mk_get_stats are what they were.  The context's chunk buffers serve as
+ * scratch.
+ * mk_screen_text: text in host memory, moved to the device in pieces of about piece_bytes (0: pick; limits of
+ * mk_load_tsv) that are cut where a record starts (the rule of mk_record_cuts: no record is split, a record longer than
+ * a piece makes its piece that long); the rows of a piece follow those of the piece before.  mk_screen_device: text and
+ * rows in DEVICE memory of the context's GPU, one piece.  st may be NULL. */
+#define MK_SCREEN_FOLD 1u   /* fold every ACGT-only window onto min(window, reverse complement) */
+typedef struct mk_screen_row_t { /* one per record, in text order */
+  uint64_t windows;  /* k-length windows of the record: max(0, L - k + 1), L = kept characters          */
+  uint64_t hits;     /* windows whose k-mer's count in the table is >= at_least                         */
+  uint64_t sum;      /* sum of the counts of all windows (modulo 2^64)                                   */
+  uint64_t min, max; /* smallest / largest count over the windows (an absent k-mer is 0); both 0 when windows == 0 */
+} mk_screen_row_t;
+typedef struct mk_screen_t {
+  uint64_t bytes;            /* text consumed                                                       */
+  uint64_t records;          /* rows                                                                */
+  uint64_t windows, hits;    /* summed over the records                                             */
+  uint64_t packed_windows;   /* windows probed in the packed table / dense bins                     */
+  uint64_t text_windows;     /* windows probed in the by-reference table                            */
+  uint64_t folded;           /* windows replaced by their reverse complement (MK_SCREEN_FOLD)       */
+  int32_t headless, pieces;  /* 1: a leading record without a header line; pieces the text went in  */
+  /* seconds: host time inside the copies towards the device; HIP-event time of the parser and the record scan; of the
+   * probe kernels; wall time of the call */
+  double s_read, s_parse, s_probe, s_total;
+} mk_screen_t;
+int mk_screen_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, uint64_t at_least,
+                   mk_screen_row_t* rows, size_t cap, size_t* nrows, mk_screen_t* st);
+int mk_screen_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, uint64_t at_least,
+                     mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_screen_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

@@ -17,7 +17,9 @@ sample type (report/diversity/<metric>-Nucleotide.tsv, report/beta_diversity/<me
 skipped beyond 4096 samples), each sample's alpha metrics (report/diversity/<type>-<sample>.tsv) and, with two or
 more samples, report/diversity-<type>.tsv.  -query FILE writes query_<type>.tsv: the count of every k-mer of a panel in every
 sample, looked up in those tables (mk_lookup_file).  -histo [HIGH] writes every sample's abundance histogram
-(histo_<type>/<sample>_histo.txt, histo_<type>.tsv), reduced in those tables (mk_histo).  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
+(histo_<type>/<sample>_histo.txt, histo_<type>.tsv), reduced in those tables (mk_histo).  -screen FILE writes, for every
+sample of FILE's type, screen_<type>/<sample>_screen.tsv: per record of FILE its k-mers, how many of them the sample's table
+holds, and how abundant they are (mk_screen_text).  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -34,7 +36,7 @@ from . import __version__
 from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_background, removeN_text
 from .kmers import read_fasta_bytes
 from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_text
-from .report import merge_counters, merge_counters_T, write_histo_files, write_histo_tsv, write_query_tsv
+from .report import merge_counters, merge_counters_T, write_histo_files, write_histo_tsv, write_query_tsv, write_screen_tsv
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
 
@@ -61,6 +63,13 @@ def parseargs(argv=None):
                         "k-mers counted more than HIGH times [10000, at most 1048576] together under HIGH + 1, and "
                         "histo_<type>.tsv with all samples side by side.  It describes the tables the run ends with: with "
                         "-c 10 the bins below 10 are empty by construction -- a spectrum for choosing -c is made with -c 1")
+    p.add_argument("-screen", type=str, required=False, metavar="FILE",
+                   help="a FASTA or FASTQ file (plain or .gz) of reads or contigs to screen against the tables on the GPU: for "
+                        "every sample of FILE's type (by its extension, as -i inputs are sorted), "
+                        "screen_<type>/<sample>_screen.tsv with one line per record of FILE: its k-mers (windows), how many "
+                        "of them the sample holds at least -screen_min times (hits), and the sum, smallest and largest of "
+                        "their counts; with -canonical the k-mers are folded")
+    p.add_argument("-screen_min", type=int, default=1, metavar="N", help="-screen: a k-mer is a hit from this count on [1]")
     p.add_argument("-k", type=int, required=True, help="kmer length")
     p.add_argument("-n", type=int, default=os.cpu_count() or 1,
                    help="no of cores [auto detect]: samples read (inflated) and counted concurrently, at most 8")
@@ -106,6 +115,15 @@ def parseargs(argv=None):
         p.error(f"file '{args.query}' is not valid.\n")
     if args.histo is not None and not 1 <= args.histo <= 1 << 20:
         p.error(f"-histo {args.histo}: HIGH must lie in 1..{1 << 20}")
+    args.screen_kind = None
+    if args.screen:
+        if not os.path.isfile(args.screen):
+            p.error(f"file '{args.screen}' is not valid.\n")
+        args.screen_kind = classify(Path(args.screen).expanduser().absolute(), True)[0]
+        if not args.screen_kind:
+            p.error(f"-screen {args.screen}: the extension names neither a nucleotide, a protein nor a FASTQ file")
+    if not 1 <= args.screen_min < 1 << 64:
+        p.error(f"-screen_min {args.screen_min}: must be 1 or more")
     args.loaded = {"nucleotide": {}, "protein": {}}  # sample -> its count table, per type (-tsv)
     for d in args.tsv:
         if not os.path.isdir(d):
@@ -442,6 +460,17 @@ def main(argv=None) -> int:
                     except native.MercatHipError as e:
                         raise SystemExit(f"-query {args.query}: {e}")
                     print(f"query_{stem[len('combined_'):]}.tsv: {n} panel k-mers in {len(tables)} sample(s)")
+                if args.screen and args.screen_kind == kind:  # from the tables still on the GPU
+                    from .kmers import screen_reads
+                    (out / f"screen_{kind}").mkdir(parents=True, exist_ok=True)
+                    for base in sorted(tables):
+                        try:
+                            names, rows = screen_reads(tables[base], args.screen, args.screen_min)
+                        except native.MercatHipError as e:
+                            raise SystemExit(f"-screen {args.screen}: {e}")
+                        write_screen_tsv(out / f"screen_{kind}" / f"{base}_screen.tsv", names, rows)
+                    print(f"screen_{kind}/: {len(names)} records of {os.path.basename(args.screen)} screened against "
+                          f"{len(tables)} sample(s)")
                 if args.histo is not None:  # from the tables still on the GPU
                     ordered = {base: tables[base] for base in sorted(tables)}
                     bins = write_histo_files(ordered, out / f"histo_{kind}", args.histo)

@@ -117,6 +117,10 @@ int mk_grow_run128(mk_ctx* c, size_t need_rows);
 int mk_grow_run_ref(mk_ctx* c, size_t need_rows);
 int mk_grow_run(mk_ctx* c, size_t more_rows);
 
+// mk_lookup.hip: how a read-only call on the tables opens (mk_lookup*, mk_screen*): the arguments, then the table made
+// final and the context's stream drained; *fold = the fold flag was given (and may be)
+int lk_open(mk_ctx* c, const char* what, unsigned flags, bool* fold);
+
 struct MkEventPair {
   hipEvent_t a, b;
   int id;

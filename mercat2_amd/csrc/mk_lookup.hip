@@ -15,20 +15,6 @@
 typedef std::chrono::steady_clock LkClk;
 static double lk_since(LkClk::time_point t0) { return std::chrono::duration<double>(LkClk::now() - t0).count(); }
 
-// the tables of one context, as the kernel sees them (a table that was never allocated has no slots)
-struct LkTables {
-  const MkSlot* run;          // one-word keys
-  u64 run_slots;
-  u64 side;                   // count of the one key kept beside it (32 x 'T' == MK_EMPTY)
-  const u64* bins;            // dense mode: the bins instead
-  u64 nbins;
-  const MkSlot128* run128;    // two-word keys
-  u64 run128_slots;
-  const MkSlot* ref;          // keys kept as text
-  u64 ref_slots;
-  const uint8_t* arena;
-};
-
 // A probe is a dependent random 16-byte read: a lane that looks one key up after the other waits a full trip to HBM per
 // key.  PER keys a lane: the home-slot loads of all of them are issued before any is compared (one-word table).
 // (A/B builds: -DLK_PER=1 is the one-key-a-lane form tools/lookup_probe.py's figures are compared with.)
@@ -121,17 +107,6 @@ __global__ void __launch_bounds__(256) lk_probe_k(const uint8_t* __restrict__ te
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static LkTables lk_tables(const mk_ctx* c) {
-  LkTables t{};
-  if (c->mode == MK_MODE_DENSE) { t.bins = (const u64*)c->run.p; t.nbins = c->run_slots; }
-  else if (c->mode == MK_MODE_HASH64) { t.run = (const MkSlot*)c->run.p; t.run_slots = c->run_slots; t.side = c->run_side; }
-  else if (c->mode == MK_MODE_HASH128) { t.run128 = (const MkSlot128*)c->run128.p; t.run128_slots = c->run128_slots; }
-  t.ref = (const MkSlot*)c->run_ref.p;
-  t.ref_slots = c->run_ref_slots;
-  t.arena = (const uint8_t*)c->arena.p;
-  return t;
-}
-
 // The probe kernel over `rows` contiguous keys (line_start == nullptr) or over the lines of a piece, on c->stream.
 static int lk_launch(mk_ctx* c, const uint8_t* d_text, const unsigned* line_start, u64 rows, unsigned cap, bool fold,
                      u64* d_counts, TlStatus* d_st) {
@@ -152,8 +127,9 @@ static int lk_launch(mk_ctx* c, const uint8_t* d_text, const unsigned* line_star
 }
 
 // How every lookup opens: the arguments, then the table made final as mk_export_size makes it (pending row totals
-// folded, read-backs landed) and the context's stream drained.
-static int lk_open(mk_ctx* c, const char* what, unsigned flags, bool* fold) {
+// folded, read-backs landed) and the context's stream drained.  (mk_screen.hip opens the same way: MK_SCREEN_FOLD is
+// MK_LOOKUP_FOLD.)
+int lk_open(mk_ctx* c, const char* what, unsigned flags, bool* fold) {
   MK_REFUSE_SPOILED(c, what);
   if (c->in_chunk) { c->err = std::string(what) + ": a chunk is open"; return MK_ERR_STATE; }
   if (flags & ~MK_LOOKUP_FOLD) { c->err = std::string(what) + ": unknown flag"; return MK_ERR_ARG; }

@@ -1,0 +1,452 @@
+// mk_screen.hip -- sequences in, per-record k-mer hits and abundance out (mk_screen_text / mk_screen_device,
+// include/mercat_hip.h): the windows of every record of a FASTA text probed in the context's tables and reduced to one
+// row {windows, hits, sum, min, max} a record.
+//
+// A piece of text goes through the general parser (mk_parse.hip) into the stream the count kernels slide over: kept
+// characters, one MK_SEP where a header line starts.  The record of a position is the number of separators at or
+// before it: sc_tiles_k counts them per tile, sc_scan_k (one workgroup) turns the counts into tile prefixes and the
+// number of records, and sc_probe_k finishes the scan inside the workgroup.  There a lane owns SC_RUN consecutive
+// window starts: it walks k - 1 + SC_RUN symbols of the workgroup's span (staged in LDS once, with a halo of k - 1),
+// ROLLS the packed key one symbol at a time, keeps "symbols since the last separator" (is this a window?) and "symbols
+// since the last byte outside the alphabet" (packed key or text key?), probes where lk_probe_k would probe the same k
+// bytes, and accumulates while it stays in one record.  Integer adds, min and max only: exact in any order.
+#include "mk_tsvpieces.h"
+#include "mk_tableview.h"
+#include <algorithm>
+#include <chrono>
+
+typedef std::chrono::steady_clock ScClk;
+static double sc_since(ScClk::time_point t0) { return std::chrono::duration<double>(ScClk::now() - t0).count(); }
+
+#define SC_RUN 32                // window starts a lane owns
+#define SC_SPAN (256 * SC_RUN)   // ... a workgroup: one tile of the record scan
+// Home-slot loads of the one-word table a lane has in flight before it compares any (LK_PER of mk_lookup.hip).
+#ifndef SC_PER
+#define SC_PER 4
+#endif
+// The span and its halo are staged in LDS up to this k (24.5 KiB); beyond it -- by-reference contexts only -- the walk
+// reads the stream itself.
+#define SC_LDS_MAX_K 16385
+
+struct ScStatus {  // device memory, read back twice a piece: after the scan (nsep, headless), after the probe
+  u64 nsep, headless;
+  u64 windows, hits, packed, text, folded, locked;
+};
+
+// bytes of w that equal MK_SEP (exact per byte: no borrow between them)
+__device__ __forceinline__ unsigned sc_seps_in(unsigned w) {
+  const unsigned x = w ^ (MK_SEP * 0x01010101u);
+  return __popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu));
+}
+
+__global__ void __launch_bounds__(256) sc_tiles_k(const uint8_t* __restrict__ seq, const MkChunkInfo* __restrict__ info,
+                                                  unsigned* __restrict__ tile_cnt) {
+  __shared__ unsigned s_wave[4];
+  const u64 seq_len = info->seq_len, base = (u64)blockIdx.x * SC_SPAN + (u64)threadIdx.x * SC_RUN;
+  unsigned n = 0;
+  if (base + SC_RUN <= seq_len) {
+    const uint4* p = reinterpret_cast<const uint4*>(seq + base);  // (seq is 256-byte aligned, base a multiple of 32)
+#pragma unroll
+    for (int i = 0; i < SC_RUN / 16; ++i) {
+      const uint4 v = p[i];
+      n += sc_seps_in(v.x) + sc_seps_in(v.y) + sc_seps_in(v.z) + sc_seps_in(v.w);
+    }
+  } else {
+    for (int j = 0; j < SC_RUN && base + j < seq_len; ++j) n += seq[base + j] == MK_SEP;
+  }
+  n = mk_wave_sum(n);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// One workgroup, in the pattern of mk_parse_scan: thread t owns tiles [t * per, (t + 1) * per).  tile_pre[i] =
+// separators in front of tile i; their total and whether kept characters stand in front of the first go to st.
+__global__ void __launch_bounds__(1024) sc_scan_k(const unsigned* __restrict__ tile_cnt, size_t ntiles, u64* __restrict__ tile_pre,
+                                                  const uint8_t* __restrict__ seq, const MkChunkInfo* __restrict__ info,
+                                                  ScStatus* __restrict__ st) {
+  __shared__ u64 s_c[1024];
+  const size_t per = (ntiles + 1023) / 1024;
+  const size_t lo = (size_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
+  u64 mine = 0;
+  for (size_t t = lo; t < hi; ++t) mine += tile_cnt[t];
+  s_c[threadIdx.x] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 run = 0;
+    for (int t = 0; t < 1024; ++t) {
+      const u64 c = s_c[t];
+      s_c[t] = run;
+      run += c;
+    }
+    st->nsep = run;
+    st->headless = (info->seq_len && seq[0] != MK_SEP) ? 1 : 0;
+  }
+  __syncthreads();
+  u64 run = s_c[threadIdx.x];
+  for (size_t t = lo; t < hi; ++t) {
+    tile_pre[t] = run;
+    run += tile_cnt[t];
+  }
+}
+
+__global__ void __launch_bounds__(256) sc_rows_init_k(mk_screen_row_t* __restrict__ rows, size_t n) {
+  mk_for_each(n, [&](size_t i) { rows[i] = mk_screen_row_t{0, 0, 0, ~0ull, 0}; });
+}
+// (a record without windows: its min was never written)
+__global__ void __launch_bounds__(256) sc_rows_final_k(mk_screen_row_t* __restrict__ rows, size_t n) {
+  mk_for_each(n, [&](size_t i) { if (rows[i].windows == 0) rows[i].min = 0; });
+}
+
+// What a lane has gathered for the record it is in.
+struct ScAcc {
+  u64 windows = 0, hits = 0, sum = 0, mn = ~0ull, mx = 0;
+  __device__ __forceinline__ void add(u64 cnt, u64 at_least) {
+    ++windows;
+    hits += cnt >= at_least ? 1 : 0;
+    sum += cnt;
+    mn = cnt < mn ? cnt : mn;
+    mx = cnt > mx ? cnt : mx;
+  }
+  __device__ __forceinline__ void flush(mk_screen_row_t* __restrict__ rows, u64 row) {  // (nothing gathered: no row is touched)
+    if (!windows) return;
+    mk_screen_row_t* r = rows + row;
+    atomicAdd((unsigned long long*)&r->windows, windows);
+    if (hits) atomicAdd((unsigned long long*)&r->hits, hits);
+    if (sum) atomicAdd((unsigned long long*)&r->sum, sum);
+    atomicMin((unsigned long long*)&r->min, mn);
+    if (mx) atomicMax((unsigned long long*)&r->max, mx);
+    *this = ScAcc();
+  }
+};
+
+// Grid: one workgroup per tile of SC_SPAN positions.  row_base: the record number of row 0 (1, or 0 when the piece
+// starts with a record that has no header line).  LDS false: KEYS == TL_TEXT_ONLY with a k whose halo LDS cannot hold.
+template <int KEYS, bool FOLD, bool LDS>
+__global__ void __launch_bounds__(256) sc_probe_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
+                                                  u64 row_base, int k, int bits, u64 at_least, LkTables t,
+                                                  mk_screen_row_t* __restrict__ rows, ScStatus* __restrict__ st) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_seq[];  // SC_SPAN + k - 1 bytes, rounded up to 16
+  __shared__ unsigned s_wave[4];
+  const u64 base = (u64)blockIdx.x * SC_SPAN;
+  if (LDS) {
+    const unsigned stage = (unsigned)(SC_SPAN + k - 1 + 15) & ~15u;
+    for (unsigned i = threadIdx.x * 16u; i < stage; i += 256u * 16u) {
+      if (base + i + 16 <= seq_len) *reinterpret_cast<uint4*>(s_seq + i) = *reinterpret_cast<const uint4*>(seq + base + i);
+      else
+        for (unsigned j = 0; j < 16; ++j) s_seq[i + j] = base + i + j < seq_len ? seq[base + i + j] : (uint8_t)MK_SEP;
+    }
+    __syncthreads();
+  }
+  // symbol at local index li of the span; positions behind the stream are separators
+  auto sym_at = [&](unsigned li) -> unsigned { return LDS ? s_seq[li] : (base + li < seq_len ? seq[base + li] : MK_SEP); };
+
+  // the record this lane's run starts in: separators in front of the tile, of the lanes before it in the workgroup
+  const unsigned l0 = threadIdx.x * SC_RUN;
+  unsigned own = 0;
+  if (LDS) {
+#pragma unroll
+    for (int i = 0; i < SC_RUN / 4; ++i) own += sc_seps_in(reinterpret_cast<const unsigned*>(s_seq + l0)[i]);
+  } else {
+    for (int j = 0; j < SC_RUN; ++j) own += sym_at(l0 + j) == MK_SEP;
+  }
+  const unsigned incl = mk_wave_scan_incl(own);
+  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  u64 rid = tile_pre[blockIdx.x] + (incl - own);
+  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
+
+  // ---- the walk: k - 1 symbols to fill the key, then one window start a symbol
+  const int kb = k * bits;
+  const u64 mask1 = kb >= 64 ? ~0ull : (1ull << kb) - 1;                                       // one-word keys
+  const unsigned __int128 mask_aa = (((unsigned __int128)1) << (kb > 127 ? 127 : kb)) - 1;     // protein 13..25-mers
+  const int sh2 = 128 - 2 * k;                                                                 // two-word nt: the last base's place in lo
+  u64 a = 0, b = 0;
+  unsigned __int128 wide = 0;
+  unsigned since_sep = 0, since_bad = 0;  // symbols since the last separator / the last byte outside the alphabet
+  unsigned li = l0, word = 0;
+  auto step = [&]() -> bool {  // takes the next symbol in; true: it is a separator
+    unsigned ch;
+    if (LDS) {
+      if ((li & 3u) == 0) word = reinterpret_cast<const unsigned*>(s_seq)[li >> 2];
+      ch = word & 0xFFu;
+      word >>= 8;
+    } else ch = sym_at(li);
+    ++li;
+    if (ch == MK_SEP) { since_sep = since_bad = 0; return true; }
+    ++since_sep;
+    if (KEYS == TL_TEXT_ONLY) return false;
+    unsigned code;
+    if (bits == 2) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 99u;
+    else code = (ch >= 'A' && ch <= 'Z') ? ch - 'A' : 99u;
+    if (code == 99u) { since_bad = 0; return false; }  // (what the key holds is pushed out before it is used again)
+    ++since_bad;
+    if (KEYS == TL_ONE_WORD) a = ((a << bits) | code) & mask1;
+    else if (KEYS == TL_TWO_WORD_AA) wide = ((wide << 5) | code) & mask_aa;
+    else { a = (a << 2) | (b >> 62); b = (b << 2) | ((u64)code << sh2); }
+    return false;
+  };
+  for (int q = 1; q < k; ++q) rid += step() ? 1 : 0;
+
+  ScAcc acc;
+  u64 n_win = 0, n_hits = 0, n_packed = 0, n_text = 0, n_folded = 0;
+  bool locked = false;
+  for (int g = 0; g < SC_RUN; g += SC_PER) {
+    u64 key[SC_PER], res[SC_PER];
+    ulonglong2 home[SC_PER];
+    bool sep[SC_PER], window[SC_PER], pending[SC_PER];
+#pragma unroll
+    for (int j = 0; j < SC_PER; ++j) {
+      sep[j] = step();
+      window[j] = !sep[j] && since_sep >= (unsigned)k;
+      pending[j] = false;
+      res[j] = 0;
+      if (!window[j]) continue;
+      if (KEYS != TL_TEXT_ONLY && since_bad >= (unsigned)k) {
+        ++n_packed;
+        u64 ka = a, kb2 = b;
+        if (KEYS == TL_TWO_WORD_AA) { ka = (u64)(wide >> 64); kb2 = (u64)wide; }
+        if (FOLD) {
+          bool turned;
+          if (KEYS == TL_TWO_WORD_NT) turned = mk_canon128(ka, kb2, k);
+          else {
+            const u64 rc = mk_revcomp2(ka, k);
+            turned = rc < ka;
+            if (turned) ka = rc;
+          }
+          n_folded += turned ? 1 : 0;
+        }
+        if (KEYS == TL_ONE_WORD) {
+          if (t.bins) res[j] = find_dense(t.bins, (size_t)t.nbins, ka);
+          else if (ka == MK_EMPTY) res[j] = t.side;
+          else if (t.run_slots) {
+            key[j] = ka;
+            home[j] = find64_home(t.run, t.run_slots - 1, ka);
+            pending[j] = true;
+          }
+        } else if (t.run128_slots) res[j] = find128(t.run128, t.run128_slots - 1, ka, kb2, &locked);
+      } else {
+        ++n_text;
+        const uint8_t* w = LDS ? s_seq + (li - (unsigned)k) : seq + base + (li - (unsigned)k);  // the window that ends here
+        if (t.ref_slots) res[j] = find_ref_of(t.ref, t.ref_slots - 1, t.arena, BytesAt{w}, k);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SC_PER; ++j) {
+      if (sep[j]) {  // the record ends in front of this symbol
+        acc.flush(rows, rid - row_base);
+        ++rid;
+      }
+      if (!window[j]) continue;
+      if (pending[j]) res[j] = find64_from(t.run, t.run_slots - 1, key[j], home[j]);
+      ++n_win;
+      n_hits += res[j] >= at_least ? 1 : 0;
+      acc.add(res[j], at_least);
+    }
+  }
+  // The whole wave ends in one record (the normal case inside a contig): reduce across it, one lane flushes -- five
+  // atomics a wave on the record's row instead of 320.  (Measured, DESIGN 8m: one 100 Mbase record 2.3 ms with it, 73 ms
+  // with every lane flushing for itself; 150 bp reads the same either way.)
+  if (__all(rid == __shfl(rid, 0))) {
+    for (int d = 32; d > 0; d >>= 1) {
+      acc.windows += __shfl_down(acc.windows, d);
+      acc.hits += __shfl_down(acc.hits, d);
+      acc.sum += __shfl_down(acc.sum, d);
+      const u64 mn = __shfl_down(acc.mn, d), mx = __shfl_down(acc.mx, d);
+      acc.mn = mn < acc.mn ? mn : acc.mn;
+      acc.mx = mx > acc.mx ? mx : acc.mx;
+    }
+    if (threadIdx.x & 63) acc.windows = 0;
+  }
+  acc.flush(rows, rid - row_base);
+  block_add(&st->windows, n_win);
+  block_add(&st->hits, n_hits);
+  block_add(&st->packed, n_packed);
+  block_add(&st->text, n_text);
+  block_add(&st->folded, n_folded);
+  if (locked) atomicAdd(&st->locked, 1ull);  // (cannot happen on a quiescent table)
+}
+
+// ------------------------------------------------------------------------------------------ host side
+struct ScCall {
+  mk_ctx* c;
+  const char* what;
+  bool fold;
+  u64 at_least;
+  MkDevBuf scratch;  // ScStatus | tile_pre[ntiles] | tile_cnt[ntiles]
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  mk_screen_t out{};
+  size_t rows_seen = 0;
+  ~ScCall() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+    buf_free(scratch);
+  }
+};
+
+static int sc_launch_probe(ScCall& s, size_t seq_len, const u64* tile_pre, u64 row_base, mk_screen_row_t* d_rows, ScStatus* d_st) {
+  mk_ctx* c = s.c;
+  const LkTables t = lk_tables(c);
+  const int keys = tl_keys_of(c), k = c->k;
+  const bool lds = k <= SC_LDS_MAX_K;
+  const unsigned grid = (unsigned)div_up(seq_len, SC_SPAN);
+  const size_t shmem = lds ? (((size_t)SC_SPAN + k - 1 + 15) & ~(size_t)15) : 0;
+#define SC_GO(K, F, L) hipLaunchKernelGGL((sc_probe_k<K, F, L>), dim3(grid), dim3(256), shmem, c->stream, (const uint8_t*)c->seq.p, \
+                                          (u64)seq_len, tile_pre, row_base, k, c->bits, s.at_least, t, d_rows, d_st)
+  if (keys == TL_ONE_WORD) { if (s.fold) SC_GO(TL_ONE_WORD, true, true); else SC_GO(TL_ONE_WORD, false, true); }
+  else if (keys == TL_TWO_WORD_NT) { if (s.fold) SC_GO(TL_TWO_WORD_NT, true, true); else SC_GO(TL_TWO_WORD_NT, false, true); }
+  else if (keys == TL_TWO_WORD_AA) SC_GO(TL_TWO_WORD_AA, false, true);
+  else if (lds) SC_GO(TL_TEXT_ONLY, false, true);
+  else SC_GO(TL_TEXT_ONLY, false, false);
+#undef SC_GO
+  MK_HIP(hipGetLastError());
+  return MK_OK;
+}
+
+// One piece of n bytes at d_text (device memory, whole records): parsed, scanned, and -- where there is room for all its
+// rows -- probed into d_rows (room rows; nullptr: the call's own buffer `own`, copied to h_rows).  The piece's records
+// are added to s.rows_seen either way.  The stream is idle afterwards.
+static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows, size_t room, MkDevBuf* own,
+                    mk_screen_row_t* h_rows) {
+  mk_ctx* c = s.c;
+  int rc;
+  const size_t ntiles = div_up(n, SC_SPAN);  // (the stream is no longer than the text)
+  const size_t pre_off = (sizeof(ScStatus) + 15) & ~(size_t)15;
+  if ((rc = mk_buf_reserve(c, s.scratch, pre_off + ntiles * (sizeof(u64) + sizeof(unsigned)) + 16)) != MK_OK) return rc;
+  ScStatus* d_st = (ScStatus*)s.scratch.p;
+  u64* tile_pre = (u64*)((char*)s.scratch.p + pre_off);
+  unsigned* tile_cnt = (unsigned*)(tile_pre + ntiles);
+  if ((rc = mk_buf_reserve(c, c->seq, n + 256)) != MK_OK) return rc;
+  if ((uintptr_t)d_text & 15) {  // (the general transducer loads 16 bytes at a time)
+    if ((rc = mk_buf_reserve(c, c->raw, n + 64)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(c->raw.p, d_text, n, hipMemcpyDeviceToDevice, c->stream));
+    d_text = (const uint8_t*)c->raw.p;
+  }
+  MkChunkInfo info{};
+  ScStatus h{};
+  float ms = 0.f;
+  MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
+  MK_HIP(hipMemsetAsync(d_st, 0, sizeof(ScStatus), c->stream));
+  MK_HIP(hipEventRecord(s.ev[0], c->stream));
+  if ((rc = mk_launch_parse(c, d_text, n)) != MK_OK) return rc;
+  hipLaunchKernelGGL(sc_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const uint8_t*)c->seq.p, (const MkChunkInfo*)c->info.p, tile_cnt);
+  hipLaunchKernelGGL(sc_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, (const uint8_t*)c->seq.p,
+                     (const MkChunkInfo*)c->info.p, d_st);
+  MK_HIP(hipGetLastError());
+  MK_HIP(hipEventRecord(s.ev[1], c->stream));
+  MK_HIP(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  MK_HIP(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+  s.out.s_parse += ms * 1e-3;
+  if (info.non_ascii) {
+    c->err = std::string(s.what) + ": the text holds " + std::to_string(info.non_ascii) +
+             " sequence byte(s) >= 0x80 (non-ASCII sequence text is not supported)";
+    return MK_ERR_NON_ASCII;
+  }
+  const size_t nrows = (size_t)(h.nsep + h.headless);
+  const size_t first = s.rows_seen;
+  s.rows_seen += nrows;
+  s.out.bytes += n;
+  s.out.pieces += 1;
+  if (h.headless) s.out.headless = 1;
+  if (!nrows || nrows > room) return MK_OK;  // (too many: the call goes on counting records and answers MK_ERR_RANGE)
+  if (!d_rows) {
+    if ((rc = mk_buf_reserve(c, *own, nrows * sizeof(mk_screen_row_t))) != MK_OK) return rc;
+    d_rows = (mk_screen_row_t*)own->p;
+  }
+  MK_HIP(hipEventRecord(s.ev[2], c->stream));
+  hipLaunchKernelGGL(sc_rows_init_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
+  if (info.seq_len && (rc = sc_launch_probe(s, (size_t)info.seq_len, tile_pre, h.headless ? 0 : 1, d_rows, d_st)) != MK_OK) return rc;
+  hipLaunchKernelGGL(sc_rows_final_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
+  MK_HIP(hipGetLastError());
+  MK_HIP(hipEventRecord(s.ev[3], c->stream));
+  MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  if (h_rows) MK_HIP(hipMemcpyAsync(h_rows + first, d_rows, nrows * sizeof(mk_screen_row_t), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  MK_HIP(hipEventElapsedTime(&ms, s.ev[2], s.ev[3]));
+  s.out.s_probe += ms * 1e-3;
+  if (h.locked) {
+    c->err = std::string(s.what) + ": a slot of the table was being claimed: something counts into it during the call";
+    return MK_ERR_STATE;
+  }
+  if (h.packed + h.text != h.windows) {
+    c->err = std::string(s.what) + ": the probe kernel lost windows (internal error)";
+    return MK_ERR_STATE;
+  }
+  s.out.windows += h.windows;
+  s.out.hits += h.hits;
+  s.out.packed_windows += h.packed;
+  s.out.text_windows += h.text;
+  s.out.folded += h.folded;
+  return MK_OK;
+}
+
+// How both calls open (lk_open's rules) and end; body: the pieces.
+template <class Body>
+static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least, size_t cap, size_t* nrows, mk_screen_t* st,
+                  Body&& body) {
+  const auto t0 = ScClk::now();
+  ScCall s{c, what, false, at_least};
+  int rc = lk_open(c, what, flags, &s.fold);
+  if (rc != MK_OK) return rc;
+  if (at_least < 1) { c->err = std::string(what) + ": at_least must be 1 or more"; return MK_ERR_ARG; }
+  for (auto& e : s.ev) MK_HIP(hipEventCreate(&e));
+  const bool profile = c->profile;  // (the parser's launches are no part of the counting figures)
+  c->profile = false;
+  rc = body(s);
+  c->profile = profile;
+  (void)hipStreamSynchronize(c->stream);
+  if (rc != MK_OK) return rc;
+  if (nrows) *nrows = s.rows_seen;
+  if (s.rows_seen > cap) {
+    c->err = std::string(what) + ": the text holds " + std::to_string(s.rows_seen) + " records, rows has room for " + std::to_string(cap);
+    return MK_ERR_RANGE;
+  }
+  s.out.records = s.rows_seen;
+  s.out.s_total = sc_since(t0);
+  if (st) *st = s.out;
+  return MK_OK;
+}
+
+extern "C" int mk_screen_device(mk_ctx* c, const uint8_t* d_text, size_t n, unsigned flags, uint64_t at_least,
+                                mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_screen_t* st) {
+  if (!c) return MK_ERR_ARG;
+  if ((n && !d_text) || (cap && !d_rows)) { c->err = "mk_screen_device: NULL buffer"; return MK_ERR_ARG; }
+  return sc_run(c, "mk_screen_device", flags, at_least, cap, nrows, st,
+                [&](ScCall& s) { return n ? sc_piece(s, d_text, n, d_rows, cap, nullptr, nullptr) : MK_OK; });
+}
+
+extern "C" int mk_screen_text(mk_ctx* c, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, uint64_t at_least,
+                              mk_screen_row_t* rows, size_t cap, size_t* nrows, mk_screen_t* st) {
+  if (!c) return MK_ERR_ARG;
+  if ((n && !text) || (cap && !rows)) { c->err = "mk_screen_text: NULL buffer"; return MK_ERR_ARG; }
+  MkDevBuf d_rows;
+  const int rc = sc_run(c, "mk_screen_text", flags, at_least, cap, nrows, st, [&](ScCall& s) -> int {
+    if (!n) return MK_OK;
+    // pieces: cut where a record starts once a piece holds piece_bytes (mk_record_cuts; the loader's default and limits)
+    size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
+    piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
+    std::vector<uint64_t> cuts(n / piece + 2);
+    size_t ncuts = 0;
+    int r = mk_record_cuts(text, n, piece, (size_t)4 << 20, cuts.data(), cuts.size(), &ncuts);
+    if (r != MK_OK) { c->err = "mk_screen_text: the record scanner failed (internal error)"; return MK_ERR_STATE; }
+    cuts.resize(ncuts);
+    cuts.push_back(n);
+    size_t at = 0;
+    for (const uint64_t end : cuts) {
+      const size_t len = (size_t)end - at;
+      if (!len) continue;
+      if ((r = mk_buf_reserve(c, c->raw, len + 64)) != MK_OK) return r;
+      const auto t1 = ScClk::now();
+      MK_HIP(hipMemcpyAsync(c->raw.p, text + at, len, hipMemcpyHostToDevice, c->stream));
+      s.out.s_read += sc_since(t1);
+      const size_t room = cap > s.rows_seen ? cap - s.rows_seen : 0;
+      if ((r = sc_piece(s, (const uint8_t*)c->raw.p, len, nullptr, room, &d_rows, rows)) != MK_OK) return r;
+      at = (size_t)end;
+    }
+    return MK_OK;
+  });
+  buf_free(d_rows);
+  return rc;
+}

@@ -152,3 +152,28 @@ __device__ __forceinline__ u64 find_ref_of(const MkSlot* __restrict__ run, u64 m
 }
 // Dense bins: one indexed load.
 __device__ __forceinline__ u64 find_dense(const u64* __restrict__ bins, size_t nbins, u64 bin) { return bin < nbins ? bins[bin] : 0; }
+
+// ---- the tables of one context, as a probing kernel sees them (mk_lookup.hip, mk_screen.hip); a table that was never
+// allocated has no slots
+struct LkTables {
+  const MkSlot* run;          // one-word keys
+  u64 run_slots;
+  u64 side;                   // count of the one key kept beside it (32 x 'T' == MK_EMPTY)
+  const u64* bins;            // dense mode: the bins instead
+  u64 nbins;
+  const MkSlot128* run128;    // two-word keys
+  u64 run128_slots;
+  const MkSlot* ref;          // keys kept as text
+  u64 ref_slots;
+  const uint8_t* arena;
+};
+static inline LkTables lk_tables(const mk_ctx* c) {
+  LkTables t{};
+  if (c->mode == MK_MODE_DENSE) { t.bins = (const u64*)c->run.p; t.nbins = c->run_slots; }
+  else if (c->mode == MK_MODE_HASH64) { t.run = (const MkSlot*)c->run.p; t.run_slots = c->run_slots; t.side = c->run_side; }
+  else if (c->mode == MK_MODE_HASH128) { t.run128 = (const MkSlot128*)c->run128.p; t.run128_slots = c->run128_slots; }
+  t.ref = (const MkSlot*)c->run_ref.p;
+  t.ref_slots = c->run_ref_slots;
+  t.arena = (const uint8_t*)c->arena.p;
+  return t;
+}

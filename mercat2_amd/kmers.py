@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import gzip
 from pathlib import Path
-from typing import Dict, Optional, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 from . import native
 
@@ -99,3 +99,40 @@ def lookup_kmers(table: "native.Counter", kmers) -> Dict[str, int]:
     k-mer it lacks -- without exporting it: what ``find_kmers(...)[kmer]`` answers, for a handful of keys."""
     kmers = list(kmers)
     return dict(zip(kmers, table.lookup(kmers).tolist()))
+
+
+FASTQ_SUFFIXES = (".fq", ".fastq", ".fq.gz", ".fastq.gz")
+_BLANKS = b" \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f"  # what str.strip() removes from ASCII text
+
+
+def record_names(text: bytes) -> List[str]:
+    """The names of a FASTA text's records, in order, as the screen calls number them: a record per header line -- a
+    line whose first non-blank character is '>', find_kmers' test after line.strip() (lib/mercat2_kmers.py:51-52) --
+    named by the first word behind the '>' ("" for none), and a leading "" when sequence stands in front of the first
+    header line.  Lines end at "\n", "\r\n" or a lone "\r", as text mode reads them."""
+    names: List[str] = []
+    headless = False
+    for line in bytes(text).splitlines():
+        line = line.strip(_BLANKS)
+        if line.startswith(b">"):
+            words = line[1:].decode("utf-8", "replace").split()
+            names.append(words[0] if words else "")
+        elif not names and not headless and line.replace(b"*", b""):
+            headless = True
+    return ([""] if headless else []) + names
+
+
+def screen_reads(table: "native.Counter", file: Union[str, Path], at_least: int = 1) -> Tuple[List[str], "native.np.ndarray"]:
+    """(names, array) of every record of a FASTA or FASTQ file screened against a table that is still on the GPU
+    (Counter.screen): array[i] = (windows, hits, sum, min, max) of record i -- its k-mers, how many of them the table
+    holds ``at_least`` times, and the sum, smallest and largest of their counts.  A '.gz' file is inflated on the host;
+    a FASTQ file ('.fq' / '.fastq', plain or '.gz') is first converted as MerCat2's fq2fa converts it (mk_fq2fa).  A
+    canonical table folds the windows."""
+    text = read_fasta_bytes(file)
+    if str(file).lower().endswith(FASTQ_SUFFIXES):
+        text, _ = native.fq2fa(text)
+    names = record_names(text)
+    rows = table.screen(text, at_least)
+    if len(names) != rows.shape[0]:
+        raise RuntimeError("screen_reads: %d header names for %d records" % (len(names), rows.shape[0]))
+    return names, rows

@@ -35,10 +35,13 @@ ABI_SYMBOLS = [
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
+    "mk_screen_text", "mk_screen_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
 LOOKUP_FOLD = 1
+SCREEN_FOLD = 1
+SCREEN_COLUMNS = ("windows", "hits", "sum", "min", "max")  # mk_screen_row_t: the columns of Counter.screen's array
 
 
 class MercatHipError(RuntimeError):
@@ -105,6 +108,21 @@ class Lookup(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in ("bytes", "lines", "keys", "found", "packed_keys", "text_keys", "folded")] +
                 [("header", C.c_int32), ("pieces", C.c_int32)] +
                 [(n, C.c_double) for n in ("s_read", "s_probe", "s_total")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ScreenRow(C.Structure):
+    """mk_screen_row_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint64) for n in SCREEN_COLUMNS]
+
+
+class Screen(C.Structure):
+    """mk_screen_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("bytes", "records", "windows", "hits", "packed_windows", "text_windows", "folded")] +
+                [("headless", C.c_int32), ("pieces", C.c_int32)] +
+                [(n, C.c_double) for n in ("s_read", "s_parse", "s_probe", "s_total")])
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -246,6 +264,9 @@ def lib() -> C.CDLL:
         "mk_lookup_file": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_uint, u64p, C.c_size_t, szp, C.POINTER(Lookup)]),
         "mk_histo": (C.c_int, [vp, C.c_uint64, u64p, C.POINTER(Histo)]),
         "mk_histo_device": (C.c_int, [vp, C.c_uint64, u64p, C.POINTER(Histo)]),
+        "mk_screen_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp,
+                                     C.POINTER(Screen)]),
+        "mk_screen_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp, C.POINTER(Screen)]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -894,6 +915,36 @@ class Counter:
         GPU).  Returns the mk_histo_t fields."""
         st = Histo()
         self._check(self._L.mk_histo_device(self._h, int(high), out_ptr, C.byref(st)))
+        return st.as_dict()
+
+    # -- screening: FASTA text in, one row {windows, hits, sum, min, max} a record out; the table is only read
+    def screen(self, path_or_bytes, at_least: int = 1, fold: Optional[bool] = None, piece_bytes: int = 0,
+               info: Optional[dict] = None) -> np.ndarray:
+        """mk_screen_text: a (records, 5) uint64 array, columns SCREEN_COLUMNS -- per record of the FASTA text (a path to a
+        plain file, or the text itself as bytes) its k-length windows, how many of them the table holds ``at_least``
+        times, and the sum, smallest and largest of their counts (an absent k-mer counts 0).  One row per header line,
+        in order, and a leading one for sequence in front of the first header (info["headless"]).  ``fold`` None: fold
+        iff the context is canonical (MK_SCREEN_FOLD).  ``info``, if given, receives the mk_screen_t fields."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, keep = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(keep == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        n, st = C.c_size_t(0), Screen()
+        self._check(self._L.mk_screen_text(self._h, addr, size, int(piece_bytes), SCREEN_FOLD if self._fold_flag(fold) else 0,
+                                           int(at_least), rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return rows[: n.value]
+
+    def screen_device(self, ptr: int, nbytes: int, out_ptr: int, cap: int, at_least: int = 1, fold: Optional[bool] = None) -> dict:
+        """mk_screen_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> rows of five uint64
+        (SCREEN_COLUMNS) at device address ``out_ptr`` with room for ``cap`` of them, both on this context's GPU.  Returns
+        the mk_screen_t fields; "records" is the number of rows written."""
+        n, st = C.c_size_t(0), Screen()
+        self._check(self._L.mk_screen_device(self._h, ptr, int(nbytes), SCREEN_FOLD if self._fold_flag(fold) else 0, int(at_least),
+                                             out_ptr, int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
 
     # -- results

@@ -125,6 +125,25 @@ def write_histo_tsv(counters: Dict[str, "native.Counter"], out_file, high: int =
     return text.count(b"\n") - 1
 
 
+def format_screen_tsv(names: Sequence[str], array) -> bytes:
+    """``record\twindows\thits\tsum\tmin\tmax``, then one line per record: its name and the five integers of its row
+    (kmers.screen_reads / Counter.screen)."""
+    if len(names) != len(array):
+        raise ValueError("format_screen_tsv: %d names for %d rows" % (len(names), len(array)))
+    out = [b"record\t" + "\t".join(native.SCREEN_COLUMNS).encode() + b"\n"]
+    for name, row in zip(names, array):
+        out.append(name.encode() + b"".join(b"\t%d" % int(v) for v in row) + b"\n")
+    return b"".join(out)
+
+
+def write_screen_tsv(path, names: Sequence[str], array) -> int:
+    """``format_screen_tsv`` written to ``path``; returns the number of records."""
+    text = format_screen_tsv(names, array)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
 def _first_header_field(path, shape: dict) -> Optional[str]:
     """The first field of a count table's header line (the combined table's first column title); None without one."""
     if not shape["header"]:
