@@ -555,6 +555,43 @@ int mk_write_tsv_multi(mk_ctx* const* ctxs, int n, const char* path, const char*
  * split over several GPUs -- and merged: the filter comes after the merge. */
 int mk_filter_min(mk_ctx* ctx, uint64_t min_count);
 
+/* ---- two tables combined by key on the GPU (KMC's `kmc_tools simple`, the Jellyfish merge variants): drop a sample's
+ *      k-mers that a background table holds, keep those a marker table holds, the shared k-mers with the smaller count,
+ *      one sample's counts minus another's -- one streaming read of a and one probe of b per row, nothing exported ----
+ * One rule defines every op.  For every key in a or b, ca and cb are its counts there, 0 where absent.  A count below
+ * min_a (respectively min_b) is first taken as 0.  dst receives the key with count f(ca, cb), and no row where that is
+ * 0; a SUM that wraps to 0 is therefore no row.  min_a, min_b >= 1: 0 is MK_ERR_ARG, and so is an unknown op.
+ * a and b are only READ, under mk_lookup's rules: made final first, a context that holds part of a refused chunk or an
+ * open chunk is MK_ERR_STATE, a sharer (mk_share_table) answers for its OWN tables, a repeated call gives the same
+ * result.  a == b is allowed.  dst is a third context (dst == a or dst == b: MK_ERR_ARG) of the same device, alphabet,
+ * k and canonical mode as a and b (else MK_ERR_ARG); a dst that shares or lends a table, or has an open chunk, is
+ * MK_ERR_STATE.  dst is emptied as mk_reset does, then filled; afterwards it is an ordinary context: the exports,
+ * mk_write_tsv, mk_lookup, mk_histo, mk_screen_*, mk_alpha_stats and further counting or loading into it all work.
+ * Keys are taken as they stand (no folding), as mk_load_tsv takes them.  Every table shape is combined on the GPU: dense
+ * bins elementwise, the one-word table (f of the two counts of the 32 x 'T' key kept beside it: on the host), the
+ * two-word tables, and the rows kept as text -- a's bytes from a's arena, probed in b's by-reference table, stored in
+ * dst's.  A packed row is probed only in b's packed table and a text row only in b's text table: where a key lives is
+ * decided by the key alone.  A table never allocated has no slots and answers 0.  All arithmetic is integer: the result
+ * is exact whatever the order.  When the call fails after dst was emptied, dst is left empty.  st may be NULL. */
+#define MK_OP_MIN   0  /* min(ca, cb): keys in both, the smaller count (KMC intersect)      */
+#define MK_OP_MAX   1  /* max(ca, cb): keys in either                                       */
+#define MK_OP_SUM   2  /* ca + cb modulo 2^64: keys in either (what mk_merge_from adds up)  */
+#define MK_OP_LEFT  3  /* cb ? ca : 0: a's rows whose key b holds, a's counts               */
+#define MK_OP_ONLY  4  /* cb ? 0 : ca: a's rows whose key b lacks (KMC kmers_subtract)      */
+#define MK_OP_DIFF  5  /* ca > cb ? ca - cb : 0 (KMC counters_subtract)                     */
+typedef struct mk_table_op_t {
+  uint64_t rows_a, rows_b;   /* rows of a / of b at or above their threshold                          */
+  uint64_t both;             /* keys so present in both                                               */
+  uint64_t rows_out;         /* rows of dst                                                           */
+  uint64_t total_out;        /* sum of their counts (modulo 2^64)                                     */
+  uint64_t packed_out, text_out; /* ... in the packed table / kept as text                            */
+  uint64_t slots;            /* table slots (dense bins) read                                         */
+  int32_t passes;            /* 1, or 2: MAX and SUM also probe a for every row of b                  */
+  int32_t op;
+  double s_scan, s_total;    /* seconds: HIP-event time of the kernels; wall time of the call         */
+} mk_table_op_t;
+int mk_table_op(mk_ctx* dst, mk_ctx* a, mk_ctx* b, int op, uint64_t min_a, uint64_t min_b, mk_table_op_t* st);
+
 /* ---- statistics / profiling ----------------------------------------------------------- */
 int mk_set_profiling(mk_ctx* ctx, int on);
 int mk_get_stats(mk_ctx* ctx, mk_stats_t* out);

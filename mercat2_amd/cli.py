@@ -19,7 +19,9 @@ more samples, report/diversity-<type>.tsv.  -query FILE writes query_<type>.tsv:
 sample, looked up in those tables (mk_lookup_file).  -histo [HIGH] writes every sample's abundance histogram
 (histo_<type>/<sample>_histo.txt, histo_<type>.tsv), reduced in those tables (mk_histo).  -screen FILE writes, for every
 sample of FILE's type, screen_<type>/<sample>_screen.tsv: per record of FILE its k-mers, how many of them the sample's table
-holds, and how abundant they are (mk_screen_text).  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
+holds, and how abundant they are (mk_screen_text).  -against FILE -op OP writes, for every sample of FILE's type,
+against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
+(mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -36,7 +38,10 @@ from . import __version__
 from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_background, removeN_text
 from .kmers import read_fasta_bytes
 from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_text
-from .report import merge_counters, merge_counters_T, write_histo_files, write_histo_tsv, write_query_tsv, write_screen_tsv
+from .report import (merge_counters, merge_counters_T, write_against_tsvs, write_histo_files, write_histo_tsv, write_query_tsv,
+                     write_screen_tsv)
+
+AGAINST_OPS = ("min", "max", "sum", "left", "only", "diff")  # native.OPS, for the parser (which loads no library)
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
 
@@ -70,6 +75,18 @@ def parseargs(argv=None):
                         "of them the sample holds at least -screen_min times (hits), and the sum, smallest and largest of "
                         "their counts; with -canonical the k-mers are folded")
     p.add_argument("-screen_min", type=int, default=1, metavar="N", help="-screen: a k-mer is a hit from this count on [1]")
+    p.add_argument("-against", type=str, required=False, metavar="FILE",
+                   help="a count table -- a counts TSV, or a Jellyfish / KMC dump -- of k-mer length -k to combine every sample "
+                        "with by key, in the tables on the GPU (needs -op): for every sample of FILE's type (nucleotide or "
+                        "protein, by its keys), against/tsv_<type>/<sample>_counts.tsv holds 'sample OP FILE', so that "
+                        "-tsv <out>/against feeds the result to a next run.  Keys are compared as they stand: with "
+                        "-canonical FILE must hold canonical keys")
+    p.add_argument("-op", type=str, required=False, choices=AGAINST_OPS,
+                   help="-against: per k-mer, with a the sample's count and b FILE's (0 where absent), the result holds min: "
+                        "min(a, b), the shared k-mers; max: max(a, b); sum: a + b; left: a where FILE holds the k-mer; only: a "
+                        "where FILE lacks it; diff: a - b where that is positive -- and no row where that is 0")
+    p.add_argument("-against_min", type=int, default=1, metavar="N",
+                   help="-against: a count of FILE below N is taken as absent [1]")
     p.add_argument("-k", type=int, required=True, help="kmer length")
     p.add_argument("-n", type=int, default=os.cpu_count() or 1,
                    help="no of cores [auto detect]: samples read (inflated) and counted concurrently, at most 8")
@@ -124,6 +141,26 @@ def parseargs(argv=None):
             p.error(f"-screen {args.screen}: the extension names neither a nucleotide, a protein nor a FASTQ file")
     if not 1 <= args.screen_min < 1 << 64:
         p.error(f"-screen_min {args.screen_min}: must be 1 or more")
+    args.against_kind = None
+    if args.op and not args.against:
+        p.error("-op needs -against FILE")
+    if args.against:
+        if not args.op:
+            p.error("-against needs -op {%s}" % ",".join(AGAINST_OPS))
+        if not os.path.isfile(args.against):
+            p.error(f"file '{args.against}' is not valid.\n")
+        if not 1 <= args.against_min < 1 << 64:
+            p.error(f"-against_min {args.against_min}: must be 1 or more")
+        from . import native
+        try:
+            shape = native.tsv_shape(args.against)
+        except native.MercatHipError as e:
+            p.error(f"-against {args.against}: {e}")
+        if shape["k"] != args.k:
+            p.error(f"-k {args.k}: '{args.against}' holds {shape['k']}-mers")
+        if shape["alphabet"] == native.ALPHABET_RAW:
+            p.error(f"-against {args.against}: its keys are neither nucleotide (ACGT) nor protein (A-Z) k-mers")
+        args.against_kind = "nucleotide" if shape["alphabet"] == native.ALPHABET_NT2 else "protein"
     args.loaded = {"nucleotide": {}, "protein": {}}  # sample -> its count table, per type (-tsv)
     for d in args.tsv:
         if not os.path.isdir(d):
@@ -471,6 +508,14 @@ def main(argv=None) -> int:
                         write_screen_tsv(out / f"screen_{kind}" / f"{base}_screen.tsv", names, rows)
                     print(f"screen_{kind}/: {len(names)} records of {os.path.basename(args.screen)} screened against "
                           f"{len(tables)} sample(s)")
+                if args.against and args.against_kind == kind:  # from the tables still on the GPU
+                    try:
+                        rows = write_against_tsvs({base: tables[base] for base in sorted(tables)}, args.against, args.op,
+                                                  out / "against" / f"tsv_{kind}", args.against_min)
+                    except native.MercatHipError as e:
+                        raise SystemExit(f"-against {args.against}: {e}")
+                    print(f"against/tsv_{kind}/: {len(tables)} sample(s) {args.op} {os.path.basename(args.against)}, "
+                          f"{sum(1 for n in rows.values() if n)} with rows left")
                 if args.histo is not None:  # from the tables still on the GPU
                     ordered = {base: tables[base] for base in sorted(tables)}
                     bins = write_histo_files(ordered, out / f"histo_{kind}", args.histo)

@@ -396,6 +396,10 @@ int mk_launch_import_ref(mk_ctx* c, const uint8_t* d_kmers, const uint64_t* d_co
 // two-word keys: survivors {hi, lo, count} per bucket region -> run128
 int mk_launch_import128_regions(mk_ctx* c, const uint64_t* hi, const uint64_t* lo, const uint64_t* cnts, const uint64_t* kstart,
                                 const uint64_t* nsurv, size_t p1);
+// mk_table_op: one scan of x's tables with y's probed, the rows into dst's (mk_setop_k); tallies per table in d_out
+enum { MK_SO_ROWS_A = 0, MK_SO_ROWS_B, MK_SO_BOTH, MK_SO_ROWS_OUT, MK_SO_TOTAL_OUT, MK_SO_WORDS = 8 };
+int mk_launch_setop(mk_ctx* dst, const mk_ctx* x, const mk_ctx* y, bool scan_b, int op, bool insert, uint64_t min_x, uint64_t min_y,
+                    uint64_t* d_out, uint64_t* slots);
 int mk_launch_refilter_dense(mk_ctx* c, uint64_t* bins, size_t nbins, uint64_t min_count);
 int mk_launch_compact128(mk_ctx* c, const MkSlot128* t, size_t slots, uint64_t* hi, uint64_t* lo, uint64_t* cnts, size_t cap,
                          uint64_t* d_cursor);

@@ -664,3 +664,150 @@ int mk_launch_alpha(mk_ctx* c, u64* d_out) {
     rc = launch(c, mk_alpha_k<View128>, grid_for(c->run128_slots, 256, 1024), View128{(const MkSlot128*)c->run128.p}, c->run128_slots, d_out);
   return rc;
 }
+
+// ------------------------------------------------------------------ two tables combined by key (mk_table_op)
+// f(ca, cb) of include/mercat_hip.h; op is uniform over the launch.
+__device__ __forceinline__ u64 setop_f(int op, u64 ca, u64 cb) {
+  switch (op) {
+    case MK_OP_MIN: return ca < cb ? ca : cb;
+    case MK_OP_MAX: return ca > cb ? ca : cb;
+    case MK_OP_SUM: return ca + cb;
+    case MK_OP_LEFT: return cb ? ca : 0;
+    case MK_OP_ONLY: return cb ? 0 : ca;
+    default: return ca > cb ? ca - cb : 0;  // MK_OP_DIFF
+  }
+}
+
+// ---- the OTHER table asked for the key a view hands out: probe(a, b) -> its count there, 0 when absent.  A table that
+// was never allocated has no slots and answers 0.  The inputs are final (lk_open): in the two-word table an all-ones
+// count word is a count.
+struct Probe64 {
+  const MkSlot* t;
+  u64 slots;
+  __device__ __forceinline__ u64 operator()(u64 key, u64) const { return slots ? find64(t, slots - 1, key) : 0; }
+};
+struct Probe128 {
+  const MkSlot128* t;
+  u64 slots;
+  __device__ __forceinline__ u64 operator()(u64 hi, u64 lo) const { return slots ? find128(t, slots - 1, hi, lo, nullptr) : 0; }
+};
+struct ProbeBins {
+  const u64* bins;
+  size_t nbins;
+  __device__ __forceinline__ u64 operator()(u64 bin, u64) const { return find_dense(bins, nbins, bin); }
+};
+// Rows kept as text: the view hands out the slot key (tag | arena row) of the table it walks; the row's k bytes, in
+// THAT table's arena (from), are what the other table is asked for and what the sink stores.
+struct ProbeRef {
+  const MkSlot* ref;
+  u64 slots;
+  const uint8_t *arena, *from;
+  int k;
+  __device__ __forceinline__ u64 operator()(u64 key, u64) const {
+    return slots ? find_ref_of(ref, slots - 1, arena, BytesAt{from + (key & REF_POS_MASK) * (u64)k}, k) : 0;
+  }
+};
+// Two-word keys that are distinct within the launch and new to the table: the first free slot from the key's home on
+// is claimed with the count, as the rebuild places a row (no key is compared, no slot waited for: upsert128 would take
+// a count of 2^64 - 1 in a slot on its way for MK_LOCK128 and spin).
+struct SinkPlace128 {
+  MkSlot128* run;
+  u64 mask;
+  __device__ __forceinline__ bool put(u64 hi, u64 lo, u64 cnt) const {
+    place(run, mask, home128(hi, lo, mask), hi, lo, cnt);
+    return true;
+  }
+};
+struct SinkRef {
+  MkSlot* run;
+  u64 mask;
+  uint8_t* arena;
+  const uint8_t* from;
+  int k;
+  u64* new_rows;  // (the arena's row cursor: the table was emptied, rows are handed out from 0)
+  __device__ __forceinline__ bool put(u64 key, u64, u64 cnt) const {
+    return upsert_ref(run, mask, arena, from + (key & REF_POS_MASK) * (u64)k, k, cnt, 0, new_rows);
+  }
+};
+
+// One table walked through its view (x), the other probed (y), f into the sink: the kernel of mk_table_op, once for
+// every table shape.  mk_import_k with a probe between the view and the sink, and with the call's five tallies, which
+// that kernel has no place for.
+//   SO_SCAN_A  x = a, y = b: every row of a at or above min_a; f(ca, cb) where that is not 0.
+//   SO_SCAN_B  x = b, y = a: the rows of b at or above min_b are counted; with `insert` (MAX, SUM: f(0, cb) != 0) a is
+//              probed and f(0, cb) goes in for the keys a lacks at or above min_a -- keys the first scan has not met.
+//              Without it nothing is probed: the scan only counts rows_b.
+//   SO_SCAN_AB dense bins, where slot i is the same key in both: one elementwise pass does all of it.
+// Keys coming out of one table are distinct, and those of SO_SCAN_B are distinct from those of SO_SCAN_A: the sinks
+// never add to a row, and whatever order the rows arrive in, the table's content is the same.
+enum { SO_SCAN_A = 0, SO_SCAN_B = 1, SO_SCAN_AB = 2 };
+template <int SCAN, class View, class Probe, class Sink>
+__global__ void mk_setop_k(View v, size_t n, Probe probe, Sink sink, int op, int insert, u64 min_x, u64 min_y,
+                           u64* __restrict__ out) {
+  u64 rows_x = 0, rows_y = 0, both = 0, rows_out = 0, total_out = 0;
+  mk_for_each(n, [&](size_t i) {
+    u64 a, b, cx;
+    if (!(SCAN == SO_SCAN_AB ? v.keyed(i, a, b, cx) : v.get(i, a, b, cx))) return;
+    if (cx < min_x) cx = 0;
+    if (SCAN != SO_SCAN_AB && !cx) return;
+    rows_x += cx ? 1 : 0;
+    if (SCAN == SO_SCAN_B && !insert) return;
+    u64 cy = probe(a, b);
+    if (cy < min_y) cy = 0;
+    if (SCAN == SO_SCAN_B && cy) return;  // (a holds it: the first scan has dealt with the key)
+    rows_y += cy ? 1 : 0;
+    both += (cx && cy) ? 1 : 0;
+    const u64 f = SCAN == SO_SCAN_B ? setop_f(op, 0, cx) : setop_f(op, cx, cy);
+    if (!f) return;
+    rows_out += 1;
+    total_out += f;
+    sink.put(a, b, f);
+  });
+  block_add(&out[SCAN == SO_SCAN_B ? MK_SO_ROWS_B : MK_SO_ROWS_A], rows_x);
+  if (SCAN == SO_SCAN_AB) block_add(&out[MK_SO_ROWS_B], rows_y);
+  if (SCAN != SO_SCAN_B) block_add(&out[MK_SO_BOTH], both);
+  block_add(&out[MK_SO_ROWS_OUT], rows_out);
+  block_add(&out[MK_SO_TOTAL_OUT], total_out);
+}
+
+template <int SCAN, class View, class Probe, class Sink>
+static int launch_setop(mk_ctx* dst, View v, size_t n, Probe probe, Sink sink, int op, bool insert, u64 min_x, u64 min_y, u64* d_out) {
+  return launch(dst, mk_setop_k<SCAN, View, Probe, Sink>, grid_for(n, 256, 8192), v, n, probe, sink, op, insert ? 1 : 0, min_x, min_y, d_out);
+}
+
+// One scan of mk_table_op on dst's stream: x's tables walked (scan_b: x is b, else a), y's probed, the rows into dst's
+// tables, which are empty or hold the first scan's rows and have room for every row this scan can add.  The packed
+// table's tallies go to d_out[0 .. MK_SO_WORDS), those of the rows kept as text to the MK_SO_WORDS words behind them;
+// *slots: table slots read.
+int mk_launch_setop(mk_ctx* dst, const mk_ctx* x, const mk_ctx* y, bool scan_b, int op, bool insert, uint64_t min_x, uint64_t min_y,
+                    uint64_t* d_out_, uint64_t* slots) {
+  u64* d_out = (u64*)d_out_;
+  MkChunkInfo* info = (MkChunkInfo*)dst->info.p;
+  int rc = MK_OK;
+#define SO_GO(VIEW, N, PROBE, SINK, OUT)                                                                                     \
+  do {                                                                                                                     \
+    rc = scan_b ? launch_setop<SO_SCAN_B>(dst, VIEW, N, PROBE, SINK, op, insert, min_x, min_y, OUT)                          \
+                : launch_setop<SO_SCAN_A>(dst, VIEW, N, PROBE, SINK, op, insert, min_x, min_y, OUT);                         \
+    *slots += N;                                                                                                           \
+  } while (0)
+  if (x->mode == MK_MODE_DENSE) {
+    if (!scan_b) {  // (the one elementwise pass)
+      rc = launch_setop<SO_SCAN_AB>(dst, ViewDense{(const u64*)x->run.p}, x->run_slots, ProbeBins{(const u64*)y->run.p, y->run_slots},
+                                    sink_bins(dst), op, true, min_x, min_y, d_out);
+      *slots += x->run_slots + y->run_slots;
+    }
+  } else if (x->mode == MK_MODE_HASH64 && x->run_slots) {
+    SO_GO(View64{(const MkSlot*)x->run.p}, x->run_slots, (Probe64{(const MkSlot*)y->run.p, (u64)y->run_slots}), sink64<true>(dst), d_out);
+  } else if (x->mode == MK_MODE_HASH128 && x->run128_slots) {
+    SO_GO(View128{(const MkSlot128*)x->run128.p}, x->run128_slots, (Probe128{(const MkSlot128*)y->run128.p, (u64)y->run128_slots}),
+          (SinkPlace128{(MkSlot128*)dst->run128.p, (u64)(dst->run128_slots - 1)}), d_out);
+  }
+  if (rc == MK_OK && x->run_ref_slots) {
+    const uint8_t* from = (const uint8_t*)x->arena.p;
+    const ProbeRef probe{(const MkSlot*)y->run_ref.p, (u64)y->run_ref_slots, (const uint8_t*)y->arena.p, from, x->k};
+    const SinkRef sink{(MkSlot*)dst->run_ref.p, (u64)(dst->run_ref_slots - 1), (uint8_t*)dst->arena.p, from, x->k, &info->new_rows_ref};
+    SO_GO(View64{(const MkSlot*)x->run_ref.p}, x->run_ref_slots, probe, sink, d_out + MK_SO_WORDS);
+  }
+#undef SO_GO
+  return rc;
+}

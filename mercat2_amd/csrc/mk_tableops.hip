@@ -1,7 +1,8 @@
 // mk_tableops.hip -- rows going INTO a running table from outside a chunk, and table-to-table operations: the imports
 // of the multi-GPU merge (mk_import_pairs_device, mk_import_exotic; their exports are in mk_export.hip), mk_filter_min,
-// mk_merge_from.  Host code only.
+// mk_merge_from, mk_table_op.  Host code only.
 #include "mk_common.h"
+#include <chrono>
 #include <cstring>
 
 typedef unsigned long long u64;
@@ -137,5 +138,100 @@ extern "C" int mk_merge_from(mk_ctx* dst, mk_ctx* src) {
     if ((rc = mk_export_exotic(src, km.data(), cn.data(), n, &n)) != MK_OK) { dst->err = src->err; return rc; }
     if ((rc = mk_import_exotic(dst, km.data(), cn.data(), n)) != MK_OK) return rc;
   }
+  return MK_OK;
+}
+
+// ------------------------------------------------------------------------------- two tables combined by key
+static u64 so_f(int op, u64 ca, u64 cb) {  // (setop_f of mk_table.hip, for the one key kept beside the one-word table)
+  switch (op) {
+    case MK_OP_MIN: return ca < cb ? ca : cb;
+    case MK_OP_MAX: return ca > cb ? ca : cb;
+    case MK_OP_SUM: return ca + cb;
+    case MK_OP_LEFT: return cb ? ca : 0;
+    case MK_OP_ONLY: return cb ? 0 : ca;
+    default: return ca > cb ? ca - cb : 0;
+  }
+}
+
+extern "C" int mk_table_op(mk_ctx* dst, mk_ctx* a, mk_ctx* b, int op, uint64_t min_a, uint64_t min_b, mk_table_op_t* st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!dst || !a || !b) return MK_ERR_ARG;
+  mk_ctx* c = dst;
+  if (dst == a || dst == b) { c->err = "mk_table_op: dst must be a third context"; return MK_ERR_ARG; }
+  if (op < MK_OP_MIN || op > MK_OP_DIFF) { c->err = "mk_table_op: unknown op"; return MK_ERR_ARG; }
+  if (!min_a || !min_b) { c->err = "mk_table_op: min_a and min_b are at least 1"; return MK_ERR_ARG; }
+  for (const mk_ctx* o : {a, b})
+    if (dst->device != o->device || dst->alphabet != o->alphabet || dst->k != o->k || dst->canonical != o->canonical) {
+      c->err = "mk_table_op: contexts differ in device, alphabet, k or canonical mode";
+      return MK_ERR_ARG;
+    }
+  if (dst->share_owner || dst->n_sharers) { c->err = "mk_table_op: dst shares or lends a table (mk_share_table)"; return MK_ERR_STATE; }
+  if (dst->in_chunk) { c->err = "mk_table_op: a chunk is open in dst"; return MK_ERR_STATE; }
+  int rc;
+  bool fold;
+  // the inputs as every read-only call opens them: not spoiled, no open chunk, made final, their streams drained
+  for (mk_ctx* o : {a, b})
+    if ((rc = lk_open(o, "mk_table_op", 0, &fold)) != MK_OK) { dst->err = o->err; return rc; }
+  if ((rc = mk_reset(dst)) != MK_OK) return rc;
+  const bool two = op == MK_OP_MAX || op == MK_OP_SUM;  // f(0, cb) != 0: b's own keys go in as well
+  // Room in dst for every row the scans can add, BEFORE the launches: nothing grows under a kernel.  (One more than
+  // the rows: a table with slots and no rows is still walked, and its sink wants a table.)
+  const size_t packed = (size_t)a->run_rows + a->run128_rows + (two ? (size_t)b->run_rows + b->run128_rows : 0);
+  const size_t text = a->run_ref_rows + (two ? b->run_ref_rows : 0);
+  if ((rc = mk_grow_run(dst, packed + 1)) != MK_OK) return rc;
+  if ((a->run_ref_slots || (two && b->run_ref_slots)) && (rc = mk_grow_run_ref(dst, text + 1)) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, c->ex_tmp, 2 * MK_SO_WORDS * sizeof(u64))) != MK_OK) return rc;
+  u64* d_out = (u64*)c->ex_tmp.p;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (auto& e : ev) MK_HIP(hipEventCreate(&e));
+  u64 h[2 * MK_SO_WORDS] = {0}, slots = 0;
+  float ms = 0.f;
+  rc = [&]() -> int {
+    MK_HIP(hipMemsetAsync(d_out, 0, sizeof h, c->stream));
+    MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
+    MK_HIP(hipEventRecord(ev[0], c->stream));
+    int r = mk_launch_setop(dst, a, b, false, op, true, min_a, min_b, (uint64_t*)d_out, (uint64_t*)&slots);
+    // (b is walked for the one-pass ops too, without a probe or an insert: rows_b is a figure of the call)
+    if (r == MK_OK) r = mk_launch_setop(dst, b, a, true, op, two, min_b, min_a, (uint64_t*)d_out, (uint64_t*)&slots);
+    if (r != MK_OK) return r;
+    MK_HIP(hipEventRecord(ev[1], c->stream));
+    MK_HIP(hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    const int r2 = mk_pull_info(dst);  // (the arena rows handed out; the stream is idle afterwards)
+    if (r2 != MK_OK) return r2;
+    MK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    return MK_OK;
+  }();
+  for (auto e : ev) (void)hipEventDestroy(e);
+  if (rc != MK_OK) { (void)hipStreamSynchronize(c->stream); (void)mk_reset(dst); return rc; }
+  const u64* ht = h + MK_SO_WORDS;  // the rows kept as text
+  if (c->h_info->new_rows_ref != ht[MK_SO_ROWS_OUT]) {
+    (void)mk_reset(dst);
+    c->err = "mk_table_op: the rows kept as text and their arena rows differ";
+    return MK_ERR_STATE;
+  }
+  // the one key kept beside the one-word table (32 x 'T'): f of the two side counts, as mk_histo adds it
+  u64 sa = 0, sb = 0, sf = 0;
+  if (dst->mode == MK_MODE_HASH64) {
+    sa = a->run_side >= min_a ? a->run_side : 0;
+    sb = b->run_side >= min_b ? b->run_side : 0;
+    sf = so_f(op, sa, sb);
+    dst->run_side = sf;
+  }
+  mk_add_packed_rows(dst, dst->mode == MK_MODE_DENSE ? 0 : (size_t)h[MK_SO_ROWS_OUT]);
+  dst->run_ref_rows = (size_t)ht[MK_SO_ROWS_OUT];
+  if (!st) return MK_OK;
+  memset(st, 0, sizeof *st);
+  st->rows_a = h[MK_SO_ROWS_A] + ht[MK_SO_ROWS_A] + (sa ? 1 : 0);
+  st->rows_b = h[MK_SO_ROWS_B] + ht[MK_SO_ROWS_B] + (sb ? 1 : 0);
+  st->both = h[MK_SO_BOTH] + ht[MK_SO_BOTH] + (sa && sb ? 1 : 0);
+  st->packed_out = h[MK_SO_ROWS_OUT] + (sf ? 1 : 0);
+  st->text_out = ht[MK_SO_ROWS_OUT];
+  st->rows_out = st->packed_out + st->text_out;
+  st->total_out = h[MK_SO_TOTAL_OUT] + ht[MK_SO_TOTAL_OUT] + sf;
+  st->slots = slots;
+  st->passes = two ? 2 : 1;
+  st->op = op;
+  st->s_scan = ms * 1e-3;
+  st->s_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return MK_OK;
 }

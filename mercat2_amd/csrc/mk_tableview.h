@@ -120,13 +120,14 @@ __device__ __forceinline__ u64 find64(const MkSlot* __restrict__ t, u64 mask, u6
   return find64_from(t, mask, key, find64_home(t, mask, key));
 }
 // Two-word table: the count word is the slot's state, 0 = free.  MK_LOCK128 cannot be met on a quiescent table:
-// *locked is set and the probe ends (a state error for the caller, not a spin).
+// *locked is set and the probe ends (a state error for the caller, not a spin).  locked == nullptr: the caller vouches
+// that the table is final, and an all-ones count word is what it can only be there, a count of 2^64 - 1 (mk_table_op).
 __device__ __forceinline__ u64 find128(const MkSlot128* __restrict__ t, u64 mask, u64 hi, u64 lo, bool* locked) {
   u64 slot = home128(hi, lo, mask);
   for (;;) {
     const ulonglong4 s = reinterpret_cast<const ulonglong4*>(t)[slot];
     if (s.z == 0) return 0;
-    if (s.z == MK_LOCK128) { *locked = true; return 0; }
+    if (s.z == MK_LOCK128 && locked) { *locked = true; return 0; }
     if (s.x == hi && s.y == lo) return s.z;
     slot = (slot + 1) & mask;
   }

@@ -35,12 +35,15 @@ ABI_SYMBOLS = [
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
-    "mk_screen_text", "mk_screen_device",
+    "mk_screen_text", "mk_screen_device", "mk_table_op",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
 LOOKUP_FOLD = 1
 SCREEN_FOLD = 1
+# mk_table_op: f(ca, cb) per key (include/mercat_hip.h)
+OP_MIN, OP_MAX, OP_SUM, OP_LEFT, OP_ONLY, OP_DIFF = range(6)
+OPS = {"min": OP_MIN, "max": OP_MAX, "sum": OP_SUM, "left": OP_LEFT, "only": OP_ONLY, "diff": OP_DIFF}
 SCREEN_COLUMNS = ("windows", "hits", "sum", "min", "max")  # mk_screen_row_t: the columns of Counter.screen's array
 
 
@@ -131,6 +134,16 @@ class Screen(C.Structure):
 class Histo(C.Structure):
     """mk_histo_t (include/mercat_hip.h)."""
     _fields_ = ([(n, C.c_uint64) for n in ("distinct", "total", "max_count", "over_rows", "over_total", "slots")] +
+                [(n, C.c_double) for n in ("s_scan", "s_total")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TableOp(C.Structure):
+    """mk_table_op_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("rows_a", "rows_b", "both", "rows_out", "total_out", "packed_out", "text_out", "slots")] +
+                [("passes", C.c_int32), ("op", C.c_int32)] +
                 [(n, C.c_double) for n in ("s_scan", "s_total")])
 
     def as_dict(self):
@@ -267,6 +280,7 @@ def lib() -> C.CDLL:
         "mk_screen_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp,
                                      C.POINTER(Screen)]),
         "mk_screen_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp, C.POINTER(Screen)]),
+        "mk_table_op": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(TableOp)]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -1034,6 +1048,32 @@ class Counter:
     def merge_from(self, other: "Counter"):
         """Add every row of ``other`` (same GPU, alphabet, k) into this context, on the device."""
         self._check(self._L.mk_merge_from(self._h, other._h))
+
+    def combine(self, other: "Counter", op, min_self: int = 1, min_other: int = 1, into: Optional["Counter"] = None,
+                info: Optional[dict] = None) -> "Counter":
+        """mk_table_op: this table and ``other``'s combined by key on the GPU.  For every key of either, with ca / cb its
+        count here / there (0 where absent, and where below ``min_self`` / ``min_other``), the result holds f(ca, cb)
+        where that is not 0: ``op`` "min" (keys in both, the smaller count), "max", "sum", "left" (this table's rows
+        whose key ``other`` holds), "only" (those it lacks), "diff" (ca - cb where positive) -- a name of OPS or its
+        code.  Keys are compared as they stand.  Both inputs are only read (``other`` may be ``self``).  Returns
+        ``into`` -- a third context of the same k, alphabet, device and canonical mode, emptied first -- or a new
+        Counter of that kind, which the caller closes.  ``info``, if given, receives the mk_table_op_t fields."""
+        if isinstance(op, str):
+            if op not in OPS:
+                raise ValueError("combine: op must be one of %s" % ", ".join(OPS))
+            op = OPS[op]
+        dst = into if into is not None else Counter(self.k, self.alphabet, self.device, canonical=self.canonical)
+        st = TableOp()
+        rc = self._L.mk_table_op(dst._h, self._h, other._h, int(op), int(min_self), int(min_other), C.byref(st))
+        if rc:
+            try:
+                dst._check(rc)
+            finally:
+                if into is None:
+                    dst.close()
+        if info is not None:
+            info.update(st.as_dict())
+        return dst
 
     def share_table(self, owner: Optional["Counter"]):
         """From now on this context's count kernels put the survivors of its chunks into ``owner``'s running table (same

@@ -144,6 +144,33 @@ def write_screen_tsv(path, names: Sequence[str], array) -> int:
     return len(names)
 
 
+def write_against_tsvs(tables: Dict[str, "native.Counter"], against, op, out_dir, min_other: int = 1) -> Dict[str, int]:
+    """For every sample of ``{sample name: Counter}``, ``sample op against`` (Counter.combine, keys compared as they
+    stand) written as ``out_dir/<sample>_counts.tsv`` with Counter.write_tsv; a sample whose result is empty writes no
+    file, as everywhere.  ``against``: a Counter, or the path of a counts TSV (a Jellyfish / KMC dump) of the samples'
+    k-mer length, which is loaded once per device the tables are on.  A count of ``against`` below ``min_other`` is
+    taken as absent.  Returns {sample name: rows of its result}."""
+    os.makedirs(out_dir, exist_ok=True)
+    loaded = {}  # device -> the background table there
+    rows = {}
+    try:
+        for name, table in tables.items():
+            other = against
+            if not isinstance(against, native.Counter):
+                if table.device not in loaded:
+                    loaded[table.device] = native.Counter(table.k, table.alphabet, table.device, canonical=table.canonical)
+                    loaded[table.device].load_tsv(against)
+                other = loaded[table.device]
+            with table.combine(other, op, 1, min_other) as result:
+                rows[name] = result.rows()
+                if rows[name]:
+                    result.write_tsv(os.path.join(out_dir, f"{name}_counts.tsv"), name)
+    finally:
+        for c in loaded.values():
+            c.close()
+    return rows
+
+
 def _first_header_field(path, shape: dict) -> Optional[str]:
     """The first field of a count table's header line (the combined table's first column title); None without one."""
     if not shape["header"]:
