@@ -135,6 +135,26 @@ int mk_refuse_spoiled(mk_ctx* c, const char* what) {
   return MK_ERR_STATE;
 }
 
+// How every read-only call on the tables opens (mk_lookup*, mk_screen*, the inputs of mk_table_op): the arguments, then
+// the table made final as mk_export_size makes it (pending row totals folded, read-backs landed) and the context's
+// stream drained.  (MK_SCREEN_FOLD is MK_LOOKUP_FOLD.)
+int lk_open(mk_ctx* c, const char* what, unsigned flags, bool* fold) {
+  MK_REFUSE_SPOILED(c, what);
+  if (c->in_chunk) { c->err = std::string(what) + ": a chunk is open"; return MK_ERR_STATE; }
+  if (flags & ~MK_LOOKUP_FOLD) { c->err = std::string(what) + ": unknown flag"; return MK_ERR_ARG; }
+  *fold = (flags & MK_LOOKUP_FOLD) != 0;
+  if (*fold && !(c->canonical && c->alphabet == MK_ALPHABET_NT2 && c->k <= 64)) {
+    c->err = std::string(what) + ": MK_LOOKUP_FOLD takes a canonical nucleotide context with k <= 64";
+    return MK_ERR_ARG;
+  }
+  size_t rows = 0;
+  const int rc = mk_export_size(c, &rows);
+  if (rc != MK_OK) return rc;
+  MK_HIP(hipSetDevice(c->device));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  return MK_OK;
+}
+
 extern "C" int mk_create(int device, int alphabet, int k, mk_ctx** out) {
   if (!out) { g_err = "mk_create: out is NULL"; return MK_ERR_ARG; }
   *out = nullptr;

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <string>
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include <shared_mutex>
 #include <vector>
@@ -93,6 +94,10 @@ struct MkDevBuf {
   size_t cap = 0;
 };
 
+// Wall-clock seconds since t0 = MkClock::now(): the s_total / s_read figures of the read-only calls.
+typedef std::chrono::steady_clock MkClock;
+static inline double mk_since(MkClock::time_point t0) { return std::chrono::duration<double>(MkClock::now() - t0).count(); }
+
 struct mk_ctx;
 // ---- host plumbing shared by the host-only files (mk_api / mk_chunk / mk_export / mk_combine / mk_tableops / mk_multi) ----
 // mk_api.hip: growable device buffers
@@ -117,8 +122,8 @@ int mk_grow_run128(mk_ctx* c, size_t need_rows);
 int mk_grow_run_ref(mk_ctx* c, size_t need_rows);
 int mk_grow_run(mk_ctx* c, size_t more_rows);
 
-// mk_lookup.hip: how a read-only call on the tables opens (mk_lookup*, mk_screen*): the arguments, then the table made
-// final and the context's stream drained; *fold = the fold flag was given (and may be)
+// mk_api.hip: how a read-only call on the tables opens (mk_lookup*, mk_screen*, the inputs of mk_table_op): the
+// arguments, then the table made final and the context's stream drained; *fold = the fold flag was given (and may be)
 int lk_open(mk_ctx* c, const char* what, unsigned flags, bool* fold);
 
 struct MkEventPair {
@@ -248,6 +253,37 @@ struct mk_ctx {
       return MK_ERR_HIP;                                                                     \
     }                                                                                        \
   } while (0)
+
+// A section of the context's stream timed by a pair of events (the s_probe / s_scan / s_parse figures of the read-only
+// calls): begin(), the launches, end(), the caller's read-backs and its sync, then add_to().  The events die with it,
+// on every path.
+struct MkTimed {
+  mk_ctx* c;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  explicit MkTimed(mk_ctx* c_) : c(c_) {}
+  MkTimed(const MkTimed&) = delete;
+  MkTimed& operator=(const MkTimed&) = delete;
+  ~MkTimed() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int begin() {
+    for (auto& e : ev)
+      if (!e) MK_HIP(hipEventCreate(&e));
+    MK_HIP(hipEventRecord(ev[0], c->stream));
+    return MK_OK;
+  }
+  int end() {
+    MK_HIP(hipEventRecord(ev[1], c->stream));
+    return MK_OK;
+  }
+  int add_to(double& seconds) {  // (once the stream has passed end())
+    float ms = 0.f;
+    MK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    seconds += ms * 1e-3;
+    return MK_OK;
+  }
+};
 
 // How an ABI entry point opens: refuse a spoiled context, fold pending row totals.  Both return from the caller.
 #define MK_REFUSE_SPOILED(c, what)                                                           \

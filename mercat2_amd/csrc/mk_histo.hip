@@ -1,17 +1,16 @@
 // mk_histo.hip -- the abundance spectrum of the table a context holds (mk_histo*, include/mercat_hip.h): how many
 // distinct k-mers occur once, twice, ... `high` times, and how many more often (what Jellyfish calls `histo`).
 //
-// One kernel template over the slot views of mk_tableview.h, one launch per table the context holds, chosen as
-// mk_launch_alpha chooses them; the one key kept beside the one-word table (run_side) is added by the host.  The same
-// pass reduces the rows, the sum of the counts, the largest count and the sum of the counts above `high`.  Everything is
-// an integer add: the result is exact and does not depend on the order of the slots or of the workgroups.
+// One kernel template over the slot views of mk_tableview.h, one launch per table the context holds (mk_each_table);
+// the one key kept beside the one-word table (run_side) is added by the host.  The same pass reduces the rows, the sum
+// of the counts, the largest count and the sum of the counts above `high`.  Everything is an integer add: the result is
+// exact and does not depend on the order of the slots or of the workgroups.
 //
 // Where the bins live.  A k-mer spectrum is skewed: nearly every row of a shallow sample has count 1, most rows of a deep
 // one sit within a few bins of the coverage peak.  The low HS_WINDOW bins are private to the workgroup, u32 words in
 // LDS, and only those that are not zero are added to the global bins when the workgroup ends; counts from HS_WINDOW up to
 // `high` are rare and go to the global bins at once; counts above `high` are counted in registers.
 #include "mk_tableview.h"
-#include <chrono>
 #include <string.h>
 
 // Low bins a workgroup keeps in LDS.  8 KiB a workgroup: the eight workgroups of 256 threads a CU can hold take 64 of its
@@ -71,32 +70,14 @@ __global__ __launch_bounds__(256) void hs_scan_k(View v, size_t n, u64 high, u64
 }
 
 // ------------------------------------------------------------------------------------------ host side
-template <class View>
-static int hs_launch(mk_ctx* c, View v, size_t slots, u64 high, u64* d_bins, u64* d_out) {
-  hipLaunchKernelGGL(hs_scan_k<View>, dim3(grid_for(slots, 256, HS_GRID)), dim3(256), 0, c->stream, v, slots, high, d_bins, d_out);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-// The tables of the context, as mk_launch_alpha walks them; *slots: table slots read.
+// Every table of the context; *slots: table slots read.
 static int hs_launch_all(mk_ctx* c, u64 high, u64* d_bins, u64* d_out, u64* slots) {
-  int rc = MK_OK;
-  if (c->mode == MK_MODE_DENSE) {
-    rc = hs_launch(c, ViewDense{(const u64*)c->run.p}, c->run_slots, high, d_bins, d_out);
-    *slots += c->run_slots;
-  } else if (c->run_slots) {
-    rc = hs_launch(c, View64{(const MkSlot*)c->run.p}, c->run_slots, high, d_bins, d_out);
-    *slots += c->run_slots;
-  }
-  if (rc == MK_OK && c->run_ref_slots) {
-    rc = hs_launch(c, View64{(const MkSlot*)c->run_ref.p}, c->run_ref_slots, high, d_bins, d_out);
-    *slots += c->run_ref_slots;
-  }
-  if (rc == MK_OK && c->run128_slots) {
-    rc = hs_launch(c, View128{(const MkSlot128*)c->run128.p}, c->run128_slots, high, d_bins, d_out);
-    *slots += c->run128_slots;
-  }
-  return rc;
+  return mk_each_table(c, [&](auto v, size_t n, int) -> int {
+    hipLaunchKernelGGL(hs_scan_k<decltype(v)>, dim3(grid_for(n, 256, HS_GRID)), dim3(256), 0, c->stream, v, n, high, d_bins, d_out);
+    MK_HIP(hipGetLastError());
+    *slots += n;
+    return MK_OK;
+  });
 }
 
 #define HS_MAX_HIGH ((uint64_t)1 << 20)
@@ -104,7 +85,7 @@ static int hs_launch_all(mk_ctx* c, u64 high, u64* d_bins, u64* d_out, u64* slot
 // The histogram into d_bins (device memory of the context's GPU), or with d_bins == NULL into the context's scratch and
 // from there into h_bins.
 static int hs_run(mk_ctx* c, const char* what, uint64_t high, u64* d_bins, uint64_t* h_bins, mk_histo_t* st) {
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = MkClock::now();
   MK_REFUSE_SPOILED(c, what);
   if (c->in_chunk) { c->err = std::string(what) + ": a chunk is open"; return MK_ERR_STATE; }
   if (high < 1 || high > HS_MAX_HIGH) { c->err = std::string(what) + ": high must lie in 1 .. 2^20"; return MK_ERR_ARG; }
@@ -116,28 +97,24 @@ static int hs_run(mk_ctx* c, const char* what, uint64_t high, u64* d_bins, uint6
   if ((rc = mk_buf_reserve(c, c->ex_tmp, (HS_WORDS + (d_bins ? 0 : words)) * sizeof(u64))) != MK_OK) return rc;
   u64* d_out = (u64*)c->ex_tmp.p;
   if (!d_bins) d_bins = d_out + HS_WORDS;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto& e : ev) MK_HIP(hipEventCreate(&e));
+  MkTimed scan(c);
   u64 h[HS_WORDS] = {0}, slots = 0;
-  float ms = 0.f;
+  double s_scan = 0;
   const u64 side = c->run_side;  // the one key kept beside the one-word table (32 x 'T')
   rc = [&]() -> int {
+    int r;
     MK_HIP(hipMemsetAsync(d_out, 0, HS_WORDS * sizeof(u64), c->stream));
     MK_HIP(hipMemsetAsync(d_bins, 0, words * sizeof(u64), c->stream));
     // (its row: the low half of a cleared bin set to 1, ahead of the kernels' adds)
     if (side) MK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_bins + (side > high ? high + 1 : side)), 1, 1, c->stream));
-    MK_HIP(hipEventRecord(ev[0], c->stream));
-    const int r = hs_launch_all(c, high, d_bins, d_out, &slots);
-    if (r != MK_OK) return r;
-    MK_HIP(hipEventRecord(ev[1], c->stream));
+    if ((r = scan.begin()) != MK_OK || (r = hs_launch_all(c, high, d_bins, d_out, &slots)) != MK_OK || (r = scan.end()) != MK_OK)
+      return r;
     MK_HIP(hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
     if (h_bins) MK_HIP(hipMemcpyAsync(h_bins, d_bins, words * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));
-    MK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    return MK_OK;
+    return scan.add_to(s_scan);
   }();
-  for (auto e : ev) (void)hipEventDestroy(e);
-  if (rc != MK_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  if (rc != MK_OK) { (void)hipStreamSynchronize(c->stream); return rc; }  // (nothing of the call is left in flight)
   if (!st) return MK_OK;
   memset(st, 0, sizeof *st);
   st->distinct = h[HS_ROWS] + (side ? 1 : 0);
@@ -146,8 +123,8 @@ static int hs_run(mk_ctx* c, const char* what, uint64_t high, u64* d_bins, uint6
   st->over_rows = h[HS_OVER_ROWS] + (side > high ? 1 : 0);
   st->over_total = h[HS_OVER_TOTAL] + (side > high ? side : 0);
   st->slots = slots;
-  st->s_scan = ms * 1e-3;
-  st->s_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st->s_scan = s_scan;
+  st->s_total = mk_since(t0);
   return MK_OK;
 }
 

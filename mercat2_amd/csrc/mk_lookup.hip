@@ -4,29 +4,17 @@
 // table the context holds?  One kernel serves the contiguous form (row i starts at i * k) and the line form (a panel in
 // text form, one key a line, its starts from the loader's line-start passes): per key it validates the row, classifies
 // and packs the key as counting and mk_load_tsv place it (tl_pack_key), folds it onto its reverse complement if asked,
-// probes the one table the key can live in (find64 / find128 / find_ref_of / find_dense, mk_tableview.h) and writes
-// counts[row].  No lists, no ranks: order is the row index.  The text form travels through the loader's piece pipeline
+// probes the one table the key can live in (LkStep, mk_tableview.h) and writes counts[row].  No lists, no ranks: order is the row index.  The text form travels through the loader's piece pipeline
 // (TlPieces, mk_tsvpieces.h) with the probe as the last stage of a piece where the loader has its import.
 #include "mk_tsvpieces.h"
 #include "mk_tableview.h"
 #include <algorithm>
-#include <chrono>
-
-typedef std::chrono::steady_clock LkClk;
-static double lk_since(LkClk::time_point t0) { return std::chrono::duration<double>(LkClk::now() - t0).count(); }
-
-// A probe is a dependent random 16-byte read: a lane that looks one key up after the other waits a full trip to HBM per
-// key.  PER keys a lane: the home-slot loads of all of them are issued before any is compared (one-word table).
-// (A/B builds: -DLK_PER=1 is the one-key-a-lane form tools/lookup_probe.py's figures are compared with.)
-#ifndef LK_PER
-#define LK_PER 4
-#endif
 
 // LINES: row i is line i of a piece (line_start from tl_emit_k; rows = the lines looked at, at most cap), a key and
 // then nothing or "\t<count>"; else row i is the k bytes at i * k and there are `rows` of them.
-template <int KEYS, bool LINES, int PER>
+template <int KEYS, bool FOLD, bool LINES, int PER>
 __global__ void __launch_bounds__(256) lk_probe_k(const uint8_t* __restrict__ text, const unsigned* __restrict__ line_start,
-                                                  u64 rows, unsigned cap, int k, int bits, int fold, LkTables t,
+                                                  u64 rows, unsigned cap, int k, int bits, LkTables t,
                                                   u64* __restrict__ counts, TlStatus* __restrict__ st) {
   u64 n = rows;
   if (LINES) {
@@ -34,16 +22,13 @@ __global__ void __launch_bounds__(256) lk_probe_k(const uint8_t* __restrict__ te
     n = lines < (u64)cap ? lines : (u64)cap;
   }
   u64 found = 0, packed = 0, textk = 0, folded = 0;
+  LkStep<KEYS, PER> p;
   const u64 stride = (u64)gridDim.x * 256u;
   for (u64 first = (u64)blockIdx.x * 256u + threadIdx.x; first < n; first += stride * PER) {
-    u64 key[PER], res[PER];
-    ulonglong2 home[PER];
-    bool pending[PER];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const u64 i = first + (u64)j * stride;
-      pending[j] = false;
-      res[j] = 0;
+      p.clear(j);
       if (i >= n) continue;
       size_t s = (size_t)i * (size_t)k;
       bool ok = true;
@@ -63,47 +48,27 @@ __global__ void __launch_bounds__(256) lk_probe_k(const uint8_t* __restrict__ te
       u64 a, b;
       if (tl_pack_key<KEYS>(text + s, k, bits, a, b)) {
         ++packed;
-        if (fold) {
-          bool turned;
-          if (KEYS == TL_TWO_WORD_NT) turned = mk_canon128(a, b, k);
-          else {
-            const u64 rc = mk_revcomp2(a, k);
-            turned = rc < a;
-            if (turned) a = rc;
-          }
-          folded += turned ? 1 : 0;
-        }
-        if (KEYS == TL_ONE_WORD) {
-          if (t.bins) res[j] = find_dense(t.bins, (size_t)t.nbins, a);
-          else if (a == MK_EMPTY) res[j] = t.side;
-          else if (t.run_slots) {
-            key[j] = a;
-            home[j] = find64_home(t.run, t.run_slots - 1, a);
-            pending[j] = true;
-          }
-        } else if (KEYS != TL_TEXT_ONLY && t.run128_slots) {
-          bool locked = false;
-          res[j] = find128(t.run128, t.run128_slots - 1, a, b, &locked);
-          if (locked) atomicAdd(&st->locked, 1ull);  // (cannot happen on a quiescent table)
-        }
+        if (FOLD) folded += p.fold(a, b, k) ? 1 : 0;
+        p.issue(j, t, a, b);
       } else {
         ++textk;
-        if (t.ref_slots) res[j] = find_ref_of(t.ref, t.ref_slots - 1, t.arena, BytesAt{text + s}, k);
+        p.issue(j, t, BytesAt{text + s}, k);
       }
     }
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const u64 i = first + (u64)j * stride;
       if (i >= n) continue;
-      if (pending[j]) res[j] = find64_from(t.run, t.run_slots - 1, key[j], home[j]);
-      found += res[j] ? 1 : 0;
-      counts[i] = res[j];
+      const u64 cnt = p.finish(j, t);
+      found += cnt ? 1 : 0;
+      counts[i] = cnt;
     }
   }
   block_add(&st->found, found);
   block_add(&st->packed, packed);
   block_add(&st->text, textk);
   block_add(&st->folded, folded);
+  if (p.locked) atomicAdd(&st->locked, 1ull);  // (cannot happen on a quiescent table)
 }
 
 // ------------------------------------------------------------------------------------------ host side
@@ -113,36 +78,17 @@ static int lk_launch(mk_ctx* c, const uint8_t* d_text, const unsigned* line_star
   const LkTables t = lk_tables(c);
   const int keys = tl_keys_of(c);
   const unsigned grid = grid_for(div_up(line_start ? (size_t)cap : (size_t)rows, LK_PER), 256, 8192);
-#define LK_GO(K, L) hipLaunchKernelGGL((lk_probe_k<K, L, LK_PER>), dim3(grid), dim3(256), 0, c->stream, d_text, line_start, rows, cap, \
-                                       c->k, c->bits, fold ? 1 : 0, t, d_counts, d_st)
-#define LK_FORM(K) do { if (line_start) LK_GO(K, true); else LK_GO(K, false); } while (0)
-  if (keys == TL_ONE_WORD) LK_FORM(TL_ONE_WORD);
-  else if (keys == TL_TWO_WORD_NT) LK_FORM(TL_TWO_WORD_NT);
-  else if (keys == TL_TWO_WORD_AA) LK_FORM(TL_TWO_WORD_AA);
-  else LK_FORM(TL_TEXT_ONLY);
+#define LK_GO(K, F, L) hipLaunchKernelGGL((lk_probe_k<K, F, L, LK_PER>), dim3(grid), dim3(256), 0, c->stream, d_text, line_start, rows, \
+                                          cap, c->k, c->bits, t, d_counts, d_st)
+#define LK_FORM(K, F) do { if (line_start) LK_GO(K, F, true); else LK_GO(K, F, false); } while (0)
+  // (lk_open: only nucleotide keys of one or two words fold)
+  if (keys == TL_ONE_WORD) { if (fold) LK_FORM(TL_ONE_WORD, true); else LK_FORM(TL_ONE_WORD, false); }
+  else if (keys == TL_TWO_WORD_NT) { if (fold) LK_FORM(TL_TWO_WORD_NT, true); else LK_FORM(TL_TWO_WORD_NT, false); }
+  else if (keys == TL_TWO_WORD_AA) LK_FORM(TL_TWO_WORD_AA, false);
+  else LK_FORM(TL_TEXT_ONLY, false);
 #undef LK_FORM
 #undef LK_GO
   MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-// How every lookup opens: the arguments, then the table made final as mk_export_size makes it (pending row totals
-// folded, read-backs landed) and the context's stream drained.  (mk_screen.hip opens the same way: MK_SCREEN_FOLD is
-// MK_LOOKUP_FOLD.)
-int lk_open(mk_ctx* c, const char* what, unsigned flags, bool* fold) {
-  MK_REFUSE_SPOILED(c, what);
-  if (c->in_chunk) { c->err = std::string(what) + ": a chunk is open"; return MK_ERR_STATE; }
-  if (flags & ~MK_LOOKUP_FOLD) { c->err = std::string(what) + ": unknown flag"; return MK_ERR_ARG; }
-  *fold = (flags & MK_LOOKUP_FOLD) != 0;
-  if (*fold && !(c->canonical && c->alphabet == MK_ALPHABET_NT2 && c->k <= 64)) {
-    c->err = std::string(what) + ": MK_LOOKUP_FOLD takes a canonical nucleotide context with k <= 64";
-    return MK_ERR_ARG;
-  }
-  size_t rows = 0;
-  const int rc = mk_export_size(c, &rows);
-  if (rc != MK_OK) return rc;
-  MK_HIP(hipSetDevice(c->device));
-  MK_HIP(hipStreamSynchronize(c->stream));
   return MK_OK;
 }
 
@@ -158,24 +104,15 @@ static int lk_rows(mk_ctx* c, const char* what, const uint8_t* d_kmers, size_t r
   int rc;
   if ((rc = mk_buf_reserve(c, c->ex_tmp, sizeof(TlStatus))) != MK_OK) return rc;
   TlStatus* d_st = (TlStatus*)c->ex_tmp.p;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto& e : ev) MK_HIP(hipEventCreate(&e));
+  MkTimed probe(c);
   TlStatus h{};
-  float ms = 0.f;
-  rc = [&]() -> int {
-    MK_HIP(hipMemsetAsync(d_st, 0xFF, 16, c->stream));
-    MK_HIP(hipMemsetAsync((char*)d_st + 16, 0, sizeof(TlStatus) - 16, c->stream));
-    MK_HIP(hipEventRecord(ev[0], c->stream));
-    const int r = lk_launch(c, d_kmers, nullptr, (u64)rows, 0, fold, d_counts, d_st);
-    if (r != MK_OK) return r;
-    MK_HIP(hipEventRecord(ev[1], c->stream));
-    MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    MK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    return MK_OK;
-  }();
-  for (auto e : ev) (void)hipEventDestroy(e);
-  if (rc != MK_OK) return rc;
+  MK_HIP(hipMemsetAsync(d_st, 0xFF, 16, c->stream));
+  MK_HIP(hipMemsetAsync((char*)d_st + 16, 0, sizeof(TlStatus) - 16, c->stream));
+  if ((rc = probe.begin()) != MK_OK || (rc = lk_launch(c, d_kmers, nullptr, (u64)rows, 0, fold, d_counts, d_st)) != MK_OK ||
+      (rc = probe.end()) != MK_OK)
+    return rc;
+  MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
   if (h.bad_byte != ~0ull) {
     c->err = std::string(what) + ": key " + std::to_string(first_key + h.bad_byte) + " holds a byte >= 0x80 (only ASCII keys are counted)";
     return MK_ERR_NON_ASCII;
@@ -186,20 +123,19 @@ static int lk_rows(mk_ctx* c, const char* what, const uint8_t* d_kmers, size_t r
   out.packed_keys += h.packed;
   out.text_keys += h.text;
   out.folded += h.folded;
-  out.s_probe += ms * 1e-3;
-  return MK_OK;
+  return probe.add_to(out.s_probe);
 }
 
 extern "C" int mk_lookup_device(mk_ctx* c, const uint8_t* d_kmers, size_t rows, unsigned flags, uint64_t* d_counts, mk_lookup_t* st) {
   if (!c) return MK_ERR_ARG;
-  const auto t0 = LkClk::now();
+  const auto t0 = MkClock::now();
   if (rows && (!d_kmers || !d_counts)) { c->err = "mk_lookup_device: NULL buffer"; return MK_ERR_ARG; }
   bool fold = false;
   int rc = lk_open(c, "mk_lookup_device", flags, &fold);
   if (rc != MK_OK) return rc;
   mk_lookup_t out{};
   if (rows && (rc = lk_rows(c, "mk_lookup_device", d_kmers, rows, 0, fold, (u64*)d_counts, out)) != MK_OK) return rc;
-  out.s_total = lk_since(t0);
+  out.s_total = mk_since(t0);
   if (st) *st = out;
   return MK_OK;
 }
@@ -208,7 +144,7 @@ extern "C" int mk_lookup_device(mk_ctx* c, const uint8_t* d_kmers, size_t rows, 
 #define LK_BATCH ((size_t)64 << 20)
 extern "C" int mk_lookup(mk_ctx* c, const uint8_t* kmers, size_t rows, unsigned flags, uint64_t* counts, mk_lookup_t* st) {
   if (!c) return MK_ERR_ARG;
-  const auto t0 = LkClk::now();
+  const auto t0 = MkClock::now();
   if (rows && (!kmers || !counts)) { c->err = "mk_lookup: NULL buffer"; return MK_ERR_ARG; }
   bool fold = false;
   int rc = lk_open(c, "mk_lookup", flags, &fold);
@@ -222,9 +158,9 @@ extern "C" int mk_lookup(mk_ctx* c, const uint8_t* kmers, size_t rows, unsigned 
     if ((r = mk_buf_reserve(c, d_keys, per * k)) != MK_OK || (r = mk_buf_reserve(c, d_cnts, per * 8)) != MK_OK) return r;
     for (size_t at = 0; at < rows; at += per) {
       const size_t n = std::min(per, rows - at);
-      const auto t1 = LkClk::now();
+      const auto t1 = MkClock::now();
       MK_HIP(hipMemcpyAsync(d_keys.p, kmers + at * k, n * k, hipMemcpyHostToDevice, c->stream));
-      out.s_read += lk_since(t1);
+      out.s_read += mk_since(t1);
       if ((r = lk_rows(c, "mk_lookup", (const uint8_t*)d_keys.p, n, at, fold, (u64*)d_cnts.p, out)) != MK_OK) return r;
       MK_HIP(hipMemcpyAsync(counts + at, d_cnts.p, n * 8, hipMemcpyDeviceToHost, c->stream));
       MK_HIP(hipStreamSynchronize(c->stream));
@@ -235,7 +171,7 @@ extern "C" int mk_lookup(mk_ctx* c, const uint8_t* kmers, size_t rows, unsigned 
   buf_free(d_keys);
   buf_free(d_cnts);
   if (rc != MK_OK) return rc;
-  out.s_total = lk_since(t0);
+  out.s_total = mk_since(t0);
   if (st) *st = out;
   return MK_OK;
 }
@@ -283,7 +219,7 @@ struct LkText : TlPieces {
 
 static int lk_text(mk_ctx* c, const char* what, TlSource src, size_t total_hint, size_t piece_bytes, unsigned flags,
                    uint64_t* counts, size_t cap, size_t* rows, mk_lookup_t* st) {
-  const auto t0 = LkClk::now();
+  const auto t0 = MkClock::now();
   LkText L(c, src, what, false, counts, cap);  // (owns the file from here on)
   if (cap && !counts) { c->err = std::string(what) + ": counts is NULL"; return MK_ERR_ARG; }
   int rc = lk_open(c, what, flags, &L.fold);
@@ -302,7 +238,7 @@ static int lk_text(mk_ctx* c, const char* what, TlSource src, size_t total_hint,
   L.out.pieces = L.pieces;
   L.out.s_read = L.s_read;
   L.out.s_probe = L.s_parse;
-  L.out.s_total = lk_since(t0);
+  L.out.s_total = mk_since(t0);
   if (st) *st = L.out;
   return MK_OK;
 }

@@ -13,16 +13,12 @@
 #include "mk_tsvpieces.h"
 #include "mk_tableview.h"
 #include <algorithm>
-#include <chrono>
-
-typedef std::chrono::steady_clock ScClk;
-static double sc_since(ScClk::time_point t0) { return std::chrono::duration<double>(ScClk::now() - t0).count(); }
 
 #define SC_RUN 32                // window starts a lane owns
 #define SC_SPAN (256 * SC_RUN)   // ... a workgroup: one tile of the record scan
-// Home-slot loads of the one-word table a lane has in flight before it compares any (LK_PER of mk_lookup.hip).
+// Home-slot loads of the one-word table a lane has in flight before it compares any: the lookup's knob.
 #ifndef SC_PER
-#define SC_PER 4
+#define SC_PER LK_PER
 #endif
 // The span and its halo are staged in LDS up to this k (24.5 KiB); beyond it -- by-reference contexts only -- the walk
 // reads the stream itself.
@@ -206,16 +202,9 @@ __global__ void __launch_bounds__(256) sc_probe_k(const uint8_t* __restrict__ se
         ++n_packed;
         u64 ka = a, kb2 = b;
         if (KEYS == TL_TWO_WORD_AA) { ka = (u64)(wide >> 64); kb2 = (u64)wide; }
-        if (FOLD) {
-          bool turned;
-          if (KEYS == TL_TWO_WORD_NT) turned = mk_canon128(ka, kb2, k);
-          else {
-            const u64 rc = mk_revcomp2(ka, k);
-            turned = rc < ka;
-            if (turned) ka = rc;
-          }
-          n_folded += turned ? 1 : 0;
-        }
+        if (FOLD) n_folded += LkStep<KEYS, SC_PER>::fold(ka, kb2, k) ? 1 : 0;
+        // (LkStep's issue and finish, spelled out here: with the whole step this kernel's s_probe was 2 to 6 % slower on
+        // the MI355X, outside the spread of this form, and the cause is not known -- profiles/table_reads_refactor.md)
         if (KEYS == TL_ONE_WORD) {
           if (t.bins) res[j] = find_dense(t.bins, (size_t)t.nbins, ka);
           else if (ka == MK_EMPTY) res[j] = t.side;
@@ -274,14 +263,10 @@ struct ScCall {
   bool fold;
   u64 at_least;
   MkDevBuf scratch;  // ScStatus | tile_pre[ntiles] | tile_cnt[ntiles]
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  MkTimed parse{c}, probe{c};  // (the events of the first piece serve every piece)
   mk_screen_t out{};
   size_t rows_seen = 0;
-  ~ScCall() {
-    for (auto e : ev)
-      if (e) (void)hipEventDestroy(e);
-    buf_free(scratch);
-  }
+  ~ScCall() { buf_free(scratch); }
 };
 
 static int sc_launch_probe(ScCall& s, size_t seq_len, const u64* tile_pre, u64 row_base, mk_screen_row_t* d_rows, ScStatus* d_st) {
@@ -324,21 +309,18 @@ static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t*
   }
   MkChunkInfo info{};
   ScStatus h{};
-  float ms = 0.f;
   MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
   MK_HIP(hipMemsetAsync(d_st, 0, sizeof(ScStatus), c->stream));
-  MK_HIP(hipEventRecord(s.ev[0], c->stream));
-  if ((rc = mk_launch_parse(c, d_text, n)) != MK_OK) return rc;
+  if ((rc = s.parse.begin()) != MK_OK || (rc = mk_launch_parse(c, d_text, n)) != MK_OK) return rc;
   hipLaunchKernelGGL(sc_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const uint8_t*)c->seq.p, (const MkChunkInfo*)c->info.p, tile_cnt);
   hipLaunchKernelGGL(sc_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, (const uint8_t*)c->seq.p,
                      (const MkChunkInfo*)c->info.p, d_st);
   MK_HIP(hipGetLastError());
-  MK_HIP(hipEventRecord(s.ev[1], c->stream));
+  if ((rc = s.parse.end()) != MK_OK) return rc;
   MK_HIP(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipStreamSynchronize(c->stream));
-  MK_HIP(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
-  s.out.s_parse += ms * 1e-3;
+  if ((rc = s.parse.add_to(s.out.s_parse)) != MK_OK) return rc;
   if (info.non_ascii) {
     c->err = std::string(s.what) + ": the text holds " + std::to_string(info.non_ascii) +
              " sequence byte(s) >= 0x80 (non-ASCII sequence text is not supported)";
@@ -355,17 +337,16 @@ static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t*
     if ((rc = mk_buf_reserve(c, *own, nrows * sizeof(mk_screen_row_t))) != MK_OK) return rc;
     d_rows = (mk_screen_row_t*)own->p;
   }
-  MK_HIP(hipEventRecord(s.ev[2], c->stream));
+  if ((rc = s.probe.begin()) != MK_OK) return rc;
   hipLaunchKernelGGL(sc_rows_init_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
   if (info.seq_len && (rc = sc_launch_probe(s, (size_t)info.seq_len, tile_pre, h.headless ? 0 : 1, d_rows, d_st)) != MK_OK) return rc;
   hipLaunchKernelGGL(sc_rows_final_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
   MK_HIP(hipGetLastError());
-  MK_HIP(hipEventRecord(s.ev[3], c->stream));
+  if ((rc = s.probe.end()) != MK_OK) return rc;
   MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
   if (h_rows) MK_HIP(hipMemcpyAsync(h_rows + first, d_rows, nrows * sizeof(mk_screen_row_t), hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipStreamSynchronize(c->stream));
-  MK_HIP(hipEventElapsedTime(&ms, s.ev[2], s.ev[3]));
-  s.out.s_probe += ms * 1e-3;
+  if ((rc = s.probe.add_to(s.out.s_probe)) != MK_OK) return rc;
   if (h.locked) {
     c->err = std::string(s.what) + ": a slot of the table was being claimed: something counts into it during the call";
     return MK_ERR_STATE;
@@ -386,12 +367,11 @@ static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t*
 template <class Body>
 static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least, size_t cap, size_t* nrows, mk_screen_t* st,
                   Body&& body) {
-  const auto t0 = ScClk::now();
+  const auto t0 = MkClock::now();
   ScCall s{c, what, false, at_least};
   int rc = lk_open(c, what, flags, &s.fold);
   if (rc != MK_OK) return rc;
   if (at_least < 1) { c->err = std::string(what) + ": at_least must be 1 or more"; return MK_ERR_ARG; }
-  for (auto& e : s.ev) MK_HIP(hipEventCreate(&e));
   const bool profile = c->profile;  // (the parser's launches are no part of the counting figures)
   c->profile = false;
   rc = body(s);
@@ -404,7 +384,7 @@ static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least
     return MK_ERR_RANGE;
   }
   s.out.records = s.rows_seen;
-  s.out.s_total = sc_since(t0);
+  s.out.s_total = mk_since(t0);
   if (st) *st = s.out;
   return MK_OK;
 }
@@ -438,9 +418,9 @@ extern "C" int mk_screen_text(mk_ctx* c, const uint8_t* text, size_t n, size_t p
       const size_t len = (size_t)end - at;
       if (!len) continue;
       if ((r = mk_buf_reserve(c, c->raw, len + 64)) != MK_OK) return r;
-      const auto t1 = ScClk::now();
+      const auto t1 = MkClock::now();
       MK_HIP(hipMemcpyAsync(c->raw.p, text + at, len, hipMemcpyHostToDevice, c->stream));
-      s.out.s_read += sc_since(t1);
+      s.out.s_read += mk_since(t1);
       const size_t room = cap > s.rows_seen ? cap - s.rows_seen : 0;
       if ((r = sc_piece(s, (const uint8_t*)c->raw.p, len, nullptr, room, &d_rows, rows)) != MK_OK) return r;
       at = (size_t)end;

@@ -653,33 +653,12 @@ __global__ __launch_bounds__(256) void mk_alpha_k(View v, size_t n, u64* __restr
 
 int mk_launch_alpha(mk_ctx* c, u64* d_out) {
   MK_HIP(hipMemsetAsync(d_out, 0, 16 * sizeof(u64), c->stream));
-  int rc = MK_OK;
-  if (c->mode == MK_MODE_DENSE)
-    rc = launch(c, mk_alpha_k<ViewDense>, grid_for(c->run_slots, 256, 1024), ViewDense{(const u64*)c->run.p}, c->run_slots, d_out);
-  else if (c->run_slots)
-    rc = launch(c, mk_alpha_k<View64>, grid_for(c->run_slots, 256, 1024), View64{(const MkSlot*)c->run.p}, c->run_slots, d_out);
-  if (rc == MK_OK && c->run_ref_slots)
-    rc = launch(c, mk_alpha_k<View64>, grid_for(c->run_ref_slots, 256, 1024), View64{(const MkSlot*)c->run_ref.p}, c->run_ref_slots, d_out);
-  if (rc == MK_OK && c->run128_slots)
-    rc = launch(c, mk_alpha_k<View128>, grid_for(c->run128_slots, 256, 1024), View128{(const MkSlot128*)c->run128.p}, c->run128_slots, d_out);
-  return rc;
+  return mk_each_table(c, [&](auto v, size_t n, int) { return launch(c, mk_alpha_k<decltype(v)>, grid_for(n, 256, 1024), v, n, d_out); });
 }
 
 // ------------------------------------------------------------------ two tables combined by key (mk_table_op)
-// f(ca, cb) of include/mercat_hip.h; op is uniform over the launch.
-__device__ __forceinline__ u64 setop_f(int op, u64 ca, u64 cb) {
-  switch (op) {
-    case MK_OP_MIN: return ca < cb ? ca : cb;
-    case MK_OP_MAX: return ca > cb ? ca : cb;
-    case MK_OP_SUM: return ca + cb;
-    case MK_OP_LEFT: return cb ? ca : 0;
-    case MK_OP_ONLY: return cb ? 0 : ca;
-    default: return ca > cb ? ca - cb : 0;  // MK_OP_DIFF
-  }
-}
-
-// ---- the OTHER table asked for the key a view hands out: probe(a, b) -> its count there, 0 when absent.  A table that
-// was never allocated has no slots and answers 0.  The inputs are final (lk_open): in the two-word table an all-ones
+// ---- the OTHER table asked for the key a view hands out: probe(a, b) -> its count there, 0 when absent; each holds the
+// fields of the other context's LkTables that it reads.  A table that was never allocated has no slots and answers 0.  The inputs are final (lk_open): in the two-word table an all-ones
 // count word is a count.
 struct Probe64 {
   const MkSlot* t;
@@ -783,6 +762,7 @@ int mk_launch_setop(mk_ctx* dst, const mk_ctx* x, const mk_ctx* y, bool scan_b, 
                     uint64_t* d_out_, uint64_t* slots) {
   u64* d_out = (u64*)d_out_;
   MkChunkInfo* info = (MkChunkInfo*)dst->info.p;
+  const LkTables tx = lk_tables(x), ty = lk_tables(y);  // (the same mode: mk_table_op has compared alphabet and k)
   int rc = MK_OK;
 #define SO_GO(VIEW, N, PROBE, SINK, OUT)                                                                                     \
   do {                                                                                                                     \
@@ -792,21 +772,19 @@ int mk_launch_setop(mk_ctx* dst, const mk_ctx* x, const mk_ctx* y, bool scan_b, 
   } while (0)
   if (x->mode == MK_MODE_DENSE) {
     if (!scan_b) {  // (the one elementwise pass)
-      rc = launch_setop<SO_SCAN_AB>(dst, ViewDense{(const u64*)x->run.p}, x->run_slots, ProbeBins{(const u64*)y->run.p, y->run_slots},
-                                    sink_bins(dst), op, true, min_x, min_y, d_out);
-      *slots += x->run_slots + y->run_slots;
+      rc = launch_setop<SO_SCAN_AB>(dst, ViewDense{tx.bins}, tx.nbins, ProbeBins{ty.bins, ty.nbins}, sink_bins(dst), op, true, min_x, min_y, d_out);
+      *slots += tx.nbins + ty.nbins;
     }
-  } else if (x->mode == MK_MODE_HASH64 && x->run_slots) {
-    SO_GO(View64{(const MkSlot*)x->run.p}, x->run_slots, (Probe64{(const MkSlot*)y->run.p, (u64)y->run_slots}), sink64<true>(dst), d_out);
-  } else if (x->mode == MK_MODE_HASH128 && x->run128_slots) {
-    SO_GO(View128{(const MkSlot128*)x->run128.p}, x->run128_slots, (Probe128{(const MkSlot128*)y->run128.p, (u64)y->run128_slots}),
+  } else if (tx.run_slots) {
+    SO_GO(View64{tx.run}, tx.run_slots, (Probe64{ty.run, ty.run_slots}), sink64<true>(dst), d_out);
+  } else if (tx.run128_slots) {
+    SO_GO(View128{tx.run128}, tx.run128_slots, (Probe128{ty.run128, ty.run128_slots}),
           (SinkPlace128{(MkSlot128*)dst->run128.p, (u64)(dst->run128_slots - 1)}), d_out);
   }
-  if (rc == MK_OK && x->run_ref_slots) {
-    const uint8_t* from = (const uint8_t*)x->arena.p;
-    const ProbeRef probe{(const MkSlot*)y->run_ref.p, (u64)y->run_ref_slots, (const uint8_t*)y->arena.p, from, x->k};
-    const SinkRef sink{(MkSlot*)dst->run_ref.p, (u64)(dst->run_ref_slots - 1), (uint8_t*)dst->arena.p, from, x->k, &info->new_rows_ref};
-    SO_GO(View64{(const MkSlot*)x->run_ref.p}, x->run_ref_slots, probe, sink, d_out + MK_SO_WORDS);
+  if (rc == MK_OK && tx.ref_slots) {
+    const ProbeRef probe{ty.ref, ty.ref_slots, ty.arena, tx.arena, x->k};
+    const SinkRef sink{(MkSlot*)dst->run_ref.p, (u64)(dst->run_ref_slots - 1), (uint8_t*)dst->arena.p, tx.arena, x->k, &info->new_rows_ref};
+    SO_GO(View64{tx.ref}, tx.ref_slots, probe, sink, d_out + MK_SO_WORDS);
   }
 #undef SO_GO
   return rc;

@@ -1,11 +1,8 @@
 // mk_tableops.hip -- rows going INTO a running table from outside a chunk, and table-to-table operations: the imports
 // of the multi-GPU merge (mk_import_pairs_device, mk_import_exotic; their exports are in mk_export.hip), mk_filter_min,
 // mk_merge_from, mk_table_op.  Host code only.
-#include "mk_common.h"
-#include <chrono>
+#include "mk_tableview.h"  // setop_f
 #include <cstring>
-
-typedef unsigned long long u64;
 
 extern "C" int mk_import_pairs_device(mk_ctx* c, const uint64_t* d_keys, const uint64_t* d_counts, size_t rows) {
   if (!c) return MK_ERR_ARG;
@@ -142,19 +139,8 @@ extern "C" int mk_merge_from(mk_ctx* dst, mk_ctx* src) {
 }
 
 // ------------------------------------------------------------------------------- two tables combined by key
-static u64 so_f(int op, u64 ca, u64 cb) {  // (setop_f of mk_table.hip, for the one key kept beside the one-word table)
-  switch (op) {
-    case MK_OP_MIN: return ca < cb ? ca : cb;
-    case MK_OP_MAX: return ca > cb ? ca : cb;
-    case MK_OP_SUM: return ca + cb;
-    case MK_OP_LEFT: return cb ? ca : 0;
-    case MK_OP_ONLY: return cb ? 0 : ca;
-    default: return ca > cb ? ca - cb : 0;
-  }
-}
-
 extern "C" int mk_table_op(mk_ctx* dst, mk_ctx* a, mk_ctx* b, int op, uint64_t min_a, uint64_t min_b, mk_table_op_t* st) {
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = MkClock::now();
   if (!dst || !a || !b) return MK_ERR_ARG;
   mk_ctx* c = dst;
   if (dst == a || dst == b) { c->err = "mk_table_op: dst must be a third context"; return MK_ERR_ARG; }
@@ -182,26 +168,23 @@ extern "C" int mk_table_op(mk_ctx* dst, mk_ctx* a, mk_ctx* b, int op, uint64_t m
   if ((a->run_ref_slots || (two && b->run_ref_slots)) && (rc = mk_grow_run_ref(dst, text + 1)) != MK_OK) return rc;
   if ((rc = mk_buf_reserve(c, c->ex_tmp, 2 * MK_SO_WORDS * sizeof(u64))) != MK_OK) return rc;
   u64* d_out = (u64*)c->ex_tmp.p;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto& e : ev) MK_HIP(hipEventCreate(&e));
+  MkTimed scan(c);
   u64 h[2 * MK_SO_WORDS] = {0}, slots = 0;
-  float ms = 0.f;
+  double s_scan = 0;
   rc = [&]() -> int {
+    int r;
     MK_HIP(hipMemsetAsync(d_out, 0, sizeof h, c->stream));
     MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
-    MK_HIP(hipEventRecord(ev[0], c->stream));
-    int r = mk_launch_setop(dst, a, b, false, op, true, min_a, min_b, (uint64_t*)d_out, (uint64_t*)&slots);
     // (b is walked for the one-pass ops too, without a probe or an insert: rows_b is a figure of the call)
-    if (r == MK_OK) r = mk_launch_setop(dst, b, a, true, op, two, min_b, min_a, (uint64_t*)d_out, (uint64_t*)&slots);
-    if (r != MK_OK) return r;
-    MK_HIP(hipEventRecord(ev[1], c->stream));
+    if ((r = scan.begin()) != MK_OK ||
+        (r = mk_launch_setop(dst, a, b, false, op, true, min_a, min_b, (uint64_t*)d_out, (uint64_t*)&slots)) != MK_OK ||
+        (r = mk_launch_setop(dst, b, a, true, op, two, min_b, min_a, (uint64_t*)d_out, (uint64_t*)&slots)) != MK_OK ||
+        (r = scan.end()) != MK_OK)
+      return r;
     MK_HIP(hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    const int r2 = mk_pull_info(dst);  // (the arena rows handed out; the stream is idle afterwards)
-    if (r2 != MK_OK) return r2;
-    MK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    return MK_OK;
+    if ((r = mk_pull_info(dst)) != MK_OK) return r;  // (the arena rows handed out; the stream is idle afterwards)
+    return scan.add_to(s_scan);
   }();
-  for (auto e : ev) (void)hipEventDestroy(e);
   if (rc != MK_OK) { (void)hipStreamSynchronize(c->stream); (void)mk_reset(dst); return rc; }
   const u64* ht = h + MK_SO_WORDS;  // the rows kept as text
   if (c->h_info->new_rows_ref != ht[MK_SO_ROWS_OUT]) {
@@ -214,7 +197,7 @@ extern "C" int mk_table_op(mk_ctx* dst, mk_ctx* a, mk_ctx* b, int op, uint64_t m
   if (dst->mode == MK_MODE_HASH64) {
     sa = a->run_side >= min_a ? a->run_side : 0;
     sb = b->run_side >= min_b ? b->run_side : 0;
-    sf = so_f(op, sa, sb);
+    sf = setop_f(op, sa, sb);
     dst->run_side = sf;
   }
   mk_add_packed_rows(dst, dst->mode == MK_MODE_DENSE ? 0 : (size_t)h[MK_SO_ROWS_OUT]);
@@ -231,7 +214,7 @@ extern "C" int mk_table_op(mk_ctx* dst, mk_ctx* a, mk_ctx* b, int op, uint64_t m
   st->slots = slots;
   st->passes = two ? 2 : 1;
   st->op = op;
-  st->s_scan = ms * 1e-3;
-  st->s_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st->s_scan = s_scan;
+  st->s_total = mk_since(t0);
   return MK_OK;
 }

@@ -154,8 +154,8 @@ __device__ __forceinline__ u64 find_ref_of(const MkSlot* __restrict__ run, u64 m
 // Dense bins: one indexed load.
 __device__ __forceinline__ u64 find_dense(const u64* __restrict__ bins, size_t nbins, u64 bin) { return bin < nbins ? bins[bin] : 0; }
 
-// ---- the tables of one context, as a probing kernel sees them (mk_lookup.hip, mk_screen.hip); a table that was never
-// allocated has no slots
+// ---- the tables of one context, as a reading kernel sees them: the one place where the context's buffers are given
+// their types.  A table that was never allocated has no slots.
 struct LkTables {
   const MkSlot* run;          // one-word keys
   u64 run_slots;
@@ -177,4 +177,99 @@ static inline LkTables lk_tables(const mk_ctx* c) {
   t.ref_slots = c->run_ref_slots;
   t.arena = (const uint8_t*)c->arena.p;
   return t;
+}
+
+// f(view, slots, kind: MkTableKind) for every table the context holds -- the dense bins or else the one-word table, then
+// the by-reference table, then the two-word table, each only if it has slots -- until one answers other than MK_OK.
+// (The one key kept beside the one-word table is no slot: whoever walks the tables adds run_side itself.)
+template <class F>
+static inline int mk_each_table(const mk_ctx* c, F&& f) {
+  const LkTables t = lk_tables(c);
+  int rc = MK_OK;
+  if (c->mode == MK_MODE_DENSE) rc = f(ViewDense{t.bins}, (size_t)t.nbins, MK_TABLE_DENSE);
+  else if (t.run_slots) rc = f(View64{t.run}, (size_t)t.run_slots, MK_TABLE_ONE);
+  if (rc == MK_OK && t.ref_slots) rc = f(View64{t.ref}, (size_t)t.ref_slots, MK_TABLE_REF);
+  if (rc == MK_OK && t.run128_slots) rc = f(View128{t.run128}, (size_t)t.run128_slots, MK_TABLE_TWO);
+  return rc;
+}
+
+// The kind of key a context packs: one word, two words (nucleotide 33..64-mers; amino acid 13..25-mers), or none -- every
+// key is kept as text.
+enum TlKeys { TL_ONE_WORD = 0, TL_TWO_WORD_NT = 1, TL_TWO_WORD_AA = 2, TL_TEXT_ONLY = 3 };
+static inline int tl_keys_of(const mk_ctx* c) {
+  return c->mode == MK_MODE_BYREF ? TL_TEXT_ONLY
+         : c->mode != MK_MODE_HASH128 ? TL_ONE_WORD
+         : c->alphabet == MK_ALPHABET_NT2 ? TL_TWO_WORD_NT : TL_TWO_WORD_AA;
+}
+
+// A probe is a dependent random 16-byte read: a lane that looks one key up after the other waits a full trip to HBM per
+// key.  PER keys a lane: the home-slot loads of all of them are issued before any is compared (one-word table).  The
+// knob of mk_lookup.hip; the windows of mk_screen.hip take as many (SC_PER).
+// (A/B builds: -DLK_PER=1 is the one-key-a-lane form tools/lookup_probe.py's figures are compared with.)
+#ifndef LK_PER
+#define LK_PER 4
+#endif
+
+// ---- one key looked up by a kernel that has PER keys a lane in flight (lk_probe_k; sc_probe_k takes the fold).  KEYS: the kind of the
+// context's packed keys.  j is a constant under #pragma unroll: the arrays live in registers.
+//   fold    the key onto its reverse complement where that is smaller (one-word and two-word nucleotide keys)
+//   issue   a packed key: dense bins and the two-word table answer at once, the all-ones one-word key is the one kept
+//           beside its table, any other one-word key has its home slot loaded and is left pending, so that a lane has
+//           the loads of all its keys in flight before it compares any
+//   issue   a key kept as text, its k bytes through an accessor: the by-reference table answers at once
+//   finish  the count, a pending key's probe brought to its end
+// locked: a slot of the two-word table was being claimed (cannot happen on a quiescent table; the caller reports it).
+// A word, not a bool: as a bool it is a lane mask in two scalar registers across the whole loop, and the two-word
+// instances of both kernels spill scalars for it.
+template <int KEYS, int PER>
+struct LkStep {
+  u64 key[PER], res[PER];
+  ulonglong2 home[PER];
+  bool pending[PER];
+  unsigned locked = 0;
+
+  static __device__ __forceinline__ bool fold(u64& a, u64& b, int k) {
+    if (KEYS == TL_TWO_WORD_NT) return mk_canon128(a, b, k);
+    const u64 rc = mk_revcomp2(a, k);
+    const bool turned = rc < a;
+    if (turned) a = rc;
+    return turned;
+  }
+  __device__ __forceinline__ void clear(int j) { pending[j] = false; res[j] = 0; }
+  __device__ __forceinline__ void issue(int j, const LkTables& t, u64 a, u64 b) {
+    if (KEYS == TL_ONE_WORD) {
+      if (t.bins) res[j] = find_dense(t.bins, (size_t)t.nbins, a);
+      else if (a == MK_EMPTY) res[j] = t.side;
+      else if (t.run_slots) {
+        key[j] = a;
+        home[j] = find64_home(t.run, t.run_slots - 1, a);
+        pending[j] = true;
+      }
+    } else if (t.run128_slots) {
+      bool met = false;
+      res[j] = find128(t.run128, t.run128_slots - 1, a, b, &met);
+      locked |= met ? 1u : 0u;
+    }
+  }
+  template <class Get>
+  __device__ __forceinline__ void issue(int j, const LkTables& t, const Get& get, int k) {
+    if (t.ref_slots) res[j] = find_ref_of(t.ref, t.ref_slots - 1, t.arena, get, k);
+  }
+  __device__ __forceinline__ u64 finish(int j, const LkTables& t) {
+    if (pending[j]) res[j] = find64_from(t.run, t.run_slots - 1, key[j], home[j]);
+    return res[j];
+  }
+};
+
+// ---- f(ca, cb) of mk_table_op (include/mercat_hip.h): in mk_setop_k, where op is uniform over the launch, and on the
+// host for the one key kept beside the one-word table
+__host__ __device__ static inline u64 setop_f(int op, u64 ca, u64 cb) {
+  switch (op) {
+    case MK_OP_MIN: return ca < cb ? ca : cb;
+    case MK_OP_MAX: return ca > cb ? ca : cb;
+    case MK_OP_SUM: return ca + cb;
+    case MK_OP_LEFT: return cb ? ca : 0;
+    case MK_OP_ONLY: return cb ? 0 : ca;
+    default: return ca > cb ? ca - cb : 0;  // MK_OP_DIFF
+  }
 }

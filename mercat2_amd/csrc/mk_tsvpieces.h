@@ -6,6 +6,7 @@
 #pragma once
 #include "mk_common.h"
 #include "mk_device.h"
+#include "mk_tableview.h"  // TlKeys, tl_keys_of
 #include <deque>
 
 #define TL_TILE 4096u           // bytes per workgroup of the line-start passes: 256 lanes x 16 bytes
@@ -22,13 +23,6 @@ struct TlStatus {
   // being claimed (MK_LOCK128: somebody counts into the table meanwhile)
   u64 found, folded, locked, pad;
 };
-
-enum TlKeys { TL_ONE_WORD = 0, TL_TWO_WORD_NT = 1, TL_TWO_WORD_AA = 2, TL_TEXT_ONLY = 3 };
-static inline int tl_keys_of(const mk_ctx* c) {
-  return c->mode == MK_MODE_BYREF ? TL_TEXT_ONLY
-         : c->mode != MK_MODE_HASH128 ? TL_ONE_WORD
-         : c->alphabet == MK_ALPHABET_NT2 ? TL_TWO_WORD_NT : TL_TWO_WORD_AA;
-}
 
 // The k key bytes at `key` classified against the alphabet (bits: 2 nucleotide, 5 amino acids) and packed into the
 // layout mk_import_pairs_device takes: one word, or {a, b} = {hi, lo}.  Returns whether every byte is of the alphabet
