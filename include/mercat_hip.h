@@ -397,6 +397,49 @@ int mk_screen_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_byte
 int mk_screen_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, uint64_t at_least,
                      mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_screen_t* st);
 
+/* ---- sequences in, the matched (or the unmatched) records out: the reads themselves, filtered on the GPU by what
+ *      mk_screen_* finds for them (BBDuk's outm / out, kmc_tools filter, khmer's filter-abund) ----
+ * The text is read, cut into records and probed exactly as mk_screen_text does it: same parser, same rows, same
+ * mk_screen_t figures (st->screen; its s_total is the wall time of this whole call), same opening rules and errors --
+ * the table only read and made final first, MK_ERR_STATE with an open chunk or a refused one, MK_ERR_NON_ASCII, the fold
+ * rule (MK_FILTER_FOLD = MK_SCREEN_FOLD), pieces cut by mk_record_cuts, device text of any alignment, the stream idle
+ * afterwards and the counting figures untouched.
+ * Bytes of a record: from the first byte of its header LINE (the byte after the nearest LF or CR in front of the '>', or
+ * the first byte of the text: leading blanks of the line belong to the record) to the byte in front of the next
+ * record's header line, or the end of the text.  The headless record (st->screen.headless) runs from byte 0.  Otherwise
+ * the bytes in front of the first header line are the preamble (st->preamble): they hold no kept character and belong
+ * to no record.  The records partition the text minus its preamble.
+ * Rule: hits counts the windows whose count is >= at_least, as in screen.  A record is MATCHED iff windows > 0 and
+ * hits >= min_hits and hits * 1000000 >= min_ppm * windows (128-bit integers); a record without windows never is.
+ * "every k-mer occurs at least N times" is {N, 1, 1000000}.  at_least and min_hits >= 1, min_ppm <= 1000000, reserved
+ * is ignored; a NULL rule, a value out of range or an unknown flag bit is MK_ERR_ARG and the message names it.
+ * Output: the bytes of the matched records -- with MK_FILTER_INVERT of the unmatched ones -- in text order, byte for
+ * byte: nothing is re-wrapped, the preamble goes to neither, *out_len <= n.  keep[r] = 1 iff record r was emitted;
+ * rows[r] is its screen row.  rows and keep may each be NULL (cap is ignored when both are).  With out_cap or cap too
+ * small: MK_ERR_RANGE, the needed sizes in *out_len and *nrows, nothing written past either -- every piece is still
+ * walked to learn them.  st may be NULL.
+ * mk_filter_text: host memory in and out, piece by piece (each piece's output is appended to out by its copy back).
+ * mk_filter_device: text, out, rows and keep in DEVICE memory of the context's GPU, one piece. */
+#define MK_FILTER_FOLD   1u   /* = MK_SCREEN_FOLD */
+#define MK_FILTER_INVERT 2u   /* emit the unmatched records */
+typedef struct mk_filter_rule_t {
+  uint64_t at_least, min_hits;
+  uint32_t min_ppm, reserved;
+} mk_filter_rule_t;
+typedef struct mk_filter_t {
+  mk_screen_t screen;                 /* as mk_screen_* fills it for the same text                              */
+  uint64_t records_out, bytes_out;    /* records emitted, their bytes                                          */
+  uint64_t preamble;                  /* bytes in front of the first header line of a text that is not headless */
+  /* seconds: HIP-event time of the record starts, the decision and the scan; of the gather; host time in the copies back */
+  double s_place, s_gather, s_write;
+} mk_filter_t;
+int mk_filter_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, const mk_filter_rule_t* rule,
+                   uint8_t* out, size_t out_cap, size_t* out_len,
+                   mk_screen_row_t* rows, uint8_t* keep, size_t cap, size_t* nrows, mk_filter_t* st);
+int mk_filter_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_filter_rule_t* rule,
+                     uint8_t* d_out, size_t out_cap, size_t* out_len,
+                     mk_screen_row_t* d_rows, uint8_t* d_keep, size_t cap, size_t* nrows, mk_filter_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

@@ -19,7 +19,9 @@ more samples, report/diversity-<type>.tsv.  -query FILE writes query_<type>.tsv:
 sample, looked up in those tables (mk_lookup_file).  -histo [HIGH] writes every sample's abundance histogram
 (histo_<type>/<sample>_histo.txt, histo_<type>.tsv), reduced in those tables (mk_histo).  -screen FILE writes, for every
 sample of FILE's type, screen_<type>/<sample>_screen.tsv: per record of FILE its k-mers, how many of them the sample's table
-holds, and how abundant they are (mk_screen_text).  -against FILE -op OP writes, for every sample of FILE's type,
+holds, and how abundant they are (mk_screen_text).  -filter FILE writes, for every sample of FILE's type,
+filter_<type>/<sample>_<matched|unmatched>.fna (.faa): the records of FILE that share k-mers with the sample's table, or those
+that do not, copied out on the GPU (mk_filter_text).  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
 (mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
@@ -41,6 +43,7 @@ from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_t
 from .report import (merge_counters, merge_counters_T, write_against_tsvs, write_histo_files, write_histo_tsv, write_query_tsv,
                      write_screen_tsv)
 
+FILTER_KEEP = ("matched", "unmatched")
 AGAINST_OPS = ("min", "max", "sum", "left", "only", "diff")  # native.OPS, for the parser (which loads no library)
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
@@ -75,6 +78,18 @@ def parseargs(argv=None):
                         "of them the sample holds at least -screen_min times (hits), and the sum, smallest and largest of "
                         "their counts; with -canonical the k-mers are folded")
     p.add_argument("-screen_min", type=int, default=1, metavar="N", help="-screen: a k-mer is a hit from this count on [1]")
+    p.add_argument("-filter", type=str, required=False, metavar="FILE",
+                   help="a FASTA or FASTQ file (plain or .gz) of reads or contigs to filter against the tables on the GPU: for "
+                        "every sample of FILE's type, filter_<type>/<sample>_<matched|unmatched>.fna (.faa for protein) with "
+                        "the records of FILE that match the sample's table, or those that do not (-filter_keep), byte for "
+                        "byte and in order.  A FASTQ file is first converted as MerCat2's fq2fa converts it, so the output is "
+                        "FASTA, the text MerCat2 itself counts; with -canonical the k-mers are folded")
+    p.add_argument("-filter_min", type=int, default=None, metavar="N", help="-filter: a k-mer is a hit from this count on [1]")
+    p.add_argument("-filter_hits", type=int, default=None, metavar="N", help="-filter: a record matches from this many hits on [1]")
+    p.add_argument("-filter_frac", type=float, default=None, metavar="F",
+                   help="-filter: ... and only if at least this fraction (0..1) of its k-mers are hits [0]")
+    p.add_argument("-filter_keep", type=str, default=None, choices=FILTER_KEEP,
+                   help="-filter: write the records that match, or those that do not [unmatched, as BBDuk's out]")
     p.add_argument("-against", type=str, required=False, metavar="FILE",
                    help="a count table -- a counts TSV, or a Jellyfish / KMC dump -- of k-mer length -k to combine every sample "
                         "with by key, in the tables on the GPU (needs -op): for every sample of FILE's type (nucleotide or "
@@ -141,6 +156,27 @@ def parseargs(argv=None):
             p.error(f"-screen {args.screen}: the extension names neither a nucleotide, a protein nor a FASTQ file")
     if not 1 <= args.screen_min < 1 << 64:
         p.error(f"-screen_min {args.screen_min}: must be 1 or more")
+    args.filter_kind = None
+    if not args.filter:
+        for flag in ("filter_min", "filter_hits", "filter_frac", "filter_keep"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -filter FILE")
+    else:
+        if not os.path.isfile(args.filter):
+            p.error(f"file '{args.filter}' is not valid.\n")
+        args.filter_kind = classify(Path(args.filter).expanduser().absolute(), True)[0]
+        if not args.filter_kind:
+            p.error(f"-filter {args.filter}: the extension names neither a nucleotide, a protein nor a FASTQ file")
+        args.filter_min = 1 if args.filter_min is None else args.filter_min
+        args.filter_hits = 1 if args.filter_hits is None else args.filter_hits
+        args.filter_frac = 0.0 if args.filter_frac is None else args.filter_frac
+        args.filter_keep = args.filter_keep or "unmatched"
+        if not 1 <= args.filter_min < 1 << 64:
+            p.error(f"-filter_min {args.filter_min}: must be 1 or more")
+        if not 1 <= args.filter_hits < 1 << 64:
+            p.error(f"-filter_hits {args.filter_hits}: must be 1 or more")
+        if not 0.0 <= args.filter_frac <= 1.0:  # (the rule kmers.filter_reads applies: native.ppm_of_fraction)
+            p.error(f"-filter_frac {args.filter_frac}: must lie in 0..1")
     args.against_kind = None
     if args.op and not args.against:
         p.error("-op needs -against FILE")
@@ -508,6 +544,21 @@ def main(argv=None) -> int:
                         write_screen_tsv(out / f"screen_{kind}" / f"{base}_screen.tsv", names, rows)
                     print(f"screen_{kind}/: {len(names)} records of {os.path.basename(args.screen)} screened against "
                           f"{len(tables)} sample(s)")
+                if args.filter and args.filter_kind == kind:  # from the tables still on the GPU
+                    from .kmers import filter_reads
+                    (out / f"filter_{kind}").mkdir(parents=True, exist_ok=True)
+                    ext = "faa" if kind == "protein" else "fna"
+                    kept = {}
+                    for base in sorted(tables):
+                        try:
+                            res = filter_reads(tables[base], args.filter, out / f"filter_{kind}" / f"{base}_{args.filter_keep}.{ext}",
+                                               args.filter_min, args.filter_hits, args.filter_frac, args.filter_keep == "unmatched")
+                        except native.MercatHipError as e:
+                            raise SystemExit(f"-filter {args.filter}: {e}")
+                        kept[base] = res["kept"]
+                    print(f"filter_{kind}/: {res['records']} records of {os.path.basename(args.filter)} filtered against "
+                          f"{len(tables)} sample(s), {args.filter_keep} records written: " +
+                          ", ".join(f"{base} {n}" for base, n in kept.items()))
                 if args.against and args.against_kind == kind:  # from the tables still on the GPU
                     try:
                         rows = write_against_tsvs({base: tables[base] for base in sorted(tables)}, args.against, args.op,

@@ -4,6 +4,13 @@
 
 typedef unsigned long long u64;
 
+// How the FASTA readers see a byte (mk_parse.hip's transducer, mk_filter.hip's record starts): lines end at LF or CR;
+// blanks are what str.strip() removes, minus the newlines.
+__device__ __forceinline__ bool mk_is_nl(unsigned c) { return c == 10u || c == 13u; }
+__device__ __forceinline__ bool mk_is_blank(unsigned c) {
+  return c == 32u || c == 9u || c == 11u || c == 12u || (c >= 28u && c <= 31u);
+}
+
 // Key of the k symbols that start at symbol s of `cur`, continuing into `nxt` (packed layout of
 // mk_pack.hip: symbols MSB first, BITS each, SPW per word).
 template <int BITS, int SPW>

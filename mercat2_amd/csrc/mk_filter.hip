@@ -1,0 +1,413 @@
+// mk_filter.hip -- sequences in, the matched (or the unmatched) records out (mk_filter_text / mk_filter_device,
+// include/mercat_hip.h): what mk_screen_* finds for every record of a FASTA text decides whether the record's bytes are
+// copied to the output, on the GPU, where the text and the rows already are.
+//
+// A piece goes through sc_piece (mk_screenpiece.h: parse, record scan, probe) and leaves its rows on the device.  Then
+//   fl_tiles_k / fl_scan_k / fl_starts_k   the header lines of the RAW text: start[r] for every row, start[nrows] = n.
+//                                          Only a '>' byte pays for the look back over blanks to a newline.  The header
+//                                          lines found must be the parser's separators: that guard (fl_piece) is the
+//                                          only link between the two views of the text.
+//   fl_decide_k                            a lane per record: keep[r] from its row and the rule, the kept length
+//   rocprim::exclusive_scan                dst[r], dst[nrows] = the piece's output length
+//   fl_gather_k (fl_edges_k)               the only kernel that moves text: output-driven, a lane owns 16 aligned output
+//                                          bytes at a time, finds their record by search in dst[], reads the (unaligned)
+//                                          source and issues one 16-byte store.  No atomics, no byte stores but for the
+//                                          at most 15 + 15 bytes in front of and behind the aligned body.
+#include "mk_screenpiece.h"
+#include "mk_tableview.h"
+#include <rocprim/device/device_scan.hpp>
+
+#define FL_RUN 32                // text bytes a lane of the start kernels owns
+#define FL_SPAN (256 * FL_RUN)   // ... a workgroup: one tile of the header scan
+
+struct FlStatus {  // device memory, read back once a piece
+  u64 headers, records_out;
+};
+
+// 0x80 in every byte of w that is '>' (exact per byte: no borrow between them)
+__device__ __forceinline__ unsigned fl_gt_in(unsigned w) {
+  const unsigned x = w ^ 0x3E3E3E3Eu;
+  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+}
+
+// f(j, line) for the j-th header line whose '>' lies in the FL_RUN bytes at base: line = the first byte of that line.
+// Returns how many there are.  A '>' opens a header line iff only blanks stand between it and the line's start.
+template <class F>
+__device__ __forceinline__ unsigned fl_headers_in(const uint8_t* __restrict__ text, u64 n, u64 base, F&& f) {
+  unsigned cnt = 0;
+  auto at = [&](u64 i) {
+    u64 j = i;
+    while (j > 0 && mk_is_blank(text[j - 1])) --j;
+    if (j == 0 || mk_is_nl(text[j - 1])) f(cnt++, j);
+  };
+  if (base + FL_RUN <= n) {
+    const uint4* p = reinterpret_cast<const uint4*>(text + base);  // (text is 16-byte aligned, base a multiple of 32)
+#pragma unroll
+    for (int i = 0; i < FL_RUN / 16; ++i) {
+      const uint4 v = p[i];
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        for (unsigned m = fl_gt_in(w[q]); m; m &= m - 1) at(base + i * 16 + q * 4 + ((__ffs(m) - 1) >> 3));
+    }
+  } else {
+    for (int j = 0; j < FL_RUN && base + j < n; ++j)
+      if (text[base + j] == '>') at(base + j);
+  }
+  return cnt;
+}
+
+__global__ void __launch_bounds__(256) fl_tiles_k(const uint8_t* __restrict__ text, u64 n, unsigned* __restrict__ tile_cnt) {
+  __shared__ unsigned s_wave[4];
+  const u64 base = (u64)blockIdx.x * FL_SPAN + (u64)threadIdx.x * FL_RUN;
+  unsigned cnt = mk_wave_sum(fl_headers_in(text, n, base, [](unsigned, u64) {}));
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// One workgroup, in the pattern of sc_scan_k: thread t owns tiles [t * per, (t + 1) * per).  tile_pre[i] = header
+// lines in front of tile i; their total goes to st.  The two starts no header line gives are written here: the end of
+// the text behind the last row, byte 0 for a headless row 0.
+__global__ void __launch_bounds__(1024) fl_scan_k(const unsigned* __restrict__ tile_cnt, size_t ntiles, u64* __restrict__ tile_pre,
+                                                  u64 n, size_t nrows, int headless, u64* __restrict__ start, FlStatus* __restrict__ st) {
+  __shared__ u64 s_c[1024];
+  const size_t per = (ntiles + 1023) / 1024;
+  const size_t lo = (size_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
+  u64 mine = 0;
+  for (size_t t = lo; t < hi; ++t) mine += tile_cnt[t];
+  s_c[threadIdx.x] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 run = 0;
+    for (int t = 0; t < 1024; ++t) {
+      const u64 c = s_c[t];
+      s_c[t] = run;
+      run += c;
+    }
+    st->headers = run;
+    start[nrows] = n;
+    if (headless) start[0] = 0;
+  }
+  __syncthreads();
+  u64 run = s_c[threadIdx.x];
+  for (size_t t = lo; t < hi; ++t) {
+    tile_pre[t] = run;
+    run += tile_cnt[t];
+  }
+}
+
+// start[row_base + j] = the first byte of header line j (row_base 1: row 0 is the headless record).  A header line past
+// the rows the parser counted is not written: the host's guard reports it.
+__global__ void __launch_bounds__(256) fl_starts_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ tile_pre,
+                                                   u64 row_base, size_t nrows, u64* __restrict__ start) {
+  __shared__ unsigned s_wave[4];
+  const u64 base = (u64)blockIdx.x * FL_SPAN + (u64)threadIdx.x * FL_RUN;
+  const unsigned own = fl_headers_in(text, n, base, [](unsigned, u64) {});
+  const unsigned incl = mk_wave_scan_incl(own);
+  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  u64 first = row_base + tile_pre[blockIdx.x] + (incl - own);
+  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) first += s_wave[w];
+  if (own)
+    fl_headers_in(text, n, base, [&](unsigned j, u64 line) {
+      if (first + j < nrows) start[first + j] = line;
+    });
+}
+
+// A lane per record (and one for the slot behind the last, whose length is 0 so that the scan ends in the total).
+__global__ void __launch_bounds__(256) fl_decide_k(const mk_screen_row_t* __restrict__ rows, const u64* __restrict__ start, size_t nrows,
+                                                   u64 min_hits, u64 min_ppm, bool invert, uint8_t* __restrict__ keep,
+                                                   u64* __restrict__ len, FlStatus* __restrict__ st) {
+  u64 kept = 0;
+  mk_for_each(nrows + 1, [&](size_t r) {
+    if (r == nrows) { len[r] = 0; return; }
+    const u64 windows = rows[r].windows, hits = rows[r].hits;
+    const bool matched = windows > 0 && hits >= min_hits &&
+                         (unsigned __int128)hits * 1000000u >= (unsigned __int128)min_ppm * windows;
+    const bool k = matched != invert;
+    keep[r] = k ? 1 : 0;
+    len[r] = k ? start[r + 1] - start[r] : 0;
+    kept += k ? 1 : 0;
+  });
+  block_add(&st->records_out, kept);
+}
+
+// The record whose output bytes hold offset o: the largest r in [lo, hi] with dst[r] <= o.  (A dropped record has
+// dst[r] == dst[r + 1], so the largest such r is a kept one.)
+__device__ __forceinline__ size_t fl_record_of(const u64* __restrict__ dst, size_t lo, size_t hi, u64 o) {
+  while (lo < hi) {
+    const size_t mid = lo + (hi - lo + 1) / 2;
+    if (dst[mid] <= o) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ u64 fl_first_lane(u64 v) {
+  return ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// The same from a record r that is known not to lie behind o's: steps of 1, 2, 4, ... records, then the search between
+// the last two.  One load when o is still in r, 2 log2(d) + 1 for a record d further on.
+__device__ __forceinline__ size_t fl_record_from(const u64* __restrict__ dst, size_t r, size_t nrows, u64 o) {
+  size_t step = 1;
+  while (r + step < nrows && dst[r + step] <= o) {
+    r += step;
+    step <<= 1;
+  }
+  return fl_record_of(dst, r, (r + step < nrows ? r + step : nrows) - 1, o);
+}
+
+// The 16 text bytes at src, which is not aligned: the two aligned 16 bytes around them, shifted together.  Within the
+// last 32 bytes of the text, byte by byte; bytes behind the text read as 0.
+__device__ __forceinline__ unsigned __int128 fl_load16(const uint8_t* __restrict__ text, u64 n, u64 src) {
+  const u64 a = src & ~(u64)15;
+  u64 y0 = 0, y1 = 0;
+  if (a + 32 <= n) {
+    const uint4* p = reinterpret_cast<const uint4*>(text + a);
+    const uint4 lo = p[0], hi = p[1];
+    u64 x0 = lo.x | ((u64)lo.y << 32), x1 = lo.z | ((u64)lo.w << 32), x2 = hi.x | ((u64)hi.y << 32);
+    const u64 x3 = hi.z | ((u64)hi.w << 32);
+    const unsigned s = (unsigned)(src & 15);
+    if (s >= 8) { x0 = x1; x1 = x2; x2 = x3; }
+    const unsigned sh = (s & 7) * 8;
+    y0 = sh ? (x0 >> sh) | (x1 << (64 - sh)) : x0;
+    y1 = sh ? (x1 >> sh) | (x2 << (64 - sh)) : x1;
+  } else {
+    for (int b = 0; b < 8; ++b) {
+      if (src + b < n) y0 |= (u64)text[src + b] << (8 * b);
+      if (src + 8 + b < n) y1 |= (u64)text[src + 8 + b] << (8 * b);
+    }
+  }
+  return ((unsigned __int128)y1 << 64) | y0;
+}
+
+// Chunk g is the output bytes [head + 16 g, head + 16 g + 16), 16-byte aligned in memory; nbody of them.  A wave owns
+// FL_CHUNKS KiB of them: in round j lane l takes chunk 64 j + l of the wave's, so that a store instruction of the wave
+// writes 1 KiB in one piece.  The wave searches dst[] once, for the record of its first byte (the same loads in every
+// lane); from there a lane steps forward (fl_record_from) to the record of each of its chunks: about six reads of 150
+// bases further on each round, the same record all the way inside a contig.  A chunk is then filled record by record:
+// the 16 bytes at the source (fl_load16) masked to what the record still has and shifted to their place.  One trip
+// inside a record -- every chunk of a contig, nine in ten of 150-base reads -- and one more per record that starts in
+// the chunk: sixteen at the most, whatever the records are.  The next record is r + 1, or, if that one is dropped, the
+// next kept one, found by stepping on from it.
+#define FL_CHUNKS 4
+__global__ void __launch_bounds__(256) fl_gather_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ start,
+                                                   const u64* __restrict__ dst, size_t nrows, u64 head, u64 nbody,
+                                                   uint8_t* __restrict__ out) {
+  const u64 g0 = fl_first_lane((((u64)blockIdx.x * 256 + threadIdx.x) >> 6) * (64 * FL_CHUNKS));
+  if (g0 >= nbody) return;
+  size_t r = fl_record_of(dst, 0, nrows - 1, head + 16 * g0);
+  for (int j = 0; j < FL_CHUNKS; ++j) {
+    const u64 g = g0 + j * 64 + (threadIdx.x & 63);
+    if (g >= nbody) break;
+    const u64 o0 = head + 16 * g;
+    r = fl_record_from(dst, r, nrows, o0);
+    u64 end = dst[r + 1];
+    u64 src = start[r] + (o0 - dst[r]);
+    unsigned __int128 v = 0;
+    for (unsigned b = 0;;) {  // b: bytes of the chunk filled
+      const u64 left = end - (o0 + b);  // (1 or more: the record holds byte o0 + b)
+      const unsigned m = left < 16 - b ? (unsigned)left : 16 - b;
+      unsigned __int128 seg = fl_load16(text, n, src);
+      if (m < 16) seg &= (((unsigned __int128)1) << (8 * m)) - 1;
+      v |= seg << (8 * b);
+      b += m;
+      if (b == 16) break;
+      ++r;  // the record ended inside the chunk (bytes follow: a kept record does)
+      if (dst[r + 1] == dst[r]) r = fl_record_from(dst, r, nrows, o0 + b);
+      end = dst[r + 1];
+      src = start[r];
+    }
+    const u64 v0 = (u64)v, v1 = (u64)(v >> 64);
+    *reinterpret_cast<uint4*>(out + o0) = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
+  }
+}
+
+// The bytes in front of the first aligned 16 of the output (head of them) and behind the last (from tail_at on): a lane
+// a byte, at most 15 + 15.
+__global__ void __launch_bounds__(64) fl_edges_k(const uint8_t* __restrict__ text, const u64* __restrict__ start,
+                                                 const u64* __restrict__ dst, size_t nrows, u64 head, u64 tail_at, u64 out_len,
+                                                 uint8_t* __restrict__ out) {
+  u64 o;
+  if (threadIdx.x < 16) o = threadIdx.x < head ? threadIdx.x : out_len;
+  else if (threadIdx.x < 32) o = tail_at + (threadIdx.x - 16);
+  else return;
+  if (o >= out_len) return;
+  const size_t r = fl_record_of(dst, 0, nrows - 1, o);
+  out[o] = text[start[r] + (o - dst[r])];
+}
+
+// ------------------------------------------------------------------------------------------ host side
+struct FlCall {
+  mk_filter_rule_t rule;
+  bool invert;
+  uint8_t* out;       // where the output goes (text call: host memory, device call: device memory), out_cap bytes of room
+  size_t out_cap;
+  mk_screen_row_t* rows;  // the caller's, or nullptr; cap of each
+  uint8_t* keep;
+  size_t cap;
+  bool device;        // out / rows / keep are device memory
+  MkDevBuf d_rows, d_keep, meta, scan_tmp, stage;
+  MkTimed place, gather;
+  mk_filter_t st{};
+  size_t bytes_out = 0;  // of all pieces so far, written or not
+  FlCall(mk_ctx* c, const mk_filter_rule_t& r, bool inv, uint8_t* o, size_t oc, mk_screen_row_t* rw, uint8_t* kp, size_t cp, bool dev)
+      : rule(r), invert(inv), out(o), out_cap(oc), rows(rw), keep(kp), cap(cp), device(dev), place(c), gather(c) {}
+  ~FlCall() {
+    for (MkDevBuf* b : {&d_rows, &d_keep, &meta, &scan_tmp, &stage}) buf_free(*b);
+  }
+};
+
+// What follows sc_piece for a piece of n bytes whose rows start at row `first` of the call: record starts, decision,
+// placement, gather, and the copies to the caller's buffers where they have room.  The stream is idle afterwards.
+static int fl_piece(ScCall& s, FlCall& f, size_t n, size_t first) {
+  mk_ctx* c = s.c;
+  int rc;
+  const size_t nrows = s.last.nrows;
+  if (!nrows) {  // (no header line, no kept character)
+    f.st.preamble += n;
+    return MK_OK;
+  }
+  const uint8_t* text = s.last.text;
+  const mk_screen_row_t* d_rows = s.last.d_rows;
+  const size_t ntiles = div_up(n, FL_SPAN);
+  // meta: FlStatus (16) | start[nrows + 1] | len[nrows + 1] | dst[nrows + 1] | tile_pre[ntiles] | tile_cnt[ntiles]
+  if ((rc = mk_buf_reserve(c, f.meta, 16 + (3 * (nrows + 1) + ntiles) * sizeof(u64) + ntiles * sizeof(unsigned))) != MK_OK) return rc;
+  if ((rc = mk_buf_reserve(c, f.d_keep, nrows)) != MK_OK) return rc;
+  FlStatus* d_st = (FlStatus*)f.meta.p;
+  u64* start = (u64*)((char*)f.meta.p + 16);
+  u64* len = start + nrows + 1;
+  u64* dst = len + nrows + 1;
+  u64* tile_pre = dst + nrows + 1;
+  unsigned* tile_cnt = (unsigned*)(tile_pre + ntiles);
+  uint8_t* d_keep = (uint8_t*)f.d_keep.p;
+  size_t tmp = 0;
+  MK_HIP(rocprim::exclusive_scan((void*)nullptr, tmp, (const u64*)len, dst, 0ull, nrows + 1, rocprim::plus<u64>(), c->stream));
+  if ((rc = mk_buf_reserve(c, f.scan_tmp, tmp ? tmp : 16)) != MK_OK) return rc;
+
+  MK_HIP(hipMemsetAsync(d_st, 0, sizeof(FlStatus), c->stream));
+  if ((rc = f.place.begin()) != MK_OK) return rc;
+  hipLaunchKernelGGL(fl_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, text, (u64)n, tile_cnt);
+  hipLaunchKernelGGL(fl_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, (u64)n, nrows,
+                     s.last.headless ? 1 : 0, start, d_st);
+  hipLaunchKernelGGL(fl_starts_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, text, (u64)n, (const u64*)tile_pre,
+                     (u64)(s.last.headless ? 1 : 0), nrows, start);
+  MK_HIP(hipGetLastError());
+  // (the lengths are only added up before the guard below has compared the two views: no address is made of them)
+  hipLaunchKernelGGL(fl_decide_k, dim3(grid_for(nrows + 1, 256, 4096)), dim3(256), 0, c->stream, d_rows, (const u64*)start, nrows,
+                     (u64)f.rule.min_hits, (u64)f.rule.min_ppm, f.invert, d_keep, len, d_st);
+  MK_HIP(hipGetLastError());
+  MK_HIP(rocprim::exclusive_scan(f.scan_tmp.p, tmp, (const u64*)len, dst, 0ull, nrows + 1, rocprim::plus<u64>(), c->stream));
+  if ((rc = f.place.end()) != MK_OK) return rc;
+  FlStatus h{};
+  u64 piece_out = 0, start0 = 0;
+  MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&piece_out, dst + nrows, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&start0, start, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = f.place.add_to(f.st.s_place)) != MK_OK) return rc;
+  if (h.headers + (s.last.headless ? 1 : 0) != nrows) {
+    c->err = std::string(s.what) + ": " + std::to_string(h.headers) + " header lines in the text, " +
+             std::to_string(nrows - (s.last.headless ? 1 : 0)) + " in the parsed stream (internal error)";
+    return MK_ERR_STATE;
+  }
+  if (piece_out > n - start0) {
+    c->err = std::string(s.what) + ": the output of a piece is longer than its records (internal error)";
+    return MK_ERR_STATE;
+  }
+  f.st.preamble += start0;
+  f.st.records_out += h.records_out;
+  const size_t at = f.bytes_out;
+  f.bytes_out += (size_t)piece_out;
+
+  // rows and keep of the piece, where the caller has room for them
+  if (first + nrows <= f.cap) {
+    const auto t1 = MkClock::now();
+    const hipMemcpyKind kind = f.device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (f.rows) MK_HIP(hipMemcpyAsync(f.rows + first, d_rows, nrows * sizeof(mk_screen_row_t), kind, c->stream));
+    if (f.keep) MK_HIP(hipMemcpyAsync(f.keep + first, d_keep, nrows, kind, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    if (!f.device) f.st.s_write += mk_since(t1);
+  }
+  if (!piece_out || f.bytes_out > f.out_cap) return MK_OK;  // (no room: the call goes on adding up and answers MK_ERR_RANGE)
+
+  // the gather: into the caller's device memory, or into a staging buffer that is copied to the host
+  uint8_t* d_out = f.out + at;
+  if (!f.device) {
+    if ((rc = mk_buf_reserve(c, f.stage, (size_t)piece_out)) != MK_OK) return rc;
+    d_out = (uint8_t*)f.stage.p;
+  }
+  const u64 head = std::min<u64>((16 - ((uintptr_t)d_out & 15)) & 15, piece_out);
+  const u64 nbody = (piece_out - head) / 16, tail_at = head + 16 * nbody;
+  if ((rc = f.gather.begin()) != MK_OK) return rc;
+  if (nbody)
+    hipLaunchKernelGGL(fl_gather_k, dim3((unsigned)div_up((size_t)nbody, 256 * FL_CHUNKS)), dim3(256), 0, c->stream, text, (u64)n,
+                       (const u64*)start, (const u64*)dst, nrows, head, nbody, d_out);
+  if (head || tail_at < piece_out)
+    hipLaunchKernelGGL(fl_edges_k, dim3(1), dim3(64), 0, c->stream, text, (const u64*)start, (const u64*)dst, nrows, head, tail_at,
+                       piece_out, d_out);
+  MK_HIP(hipGetLastError());
+  if ((rc = f.gather.end()) != MK_OK) return rc;
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = f.gather.add_to(f.st.s_gather)) != MK_OK) return rc;
+  if (!f.device) {
+    const auto t1 = MkClock::now();
+    MK_HIP(hipMemcpyAsync(f.out + at, d_out, (size_t)piece_out, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    f.st.s_write += mk_since(t1);
+  }
+  return MK_OK;
+}
+
+// How both calls check their own arguments, open as the screen calls open, and end; body(s, f): the pieces.
+template <class Body>
+static int fl_run(mk_ctx* c, const char* what, unsigned flags, const mk_filter_rule_t* rule, FlCall* f, size_t* out_len,
+                  size_t* nrows, mk_filter_t* st, Body&& body) {
+  if (!rule) { c->err = std::string(what) + ": rule is NULL"; return MK_ERR_ARG; }
+  if (flags & ~(MK_FILTER_FOLD | MK_FILTER_INVERT)) { c->err = std::string(what) + ": unknown flag"; return MK_ERR_ARG; }
+  if (rule->min_hits < 1) { c->err = std::string(what) + ": min_hits must be 1 or more"; return MK_ERR_ARG; }
+  if (rule->min_ppm > 1000000u) { c->err = std::string(what) + ": min_ppm must lie in 0..1000000"; return MK_ERR_ARG; }
+  const size_t cap = (f->rows || f->keep) ? f->cap : ~(size_t)0;
+  f->cap = cap;
+  int rc = sc_run(c, what, flags & MK_FILTER_FOLD, rule->at_least, cap, nrows, &f->st.screen, [&](ScCall& s) { return body(s); });
+  if (rc != MK_OK && rc != MK_ERR_RANGE) return rc;
+  if (out_len) *out_len = f->bytes_out;
+  if (rc != MK_OK) return rc;
+  if (f->bytes_out > f->out_cap) {
+    c->err = std::string(what) + ": the output holds " + std::to_string(f->bytes_out) + " bytes, out has room for " + std::to_string(f->out_cap);
+    return MK_ERR_RANGE;
+  }
+  f->st.bytes_out = f->bytes_out;
+  if (st) *st = f->st;
+  return MK_OK;
+}
+
+extern "C" int mk_filter_device(mk_ctx* c, const uint8_t* d_text, size_t n, unsigned flags, const mk_filter_rule_t* rule,
+                                uint8_t* d_out, size_t out_cap, size_t* out_len, mk_screen_row_t* d_rows, uint8_t* d_keep, size_t cap,
+                                size_t* nrows, mk_filter_t* st) {
+  if (!c) return MK_ERR_ARG;
+  if ((n && !d_text) || (out_cap && !d_out)) { c->err = "mk_filter_device: NULL buffer"; return MK_ERR_ARG; }
+  FlCall f(c, rule ? *rule : mk_filter_rule_t{}, (flags & MK_FILTER_INVERT) != 0, d_out, out_cap, d_rows, d_keep, cap, true);
+  return fl_run(c, "mk_filter_device", flags, rule, &f, out_len, nrows, st, [&](ScCall& s) -> int {
+    if (!n) return MK_OK;
+    const int rc = sc_piece(s, d_text, n, nullptr, ~(size_t)0, &f.d_rows, nullptr);
+    return rc != MK_OK ? rc : fl_piece(s, f, n, 0);
+  });
+}
+
+extern "C" int mk_filter_text(mk_ctx* c, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, const mk_filter_rule_t* rule,
+                              uint8_t* out, size_t out_cap, size_t* out_len, mk_screen_row_t* rows, uint8_t* keep, size_t cap,
+                              size_t* nrows, mk_filter_t* st) {
+  if (!c) return MK_ERR_ARG;
+  if ((n && !text) || (out_cap && !out)) { c->err = "mk_filter_text: NULL buffer"; return MK_ERR_ARG; }
+  FlCall f(c, rule ? *rule : mk_filter_rule_t{}, (flags & MK_FILTER_INVERT) != 0, out, out_cap, rows, keep, cap, false);
+  return fl_run(c, "mk_filter_text", flags, rule, &f, out_len, nrows, st, [&](ScCall& s) -> int {
+    return sc_text_pieces(s, text, n, piece_bytes, [&](const uint8_t* d_piece, size_t len) -> int {
+      const size_t first = s.rows_seen;
+      const int rc = sc_piece(s, d_piece, len, nullptr, ~(size_t)0, &f.d_rows, nullptr);
+      return rc != MK_OK ? rc : fl_piece(s, f, len, first);
+    });
+  });
+}

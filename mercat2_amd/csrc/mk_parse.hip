@@ -16,7 +16,7 @@
 // so that no window can span two records.  A blank inside a sequence line is kept iff a
 // non-blank follows before the line ends (strip() only trims the ends) -- decided by a short
 // forward look-ahead, which only blanks pay for.
-#include "mk_common.h"
+#include "mk_device.h"
 
 #define PT 256   // threads per workgroup
 #define PB 32    // bytes per thread
@@ -47,25 +47,20 @@ __device__ __forceinline__ PMap pm_compose(const PMap& a, const PMap& b) {  // a
   return r;
 }
 
-__device__ __forceinline__ bool is_nl(unsigned c) { return c == 10u || c == 13u; }
-__device__ __forceinline__ bool is_blank(unsigned c) {  // str.strip() set minus the newlines
-  return c == 32u || c == 9u || c == 11u || c == 12u || (c >= 28u && c <= 31u);
-}
-
 // Does a non-blank character follow position i before the line ends?
 __device__ __forceinline__ bool blank_is_inner(const uint8_t* __restrict__ raw, size_t i, size_t n) {
   size_t j = i + 1;
-  while (j < n && is_blank(raw[j])) ++j;
-  return j < n && !is_nl(raw[j]);
+  while (j < n && mk_is_blank(raw[j])) ++j;
+  return j < n && !mk_is_nl(raw[j]);
 }
 
 // One transducer step from state q on byte ch. Returns the emitted byte in `out` (valid iff true).
 __device__ __forceinline__ bool pstep(unsigned& q, unsigned ch, const uint8_t* __restrict__ raw, size_t i, size_t n,
                                       unsigned& out) {
-  if (is_nl(ch)) { q = Q_L0; return false; }
+  if (mk_is_nl(ch)) { q = Q_L0; return false; }
   if (q == Q_H) return false;
   if (q == Q_L0) {
-    if (is_blank(ch)) return false;
+    if (mk_is_blank(ch)) return false;
     if (ch == '>') { q = Q_H; out = MK_SEP; return true; }
     q = Q_S;
     out = ch;
@@ -73,7 +68,7 @@ __device__ __forceinline__ bool pstep(unsigned& q, unsigned ch, const uint8_t* _
   }
   // Q_S
   out = ch;
-  if (is_blank(ch)) return blank_is_inner(raw, i, n);
+  if (mk_is_blank(ch)) return blank_is_inner(raw, i, n);
   return ch != '*';
 }
 
@@ -85,7 +80,7 @@ __device__ __forceinline__ PMap thread_map(const uint8_t* __restrict__ raw, size
     size_t i = base + j;
     if (i >= n) break;
     unsigned ch = b[j], out;
-    if (is_nl(ch)) { q0 = q1 = q2 = Q_L0; continue; }
+    if (mk_is_nl(ch)) { q0 = q1 = q2 = Q_L0; continue; }
     if (q0 == q1 && q1 == q2) {  // converged (the common case after the first newline)
       unsigned e = pstep(q0, ch, raw, i, n, out) ? 1u : 0u;
       q1 = q2 = q0;

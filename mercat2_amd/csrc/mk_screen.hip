@@ -10,9 +10,8 @@
 // ROLLS the packed key one symbol at a time, keeps "symbols since the last separator" (is this a window?) and "symbols
 // since the last byte outside the alphabet" (packed key or text key?), probes where lk_probe_k would probe the same k
 // bytes, and accumulates while it stays in one record.  Integer adds, min and max only: exact in any order.
-#include "mk_tsvpieces.h"
+#include "mk_screenpiece.h"
 #include "mk_tableview.h"
-#include <algorithm>
 
 #define SC_RUN 32                // window starts a lane owns
 #define SC_SPAN (256 * SC_RUN)   // ... a workgroup: one tile of the record scan
@@ -257,18 +256,6 @@ __global__ void __launch_bounds__(256) sc_probe_k(const uint8_t* __restrict__ se
 }
 
 // ------------------------------------------------------------------------------------------ host side
-struct ScCall {
-  mk_ctx* c;
-  const char* what;
-  bool fold;
-  u64 at_least;
-  MkDevBuf scratch;  // ScStatus | tile_pre[ntiles] | tile_cnt[ntiles]
-  MkTimed parse{c}, probe{c};  // (the events of the first piece serve every piece)
-  mk_screen_t out{};
-  size_t rows_seen = 0;
-  ~ScCall() { buf_free(scratch); }
-};
-
 static int sc_launch_probe(ScCall& s, size_t seq_len, const u64* tile_pre, u64 row_base, mk_screen_row_t* d_rows, ScStatus* d_st) {
   mk_ctx* c = s.c;
   const LkTables t = lk_tables(c);
@@ -288,11 +275,9 @@ static int sc_launch_probe(ScCall& s, size_t seq_len, const u64* tile_pre, u64 r
   return MK_OK;
 }
 
-// One piece of n bytes at d_text (device memory, whole records): parsed, scanned, and -- where there is room for all its
-// rows -- probed into d_rows (room rows; nullptr: the call's own buffer `own`, copied to h_rows).  The piece's records
-// are added to s.rows_seen either way.  The stream is idle afterwards.
-static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows, size_t room, MkDevBuf* own,
-                    mk_screen_row_t* h_rows) {
+// The piece routine both callers share (declared in mk_screenpiece.h).
+int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows, size_t room, MkDevBuf* own,
+             mk_screen_row_t* h_rows) {
   mk_ctx* c = s.c;
   int rc;
   const size_t ntiles = div_up(n, SC_SPAN);  // (the stream is no longer than the text)
@@ -307,6 +292,7 @@ static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t*
     MK_HIP(hipMemcpyAsync(c->raw.p, d_text, n, hipMemcpyDeviceToDevice, c->stream));
     d_text = (const uint8_t*)c->raw.p;
   }
+  s.last = {d_text, nullptr, 0, false};
   MkChunkInfo info{};
   ScStatus h{};
   MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
@@ -332,11 +318,14 @@ static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t*
   s.out.bytes += n;
   s.out.pieces += 1;
   if (h.headless) s.out.headless = 1;
+  s.last.nrows = nrows;
+  s.last.headless = h.headless != 0;
   if (!nrows || nrows > room) return MK_OK;  // (too many: the call goes on counting records and answers MK_ERR_RANGE)
   if (!d_rows) {
     if ((rc = mk_buf_reserve(c, *own, nrows * sizeof(mk_screen_row_t))) != MK_OK) return rc;
     d_rows = (mk_screen_row_t*)own->p;
   }
+  s.last.d_rows = d_rows;
   if ((rc = s.probe.begin()) != MK_OK) return rc;
   hipLaunchKernelGGL(sc_rows_init_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
   if (info.seq_len && (rc = sc_launch_probe(s, (size_t)info.seq_len, tile_pre, h.headless ? 0 : 1, d_rows, d_st)) != MK_OK) return rc;
@@ -363,32 +352,6 @@ static int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t*
   return MK_OK;
 }
 
-// How both calls open (lk_open's rules) and end; body: the pieces.
-template <class Body>
-static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least, size_t cap, size_t* nrows, mk_screen_t* st,
-                  Body&& body) {
-  const auto t0 = MkClock::now();
-  ScCall s{c, what, false, at_least};
-  int rc = lk_open(c, what, flags, &s.fold);
-  if (rc != MK_OK) return rc;
-  if (at_least < 1) { c->err = std::string(what) + ": at_least must be 1 or more"; return MK_ERR_ARG; }
-  const bool profile = c->profile;  // (the parser's launches are no part of the counting figures)
-  c->profile = false;
-  rc = body(s);
-  c->profile = profile;
-  (void)hipStreamSynchronize(c->stream);
-  if (rc != MK_OK) return rc;
-  if (nrows) *nrows = s.rows_seen;
-  if (s.rows_seen > cap) {
-    c->err = std::string(what) + ": the text holds " + std::to_string(s.rows_seen) + " records, rows has room for " + std::to_string(cap);
-    return MK_ERR_RANGE;
-  }
-  s.out.records = s.rows_seen;
-  s.out.s_total = mk_since(t0);
-  if (st) *st = s.out;
-  return MK_OK;
-}
-
 extern "C" int mk_screen_device(mk_ctx* c, const uint8_t* d_text, size_t n, unsigned flags, uint64_t at_least,
                                 mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_screen_t* st) {
   if (!c) return MK_ERR_ARG;
@@ -403,29 +366,10 @@ extern "C" int mk_screen_text(mk_ctx* c, const uint8_t* text, size_t n, size_t p
   if ((n && !text) || (cap && !rows)) { c->err = "mk_screen_text: NULL buffer"; return MK_ERR_ARG; }
   MkDevBuf d_rows;
   const int rc = sc_run(c, "mk_screen_text", flags, at_least, cap, nrows, st, [&](ScCall& s) -> int {
-    if (!n) return MK_OK;
-    // pieces: cut where a record starts once a piece holds piece_bytes (mk_record_cuts; the loader's default and limits)
-    size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
-    piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
-    std::vector<uint64_t> cuts(n / piece + 2);
-    size_t ncuts = 0;
-    int r = mk_record_cuts(text, n, piece, (size_t)4 << 20, cuts.data(), cuts.size(), &ncuts);
-    if (r != MK_OK) { c->err = "mk_screen_text: the record scanner failed (internal error)"; return MK_ERR_STATE; }
-    cuts.resize(ncuts);
-    cuts.push_back(n);
-    size_t at = 0;
-    for (const uint64_t end : cuts) {
-      const size_t len = (size_t)end - at;
-      if (!len) continue;
-      if ((r = mk_buf_reserve(c, c->raw, len + 64)) != MK_OK) return r;
-      const auto t1 = MkClock::now();
-      MK_HIP(hipMemcpyAsync(c->raw.p, text + at, len, hipMemcpyHostToDevice, c->stream));
-      s.out.s_read += mk_since(t1);
+    return sc_text_pieces(s, text, n, piece_bytes, [&](const uint8_t* d_piece, size_t len) {
       const size_t room = cap > s.rows_seen ? cap - s.rows_seen : 0;
-      if ((r = sc_piece(s, (const uint8_t*)c->raw.p, len, nullptr, room, &d_rows, rows)) != MK_OK) return r;
-      at = (size_t)end;
-    }
-    return MK_OK;
+      return sc_piece(s, d_piece, len, nullptr, room, &d_rows, rows);
+    });
   });
   buf_free(d_rows);
   return rc;

@@ -1,0 +1,88 @@
+// mk_screenpiece.h -- the piece routine of mk_screen.hip for the calls that read a text record by record against the
+// tables: mk_screen_* (mk_screen.hip) reports the rows, mk_filter_* (mk_filter.hip) goes on from them to the records'
+// bytes.  One opening (sc_run), one way of cutting a host text into pieces (sc_text_pieces), one piece routine
+// (sc_piece: parse, record scan, probe) -- the kernels and their launches live in mk_screen.hip.
+#pragma once
+#include "mk_tsvpieces.h"
+#include "mk_device.h"
+#include <algorithm>
+#include <vector>
+
+struct ScCall {
+  mk_ctx* c;
+  const char* what;
+  bool fold;
+  u64 at_least;
+  MkDevBuf scratch;  // ScStatus | tile_pre[ntiles] | tile_cnt[ntiles]
+  MkTimed parse{c}, probe{c};  // (the events of the first piece serve every piece)
+  mk_screen_t out{};
+  size_t rows_seen = 0;
+  // what the last sc_piece left on the device: the text as the parser read it (16-byte aligned: the caller's bytes or
+  // their copy in c->raw), its rows (nullptr: none, or no room for them) and whether row 0 has no header line
+  struct {
+    const uint8_t* text = nullptr;
+    mk_screen_row_t* d_rows = nullptr;
+    size_t nrows = 0;
+    bool headless = false;
+  } last;
+  ~ScCall() { buf_free(scratch); }
+};
+
+// One piece of n bytes at d_text (device memory, whole records): parsed, scanned, and -- where there is room for all its
+// rows -- probed into d_rows (room rows; nullptr: the call's own buffer `own`, copied to h_rows if that is given).  The
+// piece's records are added to s.rows_seen either way.  The stream is idle afterwards.
+int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows, size_t room, MkDevBuf* own, mk_screen_row_t* h_rows);
+
+// How the calls open (lk_open's rules) and end; body: the pieces.  cap: rows the caller has room for.
+template <class Body>
+static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least, size_t cap, size_t* nrows, mk_screen_t* st,
+                  Body&& body) {
+  const auto t0 = MkClock::now();
+  ScCall s{c, what, false, at_least};
+  int rc = lk_open(c, what, flags, &s.fold);
+  if (rc != MK_OK) return rc;
+  if (at_least < 1) { c->err = std::string(what) + ": at_least must be 1 or more"; return MK_ERR_ARG; }
+  const bool profile = c->profile;  // (the parser's launches are no part of the counting figures)
+  c->profile = false;
+  rc = body(s);
+  c->profile = profile;
+  (void)hipStreamSynchronize(c->stream);
+  if (rc != MK_OK) return rc;
+  if (nrows) *nrows = s.rows_seen;
+  if (s.rows_seen > cap) {
+    c->err = std::string(what) + ": the text holds " + std::to_string(s.rows_seen) + " records, rows has room for " + std::to_string(cap);
+    return MK_ERR_RANGE;
+  }
+  s.out.records = s.rows_seen;
+  s.out.s_total = mk_since(t0);
+  if (st) *st = s.out;
+  return MK_OK;
+}
+
+// A host text in pieces: cut where a record starts once a piece holds piece_bytes (mk_record_cuts; the loader's default
+// and limits), each copied into c->raw and handed to piece(d_piece, len).
+template <class Piece>
+static int sc_text_pieces(ScCall& s, const uint8_t* text, size_t n, size_t piece_bytes, Piece&& piece_fn) {
+  mk_ctx* c = s.c;
+  if (!n) return MK_OK;
+  size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
+  piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
+  std::vector<uint64_t> cuts(n / piece + 2);
+  size_t ncuts = 0;
+  int r = mk_record_cuts(text, n, piece, (size_t)4 << 20, cuts.data(), cuts.size(), &ncuts);
+  if (r != MK_OK) { c->err = std::string(s.what) + ": the record scanner failed (internal error)"; return MK_ERR_STATE; }
+  cuts.resize(ncuts);
+  cuts.push_back(n);
+  size_t at = 0;
+  for (const uint64_t end : cuts) {
+    const size_t len = (size_t)end - at;
+    if (!len) continue;
+    if ((r = mk_buf_reserve(c, c->raw, len + 64)) != MK_OK) return r;
+    const auto t1 = MkClock::now();
+    MK_HIP(hipMemcpyAsync(c->raw.p, text + at, len, hipMemcpyHostToDevice, c->stream));
+    s.out.s_read += mk_since(t1);
+    if ((r = piece_fn((const uint8_t*)c->raw.p, len)) != MK_OK) return r;
+    at = (size_t)end;
+  }
+  return MK_OK;
+}

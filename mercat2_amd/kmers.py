@@ -136,3 +136,26 @@ def screen_reads(table: "native.Counter", file: Union[str, Path], at_least: int 
     if len(names) != rows.shape[0]:
         raise RuntimeError("screen_reads: %d header names for %d records" % (len(names), rows.shape[0]))
     return names, rows
+
+
+def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 1, min_hits: int = 1,
+                 min_frac: float = 0.0, invert: bool = False) -> Dict[str, int]:
+    """The records of a FASTA or FASTQ file that match a table still on the GPU (Counter.filter), written to ``out_path``
+    -- gzip (level 1) if that name ends in '.gz', plain bytes otherwise; with ``invert`` the records that do not match.  A
+    record matches iff at least ``min_hits`` of its k-mers occur ``at_least`` times in the table and they are at least
+    ``min_frac`` (0..1) of its k-mers.  The file is read as screen_reads reads it: '.gz' inflated on the host, a FASTQ
+    file ('.fq' / '.fastq', plain or '.gz') first converted as MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is
+    always FASTA, the text MerCat2 itself counts, and the qualities are gone.  The records are copied byte for byte, in
+    order.  A canonical table folds the windows.  Returns {"records", "kept", "bytes_in", "bytes_out"}."""
+    min_ppm = native.ppm_of_fraction(min_frac)
+    text = read_fasta_bytes(file)
+    if str(file).lower().endswith(FASTQ_SUFFIXES):
+        text, _ = native.fq2fa(text)
+    out, keep, _ = table.filter(text, at_least, min_hits, min_ppm, invert)
+    if str(out_path).lower().endswith(".gz"):
+        with gzip.open(out_path, "wb", compresslevel=1) as fh:
+            fh.write(out)
+    else:
+        with open(out_path, "wb") as fh:
+            fh.write(out)
+    return {"records": int(keep.shape[0]), "kept": int(keep.sum()), "bytes_in": len(text), "bytes_out": len(out)}

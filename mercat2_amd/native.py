@@ -35,12 +35,13 @@ ABI_SYMBOLS = [
     "mk_export_stats", "mk_share_table", "mk_set_fastq", "mk_fastq_stats", "mk_fq2fa", "mk_gram", "mk_gram_matrix",
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
-    "mk_screen_text", "mk_screen_device", "mk_table_op",
+    "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
 LOOKUP_FOLD = 1
 SCREEN_FOLD = 1
+FILTER_FOLD, FILTER_INVERT = 1, 2
 # mk_table_op: f(ca, cb) per key (include/mercat_hip.h)
 OP_MIN, OP_MAX, OP_SUM, OP_LEFT, OP_ONLY, OP_DIFF = range(6)
 OPS = {"min": OP_MIN, "max": OP_MAX, "sum": OP_SUM, "left": OP_LEFT, "only": OP_ONLY, "diff": OP_DIFF}
@@ -129,6 +130,31 @@ class Screen(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FilterRule(C.Structure):
+    """mk_filter_rule_t (include/mercat_hip.h)."""
+    _fields_ = [("at_least", C.c_uint64), ("min_hits", C.c_uint64), ("min_ppm", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Filter(C.Structure):
+    """mk_filter_t (include/mercat_hip.h)."""
+    _fields_ = ([("screen", Screen)] + [(n, C.c_uint64) for n in ("records_out", "bytes_out", "preamble")] +
+                [(n, C.c_double) for n in ("s_place", "s_gather", "s_write")])
+
+    def as_dict(self):
+        d = self.screen.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+def ppm_of_fraction(min_frac: float) -> int:
+    """min_ppm of mk_filter_rule_t for "at least this fraction of the record's k-mers are hits": round(min_frac * 10^6);
+    ValueError outside 0..1 (and for a NaN)."""
+    f = float(min_frac)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError("min_frac %r: must lie in 0..1" % (min_frac,))
+    return int(round(f * 1_000_000))
 
 
 class Histo(C.Structure):
@@ -280,6 +306,10 @@ def lib() -> C.CDLL:
         "mk_screen_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp,
                                      C.POINTER(Screen)]),
         "mk_screen_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp, C.POINTER(Screen)]),
+        "mk_filter_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(FilterRule), C.c_void_p, C.c_size_t, szp,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Filter)]),
+        "mk_filter_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(FilterRule), C.c_void_p, C.c_size_t, szp,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Filter)]),
         "mk_table_op": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(TableOp)]),
     }
     L.mk_version.restype = C.c_char_p
@@ -959,6 +989,49 @@ class Counter:
         n, st = C.c_size_t(0), Screen()
         self._check(self._L.mk_screen_device(self._h, ptr, int(nbytes), SCREEN_FOLD if self._fold_flag(fold) else 0, int(at_least),
                                              out_ptr, int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
+    # -- filtering: FASTA text in, the bytes of the matched (or unmatched) records out; the table is only read
+    def _filter_flags(self, fold: Optional[bool], invert: bool) -> int:
+        return (FILTER_FOLD if self._fold_flag(fold) else 0) | (FILTER_INVERT if invert else 0)
+
+    def filter(self, path_or_bytes, at_least: int = 1, min_hits: int = 1, min_ppm: int = 0, invert: bool = False,
+               fold: Optional[bool] = None, piece_bytes: int = 0, info: Optional[dict] = None) -> Tuple[bytes, np.ndarray, np.ndarray]:
+        """mk_filter_text: (out, keep, rows) -- ``out`` the bytes of the records of the FASTA text (a path to a plain file,
+        or the text itself as bytes) that match the rule, in text order and byte for byte; with ``invert`` of those that
+        do not.  A record matches iff it has windows, at least ``min_hits`` of them are hits (count >= ``at_least``) and
+        hits * 10^6 >= ``min_ppm`` * windows.  ``keep``: one bool per record, True where it was emitted; ``rows``: the
+        (records, 5) uint64 array Counter.screen gives for the same text.  ``fold`` None: fold iff the context is
+        canonical.  ``info``, if given, receives the mk_filter_t fields (those of mk_screen_t beside them)."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(held == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        keep = np.zeros(cap, dtype=np.uint8)
+        out = np.empty(max(size, 1), dtype=np.uint8)  # (the output is never longer than the text)
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Filter()
+        rule = FilterRule(int(at_least), int(min_hits), int(min_ppm), 0)
+        self._check(self._L.mk_filter_text(self._h, addr, size, int(piece_bytes), self._filter_flags(fold, invert), C.byref(rule),
+                                           out.ctypes.data, size, C.byref(out_len), rows.ctypes.data, keep.ctypes.data, cap,
+                                           C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), keep[: n.value].astype(bool), rows[: n.value]
+
+    def filter_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, rows_ptr: int = 0, keep_ptr: int = 0, cap: int = 0,
+                      at_least: int = 1, min_hits: int = 1, min_ppm: int = 0, invert: bool = False,
+                      fold: Optional[bool] = None) -> dict:
+        """mk_filter_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> the bytes of the emitted
+        records at device address ``out_ptr`` (room for ``out_cap``), and, where given, the rows (five uint64 a record) at
+        ``rows_ptr`` and one keep byte a record at ``keep_ptr`` with room for ``cap`` records each -- all on this context's
+        GPU.  Returns the mk_filter_t fields: "bytes_out" bytes were written, "records" rows."""
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Filter()
+        rule = FilterRule(int(at_least), int(min_hits), int(min_ppm), 0)
+        self._check(self._L.mk_filter_device(self._h, ptr, int(nbytes), self._filter_flags(fold, invert), C.byref(rule), out_ptr or None,
+                                             int(out_cap), C.byref(out_len), rows_ptr or None, keep_ptr or None, int(cap), C.byref(n),
+                                             C.byref(st)))
         return st.as_dict()
 
     # -- results
