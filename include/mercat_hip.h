@@ -440,6 +440,45 @@ int mk_filter_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flag
                      uint8_t* d_out, size_t out_cap, size_t* out_len,
                      mk_screen_row_t* d_rows, uint8_t* d_keep, size_t cap, size_t* nrows, mk_filter_t* st);
 
+/* ---- sequences in, the count under every k-mer window out: the vector mk_screen_* folds into five numbers a record,
+ *      position by position (Jellyfish `query -s`, a k-mer coverage track along a contig, the first window whose count
+ *      drops), and the median of every record's counts (khmer's count-median, the decision of normalize-by-median) ----
+ * Text, records, windows, probing, fold, opening rules and errors are mk_screen_*'s, word for word: same parser, same
+ * rows (rows[r] is the screen row of record r for the same text and at_least), same mk_screen_t figures (st->screen; its
+ * s_total is the wall time of this whole call), the table only read and made final first, MK_ERR_STATE with an open
+ * chunk or a refused one, MK_ERR_NON_ASCII, the fold rule (MK_TRACK_FOLD = MK_SCREEN_FOLD), pieces cut by
+ * mk_record_cuts, device text of any alignment, the stream idle afterwards, the counting figures and the export
+ * untouched.
+ * Record r has rows[r].windows windows; window j starts at the record's j-th kept character.  counts[offsets[r] + j] is
+ * the count mk_lookup would return for those k bytes -- under min(window, reverse complement) with MK_TRACK_FOLD -- 0
+ * when the k-mer is absent.  offsets[0] = 0, offsets[r + 1] = offsets[r] + rows[r].windows, offsets[nrows] = *nwindows:
+ * offsets needs cap + 1 entries, and they number the whole call, not a piece.  median[r] is element windows / 2 of the
+ * record's counts sorted ascending, as stored (so clipped under MK_TRACK_SAT32) -- khmer's rule -- and 0 for a record
+ * without windows.  With MK_TRACK_SAT32 counts and median are uint32_t, min(count, 2^32 - 1), and st->saturated counts
+ * the elements clipped; without it both are uint64_t.
+ * offsets, median and rows may each be NULL (cap is ignored when all three are); with median NULL nothing of the median
+ * runs.  counts_cap is in elements.  With counts_cap or cap too small: MK_ERR_RANGE, the needed sizes in *nwindows and
+ * *nrows, nothing written past either -- every piece is still walked to learn them (counts = NULL, counts_cap = 0 is the
+ * sizing call).  An unknown flag bit or at_least == 0 is MK_ERR_ARG and the message names it.  st may be NULL.
+ * mk_track_text: host memory in and out, piece by piece (each piece's counts are appended to counts by its copy back).
+ * mk_track_device: text, counts, offsets, median and rows in DEVICE memory of the context's GPU, one piece; the text at
+ * any address, the others aligned to their elements (MK_ERR_ARG otherwise); the median takes fewer than 2^32 windows. */
+#define MK_TRACK_FOLD  1u   /* = MK_SCREEN_FOLD */
+#define MK_TRACK_SAT32 2u   /* counts (and medians) are uint32_t, min(count, 2^32 - 1) */
+typedef struct mk_track_t {
+  mk_screen_t screen;          /* as mk_screen_* fills it for the same text and at_least */
+  uint64_t windows_out;        /* elements written to counts */
+  uint64_t saturated;          /* elements clipped by MK_TRACK_SAT32 */
+  /* seconds: HIP-event time of the offsets scan; of the track kernel; of the sort and the pick; host time in the copies back */
+  double s_place, s_track, s_median, s_write;
+} mk_track_t;
+int mk_track_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, uint64_t at_least,
+                  void* counts, size_t counts_cap, size_t* nwindows,
+                  uint64_t* offsets, void* median, mk_screen_row_t* rows, size_t cap, size_t* nrows, mk_track_t* st);
+int mk_track_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, uint64_t at_least,
+                    void* d_counts, size_t counts_cap, size_t* nwindows,
+                    uint64_t* d_offsets, void* d_median, mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_track_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

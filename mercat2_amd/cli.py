@@ -21,7 +21,9 @@ sample, looked up in those tables (mk_lookup_file).  -histo [HIGH] writes every 
 sample of FILE's type, screen_<type>/<sample>_screen.tsv: per record of FILE its k-mers, how many of them the sample's table
 holds, and how abundant they are (mk_screen_text).  -filter FILE writes, for every sample of FILE's type,
 filter_<type>/<sample>_<matched|unmatched>.fna (.faa): the records of FILE that share k-mers with the sample's table, or those
-that do not, copied out on the GPU (mk_filter_text).  -against FILE -op OP writes, for every sample of FILE's type,
+that do not, copied out on the GPU (mk_filter_text).  -track FILE writes, for every sample of FILE's type,
+track_<type>/<sample>_track.txt -- per record of FILE the count of every one of its k-mers in the sample's table, in read
+order -- and track_<type>/<sample>_median.tsv with the median of those counts (mk_track_text).  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
 (mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
@@ -41,7 +43,7 @@ from .fasta import _write_clean_gz, fq2fa_background, fq2fa_text, removeN_backgr
 from .kmers import read_fasta_bytes
 from .harness import load_table, run_raw_clean, run_raw_fastq, run_sample, run_text
 from .report import (merge_counters, merge_counters_T, write_against_tsvs, write_histo_files, write_histo_tsv, write_query_tsv,
-                     write_screen_tsv)
+                     write_screen_tsv, write_track_median_tsv, write_track_txt)
 
 FILTER_KEEP = ("matched", "unmatched")
 AGAINST_OPS = ("min", "max", "sum", "left", "only", "diff")  # native.OPS, for the parser (which loads no library)
@@ -84,6 +86,13 @@ def parseargs(argv=None):
                         "the records of FILE that match the sample's table, or those that do not (-filter_keep), byte for "
                         "byte and in order.  A FASTQ file is first converted as MerCat2's fq2fa converts it, so the output is "
                         "FASTA, the text MerCat2 itself counts; with -canonical the k-mers are folded")
+    p.add_argument("-track", type=str, required=False, metavar="FILE",
+                   help="a FASTA or FASTQ file (plain or .gz) of reads or contigs to track against the tables on the GPU: for "
+                        "every sample of FILE's type (nucleotide / protein by its extension; FASTQ is nucleotide), "
+                        "track_<type>/<sample>_track.txt with, per record of FILE, a '>name' line and one line of the counts "
+                        "of its k-mers in the sample, in read order (0: absent), and track_<type>/<sample>_median.tsv with "
+                        "each record's k-mers, the median of their counts, and their sum, smallest and largest")
+    p.add_argument("-track_sat32", action="store_true", help="-track: 32-bit counts, clipped at 2^32 - 1 (half the bytes moved)")
     p.add_argument("-filter_min", type=int, default=None, metavar="N", help="-filter: a k-mer is a hit from this count on [1]")
     p.add_argument("-filter_hits", type=int, default=None, metavar="N", help="-filter: a record matches from this many hits on [1]")
     p.add_argument("-filter_frac", type=float, default=None, metavar="F",
@@ -156,6 +165,15 @@ def parseargs(argv=None):
             p.error(f"-screen {args.screen}: the extension names neither a nucleotide, a protein nor a FASTQ file")
     if not 1 <= args.screen_min < 1 << 64:
         p.error(f"-screen_min {args.screen_min}: must be 1 or more")
+    args.track_kind = None
+    if args.track:
+        if not os.path.isfile(args.track):
+            p.error(f"file '{args.track}' is not valid.\n")
+        args.track_kind = classify(Path(args.track).expanduser().absolute(), True)[0]
+        if not args.track_kind:
+            p.error(f"-track {args.track}: the extension names neither a nucleotide, a protein nor a FASTQ file")
+    elif args.track_sat32:
+        p.error("-track_sat32 needs -track FILE")
     args.filter_kind = None
     if not args.filter:
         for flag in ("filter_min", "filter_hits", "filter_frac", "filter_keep"):
@@ -559,6 +577,20 @@ def main(argv=None) -> int:
                     print(f"filter_{kind}/: {res['records']} records of {os.path.basename(args.filter)} filtered against "
                           f"{len(tables)} sample(s), {args.filter_keep} records written: " +
                           ", ".join(f"{base} {n}" for base, n in kept.items()))
+                if args.track and args.track_kind == kind:  # from the tables still on the GPU
+                    from .kmers import track_reads
+                    (out / f"track_{kind}").mkdir(parents=True, exist_ok=True)
+                    tracked = (0, 0)  # (records and k-mers are those of FILE at this k: the same for every sample)
+                    for base in sorted(tables):
+                        try:
+                            names, counts, offsets, rows, med = track_reads(tables[base], args.track, sat32=args.track_sat32)
+                        except native.MercatHipError as e:
+                            raise SystemExit(f"-track {args.track}: {e}")
+                        write_track_txt(out / f"track_{kind}" / f"{base}_track.txt", names, counts, offsets)
+                        write_track_median_tsv(out / f"track_{kind}" / f"{base}_median.tsv", names, rows, med)
+                        tracked = (len(names), len(counts))
+                    print(f"track_{kind}/: the {tracked[1]} k-mers of the {tracked[0]} records of {os.path.basename(args.track)} "
+                          f"tracked against each of {len(tables)} sample(s)")
                 if args.against and args.against_kind == kind:  # from the tables still on the GPU
                     try:
                         rows = write_against_tsvs({base: tables[base] for base in sorted(tables)}, args.against, args.op,

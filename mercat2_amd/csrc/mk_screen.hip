@@ -13,26 +13,10 @@
 #include "mk_screenpiece.h"
 #include "mk_tableview.h"
 
-#define SC_RUN 32                // window starts a lane owns
-#define SC_SPAN (256 * SC_RUN)   // ... a workgroup: one tile of the record scan
-// Home-slot loads of the one-word table a lane has in flight before it compares any: the lookup's knob.
-#ifndef SC_PER
-#define SC_PER LK_PER
-#endif
-// The span and its halo are staged in LDS up to this k (24.5 KiB); beyond it -- by-reference contexts only -- the walk
-// reads the stream itself.
-#define SC_LDS_MAX_K 16385
-
 struct ScStatus {  // device memory, read back twice a piece: after the scan (nsep, headless), after the probe
   u64 nsep, headless;
   u64 windows, hits, packed, text, folded, locked;
 };
-
-// bytes of w that equal MK_SEP (exact per byte: no borrow between them)
-__device__ __forceinline__ unsigned sc_seps_in(unsigned w) {
-  const unsigned x = w ^ (MK_SEP * 0x01010101u);
-  return __popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu));
-}
 
 __global__ void __launch_bounds__(256) sc_tiles_k(const uint8_t* __restrict__ seq, const MkChunkInfo* __restrict__ info,
                                                   unsigned* __restrict__ tile_cnt) {
@@ -152,6 +136,7 @@ __global__ void __launch_bounds__(256) sc_probe_k(const uint8_t* __restrict__ se
   for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
 
   // ---- the walk: k - 1 symbols to fill the key, then one window start a symbol
+  // (mk_screenwalk.h holds a copy of this walk for tk_probe_k: a change here is made there too)
   const int kb = k * bits;
   const u64 mask1 = kb >= 64 ? ~0ull : (1ull << kb) - 1;                                       // one-word keys
   const unsigned __int128 mask_aa = (((unsigned __int128)1) << (kb > 127 ? 127 : kb)) - 1;     // protein 13..25-mers
@@ -292,7 +277,7 @@ int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows
     MK_HIP(hipMemcpyAsync(c->raw.p, d_text, n, hipMemcpyDeviceToDevice, c->stream));
     d_text = (const uint8_t*)c->raw.p;
   }
-  s.last = {d_text, nullptr, 0, false};
+  s.last = {d_text, nullptr, 0, false, nullptr, 0, 0};
   MkChunkInfo info{};
   ScStatus h{};
   MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
@@ -326,6 +311,9 @@ int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows
     d_rows = (mk_screen_row_t*)own->p;
   }
   s.last.d_rows = d_rows;
+  s.last.tile_pre = tile_pre;
+  s.last.seq_len = (size_t)info.seq_len;
+  s.last.row_base = h.headless ? 0 : 1;
   if ((rc = s.probe.begin()) != MK_OK) return rc;
   hipLaunchKernelGGL(sc_rows_init_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
   if (info.seq_len && (rc = sc_launch_probe(s, (size_t)info.seq_len, tile_pre, h.headless ? 0 : 1, d_rows, d_st)) != MK_OK) return rc;

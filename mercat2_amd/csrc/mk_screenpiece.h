@@ -8,6 +8,24 @@
 #include <algorithm>
 #include <vector>
 
+#define SC_RUN 32                // window starts a lane owns
+#define SC_SPAN (256 * SC_RUN)   // ... a workgroup: one tile of the record scan
+// Home-slot loads of the one-word table a lane has in flight before it compares any: the lookup's knob.
+#ifndef SC_PER
+#define SC_PER LK_PER
+#endif
+// The span and its halo are staged in LDS up to this k (24.5 KiB); beyond it -- by-reference contexts only -- the walk
+// reads the stream itself.
+#define SC_LDS_MAX_K 16385
+
+// bytes of w that equal MK_SEP (exact per byte: no borrow between them)
+#ifdef __HIPCC__
+__device__ __forceinline__ unsigned sc_seps_in(unsigned w) {
+  const unsigned x = w ^ (MK_SEP * 0x01010101u);
+  return __popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu));
+}
+#endif
+
 struct ScCall {
   mk_ctx* c;
   const char* what;
@@ -18,12 +36,17 @@ struct ScCall {
   mk_screen_t out{};
   size_t rows_seen = 0;
   // what the last sc_piece left on the device: the text as the parser read it (16-byte aligned: the caller's bytes or
-  // their copy in c->raw), its rows (nullptr: none, or no room for them) and whether row 0 has no header line
+  // their copy in c->raw), its rows (nullptr: none, or no room for them), whether row 0 has no header line
   struct {
     const uint8_t* text = nullptr;
     mk_screen_row_t* d_rows = nullptr;
     size_t nrows = 0;
     bool headless = false;
+    // what a further walk over the same stream (c->seq) needs of the record scan: separators in front of every tile
+    // (in s.scratch), the stream's length, the record number of row 0
+    const u64* tile_pre = nullptr;
+    size_t seq_len = 0;
+    u64 row_base = 0;
   } last;
   ~ScCall() { buf_free(scratch); }
 };

@@ -1,0 +1,138 @@
+// mk_screenwalk.h -- the lane walk over one tile of the parsed stream, with the sink a template parameter: tk_probe_k
+// (mk_track.hip) writes every count where its window stands.  THIS IS A COPY of the walk inside sc_probe_k
+// (mk_screen.hip), which folds the same counts into the record's row and keeps its own text: its device code reacts to
+// restructuring ("one walk").  A change to the walk is made in both places.
+//
+// A lane owns SC_RUN consecutive window starts: it walks k - 1 + SC_RUN symbols of the workgroup's span (staged in LDS
+// once, with a halo of k - 1), ROLLS the packed key one symbol at a time, keeps "symbols since the last separator" (is
+// this a window?) and "symbols since the last byte outside the alphabet" (packed key or text key?) and probes where
+// lk_probe_k would probe the same k bytes, SC_PER home-slot loads of the one-word table in flight.  What it hands to the
+// sink, in stream order:
+//   sink.begin(rid, at)         the lane's run starts at stream position `at`, inside record rid
+//   sink.window(rid, pos, cnt)  a window of record rid has count cnt; it starts at the pos-th of the record's symbols THE
+//                               LANE HAS SEEN: since_sep is the lane's own, so for the record its run started in the
+//                               sink adds what lay in front of the run
+#pragma once
+#include "mk_screenpiece.h"
+#include "mk_tableview.h"
+
+struct ScWalked {  // what a lane's walk counted
+  u64 windows = 0, packed = 0, text = 0, folded = 0;
+  bool locked = false;
+};
+
+// The walk of the calling lane over tile blockIdx.x (workgroups of 256).  s_seq: dynamic LDS of SC_SPAN + k - 1 bytes,
+// rounded up to 16 (unused when LDS is false: KEYS == TL_TEXT_ONLY with a k whose halo LDS cannot hold).  Returns the
+// record the lane ends in.  Every lane of the workgroup must call it (two barriers inside).
+template <int KEYS, bool FOLD, bool LDS, class Sink>
+__device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_t* __restrict__ seq, u64 seq_len,
+                                       const u64* __restrict__ tile_pre, int k, int bits, const LkTables& t, Sink& sink,
+                                       ScWalked& n) {
+  __shared__ unsigned s_wave[4];
+  const u64 base = (u64)blockIdx.x * SC_SPAN;
+  if (LDS) {
+    const unsigned stage = (unsigned)(SC_SPAN + k - 1 + 15) & ~15u;
+    for (unsigned i = threadIdx.x * 16u; i < stage; i += 256u * 16u) {
+      if (base + i + 16 <= seq_len) *reinterpret_cast<uint4*>(s_seq + i) = *reinterpret_cast<const uint4*>(seq + base + i);
+      else
+        for (unsigned j = 0; j < 16; ++j) s_seq[i + j] = base + i + j < seq_len ? seq[base + i + j] : (uint8_t)MK_SEP;
+    }
+    __syncthreads();
+  }
+  // symbol at local index li of the span; positions behind the stream are separators
+  auto sym_at = [&](unsigned li) -> unsigned { return LDS ? s_seq[li] : (base + li < seq_len ? seq[base + li] : MK_SEP); };
+
+  // the record this lane's run starts in: separators in front of the tile, of the lanes before it in the workgroup
+  const unsigned l0 = threadIdx.x * SC_RUN;
+  unsigned own = 0;
+  if (LDS) {
+#pragma unroll
+    for (int i = 0; i < SC_RUN / 4; ++i) own += sc_seps_in(reinterpret_cast<const unsigned*>(s_seq + l0)[i]);
+  } else {
+    for (int j = 0; j < SC_RUN; ++j) own += sym_at(l0 + j) == MK_SEP;
+  }
+  const unsigned incl = mk_wave_scan_incl(own);
+  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  u64 rid = tile_pre[blockIdx.x] + (incl - own);
+  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
+  sink.begin(rid, base + l0);
+
+  // ---- the walk: k - 1 symbols to fill the key, then one window start a symbol
+  const int kb = k * bits;
+  const u64 mask1 = kb >= 64 ? ~0ull : (1ull << kb) - 1;                                       // one-word keys
+  const unsigned __int128 mask_aa = (((unsigned __int128)1) << (kb > 127 ? 127 : kb)) - 1;     // protein 13..25-mers
+  const int sh2 = 128 - 2 * k;                                                                 // two-word nt: the last base's place in lo
+  u64 a = 0, b = 0;
+  unsigned __int128 wide = 0;
+  unsigned since_sep = 0, since_bad = 0;  // symbols since the last separator / the last byte outside the alphabet
+  unsigned li = l0, word = 0;
+  auto step = [&]() -> bool {  // takes the next symbol in; true: it is a separator
+    unsigned ch;
+    if (LDS) {
+      if ((li & 3u) == 0) word = reinterpret_cast<const unsigned*>(s_seq)[li >> 2];
+      ch = word & 0xFFu;
+      word >>= 8;
+    } else ch = sym_at(li);
+    ++li;
+    if (ch == MK_SEP) { since_sep = since_bad = 0; return true; }
+    ++since_sep;
+    if (KEYS == TL_TEXT_ONLY) return false;
+    unsigned code;
+    if (bits == 2) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 99u;
+    else code = (ch >= 'A' && ch <= 'Z') ? ch - 'A' : 99u;
+    if (code == 99u) { since_bad = 0; return false; }  // (what the key holds is pushed out before it is used again)
+    ++since_bad;
+    if (KEYS == TL_ONE_WORD) a = ((a << bits) | code) & mask1;
+    else if (KEYS == TL_TWO_WORD_AA) wide = ((wide << 5) | code) & mask_aa;
+    else { a = (a << 2) | (b >> 62); b = (b << 2) | ((u64)code << sh2); }
+    return false;
+  };
+  for (int q = 1; q < k; ++q) rid += step() ? 1 : 0;
+
+  for (int g = 0; g < SC_RUN; g += SC_PER) {
+    u64 key[SC_PER], res[SC_PER];
+    ulonglong2 home[SC_PER];
+    unsigned pos[SC_PER];
+    bool sep[SC_PER], window[SC_PER], pending[SC_PER];
+#pragma unroll
+    for (int j = 0; j < SC_PER; ++j) {
+      sep[j] = step();
+      window[j] = !sep[j] && since_sep >= (unsigned)k;
+      pos[j] = since_sep - (unsigned)k;
+      pending[j] = false;
+      res[j] = 0;
+      if (!window[j]) continue;
+      if (KEYS != TL_TEXT_ONLY && since_bad >= (unsigned)k) {
+        ++n.packed;
+        u64 ka = a, kb2 = b;
+        if (KEYS == TL_TWO_WORD_AA) { ka = (u64)(wide >> 64); kb2 = (u64)wide; }
+        if (FOLD) n.folded += LkStep<KEYS, SC_PER>::fold(ka, kb2, k) ? 1 : 0;
+        // (LkStep's issue and finish, spelled out here: with the whole step sc_probe_k's s_probe was 2 to 6 % slower on
+        // the MI355X, outside the spread of this form, and the cause is not known -- profiles/table_reads_refactor.md)
+        if (KEYS == TL_ONE_WORD) {
+          if (t.bins) res[j] = find_dense(t.bins, (size_t)t.nbins, ka);
+          else if (ka == MK_EMPTY) res[j] = t.side;
+          else if (t.run_slots) {
+            key[j] = ka;
+            home[j] = find64_home(t.run, t.run_slots - 1, ka);
+            pending[j] = true;
+          }
+        } else if (t.run128_slots) res[j] = find128(t.run128, t.run128_slots - 1, ka, kb2, &n.locked);
+      } else {
+        ++n.text;
+        const uint8_t* w = LDS ? s_seq + (li - (unsigned)k) : seq + base + (li - (unsigned)k);  // the window that ends here
+        if (t.ref_slots) res[j] = find_ref_of(t.ref, t.ref_slots - 1, t.arena, BytesAt{w}, k);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SC_PER; ++j) {
+      if (sep[j]) ++rid;  // the record ends in front of this symbol
+      if (!window[j]) continue;
+      if (pending[j]) res[j] = find64_from(t.run, t.run_slots - 1, key[j], home[j]);
+      ++n.windows;
+      sink.window(rid, pos[j], res[j]);
+    }
+  }
+  return rid;
+}

@@ -1,0 +1,393 @@
+// mk_track.hip -- sequences in, the count under every k-mer window out (mk_track_text / mk_track_device,
+// include/mercat_hip.h): what mk_screen_* folds into five numbers a record, written out position by position, and --
+// where asked for -- the median of every record's counts.
+//
+// A piece goes through sc_piece (mk_screenpiece.h: parse, record scan, probe) and leaves its rows on the device.  Then
+//   tk_lens_k + rocprim::exclusive_scan     woff[r] = windows of the piece's records in front of r, woff[nrows] = all of
+//                                           them; the largest count of the piece beside it (the sort's end_bit)
+//   tk_starts_k                             sstart[r] = where record r starts in the stream: a lane of the walk knows how
+//                                           far it is from the last separator IT saw, not from the record's
+//   tk_probe_k                              the hot path: the walk of mk_screenwalk.h over the same stream and the same
+//                                           tile prefixes, its sink positional -- window j of record r goes to
+//                                           woff[r] + j, j = (the lane's place - sstart[r]) + its own count.  Inside a
+//                                           tile those places are one contiguous range (only separators and the first
+//                                           k - 1 symbols of a record give no window), so the tile's counts are gathered
+//                                           in LDS, addressed by their place modulo the tile, and the range leaves in
+//                                           whole-wave stores.  (-DTK_DIRECT: every lane stores its own elements -- 18 %
+//                                           slower on reads, 42 % on a contig: DESIGN 8p, profiles/track_probe.md.)
+//   rocprim::segmented_radix_sort_keys      (median only) the piece's counts, a segment a record, into scratch
+//   tk_pick_k                               (median only) a lane per record: element windows / 2 of its segment
+//   tk_offsets_k                            offsets of the piece, the windows of the pieces before it added
+#include "mk_screenwalk.h"
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+
+// The sink's form: gathered in LDS and written by the workgroup, or (an A/B build, make EXTRA=-DTK_DIRECT) lane by lane.
+#ifdef TK_DIRECT
+#define TK_STAGE false
+#else
+#define TK_STAGE true
+#endif
+
+struct TkStatus {  // device memory, read back once a piece
+  u64 max_count, written, saturated;
+};
+
+// wlen[r] = windows of row r, wlen[nrows] = 0 (so that the scan ends in the total); the largest count of the piece.
+__global__ void __launch_bounds__(256) tk_lens_k(const mk_screen_row_t* __restrict__ rows, size_t nrows, u64* __restrict__ wlen,
+                                                 TkStatus* __restrict__ st) {
+  u64 mx = 0;
+  mk_for_each(nrows + 1, [&](size_t r) {
+    if (r == nrows) { wlen[r] = 0; return; }
+    wlen[r] = rows[r].windows;
+    mx = rows[r].max > mx ? rows[r].max : mx;
+  });
+  for (int d = 32; d > 0; d >>= 1) {
+    const u64 o = __shfl_down(mx, d);
+    mx = o > mx ? o : mx;
+  }
+  if ((threadIdx.x & 63) == 0 && mx) atomicMax((unsigned long long*)&st->max_count, mx);
+}
+
+// sstart[r] = the stream position of the first symbol of row r: behind its separator, 0 for a headless row 0.  The
+// record scan of sc_probe_k on the stream's own tiles (tile_pre: separators in front of every tile).
+__global__ void __launch_bounds__(256) tk_starts_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
+                                                   u64 row_base, size_t nrows, u64* __restrict__ sstart) {
+  __shared__ unsigned s_wave[4];
+  const u64 at = (u64)blockIdx.x * SC_SPAN + (u64)threadIdx.x * SC_RUN;
+  unsigned own = 0;
+  for (int j = 0; j < SC_RUN && at + j < seq_len; ++j) own += seq[at + j] == MK_SEP;
+  const unsigned incl = mk_wave_scan_incl(own);
+  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  u64 rid = tile_pre[blockIdx.x] + (incl - own);
+  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && row_base == 0 && nrows) sstart[0] = 0;
+  if (own)
+    for (int j = 0; j < SC_RUN && at + j < seq_len; ++j)
+      if (seq[at + j] == MK_SEP) {
+        ++rid;
+        if (rid - row_base < nrows) sstart[rid - row_base] = at + j + 1;
+      }
+}
+
+__global__ void __launch_bounds__(256) tk_offsets_k(const u64* __restrict__ woff, size_t n, u64 add, u64* __restrict__ out) {
+  mk_for_each(n, [&](size_t r) { out[r] = woff[r] + add; });
+}
+
+template <class E>
+__global__ void __launch_bounds__(256) tk_pick_k(const E* __restrict__ sorted, const u64* __restrict__ woff, size_t nrows,
+                                                 E* __restrict__ median) {
+  mk_for_each(nrows, [&](size_t r) {
+    const u64 w = woff[r + 1] - woff[r];
+    median[r] = w ? sorted[woff[r] + w / 2] : (E)0;
+  });
+}
+
+// The positional sink of the walk.  out: where element 0 of the piece goes; total: the piece's windows (woff[nrows]).
+// An element whose record or place lies outside what the placement counted is dropped, never written -- the host
+// compares st->written with the total.
+template <class E, bool STAGE>
+struct TkSink {
+  E* __restrict__ out;
+  E* s_out;  // STAGE: SC_SPAN elements of LDS, element i of the piece at i % SC_SPAN
+  const u64* __restrict__ woff;
+  const u64* __restrict__ sstart;
+  u64 row_base, nrows, total;
+  u64 at_rid0 = ~0ull, ahead = 0;       // that record; symbols of the record the lane's run started in that lie in front of the run
+  u64 at_rid = ~0ull, at_base = 0;      // the record whose woff this lane holds
+  u64 first = ~0ull, last = 0, sat = 0, written = 0;
+  __device__ __forceinline__ void begin(u64 rid, u64 at) {
+    const u64 r = rid - row_base;
+    if (r < nrows && sstart[r] <= at) ahead = at - sstart[r];
+    at_rid0 = rid;
+  }
+  __device__ __forceinline__ void window(u64 rid, unsigned pos, u64 cnt) {
+    if (rid != at_rid) {
+      at_rid = rid;
+      const u64 r = rid - row_base;
+      at_base = r < nrows ? woff[r] : total;
+    }
+    const u64 i = at_base + (rid == at_rid0 ? ahead : 0) + pos;  // (a record may end inside the k - 1 symbols that fill the key)
+    if (i >= total) return;
+    E v = (E)cnt;
+    if (sizeof(E) == 4 && cnt > 0xFFFFFFFFull) { v = (E)0xFFFFFFFFu; ++sat; }
+    ++written;
+    if (STAGE) {
+      s_out[i & (SC_SPAN - 1)] = v;
+      if (first == ~0ull) first = i;  // (the places of a lane ascend)
+      last = i + 1;
+    } else out[i] = v;
+  }
+};
+
+// Grid and arguments of sc_probe_k; dynamic LDS: the span (SC_SPAN + k - 1 bytes rounded up to 16, none when LDS is
+// false), then with STAGE SC_SPAN elements.
+template <int KEYS, bool FOLD, bool LDS, class E, bool STAGE>
+__global__ void __launch_bounds__(256) tk_probe_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
+                                                  u64 row_base, int k, int bits, LkTables t, const u64* __restrict__ woff,
+                                                  const u64* __restrict__ sstart, u64 nrows, u64 total, E* __restrict__ out, TkStatus* __restrict__ st) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+  __shared__ unsigned long long s_lo, s_hi;
+  const unsigned span_bytes = LDS ? (unsigned)(SC_SPAN + k - 1 + 15) & ~15u : 0u;
+  if (STAGE && threadIdx.x == 0) { s_lo = ~0ull; s_hi = 0; }  // (the walk's barriers stand between this and the atomics)
+  TkSink<E, STAGE> sink{out, reinterpret_cast<E*>(s_dyn + span_bytes), woff, sstart, row_base, nrows, total};
+  ScWalked n;
+  sc_walk<KEYS, FOLD, LDS>(s_dyn, seq, seq_len, tile_pre, k, bits, t, sink, n);
+  if (STAGE) {
+    // The tile's range: its windows are at most SC_SPAN consecutive places, so no two share an LDS element.
+    if (sink.last) {
+      atomicMin(&s_lo, (unsigned long long)sink.first);
+      atomicMax(&s_hi, (unsigned long long)sink.last);
+    }
+    __syncthreads();
+    const u64 lo = s_lo, hi = s_hi;
+    if (hi > lo && hi - lo <= SC_SPAN)
+      for (u64 i = lo + threadIdx.x; i < hi; i += 256) out[i] = sink.s_out[i & (SC_SPAN - 1)];
+    else sink.written = 0;
+  }
+  block_add(&st->written, sink.written);
+  if (sizeof(E) == 4) block_add(&st->saturated, sink.sat);
+}
+
+// ------------------------------------------------------------------------------------------ host side
+struct TkCall {
+  bool sat32, device;
+  void* counts;        // the caller's (text call: host memory, device call: device memory), counts_cap elements of room
+  size_t counts_cap;
+  uint64_t* offsets;   // each the caller's or nullptr; cap rows (cap + 1 offsets)
+  void* median;
+  mk_screen_row_t* rows;
+  size_t cap;
+  MkDevBuf d_rows, meta, scan_tmp, stage, sorted, sort_tmp, small;
+  MkTimed place, track, sort;
+  mk_track_t st{};
+  size_t windows_seen = 0;  // of all pieces so far, written or not
+  TkCall(mk_ctx* c, bool s32, bool dev, void* cn, size_t cc, uint64_t* of, void* md, mk_screen_row_t* rw, size_t cp)
+      : sat32(s32), device(dev), counts(cn), counts_cap(cc), offsets(of), median(md), rows(rw), cap(cp), place(c), track(c), sort(c) {}
+  ~TkCall() {
+    for (MkDevBuf* b : {&d_rows, &meta, &scan_tmp, &stage, &sorted, &sort_tmp, &small}) buf_free(*b);
+  }
+};
+
+template <class E, bool STAGE>
+static int tk_launch_probe(ScCall& s, const u64* woff, const u64* sstart, size_t nrows, u64 total, E* d_out, TkStatus* d_st) {
+  mk_ctx* c = s.c;
+  const LkTables t = lk_tables(c);
+  const int keys = tl_keys_of(c), k = c->k;
+  const bool lds = k <= SC_LDS_MAX_K;
+  const unsigned grid = (unsigned)div_up(s.last.seq_len, SC_SPAN);
+  const size_t shmem = (lds ? (((size_t)SC_SPAN + k - 1 + 15) & ~(size_t)15) : 0) + (STAGE ? (size_t)SC_SPAN * sizeof(E) : 0);
+#define TK_GO(K, F, L)                                                                                                         \
+  do {                                                                                                                         \
+    auto kern = tk_probe_k<K, F, L, E, STAGE>;                                                                                 \
+    static size_t raised[64]; /* per instantiation and device: the dynamic LDS the kernel has been allowed so far */           \
+    if (shmem > 64 * 1024 && shmem > raised[c->device & 63]) {                                                                 \
+      MK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+      raised[c->device & 63] = shmem;                                                                                          \
+    }                                                                                                                          \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, c->stream, (const uint8_t*)c->seq.p, (u64)s.last.seq_len,           \
+                       s.last.tile_pre, s.last.row_base, k, c->bits, t, woff, sstart, (u64)nrows, total, d_out, d_st);                 \
+  } while (0)
+  if (keys == TL_ONE_WORD) { if (s.fold) TK_GO(TL_ONE_WORD, true, true); else TK_GO(TL_ONE_WORD, false, true); }
+  else if (keys == TL_TWO_WORD_NT) { if (s.fold) TK_GO(TL_TWO_WORD_NT, true, true); else TK_GO(TL_TWO_WORD_NT, false, true); }
+  else if (keys == TL_TWO_WORD_AA) TK_GO(TL_TWO_WORD_AA, false, true);
+  else if (lds) TK_GO(TL_TEXT_ONLY, false, true);
+  else TK_GO(TL_TEXT_ONLY, false, false);
+#undef TK_GO
+  MK_HIP(hipGetLastError());
+  return MK_OK;
+}
+
+// The sort of the piece's `total` elements at d_in into f.sorted, a segment a record, and the pick into d_med.
+template <class E>
+static int tk_median(mk_ctx* c, TkCall& f, const E* d_in, const u64* woff, size_t nrows, u64 total, u64 max_count, E* d_med) {
+  int rc;
+  if (total) {
+    if ((rc = mk_buf_reserve(c, f.sorted, (size_t)total * sizeof(E))) != MK_OK) return rc;
+    unsigned end_bit = 1;  // (the bits the largest count of the piece has: small counts sort in one or two passes)
+    while (end_bit < 8 * sizeof(E) && (max_count >> end_bit)) ++end_bit;
+    size_t tmp = 0;
+    MK_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp, d_in, (E*)f.sorted.p, (unsigned)total, (unsigned)nrows, woff, woff + 1, 0u,
+                                              end_bit, c->stream));
+    if ((rc = mk_buf_reserve(c, f.sort_tmp, tmp ? tmp : 16)) != MK_OK) return rc;
+    MK_HIP(rocprim::segmented_radix_sort_keys(f.sort_tmp.p, tmp, d_in, (E*)f.sorted.p, (unsigned)total, (unsigned)nrows, woff, woff + 1,
+                                              0u, end_bit, c->stream));
+  }
+  hipLaunchKernelGGL(tk_pick_k<E>, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, (const E*)f.sorted.p, woff, nrows, d_med);
+  MK_HIP(hipGetLastError());
+  return MK_OK;
+}
+
+// What follows sc_piece for a piece whose rows start at row `first` of the call: placement, the track kernel, the
+// median, and the copies to the caller's buffers where they have room.  The stream is idle afterwards.
+template <class E>
+static int tk_piece(ScCall& s, TkCall& f, size_t first) {
+  mk_ctx* c = s.c;
+  int rc;
+  const size_t nrows = s.last.nrows;
+  if (!nrows) return MK_OK;
+  const mk_screen_row_t* d_rows = s.last.d_rows;
+  // meta: TkStatus (32) | wlen[nrows + 1] | woff[nrows + 1] | sstart[nrows]
+  if ((rc = mk_buf_reserve(c, f.meta, 32 + (3 * nrows + 2) * sizeof(u64))) != MK_OK) return rc;
+  TkStatus* d_st = (TkStatus*)f.meta.p;
+  u64* wlen = (u64*)((char*)f.meta.p + 32);
+  u64* woff = wlen + nrows + 1;
+  u64* sstart = woff + nrows + 1;
+  size_t tmp = 0;
+  MK_HIP(rocprim::exclusive_scan((void*)nullptr, tmp, (const u64*)wlen, woff, 0ull, nrows + 1, rocprim::plus<u64>(), c->stream));
+  if ((rc = mk_buf_reserve(c, f.scan_tmp, tmp ? tmp : 16)) != MK_OK) return rc;
+
+  MK_HIP(hipMemsetAsync(d_st, 0, sizeof(TkStatus), c->stream));
+  if ((rc = f.place.begin()) != MK_OK) return rc;
+  hipLaunchKernelGGL(tk_lens_k, dim3(grid_for(nrows + 1, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows, wlen, d_st);
+  if (s.last.seq_len)
+    hipLaunchKernelGGL(tk_starts_k, dim3((unsigned)div_up(s.last.seq_len, SC_SPAN)), dim3(256), 0, c->stream, (const uint8_t*)c->seq.p,
+                       (u64)s.last.seq_len, s.last.tile_pre, s.last.row_base, nrows, sstart);
+  MK_HIP(hipGetLastError());
+  MK_HIP(rocprim::exclusive_scan(f.scan_tmp.p, tmp, (const u64*)wlen, woff, 0ull, nrows + 1, rocprim::plus<u64>(), c->stream));
+  if ((rc = f.place.end()) != MK_OK) return rc;
+  TkStatus h{};
+  u64 total = 0;
+  MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&total, woff + nrows, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = f.place.add_to(f.st.s_place)) != MK_OK) return rc;
+  if (total > s.last.seq_len) {
+    c->err = std::string(s.what) + ": more windows in the rows of a piece than symbols in its stream (internal error)";
+    return MK_ERR_STATE;
+  }
+  const size_t at = f.windows_seen;
+  f.windows_seen += (size_t)total;
+  const bool rows_fit = first + nrows <= f.cap;
+
+  // rows and offsets of the piece, where the caller has room for them
+  const hipMemcpyKind kind = f.device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (rows_fit && (f.rows || f.offsets)) {
+    u64* d_off = f.device ? (u64*)f.offsets + first : nullptr;
+    if (f.offsets && !f.device) {
+      if ((rc = mk_buf_reserve(c, f.small, (nrows + 1) * sizeof(u64))) != MK_OK) return rc;
+      d_off = (u64*)f.small.p;
+    }
+    if (f.offsets) {
+      hipLaunchKernelGGL(tk_offsets_k, dim3(grid_for(nrows + 1, 256, 4096)), dim3(256), 0, c->stream, (const u64*)woff, nrows + 1, (u64)at, d_off);
+      MK_HIP(hipGetLastError());
+    }
+    const auto t1 = MkClock::now();
+    if (f.rows) MK_HIP(hipMemcpyAsync(f.rows + first, d_rows, nrows * sizeof(mk_screen_row_t), kind, c->stream));
+    if (f.offsets && !f.device) MK_HIP(hipMemcpyAsync(f.offsets + first, d_off, (nrows + 1) * sizeof(u64), kind, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    if (!f.device) f.st.s_write += mk_since(t1);
+  }
+  if (f.windows_seen > f.counts_cap) return MK_OK;  // (no room: the call goes on adding up and answers MK_ERR_RANGE)
+  if (f.median && total >> 32) {
+    c->err = std::string(s.what) + ": the median takes pieces of fewer than 2^32 windows";
+    return MK_ERR_ARG;
+  }
+
+  // the track kernel: into the caller's device memory, or into a staging buffer that is copied to the host
+  E* d_out = (E*)f.counts + at;
+  if (!f.device) {
+    if ((rc = mk_buf_reserve(c, f.stage, std::max<size_t>((size_t)total * sizeof(E), 16))) != MK_OK) return rc;
+    d_out = (E*)f.stage.p;
+  }
+  if (total) {
+    if ((rc = f.track.begin()) != MK_OK) return rc;
+    if ((rc = tk_launch_probe<E, TK_STAGE>(s, woff, sstart, nrows, total, d_out, d_st)) != MK_OK) return rc;
+    if ((rc = f.track.end()) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = f.track.add_to(f.st.s_track)) != MK_OK) return rc;
+    if (h.written != total) {
+      c->err = std::string(s.what) + ": the track kernel wrote " + std::to_string(h.written) + " of " + std::to_string(total) +
+               " windows (internal error)";
+      return MK_ERR_STATE;
+    }
+    f.st.saturated += h.saturated;
+  }
+  E* d_med = nullptr;
+  if (f.median && rows_fit) {
+    d_med = (E*)f.median + first;
+    if (!f.device) {
+      if ((rc = mk_buf_reserve(c, f.small, std::max((nrows + 1) * sizeof(u64), nrows * sizeof(E)))) != MK_OK) return rc;
+      d_med = (E*)f.small.p;
+    }
+    if ((rc = f.sort.begin()) != MK_OK) return rc;
+    const u64 mx = sizeof(E) == 4 && h.max_count > 0xFFFFFFFFull ? 0xFFFFFFFFull : h.max_count;
+    if ((rc = tk_median<E>(c, f, d_out, woff, nrows, total, mx, d_med)) != MK_OK) return rc;
+    if ((rc = f.sort.end()) != MK_OK) return rc;
+    MK_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = f.sort.add_to(f.st.s_median)) != MK_OK) return rc;
+  }
+  if (!f.device) {
+    const auto t1 = MkClock::now();
+    if (total) MK_HIP(hipMemcpyAsync((E*)f.counts + at, d_out, (size_t)total * sizeof(E), hipMemcpyDeviceToHost, c->stream));
+    if (d_med) MK_HIP(hipMemcpyAsync((E*)f.median + first, d_med, nrows * sizeof(E), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    f.st.s_write += mk_since(t1);
+  }
+  return MK_OK;
+}
+
+// How both calls check their own arguments, open as the screen calls open, and end; body(s): the pieces.
+template <class Body>
+static int tk_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least, TkCall* f, size_t* nwindows, size_t* nrows,
+                  mk_track_t* st, Body&& body) {
+  if (flags & ~(MK_TRACK_FOLD | MK_TRACK_SAT32)) { c->err = std::string(what) + ": unknown flag"; return MK_ERR_ARG; }
+  const size_t cap = (f->rows || f->offsets || f->median) ? f->cap : ~(size_t)0;
+  f->cap = cap;
+  int rc = sc_run(c, what, flags & MK_TRACK_FOLD, at_least, cap, nrows, &f->st.screen, [&](ScCall& s) -> int {
+    if (f->offsets) {  // (offsets[0] of a text without records)
+      if (f->device) MK_HIP(hipMemsetAsync(f->offsets, 0, sizeof(u64), c->stream));
+      else f->offsets[0] = 0;
+    }
+    return body(s);
+  });
+  if (rc != MK_OK && rc != MK_ERR_RANGE) return rc;
+  if (nwindows) *nwindows = f->windows_seen;
+  if (rc != MK_OK) return rc;
+  if (f->windows_seen > f->counts_cap) {
+    c->err = std::string(what) + ": the text holds " + std::to_string(f->windows_seen) + " windows, counts has room for " +
+             std::to_string(f->counts_cap);
+    return MK_ERR_RANGE;
+  }
+  f->st.windows_out = f->windows_seen;
+  if (st) *st = f->st;
+  return MK_OK;
+}
+
+extern "C" int mk_track_device(mk_ctx* c, const uint8_t* d_text, size_t n, unsigned flags, uint64_t at_least, void* d_counts,
+                               size_t counts_cap, size_t* nwindows, uint64_t* d_offsets, void* d_median, mk_screen_row_t* d_rows,
+                               size_t cap, size_t* nrows, mk_track_t* st) {
+  if (!c) return MK_ERR_ARG;
+  if ((n && !d_text) || (counts_cap && !d_counts)) { c->err = "mk_track_device: NULL buffer"; return MK_ERR_ARG; }
+  const bool sat32 = (flags & MK_TRACK_SAT32) != 0;
+  if (((uintptr_t)d_counts | (uintptr_t)d_median) & (sat32 ? 3 : 7) || ((uintptr_t)d_offsets | (uintptr_t)d_rows) & 7) {
+    c->err = "mk_track_device: a buffer is not aligned to its elements";
+    return MK_ERR_ARG;
+  }
+  TkCall f(c, sat32, true, d_counts, counts_cap, d_offsets, d_median, d_rows, cap);
+  return tk_run(c, "mk_track_device", flags, at_least, &f, nwindows, nrows, st, [&](ScCall& s) -> int {
+    if (!n) return MK_OK;
+    const int rc = sc_piece(s, d_text, n, nullptr, ~(size_t)0, &f.d_rows, nullptr);
+    if (rc != MK_OK) return rc;
+    return sat32 ? tk_piece<uint32_t>(s, f, 0) : tk_piece<u64>(s, f, 0);
+  });
+}
+
+extern "C" int mk_track_text(mk_ctx* c, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, uint64_t at_least,
+                             void* counts, size_t counts_cap, size_t* nwindows, uint64_t* offsets, void* median,
+                             mk_screen_row_t* rows, size_t cap, size_t* nrows, mk_track_t* st) {
+  if (!c) return MK_ERR_ARG;
+  if ((n && !text) || (counts_cap && !counts)) { c->err = "mk_track_text: NULL buffer"; return MK_ERR_ARG; }
+  const bool sat32 = (flags & MK_TRACK_SAT32) != 0;
+  TkCall f(c, sat32, false, counts, counts_cap, offsets, median, rows, cap);
+  return tk_run(c, "mk_track_text", flags, at_least, &f, nwindows, nrows, st, [&](ScCall& s) -> int {
+    return sc_text_pieces(s, text, n, piece_bytes, [&](const uint8_t* d_piece, size_t len) -> int {
+      const size_t first = s.rows_seen;
+      const int rc = sc_piece(s, d_piece, len, nullptr, ~(size_t)0, &f.d_rows, nullptr);
+      if (rc != MK_OK) return rc;
+      return sat32 ? tk_piece<uint32_t>(s, f, first) : tk_piece<u64>(s, f, first);
+    });
+  });
+}

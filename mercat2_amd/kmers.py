@@ -138,6 +138,24 @@ def screen_reads(table: "native.Counter", file: Union[str, Path], at_least: int 
     return names, rows
 
 
+def track_reads(table: "native.Counter", file: Union[str, Path], at_least: int = 1, sat32: bool = False, median: bool = True):
+    """(names, counts, offsets, rows, median) of every record of a FASTA or FASTQ file tracked against a table that is
+    still on the GPU (Counter.track): counts[offsets[i] : offsets[i + 1]] are the counts of record i's k-mers in the order
+    they stand in the read (0 for one the table lacks), rows[i] its screen row (windows, hits, sum, min, max) and
+    median[i] element windows // 2 of its sorted counts -- khmer's median k-mer abundance -- or None without ``median``.
+    ``sat32``: uint32 counts clipped at 2^32 - 1, half the bytes.  The file is read exactly as screen_reads reads it:
+    '.gz' inflated on the host, a FASTQ file first converted as MerCat2's fq2fa converts it (mk_fq2fa).  A canonical
+    table folds the windows."""
+    text = read_fasta_bytes(file)
+    if str(file).lower().endswith(FASTQ_SUFFIXES):
+        text, _ = native.fq2fa(text)
+    names = record_names(text)
+    counts, offsets, rows, med = table.track(text, at_least, sat32=sat32, median=median)
+    if len(names) != rows.shape[0]:
+        raise RuntimeError("track_reads: %d header names for %d records" % (len(names), rows.shape[0]))
+    return names, counts, offsets, rows, med
+
+
 def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 1, min_hits: int = 1,
                  min_frac: float = 0.0, invert: bool = False) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file that match a table still on the GPU (Counter.filter), written to ``out_path``

@@ -36,12 +36,14 @@ ABI_SYMBOLS = [
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
+    "mk_track_text", "mk_track_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
 LOOKUP_FOLD = 1
 SCREEN_FOLD = 1
 FILTER_FOLD, FILTER_INVERT = 1, 2
+TRACK_FOLD, TRACK_SAT32 = 1, 2
 # mk_table_op: f(ca, cb) per key (include/mercat_hip.h)
 OP_MIN, OP_MAX, OP_SUM, OP_LEFT, OP_ONLY, OP_DIFF = range(6)
 OPS = {"min": OP_MIN, "max": OP_MAX, "sum": OP_SUM, "left": OP_LEFT, "only": OP_ONLY, "diff": OP_DIFF}
@@ -141,6 +143,17 @@ class Filter(C.Structure):
     """mk_filter_t (include/mercat_hip.h)."""
     _fields_ = ([("screen", Screen)] + [(n, C.c_uint64) for n in ("records_out", "bytes_out", "preamble")] +
                 [(n, C.c_double) for n in ("s_place", "s_gather", "s_write")])
+
+    def as_dict(self):
+        d = self.screen.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+class Track(C.Structure):
+    """mk_track_t (include/mercat_hip.h)."""
+    _fields_ = ([("screen", Screen)] + [(n, C.c_uint64) for n in ("windows_out", "saturated")] +
+                [(n, C.c_double) for n in ("s_place", "s_track", "s_median", "s_write")])
 
     def as_dict(self):
         d = self.screen.as_dict()
@@ -310,6 +323,10 @@ def lib() -> C.CDLL:
                                      C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Filter)]),
         "mk_filter_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(FilterRule), C.c_void_p, C.c_size_t, szp,
                                        C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Filter)]),
+        "mk_track_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Track)]),
+        "mk_track_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Track)]),
         "mk_table_op": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(TableOp)]),
     }
     L.mk_version.restype = C.c_char_p
@@ -1032,6 +1049,50 @@ class Counter:
         self._check(self._L.mk_filter_device(self._h, ptr, int(nbytes), self._filter_flags(fold, invert), C.byref(rule), out_ptr or None,
                                              int(out_cap), C.byref(out_len), rows_ptr or None, keep_ptr or None, int(cap), C.byref(n),
                                              C.byref(st)))
+        return st.as_dict()
+
+    # -- tracking: FASTA text in, the count under every window out (and the median a record); the table is only read
+    def _track_flags(self, fold: Optional[bool], sat32: bool) -> int:
+        return (TRACK_FOLD if self._fold_flag(fold) else 0) | (TRACK_SAT32 if sat32 else 0)
+
+    def track(self, path_or_bytes, at_least: int = 1, fold: Optional[bool] = None, sat32: bool = False, median: bool = False,
+              piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_track_text: (counts, offsets, rows, median_or_None) of the FASTA text (a path to a plain file, or the text
+        itself as bytes).  ``counts[offsets[r] + j]`` is the count of window j of record r -- the k bytes that start at
+        the record's j-th kept character, 0 for a k-mer the table lacks -- ``offsets`` has records + 1 entries and
+        ``rows`` is the (records, 5) uint64 array Counter.screen gives for the same text and ``at_least``.  ``median``:
+        also element windows // 2 of every record's sorted counts (0 without windows).  ``sat32``: counts and median are
+        uint32, clipped at 2^32 - 1 (info["saturated"] of them), else uint64.  ``fold`` None: fold iff the context is
+        canonical.  ``info``, if given, receives the mk_track_t fields (those of mk_screen_t beside them)."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(held == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        dtype = np.uint32 if sat32 else np.uint64
+        counts = np.empty(max(size, 1), dtype=dtype)  # (an upper bound: a window starts at a kept character; untouched pages cost nothing)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        med = np.zeros(cap, dtype=dtype) if median else None
+        n, nwin, st = C.c_size_t(0), C.c_size_t(0), Track()
+        self._check(self._L.mk_track_text(self._h, addr, size, int(piece_bytes), self._track_flags(fold, sat32), int(at_least),
+                                          counts.ctypes.data, size, C.byref(nwin), offsets.ctypes.data,
+                                          med.ctypes.data if median else None, rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return counts[: nwin.value], offsets[: n.value + 1], rows[: n.value], (med[: n.value] if median else None)
+
+    def track_device(self, ptr: int, nbytes: int, counts_ptr: int, counts_cap: int, offsets_ptr: int = 0, median_ptr: int = 0,
+                     rows_ptr: int = 0, cap: int = 0, at_least: int = 1, fold: Optional[bool] = None, sat32: bool = False) -> dict:
+        """mk_track_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> the counts at device
+        address ``counts_ptr`` (room for ``counts_cap`` elements: uint64, or uint32 with ``sat32``) and, where given,
+        ``cap`` + 1 uint64 offsets at ``offsets_ptr``, the medians at ``median_ptr`` and the rows (five uint64 a record) at
+        ``rows_ptr`` with room for ``cap`` records each -- all on this context's GPU, each aligned to its elements.
+        Returns the mk_track_t fields: "windows_out" elements were written, "records" rows."""
+        n, nwin, st = C.c_size_t(0), C.c_size_t(0), Track()
+        self._check(self._L.mk_track_device(self._h, ptr, int(nbytes), self._track_flags(fold, sat32), int(at_least),
+                                            counts_ptr or None, int(counts_cap), C.byref(nwin), offsets_ptr or None,
+                                            median_ptr or None, rows_ptr or None, int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
 
     # -- results

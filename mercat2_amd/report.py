@@ -144,6 +144,45 @@ def write_screen_tsv(path, names: Sequence[str], array) -> int:
     return len(names)
 
 
+def format_track_txt(names: Sequence[str], counts, offsets) -> bytes:
+    """The layout of a FASTA .qual file: a ``>name`` line, then one line with the counts of the record's k-mers in read
+    order, separated by single spaces -- an empty line for a record without windows (kmers.track_reads / Counter.track)."""
+    if len(names) + 1 != len(offsets):
+        raise ValueError("format_track_txt: %d names for %d offsets" % (len(names), len(offsets)))
+    out = []
+    for i, name in enumerate(names):
+        values = counts[int(offsets[i]): int(offsets[i + 1])].tolist()
+        out.append(b">" + name.encode() + b"\n" + " ".join(map(str, values)).encode() + b"\n")
+    return b"".join(out)
+
+
+def write_track_txt(path, names: Sequence[str], counts, offsets) -> int:
+    """``format_track_txt`` written to ``path``; returns the number of records."""
+    text = format_track_txt(names, counts, offsets)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
+def format_track_median_tsv(names: Sequence[str], rows, median) -> bytes:
+    """``record\twindows\tmedian\tsum\tmin\tmax``, then one line per record (kmers.track_reads): its name, its k-mers,
+    the median of their counts, and their sum, smallest and largest from its screen row."""
+    if len(names) != len(rows) or len(names) != len(median):
+        raise ValueError("format_track_median_tsv: %d names for %d rows and %d medians" % (len(names), len(rows), len(median)))
+    out = [b"record\twindows\tmedian\tsum\tmin\tmax\n"]
+    for name, row, med in zip(names, rows, median):
+        out.append(name.encode() + b"\t%d\t%d\t%d\t%d\t%d\n" % (int(row[0]), int(med), int(row[2]), int(row[3]), int(row[4])))
+    return b"".join(out)
+
+
+def write_track_median_tsv(path, names: Sequence[str], rows, median) -> int:
+    """``format_track_median_tsv`` written to ``path``; returns the number of records."""
+    text = format_track_median_tsv(names, rows, median)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
 def write_against_tsvs(tables: Dict[str, "native.Counter"], against, op, out_dir, min_other: int = 1) -> Dict[str, int]:
     """For every sample of ``{sample name: Counter}``, ``sample op against`` (Counter.combine, keys compared as they
     stand) written as ``out_dir/<sample>_counts.tsv`` with Counter.write_tsv; a sample whose result is empty writes no
