@@ -46,6 +46,16 @@ __device__ __forceinline__ unsigned mk_wave_scan_incl(unsigned v) {
 __device__ __forceinline__ unsigned mk_wave_sum(unsigned v) { return (unsigned)__builtin_amdgcn_readlane((int)mk_wave_scan_incl(v), 63); }
 // the value lane 63 holds, in every lane (v_readlane: no trip through the LDS)
 __device__ __forceinline__ unsigned mk_wave_last(unsigned v) { return (unsigned)__builtin_amdgcn_readlane((int)v, 63); }
+// Exclusive prefix sum over a workgroup of 256, in thread order: what the lanes in front of this one hold together.
+// s_wave: four words of the caller's LDS.  One barrier inside: every thread must call it.
+__device__ __forceinline__ unsigned mk_block_scan_excl(unsigned own, unsigned* s_wave) {
+  const unsigned incl = mk_wave_scan_incl(own);
+  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  unsigned pre = incl - own;
+  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) pre += s_wave[w];
+  return pre;
+}
 
 __device__ __forceinline__ void wave_add(u64* target, u64 mine) {
   for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);

@@ -66,34 +66,16 @@ __global__ void __launch_bounds__(256) fl_tiles_k(const uint8_t* __restrict__ te
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
-// One workgroup, in the pattern of sc_scan_k: thread t owns tiles [t * per, (t + 1) * per).  tile_pre[i] = header
-// lines in front of tile i; their total goes to st.  The two starts no header line gives are written here: the end of
-// the text behind the last row, byte 0 for a headless row 0.
+// One workgroup: tile_pre[i] = header lines in front of tile i (sc_tile_scan); their total goes to st.  The two starts
+// no header line gives are written here: the end of the text behind the last row, byte 0 for a headless row 0.
 __global__ void __launch_bounds__(1024) fl_scan_k(const unsigned* __restrict__ tile_cnt, size_t ntiles, u64* __restrict__ tile_pre,
                                                   u64 n, size_t nrows, int headless, u64* __restrict__ start, FlStatus* __restrict__ st) {
   __shared__ u64 s_c[1024];
-  const size_t per = (ntiles + 1023) / 1024;
-  const size_t lo = (size_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
-  u64 mine = 0;
-  for (size_t t = lo; t < hi; ++t) mine += tile_cnt[t];
-  s_c[threadIdx.x] = mine;
-  __syncthreads();
+  const u64 headers = sc_tile_scan(tile_cnt, ntiles, tile_pre, s_c);
   if (threadIdx.x == 0) {
-    u64 run = 0;
-    for (int t = 0; t < 1024; ++t) {
-      const u64 c = s_c[t];
-      s_c[t] = run;
-      run += c;
-    }
-    st->headers = run;
+    st->headers = headers;
     start[nrows] = n;
     if (headless) start[0] = 0;
-  }
-  __syncthreads();
-  u64 run = s_c[threadIdx.x];
-  for (size_t t = lo; t < hi; ++t) {
-    tile_pre[t] = run;
-    run += tile_cnt[t];
   }
 }
 
@@ -104,11 +86,7 @@ __global__ void __launch_bounds__(256) fl_starts_k(const uint8_t* __restrict__ t
   __shared__ unsigned s_wave[4];
   const u64 base = (u64)blockIdx.x * FL_SPAN + (u64)threadIdx.x * FL_RUN;
   const unsigned own = fl_headers_in(text, n, base, [](unsigned, u64) {});
-  const unsigned incl = mk_wave_scan_incl(own);
-  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  u64 first = row_base + tile_pre[blockIdx.x] + (incl - own);
-  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) first += s_wave[w];
+  const u64 first = row_base + tile_pre[blockIdx.x] + mk_block_scan_excl(own, s_wave);
   if (own)
     fl_headers_in(text, n, base, [&](unsigned j, u64 line) {
       if (first + j < nrows) start[first + j] = line;

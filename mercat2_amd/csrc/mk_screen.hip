@@ -5,13 +5,10 @@
 // A piece of text goes through the general parser (mk_parse.hip) into the stream the count kernels slide over: kept
 // characters, one MK_SEP where a header line starts.  The record of a position is the number of separators at or
 // before it: sc_tiles_k counts them per tile, sc_scan_k (one workgroup) turns the counts into tile prefixes and the
-// number of records, and sc_probe_k finishes the scan inside the workgroup.  There a lane owns SC_RUN consecutive
-// window starts: it walks k - 1 + SC_RUN symbols of the workgroup's span (staged in LDS once, with a halo of k - 1),
-// ROLLS the packed key one symbol at a time, keeps "symbols since the last separator" (is this a window?) and "symbols
-// since the last byte outside the alphabet" (packed key or text key?), probes where lk_probe_k would probe the same k
-// bytes, and accumulates while it stays in one record.  Integer adds, min and max only: exact in any order.
-#include "mk_screenpiece.h"
-#include "mk_tableview.h"
+// number of records, and the walk finishes the scan inside the workgroup.  sc_probe_k is the lane walk of
+// mk_screenwalk.h with a row sink: a lane accumulates the counts of its windows while it stays in one record and adds
+// them to the record's row where the record, or its run, ends.  Integer adds, min and max only: exact in any order.
+#include "mk_screenwalk.h"
 
 struct ScStatus {  // device memory, read back twice a piece: after the scan (nsep, headless), after the probe
   u64 nsep, headless;
@@ -39,33 +36,16 @@ __global__ void __launch_bounds__(256) sc_tiles_k(const uint8_t* __restrict__ se
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
-// One workgroup, in the pattern of mk_parse_scan: thread t owns tiles [t * per, (t + 1) * per).  tile_pre[i] =
-// separators in front of tile i; their total and whether kept characters stand in front of the first go to st.
+// One workgroup: tile_pre[i] = separators in front of tile i (sc_tile_scan); their total and whether kept characters
+// stand in front of the first go to st.
 __global__ void __launch_bounds__(1024) sc_scan_k(const unsigned* __restrict__ tile_cnt, size_t ntiles, u64* __restrict__ tile_pre,
                                                   const uint8_t* __restrict__ seq, const MkChunkInfo* __restrict__ info,
                                                   ScStatus* __restrict__ st) {
   __shared__ u64 s_c[1024];
-  const size_t per = (ntiles + 1023) / 1024;
-  const size_t lo = (size_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
-  u64 mine = 0;
-  for (size_t t = lo; t < hi; ++t) mine += tile_cnt[t];
-  s_c[threadIdx.x] = mine;
-  __syncthreads();
+  const u64 nsep = sc_tile_scan(tile_cnt, ntiles, tile_pre, s_c);
   if (threadIdx.x == 0) {
-    u64 run = 0;
-    for (int t = 0; t < 1024; ++t) {
-      const u64 c = s_c[t];
-      s_c[t] = run;
-      run += c;
-    }
-    st->nsep = run;
+    st->nsep = nsep;
     st->headless = (info->seq_len && seq[0] != MK_SEP) ? 1 : 0;
-  }
-  __syncthreads();
-  u64 run = s_c[threadIdx.x];
-  for (size_t t = lo; t < hi; ++t) {
-    tile_pre[t] = run;
-    run += tile_cnt[t];
   }
 }
 
@@ -99,124 +79,31 @@ struct ScAcc {
   }
 };
 
+// The row sink of the walk: the lane's counts go to the row of the record they belong to when the record ends.
+struct ScRowSink {
+  mk_screen_row_t* __restrict__ rows;
+  u64 row_base, at_least;
+  ScAcc acc;
+  u64 hits = 0;  // of the lane's whole run, for ScStatus
+  __device__ __forceinline__ void begin(u64, u64) {}
+  __device__ __forceinline__ void record_end(u64 rid) { acc.flush(rows, rid - row_base); }
+  __device__ __forceinline__ void window(u64, unsigned, u64 cnt) {
+    hits += cnt >= at_least ? 1 : 0;
+    acc.add(cnt, at_least);
+  }
+};
+
 // Grid: one workgroup per tile of SC_SPAN positions.  row_base: the record number of row 0 (1, or 0 when the piece
 // starts with a record that has no header line).  LDS false: KEYS == TL_TEXT_ONLY with a k whose halo LDS cannot hold.
 template <int KEYS, bool FOLD, bool LDS>
 __global__ void __launch_bounds__(256) sc_probe_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
                                                   u64 row_base, int k, int bits, u64 at_least, LkTables t,
                                                   mk_screen_row_t* __restrict__ rows, ScStatus* __restrict__ st) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t s_seq[];  // SC_SPAN + k - 1 bytes, rounded up to 16
-  __shared__ unsigned s_wave[4];
-  const u64 base = (u64)blockIdx.x * SC_SPAN;
-  if (LDS) {
-    const unsigned stage = (unsigned)(SC_SPAN + k - 1 + 15) & ~15u;
-    for (unsigned i = threadIdx.x * 16u; i < stage; i += 256u * 16u) {
-      if (base + i + 16 <= seq_len) *reinterpret_cast<uint4*>(s_seq + i) = *reinterpret_cast<const uint4*>(seq + base + i);
-      else
-        for (unsigned j = 0; j < 16; ++j) s_seq[i + j] = base + i + j < seq_len ? seq[base + i + j] : (uint8_t)MK_SEP;
-    }
-    __syncthreads();
-  }
-  // symbol at local index li of the span; positions behind the stream are separators
-  auto sym_at = [&](unsigned li) -> unsigned { return LDS ? s_seq[li] : (base + li < seq_len ? seq[base + li] : MK_SEP); };
-
-  // the record this lane's run starts in: separators in front of the tile, of the lanes before it in the workgroup
-  const unsigned l0 = threadIdx.x * SC_RUN;
-  unsigned own = 0;
-  if (LDS) {
-#pragma unroll
-    for (int i = 0; i < SC_RUN / 4; ++i) own += sc_seps_in(reinterpret_cast<const unsigned*>(s_seq + l0)[i]);
-  } else {
-    for (int j = 0; j < SC_RUN; ++j) own += sym_at(l0 + j) == MK_SEP;
-  }
-  const unsigned incl = mk_wave_scan_incl(own);
-  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  u64 rid = tile_pre[blockIdx.x] + (incl - own);
-  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
-
-  // ---- the walk: k - 1 symbols to fill the key, then one window start a symbol
-  // (mk_screenwalk.h holds a copy of this walk for tk_probe_k: a change here is made there too)
-  const int kb = k * bits;
-  const u64 mask1 = kb >= 64 ? ~0ull : (1ull << kb) - 1;                                       // one-word keys
-  const unsigned __int128 mask_aa = (((unsigned __int128)1) << (kb > 127 ? 127 : kb)) - 1;     // protein 13..25-mers
-  const int sh2 = 128 - 2 * k;                                                                 // two-word nt: the last base's place in lo
-  u64 a = 0, b = 0;
-  unsigned __int128 wide = 0;
-  unsigned since_sep = 0, since_bad = 0;  // symbols since the last separator / the last byte outside the alphabet
-  unsigned li = l0, word = 0;
-  auto step = [&]() -> bool {  // takes the next symbol in; true: it is a separator
-    unsigned ch;
-    if (LDS) {
-      if ((li & 3u) == 0) word = reinterpret_cast<const unsigned*>(s_seq)[li >> 2];
-      ch = word & 0xFFu;
-      word >>= 8;
-    } else ch = sym_at(li);
-    ++li;
-    if (ch == MK_SEP) { since_sep = since_bad = 0; return true; }
-    ++since_sep;
-    if (KEYS == TL_TEXT_ONLY) return false;
-    unsigned code;
-    if (bits == 2) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 99u;
-    else code = (ch >= 'A' && ch <= 'Z') ? ch - 'A' : 99u;
-    if (code == 99u) { since_bad = 0; return false; }  // (what the key holds is pushed out before it is used again)
-    ++since_bad;
-    if (KEYS == TL_ONE_WORD) a = ((a << bits) | code) & mask1;
-    else if (KEYS == TL_TWO_WORD_AA) wide = ((wide << 5) | code) & mask_aa;
-    else { a = (a << 2) | (b >> 62); b = (b << 2) | ((u64)code << sh2); }
-    return false;
-  };
-  for (int q = 1; q < k; ++q) rid += step() ? 1 : 0;
-
-  ScAcc acc;
-  u64 n_win = 0, n_hits = 0, n_packed = 0, n_text = 0, n_folded = 0;
-  bool locked = false;
-  for (int g = 0; g < SC_RUN; g += SC_PER) {
-    u64 key[SC_PER], res[SC_PER];
-    ulonglong2 home[SC_PER];
-    bool sep[SC_PER], window[SC_PER], pending[SC_PER];
-#pragma unroll
-    for (int j = 0; j < SC_PER; ++j) {
-      sep[j] = step();
-      window[j] = !sep[j] && since_sep >= (unsigned)k;
-      pending[j] = false;
-      res[j] = 0;
-      if (!window[j]) continue;
-      if (KEYS != TL_TEXT_ONLY && since_bad >= (unsigned)k) {
-        ++n_packed;
-        u64 ka = a, kb2 = b;
-        if (KEYS == TL_TWO_WORD_AA) { ka = (u64)(wide >> 64); kb2 = (u64)wide; }
-        if (FOLD) n_folded += LkStep<KEYS, SC_PER>::fold(ka, kb2, k) ? 1 : 0;
-        // (LkStep's issue and finish, spelled out here: with the whole step this kernel's s_probe was 2 to 6 % slower on
-        // the MI355X, outside the spread of this form, and the cause is not known -- profiles/table_reads_refactor.md)
-        if (KEYS == TL_ONE_WORD) {
-          if (t.bins) res[j] = find_dense(t.bins, (size_t)t.nbins, ka);
-          else if (ka == MK_EMPTY) res[j] = t.side;
-          else if (t.run_slots) {
-            key[j] = ka;
-            home[j] = find64_home(t.run, t.run_slots - 1, ka);
-            pending[j] = true;
-          }
-        } else if (t.run128_slots) res[j] = find128(t.run128, t.run128_slots - 1, ka, kb2, &locked);
-      } else {
-        ++n_text;
-        const uint8_t* w = LDS ? s_seq + (li - (unsigned)k) : seq + base + (li - (unsigned)k);  // the window that ends here
-        if (t.ref_slots) res[j] = find_ref_of(t.ref, t.ref_slots - 1, t.arena, BytesAt{w}, k);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < SC_PER; ++j) {
-      if (sep[j]) {  // the record ends in front of this symbol
-        acc.flush(rows, rid - row_base);
-        ++rid;
-      }
-      if (!window[j]) continue;
-      if (pending[j]) res[j] = find64_from(t.run, t.run_slots - 1, key[j], home[j]);
-      ++n_win;
-      n_hits += res[j] >= at_least ? 1 : 0;
-      acc.add(res[j], at_least);
-    }
-  }
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_seq[];  // sc_span_bytes(k)
+  ScRowSink sink{rows, row_base, at_least};
+  ScWalked n;
+  const u64 rid = sc_walk<KEYS, FOLD, LDS>(s_seq, seq, seq_len, tile_pre, k, bits, t, sink, n);
+  ScAcc& acc = sink.acc;  // what the lane holds belongs to the record it ends in
   // The whole wave ends in one record (the normal case inside a contig): reduce across it, one lane flushes -- five
   // atomics a wave on the record's row instead of 320.  (Measured, DESIGN 8m: one 100 Mbase record 2.3 ms with it, 73 ms
   // with every lane flushing for itself; 150 bp reads the same either way.)
@@ -232,30 +119,25 @@ __global__ void __launch_bounds__(256) sc_probe_k(const uint8_t* __restrict__ se
     if (threadIdx.x & 63) acc.windows = 0;
   }
   acc.flush(rows, rid - row_base);
-  block_add(&st->windows, n_win);
-  block_add(&st->hits, n_hits);
-  block_add(&st->packed, n_packed);
-  block_add(&st->text, n_text);
-  block_add(&st->folded, n_folded);
-  if (locked) atomicAdd(&st->locked, 1ull);  // (cannot happen on a quiescent table)
+  block_add(&st->windows, n.windows);
+  block_add(&st->hits, sink.hits);
+  block_add(&st->packed, n.packed);
+  block_add(&st->text, n.text);
+  block_add(&st->folded, n.folded);
+  if (n.locked) atomicAdd(&st->locked, 1ull);  // (cannot happen on a quiescent table)
 }
 
 // ------------------------------------------------------------------------------------------ host side
 static int sc_launch_probe(ScCall& s, size_t seq_len, const u64* tile_pre, u64 row_base, mk_screen_row_t* d_rows, ScStatus* d_st) {
   mk_ctx* c = s.c;
   const LkTables t = lk_tables(c);
-  const int keys = tl_keys_of(c), k = c->k;
-  const bool lds = k <= SC_LDS_MAX_K;
   const unsigned grid = (unsigned)div_up(seq_len, SC_SPAN);
-  const size_t shmem = lds ? (((size_t)SC_SPAN + k - 1 + 15) & ~(size_t)15) : 0;
-#define SC_GO(K, F, L) hipLaunchKernelGGL((sc_probe_k<K, F, L>), dim3(grid), dim3(256), shmem, c->stream, (const uint8_t*)c->seq.p, \
-                                          (u64)seq_len, tile_pre, row_base, k, c->bits, s.at_least, t, d_rows, d_st)
-  if (keys == TL_ONE_WORD) { if (s.fold) SC_GO(TL_ONE_WORD, true, true); else SC_GO(TL_ONE_WORD, false, true); }
-  else if (keys == TL_TWO_WORD_NT) { if (s.fold) SC_GO(TL_TWO_WORD_NT, true, true); else SC_GO(TL_TWO_WORD_NT, false, true); }
-  else if (keys == TL_TWO_WORD_AA) SC_GO(TL_TWO_WORD_AA, false, true);
-  else if (lds) SC_GO(TL_TEXT_ONLY, false, true);
-  else SC_GO(TL_TEXT_ONLY, false, false);
-#undef SC_GO
+  sc_dispatch_walk(s, [&](auto keys, auto fold, auto lds) {
+    hipLaunchKernelGGL((sc_probe_k<decltype(keys)::value, decltype(fold)::value, decltype(lds)::value>), dim3(grid), dim3(256),
+                       decltype(lds)::value ? sc_span_bytes(c->k) : 0, c->stream, (const uint8_t*)c->seq.p, (u64)seq_len, tile_pre,
+                       row_base, c->k, c->bits, s.at_least, t, d_rows, d_st);
+    return MK_OK;
+  });
   MK_HIP(hipGetLastError());
   return MK_OK;
 }

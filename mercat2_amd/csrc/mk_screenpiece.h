@@ -1,7 +1,9 @@
-// mk_screenpiece.h -- the piece routine of mk_screen.hip for the calls that read a text record by record against the
-// tables: mk_screen_* (mk_screen.hip) reports the rows, mk_filter_* (mk_filter.hip) goes on from them to the records'
-// bytes.  One opening (sc_run), one way of cutting a host text into pieces (sc_text_pieces), one piece routine
-// (sc_piece: parse, record scan, probe) -- the kernels and their launches live in mk_screen.hip.
+// mk_screenpiece.h -- what the calls share that read a text record by record against the tables: mk_screen_*
+// (mk_screen.hip) reports the rows, mk_filter_* (mk_filter.hip) goes on from them to the records' bytes, mk_track_*
+// (mk_track.hip) to the count under every window.  One opening (sc_run), one way of cutting a host text into pieces
+// (sc_text_pieces), one piece routine (sc_piece: parse, record scan, probe -- its kernels and launches live in
+// mk_screen.hip), the tile's sizes (SC_RUN, SC_SPAN, sc_span_bytes) and the one-workgroup scan that turns tile counts
+// into tile prefixes (sc_tile_scan).  The lane walk over a tile is mk_screenwalk.h.
 #pragma once
 #include "mk_tsvpieces.h"
 #include "mk_device.h"
@@ -23,6 +25,33 @@
 __device__ __forceinline__ unsigned sc_seps_in(unsigned w) {
   const unsigned x = w ^ (MK_SEP * 0x01010101u);
   return __popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu));
+}
+
+// Bytes of LDS a workgroup stages: its span and the halo of k - 1 behind it, rounded up to 16.
+__host__ __device__ constexpr unsigned sc_span_bytes(int k) { return (unsigned)(SC_SPAN + k - 1 + 15) & ~15u; }
+
+// One workgroup of 1024, in the pattern of mk_parse_scan: thread t owns tiles [t * per, (t + 1) * per).  tile_pre[i] =
+// what tile_cnt holds in front of tile i.  s_c: 1024 words of the caller's LDS.  Returns the total, to thread 0 only.
+__device__ __forceinline__ u64 sc_tile_scan(const unsigned* __restrict__ tile_cnt, size_t ntiles, u64* __restrict__ tile_pre, u64* s_c) {
+  const size_t per = (ntiles + 1023) / 1024;
+  const size_t lo = (size_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
+  u64 mine = 0, total = 0;
+  for (size_t t = lo; t < hi; ++t) mine += tile_cnt[t];
+  s_c[threadIdx.x] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int t = 0; t < 1024; ++t) {
+      const u64 c = s_c[t];
+      s_c[t] = total;
+      total += c;
+    }
+  __syncthreads();
+  u64 run = s_c[threadIdx.x];
+  for (size_t t = lo; t < hi; ++t) {
+    tile_pre[t] = run;
+    run += tile_cnt[t];
+  }
+  return total;
 }
 #endif
 

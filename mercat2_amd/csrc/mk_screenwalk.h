@@ -1,28 +1,30 @@
-// mk_screenwalk.h -- the lane walk over one tile of the parsed stream, with the sink a template parameter: tk_probe_k
-// (mk_track.hip) writes every count where its window stands.  THIS IS A COPY of the walk inside sc_probe_k
-// (mk_screen.hip), which folds the same counts into the record's row and keeps its own text: its device code reacts to
-// restructuring ("one walk").  A change to the walk is made in both places.
+// mk_screenwalk.h -- the lane walk over one tile of the parsed stream, with the sink a template parameter, and the
+// ladder that picks a walking kernel's instantiation.  sc_probe_k (mk_screen.hip) folds every window's count into the
+// record's row; tk_probe_k (mk_track.hip) writes it where its window stands.  The walk's device code reacts to
+// restructuring: a change here is measured on both kernels (profiles/screen_walk.md, DESIGN 8p "one walk").
 //
 // A lane owns SC_RUN consecutive window starts: it walks k - 1 + SC_RUN symbols of the workgroup's span (staged in LDS
 // once, with a halo of k - 1), ROLLS the packed key one symbol at a time, keeps "symbols since the last separator" (is
 // this a window?) and "symbols since the last byte outside the alphabet" (packed key or text key?) and probes where
-// lk_probe_k would probe the same k bytes, SC_PER home-slot loads of the one-word table in flight.  What it hands to the
-// sink, in stream order:
+// lk_probe_k would probe the same k bytes, SC_PER home-slot loads of the one-word table in flight.  Integer work only:
+// exact in any order.  What it hands to the sink, in stream order:
 //   sink.begin(rid, at)         the lane's run starts at stream position `at`, inside record rid
+//   sink.record_end(rid)        a separator among the lane's window starts: record rid ends in front of it
 //   sink.window(rid, pos, cnt)  a window of record rid has count cnt; it starts at the pos-th of the record's symbols THE
 //                               LANE HAS SEEN: since_sep is the lane's own, so for the record its run started in the
 //                               sink adds what lay in front of the run
 #pragma once
 #include "mk_screenpiece.h"
 #include "mk_tableview.h"
+#include <type_traits>
 
 struct ScWalked {  // what a lane's walk counted
   u64 windows = 0, packed = 0, text = 0, folded = 0;
   bool locked = false;
 };
 
-// The walk of the calling lane over tile blockIdx.x (workgroups of 256).  s_seq: dynamic LDS of SC_SPAN + k - 1 bytes,
-// rounded up to 16 (unused when LDS is false: KEYS == TL_TEXT_ONLY with a k whose halo LDS cannot hold).  Returns the
+// The walk of the calling lane over tile blockIdx.x (workgroups of 256).  s_seq: dynamic LDS of sc_span_bytes(k)
+// (unused when LDS is false: KEYS == TL_TEXT_ONLY with a k whose halo LDS cannot hold).  Returns the
 // record the lane ends in.  Every lane of the workgroup must call it (two barriers inside).
 template <int KEYS, bool FOLD, bool LDS, class Sink>
 __device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_t* __restrict__ seq, u64 seq_len,
@@ -31,7 +33,7 @@ __device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_
   __shared__ unsigned s_wave[4];
   const u64 base = (u64)blockIdx.x * SC_SPAN;
   if (LDS) {
-    const unsigned stage = (unsigned)(SC_SPAN + k - 1 + 15) & ~15u;
+    const unsigned stage = sc_span_bytes(k);
     for (unsigned i = threadIdx.x * 16u; i < stage; i += 256u * 16u) {
       if (base + i + 16 <= seq_len) *reinterpret_cast<uint4*>(s_seq + i) = *reinterpret_cast<const uint4*>(seq + base + i);
       else
@@ -51,11 +53,7 @@ __device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_
   } else {
     for (int j = 0; j < SC_RUN; ++j) own += sym_at(l0 + j) == MK_SEP;
   }
-  const unsigned incl = mk_wave_scan_incl(own);
-  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  u64 rid = tile_pre[blockIdx.x] + (incl - own);
-  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
+  u64 rid = tile_pre[blockIdx.x] + mk_block_scan_excl(own, s_wave);
   sink.begin(rid, base + l0);
 
   // ---- the walk: k - 1 symbols to fill the key, then one window start a symbol
@@ -127,7 +125,10 @@ __device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_
     }
 #pragma unroll
     for (int j = 0; j < SC_PER; ++j) {
-      if (sep[j]) ++rid;  // the record ends in front of this symbol
+      if (sep[j]) {  // the record ends in front of this symbol
+        sink.record_end(rid);
+        ++rid;
+      }
       if (!window[j]) continue;
       if (pending[j]) res[j] = find64_from(t.run, t.run_slots - 1, key[j], home[j]);
       ++n.windows;
@@ -135,4 +136,24 @@ __device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_
     }
   }
   return rid;
+}
+
+// The seven instantiations of a walking kernel, by the context's key kind, the call's fold and whether LDS holds the
+// halo of this k: go(KEYS, FOLD, LDS), each a std::integral_constant, launches the one that serves s.
+template <class Go>
+static int sc_dispatch_walk(const ScCall& s, Go&& go) {
+  using std::false_type;
+  using std::true_type;
+  const int keys = tl_keys_of(s.c);
+  if (keys == TL_ONE_WORD) {
+    std::integral_constant<int, TL_ONE_WORD> one;
+    return s.fold ? go(one, true_type{}, true_type{}) : go(one, false_type{}, true_type{});
+  }
+  if (keys == TL_TWO_WORD_NT) {
+    std::integral_constant<int, TL_TWO_WORD_NT> two;
+    return s.fold ? go(two, true_type{}, true_type{}) : go(two, false_type{}, true_type{});
+  }
+  if (keys == TL_TWO_WORD_AA) return go(std::integral_constant<int, TL_TWO_WORD_AA>{}, false_type{}, true_type{});
+  std::integral_constant<int, TL_TEXT_ONLY> text;
+  return s.c->k <= SC_LDS_MAX_K ? go(text, false_type{}, true_type{}) : go(text, false_type{}, false_type{});
 }

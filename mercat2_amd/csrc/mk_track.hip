@@ -13,21 +13,14 @@
 //                                           tile those places are one contiguous range (only separators and the first
 //                                           k - 1 symbols of a record give no window), so the tile's counts are gathered
 //                                           in LDS, addressed by their place modulo the tile, and the range leaves in
-//                                           whole-wave stores.  (-DTK_DIRECT: every lane stores its own elements -- 18 %
-//                                           slower on reads, 42 % on a contig: DESIGN 8p, profiles/track_probe.md.)
+//                                           whole-wave stores.  (Every lane storing its own elements was 19 to 49 %
+//                                           slower: DESIGN 8p, profiles/track_probe.md.)
 //   rocprim::segmented_radix_sort_keys      (median only) the piece's counts, a segment a record, into scratch
 //   tk_pick_k                               (median only) a lane per record: element windows / 2 of its segment
 //   tk_offsets_k                            offsets of the piece, the windows of the pieces before it added
 #include "mk_screenwalk.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
-
-// The sink's form: gathered in LDS and written by the workgroup, or (an A/B build, make EXTRA=-DTK_DIRECT) lane by lane.
-#ifdef TK_DIRECT
-#define TK_STAGE false
-#else
-#define TK_STAGE true
-#endif
 
 struct TkStatus {  // device memory, read back once a piece
   u64 max_count, written, saturated;
@@ -57,11 +50,7 @@ __global__ void __launch_bounds__(256) tk_starts_k(const uint8_t* __restrict__ s
   const u64 at = (u64)blockIdx.x * SC_SPAN + (u64)threadIdx.x * SC_RUN;
   unsigned own = 0;
   for (int j = 0; j < SC_RUN && at + j < seq_len; ++j) own += seq[at + j] == MK_SEP;
-  const unsigned incl = mk_wave_scan_incl(own);
-  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  u64 rid = tile_pre[blockIdx.x] + (incl - own);
-  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rid += s_wave[w];
+  u64 rid = tile_pre[blockIdx.x] + mk_block_scan_excl(own, s_wave);
   if (blockIdx.x == 0 && threadIdx.x == 0 && row_base == 0 && nrows) sstart[0] = 0;
   if (own)
     for (int j = 0; j < SC_RUN && at + j < seq_len; ++j)
@@ -84,13 +73,12 @@ __global__ void __launch_bounds__(256) tk_pick_k(const E* __restrict__ sorted, c
   });
 }
 
-// The positional sink of the walk.  out: where element 0 of the piece goes; total: the piece's windows (woff[nrows]).
-// An element whose record or place lies outside what the placement counted is dropped, never written -- the host
-// compares st->written with the total.
-template <class E, bool STAGE>
+// The positional sink of the walk.  s_out: SC_SPAN elements of LDS, element i of the piece at i % SC_SPAN; total: the
+// piece's windows (woff[nrows]).  An element whose record or place lies outside what the placement counted is dropped,
+// never written -- the host compares st->written with the total.
+template <class E>
 struct TkSink {
-  E* __restrict__ out;
-  E* s_out;  // STAGE: SC_SPAN elements of LDS, element i of the piece at i % SC_SPAN
+  E* s_out;
   const u64* __restrict__ woff;
   const u64* __restrict__ sstart;
   u64 row_base, nrows, total;
@@ -102,6 +90,7 @@ struct TkSink {
     if (r < nrows && sstart[r] <= at) ahead = at - sstart[r];
     at_rid0 = rid;
   }
+  __device__ __forceinline__ void record_end(u64) {}
   __device__ __forceinline__ void window(u64 rid, unsigned pos, u64 cnt) {
     if (rid != at_rid) {
       at_rid = rid;
@@ -113,39 +102,35 @@ struct TkSink {
     E v = (E)cnt;
     if (sizeof(E) == 4 && cnt > 0xFFFFFFFFull) { v = (E)0xFFFFFFFFu; ++sat; }
     ++written;
-    if (STAGE) {
-      s_out[i & (SC_SPAN - 1)] = v;
-      if (first == ~0ull) first = i;  // (the places of a lane ascend)
-      last = i + 1;
-    } else out[i] = v;
+    s_out[i & (SC_SPAN - 1)] = v;
+    if (first == ~0ull) first = i;  // (the places of a lane ascend)
+    last = i + 1;
   }
 };
 
-// Grid and arguments of sc_probe_k; dynamic LDS: the span (SC_SPAN + k - 1 bytes rounded up to 16, none when LDS is
-// false), then with STAGE SC_SPAN elements.
-template <int KEYS, bool FOLD, bool LDS, class E, bool STAGE>
+// Grid and arguments of sc_probe_k; dynamic LDS: the span (sc_span_bytes(k), none when LDS is false), then SC_SPAN
+// elements.
+template <int KEYS, bool FOLD, bool LDS, class E>
 __global__ void __launch_bounds__(256) tk_probe_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
                                                   u64 row_base, int k, int bits, LkTables t, const u64* __restrict__ woff,
                                                   const u64* __restrict__ sstart, u64 nrows, u64 total, E* __restrict__ out, TkStatus* __restrict__ st) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
   __shared__ unsigned long long s_lo, s_hi;
-  const unsigned span_bytes = LDS ? (unsigned)(SC_SPAN + k - 1 + 15) & ~15u : 0u;
-  if (STAGE && threadIdx.x == 0) { s_lo = ~0ull; s_hi = 0; }  // (the walk's barriers stand between this and the atomics)
-  TkSink<E, STAGE> sink{out, reinterpret_cast<E*>(s_dyn + span_bytes), woff, sstart, row_base, nrows, total};
+  const unsigned span_bytes = LDS ? sc_span_bytes(k) : 0u;
+  if (threadIdx.x == 0) { s_lo = ~0ull; s_hi = 0; }  // (the walk's barriers stand between this and the atomics)
+  TkSink<E> sink{reinterpret_cast<E*>(s_dyn + span_bytes), woff, sstart, row_base, nrows, total};
   ScWalked n;
   sc_walk<KEYS, FOLD, LDS>(s_dyn, seq, seq_len, tile_pre, k, bits, t, sink, n);
-  if (STAGE) {
-    // The tile's range: its windows are at most SC_SPAN consecutive places, so no two share an LDS element.
-    if (sink.last) {
-      atomicMin(&s_lo, (unsigned long long)sink.first);
-      atomicMax(&s_hi, (unsigned long long)sink.last);
-    }
-    __syncthreads();
-    const u64 lo = s_lo, hi = s_hi;
-    if (hi > lo && hi - lo <= SC_SPAN)
-      for (u64 i = lo + threadIdx.x; i < hi; i += 256) out[i] = sink.s_out[i & (SC_SPAN - 1)];
-    else sink.written = 0;
+  // The tile's range: its windows are at most SC_SPAN consecutive places, so no two share an LDS element.
+  if (sink.last) {
+    atomicMin(&s_lo, (unsigned long long)sink.first);
+    atomicMax(&s_hi, (unsigned long long)sink.last);
   }
+  __syncthreads();
+  const u64 lo = s_lo, hi = s_hi;
+  if (hi > lo && hi - lo <= SC_SPAN)
+    for (u64 i = lo + threadIdx.x; i < hi; i += 256) out[i] = sink.s_out[i & (SC_SPAN - 1)];
+  else sink.written = 0;
   block_add(&st->written, sink.written);
   if (sizeof(E) == 4) block_add(&st->saturated, sink.sat);
 }
@@ -170,31 +155,24 @@ struct TkCall {
   }
 };
 
-template <class E, bool STAGE>
+template <class E>
 static int tk_launch_probe(ScCall& s, const u64* woff, const u64* sstart, size_t nrows, u64 total, E* d_out, TkStatus* d_st) {
   mk_ctx* c = s.c;
   const LkTables t = lk_tables(c);
-  const int keys = tl_keys_of(c), k = c->k;
-  const bool lds = k <= SC_LDS_MAX_K;
   const unsigned grid = (unsigned)div_up(s.last.seq_len, SC_SPAN);
-  const size_t shmem = (lds ? (((size_t)SC_SPAN + k - 1 + 15) & ~(size_t)15) : 0) + (STAGE ? (size_t)SC_SPAN * sizeof(E) : 0);
-#define TK_GO(K, F, L)                                                                                                         \
-  do {                                                                                                                         \
-    auto kern = tk_probe_k<K, F, L, E, STAGE>;                                                                                 \
-    static size_t raised[64]; /* per instantiation and device: the dynamic LDS the kernel has been allowed so far */           \
-    if (shmem > 64 * 1024 && shmem > raised[c->device & 63]) {                                                                 \
-      MK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-      raised[c->device & 63] = shmem;                                                                                          \
-    }                                                                                                                          \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, c->stream, (const uint8_t*)c->seq.p, (u64)s.last.seq_len,           \
-                       s.last.tile_pre, s.last.row_base, k, c->bits, t, woff, sstart, (u64)nrows, total, d_out, d_st);                 \
-  } while (0)
-  if (keys == TL_ONE_WORD) { if (s.fold) TK_GO(TL_ONE_WORD, true, true); else TK_GO(TL_ONE_WORD, false, true); }
-  else if (keys == TL_TWO_WORD_NT) { if (s.fold) TK_GO(TL_TWO_WORD_NT, true, true); else TK_GO(TL_TWO_WORD_NT, false, true); }
-  else if (keys == TL_TWO_WORD_AA) TK_GO(TL_TWO_WORD_AA, false, true);
-  else if (lds) TK_GO(TL_TEXT_ONLY, false, true);
-  else TK_GO(TL_TEXT_ONLY, false, false);
-#undef TK_GO
+  const int rc = sc_dispatch_walk(s, [&](auto keys, auto fold, auto lds) -> int {
+    auto kern = tk_probe_k<decltype(keys)::value, decltype(fold)::value, decltype(lds)::value, E>;
+    const size_t shmem = (decltype(lds)::value ? sc_span_bytes(c->k) : 0) + (size_t)SC_SPAN * sizeof(E);
+    static size_t raised[64];  // per instantiation and device: the dynamic LDS the kernel has been allowed so far
+    if (shmem > 64 * 1024 && shmem > raised[c->device & 63]) {
+      MK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+      raised[c->device & 63] = shmem;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, c->stream, (const uint8_t*)c->seq.p, (u64)s.last.seq_len, s.last.tile_pre,
+                       s.last.row_base, c->k, c->bits, t, woff, sstart, (u64)nrows, total, d_out, d_st);
+    return MK_OK;
+  });
+  if (rc != MK_OK) return rc;
   MK_HIP(hipGetLastError());
   return MK_OK;
 }
@@ -293,7 +271,7 @@ static int tk_piece(ScCall& s, TkCall& f, size_t first) {
   }
   if (total) {
     if ((rc = f.track.begin()) != MK_OK) return rc;
-    if ((rc = tk_launch_probe<E, TK_STAGE>(s, woff, sstart, nrows, total, d_out, d_st)) != MK_OK) return rc;
+    if ((rc = tk_launch_probe<E>(s, woff, sstart, nrows, total, d_out, d_st)) != MK_OK) return rc;
     if ((rc = f.track.end()) != MK_OK) return rc;
     MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));

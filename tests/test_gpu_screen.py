@@ -12,6 +12,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import walk_seams
 from conftest import read_input
 from mercat2_amd import cli, kmers, native, report
 from oracle import cpu_ref
@@ -145,6 +146,48 @@ def test_pieces():
         assert info["pieces"] == 1 and 4 <= info5["pieces"] <= 6 and info_s["pieces"] > 8
         assert whole.tolist() == five.tolist() == small.tolist()
         assert info5["headless"] == info_s["headless"] == 1
+
+
+# --------------------------------------------------------------------------------------- the walk's own seams
+@functools.lru_cache(maxsize=None)
+def seam_rows(k: int, at_least: int = 1):
+    return expected_rows(walk_seams.seam_text(k), table_of(walk_seams.other_text(k), k), k, at_least)
+
+
+@pytest.mark.parametrize("k,at_least", [(5, 17), (31, 1)])  # (nearly every 5-mer is in any table: hits and misses by its counts)
+def test_walk_seams(k, at_least):
+    """Record boundaries on every lane, wave and tile seam of the walk (tests/walk_seams.py), in one piece and in many."""
+    text, source, want = walk_seams.seam_text(k), walk_seams.other_text(k), seam_rows(k, at_least)
+    with native.Counter(k, NT) as ctx:
+        ctx.count_chunk(source, 1)
+        for piece_bytes in (0, len(text) // 12):
+            info = {}
+            got = ctx.screen(text, at_least, info=info, piece_bytes=piece_bytes)
+            assert got.dtype == np.uint64 and got.tolist() == want
+            assert info["records"] == len(want) and (info["pieces"] > 8 if piece_bytes else info["pieces"] == 1)
+            assert info["windows"] == sum(r[0] for r in want) and info["hits"] == sum(r[1] for r in want)
+            assert 0 < info["hits"] < info["windows"] and info["packed_windows"] == info["windows"]
+        names = [name for name, _ in ref_records(text)]
+        assert int(got[names.index("long")][0]) > 3 * walk_seams.TILE - k
+
+
+@pytest.mark.parametrize("k,at_least,min_ppm", [(5, 17, 500_000), (31, 1, 400_000)])
+def test_walk_seams_filter(k, at_least, min_ppm):
+    """The same text through Counter.filter and back: the rows, the decision and the bytes of the records it keeps."""
+    text, source, want = walk_seams.seam_text(k), walk_seams.other_text(k), seam_rows(k, at_least)
+    want_keep = [w > 0 and h >= 1 and h * 1_000_000 >= min_ppm * w for w, h, _, _, _ in want]
+    recs = [b">" + r for r in text.split(b">")[1:]]
+    assert len(recs) == len(want) and 0 < sum(want_keep) < len(want_keep)
+    with native.Counter(k, NT) as ctx:
+        ctx.count_chunk(source, 1)
+        for piece_bytes in (0, len(text) // 12):
+            info = {}
+            kept, keep, rows = ctx.filter(text, at_least, 1, min_ppm, piece_bytes=piece_bytes, info=info)
+            assert rows.tolist() == want and keep.tolist() == want_keep
+            assert kept == b"".join(r for r, k_ in zip(recs, want_keep) if k_)
+            assert info["pieces"] > 8 if piece_bytes else info["pieces"] == 1
+        dropped, _, _ = ctx.filter(text, at_least, 1, min_ppm, invert=True)
+        assert dropped == b"".join(r for r, k_ in zip(recs, want_keep) if not k_)
 
 
 # ----------------------------------------------------------------------------------------------- table shapes

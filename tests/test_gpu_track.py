@@ -17,6 +17,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import walk_seams
 from conftest import read_input
 from mercat2_amd import cli, kmers, native, report
 from oracle import cpu_ref
@@ -179,6 +180,29 @@ def test_pieces():
         assert info5["headless"] == info_s["headless"] == 1
         sat, info32 = check(ctx, text, None, tracks=tracks, sat32=True, piece_bytes=len(text) // 12)
         assert info32["pieces"] == info5["pieces"] and sat[1].tolist() == whole[1].tolist()
+
+
+# --------------------------------------------------------------------------------------- the walk's own seams
+@functools.lru_cache(maxsize=None)
+def seam_tracks(k: int):
+    return expected_tracks(walk_seams.seam_text(k), table_of(walk_seams.other_text(k), k), k)
+
+
+@pytest.mark.parametrize("sat32", [False, True], ids=["u64", "sat32"])
+@pytest.mark.parametrize("k", [5, 31])
+def test_walk_seams(k, sat32):
+    """Record boundaries on every lane, wave and tile seam of the walk (tests/walk_seams.py), in one piece and in many:
+    counts, offsets, rows and medians."""
+    text, tracks = walk_seams.seam_text(k), seam_tracks(k)
+    with native.Counter(k, NT) as ctx:
+        ctx.count_chunk(walk_seams.other_text(k), 1)
+        one, info = check(ctx, text, None, sat32=sat32, tracks=tracks)
+        many, info_p = check(ctx, text, None, sat32=sat32, tracks=tracks, piece_bytes=len(text) // 12)
+        assert info["pieces"] == 1 and info_p["pieces"] > 8
+        assert one[0].min() < one[0].max() and info["packed_windows"] == info["windows"]
+        if k == 31:  # (nearly every 5-mer is in any table) hits and misses
+            assert 0 < np.count_nonzero(one[0]) < len(one[0])
+        assert max(len(v) for v in tracks) > 3 * walk_seams.TILE - k
 
 
 # ------------------------------------------------------------------------------------------------- key kinds

@@ -7,8 +7,8 @@ warm-ups, then median (min-max) of the runs.
 
     python tools/track_probe.py [--pass-reads 100000] [--reads 1000000] [--long 100000000] [--runs 5] [--long-median-runs 1]
 
-The direct-store form of the track kernel is an A/B build beside the library (mercat2_amd/csrc/Makefile: OBJDIR=...
-LIB=../libmercat_hip_ab.so EXTRA=-DTK_DIRECT), probed with MERCAT_HIP_LIB pointing at it, alternately with the library.
+Another build of the library (mercat2_amd/csrc/Makefile: OBJDIR=... LIB=../libmercat_hip_ab.so) is probed with
+MERCAT_HIP_LIB pointing at it, alternately with the library.
 """
 import argparse
 import statistics
