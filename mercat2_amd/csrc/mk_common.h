@@ -447,6 +447,11 @@ int mk_launch_compact(mk_ctx* c, const MkSlot* t, size_t slots, uint64_t* d_keys
                       uint64_t* d_cursor);
 int mk_sort_pairs(mk_ctx* c, const uint64_t* keys_in, const uint64_t* vals_in, uint64_t* keys_out, uint64_t* vals_out,
                   size_t n, int key_bits);
+// mk_binsort.hip: a one-word table of `rows` rows straight to sorted columns (rows binned by key prefix, bins sorted in
+// LDS); *d_scal = two device words for the caller's read-back: rows found, bins too large to sort (then: the library sort)
+bool mk_binsort_takes(size_t rows);
+int mk_binsort_export(mk_ctx* c, const MkSlot* t, size_t slots, size_t rows, int key_bits, uint64_t* keys_out,
+                      uint64_t* cnts_out, const uint64_t** d_scal);
 
 // mk_table.hip: interleaved rows {key word(s), count} -> running table (dense: {bin, count})
 int mk_launch_import_rows(mk_ctx* c, const uint64_t* d_rows, size_t rows);

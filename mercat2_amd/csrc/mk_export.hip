@@ -45,18 +45,6 @@ static int gather_packed(mk_ctx* c, ExportView& v, u64* d_keys_out, u64* d_cnts_
     const size_t side = !two && c->run_side ? 1 : 0;
     if (!to_host && rows + side > cap) { c->err = "export: device buffers too small"; return MK_ERR_RANGE; }
     if (rows) {
-      mk_prof_begin(c, MK_K_EXPORT);
-      // compacted rows: one-word keys | counts; two-word hi | lo | count + 4 n words of sort scratch
-      if ((rc = two ? mk_buf_reserve(c, c->ex128, 7 * rows * 8 + 64) : mk_buf_reserve(c, c->ex_keys, rows * 8 + 64)) != MK_OK) return rc;
-      if (!two && (rc = mk_buf_reserve(c, c->ex_cnts, rows * 8 + 64)) != MK_OK) return rc;
-      u64* k0 = (u64*)(two ? c->ex128.p : c->ex_keys.p);
-      u64* cn = two ? k0 + 2 * rows : (u64*)c->ex_cnts.p;
-      u64* d_cursor = (u64*)((char*)c->info.p + sizeof(MkChunkInfo));
-      MK_HIP(hipMemsetAsync(d_cursor, 0, 8, c->stream));
-      if ((rc = two ? mk_launch_compact128(c, (const MkSlot128*)c->run128.p, c->run128_slots, (uint64_t*)k0, (uint64_t*)(k0 + rows),
-                                           (uint64_t*)cn, rows, (uint64_t*)d_cursor)
-                    : mk_launch_compact(c, (const MkSlot*)c->run.p, c->run_slots, (uint64_t*)k0, (uint64_t*)cn, rows,
-                                        (uint64_t*)d_cursor)) != MK_OK) return rc;
       u64* ok = d_keys_out;
       u64* oc = d_cnts_out;
       if (to_host) {  // sorted rows for the host: keys, then counts
@@ -66,24 +54,52 @@ static int gather_packed(mk_ctx* c, ExportView& v, u64* d_keys_out, u64* d_cnts_
         ok = (u64*)kb.p;
         oc = two ? ok + 2 * rows : (u64*)c->ex_cnts2.p;
       }
-      if ((rc = two ? mk_sort_pairs128(c, (const uint64_t*)k0, (const uint64_t*)(k0 + rows), (const uint64_t*)cn, rows,
-                                       2 * (c->k - 32), (uint64_t*)(cn + rows), (uint64_t*)ok, (uint64_t*)oc)
-                    : mk_sort_pairs(c, (const uint64_t*)k0, (const uint64_t*)cn, (uint64_t*)ok, (uint64_t*)oc, rows,
-                                    c->bits * c->k)) != MK_OK) return rc;
-      mk_prof_end(c);
-      if (to_host) {
-        MK_HIP(hipStreamSynchronize(c->stream));  // (so that sort and copy are timed apart: ~10 us)
-        c->ex_st.s_sort += since(t_gather);
-        v.pkeys.resize(w * rows);
-        v.pcnts.resize(rows);
-        MK_HIP(hipMemcpyAsync(v.pkeys.data(), ok, w * rows * 8, hipMemcpyDeviceToHost, c->stream));
-        MK_HIP(hipMemcpyAsync(v.pcnts.data(), oc, rows * 8, hipMemcpyDeviceToHost, c->stream));
+      // one-word tables: rows binned by key prefix, the bins sorted in LDS (mk_binsort.hip); the others, and a table
+      // with a bin too large for that, by the library sort
+      bool binned = !two && mk_binsort_takes(rows) && mk_env_int("MK_EXPORT_LIBSORT", 0) == 0;
+      u64 got[2] = {0, 0};  // rows found; bins the binned sort left alone
+      auto t_sort = t_gather;
+      for (;;) {
+        const u64* d_got = nullptr;
+        mk_prof_begin(c, MK_K_EXPORT);
+        if (binned) {
+          if ((rc = mk_binsort_export(c, (const MkSlot*)c->run.p, c->run_slots, rows, c->bits * c->k, (uint64_t*)ok, (uint64_t*)oc,
+                                      (const uint64_t**)&d_got)) != MK_OK) return rc;
+        } else {
+          // compacted rows: one-word keys | counts; two-word hi | lo | count + 4 n words of sort scratch
+          if ((rc = two ? mk_buf_reserve(c, c->ex128, 7 * rows * 8 + 64) : mk_buf_reserve(c, c->ex_keys, rows * 8 + 64)) != MK_OK) return rc;
+          if (!two && (rc = mk_buf_reserve(c, c->ex_cnts, rows * 8 + 64)) != MK_OK) return rc;
+          u64* k0 = (u64*)(two ? c->ex128.p : c->ex_keys.p);
+          u64* cn = two ? k0 + 2 * rows : (u64*)c->ex_cnts.p;
+          u64* d_cursor = (u64*)((char*)c->info.p + sizeof(MkChunkInfo));
+          MK_HIP(hipMemsetAsync(d_cursor, 0, 8, c->stream));
+          if ((rc = two ? mk_launch_compact128(c, (const MkSlot128*)c->run128.p, c->run128_slots, (uint64_t*)k0, (uint64_t*)(k0 + rows),
+                                               (uint64_t*)cn, rows, (uint64_t*)d_cursor)
+                        : mk_launch_compact(c, (const MkSlot*)c->run.p, c->run_slots, (uint64_t*)k0, (uint64_t*)cn, rows,
+                                            (uint64_t*)d_cursor)) != MK_OK) return rc;
+          if ((rc = two ? mk_sort_pairs128(c, (const uint64_t*)k0, (const uint64_t*)(k0 + rows), (const uint64_t*)cn, rows,
+                                           2 * (c->k - 32), (uint64_t*)(cn + rows), (uint64_t*)ok, (uint64_t*)oc)
+                        : mk_sort_pairs(c, (const uint64_t*)k0, (const uint64_t*)cn, (uint64_t*)ok, (uint64_t*)oc, rows,
+                                        c->bits * c->k)) != MK_OK) return rc;
+          d_got = d_cursor;
+        }
+        mk_prof_end(c);
+        if (to_host) {
+          MK_HIP(hipStreamSynchronize(c->stream));  // (so that sort and copy are timed apart: ~10 us)
+          c->ex_st.s_sort += since(t_sort);
+          v.pkeys.resize(w * rows);
+          v.pcnts.resize(rows);
+          MK_HIP(hipMemcpyAsync(v.pkeys.data(), ok, w * rows * 8, hipMemcpyDeviceToHost, c->stream));
+          MK_HIP(hipMemcpyAsync(v.pcnts.data(), oc, rows * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+        MK_HIP(hipMemcpyAsync(got, d_got, binned ? 16 : 8, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipStreamSynchronize(c->stream));
+        if (!(binned && got[0] == rows && got[1])) break;
+        binned = false;  // (keys crowded under one prefix: the whole export again)
+        t_sort = Clk::now();
       }
-      u64 got = 0;
-      MK_HIP(hipMemcpyAsync(&got, d_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-      MK_HIP(hipStreamSynchronize(c->stream));
-      if (got != rows) {
-        c->err = std::string("export: ") + (two ? "two-word table" : "table") + " holds " + std::to_string(got) + " rows, expected " + std::to_string(rows);
+      if (got[0] != rows) {
+        c->err = std::string("export: ") + (two ? "two-word table" : "table") + " holds " + std::to_string(got[0]) + " rows, expected " + std::to_string(rows);
         return MK_ERR_STATE;
       }
     }

@@ -2,9 +2,10 @@
 //
 // The reference writes rows in Python sorted() order of the k-mer strings (bin/mercat2.py:132).
 // Packed keys are MSB-first with codes in ASCII order, so that order is the unsigned integer
-// order of the keys: one device radix sort of (key, count) pairs over the key's used bits.
-// rocPRIM's device radix sort is the ROCm library primitive used for this step (it is not on
-// the counting hot path: it runs once per sample over the surviving rows).
+// order of the keys.  One-word tables are exported by mk_binsort.hip (bins by key prefix, sorted in LDS): the export
+// ends every sample's step and nothing overlaps it.  What is here is the library path: rocPRIM's device radix sort of
+// (key, count) pairs over the key's used bits -- two-word tables, the rows kept as text, a one-word table with more
+// rows under one key prefix than a workgroup sorts, and every export under MK_EXPORT_LIBSORT.
 #include "mk_common.h"
 #include <cstring>
 #include <string.h>
