@@ -19,6 +19,8 @@
 //   3 mk_sk_scatterq same analysis over tiles of 2 or 3 x 512 threads, the records listed in per-wave queues in
 //                    LDS; rank of each record inside its (tile,bucket) run from an LDS counter, one sweep
 //                    of cursor atomics per tile checked against the region ends, 16-byte record stores
+//                    (a run that reaches a thread's last window goes on in the next lane's, MK_SK_SPAN: the histogram,
+//                    which cuts at every thread, is an upper bound per bucket for what is written)
 //   4 mk_sk_count    (mk_skcount.hip) persistent, one workgroup per CU walks the buckets: expands the records into k-mers
 //                    and counts them in an LDS open-addressing table (claim-or-compare with one
 //                    compare-and-swap), emits entries with count >= min_count into the bucket's survivor
@@ -54,17 +56,22 @@ __device__ __forceinline__ void sk_for_each_record(u64 w0, u64 w1, u64 badw, int
   sk_walk(r, w0, w1, nkmax, canon, emit);
 }
 
-__device__ __forceinline__ ulonglong2 sk_make_record(u64 w0, u64 w1, int jstart, int nk, int k) {
-  // (w0:w1) << 2 jstart, its top 2 L bits kept, nk in the low bits -- selects, no branches: the walk's lanes diverge enough
+// (w2: the word after w1 -- a record that goes on into the next thread's windows, mk_sk_scatterq_k, has bases past 63:
+// jstart + nk + k - 2 <= 31 + 31 + 29 = 91)
+__device__ __forceinline__ ulonglong2 sk_make_record(u64 w0, u64 w1, u64 w2, int jstart, int nk, int k) {
+  // (w0:w1:w2) << 2 jstart, its top 2 L bits kept, nk in the low bits -- selects, no branches: the walk's lanes diverge enough
   const int s = 2 * jstart;  // 0 .. 62
   u64 hi = (w0 << s) | ((w1 >> 1) >> (63 - s));
-  u64 lo = w1 << s;
+  u64 lo = (w1 << s) | ((w2 >> 1) >> (63 - s));
   const int t = 2 * (nk + k - 1);  // bits of the record's bases, <= 122
   const u64 mh = t >= 64 ? ~0ull : (~0ull << ((64 - t) & 63));
   const u64 ml = t <= 64 ? 0ull : (~0ull << ((128 - t) & 63));
   hi &= mh;
   lo = (lo & ml) | (u64)nk;
   return make_ulonglong2(hi, lo);
+}
+__device__ __forceinline__ ulonglong2 sk_make_record(u64 w0, u64 w1, int jstart, int nk, int k) {
+  return sk_make_record(w0, w1, 0ull, jstart, nk, k);  // (a record inside one thread's windows: bases up to 63)
 }
 
 // ------------------------------------------------------------------------------ 1 hist
@@ -85,7 +92,9 @@ __global__ __launch_bounds__(SK_HIST_THREADS) void mk_sk_hist_k(const u64* __res
 
 // ------------------------------------------------------------------------------ 2 scan
 // Bucket regions of the record buffer (start/cursor) and of the survivor buffer (kstart) in one pass.
-// Exact histogram: a bucket gets exactly its records, and room for ceil(kmers / min_count) survivors
+// Exact histogram: a bucket gets room for exactly the records the histogram counted -- an upper bound for what the
+// queue scatter writes, whose runs span threads (MK_SK_SPAN): the count kernel reads a region up to its cursor -- and
+// room for ceil(kmers / min_count) survivors
 // (no more entries than that can reach min_count).  Sampled histogram (S = 2^sample_log2): the
 // estimate S*h plus six standard deviations of it plus a floor.  The sampling unit is a thread, which
 // can put up to SK_R / SK_NKMAX records (SK_R k-mers) into one bucket, so the deviation is taken as
@@ -214,7 +223,7 @@ template <int W, bool CANON, int SKQ_SUBT, int SKQ_QCAP>
 __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void mk_sk_scatterq_k(const u64* __restrict__ codes, const u64* __restrict__ bad,
                                                          MkChunkInfo* __restrict__ info, const u64* __restrict__ start,
                                                          SkCursor* __restrict__ cursor, ulonglong2* __restrict__ part,
-                                                         int p1_log2, int k, int nkmax, size_t ntiles, unsigned qcap, int nseg) {
+                                                         int p1_log2, int k, int nkmax, size_t ntiles, unsigned qcap, int nseg, int span) {
   // nseg = 9: a bucket has one region per XCD (and a shared one, below) and this workgroup fills the regions of the XCD
   // it runs on: the sectors of a line then reach the memory side from one L2 instead of eight (scatter -10..-17 %; the bytes
   // written stay what they were, 32 per 16-byte record: a partly written sector leaves the L2 long before its neighbour
@@ -248,6 +257,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   const unsigned p1 = 1u << p1_log2;
   const size_t seq_len = info->seq_len;
   const int lane = threadIdx.x & 63;
+  const unsigned nk_recip = 65535u / (unsigned)nkmax + 1u;  // (sk_span_in)
   // (the wave's number, computed again at every use from an empty asm: kept in a register -- with the queue and word-row
   // addresses the compiler derives from it for every sub-tile -- it was spilled to scratch under the kernel's 128 registers
   // and loaded back once per sub-tile)
@@ -279,7 +289,25 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
       }
       pk_x[st][wv][lane] = ww0;
       if (lane == 63) pk_x[st][wv][64] = ww1;
-      const unsigned s2 = sk_cut_starts(runs.starts, runs.valid, nkmax);
+      // span: a run that reaches the thread's last window goes on in the next lane's first windows (sk_span_in) instead
+      // of being cut there for no reason of the data's -- 8.8 % fewer records on reads at k = 31.  The record belongs to
+      // the lane it starts in: the next lane tells how many of its windows (`ext`: up to its first start, cut or invalid
+      // window) the record takes, and does not list them.  The wave's ends stay cuts (lane 0 is handed nothing, lane 63
+      // told nothing: a wave reads no other wave's words); threads past the text have no valid window and hand on nothing.
+      // The histogram and the walking waves below keep the cut at every thread: a run in one piece files under the same
+      // minimizer, so in the same bucket, as its two halves, and ceil((a + b) / nkmax) <= ceil(a / nkmax) + ceil(b / nkmax):
+      // the histogram is an UPPER BOUND per bucket for what is written here, sampled or exact, and the count kernel
+      // reads a region up to min(cursor, end).
+      unsigned st2 = runs.starts, seed = 0, ext = 0;
+      if (span)  // (wave_shr:1 -- lane t from lane t - 1, lane 0 keeps the 0)
+        seed = sk_span_in((unsigned)__builtin_amdgcn_update_dpp(0, (int)sk_span_out(runs), 0x138, 0xf, 0xf, false), st2, runs.valid,
+                          (unsigned)runs.pos[0] & 63u, nkmax, nk_recip);
+      const unsigned s2 = sk_cut_starts(st2, runs.valid, nkmax, seed);
+      if (span) {  // (wave_shl:1 -- lane t from lane t + 1, lane 63 keeps the 0)
+        const unsigned ends = s2 | ~runs.valid;  // (not empty where a run came in: sk_span_in)
+        const unsigned mine = (runs.starts & ~st2 & 1u) ? (unsigned)__ffs((int)ends) - 1u : 0u;
+        ext = (unsigned)__builtin_amdgcn_update_dpp(0, (int)mine, 0x130, 0xf, 0xf, false);
+      }
       const unsigned cnt = __popc(s2);
       const unsigned inc = mk_wave_scan_incl(cnt);  // inclusive scan over the wave
       const unsigned total = mk_wave_last(inc);
@@ -290,7 +318,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
           const int j = __ffs(todo) - 1;
           todo &= todo - 1;
           const unsigned stop = (s2 | ~runs.valid) & ~((2u << j) - 1);
-          const int nk = (stop ? (__ffs(stop) - 1) : SK_R) - j;
+          const int nk = (stop ? (__ffs(stop) - 1) : SK_R + (int)ext) - j;  // (at most nkmax with ext: sk_span_in's cut)
           const u64 pw = j < 10 ? runs.pos[0] : (j < 20 ? runs.pos[1] : (j < 30 ? runs.pos[2] : runs.pos[3]));
           const unsigned best = (unsigned)(pw >> (6 * (j % 10))) & 63u;
           myq[at++] = (unsigned)lane | ((unsigned)j << 6) | ((unsigned)nk << 11) | (best << 16);
@@ -314,7 +342,7 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
           }
         }
         qn[st] = total;
-      } else {
+      } else {  // (wave-uniform: either all of a wave's lanes span or none does; the walk is the un-spanned runs' own)
         if (p0 < seq_len)
           sk_walk(runs, ww0, ww1, nkmax, CANON, [&](int, int, unsigned mm) {
             atomicAdd(&lh[sk_bucket(mm, p1_log2)], 1u);
@@ -398,7 +426,10 @@ __global__ __launch_bounds__(SKQ_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
             const unsigned it = myq[i];
             const unsigned at = atomicAdd(&lh[it >> 16], 1u);  // base + rank
             const u64* const wp = &pk_x[st][wv][it & 63u];
-            ulonglong2 rec = sk_make_record(wp[0], wp[1], (int)((it >> 6) & 31u), (int)((it >> 11) & 31u), k);
+            // (the third word: the lane after next's first, or for lane 62 the wave's entry 64 -- lane 63 never spans and
+            // needs none)
+            const u64 w2 = pk_x[st][wv][(it & 63u) < 62u ? (it & 63u) + 2u : 64u];
+            ulonglong2 rec = sk_make_record(wp[0], wp[1], w2, (int)((it >> 6) & 31u), (int)((it >> 11) & 31u), k);
             asm volatile("" : "+v"(rec.x), "+v"(rec.y));  // (built while the LDS answers)
             if (at < SK_NOFIT) part[(size_t)at] = rec;
           }
@@ -442,7 +473,7 @@ void mk_launch_sk_scan(mk_ctx* c, const u64* hist, const u64* khist, u64* start,
 
 template <int W, bool CANON>
 static void launch_wc(mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sample_log2, u64 surv_div, u64 part_cap, u64 surv_cap,
-                     u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg) {
+                     u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg, int span) {
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
   const size_t threads = div_up(seq_len, SK_R);
   const size_t tiles = div_up(div_up(threads, (size_t)1 << sample_log2), SK_HIST_THREADS);
@@ -465,10 +496,10 @@ static void launch_wc(mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sam
   const dim3 qgrid((unsigned)(qtiles < SK_SCAT_GRID ? qtiles : SK_SCAT_GRID));
   if (three)
     hipLaunchKernelGGL((mk_sk_scatterq_k<W, CANON, 3, 376>), qgrid, dim3(SKQ_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg);
+                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg, span);
   else
     hipLaunchKernelGGL((mk_sk_scatterq_k<W, CANON, 2, 512>), qgrid, dim3(SKQ_THREADS), 0, c->stream, (const u64*)c->codes.p,
-                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg);
+                       (const u64*)c->bad.p, info, (const u64*)start, cursor, (ulonglong2*)c->part.p, p1_log2, c->k, nkmax, qtiles, qcap, nseg, span);
 #ifdef MK_STAMP
   {
     (void)hipStreamSynchronize(c->stream);
@@ -487,10 +518,10 @@ static void launch_wc(mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sam
 // histogram + scan + scatter for W = k - 10 minimizer candidates per window; false: W out of range
 template <bool CANON>
 static bool sk_partition(int W, mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sample_log2, u64 surv_div, u64 part_cap, u64 surv_cap,
-                         u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg) {
+                         u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg, int span) {
   switch (W) {
 #define SK_CASE(W_)                                                                                                      \
-  case W_: launch_wc<W_, CANON>(c, seq_len, p1_log2, nkmax, sample_log2, surv_div, part_cap, surv_cap, hist, start, cursor, khist, kstart, reuse, nseg); return true;
+  case W_: launch_wc<W_, CANON>(c, seq_len, p1_log2, nkmax, sample_log2, surv_div, part_cap, surv_cap, hist, start, cursor, khist, kstart, reuse, nseg, span); return true;
     SK_CASE(2) SK_CASE(3) SK_CASE(4) SK_CASE(5) SK_CASE(6) SK_CASE(7)
     SK_CASE(8) SK_CASE(9) SK_CASE(10) SK_CASE(11) SK_CASE(12) SK_CASE(13) SK_CASE(14) SK_CASE(15) SK_CASE(16)
     SK_CASE(17) SK_CASE(18) SK_CASE(19) SK_CASE(20) SK_CASE(21) SK_CASE(22)
@@ -501,12 +532,12 @@ static bool sk_partition(int W, mk_ctx* c, size_t seq_len, int p1_log2, int nkma
 
 #ifdef SK_TU_CANON
 bool mk_sk_partition_canon(int W, mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sample_log2, u64 surv_div, u64 part_cap,
-                           u64 surv_cap, u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg) {
-  return sk_partition<true>(W, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, part_cap, surv_cap, hist, start, cursor, khist, kstart, reuse, nseg);
+                           u64 surv_cap, u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg, int span) {
+  return sk_partition<true>(W, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, part_cap, surv_cap, hist, start, cursor, khist, kstart, reuse, nseg, span);
 }
 #else
 bool mk_sk_partition_canon(int W, mk_ctx* c, size_t seq_len, int p1_log2, int nkmax, int sample_log2, u64 surv_div, u64 part_cap,
-                           u64 surv_cap, u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg);
+                           u64 surv_cap, u64* hist, u64* start, SkCursor* cursor, u64* khist, u64* kstart, bool reuse, int nseg, int span);
 
 // Chunks of one sample are equally long (the Chunker cuts at the first record past the size) and drawn from the
 // same text: a chunk whose predecessor sized its buckets from the sampled histogram -- the estimate plus six
@@ -587,6 +618,8 @@ int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, boo
   if (nseg != c->part_nseg) c->part_reuse_ok = false;  // (regions of the other layout cannot be inherited)
   c->part_nseg = nseg;
   const bool reuse = mk_part_inherit(c, seq_len, p1_log2, min_count, sample_log2 != 0, exact);
+  // MK_SK_SPAN=0: the scatter cuts every run at the end of its thread's 32 windows, as the histogram does (A/B runs, tests)
+  const int span = mk_env_int("MK_SK_SPAN", 1) != 0 ? 1 : 0;
   int rc;
   // (room for the nine-region layout whichever this chunk uses)
   if ((rc = mk_buf_reserve(c, c->part_meta, sk_meta_words(p1, SKC_SEG_MAX) * sizeof(u64))) != MK_OK) return rc;
@@ -603,11 +636,11 @@ int mk_launch_count_superkmer(mk_ctx* c, size_t seq_len, uint64_t min_count, boo
   mk_prof_begin(c, MK_K_PART);
   // (the canonical instances live in a translation unit of their own, mk_skmer_canon.hip: half the compile time each)
   if (c->canonical) {
-    if (!mk_sk_partition_canon(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, m.hist, m.start, m.cursor, m.khist, m.kstart, reuse, nseg)) {
+    if (!mk_sk_partition_canon(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, m.hist, m.start, m.cursor, m.khist, m.kstart, reuse, nseg, span)) {
       c->err = "mk_launch_count_superkmer: k out of range";
       return MK_ERR_ARG;
     }
-  } else if (!sk_partition<false>(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, m.hist, m.start, m.cursor, m.khist, m.kstart, reuse, nseg)) {
+  } else if (!sk_partition<false>(k - SK_M + 1, c, seq_len, p1_log2, nkmax, sample_log2, surv_div, (u64)part_cap, (u64)surv_cap, m.hist, m.start, m.cursor, m.khist, m.kstart, reuse, nseg, span)) {
     c->err = "mk_launch_count_superkmer: k out of range";
     return MK_ERR_ARG;
   }

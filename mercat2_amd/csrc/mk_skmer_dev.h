@@ -238,16 +238,46 @@ __device__ __forceinline__ void sk_walk(const SkRuns& r, u64 w0, u64 w1, int nkm
 
 // Run starts with the cuts put in: a run longer than nkmax windows is cut every nkmax windows (what sk_walk does on
 // the fly), so that every set bit is one record.
-__device__ __forceinline__ unsigned sk_cut_starts(unsigned starts, unsigned valid, int nkmax) {
-  if (nkmax >= SK_R) return starts;
+// `seed`: cuts known beforehand (sk_span_in: the first cut of a run that came in from the thread before); the chain of
+// cuts every nkmax windows goes on from them as it does from the starts.
+__device__ __forceinline__ unsigned sk_cut_starts(unsigned starts, unsigned valid, int nkmax, unsigned seed = 0) {
+  if (nkmax >= SK_R) return starts | seed;
   const unsigned cont = valid & ~starts;  // windows that continue their run
   unsigned a = cont;                      // a[p] = cont[p - nkmax + 1 .. p] all set
   int len = 1;
   while (2 * len <= nkmax) { a &= a << len; len *= 2; }
   if (len < nkmax) a &= a << (nkmax - len);
-  unsigned s2 = starts;
-  for (unsigned c = (starts << nkmax) & a; c; c = (c << nkmax) & a) s2 |= c;
+  unsigned s2 = starts | seed;
+  for (unsigned c = (s2 << nkmax) & a; c; c = (c << nkmax) & a) s2 |= c;
   return s2;
+}
+
+// ---- runs that go on across the boundary between two analysis threads of a wave (mk_sk_scatterq_k)
+// Window 31 of lane t and window 0 of lane t + 1 are neighbours in the text: when both are valid and have their minimizer
+// at the same place, they belong to one run -- the same rule as between two windows of a thread (the order is strict and
+// total).  A run is at most W = k - 10 <= 22 windows long, so it touches two threads at most, and what a lane hands on
+// depends on nothing that it is handed.
+// What lane t hands lane t + 1: bit 0 window 31 is valid, bits 1..6 its minimizer position (lane t's frame), bits 7.. the
+// windows the run has so far, 32 - its start (a valid window 31 has a start at or below it).
+__device__ __forceinline__ unsigned sk_span_out(const SkRuns& r) {
+  const unsigned pos31 = (unsigned)(r.pos[3] >> 6) & 63u;
+  return (r.valid >> 31) | (pos31 << 1) | (((unsigned)__clz((int)r.starts) + 1u) << 7);
+}
+// What the lane before handed this one (`in`, 0 for nothing).  When its run goes on here: `starts` loses bit 0, the
+// return value is the run's first cut in this thread -- where the windows before (`in` >> 7) and here reach a multiple of
+// nkmax, if the run lives that long: the cap stays a hard limit, counted from the run's true start -- as a seed for
+// sk_cut_starts.  nk_recip = 65535 / nkmax + 1: floor(c / nkmax) = c * nk_recip >> 16 for nkmax <= 31 and every c that
+// sk_span_out can hand on (1 .. 33: 32 with the start at window 0, 33 with no start at all, and then bit 0 is clear); a run
+// that does go on has c <= W - 1 <= 21.
+__device__ __forceinline__ unsigned sk_span_in(unsigned in, unsigned& starts, unsigned valid, unsigned pos0, int nkmax,
+                                               unsigned nk_recip) {
+  const unsigned ends = (starts & ~1u) | ~valid;  // where a run from window 0 would end (never empty: W < SK_R)
+  const bool go = (in & 1u) && (valid & 1u) && ends != 0 && pos0 + SK_R == ((in >> 1) & 63u);
+  if (!go) return 0u;
+  starts &= ~1u;
+  const unsigned c = in >> 7, phase = c - ((c * nk_recip) >> 16) * (unsigned)nkmax;
+  const unsigned j0 = phase ? (unsigned)nkmax - phase : 0u, e = (unsigned)__ffs((int)ends) - 1u;
+  return j0 < e ? 1u << j0 : 0u;
 }
 
 // The histogram kernels' body (mk_sk_hist_k, mk_sk2_hist_k): records and k-mers per bucket, counted in the LDS arrays
