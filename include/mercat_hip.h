@@ -479,6 +479,50 @@ int mk_track_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags
                     void* d_counts, size_t counts_cap, size_t* nwindows,
                     uint64_t* d_offsets, void* d_median, mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_track_t* st);
 
+/* ---- sequences in, every record cut in front of its first low-abundance k-mer out: what one scans mk_track_*'s counts
+ *      for, done where the counts are (khmer's trim_on_abundance / filter-abund, the error trimming in front of an
+ *      assembly or a second count) ----
+ * Text, records, windows, probing, fold, opening rules and errors are mk_screen_*'s, word for word: same parser, same
+ * rows (rows[r] is the screen row of record r for the same text and rule->at_least), same mk_screen_t figures
+ * (st->screen; its s_total is the wall time of this whole call), the table only read and made final first, MK_ERR_STATE
+ * with an open chunk or a refused one, MK_ERR_NON_ASCII, the fold rule (MK_TRIM_FOLD = MK_SCREEN_FOLD), pieces cut by
+ * mk_record_cuts, the stream idle afterwards, the counting figures and the export untouched.
+ * Rule: a window is LOW when its count -- the one mk_lookup returns for those k bytes, folded under MK_TRIM_FOLD, 0 for
+ * an absent k-mer -- is below at_least.  Record r has L kept characters and rows[r].windows windows; j is the index of
+ * its first low window.  No low window: kept[r] = L.  j >= 1: kept[r] = j + k - 1 (the characters in front of the last
+ * one of window j).  j = 0, or no window at all: kept[r] = 0.  Then kept[r] < max(min_len, k) gives kept[r] = 0
+ * (min_len 0 means k).  A record is emitted iff kept[r] > 0.  kept numbers the records of the whole call, not a piece.
+ * Output: the emitted records in text order, each as the bytes of its header LINE as they stand -- from the first byte of
+ * the line (mk_filter_*'s record start, leading blanks included) through its terminator LF, CR LF or lone CR; none for
+ * the headless record -- then its first kept[r] kept characters on one line and one LF.  The sequence comes from the
+ * parsed stream, so it is exactly what was probed: '*' removed, lines stripped and joined.  Nothing of the preamble
+ * (st->preamble, as in mk_filter_t) is emitted.  *out_len <= n + 1; for a text of one-line, LF-terminated records of
+ * which none is trimmed or dropped the output is the input byte for byte.
+ * at_least >= 1; a NULL rule, at_least == 0 or an unknown flag bit is MK_ERR_ARG and the message names it.  kept and
+ * rows may each be NULL (cap is ignored when both are).  With out_cap or cap too small: MK_ERR_RANGE, the needed sizes
+ * in *out_len and *nrows, nothing written past either -- every piece is still walked to learn them (out = NULL,
+ * out_cap = 0 is the sizing call).  st may be NULL.
+ * mk_trim_text: host memory in and out, piece by piece (each piece's output is appended to out by its copy back).
+ * mk_trim_device: text, out, kept and rows in DEVICE memory of the context's GPU, one piece; text and out at any
+ * address, d_kept and d_rows aligned to 8 (MK_ERR_ARG otherwise). */
+#define MK_TRIM_FOLD 1u          /* = MK_SCREEN_FOLD */
+typedef struct mk_trim_rule_t { uint64_t at_least, min_len; } mk_trim_rule_t;
+typedef struct mk_trim_t {
+  mk_screen_t screen;                                      /* as mk_screen_* fills it for the same text and at_least */
+  uint64_t records_out, records_trimmed, records_dropped;  /* emitted; emitted shorter than they came; not emitted */
+  uint64_t bases_in, bases_out, bytes_out;                 /* kept characters of all records; emitted; output bytes */
+  uint64_t preamble;                                       /* bytes in front of the first header line of a text that is not headless */
+  /* seconds: HIP-event time of the record starts and header ends; of the first-low walk; of the gather (the decision
+   * and its scan run between the two and are in none); host time in the copies back */
+  double s_place, s_first, s_gather, s_write;
+} mk_trim_t;
+int mk_trim_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, const mk_trim_rule_t* rule,
+                 uint8_t* out, size_t out_cap, size_t* out_len, uint64_t* kept, mk_screen_row_t* rows, size_t cap,
+                 size_t* nrows, mk_trim_t* st);
+int mk_trim_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_trim_rule_t* rule,
+                   uint8_t* d_out, size_t out_cap, size_t* out_len, uint64_t* d_kept, mk_screen_row_t* d_rows, size_t cap,
+                   size_t* nrows, mk_trim_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

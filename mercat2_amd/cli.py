@@ -23,7 +23,10 @@ holds, and how abundant they are (mk_screen_text).  -filter FILE writes, for eve
 filter_<type>/<sample>_<matched|unmatched>.fna (.faa): the records of FILE that share k-mers with the sample's table, or those
 that do not, copied out on the GPU (mk_filter_text).  -track FILE writes, for every sample of FILE's type,
 track_<type>/<sample>_track.txt -- per record of FILE the count of every one of its k-mers in the sample's table, in read
-order -- and track_<type>/<sample>_median.tsv with the median of those counts (mk_track_text).  -against FILE -op OP writes, for every sample of FILE's type,
+order -- and track_<type>/<sample>_median.tsv with the median of those counts (mk_track_text).  -trim FILE writes, for every
+sample of FILE's type, trim_<type>/<sample>_trimmed.fna (.faa): every record of FILE cut in front of its first k-mer the
+sample's table holds fewer than -trim_min times, as khmer's filter-abund trims (mk_trim_text), and
+trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
 (mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
@@ -93,6 +96,16 @@ def parseargs(argv=None):
                         "of its k-mers in the sample, in read order (0: absent), and track_<type>/<sample>_median.tsv with "
                         "each record's k-mers, the median of their counts, and their sum, smallest and largest")
     p.add_argument("-track_sat32", action="store_true", help="-track: 32-bit counts, clipped at 2^32 - 1 (half the bytes moved)")
+    p.add_argument("-trim", type=str, required=False, metavar="FILE",
+                   help="a FASTA or FASTQ file (plain or .gz) of reads to trim against the tables on the GPU: for every sample "
+                        "of FILE's type, trim_<type>/<sample>_trimmed.fna (.faa for protein) with every record of FILE cut in "
+                        "front of its first k-mer the sample holds fewer than -trim_min times -- its header line, then what it "
+                        "keeps on one line; a record that keeps fewer than -trim_len characters is dropped -- and "
+                        "trim_<type>/<sample>_trim.tsv with 'record, length, kept' per record.  A FASTQ file is first "
+                        "converted as MerCat2's fq2fa converts it, so the output is FASTA; with -canonical the k-mers are folded")
+    p.add_argument("-trim_min", type=int, default=None, metavar="N",
+                   help="-trim: a k-mer is low below this count [2, the default cutoff of khmer's filter-abund]")
+    p.add_argument("-trim_len", type=int, default=None, metavar="N", help="-trim: drop a record that keeps fewer characters [k]")
     p.add_argument("-filter_min", type=int, default=None, metavar="N", help="-filter: a k-mer is a hit from this count on [1]")
     p.add_argument("-filter_hits", type=int, default=None, metavar="N", help="-filter: a record matches from this many hits on [1]")
     p.add_argument("-filter_frac", type=float, default=None, metavar="F",
@@ -174,6 +187,23 @@ def parseargs(argv=None):
             p.error(f"-track {args.track}: the extension names neither a nucleotide, a protein nor a FASTQ file")
     elif args.track_sat32:
         p.error("-track_sat32 needs -track FILE")
+    args.trim_kind = None
+    if not args.trim:
+        for flag in ("trim_min", "trim_len"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -trim FILE")
+    else:
+        if not os.path.isfile(args.trim):
+            p.error(f"file '{args.trim}' is not valid.\n")
+        args.trim_kind = classify(Path(args.trim).expanduser().absolute(), True)[0]
+        if not args.trim_kind:
+            p.error(f"-trim {args.trim}: the extension names neither a nucleotide, a protein nor a FASTQ file")
+        args.trim_min = 2 if args.trim_min is None else args.trim_min
+        if not 1 <= args.trim_min < 1 << 64:
+            p.error(f"-trim_min {args.trim_min}: must be 1 or more")
+        if args.trim_len is not None and not 1 <= args.trim_len < 1 << 64:
+            p.error(f"-trim_len {args.trim_len}: must be 1 or more")
+        args.trim_len = args.trim_len or 0  # (0: the k-mer length)
     args.filter_kind = None
     if not args.filter:
         for flag in ("filter_min", "filter_hits", "filter_frac", "filter_keep"):
@@ -591,6 +621,21 @@ def main(argv=None) -> int:
                         tracked = (len(names), len(counts))
                     print(f"track_{kind}/: the {tracked[1]} k-mers of the {tracked[0]} records of {os.path.basename(args.track)} "
                           f"tracked against each of {len(tables)} sample(s)")
+                if args.trim and args.trim_kind == kind:  # from the tables still on the GPU
+                    from .kmers import trim_reads
+                    (out / f"trim_{kind}").mkdir(parents=True, exist_ok=True)
+                    ext = "faa" if kind == "protein" else "fna"
+                    kept = {}
+                    for base in sorted(tables):
+                        try:
+                            res = trim_reads(tables[base], args.trim, out / f"trim_{kind}" / f"{base}_trimmed.{ext}", args.trim_min,
+                                             args.trim_len, tsv_path=out / f"trim_{kind}" / f"{base}_trim.tsv")
+                        except native.MercatHipError as e:
+                            raise SystemExit(f"-trim {args.trim}: {e}")
+                        kept[base] = (res["kept"], res["trimmed"])
+                    print(f"trim_{kind}/: {res['records']} records of {os.path.basename(args.trim)} trimmed against "
+                          f"{len(tables)} sample(s), records written (of them cut): " +
+                          ", ".join(f"{base} {n} ({t})" for base, (n, t) in kept.items()))
                 if args.against and args.against_kind == kind:  # from the tables still on the GPU
                     try:
                         rows = write_against_tsvs({base: tables[base] for base in sorted(tables)}, args.against, args.op,

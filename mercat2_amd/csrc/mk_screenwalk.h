@@ -1,6 +1,8 @@
 // mk_screenwalk.h -- the lane walk over one tile of the parsed stream, with the sink a template parameter, and the
 // ladder that picks a walking kernel's instantiation.  sc_probe_k (mk_screen.hip) folds every window's count into the
-// record's row; tk_probe_k (mk_track.hip) writes it where its window stands.  The walk's device code reacts to
+// record's row; tk_probe_k (mk_track.hip) writes it where its window stands; tr_first_k (mk_trim.hip) keeps the place of
+// the first low one.  tk_starts_k, which tells a positional sink where every record starts in the stream, is here too
+// (static: mk_track.hip and mk_trim.hip each launch their own copy).  The walk's device code reacts to
 // restructuring: a change here is measured on both kernels (profiles/screen_walk.md, DESIGN 8p "one walk").
 //
 // A lane owns SC_RUN consecutive window starts: it walks k - 1 + SC_RUN symbols of the workgroup's span (staged in LDS
@@ -136,6 +138,24 @@ __device__ __forceinline__ u64 sc_walk(uint8_t* __restrict__ s_seq, const uint8_
     }
   }
   return rid;
+}
+
+// sstart[r] = the stream position of the first symbol of row r: behind its separator, 0 for a headless row 0.  The
+// record scan of sc_probe_k on the stream's own tiles (tile_pre: separators in front of every tile).
+static __global__ void __launch_bounds__(256) tk_starts_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
+                                                   u64 row_base, size_t nrows, u64* __restrict__ sstart) {
+  __shared__ unsigned s_wave[4];
+  const u64 at = (u64)blockIdx.x * SC_SPAN + (u64)threadIdx.x * SC_RUN;
+  unsigned own = 0;
+  for (int j = 0; j < SC_RUN && at + j < seq_len; ++j) own += seq[at + j] == MK_SEP;
+  u64 rid = tile_pre[blockIdx.x] + mk_block_scan_excl(own, s_wave);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && row_base == 0 && nrows) sstart[0] = 0;
+  if (own)
+    for (int j = 0; j < SC_RUN && at + j < seq_len; ++j)
+      if (seq[at + j] == MK_SEP) {
+        ++rid;
+        if (rid - row_base < nrows) sstart[rid - row_base] = at + j + 1;
+      }
 }
 
 // The seven instantiations of a walking kernel, by the context's key kind, the call's fold and whether LDS holds the

@@ -42,24 +42,6 @@ __global__ void __launch_bounds__(256) tk_lens_k(const mk_screen_row_t* __restri
   if ((threadIdx.x & 63) == 0 && mx) atomicMax((unsigned long long*)&st->max_count, mx);
 }
 
-// sstart[r] = the stream position of the first symbol of row r: behind its separator, 0 for a headless row 0.  The
-// record scan of sc_probe_k on the stream's own tiles (tile_pre: separators in front of every tile).
-__global__ void __launch_bounds__(256) tk_starts_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
-                                                   u64 row_base, size_t nrows, u64* __restrict__ sstart) {
-  __shared__ unsigned s_wave[4];
-  const u64 at = (u64)blockIdx.x * SC_SPAN + (u64)threadIdx.x * SC_RUN;
-  unsigned own = 0;
-  for (int j = 0; j < SC_RUN && at + j < seq_len; ++j) own += seq[at + j] == MK_SEP;
-  u64 rid = tile_pre[blockIdx.x] + mk_block_scan_excl(own, s_wave);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && row_base == 0 && nrows) sstart[0] = 0;
-  if (own)
-    for (int j = 0; j < SC_RUN && at + j < seq_len; ++j)
-      if (seq[at + j] == MK_SEP) {
-        ++rid;
-        if (rid - row_base < nrows) sstart[rid - row_base] = at + j + 1;
-      }
-}
-
 __global__ void __launch_bounds__(256) tk_offsets_k(const u64* __restrict__ woff, size_t n, u64 add, u64* __restrict__ out) {
   mk_for_each(n, [&](size_t r) { out[r] = woff[r] + add; });
 }

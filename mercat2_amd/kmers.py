@@ -122,6 +122,22 @@ def record_names(text: bytes) -> List[str]:
     return ([""] if headless else []) + names
 
 
+def record_lengths(text: bytes) -> List[int]:
+    """The kept characters of every record of a FASTA text, numbered as ``record_names`` numbers them: what find_kmers
+    joins of the record's lines (line.strip(), '*' removed)."""
+    lengths: List[int] = []
+    headless = 0
+    for line in bytes(text).replace(b"\r\n", b"\n").replace(b"\r", b"\n").split(b"\n"):
+        line = line.strip(_BLANKS)
+        if line.startswith(b">"):
+            lengths.append(0)
+        elif lengths:
+            lengths[-1] += len(line) - line.count(b"*")
+        else:
+            headless += len(line) - line.count(b"*")
+    return ([headless] if headless else []) + lengths
+
+
 def screen_reads(table: "native.Counter", file: Union[str, Path], at_least: int = 1) -> Tuple[List[str], "native.np.ndarray"]:
     """(names, array) of every record of a FASTA or FASTQ file screened against a table that is still on the GPU
     (Counter.screen): array[i] = (windows, hits, sum, min, max) of record i -- its k-mers, how many of them the table
@@ -177,3 +193,32 @@ def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Unio
         with open(out_path, "wb") as fh:
             fh.write(out)
     return {"records": int(keep.shape[0]), "kept": int(keep.sum()), "bytes_in": len(text), "bytes_out": len(out)}
+
+
+def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 2,
+               min_len: int = 0, tsv_path: Union[str, Path, None] = None) -> Dict[str, int]:
+    """The records of a FASTA or FASTQ file, each cut in front of its first k-mer that a table still on the GPU holds fewer
+    than ``at_least`` times (Counter.trim: khmer's trim_on_abundance), written to ``out_path`` -- gzip (level 1) if that
+    name ends in '.gz', plain bytes otherwise.  A record of which fewer than max(``min_len``, k) characters remain is
+    dropped.  The file is read as filter_reads reads it: '.gz' inflated on the host, a FASTQ file first converted as
+    MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is always FASTA: the header line as it stands, the kept
+    characters on one line.  A canonical table folds the windows.  Returns {"records", "kept", "trimmed", "dropped",
+    "bases_in", "bases_out", "bytes_out"}.  With ``tsv_path`` every record's name, length and kept characters are written
+    there too (report.write_trim_tsv)."""
+    text = read_fasta_bytes(file)
+    if str(file).lower().endswith(FASTQ_SUFFIXES):
+        text, _ = native.fq2fa(text)
+    info: Dict[str, int] = {}
+    out, kept, _ = table.trim(text, at_least, min_len, info=info)
+    if str(out_path).lower().endswith(".gz"):
+        with gzip.open(out_path, "wb", compresslevel=1) as fh:
+            fh.write(out)
+    else:
+        with open(out_path, "wb") as fh:
+            fh.write(out)
+    if tsv_path is not None:
+        from .report import write_trim_tsv
+        write_trim_tsv(tsv_path, record_names(text), record_lengths(text), kept)
+    return {"records": int(kept.shape[0]), "kept": int(info["records_out"]), "trimmed": int(info["records_trimmed"]),
+            "dropped": int(info["records_dropped"]), "bases_in": int(info["bases_in"]), "bases_out": int(info["bases_out"]),
+            "bytes_out": len(out)}

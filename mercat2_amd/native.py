@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
-    "mk_track_text", "mk_track_device",
+    "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -44,6 +44,7 @@ LOOKUP_FOLD = 1
 SCREEN_FOLD = 1
 FILTER_FOLD, FILTER_INVERT = 1, 2
 TRACK_FOLD, TRACK_SAT32 = 1, 2
+TRIM_FOLD = 1
 # mk_table_op: f(ca, cb) per key (include/mercat_hip.h)
 OP_MIN, OP_MAX, OP_SUM, OP_LEFT, OP_ONLY, OP_DIFF = range(6)
 OPS = {"min": OP_MIN, "max": OP_MAX, "sum": OP_SUM, "left": OP_LEFT, "only": OP_ONLY, "diff": OP_DIFF}
@@ -154,6 +155,24 @@ class Track(C.Structure):
     """mk_track_t (include/mercat_hip.h)."""
     _fields_ = ([("screen", Screen)] + [(n, C.c_uint64) for n in ("windows_out", "saturated")] +
                 [(n, C.c_double) for n in ("s_place", "s_track", "s_median", "s_write")])
+
+    def as_dict(self):
+        d = self.screen.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+class TrimRule(C.Structure):
+    """mk_trim_rule_t (include/mercat_hip.h)."""
+    _fields_ = [("at_least", C.c_uint64), ("min_len", C.c_uint64)]
+
+
+class Trim(C.Structure):
+    """mk_trim_t (include/mercat_hip.h)."""
+    _fields_ = ([("screen", Screen)] +
+                [(n, C.c_uint64) for n in ("records_out", "records_trimmed", "records_dropped", "bases_in", "bases_out",
+                                           "bytes_out", "preamble")] +
+                [(n, C.c_double) for n in ("s_place", "s_first", "s_gather", "s_write")])
 
     def as_dict(self):
         d = self.screen.as_dict()
@@ -327,6 +346,10 @@ def lib() -> C.CDLL:
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Track)]),
         "mk_track_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.c_uint64, C.c_void_p, C.c_size_t, szp,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Track)]),
+        "mk_trim_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(TrimRule), C.c_void_p, C.c_size_t, szp,
+                                   C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
+        "mk_trim_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(TrimRule), C.c_void_p, C.c_size_t, szp,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
         "mk_table_op": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(TableOp)]),
     }
     L.mk_version.restype = C.c_char_p
@@ -1095,6 +1118,52 @@ class Counter:
                                             median_ptr or None, rows_ptr or None, int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
 
+    # -- trimming: FASTA text in, every record cut in front of its first low-abundance k-mer out; the table is only read
+    def trim(self, path_or_bytes=None, at_least: int = 2, min_len: int = 0, fold: Optional[bool] = None, piece_bytes: int = 0,
+             info: Optional[dict] = None):
+        """Without arguments, mk_trim: free the per-chunk working memory, keep the running table; returns None.
+        With a text, mk_trim_text: (out, kept, rows) of the FASTA text (a path to a plain file, or the text itself as bytes).  A
+        record is cut in front of the last character of its first k-mer the table holds fewer than ``at_least`` times
+        (khmer's trim_on_abundance); ``kept[r]`` is the number of characters record r keeps -- 0, and the record is not
+        emitted, when its first k-mer is low, when it has no k-mer, or when fewer than max(``min_len``, k) remain.
+        ``out``: the emitted records in order, each its header line as it stands, then the kept characters on one line
+        and a newline.  ``rows``: the (records, 5) uint64 array Counter.screen gives for the same text and ``at_least``.
+        ``fold`` None: fold iff the context is canonical.  ``info``, if given, receives the mk_trim_t fields (those of
+        mk_screen_t beside them)."""
+        if path_or_bytes is None:
+            self._check(self._L.mk_trim(self._h))
+            return None
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(held == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        kept = np.zeros(cap, dtype=np.uint64)
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Trim()
+        rule = TrimRule(int(at_least), int(min_len))
+        self._check(self._L.mk_trim_text(self._h, addr, size, int(piece_bytes), TRIM_FOLD if self._fold_flag(fold) else 0,
+                                         C.byref(rule), out.ctypes.data, size + 1, C.byref(out_len), kept.ctypes.data,
+                                         rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), kept[: n.value], rows[: n.value]
+
+    def trim_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, kept_ptr: int = 0, rows_ptr: int = 0, cap: int = 0,
+                    at_least: int = 2, min_len: int = 0, fold: Optional[bool] = None) -> dict:
+        """mk_trim_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> the trimmed records at
+        device address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) and, where given, one uint64 of
+        kept characters a record at ``kept_ptr`` and the rows (five uint64 a record) at ``rows_ptr`` with room for
+        ``cap`` records each -- all on this context's GPU, the last two aligned to 8.  Returns the mk_trim_t fields:
+        "bytes_out" bytes were written, "records" rows."""
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Trim()
+        rule = TrimRule(int(at_least), int(min_len))
+        self._check(self._L.mk_trim_device(self._h, ptr, int(nbytes), TRIM_FOLD if self._fold_flag(fold) else 0, C.byref(rule),
+                                           out_ptr or None, int(out_cap), C.byref(out_len), kept_ptr or None, rows_ptr or None,
+                                           int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
     # -- results
     def rows(self) -> int:
         n = C.c_size_t(0)
@@ -1170,10 +1239,6 @@ class Counter:
         self._check(self._L.mk_alpha_stats(self._h, C.byref(a)))
         return {"observed": int(a.observed), "total": int(a.total), "freq": [int(x) for x in a.freq],
                 "sum_sq": float(a.sum_sq), "sum_clnc": float(a.sum_clnc)}
-
-    def trim(self):
-        """Free the per-chunk working memory, keep the running table (mk_trim)."""
-        self._check(self._L.mk_trim(self._h))
 
     def filter_min(self, min_count: int):
         """Drop rows whose count is below ``min_count`` (the filter of a one-chunk sample counted in pieces)."""

@@ -183,6 +183,25 @@ def write_track_median_tsv(path, names: Sequence[str], rows, median) -> int:
     return len(names)
 
 
+def format_trim_tsv(names: Sequence[str], lengths, kept) -> bytes:
+    """``record\tlength\tkept``, then one line per record (kmers.trim_reads / Counter.trim): its name, the characters it
+    came with and those it keeps (0: dropped)."""
+    if len(names) != len(lengths) or len(names) != len(kept):
+        raise ValueError("format_trim_tsv: %d names for %d lengths and %d kept" % (len(names), len(lengths), len(kept)))
+    out = [b"record\tlength\tkept\n"]
+    for name, length, k in zip(names, lengths, kept):
+        out.append(name.encode() + b"\t%d\t%d\n" % (int(length), int(k)))
+    return b"".join(out)
+
+
+def write_trim_tsv(path, names: Sequence[str], lengths, kept) -> int:
+    """``format_trim_tsv`` written to ``path``; returns the number of records."""
+    text = format_trim_tsv(names, lengths, kept)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
 def write_against_tsvs(tables: Dict[str, "native.Counter"], against, op, out_dir, min_other: int = 1) -> Dict[str, int]:
     """For every sample of ``{sample name: Counter}``, ``sample op against`` (Counter.combine, keys compared as they
     stand) written as ``out_dir/<sample>_counts.tsv`` with Counter.write_tsv; a sample whose result is empty writes no
