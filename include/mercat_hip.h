@@ -465,6 +465,12 @@ int mk_filter_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flag
  * any address, the others aligned to their elements (MK_ERR_ARG otherwise); the median takes fewer than 2^32 windows. */
 #define MK_TRACK_FOLD  1u   /* = MK_SCREEN_FOLD */
 #define MK_TRACK_SAT32 2u   /* counts (and medians) are uint32_t, min(count, 2^32 - 1) */
+/* How the median is found is no part of its definition: a record of more than this many windows is not sorted, its
+ * median is found by radix selection over its counts where they lie (a contig costs four reads of its counts, not a
+ * sort of one segment); the size from which selection was never slower on the MI355X. */
+#ifndef MK_MEDIAN_SELECT_MIN   /* (an A/B build of the library may set another) */
+#define MK_MEDIAN_SELECT_MIN 16384u
+#endif
 typedef struct mk_track_t {
   mk_screen_t screen;          /* as mk_screen_* fills it for the same text and at_least */
   uint64_t windows_out;        /* elements written to counts */
@@ -522,6 +528,57 @@ int mk_trim_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes,
 int mk_trim_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_trim_rule_t* rule,
                    uint8_t* d_out, size_t out_cap, size_t* out_len, uint64_t* d_kept, mk_screen_row_t* d_rows, size_t cap,
                    size_t* nrows, mk_trim_t* st);
+
+/* ---- sequences in, the reads thinned to a target depth out: digital normalisation by the median mk_track_* computes,
+ *      decided and applied where the counts are (BBNorm's plan with khmer's normalize-by-median depth; with abundance
+ *      trimming the other standard step in front of an assembly or a second count) ----
+ * Text, records, windows, probing, fold, opening rules, pieces and errors are mk_screen_*'s, word for word, as for
+ * mk_trim_*: same parser, same rows, same mk_screen_t figures (st->screen; its s_total is the wall time of this whole
+ * call), MK_ERR_STATE with an open chunk or a refused one, MK_ERR_NON_ASCII, the fold rule (MK_NORM_FOLD =
+ * MK_SCREEN_FOLD), pieces cut by mk_record_cuts, the stream idle afterwards, the counting figures and the export
+ * untouched.  The table is only read: it has been counted from all the reads beforehand -- count first, then keep every
+ * read with probability target / depth, which is BBNorm's plan -- and the depth of a read is khmer's: the median of its
+ * k-mers' counts.  khmer's streaming normalize-by-median is NOT this: there the table grows from the reads that were
+ * kept, so a read's fate depends on the reads in front of it, the result on their order, and the procedure is serial by
+ * definition.  Here every record is decided on its own, from a table that does not change, so pieces and lanes may take
+ * them in any order.
+ * med[r] is mk_track_*'s median under MK_TRACK_SAT32: element windows / 2 of min(count, 2^32 - 1) over the record's
+ * windows sorted ascending, 0 for a record without windows; it is returned as median[r].  Record r is KEPT iff
+ * windows > 0 and med >= min_depth and (med <= target, or else u(r) * med < target << 32).  r is the record's index over
+ * the WHOLE CALL, not over a piece, and u(r) is the upper 32 bits of splitmix64:
+ *   z = seed + (r + 1) * 0x9E3779B97F4A7C15 (mod 2^64); z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31
+ * so a record of depth med > target is kept with probability target / med, the same records for the same seed.  Both
+ * products fit in 64 bits: 1 <= target <= 2^32 - 1 and min_depth <= 2^32 - 1.  A target of 0, a target or min_depth of
+ * 2^32 or more, a NULL rule or an unknown flag bit is MK_ERR_ARG and the message names it.
+ * Output: the kept records -- with MK_NORM_INVERT every record that is not kept, records without windows included -- in
+ * text order, byte for byte as mk_filter_* emits a record: from the first byte of its header line to the byte in front
+ * of the next record's header line, the headless record from byte 0.  The preamble (st->preamble) goes to neither;
+ * *out_len <= n.  keep[r] = 1 iff record r was emitted; rows[r] is its screen row for at_least = max(min_depth, 1).
+ * median, keep and rows may each be NULL (cap is ignored when all three are).  With out_cap or cap too small:
+ * MK_ERR_RANGE, the needed sizes in *out_len and *nrows, nothing written past either -- every piece is still walked to
+ * learn them.  The output does not depend on piece_bytes.  st may be NULL.
+ * mk_norm_text: host memory in and out, piece by piece.  mk_norm_device: text, out, median, keep and rows in DEVICE
+ * memory of the context's GPU, one piece; text and out at any address, d_median aligned to 4 and d_rows to 8
+ * (MK_ERR_ARG otherwise).  As with mk_track_*'s median, a piece of 2^32 windows or more is refused (MK_ERR_ARG). */
+#define MK_NORM_FOLD   1u   /* = MK_SCREEN_FOLD */
+#define MK_NORM_INVERT 2u   /* emit the records that are NOT kept (BBNorm's outt) */
+typedef struct mk_norm_rule_t { uint64_t target, min_depth, seed; } mk_norm_rule_t;
+typedef struct mk_norm_t {
+  mk_screen_t screen;      /* as mk_screen_* fills it for the same text and at_least = max(min_depth, 1) */
+  /* emitted; windows == 0; med < min_depth; med > target; of those, not kept */
+  uint64_t records_out, records_short, records_low, records_over, records_thinned;
+  uint64_t bytes_out, preamble;
+  /* seconds: HIP-event time of the placement (window offsets, record starts); of the track kernel; of the median; of
+   * the gather (the decision and its scan run between the two and are in none); host time in the copies back */
+  double s_place, s_track, s_median, s_gather, s_write;
+} mk_norm_t;
+int mk_norm_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, const mk_norm_rule_t* rule,
+                 uint8_t* out, size_t out_cap, size_t* out_len, uint32_t* median, uint8_t* keep, mk_screen_row_t* rows,
+                 size_t cap, size_t* nrows, mk_norm_t* st);
+int mk_norm_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_norm_rule_t* rule,
+                   uint8_t* d_out, size_t out_cap, size_t* out_len, uint32_t* d_median, uint8_t* d_keep,
+                   mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_norm_t* st);
 
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):

@@ -26,7 +26,10 @@ track_<type>/<sample>_track.txt -- per record of FILE the count of every one of 
 order -- and track_<type>/<sample>_median.tsv with the median of those counts (mk_track_text).  -trim FILE writes, for every
 sample of FILE's type, trim_<type>/<sample>_trimmed.fna (.faa): every record of FILE cut in front of its first k-mer the
 sample's table holds fewer than -trim_min times, as khmer's filter-abund trims (mk_trim_text), and
-trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -against FILE -op OP writes, for every sample of FILE's type,
+trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -norm FILE writes, for every sample of FILE's
+type, norm_<type>/<sample>_<kept|tossed>.fna (.faa): the records of FILE thinned to depth -norm_target by the median of their
+k-mers' counts in the sample's table -- digital normalisation, BBNorm's count-first plan with khmer's depth (mk_norm_text) --
+and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
 (mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
@@ -49,6 +52,7 @@ from .report import (merge_counters, merge_counters_T, write_against_tsvs, write
                      write_screen_tsv, write_track_median_tsv, write_track_txt)
 
 FILTER_KEEP = ("matched", "unmatched")
+NORM_KEEP = ("kept", "tossed")
 AGAINST_OPS = ("min", "max", "sum", "left", "only", "diff")  # native.OPS, for the parser (which loads no library)
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
@@ -106,6 +110,21 @@ def parseargs(argv=None):
     p.add_argument("-trim_min", type=int, default=None, metavar="N",
                    help="-trim: a k-mer is low below this count [2, the default cutoff of khmer's filter-abund]")
     p.add_argument("-trim_len", type=int, default=None, metavar="N", help="-trim: drop a record that keeps fewer characters [k]")
+    p.add_argument("-norm", type=str, required=False, metavar="FILE",
+                   help="a FASTA or FASTQ file (plain or .gz) of reads to thin against the tables on the GPU (digital "
+                        "normalisation; the table should have been counted from these reads): for every sample of FILE's type, "
+                        "norm_<type>/<sample>_<kept|tossed>.fna (.faa for protein) with the records of FILE whose depth -- the "
+                        "median of their k-mers' counts in the sample -- is at least -norm_min, all of them up to depth "
+                        "-norm_target and a share target / depth of the deeper ones, byte for byte and in order, or the "
+                        "records left out (-norm_keep), and norm_<type>/<sample>_norm.tsv with 'record, windows, median, "
+                        "kept' per record.  A FASTQ file is first converted as MerCat2's fq2fa converts it, so the output is "
+                        "FASTA; with -canonical the k-mers are folded")
+    p.add_argument("-norm_target", type=int, default=None, metavar="N",
+                   help="-norm: the depth to thin to [20, the default cutoff of khmer's normalize-by-median]")
+    p.add_argument("-norm_min", type=int, default=None, metavar="N", help="-norm: drop a record whose depth is below N [0]")
+    p.add_argument("-norm_seed", type=int, default=None, metavar="N", help="-norm: the seed of the draws [0]")
+    p.add_argument("-norm_keep", type=str, default=None, choices=NORM_KEEP,
+                   help="-norm: write the records that are kept, or those that are tossed [kept]")
     p.add_argument("-filter_min", type=int, default=None, metavar="N", help="-filter: a k-mer is a hit from this count on [1]")
     p.add_argument("-filter_hits", type=int, default=None, metavar="N", help="-filter: a record matches from this many hits on [1]")
     p.add_argument("-filter_frac", type=float, default=None, metavar="F",
@@ -204,6 +223,27 @@ def parseargs(argv=None):
         if args.trim_len is not None and not 1 <= args.trim_len < 1 << 64:
             p.error(f"-trim_len {args.trim_len}: must be 1 or more")
         args.trim_len = args.trim_len or 0  # (0: the k-mer length)
+    args.norm_kind = None
+    if not args.norm:
+        for flag in ("norm_target", "norm_min", "norm_seed", "norm_keep"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -norm FILE")
+    else:
+        if not os.path.isfile(args.norm):
+            p.error(f"file '{args.norm}' is not valid.\n")
+        args.norm_kind = classify(Path(args.norm).expanduser().absolute(), True)[0]
+        if not args.norm_kind:
+            p.error(f"-norm {args.norm}: the extension names neither a nucleotide, a protein nor a FASTQ file")
+        args.norm_target = 20 if args.norm_target is None else args.norm_target
+        if not 1 <= args.norm_target < 1 << 32:
+            p.error(f"-norm_target {args.norm_target}: must lie in 1..2^32 - 1")
+        args.norm_min = 0 if args.norm_min is None else args.norm_min
+        if not 0 <= args.norm_min < 1 << 32:
+            p.error(f"-norm_min {args.norm_min}: must lie in 0..2^32 - 1")
+        args.norm_seed = 0 if args.norm_seed is None else args.norm_seed
+        if not 0 <= args.norm_seed < 1 << 64:
+            p.error(f"-norm_seed {args.norm_seed}: must lie in 0..2^64 - 1")
+        args.norm_keep = args.norm_keep or "kept"
     args.filter_kind = None
     if not args.filter:
         for flag in ("filter_min", "filter_hits", "filter_frac", "filter_keep"):
@@ -635,6 +675,22 @@ def main(argv=None) -> int:
                         kept[base] = (res["kept"], res["trimmed"])
                     print(f"trim_{kind}/: {res['records']} records of {os.path.basename(args.trim)} trimmed against "
                           f"{len(tables)} sample(s), records written (of them cut): " +
+                          ", ".join(f"{base} {n} ({t})" for base, (n, t) in kept.items()))
+                if args.norm and args.norm_kind == kind:  # from the tables still on the GPU
+                    from .kmers import normalize_reads
+                    (out / f"norm_{kind}").mkdir(parents=True, exist_ok=True)
+                    ext = "faa" if kind == "protein" else "fna"
+                    kept = {}
+                    for base in sorted(tables):
+                        try:
+                            res = normalize_reads(tables[base], args.norm, out / f"norm_{kind}" / f"{base}_{args.norm_keep}.{ext}",
+                                                  args.norm_target, args.norm_min, args.norm_seed, args.norm_keep == "tossed",
+                                                  tsv_path=out / f"norm_{kind}" / f"{base}_norm.tsv")
+                        except native.MercatHipError as e:
+                            raise SystemExit(f"-norm {args.norm}: {e}")
+                        kept[base] = (res["kept"], res["thinned"])
+                    print(f"norm_{kind}/: {res['records']} records of {os.path.basename(args.norm)} thinned to depth "
+                          f"{args.norm_target} against {len(tables)} sample(s), {args.norm_keep} records written (thinned out): " +
                           ", ".join(f"{base} {n} ({t})" for base, (n, t) in kept.items()))
                 if args.against and args.against_kind == kind:  # from the tables still on the GPU
                     try:

@@ -10,7 +10,8 @@
 //                                          only link between the two views of the text.
 //   fl_decide_k                            a lane per record: keep[r] from its row and the rule, the kept length
 //   rocprim::exclusive_scan                dst[r], dst[nrows] = the piece's output length
-//   fl_gather_k (fl_edges_k)               the only kernel that moves text: output-driven, a lane owns 16 aligned output
+//   fl_emit: fl_gather_k (fl_edges_k)      (mk_recordplace.h, shared with mk_norm.hip: the same output under another
+//                                          decision) the only kernel that moves text: output-driven, a lane owns 16 aligned output
 //                                          bytes at a time, finds their record by search in dst[], reads the (unaligned)
 //                                          source and issues one 16-byte store.  No atomics, no byte stores but for the
 //                                          at most 15 + 15 bytes in front of and behind the aligned body.
@@ -36,80 +37,22 @@ __global__ void __launch_bounds__(256) fl_decide_k(const mk_screen_row_t* __rest
   block_add(&st->records_out, kept);
 }
 
-// Chunk g is the output bytes [head + 16 g, head + 16 g + 16), 16-byte aligned in memory; nbody of them.  A wave owns
-// FL_CHUNKS KiB of them: in round j lane l takes chunk 64 j + l of the wave's, so that a store instruction of the wave
-// writes 1 KiB in one piece.  The wave searches dst[] once, for the record of its first byte (the same loads in every
-// lane); from there a lane steps forward (fl_record_from) to the record of each of its chunks: about six reads of 150
-// bases further on each round, the same record all the way inside a contig.  A chunk is then filled record by record:
-// the 16 bytes at the source (fl_load16) masked to what the record still has and shifted to their place.  One trip
-// inside a record -- every chunk of a contig, nine in ten of 150-base reads -- and one more per record that starts in
-// the chunk: sixteen at the most, whatever the records are.  The next record is r + 1, or, if that one is dropped, the
-// next kept one, found by stepping on from it.
-#define FL_CHUNKS 4
-__global__ void __launch_bounds__(256) fl_gather_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ start,
-                                                   const u64* __restrict__ dst, size_t nrows, u64 head, u64 nbody,
-                                                   uint8_t* __restrict__ out) {
-  const u64 g0 = fl_first_lane((((u64)blockIdx.x * 256 + threadIdx.x) >> 6) * (64 * FL_CHUNKS));
-  if (g0 >= nbody) return;
-  size_t r = fl_record_of(dst, 0, nrows - 1, head + 16 * g0);
-  for (int j = 0; j < FL_CHUNKS; ++j) {
-    const u64 g = g0 + j * 64 + (threadIdx.x & 63);
-    if (g >= nbody) break;
-    const u64 o0 = head + 16 * g;
-    r = fl_record_from(dst, r, nrows, o0);
-    u64 end = dst[r + 1];
-    u64 src = start[r] + (o0 - dst[r]);
-    unsigned __int128 v = 0;
-    for (unsigned b = 0;;) {  // b: bytes of the chunk filled
-      const u64 left = end - (o0 + b);  // (1 or more: the record holds byte o0 + b)
-      const unsigned m = left < 16 - b ? (unsigned)left : 16 - b;
-      unsigned __int128 seg = fl_load16(text, n, src);
-      if (m < 16) seg &= (((unsigned __int128)1) << (8 * m)) - 1;
-      v |= seg << (8 * b);
-      b += m;
-      if (b == 16) break;
-      ++r;  // the record ended inside the chunk (bytes follow: a kept record does)
-      if (dst[r + 1] == dst[r]) r = fl_record_from(dst, r, nrows, o0 + b);
-      end = dst[r + 1];
-      src = start[r];
-    }
-    const u64 v0 = (u64)v, v1 = (u64)(v >> 64);
-    *reinterpret_cast<uint4*>(out + o0) = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
-  }
-}
-
-// The bytes in front of the first aligned 16 of the output (head of them) and behind the last (from tail_at on): a lane
-// a byte, at most 15 + 15.
-__global__ void __launch_bounds__(64) fl_edges_k(const uint8_t* __restrict__ text, const u64* __restrict__ start,
-                                                 const u64* __restrict__ dst, size_t nrows, u64 head, u64 tail_at, u64 out_len,
-                                                 uint8_t* __restrict__ out) {
-  u64 o;
-  if (threadIdx.x < 16) o = threadIdx.x < head ? threadIdx.x : out_len;
-  else if (threadIdx.x < 32) o = tail_at + (threadIdx.x - 16);
-  else return;
-  if (o >= out_len) return;
-  const size_t r = fl_record_of(dst, 0, nrows - 1, o);
-  out[o] = text[start[r] + (o - dst[r])];
-}
-
 // ------------------------------------------------------------------------------------------ host side
 struct FlCall {
   mk_filter_rule_t rule;
   bool invert;
-  uint8_t* out;       // where the output goes (text call: host memory, device call: device memory), out_cap bytes of room
-  size_t out_cap;
+  FlEmit emit;        // where the output goes
   mk_screen_row_t* rows;  // the caller's, or nullptr; cap of each
   uint8_t* keep;
   size_t cap;
   bool device;        // out / rows / keep are device memory
-  MkDevBuf d_rows, d_keep, meta, scan_tmp, stage;
-  MkTimed place, gather;
+  MkDevBuf d_rows, d_keep, meta, scan_tmp;
+  MkTimed place;
   mk_filter_t st{};
-  size_t bytes_out = 0;  // of all pieces so far, written or not
   FlCall(mk_ctx* c, const mk_filter_rule_t& r, bool inv, uint8_t* o, size_t oc, mk_screen_row_t* rw, uint8_t* kp, size_t cp, bool dev)
-      : rule(r), invert(inv), out(o), out_cap(oc), rows(rw), keep(kp), cap(cp), device(dev), place(c), gather(c) {}
+      : rule(r), invert(inv), emit(c, o, oc, dev), rows(rw), keep(kp), cap(cp), device(dev), place(c) {}
   ~FlCall() {
-    for (MkDevBuf* b : {&d_rows, &d_keep, &meta, &scan_tmp, &stage}) buf_free(*b);
+    for (MkDevBuf* b : {&d_rows, &d_keep, &meta, &scan_tmp}) buf_free(*b);
   }
 };
 
@@ -172,9 +115,6 @@ static int fl_piece(ScCall& s, FlCall& f, size_t n, size_t first) {
   }
   f.st.preamble += start0;
   f.st.records_out += h.records_out;
-  const size_t at = f.bytes_out;
-  f.bytes_out += (size_t)piece_out;
-
   // rows and keep of the piece, where the caller has room for them
   if (first + nrows <= f.cap) {
     const auto t1 = MkClock::now();
@@ -184,34 +124,7 @@ static int fl_piece(ScCall& s, FlCall& f, size_t n, size_t first) {
     MK_HIP(hipStreamSynchronize(c->stream));
     if (!f.device) f.st.s_write += mk_since(t1);
   }
-  if (!piece_out || f.bytes_out > f.out_cap) return MK_OK;  // (no room: the call goes on adding up and answers MK_ERR_RANGE)
-
-  // the gather: into the caller's device memory, or into a staging buffer that is copied to the host
-  uint8_t* d_out = f.out + at;
-  if (!f.device) {
-    if ((rc = mk_buf_reserve(c, f.stage, (size_t)piece_out)) != MK_OK) return rc;
-    d_out = (uint8_t*)f.stage.p;
-  }
-  const u64 head = std::min<u64>((16 - ((uintptr_t)d_out & 15)) & 15, piece_out);
-  const u64 nbody = (piece_out - head) / 16, tail_at = head + 16 * nbody;
-  if ((rc = f.gather.begin()) != MK_OK) return rc;
-  if (nbody)
-    hipLaunchKernelGGL(fl_gather_k, dim3((unsigned)div_up((size_t)nbody, 256 * FL_CHUNKS)), dim3(256), 0, c->stream, text, (u64)n,
-                       (const u64*)start, (const u64*)dst, nrows, head, nbody, d_out);
-  if (head || tail_at < piece_out)
-    hipLaunchKernelGGL(fl_edges_k, dim3(1), dim3(64), 0, c->stream, text, (const u64*)start, (const u64*)dst, nrows, head, tail_at,
-                       piece_out, d_out);
-  MK_HIP(hipGetLastError());
-  if ((rc = f.gather.end()) != MK_OK) return rc;
-  MK_HIP(hipStreamSynchronize(c->stream));
-  if ((rc = f.gather.add_to(f.st.s_gather)) != MK_OK) return rc;
-  if (!f.device) {
-    const auto t1 = MkClock::now();
-    MK_HIP(hipMemcpyAsync(f.out + at, d_out, (size_t)piece_out, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    f.st.s_write += mk_since(t1);
-  }
-  return MK_OK;
+  return fl_emit(s, f.emit, start, dst, n, nrows, piece_out, f.st.s_gather, f.st.s_write);
 }
 
 // How both calls check their own arguments, open as the screen calls open, and end; body(s, f): the pieces.
@@ -226,13 +139,13 @@ static int fl_run(mk_ctx* c, const char* what, unsigned flags, const mk_filter_r
   f->cap = cap;
   int rc = sc_run(c, what, flags & MK_FILTER_FOLD, rule->at_least, cap, nrows, &f->st.screen, [&](ScCall& s) { return body(s); });
   if (rc != MK_OK && rc != MK_ERR_RANGE) return rc;
-  if (out_len) *out_len = f->bytes_out;
+  if (out_len) *out_len = f->emit.bytes_out;
   if (rc != MK_OK) return rc;
-  if (f->bytes_out > f->out_cap) {
-    c->err = std::string(what) + ": the output holds " + std::to_string(f->bytes_out) + " bytes, out has room for " + std::to_string(f->out_cap);
+  if (f->emit.bytes_out > f->emit.out_cap) {
+    c->err = std::string(what) + ": the output holds " + std::to_string(f->emit.bytes_out) + " bytes, out has room for " + std::to_string(f->emit.out_cap);
     return MK_ERR_RANGE;
   }
-  f->st.bytes_out = f->bytes_out;
+  f->st.bytes_out = f->emit.bytes_out;
   if (st) *st = f->st;
   return MK_OK;
 }

@@ -1,8 +1,9 @@
 // mk_recordplace.h -- where the records of a RAW text start and how an output-driven gather finds its bytes: what
-// mk_filter_* (mk_filter.hip: whole records out) and mk_trim_* (mk_trim.hip: header lines and trimmed sequence out)
-// share.  fl_tiles_k / fl_scan_k / fl_starts_k give start[r], the first byte of the header line of every row, and
-// start[nrows] = n; fl_record_of / fl_record_from find the record of an output offset in dst[]; fl_load16 reads 16
-// bytes at any address of a text.  The kernels are static: every file that includes them launches its own copy.
+// mk_filter_* (mk_filter.hip: whole records out), mk_trim_* (mk_trim.hip: header lines and trimmed sequence out)
+// and mk_norm_* (mk_norm.hip: whole records out, under another decision) share.  fl_tiles_k / fl_scan_k / fl_starts_k
+// give start[r], the first byte of the header line of every row, and start[nrows] = n; fl_record_of / fl_record_from find the record of an output offset in dst[]; fl_load16 reads 16
+// bytes at any address of a text; fl_gather_k / fl_edges_k copy whole records to their places and fl_emit is the tail
+// of a piece that launches them.  The kernels are static: every file that includes them launches its own copy.
 #pragma once
 #include "mk_screenpiece.h"
 
@@ -130,4 +131,111 @@ __device__ __forceinline__ unsigned __int128 fl_load16(const uint8_t* __restrict
     }
   }
   return ((unsigned __int128)y1 << 64) | y0;
+}
+
+// Chunk g is the output bytes [head + 16 g, head + 16 g + 16), 16-byte aligned in memory; nbody of them.  A wave owns
+// FL_CHUNKS KiB of them: in round j lane l takes chunk 64 j + l of the wave's, so that a store instruction of the wave
+// writes 1 KiB in one piece.  The wave searches dst[] once, for the record of its first byte (the same loads in every
+// lane); from there a lane steps forward (fl_record_from) to the record of each of its chunks: about six reads of 150
+// bases further on each round, the same record all the way inside a contig.  A chunk is then filled record by record:
+// the 16 bytes at the source (fl_load16) masked to what the record still has and shifted to their place.  One trip
+// inside a record -- every chunk of a contig, nine in ten of 150-base reads -- and one more per record that starts in
+// the chunk: sixteen at the most, whatever the records are.  The next record is r + 1, or, if that one is dropped, the
+// next kept one, found by stepping on from it.
+#define FL_CHUNKS 4
+static __global__ void __launch_bounds__(256) fl_gather_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ start,
+                                                          const u64* __restrict__ dst, size_t nrows, u64 head, u64 nbody,
+                                                          uint8_t* __restrict__ out) {
+  const u64 g0 = fl_first_lane((((u64)blockIdx.x * 256 + threadIdx.x) >> 6) * (64 * FL_CHUNKS));
+  if (g0 >= nbody) return;
+  size_t r = fl_record_of(dst, 0, nrows - 1, head + 16 * g0);
+  for (int j = 0; j < FL_CHUNKS; ++j) {
+    const u64 g = g0 + j * 64 + (threadIdx.x & 63);
+    if (g >= nbody) break;
+    const u64 o0 = head + 16 * g;
+    r = fl_record_from(dst, r, nrows, o0);
+    u64 end = dst[r + 1];
+    u64 src = start[r] + (o0 - dst[r]);
+    unsigned __int128 v = 0;
+    for (unsigned b = 0;;) {  // b: bytes of the chunk filled
+      const u64 left = end - (o0 + b);  // (1 or more: the record holds byte o0 + b)
+      const unsigned m = left < 16 - b ? (unsigned)left : 16 - b;
+      unsigned __int128 seg = fl_load16(text, n, src);
+      if (m < 16) seg &= (((unsigned __int128)1) << (8 * m)) - 1;
+      v |= seg << (8 * b);
+      b += m;
+      if (b == 16) break;
+      ++r;  // the record ended inside the chunk (bytes follow: a kept record does)
+      if (dst[r + 1] == dst[r]) r = fl_record_from(dst, r, nrows, o0 + b);
+      end = dst[r + 1];
+      src = start[r];
+    }
+    const u64 v0 = (u64)v, v1 = (u64)(v >> 64);
+    *reinterpret_cast<uint4*>(out + o0) = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
+  }
+}
+
+// The bytes in front of the first aligned 16 of the output (head of them) and behind the last (from tail_at on): a lane
+// a byte, at most 15 + 15.
+static __global__ void __launch_bounds__(64) fl_edges_k(const uint8_t* __restrict__ text, const u64* __restrict__ start,
+                                                        const u64* __restrict__ dst, size_t nrows, u64 head, u64 tail_at, u64 out_len,
+                                                        uint8_t* __restrict__ out) {
+  u64 o;
+  if (threadIdx.x < 16) o = threadIdx.x < head ? threadIdx.x : out_len;
+  else if (threadIdx.x < 32) o = tail_at + (threadIdx.x - 16);
+  else return;
+  if (o >= out_len) return;
+  const size_t r = fl_record_of(dst, 0, nrows - 1, o);
+  out[o] = text[start[r] + (o - dst[r])];
+}
+
+// ------------------------------------------------------------------------------------------ host side
+// Where the records a call emits go, piece after piece.
+struct FlEmit {
+  uint8_t* out;       // text call: host memory, device call: device memory; out_cap bytes of room
+  size_t out_cap;
+  bool device;
+  MkDevBuf stage;
+  MkTimed gather;
+  size_t bytes_out = 0;  // of all pieces so far, written or not
+  FlEmit(mk_ctx* c, uint8_t* o, size_t oc, bool dev) : out(o), out_cap(oc), device(dev), gather(c) {}
+  ~FlEmit() { buf_free(stage); }
+};
+
+// The tail of a piece of n bytes whose decision has been taken and scanned: record r goes to [dst[r], dst[r + 1]) of the
+// piece's piece_out (= dst[nrows], which the caller has read back and checked against the text) output bytes, from
+// start[r] on.  The gather writes into the caller's device memory, or into a staging buffer that is copied to the host.
+// Without room the call goes on adding up and answers MK_ERR_RANGE at its end.  The stream is idle afterwards.
+static int fl_emit(ScCall& s, FlEmit& e, const u64* start, const u64* dst, size_t n, size_t nrows, u64 piece_out, double& s_gather,
+                   double& s_write) {
+  mk_ctx* c = s.c;
+  int rc;
+  const uint8_t* text = s.last.text;
+  const size_t at = e.bytes_out;
+  e.bytes_out += (size_t)piece_out;
+  if (!piece_out || e.bytes_out > e.out_cap) return MK_OK;
+  uint8_t* d_out = e.out + at;
+  if (!e.device) {
+    if ((rc = mk_buf_reserve(c, e.stage, (size_t)piece_out)) != MK_OK) return rc;
+    d_out = (uint8_t*)e.stage.p;
+  }
+  const u64 head = std::min<u64>((16 - ((uintptr_t)d_out & 15)) & 15, piece_out);
+  const u64 nbody = (piece_out - head) / 16, tail_at = head + 16 * nbody;
+  if ((rc = e.gather.begin()) != MK_OK) return rc;
+  if (nbody)
+    hipLaunchKernelGGL(fl_gather_k, dim3((unsigned)div_up((size_t)nbody, 256 * FL_CHUNKS)), dim3(256), 0, c->stream, text, (u64)n, start,
+                       dst, nrows, head, nbody, d_out);
+  if (head || tail_at < piece_out)
+    hipLaunchKernelGGL(fl_edges_k, dim3(1), dim3(64), 0, c->stream, text, start, dst, nrows, head, tail_at, piece_out, d_out);
+  MK_HIP(hipGetLastError());
+  if ((rc = e.gather.end()) != MK_OK) return rc;
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = e.gather.add_to(s_gather)) != MK_OK) return rc;
+  if (!e.device) {
+    const auto t1 = MkClock::now();
+    MK_HIP(hipMemcpyAsync(e.out + at, d_out, (size_t)piece_out, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    s_write += mk_since(t1);
+  }
+  return MK_OK;
 }

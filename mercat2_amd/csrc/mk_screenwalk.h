@@ -1,8 +1,8 @@
 // mk_screenwalk.h -- the lane walk over one tile of the parsed stream, with the sink a template parameter, and the
 // ladder that picks a walking kernel's instantiation.  sc_probe_k (mk_screen.hip) folds every window's count into the
-// record's row; tk_probe_k (mk_track.hip) writes it where its window stands; tr_first_k (mk_trim.hip) keeps the place of
-// the first low one.  tk_starts_k, which tells a positional sink where every record starts in the stream, is here too
-// (static: mk_track.hip and mk_trim.hip each launch their own copy).  The walk's device code reacts to
+// record's row; tk_probe_k (mk_trackwalk.h, for mk_track.hip and mk_norm.hip) writes it where its window stands;
+// tr_first_k (mk_trim.hip) keeps the place of the first low one.  tk_starts_k, which tells a positional sink where every
+// record starts in the stream, is here too (static: mk_track.hip, mk_trim.hip and mk_norm.hip each launch their own copy).  The walk's device code reacts to
 // restructuring: a change here is measured on both kernels (profiles/screen_walk.md, DESIGN 8p "one walk").
 //
 // A lane owns SC_RUN consecutive window starts: it walks k - 1 + SC_RUN symbols of the workgroup's span (staged in LDS

@@ -15,106 +15,14 @@
 //                                           in LDS, addressed by their place modulo the tile, and the range leaves in
 //                                           whole-wave stores.  (Every lane storing its own elements was 19 to 49 %
 //                                           slower: DESIGN 8p, profiles/track_probe.md.)
-//   rocprim::segmented_radix_sort_keys      (median only) the piece's counts, a segment a record, into scratch
-//   tk_pick_k                               (median only) a lane per record: element windows / 2 of its segment
+//   tk_median                               (median only) the short records' counts sorted a segment a record and picked,
+//                                           the long records' medians selected in place
 //   tk_offsets_k                            offsets of the piece, the windows of the pieces before it added
-#include "mk_screenwalk.h"
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
-struct TkStatus {  // device memory, read back once a piece
-  u64 max_count, written, saturated;
-};
-
-// wlen[r] = windows of row r, wlen[nrows] = 0 (so that the scan ends in the total); the largest count of the piece.
-__global__ void __launch_bounds__(256) tk_lens_k(const mk_screen_row_t* __restrict__ rows, size_t nrows, u64* __restrict__ wlen,
-                                                 TkStatus* __restrict__ st) {
-  u64 mx = 0;
-  mk_for_each(nrows + 1, [&](size_t r) {
-    if (r == nrows) { wlen[r] = 0; return; }
-    wlen[r] = rows[r].windows;
-    mx = rows[r].max > mx ? rows[r].max : mx;
-  });
-  for (int d = 32; d > 0; d >>= 1) {
-    const u64 o = __shfl_down(mx, d);
-    mx = o > mx ? o : mx;
-  }
-  if ((threadIdx.x & 63) == 0 && mx) atomicMax((unsigned long long*)&st->max_count, mx);
-}
+// Placement, the track kernel and the median are mk_trackwalk.h, shared with mk_norm.hip.
+#include "mk_trackwalk.h"
 
 __global__ void __launch_bounds__(256) tk_offsets_k(const u64* __restrict__ woff, size_t n, u64 add, u64* __restrict__ out) {
   mk_for_each(n, [&](size_t r) { out[r] = woff[r] + add; });
-}
-
-template <class E>
-__global__ void __launch_bounds__(256) tk_pick_k(const E* __restrict__ sorted, const u64* __restrict__ woff, size_t nrows,
-                                                 E* __restrict__ median) {
-  mk_for_each(nrows, [&](size_t r) {
-    const u64 w = woff[r + 1] - woff[r];
-    median[r] = w ? sorted[woff[r] + w / 2] : (E)0;
-  });
-}
-
-// The positional sink of the walk.  s_out: SC_SPAN elements of LDS, element i of the piece at i % SC_SPAN; total: the
-// piece's windows (woff[nrows]).  An element whose record or place lies outside what the placement counted is dropped,
-// never written -- the host compares st->written with the total.
-template <class E>
-struct TkSink {
-  E* s_out;
-  const u64* __restrict__ woff;
-  const u64* __restrict__ sstart;
-  u64 row_base, nrows, total;
-  u64 at_rid0 = ~0ull, ahead = 0;       // that record; symbols of the record the lane's run started in that lie in front of the run
-  u64 at_rid = ~0ull, at_base = 0;      // the record whose woff this lane holds
-  u64 first = ~0ull, last = 0, sat = 0, written = 0;
-  __device__ __forceinline__ void begin(u64 rid, u64 at) {
-    const u64 r = rid - row_base;
-    if (r < nrows && sstart[r] <= at) ahead = at - sstart[r];
-    at_rid0 = rid;
-  }
-  __device__ __forceinline__ void record_end(u64) {}
-  __device__ __forceinline__ void window(u64 rid, unsigned pos, u64 cnt) {
-    if (rid != at_rid) {
-      at_rid = rid;
-      const u64 r = rid - row_base;
-      at_base = r < nrows ? woff[r] : total;
-    }
-    const u64 i = at_base + (rid == at_rid0 ? ahead : 0) + pos;  // (a record may end inside the k - 1 symbols that fill the key)
-    if (i >= total) return;
-    E v = (E)cnt;
-    if (sizeof(E) == 4 && cnt > 0xFFFFFFFFull) { v = (E)0xFFFFFFFFu; ++sat; }
-    ++written;
-    s_out[i & (SC_SPAN - 1)] = v;
-    if (first == ~0ull) first = i;  // (the places of a lane ascend)
-    last = i + 1;
-  }
-};
-
-// Grid and arguments of sc_probe_k; dynamic LDS: the span (sc_span_bytes(k), none when LDS is false), then SC_SPAN
-// elements.
-template <int KEYS, bool FOLD, bool LDS, class E>
-__global__ void __launch_bounds__(256) tk_probe_k(const uint8_t* __restrict__ seq, u64 seq_len, const u64* __restrict__ tile_pre,
-                                                  u64 row_base, int k, int bits, LkTables t, const u64* __restrict__ woff,
-                                                  const u64* __restrict__ sstart, u64 nrows, u64 total, E* __restrict__ out, TkStatus* __restrict__ st) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-  __shared__ unsigned long long s_lo, s_hi;
-  const unsigned span_bytes = LDS ? sc_span_bytes(k) : 0u;
-  if (threadIdx.x == 0) { s_lo = ~0ull; s_hi = 0; }  // (the walk's barriers stand between this and the atomics)
-  TkSink<E> sink{reinterpret_cast<E*>(s_dyn + span_bytes), woff, sstart, row_base, nrows, total};
-  ScWalked n;
-  sc_walk<KEYS, FOLD, LDS>(s_dyn, seq, seq_len, tile_pre, k, bits, t, sink, n);
-  // The tile's range: its windows are at most SC_SPAN consecutive places, so no two share an LDS element.
-  if (sink.last) {
-    atomicMin(&s_lo, (unsigned long long)sink.first);
-    atomicMax(&s_hi, (unsigned long long)sink.last);
-  }
-  __syncthreads();
-  const u64 lo = s_lo, hi = s_hi;
-  if (hi > lo && hi - lo <= SC_SPAN)
-    for (u64 i = lo + threadIdx.x; i < hi; i += 256) out[i] = sink.s_out[i & (SC_SPAN - 1)];
-  else sink.written = 0;
-  block_add(&st->written, sink.written);
-  if (sizeof(E) == 4) block_add(&st->saturated, sink.sat);
 }
 
 // ------------------------------------------------------------------------------------------ host side
@@ -126,58 +34,17 @@ struct TkCall {
   void* median;
   mk_screen_row_t* rows;
   size_t cap;
-  MkDevBuf d_rows, meta, scan_tmp, stage, sorted, sort_tmp, small;
+  MkDevBuf d_rows, meta, scan_tmp, stage, small;
+  TkMedian med;
   MkTimed place, track, sort;
   mk_track_t st{};
   size_t windows_seen = 0;  // of all pieces so far, written or not
   TkCall(mk_ctx* c, bool s32, bool dev, void* cn, size_t cc, uint64_t* of, void* md, mk_screen_row_t* rw, size_t cp)
       : sat32(s32), device(dev), counts(cn), counts_cap(cc), offsets(of), median(md), rows(rw), cap(cp), place(c), track(c), sort(c) {}
   ~TkCall() {
-    for (MkDevBuf* b : {&d_rows, &meta, &scan_tmp, &stage, &sorted, &sort_tmp, &small}) buf_free(*b);
+    for (MkDevBuf* b : {&d_rows, &meta, &scan_tmp, &stage, &small}) buf_free(*b);
   }
 };
-
-template <class E>
-static int tk_launch_probe(ScCall& s, const u64* woff, const u64* sstart, size_t nrows, u64 total, E* d_out, TkStatus* d_st) {
-  mk_ctx* c = s.c;
-  const LkTables t = lk_tables(c);
-  const unsigned grid = (unsigned)div_up(s.last.seq_len, SC_SPAN);
-  const int rc = sc_dispatch_walk(s, [&](auto keys, auto fold, auto lds) -> int {
-    auto kern = tk_probe_k<decltype(keys)::value, decltype(fold)::value, decltype(lds)::value, E>;
-    const size_t shmem = (decltype(lds)::value ? sc_span_bytes(c->k) : 0) + (size_t)SC_SPAN * sizeof(E);
-    static size_t raised[64];  // per instantiation and device: the dynamic LDS the kernel has been allowed so far
-    if (shmem > 64 * 1024 && shmem > raised[c->device & 63]) {
-      MK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-      raised[c->device & 63] = shmem;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, c->stream, (const uint8_t*)c->seq.p, (u64)s.last.seq_len, s.last.tile_pre,
-                       s.last.row_base, c->k, c->bits, t, woff, sstart, (u64)nrows, total, d_out, d_st);
-    return MK_OK;
-  });
-  if (rc != MK_OK) return rc;
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
-
-// The sort of the piece's `total` elements at d_in into f.sorted, a segment a record, and the pick into d_med.
-template <class E>
-static int tk_median(mk_ctx* c, TkCall& f, const E* d_in, const u64* woff, size_t nrows, u64 total, u64 max_count, E* d_med) {
-  int rc;
-  if (total) {
-    if ((rc = mk_buf_reserve(c, f.sorted, (size_t)total * sizeof(E))) != MK_OK) return rc;
-    unsigned end_bit = 1;  // (the bits the largest count of the piece has: small counts sort in one or two passes)
-    while (end_bit < 8 * sizeof(E) && (max_count >> end_bit)) ++end_bit;
-    size_t tmp = 0;
-    MK_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp, d_in, (E*)f.sorted.p, (unsigned)total, (unsigned)nrows, woff, woff + 1, 0u,
-                                              end_bit, c->stream));
-    if ((rc = mk_buf_reserve(c, f.sort_tmp, tmp ? tmp : 16)) != MK_OK) return rc;
-    MK_HIP(rocprim::segmented_radix_sort_keys(f.sort_tmp.p, tmp, d_in, (E*)f.sorted.p, (unsigned)total, (unsigned)nrows, woff, woff + 1,
-                                              0u, end_bit, c->stream));
-  }
-  hipLaunchKernelGGL(tk_pick_k<E>, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, (const E*)f.sorted.p, woff, nrows, d_med);
-  MK_HIP(hipGetLastError());
-  return MK_OK;
-}
 
 // What follows sc_piece for a piece whose rows start at row `first` of the call: placement, the track kernel, the
 // median, and the copies to the caller's buffers where they have room.  The stream is idle afterwards.
@@ -206,6 +73,10 @@ static int tk_piece(ScCall& s, TkCall& f, size_t first) {
                        (u64)s.last.seq_len, s.last.tile_pre, s.last.row_base, nrows, sstart);
   MK_HIP(hipGetLastError());
   MK_HIP(rocprim::exclusive_scan(f.scan_tmp.p, tmp, (const u64*)wlen, woff, 0ull, nrows + 1, rocprim::plus<u64>(), c->stream));
+  if (f.median) {
+    hipLaunchKernelGGL(tk_longest_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, (const u64*)woff, nrows, d_st);
+    MK_HIP(hipGetLastError());
+  }
   if ((rc = f.place.end()) != MK_OK) return rc;
   TkStatus h{};
   u64 total = 0;
@@ -274,7 +145,7 @@ static int tk_piece(ScCall& s, TkCall& f, size_t first) {
     }
     if ((rc = f.sort.begin()) != MK_OK) return rc;
     const u64 mx = sizeof(E) == 4 && h.max_count > 0xFFFFFFFFull ? 0xFFFFFFFFull : h.max_count;
-    if ((rc = tk_median<E>(c, f, d_out, woff, nrows, total, mx, d_med)) != MK_OK) return rc;
+    if ((rc = tk_median<E>(c, f.med, d_out, woff, nrows, total, mx, h.longest, d_med)) != MK_OK) return rc;
     if ((rc = f.sort.end()) != MK_OK) return rc;
     MK_HIP(hipStreamSynchronize(c->stream));
     if ((rc = f.sort.add_to(f.st.s_median)) != MK_OK) return rc;

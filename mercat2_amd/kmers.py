@@ -222,3 +222,34 @@ def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[
     return {"records": int(kept.shape[0]), "kept": int(info["records_out"]), "trimmed": int(info["records_trimmed"]),
             "dropped": int(info["records_dropped"]), "bases_in": int(info["bases_in"]), "bases_out": int(info["bases_out"]),
             "bytes_out": len(out)}
+
+
+def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], target: int = 20,
+                    min_depth: int = 0, seed: int = 0, invert: bool = False, tsv_path: Union[str, Path, None] = None) -> Dict[str, int]:
+    """The records of a FASTA or FASTQ file thinned to depth ``target`` against a table still on the GPU that has been
+    counted from all of them (Counter.normalize: BBNorm's plan with khmer's median k-mer abundance as the depth), written to
+    ``out_path`` -- gzip (level 1) if that name ends in '.gz', plain bytes otherwise.  A record without k-mers or of depth
+    below ``min_depth`` is dropped, one of depth at most ``target`` is kept, a deeper one is kept with probability
+    target / depth by a draw that depends only on ``seed`` and the record's index; with ``invert`` the records that are
+    not kept are written instead.  The file is read as filter_reads reads it: '.gz' inflated on the host, a FASTQ file
+    first converted as MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is always FASTA, the records byte for byte
+    and in order, and the qualities are gone.  A canonical table folds the windows.  Returns {"records", "kept", "short",
+    "low", "over", "thinned", "bytes_out"} ("kept": the records written).  With ``tsv_path`` every record's name,
+    k-mers, depth and fate are written there too (report.write_norm_tsv)."""
+    text = read_fasta_bytes(file)
+    if str(file).lower().endswith(FASTQ_SUFFIXES):
+        text, _ = native.fq2fa(text)
+    info: Dict[str, int] = {}
+    out, keep, med, rows = table.normalize(text, target, min_depth, seed, invert, info=info)
+    if str(out_path).lower().endswith(".gz"):
+        with gzip.open(out_path, "wb", compresslevel=1) as fh:
+            fh.write(out)
+    else:
+        with open(out_path, "wb") as fh:
+            fh.write(out)
+    if tsv_path is not None:
+        from .report import write_norm_tsv
+        write_norm_tsv(tsv_path, record_names(text), rows[:, 0], med, keep)
+    return {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "short": int(info["records_short"]),
+            "low": int(info["records_low"]), "over": int(info["records_over"]), "thinned": int(info["records_thinned"]),
+            "bytes_out": len(out)}

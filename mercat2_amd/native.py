@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
-    "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device",
+    "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_norm_text", "mk_norm_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -45,6 +45,8 @@ SCREEN_FOLD = 1
 FILTER_FOLD, FILTER_INVERT = 1, 2
 TRACK_FOLD, TRACK_SAT32 = 1, 2
 TRIM_FOLD = 1
+NORM_FOLD, NORM_INVERT = 1, 2
+MEDIAN_SELECT_MIN = 16384  # MK_MEDIAN_SELECT_MIN: a record of more windows has its median selected, not sorted
 # mk_table_op: f(ca, cb) per key (include/mercat_hip.h)
 OP_MIN, OP_MAX, OP_SUM, OP_LEFT, OP_ONLY, OP_DIFF = range(6)
 OPS = {"min": OP_MIN, "max": OP_MAX, "sum": OP_SUM, "left": OP_LEFT, "only": OP_ONLY, "diff": OP_DIFF}
@@ -173,6 +175,24 @@ class Trim(C.Structure):
                 [(n, C.c_uint64) for n in ("records_out", "records_trimmed", "records_dropped", "bases_in", "bases_out",
                                            "bytes_out", "preamble")] +
                 [(n, C.c_double) for n in ("s_place", "s_first", "s_gather", "s_write")])
+
+    def as_dict(self):
+        d = self.screen.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+class NormRule(C.Structure):
+    """mk_norm_rule_t (include/mercat_hip.h)."""
+    _fields_ = [("target", C.c_uint64), ("min_depth", C.c_uint64), ("seed", C.c_uint64)]
+
+
+class Norm(C.Structure):
+    """mk_norm_t (include/mercat_hip.h)."""
+    _fields_ = ([("screen", Screen)] +
+                [(n, C.c_uint64) for n in ("records_out", "records_short", "records_low", "records_over", "records_thinned",
+                                           "bytes_out", "preamble")] +
+                [(n, C.c_double) for n in ("s_place", "s_track", "s_median", "s_gather", "s_write")])
 
     def as_dict(self):
         d = self.screen.as_dict()
@@ -350,6 +370,10 @@ def lib() -> C.CDLL:
                                    C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
         "mk_trim_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(TrimRule), C.c_void_p, C.c_size_t, szp,
                                      C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
+        "mk_norm_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Norm)]),
+        "mk_norm_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Norm)]),
         "mk_table_op": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(TableOp)]),
     }
     L.mk_version.restype = C.c_char_p
@@ -1161,6 +1185,54 @@ class Counter:
         rule = TrimRule(int(at_least), int(min_len))
         self._check(self._L.mk_trim_device(self._h, ptr, int(nbytes), TRIM_FOLD if self._fold_flag(fold) else 0, C.byref(rule),
                                            out_ptr or None, int(out_cap), C.byref(out_len), kept_ptr or None, rows_ptr or None,
+                                           int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
+    # -- normalising: FASTA text in, the records thinned to a target depth out; the table is only read
+    def _norm_flags(self, fold: Optional[bool], invert: bool) -> int:
+        return (NORM_FOLD if self._fold_flag(fold) else 0) | (NORM_INVERT if invert else 0)
+
+    def normalize(self, path_or_bytes, target: int, min_depth: int = 0, seed: int = 0, invert: bool = False,
+                  fold: Optional[bool] = None, piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_norm_text: (out, keep, median, rows) of the FASTA text (a path to a plain file, or the text itself as bytes).
+        The depth of a record is the median of its k-mers' counts in the table (khmer's; uint32, clipped at 2^32 - 1:
+        ``median``).  A record is kept iff it has k-mers, its depth is at least ``min_depth`` and either at most
+        ``target`` or a draw that depends only on ``seed`` and the record's index falls below target / depth (BBNorm's
+        plan: the table has been counted from all the reads beforehand).  ``out``: the kept records -- with ``invert``
+        all the others -- in text order and byte for byte, as Counter.filter emits them; ``keep``: one bool per record,
+        True where it was emitted; ``rows``: the (records, 5) uint64 array Counter.screen gives for the same text and
+        at_least = max(min_depth, 1).  ``fold`` None: fold iff the context is canonical.  ``info``, if given, receives the
+        mk_norm_t fields (those of mk_screen_t beside them)."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(held == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        keep = np.zeros(cap, dtype=np.uint8)
+        med = np.zeros(cap, dtype=np.uint32)
+        out = np.empty(max(size, 1), dtype=np.uint8)  # (the output is never longer than the text)
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Norm()
+        rule = NormRule(int(target), int(min_depth), int(seed))
+        self._check(self._L.mk_norm_text(self._h, addr, size, int(piece_bytes), self._norm_flags(fold, invert), C.byref(rule),
+                                         out.ctypes.data, size, C.byref(out_len), med.ctypes.data, keep.ctypes.data,
+                                         rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), keep[: n.value].astype(bool), med[: n.value], rows[: n.value]
+
+    def normalize_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, target: int, median_ptr: int = 0, keep_ptr: int = 0,
+                         rows_ptr: int = 0, cap: int = 0, min_depth: int = 0, seed: int = 0, invert: bool = False,
+                         fold: Optional[bool] = None) -> dict:
+        """mk_norm_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> the emitted records at
+        device address ``out_ptr`` (room for ``out_cap``; ``nbytes`` always suffice) and, where given, one uint32 median a
+        record at ``median_ptr`` (aligned to 4), one keep byte a record at ``keep_ptr`` and the rows (five uint64 a record,
+        aligned to 8) at ``rows_ptr`` with room for ``cap`` records each -- all on this context's GPU.  Returns the
+        mk_norm_t fields: "bytes_out" bytes were written, "records" rows."""
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Norm()
+        rule = NormRule(int(target), int(min_depth), int(seed))
+        self._check(self._L.mk_norm_device(self._h, ptr, int(nbytes), self._norm_flags(fold, invert), C.byref(rule), out_ptr or None,
+                                           int(out_cap), C.byref(out_len), median_ptr or None, keep_ptr or None, rows_ptr or None,
                                            int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
 

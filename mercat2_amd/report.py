@@ -202,6 +202,25 @@ def write_trim_tsv(path, names: Sequence[str], lengths, kept) -> int:
     return len(names)
 
 
+def format_norm_tsv(names: Sequence[str], windows, median, kept) -> bytes:
+    """``record\twindows\tmedian\tkept``, then one line per record (kmers.normalize_reads / Counter.normalize): its name,
+    its k-mers, the median of their counts and 1 where the record was written, 0 where not."""
+    if not len(names) == len(windows) == len(median) == len(kept):
+        raise ValueError("format_norm_tsv: %d names for %d windows, %d medians and %d kept" % (len(names), len(windows), len(median), len(kept)))
+    out = [b"record\twindows\tmedian\tkept\n"]
+    for name, w, m, k in zip(names, windows, median, kept):
+        out.append(name.encode() + b"\t%d\t%d\t%d\n" % (int(w), int(m), 1 if k else 0))
+    return b"".join(out)
+
+
+def write_norm_tsv(path, names: Sequence[str], windows, median, kept) -> int:
+    """``format_norm_tsv`` written to ``path``; returns the number of records."""
+    text = format_norm_tsv(names, windows, median, kept)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
 def write_against_tsvs(tables: Dict[str, "native.Counter"], against, op, out_dir, min_other: int = 1) -> Dict[str, int]:
     """For every sample of ``{sample name: Counter}``, ``sample op against`` (Counter.combine, keys compared as they
     stand) written as ``out_dir/<sample>_counts.tsv`` with Counter.write_tsv; a sample whose result is empty writes no
