@@ -580,6 +580,86 @@ int mk_norm_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags,
                    uint8_t* d_out, size_t out_cap, size_t* out_len, uint32_t* d_median, uint8_t* d_keep,
                    mk_screen_row_t* d_rows, size_t cap, size_t* nrows, mk_norm_t* st);
 
+/* ---- paired reads: mk_filter_*, mk_trim_* and mk_norm_* with the PAIR as the unit, so that no read is ever emitted
+ *      without its mate among the pairs (khmer's -p, BBDuk's and BBNorm's pair handling; what `megahit --12` and
+ *      `spades --12` read) ----
+ * The text is INTERLEAVED: records 2p and 2p + 1 of the whole call are the mates a and b of pair p.  Mates are defined
+ * by position only; names are not compared.  The headless record, if any, is record 0 and so a first mate.  Text,
+ * records, windows, probing, fold, opening rules, errors and argument checks are mk_screen_*'s, as for the unpaired call
+ * of the same op (rule->op; only that op's member of the rule is read and checked as that call checks it).  The
+ * per-record results are the unpaired call's, own to each mate: rows[r] for every op (at_least = filter.at_least,
+ * trim.at_least, max(norm.min_depth, 1)), kept[r] for TRIM -- always the mate's own figure --, median[r] for NORM.
+ *   FILTER  own[r] = matched by mk_filter_*'s rule.  The pair passes iff own[a] | own[b]; with MK_PAIRS_BOTH iff
+ *           own[a] & own[b].
+ *   TRIM    own[r] = kept[r] > 0.  The pair passes iff own[a] & own[b]; the mates keep their own trimmed lengths.
+ *   NORM    a mate is eligible iff windows > 0 and med >= min_depth; D = the smallest med over the eligible mates.  The
+ *           pair passes iff a mate is eligible and (D <= target or u(2p) * D < target << 32), u being mk_norm_*'s draw
+ *           at the first mate's index over the whole call.  With min_depth = 0 this is khmer's -p rule: the pair is kept
+ *           if either mate is at or under the cutoff.  own[r] = 1 iff the pair passes.
+ * out: both mates of every passing pair -- with MK_PAIRS_INVERT of every pair that does not pass -- in text order, each
+ * record byte for byte as the unpaired op emits it (mk_filter_*'s bytes for FILTER and NORM, mk_trim_*'s for TRIM): the
+ * output is itself interleaved and holds an even number of records.  singles (optional, singles_cap bytes of room): the
+ * records with own = 1 whose pair did not pass -- TRIM's orphans, the matched mates under MK_PAIRS_BOTH; NORM has none --
+ * emitted the same way, in text order; with singles NULL they are only counted and *singles_len tells their bytes.  A
+ * singles buffer together with MK_PAIRS_INVERT is MK_ERR_ARG.  keep[r]: 0 = not emitted, 1 = emitted in out, 2 = an
+ * orphan (emitted in singles where that is given).  kept (TRIM) and median (NORM) are ignored by the other ops.  keep,
+ * kept, median and rows may each be NULL (cap is ignored when all are).
+ * With out_cap, singles_cap or cap too small: MK_ERR_RANGE, the needed sizes in *out_len, *singles_len and *nrows,
+ * nothing written past any -- every piece is still walked.  An ODD number of records over the whole call is
+ * MK_ERR_RANGE: mk_last_error names the count, *out_len = *singles_len = 0 and the contents of the buffers are
+ * unspecified.  No record is success with empty outputs.  An unknown op, an unknown flag bit, MK_PAIRS_INVERT with TRIM,
+ * MK_PAIRS_BOTH with TRIM or NORM, or a NULL rule is MK_ERR_ARG.
+ * mk_pairs_text: host memory, piece by piece; no piece ends between mates (a piece that holds an odd number of records
+ * hands its last one to the next piece; one that holds a single record grows to the next cut), so out, singles and
+ * every array are independent of piece_bytes; st->screen counts every record once.  mk_pairs_device: everything in
+ * DEVICE memory of the context's GPU, one piece; text, out and singles at any address, d_kept and d_rows aligned to 8,
+ * d_median to 4 (MK_ERR_ARG otherwise).  The counting figures and the export are untouched. */
+#define MK_PAIRS_FILTER 0
+#define MK_PAIRS_TRIM   1
+#define MK_PAIRS_NORM   2
+#define MK_PAIRS_FOLD   1u  /* = MK_SCREEN_FOLD */
+#define MK_PAIRS_INVERT 2u  /* FILTER, NORM: emit the pairs that do not pass.  TRIM: MK_ERR_ARG */
+#define MK_PAIRS_BOTH   4u  /* FILTER only: a pair passes iff BOTH mates match (default: either).  Else MK_ERR_ARG */
+typedef struct mk_pairs_rule_t {
+  int32_t op, reserved;
+  mk_filter_rule_t filter;
+  mk_trim_rule_t trim;
+  mk_norm_rule_t norm;
+} mk_pairs_rule_t;
+typedef struct mk_pairs_t {
+  mk_screen_t screen;                  /* as mk_screen_* fills it for the same text and the op's at_least */
+  uint64_t pairs, pairs_out;           /* pairs of the text; pairs emitted in out */
+  uint64_t records_out, singles_out;   /* records in out (2 * pairs_out); orphans (emitted in singles where that is given) */
+  uint64_t bytes_out, bytes_singles, preamble;
+  /* per record, as mk_trim_t and mk_norm_t have them; records_dropped: kept[r] == 0; records_thinned: mates above the
+   * target whose pair did not pass */
+  uint64_t records_trimmed, records_dropped, bases_in, bases_out;
+  uint64_t records_short, records_low, records_over, records_thinned;
+  /* seconds: HIP-event time of the placement; of the op's walk (TRIM: first-low, NORM: track; FILTER: none); of the
+   * median; of the gathers; host time in the copies back */
+  double s_place, s_walk, s_median, s_gather, s_write;
+} mk_pairs_t;
+int mk_pairs_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, const mk_pairs_rule_t* rule,
+                  uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* singles, size_t singles_cap, size_t* singles_len,
+                  uint8_t* keep, uint64_t* kept, uint32_t* median, mk_screen_row_t* rows, size_t cap, size_t* nrows,
+                  mk_pairs_t* st);
+int mk_pairs_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_pairs_rule_t* rule,
+                    uint8_t* d_out, size_t out_cap, size_t* out_len, uint8_t* d_singles, size_t singles_cap, size_t* singles_len,
+                    uint8_t* d_keep, uint64_t* d_kept, uint32_t* d_median, mk_screen_row_t* d_rows, size_t cap, size_t* nrows,
+                    mk_pairs_t* st);
+/* Two files (R1 / R2) are served on the HOST, off the hot path: plain C++, no GPU.  mk_interleave writes record i of
+ * text1, then record i of text2, records delimited as mk_filter_* delimits them (a header line is one whose first
+ * non-blank byte is '>'); the preambles are dropped; a record whose last byte is neither LF nor CR -- only a text's last
+ * record can be -- gets one LF.  Texts with a headless record are MK_ERR_ARG; different record counts are MK_ERR_RANGE
+ * and mk_host_error gives both counts.  *out_len <= n1 + n2 + 2; with cap too small MK_ERR_RANGE and the needed size in
+ * *out_len (out = NULL, cap = 0 is the sizing call).  mk_split_pairs is the inverse for an interleaved text with an
+ * even record count (odd: MK_ERR_RANGE): record 2p goes to out1, record 2p + 1 to out2, byte for byte. */
+int mk_interleave(const uint8_t* text1, size_t n1, const uint8_t* text2, size_t n2, uint8_t* out, size_t cap, size_t* out_len,
+                  size_t* npairs);
+int mk_split_pairs(const uint8_t* text, size_t n, uint8_t* out1, size_t cap1, size_t* len1, uint8_t* out2, size_t cap2,
+                   size_t* len2, size_t* npairs);
+const char* mk_host_error(void); /* the message of this thread's last failed mk_interleave / mk_split_pairs */
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

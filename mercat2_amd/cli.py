@@ -29,7 +29,11 @@ sample's table holds fewer than -trim_min times, as khmer's filter-abund trims (
 trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -norm FILE writes, for every sample of FILE's
 type, norm_<type>/<sample>_<kept|tossed>.fna (.faa): the records of FILE thinned to depth -norm_target by the median of their
 k-mers' counts in the sample's table -- digital normalisation, BBNorm's count-first plan with khmer's depth (mk_norm_text) --
-and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  -against FILE -op OP writes, for every sample of FILE's type,
+and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  Paired reads: with -paired the FILE of
+-filter, -trim and -norm is interleaved, with -filter_mate / -trim_mate / -norm_mate FILE2 the pair comes in two files
+(interleaved on the host, written back as ..._1 and ..._2); either way a pair is written or left out as a whole
+(mk_pairs_text), -filter_pair says whether one matching mate is enough, -singles also writes <sample>_singles.fna (.faa)
+and the per-record TSVs gain the pair's index.  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
 (mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
@@ -53,6 +57,21 @@ from .report import (merge_counters, merge_counters_T, write_against_tsvs, write
 
 FILTER_KEEP = ("matched", "unmatched")
 NORM_KEEP = ("kept", "tossed")
+FILTER_PAIR = ("either", "both")
+
+
+def paired_outputs(args, name: str, folder, stem: str, base: str, ext: str) -> dict:
+    """The arguments of kmers.filter_reads / trim_reads / normalize_reads that say where the reads of call ``name`` go:
+    ``folder/<stem>.<ext>`` for single reads and interleaved pairs, ``<stem>_1`` and ``<stem>_2`` with a mate file,
+    ``<base>_singles`` with -singles."""
+    if not args.pairs_of[name]:
+        return {"out_path": folder / f"{stem}.{ext}"}
+    mate = getattr(args, f"{name}_mate")
+    kw = {"out_path": folder / (f"{stem}_1.{ext}" if mate else f"{stem}.{ext}"), "paired": True, "mate_file": mate,
+          "out_path2": folder / f"{stem}_2.{ext}" if mate else None}
+    if args.singles:
+        kw["singles_path"] = folder / f"{base}_singles.{ext}"
+    return kw
 AGAINST_OPS = ("min", "max", "sum", "left", "only", "diff")  # native.OPS, for the parser (which loads no library)
 
 FILE_EXT_FASTQ = [".fq", ".fastq", ".fq.gz", ".fastq.gz"]
@@ -125,6 +144,19 @@ def parseargs(argv=None):
     p.add_argument("-norm_seed", type=int, default=None, metavar="N", help="-norm: the seed of the draws [0]")
     p.add_argument("-norm_keep", type=str, default=None, choices=NORM_KEEP,
                    help="-norm: write the records that are kept, or those that are tossed [kept]")
+    p.add_argument("-paired", action="store_true",
+                   help="-filter, -trim, -norm: FILE holds paired reads, interleaved (records 2p and 2p + 1 are mates, by "
+                        "position): a pair is written or left out as a whole, so the output is interleaved again [False]")
+    p.add_argument("-filter_mate", type=str, default=None, metavar="FILE2",
+                   help="-filter: the second file of paired reads (FILE the first); implies paired, writes ..._1 and ..._2")
+    p.add_argument("-trim_mate", type=str, default=None, metavar="FILE2",
+                   help="-trim: the second file of paired reads (FILE the first); implies paired, writes ..._1 and ..._2")
+    p.add_argument("-norm_mate", type=str, default=None, metavar="FILE2",
+                   help="-norm: the second file of paired reads (FILE the first); implies paired, writes ..._1 and ..._2")
+    p.add_argument("-filter_pair", type=str, default=None, choices=FILTER_PAIR,
+                   help="-filter on paired reads: a pair matches if either mate does, or only if both do [either]")
+    p.add_argument("-singles", action="store_true",
+                   help="paired reads: also write <sample>_singles.fna, the reads that pass on their own in a pair that does not")
     p.add_argument("-filter_min", type=int, default=None, metavar="N", help="-filter: a k-mer is a hit from this count on [1]")
     p.add_argument("-filter_hits", type=int, default=None, metavar="N", help="-filter: a record matches from this many hits on [1]")
     p.add_argument("-filter_frac", type=float, default=None, metavar="F",
@@ -265,6 +297,32 @@ def parseargs(argv=None):
             p.error(f"-filter_hits {args.filter_hits}: must be 1 or more")
         if not 0.0 <= args.filter_frac <= 1.0:  # (the rule kmers.filter_reads applies: native.ppm_of_fraction)
             p.error(f"-filter_frac {args.filter_frac}: must lie in 0..1")
+    # paired reads: -paired (FILE is interleaved) or a mate file a call; both make the pair the unit
+    mates = {name: getattr(args, f"{name}_mate") for name in ("filter", "trim", "norm")}
+    for name, mate in mates.items():
+        if mate is None:
+            continue
+        if not getattr(args, name):
+            p.error(f"-{name}_mate needs -{name} FILE")
+        if args.paired:
+            p.error(f"-paired says FILE is interleaved: it does not go with -{name}_mate")
+        if not os.path.isfile(mate):
+            p.error(f"file '{mate}' is not valid.\n")
+        if classify(Path(mate).expanduser().absolute(), True)[0] != getattr(args, f"{name}_kind"):
+            p.error(f"-{name}_mate {mate}: not the type of -{name} {getattr(args, name)}")
+    if args.paired and not (args.filter or args.trim or args.norm):
+        p.error("-paired needs -filter, -trim or -norm FILE")
+    args.pairs_of = {name: bool(getattr(args, name)) and (args.paired or mates[name] is not None) for name in mates}
+    if args.filter_pair is not None and not args.pairs_of["filter"]:
+        p.error("-filter_pair needs -filter FILE with -paired or -filter_mate")
+    args.filter_pair = args.filter_pair or "either"
+    if args.singles:
+        if not any(args.pairs_of.values()):
+            p.error("-singles needs -paired or a mate file")
+        if args.pairs_of["filter"] and args.filter_keep != "matched":
+            p.error("-singles with -filter needs -filter_keep matched: the pairs that do not pass have no orphans")
+        if args.pairs_of["norm"] and args.norm_keep != "kept":
+            p.error("-singles with -norm needs -norm_keep kept")
     args.against_kind = None
     if args.op and not args.against:
         p.error("-op needs -against FILE")
@@ -639,8 +697,11 @@ def main(argv=None) -> int:
                     kept = {}
                     for base in sorted(tables):
                         try:
-                            res = filter_reads(tables[base], args.filter, out / f"filter_{kind}" / f"{base}_{args.filter_keep}.{ext}",
-                                               args.filter_min, args.filter_hits, args.filter_frac, args.filter_keep == "unmatched")
+                            where = paired_outputs(args, "filter", out / f"filter_{kind}", f"{base}_{args.filter_keep}", base, ext)
+                            if args.pairs_of["filter"]:
+                                where["both"] = args.filter_pair == "both"
+                            res = filter_reads(tables[base], args.filter, at_least=args.filter_min, min_hits=args.filter_hits,
+                                               min_frac=args.filter_frac, invert=args.filter_keep == "unmatched", **where)
                         except native.MercatHipError as e:
                             raise SystemExit(f"-filter {args.filter}: {e}")
                         kept[base] = res["kept"]
@@ -668,8 +729,9 @@ def main(argv=None) -> int:
                     kept = {}
                     for base in sorted(tables):
                         try:
-                            res = trim_reads(tables[base], args.trim, out / f"trim_{kind}" / f"{base}_trimmed.{ext}", args.trim_min,
-                                             args.trim_len, tsv_path=out / f"trim_{kind}" / f"{base}_trim.tsv")
+                            res = trim_reads(tables[base], args.trim, at_least=args.trim_min, min_len=args.trim_len,
+                                             tsv_path=out / f"trim_{kind}" / f"{base}_trim.tsv",
+                                             **paired_outputs(args, "trim", out / f"trim_{kind}", f"{base}_trimmed", base, ext))
                         except native.MercatHipError as e:
                             raise SystemExit(f"-trim {args.trim}: {e}")
                         kept[base] = (res["kept"], res["trimmed"])
@@ -677,15 +739,17 @@ def main(argv=None) -> int:
                           f"{len(tables)} sample(s), records written (of them cut): " +
                           ", ".join(f"{base} {n} ({t})" for base, (n, t) in kept.items()))
                 if args.norm and args.norm_kind == kind:  # from the tables still on the GPU
-                    from .kmers import normalize_reads
+                    from .kmers import normalize_read_pairs, normalize_reads
                     (out / f"norm_{kind}").mkdir(parents=True, exist_ok=True)
                     ext = "faa" if kind == "protein" else "fna"
                     kept = {}
                     for base in sorted(tables):
                         try:
-                            res = normalize_reads(tables[base], args.norm, out / f"norm_{kind}" / f"{base}_{args.norm_keep}.{ext}",
-                                                  args.norm_target, args.norm_min, args.norm_seed, args.norm_keep == "tossed",
-                                                  tsv_path=out / f"norm_{kind}" / f"{base}_norm.tsv")
+                            where = paired_outputs(args, "norm", out / f"norm_{kind}", f"{base}_{args.norm_keep}", base, ext)
+                            run = normalize_read_pairs if where.pop("paired", False) else normalize_reads
+                            res = run(tables[base], args.norm, target=args.norm_target, min_depth=args.norm_min,
+                                      seed=args.norm_seed, invert=args.norm_keep == "tossed",
+                                      tsv_path=out / f"norm_{kind}" / f"{base}_norm.tsv", **where)
                         except native.MercatHipError as e:
                             raise SystemExit(f"-norm {args.norm}: {e}")
                         kept[base] = (res["kept"], res["thinned"])

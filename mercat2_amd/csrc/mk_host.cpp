@@ -677,6 +677,111 @@ extern "C" int mk_fq2fa(const uint8_t* text, size_t n, uint8_t** out, size_t* ou
 
 extern "C" void mk_free(void* p) { free(p); }
 
+// ---- paired reads in two files: interleave and split on the host (no GPU; off the hot path) ------------------
+// Records are delimited as mk_filter_* delimits them: a record starts at the first byte of a line whose first non-blank
+// byte is '>'.  That is the streaming scanner's strict rule with a threshold of 0: every such line cuts.
+namespace {
+thread_local std::string g_host_err;
+struct StartsSink : MkCutSink {
+  std::vector<uint64_t> starts;
+  int feed(const uint8_t*, size_t) override { return 0; }
+  int cut(uint64_t abs) override { starts.push_back(abs); return 0; }
+};
+// starts[i] = first byte of record i, starts[records] = n.  headless: a kept character stands in front of the first.
+static void record_starts(const uint8_t* text, size_t n, std::vector<uint64_t>& starts, bool* headless) {
+  StartsSink sink;
+  MkCutScanner scan(0, &sink, true);
+  const size_t block = (size_t)4 << 20;
+  for (size_t off = 0; off < n; off += block) {
+    const size_t m = n - off < block ? n - off : block;
+    scan.block(text + off, m, memchr(text + off, '\r', m) != nullptr);
+  }
+  scan.finish();
+  starts.swap(sink.starts);
+  const size_t pre = starts.empty() ? n : (size_t)starts[0];
+  *headless = false;
+  for (size_t i = 0; i < pre; ++i) {
+    const uint8_t ch = text[i];
+    const bool blank = ch == ' ' || (ch >= 0x09 && ch <= 0x0D) || (ch >= 0x1C && ch <= 0x1F);
+    if (!blank && ch != '*') { *headless = true; break; }
+  }
+  starts.push_back(n);
+}
+// Appends record [a, b) of text at out + at where it fits in cap, with one LF if its last byte is no line end.
+static size_t put_record(const uint8_t* text, uint64_t a, uint64_t b, uint8_t* out, size_t cap, size_t at, bool add_lf) {
+  const size_t len = (size_t)(b - a);
+  const bool lf = add_lf && len && text[b - 1] != '\n' && text[b - 1] != '\r';
+  if (out && at + len + (lf ? 1 : 0) <= cap) {
+    memcpy(out + at, text + a, len);
+    if (lf) out[at + len] = '\n';
+  }
+  return at + len + (lf ? 1 : 0);
+}
+}  // namespace
+
+extern "C" const char* mk_host_error(void) { return g_host_err.c_str(); }
+
+extern "C" int mk_interleave(const uint8_t* text1, size_t n1, const uint8_t* text2, size_t n2, uint8_t* out, size_t cap,
+                             size_t* out_len, size_t* npairs) {
+  if (!out_len || (n1 && !text1) || (n2 && !text2) || (cap && !out)) { g_host_err = "mk_interleave: NULL buffer"; return MK_ERR_ARG; }
+  *out_len = 0;
+  if (npairs) *npairs = 0;
+  std::vector<uint64_t> s1, s2;
+  bool h1 = false, h2 = false;
+  record_starts(text1, n1, s1, &h1);
+  record_starts(text2, n2, s2, &h2);
+  if (h1 || h2) {
+    g_host_err = std::string("mk_interleave: text") + (h1 ? "1" : "2") + " holds sequence in front of its first header line";
+    return MK_ERR_ARG;
+  }
+  const size_t r1 = s1.size() - 1, r2 = s2.size() - 1;
+  if (r1 != r2) {
+    g_host_err = "mk_interleave: text1 holds " + std::to_string(r1) + " records, text2 holds " + std::to_string(r2);
+    return MK_ERR_RANGE;
+  }
+  size_t at = 0;
+  for (size_t i = 0; i < r1; ++i) {
+    at = put_record(text1, s1[i], s1[i + 1], out, cap, at, true);
+    at = put_record(text2, s2[i], s2[i + 1], out, cap, at, true);
+  }
+  *out_len = at;
+  if (npairs) *npairs = r1;
+  if (at > cap) {
+    g_host_err = "mk_interleave: the output holds " + std::to_string(at) + " bytes, out has room for " + std::to_string(cap);
+    return MK_ERR_RANGE;
+  }
+  return MK_OK;
+}
+
+extern "C" int mk_split_pairs(const uint8_t* text, size_t n, uint8_t* out1, size_t cap1, size_t* len1, uint8_t* out2, size_t cap2,
+                              size_t* len2, size_t* npairs) {
+  if (!len1 || !len2 || (n && !text) || (cap1 && !out1) || (cap2 && !out2)) { g_host_err = "mk_split_pairs: NULL buffer"; return MK_ERR_ARG; }
+  *len1 = *len2 = 0;
+  if (npairs) *npairs = 0;
+  std::vector<uint64_t> s;
+  bool headless = false;
+  record_starts(text, n, s, &headless);
+  if (headless) s.insert(s.begin(), 0);  // (the headless record runs from byte 0 and is a first mate)
+  const size_t r = s.size() - 1;
+  if (r & 1) {
+    g_host_err = "mk_split_pairs: the text holds " + std::to_string(r) + " records, an odd number";
+    return MK_ERR_RANGE;
+  }
+  size_t a1 = 0, a2 = 0;
+  for (size_t i = 0; i < r; i += 2) {
+    a1 = put_record(text, s[i], s[i + 1], out1, cap1, a1, false);
+    a2 = put_record(text, s[i + 1], s[i + 2], out2, cap2, a2, false);
+  }
+  *len1 = a1;
+  *len2 = a2;
+  if (npairs) *npairs = r / 2;
+  if (a1 > cap1 || a2 > cap2) {
+    g_host_err = "mk_split_pairs: the outputs hold " + std::to_string(a1) + " and " + std::to_string(a2) + " bytes, more than their room";
+    return MK_ERR_RANGE;
+  }
+  return MK_OK;
+}
+
 // ---- planning helpers of the multi-GPU path (no GPU needed) -------------------------------------------------
 // First key of owner 1..n-1 when [0, 2^key_bits) is cut into n equal ranges (the same cut as
 // mercat2_amd.dist.range_bounds): owner of a key = number of bounds <= key.

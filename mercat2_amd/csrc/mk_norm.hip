@@ -23,15 +23,6 @@ struct NmStatus {  // device memory, read back once a piece (fl: what the start 
   u64 disagree;  // records whose median contradicts their row
 };
 
-// The upper 32 bits of splitmix64 of record r (its index over the whole call) under seed.
-__device__ __forceinline__ u64 nm_u(u64 seed, u64 r) {
-  u64 z = seed + (r + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z >> 32;
-}
-
 // A lane per record (and one for the slot behind the last, whose length is 0 so that the scan ends in the total).
 // first: the index over the whole call of the piece's row 0.
 __global__ void __launch_bounds__(256) nm_decide_k(const mk_screen_row_t* __restrict__ rows, const u64* __restrict__ start,

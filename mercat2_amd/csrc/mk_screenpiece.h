@@ -115,18 +115,27 @@ static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least
 
 // A host text in pieces: cut where a record starts once a piece holds piece_bytes (mk_record_cuts; the loader's default
 // and limits), each copied into c->raw and handed to piece(d_piece, len).
-template <class Piece>
-static int sc_text_pieces(ScCall& s, const uint8_t* text, size_t n, size_t piece_bytes, Piece&& piece_fn) {
+// The ends of those pieces for a text of n > 0 bytes, ascending; the last is n.
+static int sc_piece_ends(ScCall& s, const uint8_t* text, size_t n, size_t piece_bytes, std::vector<uint64_t>& cuts) {
   mk_ctx* c = s.c;
-  if (!n) return MK_OK;
   size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
   piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
-  std::vector<uint64_t> cuts(n / piece + 2);
+  cuts.assign(n / piece + 2, 0);
   size_t ncuts = 0;
   int r = mk_record_cuts(text, n, piece, (size_t)4 << 20, cuts.data(), cuts.size(), &ncuts);
   if (r != MK_OK) { c->err = std::string(s.what) + ": the record scanner failed (internal error)"; return MK_ERR_STATE; }
   cuts.resize(ncuts);
   cuts.push_back(n);
+  return MK_OK;
+}
+
+template <class Piece>
+static int sc_text_pieces(ScCall& s, const uint8_t* text, size_t n, size_t piece_bytes, Piece&& piece_fn) {
+  mk_ctx* c = s.c;
+  if (!n) return MK_OK;
+  std::vector<uint64_t> cuts;
+  int r = sc_piece_ends(s, text, n, piece_bytes, cuts);
+  if (r != MK_OK) return r;
   size_t at = 0;
   for (const uint64_t end : cuts) {
     const size_t len = (size_t)end - at;

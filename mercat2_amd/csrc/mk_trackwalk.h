@@ -26,6 +26,16 @@ struct TkStatus {  // device memory, read back once a piece
   u64 longest;  // the windows of the piece's longest record where that is a long one, else 0 (tk_longest_k)
 };
 
+// The draw of the calls that thin by the median (mk_norm.hip, mk_pairs.hip): the upper 32 bits of splitmix64 of record
+// r (its index over the whole call) under seed.
+__device__ __forceinline__ u64 nm_u(u64 seed, u64 r) {
+  u64 z = seed + (r + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z >> 32;
+}
+
 // wlen[r] = windows of row r, wlen[nrows] = 0 (so that the scan ends in the total); the largest count of the piece.
 static __global__ void __launch_bounds__(256) tk_lens_k(const mk_screen_row_t* __restrict__ rows, size_t nrows, u64* __restrict__ wlen,
                                                         TkStatus* __restrict__ st) {

@@ -172,16 +172,77 @@ def track_reads(table: "native.Counter", file: Union[str, Path], at_least: int =
     return names, counts, offsets, rows, med
 
 
+def _reads_text(file: Union[str, Path]) -> bytes:
+    """A FASTA or FASTQ file as the read-writing calls read it: '.gz' inflated, FASTQ converted by mk_fq2fa."""
+    text = read_fasta_bytes(file)
+    if str(file).lower().endswith(FASTQ_SUFFIXES):
+        text, _ = native.fq2fa(text)
+    return text
+
+
+def _write_reads(path: Union[str, Path], data: bytes) -> None:
+    """gzip (level 1) if the name ends in '.gz', plain bytes otherwise."""
+    if str(path).lower().endswith(".gz"):
+        with gzip.open(path, "wb", compresslevel=1) as fh:
+            fh.write(data)
+    else:
+        with open(path, "wb") as fh:
+            fh.write(data)
+
+
+def _pairs_text(file, mate_file) -> bytes:
+    """The interleaved text of a paired run: the file itself, or -- with ``mate_file`` -- both files read as above and
+    interleaved on the host (native.interleave: off the GPU path, one more pass over both texts)."""
+    text = _reads_text(file)
+    return text if mate_file is None else native.interleave(text, _reads_text(mate_file))
+
+
+def _write_pairs(out: bytes, singles: Optional[bytes], out_path, out_path2, singles_path) -> None:
+    """Interleaved to ``out_path``, or split on the host into ``out_path`` and ``out_path2``; the orphans to
+    ``singles_path`` where that is given."""
+    if out_path2 is None:
+        _write_reads(out_path, out)
+    else:
+        first, second = native.split_pairs(out)
+        _write_reads(out_path, first)
+        _write_reads(out_path2, second)
+    if singles_path is not None:
+        _write_reads(singles_path, singles or b"")
+
+
+def _is_paired(paired, mate_file, out_path2, singles_path) -> bool:
+    if not (paired or mate_file is not None):
+        if out_path2 is not None or singles_path is not None:
+            raise ValueError("out_path2 and singles_path go with paired reads only (paired=True or mate_file)")
+        return False
+    return True
+
+
 def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 1, min_hits: int = 1,
-                 min_frac: float = 0.0, invert: bool = False) -> Dict[str, int]:
+                 min_frac: float = 0.0, invert: bool = False, paired: bool = False, mate_file: Union[str, Path, None] = None,
+                 out_path2: Union[str, Path, None] = None, singles_path: Union[str, Path, None] = None,
+                 both: bool = False) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file that match a table still on the GPU (Counter.filter), written to ``out_path``
     -- gzip (level 1) if that name ends in '.gz', plain bytes otherwise; with ``invert`` the records that do not match.  A
     record matches iff at least ``min_hits`` of its k-mers occur ``at_least`` times in the table and they are at least
     ``min_frac`` (0..1) of its k-mers.  The file is read as screen_reads reads it: '.gz' inflated on the host, a FASTQ
     file ('.fq' / '.fastq', plain or '.gz') first converted as MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is
     always FASTA, the text MerCat2 itself counts, and the qualities are gone.  The records are copied byte for byte, in
-    order.  A canonical table folds the windows.  Returns {"records", "kept", "bytes_in", "bytes_out"}."""
+    order.  A canonical table folds the windows.  Returns {"records", "kept", "bytes_in", "bytes_out"}.
+    Paired reads (``paired``: the file is interleaved; or ``mate_file``: the second file of the pair, read the same way
+    and interleaved with the first on the host): the pair is the unit (Counter.filter_pairs) -- it is written iff either
+    mate matches, with ``both`` iff both do.  The output is interleaved in ``out_path``, or split into ``out_path`` and
+    ``out_path2``; ``singles_path`` receives the matching mates of pairs that fail under ``both``.  The result gains
+    {"pairs", "pairs_kept", "singles"}."""
     min_ppm = native.ppm_of_fraction(min_frac)
+    if _is_paired(paired, mate_file, out_path2, singles_path):
+        text = _pairs_text(file, mate_file)
+        info: Dict[str, int] = {}
+        out, singles, keep, _, _ = table.filter_pairs(text, at_least, min_hits, min_ppm, both, invert,
+                                                      singles=singles_path is not None, info=info)
+        _write_pairs(out, singles, out_path, out_path2, singles_path)
+        return {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "bytes_in": len(text), "bytes_out": len(out),
+                "pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]), "singles": int(info["singles_out"])}
     text = read_fasta_bytes(file)
     if str(file).lower().endswith(FASTQ_SUFFIXES):
         text, _ = native.fq2fa(text)
@@ -196,7 +257,9 @@ def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Unio
 
 
 def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 2,
-               min_len: int = 0, tsv_path: Union[str, Path, None] = None) -> Dict[str, int]:
+               min_len: int = 0, tsv_path: Union[str, Path, None] = None, paired: bool = False,
+               mate_file: Union[str, Path, None] = None, out_path2: Union[str, Path, None] = None,
+               singles_path: Union[str, Path, None] = None) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file, each cut in front of its first k-mer that a table still on the GPU holds fewer
     than ``at_least`` times (Counter.trim: khmer's trim_on_abundance), written to ``out_path`` -- gzip (level 1) if that
     name ends in '.gz', plain bytes otherwise.  A record of which fewer than max(``min_len``, k) characters remain is
@@ -204,7 +267,24 @@ def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[
     MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is always FASTA: the header line as it stands, the kept
     characters on one line.  A canonical table folds the windows.  Returns {"records", "kept", "trimmed", "dropped",
     "bases_in", "bases_out", "bytes_out"}.  With ``tsv_path`` every record's name, length and kept characters are written
-    there too (report.write_trim_tsv)."""
+    there too (report.write_trim_tsv).
+    Paired reads (``paired``: the file is interleaved; or ``mate_file``: the second file of the pair, read the same way
+    and interleaved with the first on the host): the pair is the unit (Counter.trim_pairs) -- both mates are written,
+    each at its own trimmed length, iff both keep something.  The output is interleaved in ``out_path``, or split into
+    ``out_path`` and ``out_path2``; ``singles_path`` receives the mates that keep something while their mate does not.
+    "kept" then counts the records written in pairs and the result gains {"pairs", "pairs_kept", "singles"}."""
+    if _is_paired(paired, mate_file, out_path2, singles_path):
+        text = _pairs_text(file, mate_file)
+        info: Dict[str, int] = {}
+        out, singles, keep, kept, _ = table.trim_pairs(text, at_least, min_len, singles=singles_path is not None, info=info)
+        _write_pairs(out, singles, out_path, out_path2, singles_path)
+        if tsv_path is not None:
+            from .report import write_trim_tsv
+            write_trim_tsv(tsv_path, record_names(text), record_lengths(text), kept, keep)
+        return {"records": int(kept.shape[0]), "kept": int(info["records_out"]), "trimmed": int(info["records_trimmed"]),
+                "dropped": int(info["records_dropped"]), "bases_in": int(info["bases_in"]), "bases_out": int(info["bases_out"]),
+                "bytes_out": len(out), "pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]),
+                "singles": int(info["singles_out"])}
     text = read_fasta_bytes(file)
     if str(file).lower().endswith(FASTQ_SUFFIXES):
         text, _ = native.fq2fa(text)
@@ -235,7 +315,7 @@ def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: U
     first converted as MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is always FASTA, the records byte for byte
     and in order, and the qualities are gone.  A canonical table folds the windows.  Returns {"records", "kept", "short",
     "low", "over", "thinned", "bytes_out"} ("kept": the records written).  With ``tsv_path`` every record's name,
-    k-mers, depth and fate are written there too (report.write_norm_tsv)."""
+    k-mers, depth and fate are written there too (report.write_norm_tsv).  Paired reads: normalize_read_pairs."""
     text = read_fasta_bytes(file)
     if str(file).lower().endswith(FASTQ_SUFFIXES):
         text, _ = native.fq2fa(text)
@@ -253,3 +333,27 @@ def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: U
     return {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "short": int(info["records_short"]),
             "low": int(info["records_low"]), "over": int(info["records_over"]), "thinned": int(info["records_thinned"]),
             "bytes_out": len(out)}
+
+
+def normalize_read_pairs(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], target: int = 20,
+                         min_depth: int = 0, seed: int = 0, invert: bool = False, tsv_path: Union[str, Path, None] = None,
+                         mate_file: Union[str, Path, None] = None, out_path2: Union[str, Path, None] = None,
+                         singles_path: Union[str, Path, None] = None) -> Dict[str, int]:
+    """normalize_reads for paired reads (the paired form of filter_reads and trim_reads is an argument of theirs;
+    normalize_reads keeps the arguments it has).  ``file`` is interleaved, or -- with ``mate_file`` -- the first of two
+    files that are read as normalize_reads reads one and interleaved on the host.  The pair is the unit
+    (Counter.normalize_pairs): its depth is that of its shallowest mate that has k-mers and reaches ``min_depth``, its
+    draw that of its first mate.  The output is interleaved in ``out_path``, or split into ``out_path`` and
+    ``out_path2``; normalisation has no orphans, so a ``singles_path`` is written empty.  Returns normalize_reads' figures
+    ("kept": the records written) and {"pairs", "pairs_kept", "singles"}; the TSV gains the column ``pair``."""
+    text = _pairs_text(file, mate_file)
+    info: Dict[str, int] = {}
+    out, _, keep, med, rows = table.normalize_pairs(text, target, min_depth, seed, invert, info=info)
+    _write_pairs(out, b"", out_path, out_path2, singles_path)
+    if tsv_path is not None:
+        from .report import write_norm_tsv
+        write_norm_tsv(tsv_path, record_names(text), rows[:, 0], med, keep, paired=True)
+    return {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "short": int(info["records_short"]),
+            "low": int(info["records_low"]), "over": int(info["records_over"]), "thinned": int(info["records_thinned"]),
+            "bytes_out": len(out), "pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]),
+            "singles": int(info["singles_out"])}

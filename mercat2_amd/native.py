@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
     "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_norm_text", "mk_norm_device",
+    "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -46,6 +47,9 @@ FILTER_FOLD, FILTER_INVERT = 1, 2
 TRACK_FOLD, TRACK_SAT32 = 1, 2
 TRIM_FOLD = 1
 NORM_FOLD, NORM_INVERT = 1, 2
+PAIRS_FILTER, PAIRS_TRIM, PAIRS_NORM = 0, 1, 2  # mk_pairs_rule_t.op
+PAIRS_OPS = {"filter": PAIRS_FILTER, "trim": PAIRS_TRIM, "norm": PAIRS_NORM}
+PAIRS_FOLD, PAIRS_INVERT, PAIRS_BOTH = 1, 2, 4
 MEDIAN_SELECT_MIN = 16384  # MK_MEDIAN_SELECT_MIN: a record of more windows has its median selected, not sorted
 # mk_table_op: f(ca, cb) per key (include/mercat_hip.h)
 OP_MIN, OP_MAX, OP_SUM, OP_LEFT, OP_ONLY, OP_DIFF = range(6)
@@ -193,6 +197,25 @@ class Norm(C.Structure):
                 [(n, C.c_uint64) for n in ("records_out", "records_short", "records_low", "records_over", "records_thinned",
                                            "bytes_out", "preamble")] +
                 [(n, C.c_double) for n in ("s_place", "s_track", "s_median", "s_gather", "s_write")])
+
+    def as_dict(self):
+        d = self.screen.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+class PairsRule(C.Structure):
+    """mk_pairs_rule_t (include/mercat_hip.h)."""
+    _fields_ = [("op", C.c_int32), ("reserved", C.c_int32), ("filter", FilterRule), ("trim", TrimRule), ("norm", NormRule)]
+
+
+class Pairs(C.Structure):
+    """mk_pairs_t (include/mercat_hip.h)."""
+    _fields_ = ([("screen", Screen)] +
+                [(n, C.c_uint64) for n in ("pairs", "pairs_out", "records_out", "singles_out", "bytes_out", "bytes_singles",
+                                           "preamble", "records_trimmed", "records_dropped", "bases_in", "bases_out",
+                                           "records_short", "records_low", "records_over", "records_thinned")] +
+                [(n, C.c_double) for n in ("s_place", "s_walk", "s_median", "s_gather", "s_write")])
 
     def as_dict(self):
         d = self.screen.as_dict()
@@ -375,6 +398,15 @@ def lib() -> C.CDLL:
         "mk_norm_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Norm)]),
         "mk_table_op": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(TableOp)]),
+        "mk_pairs_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(PairsRule), C.c_void_p, C.c_size_t, szp,
+                                    C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp,
+                                    C.POINTER(Pairs)]),
+        "mk_pairs_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(PairsRule), C.c_void_p, C.c_size_t, szp,
+                                      C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp,
+                                      C.POINTER(Pairs)]),
+        "mk_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
+        "mk_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
+        "mk_host_error": (C.c_char_p, []),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -468,6 +500,38 @@ def fq2fa(raw) -> Tuple[bytes, dict]:
         if out.value:
             L.mk_free(out)
     return data, {n_: int(getattr(st, n_)) for n_, _ in st._fields_}
+
+
+def _host_error(rc: int, what: str) -> MercatHipError:
+    return MercatHipError(rc, (lib().mk_host_error() or b"").decode("utf-8", "replace") or what)
+
+
+def interleave(a, b) -> bytes:
+    """mk_interleave: record i of FASTA text ``a``, then record i of ``b`` (the R1 / R2 files of paired reads), records
+    delimited as Counter.filter delimits them, on the host.  The preambles are dropped and a last record without a line
+    end gets a newline.  MercatHipError (MK_ERR_RANGE) when the texts hold different numbers of records."""
+    L = lib()
+    a1, n1, k1 = _buf_ptr(a)
+    a2, n2, k2 = _buf_ptr(b)
+    out = np.empty(n1 + n2 + 2, dtype=np.uint8)
+    out_len, pairs = C.c_size_t(0), C.c_size_t(0)
+    rc = L.mk_interleave(a1, n1, a2, n2, out.ctypes.data, out.size, C.byref(out_len), C.byref(pairs))
+    if rc:
+        raise _host_error(rc, "mk_interleave")
+    return out[: out_len.value].tobytes()
+
+
+def split_pairs(text) -> Tuple[bytes, bytes]:
+    """mk_split_pairs: (records 0, 2, 4, ...; records 1, 3, 5, ...) of an interleaved FASTA text, byte for byte, on the
+    host.  MercatHipError (MK_ERR_RANGE) for an odd number of records."""
+    L = lib()
+    addr, n, keep = _buf_ptr(text)
+    o1, o2 = np.empty(max(n, 1), dtype=np.uint8), np.empty(max(n, 1), dtype=np.uint8)
+    l1, l2, pairs = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    rc = L.mk_split_pairs(addr, n, o1.ctypes.data, n, C.byref(l1), o2.ctypes.data, n, C.byref(l2), C.byref(pairs))
+    if rc:
+        raise _host_error(rc, "mk_split_pairs")
+    return o1[: l1.value].tobytes(), o2[: l2.value].tobytes()
 
 
 def textwrap_lines(text, width: int = 80) -> list:
@@ -1235,6 +1299,92 @@ class Counter:
                                            int(out_cap), C.byref(out_len), median_ptr or None, keep_ptr or None, rows_ptr or None,
                                            int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
+
+    # -- paired reads: interleaved FASTA text in, the pairs that pass out; the table is only read
+    def _pairs_rule(self, op, at_least, min_hits, min_ppm, min_len, target, min_depth, seed) -> PairsRule:
+        code = PAIRS_OPS.get(op, op) if isinstance(op, str) else op
+        if isinstance(code, str):
+            raise ValueError("op %r: one of %s" % (op, ", ".join(PAIRS_OPS)))
+        if at_least is None:
+            at_least = 2 if code == PAIRS_TRIM else 1
+        return PairsRule(int(code), 0, FilterRule(int(at_least), int(min_hits), int(min_ppm), 0), TrimRule(int(at_least), int(min_len)),
+                         NormRule(int(target), int(min_depth), int(seed)))
+
+    def _pairs_flags(self, fold: Optional[bool], invert: bool, both: bool) -> int:
+        return (PAIRS_FOLD if self._fold_flag(fold) else 0) | (PAIRS_INVERT if invert else 0) | (PAIRS_BOTH if both else 0)
+
+    def pairs(self, path_or_bytes, op, at_least: Optional[int] = None, min_hits: int = 1, min_ppm: int = 0, min_len: int = 0,
+              target: int = 1, min_depth: int = 0, seed: int = 0, both: bool = False, invert: bool = False, singles: bool = False,
+              fold: Optional[bool] = None, piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_pairs_text: (out, singles, keep, own, rows) of an INTERLEAVED FASTA text (a path to a plain file, or the text
+        itself as bytes): records 2p and 2p + 1 are the mates of pair p, by position.  ``op`` "filter", "trim" or "norm"
+        (or PAIRS_FILTER / PAIRS_TRIM / PAIRS_NORM) with that call's own arguments (``at_least`` None: 1, for trim 2).
+        Every mate gets the unpaired call's result -- ``rows``, and ``own``: None for filter, ``kept`` (uint64) for trim,
+        ``median`` (uint32) for norm -- and the pair passes as a whole: filter iff either mate matches (``both``: both),
+        trim iff both mates keep something, norm iff the shallowest eligible mate passes the depth rule with the draw of
+        the first mate's index.  ``out``: both mates of every passing pair (``invert``: of every other pair), each as the
+        unpaired call emits it.  ``singles``: with ``singles`` the bytes of the orphans -- records that pass on their own
+        in a pair that does not -- else None.  ``keep``: uint8 a record, 0 not emitted, 1 in out, 2 an orphan.  An odd
+        number of records is MercatHipError (MK_ERR_RANGE).  ``info``, if given, receives the mk_pairs_t fields."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        rule = self._pairs_rule(op, at_least, min_hits, min_ppm, min_len, target, min_depth, seed)
+        addr, size, held = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(held == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        keep = np.zeros(cap, dtype=np.uint8)
+        kept = np.zeros(cap, dtype=np.uint64) if rule.op == PAIRS_TRIM else None
+        med = np.zeros(cap, dtype=np.uint32) if rule.op == PAIRS_NORM else None
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        sg = np.empty(size + 1, dtype=np.uint8) if singles else None
+        n, out_len, sg_len, st = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), Pairs()
+        self._check(self._L.mk_pairs_text(self._h, addr, size, int(piece_bytes), self._pairs_flags(fold, invert, both), C.byref(rule),
+                                          out.ctypes.data, size + 1, C.byref(out_len), sg.ctypes.data if singles else None,
+                                          size + 1 if singles else 0, C.byref(sg_len), keep.ctypes.data,
+                                          kept.ctypes.data if kept is not None else None, med.ctypes.data if med is not None else None,
+                                          rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        own = kept[: n.value] if kept is not None else med[: n.value] if med is not None else None
+        return (out[: out_len.value].tobytes(), sg[: sg_len.value].tobytes() if singles else None, keep[: n.value], own,
+                rows[: n.value])
+
+    def pairs_device(self, ptr: int, nbytes: int, op, out_ptr: int, out_cap: int, singles_ptr: int = 0, singles_cap: int = 0,
+                     keep_ptr: int = 0, kept_ptr: int = 0, median_ptr: int = 0, rows_ptr: int = 0, cap: int = 0,
+                     at_least: Optional[int] = None, min_hits: int = 1, min_ppm: int = 0, min_len: int = 0, target: int = 1,
+                     min_depth: int = 0, seed: int = 0, both: bool = False, invert: bool = False, fold: Optional[bool] = None) -> dict:
+        """mk_pairs_device: ``nbytes`` of interleaved FASTA text (whole pairs) at device address ``ptr`` -> the passing
+        pairs at ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice), the orphans at ``singles_ptr`` where
+        given, and, where given, one keep byte, one uint64 of kept characters (trim), one uint32 median (norm) and the
+        rows (five uint64) a record with room for ``cap`` records each -- all on this context's GPU, kept and rows
+        aligned to 8, median to 4.  Returns the mk_pairs_t fields."""
+        rule = self._pairs_rule(op, at_least, min_hits, min_ppm, min_len, target, min_depth, seed)
+        n, out_len, sg_len, st = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), Pairs()
+        self._check(self._L.mk_pairs_device(self._h, ptr, int(nbytes), self._pairs_flags(fold, invert, both), C.byref(rule),
+                                            out_ptr or None, int(out_cap), C.byref(out_len), singles_ptr or None, int(singles_cap),
+                                            C.byref(sg_len), keep_ptr or None, kept_ptr or None, median_ptr or None, rows_ptr or None,
+                                            int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
+    def filter_pairs(self, path_or_bytes, at_least: int = 1, min_hits: int = 1, min_ppm: int = 0, both: bool = False,
+                     invert: bool = False, singles: bool = False, fold: Optional[bool] = None, piece_bytes: int = 0,
+                     info: Optional[dict] = None):
+        """Counter.filter with the pair as the unit: Counter.pairs(op="filter")."""
+        return self.pairs(path_or_bytes, PAIRS_FILTER, at_least=at_least, min_hits=min_hits, min_ppm=min_ppm, both=both, invert=invert,
+                          singles=singles, fold=fold, piece_bytes=piece_bytes, info=info)
+
+    def trim_pairs(self, path_or_bytes, at_least: int = 2, min_len: int = 0, singles: bool = False, fold: Optional[bool] = None,
+                   piece_bytes: int = 0, info: Optional[dict] = None):
+        """Counter.trim with the pair as the unit: Counter.pairs(op="trim")."""
+        return self.pairs(path_or_bytes, PAIRS_TRIM, at_least=at_least, min_len=min_len, singles=singles, fold=fold,
+                          piece_bytes=piece_bytes, info=info)
+
+    def normalize_pairs(self, path_or_bytes, target: int, min_depth: int = 0, seed: int = 0, invert: bool = False,
+                        fold: Optional[bool] = None, piece_bytes: int = 0, info: Optional[dict] = None):
+        """Counter.normalize with the pair as the unit: Counter.pairs(op="norm")."""
+        return self.pairs(path_or_bytes, PAIRS_NORM, target=target, min_depth=min_depth, seed=seed, invert=invert, fold=fold,
+                          piece_bytes=piece_bytes, info=info)
 
     # -- results
     def rows(self) -> int:

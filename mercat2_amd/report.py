@@ -183,39 +183,50 @@ def write_track_median_tsv(path, names: Sequence[str], rows, median) -> int:
     return len(names)
 
 
-def format_trim_tsv(names: Sequence[str], lengths, kept) -> bytes:
+_EMITTED = (b"0", b"pair", b"single")  # keep[r] of Counter.pairs
+
+
+def format_trim_tsv(names: Sequence[str], lengths, kept, keep=None) -> bytes:
     """``record\tlength\tkept``, then one line per record (kmers.trim_reads / Counter.trim): its name, the characters it
-    came with and those it keeps (0: dropped)."""
-    if len(names) != len(lengths) or len(names) != len(kept):
+    came with and those it keeps (0: dropped).  A paired run (``keep``: Counter.trim_pairs' 0 / 1 / 2 a record) adds the
+    columns ``emitted`` -- ``0``, ``pair`` or ``single``; ``kept`` stays the mate's own figure -- and ``pair``, the pair's
+    index."""
+    if len(names) != len(lengths) or len(names) != len(kept) or (keep is not None and len(keep) != len(names)):
         raise ValueError("format_trim_tsv: %d names for %d lengths and %d kept" % (len(names), len(lengths), len(kept)))
-    out = [b"record\tlength\tkept\n"]
-    for name, length, k in zip(names, lengths, kept):
-        out.append(name.encode() + b"\t%d\t%d\n" % (int(length), int(k)))
+    if keep is None:
+        out = [b"record\tlength\tkept\n"]
+        for name, length, k in zip(names, lengths, kept):
+            out.append(name.encode() + b"\t%d\t%d\n" % (int(length), int(k)))
+        return b"".join(out)
+    out = [b"record\tlength\tkept\temitted\tpair\n"]
+    for r, (name, length, k, e) in enumerate(zip(names, lengths, kept, keep)):
+        out.append(name.encode() + b"\t%d\t%d\t%s\t%d\n" % (int(length), int(k), _EMITTED[int(e)], r // 2))
     return b"".join(out)
 
 
-def write_trim_tsv(path, names: Sequence[str], lengths, kept) -> int:
+def write_trim_tsv(path, names: Sequence[str], lengths, kept, keep=None) -> int:
     """``format_trim_tsv`` written to ``path``; returns the number of records."""
-    text = format_trim_tsv(names, lengths, kept)
+    text = format_trim_tsv(names, lengths, kept, keep)
     with open(path, "wb") as fh:
         fh.write(text)
     return len(names)
 
 
-def format_norm_tsv(names: Sequence[str], windows, median, kept) -> bytes:
+def format_norm_tsv(names: Sequence[str], windows, median, kept, paired: bool = False) -> bytes:
     """``record\twindows\tmedian\tkept``, then one line per record (kmers.normalize_reads / Counter.normalize): its name,
-    its k-mers, the median of their counts and 1 where the record was written, 0 where not."""
+    its k-mers, the median of their counts and 1 where the record was written, 0 where not.  A ``paired`` run adds a last
+    column ``pair``, the pair's index."""
     if not len(names) == len(windows) == len(median) == len(kept):
         raise ValueError("format_norm_tsv: %d names for %d windows, %d medians and %d kept" % (len(names), len(windows), len(median), len(kept)))
-    out = [b"record\twindows\tmedian\tkept\n"]
-    for name, w, m, k in zip(names, windows, median, kept):
-        out.append(name.encode() + b"\t%d\t%d\t%d\n" % (int(w), int(m), 1 if k else 0))
+    out = [b"record\twindows\tmedian\tkept\tpair\n" if paired else b"record\twindows\tmedian\tkept\n"]
+    for r, (name, w, m, k) in enumerate(zip(names, windows, median, kept)):
+        out.append(name.encode() + b"\t%d\t%d\t%d" % (int(w), int(m), 1 if k else 0) + (b"\t%d\n" % (r // 2) if paired else b"\n"))
     return b"".join(out)
 
 
-def write_norm_tsv(path, names: Sequence[str], windows, median, kept) -> int:
+def write_norm_tsv(path, names: Sequence[str], windows, median, kept, paired: bool = False) -> int:
     """``format_norm_tsv`` written to ``path``; returns the number of records."""
-    text = format_norm_tsv(names, windows, median, kept)
+    text = format_norm_tsv(names, windows, median, kept, paired)
     with open(path, "wb") as fh:
         fh.write(text)
     return len(names)
