@@ -16,12 +16,17 @@
 // One 32-bit add resolves it inside a lane, one 64-bit add over the wave's ballots resolves it
 // across the 64 lanes (1 KiB), and the state between waves is a 2-state map scanned by
 // mk_fparse_scan -- no per-byte branching anywhere.
-//   pass 1 mk_fparse_summ  per wave (4 KiB): {has newline, exit state, bytes emitted for entry 0 / 1}
+//   pass 1 mk_fparse_summ  per wave (8 KiB): {has newline, exit state, bytes emitted for entry 0 / 1}; the `out` and
+//                          `sep` masks of every lane and sub-step under entry state 0 are stored (4 bytes per 16 of
+//                          text), with three facts per wave that tell how far they can be trusted (FP_F_*)
 //   pass 2 mk_fparse_scan  exclusive scan of those maps -> entry state + output offset per wave
-//   pass 3 mk_fparse_emit  recompute masks, compact the kept bytes into LDS at the alignment of
-//                          their destination, write them out with aligned 16-byte stores
+//   pass 3 mk_fparse_emit  load the stored masks -- or, for the sub-steps of a wave entered inside a header line that
+//                          come before its first newline, and for a wave with bytes >= 0x80, compute them again (the
+//                          "classic" path; MK_FP_CLASSIC=1 takes it everywhere) --, compact the kept bytes into LDS at
+//                          the alignment of their destination, write them out with aligned 16-byte stores
 #include "mk_common.h"
 #include "mk_device.h"
+#include "mk_env.h"
 
 typedef unsigned long long u64;
 
@@ -34,14 +39,24 @@ typedef unsigned long long u64;
 #define FP_WAVES (FP_THREADS / 64)
 
 struct FpEntry {  // per wave summary / scan result
-  unsigned a;     // summ: bit0 has_nl, bit1 exit0, bits 2.. separators (header lines that start in the wave)
+  unsigned a;     // summ: bit0 has_nl, bit1 exit0, bits 2..14 separators (header lines that start in the wave: at most
+                  // FP_WAVE_BYTES / 2), bits 15.. the wave's facts (FP_F_*)
   unsigned b;     // summ: cnt0 | cnt1 << 16
 };
+#define FP_A_SEPS(a) (((a) >> 2) & 0x1FFFu)
+#define FP_A_FACTS 15
+// What the emit pass must know about a wave before it trusts the masks the summary pass stored (they hold for entry
+// state 0):
+#define FP_F_CONV 0xFu         // leading sub-steps (1..FP_SUB) entered with the two entry states' chains still apart: a
+                               // wave that starts inside a header line computes those itself
+#define FP_F_LOW_HEAD (1u << 4)  // a blank outside header lines, under entry state 0, in one of those sub-steps ...
+#define FP_F_LOW_TAIL (1u << 5)  // ... and in one behind them, where the entry state no longer matters
+#define FP_F_HI (1u << 6)        // some byte of the wave is >= 0x80
+static_assert(FP_SUB <= 15 && FP_WAVE_BYTES / 2 <= 0x1FFF, "FpEntry.a: bit fields");
 
-// Class masks of 16 bytes. Bytes outside [begin, n) behave like newlines (they emit nothing): `raw` is
-// the 16-byte-aligned address at or below the chunk's first byte, `begin` the chunk's offset in it.
-__device__ __forceinline__ uint4 classify16(const uint8_t* __restrict__ raw, size_t pos, size_t begin, size_t n, unsigned& nl,
-                                            unsigned& gt, unsigned& st, unsigned& low, unsigned& hi) {
+// The 16 bytes of a lane and their class masks. Bytes outside [begin, n) behave like newlines (they emit nothing): `raw`
+// is the 16-byte-aligned address at or below the chunk's first byte, `begin` the chunk's offset in it.
+__device__ __forceinline__ uint4 load16(const uint8_t* __restrict__ raw, size_t pos, size_t begin, size_t n) {
   uint4 v;
   if (pos + 16 <= n && pos >= begin) {
     v = *reinterpret_cast<const uint4*>(raw + pos);
@@ -55,6 +70,10 @@ __device__ __forceinline__ uint4 classify16(const uint8_t* __restrict__ raw, siz
     }
     v = make_uint4(w0, w1, w2, w3);
   }
+  return v;
+}
+
+__device__ __forceinline__ void classify16(const uint4 v, unsigned& nl, unsigned& gt, unsigned& st, unsigned& low, unsigned& hi) {
   // Four bytes per 32-bit operation.  FP_NZ7(t): bit 7 of every byte of t that is not zero (the other bits are
   // garbage); so ~FP_NZ7(x ^ pattern) & 0x80808080 flags the bytes equal to the pattern.  A v_dot4_u32_u8 with the
   // weights 1,2,4,8 (16,..,128 for the odd words) then lines the four flags of a word up as a nibble: two words
@@ -79,7 +98,6 @@ __device__ __forceinline__ uint4 classify16(const uint8_t* __restrict__ raw, siz
   st = (a_st[0] >> 7) | ((a_st[1] >> 7) << 8);
   low = (a_lo[0] >> 7) | ((a_lo[1] >> 7) << 8);
   hi = (a_hi[0] >> 7) | ((a_hi[1] >> 7) << 8);  // bytes >= 0x80 (only the emit pass uses it: there it is known which bytes are kept)
-  return v;
 }
 
 // Header mask of one lane given its entry state: carries of (start|~NL) + start + hin.
@@ -127,9 +145,9 @@ __device__ __forceinline__ unsigned wave_step(unsigned nl, unsigned gt, unsigned
 // that corresponds to its input bytes (two memset launches of 39 MB per 100 MiB chunk less); the last wave takes
 // the padding words as well.
 __global__ __launch_bounds__(FP_THREADS) void mk_fparse_summ(const uint8_t* __restrict__ raw, size_t begin, size_t n, size_t nwaves,
-                                                             FpEntry* __restrict__ entries, MkChunkInfo* __restrict__ info,
-                                                             u64* __restrict__ zero_codes, u64* __restrict__ zero_bad,
-                                                             size_t code_words, size_t bad_words) {
+                                                             FpEntry* __restrict__ entries, unsigned* __restrict__ masks,
+                                                             MkChunkInfo* __restrict__ info, u64* __restrict__ zero_codes,
+                                                             u64* __restrict__ zero_bad, size_t code_words, size_t bad_words) {
   const size_t wave = (size_t)blockIdx.x * FP_WAVES + (threadIdx.x >> 6);
   if (wave >= nwaves) return;
   const int lane = threadIdx.x & 63;
@@ -141,28 +159,37 @@ __global__ __launch_bounds__(FP_THREADS) void mk_fparse_summ(const uint8_t* __re
     for (size_t w = wave * BW + (size_t)lane; w < b_end && w < bad_words; w += 64) zero_bad[w] = 0ull;
   }
   unsigned prev_nl = (base <= begin) ? 1u : ((raw[base - 1] == 10 || raw[base - 1] == 13) ? 1u : 0u);
-  unsigned s0 = 0, s1 = 1, c0 = 0, c1 = 0, seps = 0, any_nl = 0, flag_low = 0;
+  unsigned s0 = 0, s1 = 1, c0 = 0, c1 = 0, seps = 0, any_nl = 0;
+  unsigned conv = 0, low_head = 0, low_tail = 0, hi_or = 0;
+  unsigned* __restrict__ wmasks = masks + wave * (FP_SUB * 64) + lane;  // a sub-step of a wave is 64 words in a row
 #pragma unroll 1
   for (int sub = 0; sub < FP_SUB; ++sub) {
     const size_t pos = base + (size_t)sub * 1024 + (size_t)lane * 16;
     unsigned nl, gt, st, low, hi;
-    (void)classify16(raw, pos, begin, n, nl, gt, st, low, hi);
+    const uint4 v = load16(raw, pos, begin, n);
+    classify16(v, nl, gt, st, low, hi);
+    hi_or |= v.x | v.y | v.z | v.w;
     unsigned out, sep, bl, last_nl;
     const unsigned e0 = wave_step(nl, gt, st, low, prev_nl, s0, out, sep, bl, last_nl);
+    wmasks[sub * 64] = out | (sep << 16);  // what the emit pass computes again unless the wave's entry state is 1
     c0 += __popc(out);
     seps += __popc(sep);  // '>' at a line start: the same whatever the entry state
-    // (a blank inside a sequence line is looked for by the EMIT pass, which knows the wave's true entry state: under
-    // the wrong one of the two assumed here every blank of a header line that the wave starts inside looked like one,
-    // and read files whose header lines hold blanks -- most do -- fell back to the general parser, chunk after chunk)
-    (void)bl;
+    // (a blank inside a sequence line is judged by the EMIT pass, which knows the wave's true entry state: under the
+    // wrong one of the two assumed here every blank of a header line that the wave starts inside looks like one, and
+    // read files whose header lines hold blanks -- most do -- fell back to the general parser, chunk after chunk.  So
+    // the blanks seen under entry 0 are handed on in two parts: those of the sub-steps in which the entry state still
+    // matters, which only a wave entered in state 0 believes, and those behind them, which are real either way.)
     if (s1 != s0) {
       unsigned out1, sep1, bl1, ln1;
       const unsigned e1 = wave_step(nl, gt, st, low, prev_nl, s1, out1, sep1, bl1, ln1);
       c1 += __popc(out1);
       s1 = e1;
+      ++conv;
+      low_head |= bl;
     } else {
       c1 += __popc(out);
       s1 = e0;
+      low_tail |= bl;
     }
     s0 = e0;
     any_nl |= (__ballot(nl != 0) != 0) ? 1u : 0u;
@@ -171,9 +198,10 @@ __global__ __launch_bounds__(FP_THREADS) void mk_fparse_summ(const uint8_t* __re
   c0 = mk_wave_sum(c0);  // (DPP: mk_device.h)
   c1 = mk_wave_sum(c1);
   seps = mk_wave_sum(seps);
-  (void)flag_low;
+  const unsigned facts = conv | (__ballot(low_head != 0) ? FP_F_LOW_HEAD : 0u) | (__ballot(low_tail != 0) ? FP_F_LOW_TAIL : 0u) |
+                         (__ballot((hi_or & 0x80808080u) != 0) ? FP_F_HI : 0u);
   if (lane == 0) {
-    entries[wave].a = any_nl | (s0 << 1) | (seps << 2);
+    entries[wave].a = any_nl | (s0 << 1) | (seps << 2) | (facts << FP_A_FACTS);
     entries[wave].b = c0 | (c1 << 16);
   }
 }
@@ -181,7 +209,7 @@ __global__ __launch_bounds__(FP_THREADS) void mk_fparse_summ(const uint8_t* __re
 struct FpScan {
   u64 off;
   unsigned st;
-  unsigned pad;
+  unsigned facts;  // FP_F_* of the wave, passed on from its FpEntry
 };
 
 // One workgroup: thread t owns waves [t*per, (t+1)*per). A wave without a newline passes its
@@ -202,7 +230,7 @@ __global__ __launch_bounds__(1024) void mk_fparse_scan(const FpEntry* __restrict
       if (w0 + i >= hi) break;
       const unsigned wnl = en[i].a & 1u, wx0 = (en[i].a >> 1) & 1u;
       const unsigned k0 = en[i].b & 0xFFFFu, k1 = en[i].b >> 16;
-      nsep += en[i].a >> 2;
+      nsep += FP_A_SEPS(en[i].a);
       c0 += e0 ? k1 : k0;
       c1 += e1 ? k1 : k0;
       e0 = wnl ? wx0 : (e0 | wx0);
@@ -279,6 +307,7 @@ __global__ __launch_bounds__(1024) void mk_fparse_scan(const FpEntry* __restrict
       if (w0 + i >= hi) break;
       scan[w0 + i].off = off;
       scan[w0 + i].st = q;
+      scan[w0 + i].facts = en[i].a >> FP_A_FACTS;
       const unsigned wnl = en[i].a & 1u, wx0 = (en[i].a >> 1) & 1u;
       off += q ? (en[i].b >> 16) : (en[i].b & 0xFFFFu);
       q = wnl ? wx0 : (q | wx0);
@@ -287,9 +316,10 @@ __global__ __launch_bounds__(1024) void mk_fparse_scan(const FpEntry* __restrict
 }
 
 __global__ __launch_bounds__(FP_THREADS) void mk_fparse_emit(const uint8_t* __restrict__ raw, size_t begin, size_t n, size_t nwaves,
-                                                             FpScan* __restrict__ scan, uint8_t* __restrict__ seq,
-                                                             MkChunkInfo* __restrict__ info, u64* __restrict__ codes,
-                                                             u64* __restrict__ bad, int write_seq) {
+                                                             const FpScan* __restrict__ scan, const unsigned* __restrict__ masks,
+                                                             uint8_t* __restrict__ seq, MkChunkInfo* __restrict__ info,
+                                                             u64* __restrict__ codes, u64* __restrict__ bad, int write_seq,
+                                                             int classic) {
   // 64 bytes of slack on both sides: the fused pack reads whole 64-symbol words around the ends
   // (+ 256: one dump word per lane for the bytes a lane drops, see the compaction below)
   __shared__ __attribute__((aligned(16))) uint8_t stage[FP_WAVES][64 + FP_WAVE_BYTES + 32 + 64 + 256];
@@ -301,25 +331,49 @@ __global__ __launch_bounds__(FP_THREADS) void mk_fparse_emit(const uint8_t* __re
   const FpScan sc = scan[wave];
   const unsigned shift = (unsigned)(sc.off & 15);
   uint8_t* __restrict__ lds = stage[wv] + 64;
-  unsigned prev_nl = (base <= begin) ? 1u : ((raw[base - 1] == 10 || raw[base - 1] == 13) ? 1u : 0u);
+  // The summary pass stored `out` and `sep` of every lane and sub-step as they are when the wave is entered outside a
+  // header line.  They are this wave's own from its sub-step `nclassic` on (wave-uniform, hence the readfirstlane: the
+  // branch below is a scalar one): from the first for entry state 0, from where the two chains met for entry state 1,
+  // and nowhere for a wave with bytes >= 0x80, which are counted where the masks are computed.
+  const bool all_classic = classic || (sc.facts & FP_F_HI);
+  const int nclassic = __builtin_amdgcn_readfirstlane(all_classic ? FP_SUB : (sc.st ? (int)(sc.facts & FP_F_CONV) : 0));
+  unsigned prev_nl = (nclassic == 0 || base <= begin) ? 1u : ((raw[base - 1] == 10 || raw[base - 1] == 13) ? 1u : 0u);
   unsigned state = sc.st;
   unsigned filled = 0;   // bytes emitted so far by this wave
   int nbad = 0;          // kept characters outside the alphabet (separators subtracted: they are marked bad, not counted)
-  unsigned flag_low = 0;
+  // a blank (or control byte) outside header lines: this parser's assumption does not hold.  The sub-steps computed
+  // here see their own; behind them the summary pass saw them for this wave, and in front of them as well if the wave
+  // is entered in state 0 (entered in state 1, those were blanks of the header line the wave starts in)
+  unsigned flag_low = all_classic ? 0u : (sc.facts & (sc.st ? FP_F_LOW_TAIL : (FP_F_LOW_TAIL | FP_F_LOW_HEAD)));
   unsigned nhi = 0;      // KEPT bytes >= 0x80: sequence characters the reference would decode as multi-byte text
                          // (bytes of header lines never enter a k-mer: lib/mercat2_kmers.py:52-53)
+  const unsigned* __restrict__ wmasks = masks + wave * (FP_SUB * 64) + lane;
+  // (the text and the mask word of the next sub-step are asked for before this one is worked on: without the mask
+  // arithmetic between a load and its use there is little else to hide the latency behind)
+  uint4 v_next = load16(raw, base + (size_t)lane * 16, begin, n);
+  unsigned m_next = wmasks[0];
 #pragma unroll 1
   for (int sub = 0; sub < FP_SUB; ++sub) {
-    const size_t pos = base + (size_t)sub * 1024 + (size_t)lane * 16;
-    unsigned nl, gt, st, low, hi;
-    const uint4 v = classify16(raw, pos, begin, n, nl, gt, st, low, hi);
-    unsigned out, sep, bl, last_nl;
-    state = wave_step(nl, gt, st, low, prev_nl, state, out, sep, bl, last_nl);
-    prev_nl = last_nl;
-    flag_low |= bl;  // a blank (or control byte) outside header lines: this parser's assumption does not hold
+    const uint4 v = v_next;
+    const unsigned m = m_next;
+    if (sub + 1 < FP_SUB) {
+      v_next = load16(raw, base + (size_t)(sub + 1) * 1024 + (size_t)lane * 16, begin, n);
+      m_next = wmasks[(sub + 1) * 64];
+    }
+    unsigned out, sep;
+    if (sub < nclassic) {
+      unsigned nl, gt, st, low, hi, bl, last_nl;
+      classify16(v, nl, gt, st, low, hi);
+      state = wave_step(nl, gt, st, low, prev_nl, state, out, sep, bl, last_nl);
+      prev_nl = last_nl;
+      flag_low |= bl;
+      nhi += __popc(hi & out & ~sep);
+    } else {
+      out = m & 0xFFFFu;
+      sep = m >> 16;
+    }
     const unsigned cnt = __popc(out);
     nbad -= (int)__popc(sep);
-    nhi += __popc(hi & out & ~sep);
     const unsigned inc = mk_wave_scan_incl(cnt);  // inclusive scan over the wave
     unsigned at = shift + filled + inc - cnt;
 #define FP_BYTE(j) ((uint8_t)(((j) < 4 ? v.x : ((j) < 8 ? v.y : ((j) < 12 ? v.z : v.w))) >> (8 * ((j) & 3))))
@@ -451,18 +505,22 @@ int mk_launch_fparse(mk_ctx* c, const uint8_t* d_raw, size_t begin, size_t len, 
   if (len == 0) return MK_OK;
   const size_t nwaves = (n + FP_WAVE_BYTES - 1) / FP_WAVE_BYTES;
   const size_t e_bytes = (nwaves * sizeof(FpEntry) + 15) & ~(size_t)15;
-  int rc = mk_buf_reserve(c, c->tile_maps, e_bytes + nwaves * sizeof(FpScan));
+  // behind the entries and the scan: one mask word per lane and sub-step (n / 4 bytes), a wave's 64 on a 256-byte boundary
+  const size_t m_off = (e_bytes + nwaves * sizeof(FpScan) + 255) & ~(size_t)255;
+  int rc = mk_buf_reserve(c, c->tile_maps, m_off + nwaves * FP_SUB * 64 * sizeof(unsigned));
   if (rc) return rc;
   FpEntry* entries = (FpEntry*)c->tile_maps.p;
   FpScan* scan = (FpScan*)((char*)c->tile_maps.p + e_bytes);
+  unsigned* masks = (unsigned*)((char*)c->tile_maps.p + m_off);
   MkChunkInfo* info = (MkChunkInfo*)c->info.p;
   const unsigned blocks = (unsigned)((nwaves + FP_WAVES - 1) / FP_WAVES);
+  const bool classic = mk_env_int("MK_FP_CLASSIC", 0) != 0;  // the emit pass computes every mask again (A/B)
   mk_prof_begin(c, MK_K_PARSE);
-  hipLaunchKernelGGL(mk_fparse_summ, dim3(blocks), dim3(FP_THREADS), 0, c->stream, d_raw, begin, n, nwaves, entries, info, codes, bad,
-                     2 * bad_words, bad_words);  // (the summary pass clears the packed words and the bad bitmap)
+  hipLaunchKernelGGL(mk_fparse_summ, dim3(blocks), dim3(FP_THREADS), 0, c->stream, d_raw, begin, n, nwaves, entries, masks, info, codes,
+                     bad, 2 * bad_words, bad_words);  // (the summary pass clears the packed words and the bad bitmap)
   hipLaunchKernelGGL(mk_fparse_scan, dim3(1), dim3(1024), 0, c->stream, (const FpEntry*)entries, nwaves, scan, info, bad);
-  hipLaunchKernelGGL(mk_fparse_emit, dim3(blocks), dim3(FP_THREADS), 0, c->stream, d_raw, begin, n, nwaves, scan,
-                     (uint8_t*)c->seq.p, info, codes, bad, write_seq ? 1 : 0);
+  hipLaunchKernelGGL(mk_fparse_emit, dim3(blocks), dim3(FP_THREADS), 0, c->stream, d_raw, begin, n, nwaves, (const FpScan*)scan,
+                     (const unsigned*)masks, (uint8_t*)c->seq.p, info, codes, bad, write_seq ? 1 : 0, classic ? 1 : 0);
   mk_prof_end(c);
   MK_HIP(hipGetLastError());
   return MK_OK;
