@@ -716,13 +716,18 @@ int mk_pair_stats(mk_ctx* const* ctxs, int n, size_t slab_rows, mk_pair_t* out, 
 int mk_pair_stats_matrix(int device, const uint64_t* matrix, size_t rows, int n, mk_pair_t* out, uint64_t* sums,
                          uint64_t* flags);
 /* ---- alpha diversity of a sample: the moments of its count column (lib/mercat2_diversity.py:13-53
- *      computes nine scikit-bio metrics from exactly these), reduced on the GPU ------------------ */
+ *      computes nine scikit-bio metrics from exactly these), reduced on the GPU ------------------
+ * A row is a key whose count is not zero.  The integer fields are exact, total modulo 2^64.  sum_sq is added up in
+ * integers (192 bits: no table can overflow them) and converted once.  sum_clnc is a float64 sum of fl(c) * ln(fl(c))
+ * in an order the table's layout fixes and no launch changes -- no floating-point atomics: an unchanged table answers
+ * with the same bits every time; within (rows + 8) * 2^-53 of the true sum, relative, whatever the layout.
+ * A sharer (mk_share_table) answers for its OWN tables, the owner for every row its table holds. */
 typedef struct mk_alpha_t {
   uint64_t observed; /* rows (distinct k-mers)                                   */
-  uint64_t total;    /* sum of the counts                                        */
+  uint64_t total;    /* sum of the counts, modulo 2^64                           */
   uint64_t freq[11]; /* freq[i], i = 1..10: rows whose count is i (freq[0] unused) */
-  double sum_sq;     /* sum of count^2                                           */
-  double sum_clnc;   /* sum of count * ln(count)                                 */
+  double sum_sq;     /* sum of count^2: exact, rounded once                      */
+  double sum_clnc;   /* sum of count * ln(count): same table, same bits          */
 } mk_alpha_t;
 int mk_alpha_stats(mk_ctx* ctx, mk_alpha_t* out);
 

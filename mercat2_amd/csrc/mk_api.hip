@@ -535,25 +535,39 @@ extern "C" int mk_alpha_stats(mk_ctx* c, mk_alpha_t* out) {
   if (c->in_chunk) { c->err = "mk_alpha_stats: a chunk is open"; return MK_ERR_STATE; }
   MK_HIP(hipSetDevice(c->device));
   int rc;
-  if ((rc = mk_buf_reserve(c, c->ex_tmp, 16 * sizeof(u64))) != MK_OK) return rc;
-  if ((rc = mk_launch_alpha(c, (unsigned long long*)c->ex_tmp.p)) != MK_OK) return rc;
-  u64 h[16];
-  MK_HIP(hipMemcpyAsync(h, c->ex_tmp.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  size_t records = 0;
+  if ((rc = mk_launch_alpha(c, &records)) != MK_OK) return rc;
+  std::vector<u64> h(records * AL_WORDS);
+  if (records) MK_HIP(hipMemcpyAsync(h.data(), c->ex_tmp.p, h.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipStreamSynchronize(c->stream));
   memset(out, 0, sizeof *out);
-  out->observed = h[0];
-  out->total = h[1];
-  for (int i = 1; i <= 10; ++i) out->freq[i] = h[2 + i];
-  memcpy(&out->sum_sq, &h[13], 8);
-  memcpy(&out->sum_clnc, &h[14], 8);
+  // Integers are added as integers -- sum c^2 in 192 bits: 128 for the low words, the carries out of them counted --
+  // and sum c ln c record by record, as the records lie: the order is the table's, not the launch's.
+  unsigned __int128 sq = 0;
+  u64 sq_top = 0;
+  const auto add_sq = [&](unsigned __int128 v) { sq += v; sq_top += sq < v; };
+  for (size_t r = 0; r < records; ++r) {
+    const u64* rec = &h[r * AL_WORDS];
+    out->observed += rec[AL_ROWS];
+    out->total += rec[AL_TOTAL];
+    for (int i = 1; i <= 10; ++i) out->freq[i] += rec[AL_FREQ + i];
+    add_sq(((unsigned __int128)rec[AL_SQ + 1] << 64) | rec[AL_SQ]);
+    sq_top += rec[AL_SQ + 2];
+    double clnc;
+    memcpy(&clnc, &rec[AL_CLNC], 8);
+    out->sum_clnc += clnc;
+  }
   if (c->run_side) {  // the one key that lives beside the packed table (32 x 'T')
     const u64 v = c->run_side;
     out->observed += 1;
     out->total += v;
     if (v <= 10) out->freq[v] += 1;
-    out->sum_sq += (double)v * (double)v;
+    add_sq((unsigned __int128)v * v);
     out->sum_clnc += (double)v * log((double)v);
   }
+  // One rounding.  Above 2^128 the low word moves into a sticky bit, far below the 53 bits that are kept.
+  if (!sq_top) out->sum_sq = (double)sq;
+  else out->sum_sq = ldexp((double)((((unsigned __int128)sq_top << 64) | (u64)(sq >> 64)) | ((u64)sq != 0)), 64);
   return MK_OK;
 }
 

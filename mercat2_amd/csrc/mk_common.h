@@ -417,7 +417,10 @@ int mk_sort_rows(mk_ctx* c, const uint8_t* d_arena, size_t rows, int k, uint64_t
 int mk_launch_rows_by_slot(mk_ctx* c, const uint64_t* slot_keys, const uint64_t* slot_cnts, size_t rows, uint64_t* cnt_by_row, uint64_t* d_bad);
 int mk_launch_rows_gather(mk_ctx* c, const uint8_t* arena, const uint64_t* order, const uint64_t* cnt_by_row, size_t rows, int k,
                           uint8_t* out_rows, uint64_t* out_cnts);
-int mk_launch_alpha(mk_ctx* c, unsigned long long* d_out);  // 16 words: see mk_alpha_k<View>
+// The alpha moments of every table of c (mk_alpha_k<View>): *records records of AL_WORDS words in c->ex_tmp, one per
+// workgroup, the tables in mk_each_table order and a table's workgroups in block order.
+enum { AL_ROWS = 0, AL_TOTAL = 1, AL_SQ = 2 /* 3 words, low first */, AL_CLNC = 5 /* a double */, AL_FREQ = 5 /* + count, 1..10 */, AL_WORDS = 16 };
+int mk_launch_alpha(mk_ctx* c, size_t* records);
 int mk_launch_accumulate(mk_ctx* c, uint64_t min_count);
 // every row of another one-word table (same device) added into c's running table; *new_rows counts the new keys
 int mk_launch_merge_table64(mk_ctx* c, const MkSlot* from, size_t from_slots);

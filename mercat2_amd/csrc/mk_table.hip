@@ -603,57 +603,82 @@ int mk_launch_compact128(mk_ctx* c, const MkSlot128* t, size_t slots, uint64_t* 
 }
 
 // ------------------------------------------------------------------- alpha-diversity moments
-// One pass over the running table(s): everything the nine alpha metrics of lib/mercat2_diversity.py:13-53
-// need from the count column (out[0] rows, out[1] sum c, out[2..12] rows with count 0..10 (slot 2 unused),
-// then as doubles out[13] sum c^2, out[14] sum c ln c).
-__device__ __forceinline__ void alpha_take(u64 c, u64& rows, u64& total, double& sq, double& clnc, unsigned* s_freq) {
+// One pass over the running table(s): everything the nine alpha metrics of lib/mercat2_diversity.py:13-53 need from the
+// count column.  A workgroup leaves one record of AL_WORDS words (mk_common.h): rows, sum c, sum c^2 as a 192-bit
+// integer (a square takes 128 bits, and no table has 2^64 rows), sum c ln c as a double, the rows with count 1..10.
+// Nothing is added in floating point but sum c ln c, and that in a fixed order: a lane adds its slots in ascending
+// order, the lanes of a wave fold by the shuffle tree, thread 0 adds the waves in wave order, the host adds the records
+// in the order they lie.  No atomic touches a double: the same table gives the same bits.
+struct AlphaSums {
+  u64 rows = 0, total = 0, sq0 = 0, sq1 = 0, sq2 = 0;
+  double clnc = 0;
+  __device__ __forceinline__ void add_sq(u64 lo, u64 hi, u64 top) {  // 192-bit add, carries by hand
+    sq0 += lo;
+    u64 carry = sq0 < lo;
+    sq1 += hi;
+    u64 carry2 = sq1 < hi;
+    sq1 += carry;
+    carry2 += sq1 < carry;
+    sq2 += top + carry2;
+  }
+  __device__ __forceinline__ void add(u64 r, u64 t, u64 lo, u64 hi, u64 top, double cl) {
+    rows += r;
+    total += t;
+    add_sq(lo, hi, top);
+    clnc += cl;
+  }
+};
+__device__ __forceinline__ void alpha_take(u64 c, AlphaSums& s, unsigned* s_freq) {
   if (!c) return;
-  rows += 1;
-  total += c;
   const double d = (double)c;
-  sq += d * d;
-  clnc += d * log(d);
+  s.add(1, c, c * c, __umul64hi(c, c), 0, d * log(d));
   if (c <= 10) atomicAdd(&s_freq[c], 1u);
 }
 template <class View>
 __global__ __launch_bounds__(256) void mk_alpha_k(View v, size_t n, u64* __restrict__ out) {
   __shared__ unsigned s_freq[11];
-  __shared__ unsigned long long s_rows, s_total;
-  __shared__ double s_sq, s_clnc;
+  __shared__ u64 s_wave[4][5];
+  __shared__ double s_clnc[4];
   if (threadIdx.x < 11) s_freq[threadIdx.x] = 0;
-  if (threadIdx.x == 0) { s_rows = 0; s_total = 0; s_sq = 0; s_clnc = 0; }
   __syncthreads();
-  u64 rows = 0, total = 0;
-  double sq = 0, clnc = 0;
+  AlphaSums s;
   mk_for_each(n, [&](size_t i) {  // (every thread adds its slots in ascending order)
     u64 a, b, cnt;
-    if (v.keyed(i, a, b, cnt)) alpha_take(cnt, rows, total, sq, clnc, s_freq);
+    if (v.keyed(i, a, b, cnt)) alpha_take(cnt, s, s_freq);
   });
-  for (int d = 32; d > 0; d >>= 1) {
-    rows += __shfl_down(rows, d);
-    total += __shfl_down(total, d);
-    sq += __shfl_down(sq, d);
-    clnc += __shfl_down(clnc, d);
-  }
+  for (int d = 32; d > 0; d >>= 1)
+    s.add(__shfl_down(s.rows, d), __shfl_down(s.total, d), __shfl_down(s.sq0, d), __shfl_down(s.sq1, d), __shfl_down(s.sq2, d),
+          __shfl_down(s.clnc, d));
   if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&s_rows, (unsigned long long)rows);
-    atomicAdd(&s_total, (unsigned long long)total);
-    atomicAdd(&s_sq, sq);
-    atomicAdd(&s_clnc, clnc);
+    u64* w = s_wave[threadIdx.x >> 6];
+    w[0] = s.rows; w[1] = s.total; w[2] = s.sq0; w[3] = s.sq1; w[4] = s.sq2;
+    s_clnc[threadIdx.x >> 6] = s.clnc;
   }
   __syncthreads();
+  u64* rec = out + (size_t)blockIdx.x * AL_WORDS;  // every word of the record is written: nothing to clear beforehand
   if (threadIdx.x == 0) {
-    if (s_rows) atomicAdd(&out[0], (u64)s_rows);
-    if (s_total) atomicAdd(&out[1], (u64)s_total);
-    if (s_sq != 0) atomicAdd(reinterpret_cast<double*>(&out[13]), s_sq);
-    if (s_clnc != 0) atomicAdd(reinterpret_cast<double*>(&out[14]), s_clnc);
+    for (int w = 1; w < 4; ++w) s.add(s_wave[w][0], s_wave[w][1], s_wave[w][2], s_wave[w][3], s_wave[w][4], s_clnc[w]);
+    rec[AL_ROWS] = s.rows; rec[AL_TOTAL] = s.total;
+    rec[AL_SQ] = s.sq0; rec[AL_SQ + 1] = s.sq1; rec[AL_SQ + 2] = s.sq2;
+    rec[AL_CLNC] = (u64)__double_as_longlong(s.clnc);
   }
-  if (threadIdx.x < 11 && s_freq[threadIdx.x]) atomicAdd(&out[2 + threadIdx.x], (u64)s_freq[threadIdx.x]);
+  if (threadIdx.x >= 1 && threadIdx.x <= 10) rec[AL_FREQ + threadIdx.x] = s_freq[threadIdx.x];
 }
 
-int mk_launch_alpha(mk_ctx* c, u64* d_out) {
-  MK_HIP(hipMemsetAsync(d_out, 0, 16 * sizeof(u64), c->stream));
-  return mk_each_table(c, [&](auto v, size_t n, int) { return launch(c, mk_alpha_k<decltype(v)>, grid_for(n, 256, 1024), v, n, d_out); });
+int mk_launch_alpha(mk_ctx* c, size_t* records) {
+  const auto grid = [](size_t n) { return grid_for(n, 256, 1024); };
+  size_t all = 0, at = 0;
+  (void)mk_each_table(c, [&](auto, size_t n, int) { all += grid(n); return MK_OK; });
+  *records = all;
+  if (!all) return MK_OK;
+  int rc;
+  if ((rc = mk_buf_reserve(c, c->ex_tmp, all * AL_WORDS * sizeof(u64))) != MK_OK) return rc;
+  u64* out = (u64*)c->ex_tmp.p;
+  return mk_each_table(c, [&](auto v, size_t n, int) {
+    u64* recs = out + at * AL_WORDS;
+    at += grid(n);
+    return launch(c, mk_alpha_k<decltype(v)>, grid(n), v, n, recs);
+  });
 }
 
 // ------------------------------------------------------------------ two tables combined by key (mk_table_op)

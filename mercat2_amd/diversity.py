@@ -5,7 +5,15 @@ The reference reads the sample's TSV back and hands the count column to nine sci
 chao1, chao1_ci, ace).  All nine are functions of a few moments of that column -- rows, sum, sum of
 squares, sum of c*ln(c) and the number of rows with count 1..10 -- which ``mk_alpha_stats`` reduces on
 the GPU from the table that is already there; the closed forms below turn them into the same
-numbers, printed the same way (``round(x, 2)``; 'NA' where scikit-bio raises).
+numbers, printed the same way (``round(x, 2)``; 'NA' where scikit-bio raises).  The integer moments and
+the sum of squares are exact (rounded to float64 once); shannon of a one-row table prints as the
+reference's ``-0.0``.
+
+One limit: ``dominance`` is sum c^2 / n^2 here and a float64 sum of (c/n)^2 in scikit-bio.
+Where the true value is an exact decimal tie -- 200 * sum c^2 / n^2 an odd integer -- the two may round
+to different sides, and ``simpson`` with them: counts [7, 5, 8] give 138/400 = 0.345, the reference
+prints 0.35, this module 0.34.  No moment can repair that.  tests/test_alpha_moments_host.py met it in
+3 of 2160 seeded tables of 1..8 rows and in none of 840 tables of 50..5000 rows.
 
 Beta diversity: the reference hands the dense samples x k-mers matrix of combined_<type>_T.tsv to scikit-bio's
 ``beta_diversity`` (scipy's ``pdist``, scipy 1.8.1 pinned by its recipe) for 21 metrics.  Every one of them is a
@@ -94,8 +102,16 @@ def alpha_from_stats(st: dict) -> Dict[str, str]:
     if o == 0:
         return {m: "NA" for m in METRICS}
     dom = st["sum_sq"] / (n * n)
+
+    def shannon():
+        # scikit-bio sums -p ln p: -0.0 for one row (p = 1), above zero for more.  ln n - sum_clnc / n cancels to a few
+        # ulps of ln n there, on either side of zero.
+        if o == 1:
+            return -0.0
+        return max((math.log(n) - st["sum_clnc"] / n) / math.log(2), 0.0)
+
     values = {
-        "shannon": lambda: (math.log(n) - st["sum_clnc"] / n) / math.log(2),
+        "shannon": shannon,
         "simpson": lambda: 1.0 - dom,
         "simpson_e": lambda: (1.0 / dom) / o,
         "goods_coverage": lambda: 1.0 - freq[1] / n,

@@ -303,9 +303,8 @@ def test_lookups_leave_the_table_as_it_was():
             ctx.lookup(keys)
             ctx.lookup_text(b"\n".join(keys))
         after = (ctx.rows(), ctx.export(), ctx.alpha_stats())
-        # (sum_clnc: f64 atomics in an order no two launches share, n additions off by at most n * 2^-53 relative, n < 2^16)
-        clnc = (before[2].pop("sum_clnc"), after[2].pop("sum_clnc"))
-        assert before[0] == after[0] and before[2] == after[2] and clnc[1] == pytest.approx(clnc[0], rel=2.0 ** -37, abs=0)
+        # (sum_clnc too: it is added in an order the table fixes, so an unchanged table gives the same bits)
+        assert before[0] == after[0] and before[2] == after[2]
         assert (before[1][0] == after[1][0]).all() and (before[1][1] == after[1][1]).all()
 
 

@@ -360,8 +360,8 @@ def test_everything_computed_from_loaded_tables_equals_the_counted_tables(case, 
             # integers, and a sum of squares far below 2^53: exact whatever the order of the additions
             for f in ("observed", "total", "freq", "sum_sq"):
                 assert sa[f] == sb[f], f
-            # sum of count * ln(count) in f64, added with atomics in an order no two launches share: n additions are off by
-            # at most n * 2^-53 relative (n < 2^20 rows here: 2^-33 ~ 1.2e-10)
+            # sum of count * ln(count) in f64, added in the order of the slots, and two tables lay the same rows out
+            # differently: n additions are off by at most n * 2^-53 relative (n < 2^20 rows here: 2^-33 ~ 1.2e-10)
             assert sb["sum_clnc"] == pytest.approx(sa["sum_clnc"], rel=2e-10, abs=0)
     finally:
         for ctx in counted + loaded:
