@@ -529,6 +529,67 @@ int mk_trim_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags,
                    uint8_t* d_out, size_t out_cap, size_t* out_len, uint64_t* d_kept, mk_screen_row_t* d_rows, size_t cap,
                    size_t* nrows, mk_trim_t* st);
 
+/* ---- sequences in, every isolated substitution the table can name put right out: k-mer-spectrum error correction
+ *      where the counts are (the conservative "spectral alignment" step of Musket, Lighter, BFC and Quake; with
+ *      abundance trimming and normalisation the third standard step in front of an assembly or a second count) ----
+ * Text, records, kept characters, windows, probing, fold, opening rules, pieces and errors are mk_screen_*'s, word for
+ * word, as for mk_trim_*: same parser, same rows (rows[r] is the screen row of record r of the UNCORRECTED text for
+ * rule->at_least), same mk_screen_t figures (st->screen; its s_total is the wall time of this whole call), MK_ERR_STATE
+ * with an open chunk or a refused one, MK_ERR_NON_ASCII, the fold rule (MK_CORRECT_FOLD = MK_SCREEN_FOLD), pieces cut by
+ * mk_record_cuts, the stream idle afterwards, the counting figures and the export untouched.  The rule is defined for
+ * nucleotide contexts with packed keys only (MK_ALPHABET_NT2, k <= 64): any other context is MK_ERR_ARG.
+ * Rule: record r has the kept characters s[0..L) and W = L - k + 1 windows; c[j] is the count mk_lookup returns for
+ * the k bytes s[j..j+k), folded under MK_CORRECT_FOLD, 0 for an absent k-mer.  Window j is WEAK iff c[j] < at_least.  A
+ * RUN is a maximal interval [a, b] of weak windows, n = b - a + 1 of them.  A run has at most one candidate position p:
+ *   a == 0 and b == W - 1    none (nothing in the record is solid)
+ *   a == 0, n <= k           p = b             (an error in the first k characters)
+ *   b == W - 1, n <= k       p = a + k - 1     (an error in the last k characters)
+ *   interior, n == k         p = b             (= a + k - 1: the one character all k windows hold)
+ *   anything else            none
+ * The alternatives at p are the bases of A C G T other than the byte s[p]: three, or four where s[p] is none of them (an
+ * N, a lower-case letter).  An alternative x is VIABLE iff every window of the run has a count >= at_least with s[p]
+ * replaced by x -- mk_lookup's count of those k bytes again; a window that still holds a byte outside ACGT is looked up
+ * as text.  Exactly one viable alternative: s[p] becomes it (FIXED).  Two or more: AMBIGUOUS, none: UNFIXABLE, and the
+ * record stays as it is there.  Every run is judged against the record as it came, and all fixes are applied together:
+ * the windows a candidate tests are exactly the windows that hold its p, and none of them belongs to another run or
+ * holds another run's p, because a solid window lies between two runs -- so neither the order of the runs nor that of
+ * the records, pieces or lanes reaches the result.  One pass; a second pass is a second call on the output.
+ * Output: EVERY record of the text, in text order, each as the bytes of its header LINE as they stand (mk_trim_*'s: from
+ * the first byte of the line through its terminator; none for the headless record), then, if L > 0, its L characters on
+ * one line and one LF; a record without characters is its header line alone.  Nothing of the preamble (st->preamble)
+ * is emitted.  *out_len <= n + 1; a text of one-line, LF-terminated records in which nothing is fixed comes back byte
+ * for byte.  fix[r] counts record r's runs and, of those with a candidate, the fixed, ambiguous and unfixable ones:
+ * runs - fixed - ambiguous - unfixable runs had a shape without a candidate.  fix numbers the records of the whole call.
+ * at_least >= 1 and reserved == 0; a NULL rule, a value out of range or an unknown flag bit is MK_ERR_ARG and the
+ * message names it.  The result is exact for every at_least up to 2^64 - 1.  fix and rows may each be NULL (cap is
+ * ignored when both are).  With out_cap or cap too small: MK_ERR_RANGE, the needed sizes in *out_len and *nrows, nothing
+ * written past either -- every piece is still walked to learn them (out = NULL, out_cap = 0 is the sizing call).  st may
+ * be NULL.
+ * mk_correct_text: host memory in and out, piece by piece (each piece's output is appended to out by its copy back).
+ * mk_correct_device: text, out, fix and rows in DEVICE memory of the context's GPU, one piece; text and out at any
+ * address, d_fix and d_rows aligned to 8 (MK_ERR_ARG otherwise). */
+#define MK_CORRECT_FOLD 1u       /* = MK_SCREEN_FOLD */
+typedef struct mk_correct_rule_t { uint64_t at_least, reserved; } mk_correct_rule_t;
+typedef struct mk_correct_row_t { uint32_t runs, fixed, ambiguous, unfixable; } mk_correct_row_t;
+typedef struct mk_correct_t {
+  mk_screen_t screen;                                      /* as mk_screen_* fills it for the same text and at_least */
+  uint64_t records;                                        /* records emitted: all of them */
+  uint64_t runs, candidates;                               /* weak runs; those whose shape names a position */
+  uint64_t fixed, ambiguous, unfixable;                    /* the candidates by outcome: they add up to candidates */
+  uint64_t bases, bytes_out;                               /* kept characters of all records; output bytes */
+  uint64_t preamble;                                       /* bytes in front of the first header line of a text that is not headless */
+  /* seconds: HIP-event time of the placement (record starts, header ends, window offsets); of the track kernel; of the
+   * run kernel; of the try kernel and the patches; of the gather (the lengths and their scan run between the two and
+   * are in none); host time in the copies back */
+  double s_place, s_track, s_runs, s_try, s_gather, s_write;
+} mk_correct_t;
+int mk_correct_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_bytes, unsigned flags, const mk_correct_rule_t* rule,
+                    uint8_t* out, size_t out_cap, size_t* out_len, mk_correct_row_t* fix, mk_screen_row_t* rows, size_t cap,
+                    size_t* nrows, mk_correct_t* st);
+int mk_correct_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_correct_rule_t* rule,
+                      uint8_t* d_out, size_t out_cap, size_t* out_len, mk_correct_row_t* d_fix, mk_screen_row_t* d_rows, size_t cap,
+                      size_t* nrows, mk_correct_t* st);
+
 /* ---- sequences in, the reads thinned to a target depth out: digital normalisation by the median mk_track_* computes,
  *      decided and applied where the counts are (BBNorm's plan with khmer's normalize-by-median depth; with abundance
  *      trimming the other standard step in front of an assembly or a second count) ----

@@ -26,7 +26,11 @@ track_<type>/<sample>_track.txt -- per record of FILE the count of every one of 
 order -- and track_<type>/<sample>_median.tsv with the median of those counts (mk_track_text).  -trim FILE writes, for every
 sample of FILE's type, trim_<type>/<sample>_trimmed.fna (.faa): every record of FILE cut in front of its first k-mer the
 sample's table holds fewer than -trim_min times, as khmer's filter-abund trims (mk_trim_text), and
-trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -norm FILE writes, for every sample of FILE's
+trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -correct FILE writes, for every nucleotide
+sample, correct_<type>/<sample>_corrected.fna: every record of FILE with the single wrong bases put right that the sample's
+table can name -- a run of k-mers held fewer than -correct_min times, shaped as one substitution shapes it, and exactly one
+base that makes them all solid (mk_correct_text) -- and correct_<type>/<sample>_correct.tsv with every record's runs and what
+became of them; -correct_mate FILE2 corrects two files of mates together and writes ..._1 and ..._2.  -norm FILE writes, for every sample of FILE's
 type, norm_<type>/<sample>_<kept|tossed>.fna (.faa): the records of FILE thinned to depth -norm_target by the median of their
 k-mers' counts in the sample's table -- digital normalisation, BBNorm's count-first plan with khmer's depth (mk_norm_text) --
 and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  Paired reads: with -paired the FILE of
@@ -129,6 +133,20 @@ def parseargs(argv=None):
     p.add_argument("-trim_min", type=int, default=None, metavar="N",
                    help="-trim: a k-mer is low below this count [2, the default cutoff of khmer's filter-abund]")
     p.add_argument("-trim_len", type=int, default=None, metavar="N", help="-trim: drop a record that keeps fewer characters [k]")
+    p.add_argument("-correct", type=str, required=False, metavar="FILE",
+                   help="a nucleotide FASTA or FASTQ file (plain or .gz) of reads to correct against the tables on the GPU: for "
+                        "every sample of FILE's type, correct_<type>/<sample>_corrected.fna with every record of FILE -- its "
+                        "header line, then its characters on one line -- in which each base that alone makes a run of k-mers "
+                        "rarer than -correct_min, and that exactly one other base repairs, is replaced by that base, and "
+                        "correct_<type>/<sample>_correct.tsv with 'record, length, runs, fixed, ambiguous, unfixable' per "
+                        "record.  A FASTQ file is first converted as MerCat2's fq2fa converts it, so the output is FASTA; "
+                        "with -canonical the k-mers are folded; -k at most 64")
+    p.add_argument("-correct_min", type=int, default=None, metavar="N", help="-correct: a k-mer is weak below this count [2]")
+    p.add_argument("-correct_rounds", type=int, default=None, metavar="N",
+                   help="-correct: correct the output again, N passes in all [1]")
+    p.add_argument("-correct_mate", type=str, default=None, metavar="FILE2",
+                   help="-correct: the second file of paired reads (FILE the first); every record is written, to "
+                        "..._corrected_1 and ..._corrected_2")
     p.add_argument("-norm", type=str, required=False, metavar="FILE",
                    help="a FASTA or FASTQ file (plain or .gz) of reads to thin against the tables on the GPU (digital "
                         "normalisation; the table should have been counted from these reads): for every sample of FILE's type, "
@@ -255,6 +273,32 @@ def parseargs(argv=None):
         if args.trim_len is not None and not 1 <= args.trim_len < 1 << 64:
             p.error(f"-trim_len {args.trim_len}: must be 1 or more")
         args.trim_len = args.trim_len or 0  # (0: the k-mer length)
+    args.correct_kind = None
+    if not args.correct:
+        for flag in ("correct_min", "correct_rounds", "correct_mate"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -correct FILE")
+    else:
+        if not os.path.isfile(args.correct):
+            p.error(f"file '{args.correct}' is not valid.\n")
+        args.correct_kind = classify(Path(args.correct).expanduser().absolute(), True)[0]
+        if not args.correct_kind:
+            p.error(f"-correct {args.correct}: the extension names neither a nucleotide nor a FASTQ file")
+        if args.correct_kind == "protein":
+            p.error(f"-correct {args.correct}: a protein file; the correction rule is defined for nucleotide reads only")
+        if args.k > 64:
+            p.error(f"-correct needs -k of at most 64, not {args.k}")
+        args.correct_min = 2 if args.correct_min is None else args.correct_min
+        if not 1 <= args.correct_min < 1 << 64:
+            p.error(f"-correct_min {args.correct_min}: must be 1 or more")
+        args.correct_rounds = 1 if args.correct_rounds is None else args.correct_rounds
+        if not 1 <= args.correct_rounds <= 64:
+            p.error(f"-correct_rounds {args.correct_rounds}: must lie in 1..64")
+        if args.correct_mate is not None:
+            if not os.path.isfile(args.correct_mate):
+                p.error(f"file '{args.correct_mate}' is not valid.\n")
+            if classify(Path(args.correct_mate).expanduser().absolute(), True)[0] != args.correct_kind:
+                p.error(f"-correct_mate {args.correct_mate}: not the type of -correct {args.correct}")
     args.norm_kind = None
     if not args.norm:
         for flag in ("norm_target", "norm_min", "norm_seed", "norm_keep"):
@@ -738,6 +782,24 @@ def main(argv=None) -> int:
                     print(f"trim_{kind}/: {res['records']} records of {os.path.basename(args.trim)} trimmed against "
                           f"{len(tables)} sample(s), records written (of them cut): " +
                           ", ".join(f"{base} {n} ({t})" for base, (n, t) in kept.items()))
+                if args.correct and args.correct_kind == kind:  # from the tables still on the GPU
+                    from .kmers import correct_reads
+                    folder = out / f"correct_{kind}"
+                    folder.mkdir(parents=True, exist_ok=True)
+                    fixed = {}
+                    for base in sorted(tables):
+                        mate = args.correct_mate
+                        try:
+                            res = correct_reads(tables[base], args.correct, folder / (f"{base}_corrected_1.fna" if mate else f"{base}_corrected.fna"),
+                                                at_least=args.correct_min, rounds=args.correct_rounds,
+                                                tsv_path=folder / f"{base}_correct.tsv", mate_file=mate,
+                                                out_path2=folder / f"{base}_corrected_2.fna" if mate else None)
+                        except native.MercatHipError as e:
+                            raise SystemExit(f"-correct {args.correct}: {e}")
+                        fixed[base] = (res["fixed"], res["runs"])
+                    print(f"correct_{kind}/: {res['records']} records of {os.path.basename(args.correct)} corrected against "
+                          f"{len(tables)} sample(s), bases replaced (of weak runs): " +
+                          ", ".join(f"{base} {n} ({t})" for base, (n, t) in fixed.items()))
                 if args.norm and args.norm_kind == kind:  # from the tables still on the GPU
                     from .kmers import normalize_read_pairs, normalize_reads
                     (out / f"norm_{kind}").mkdir(parents=True, exist_ok=True)

@@ -1,7 +1,8 @@
 // mk_screenpiece.h -- what the calls share that read a text record by record against the tables: mk_screen_*
 // (mk_screen.hip) reports the rows, mk_filter_* (mk_filter.hip) goes on from them to the records' bytes, mk_track_*
 // (mk_track.hip) to the count under every window, mk_trim_* (mk_trim.hip) to the records cut at their first low one,
-// mk_norm_* (mk_norm.hip) to the records thinned by the median of those counts.
+// mk_norm_* (mk_norm.hip) to the records thinned by the median of those counts, mk_correct_* (mk_correct.hip) to the
+// records with their isolated substitutions put right.
 // One opening (sc_run), one way of cutting a host text into pieces
 // (sc_text_pieces), one piece routine (sc_piece: parse, record scan, probe -- its kernels and launches live in
 // mk_screen.hip), the tile's sizes (SC_RUN, SC_SPAN, sc_span_bytes) and the one-workgroup scan that turns tile counts

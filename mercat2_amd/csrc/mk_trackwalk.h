@@ -1,6 +1,7 @@
 // mk_trackwalk.h -- the count under every window of a piece, placed and written, and the median of every record's
 // counts: what mk_track_* (mk_track.hip: the counts go to the caller) and mk_norm_* (mk_norm.hip: the counts stay in
-// device scratch, only the medians are used) share.  tk_lens_k and the scan give woff[]; tk_probe_k is the walk of
+// device scratch, only the medians are used) share; mk_correct_* (mk_correct.hip) takes the placement and tk_probe_k for
+// the counts its runs are read from.  tk_lens_k and the scan give woff[]; tk_probe_k is the walk of
 // mk_screenwalk.h with the positional sink; tk_median sorts the short records' counts a segment a record
 // (rocprim::segmented_radix_sort_keys, tk_pick_k) and finds the median of a LONG record -- more than
 // MK_MEDIAN_SELECT_MIN windows -- by radix selection in place (tk_longest_k, tk_long_k, tk_sel_hist_k, tk_sel_pick_k).

@@ -1,5 +1,6 @@
 // mk_trimwalk.h -- a record cut in front of its first low window, found and written: what mk_trim_* (mk_trim.hip: every
-// record on its own) and mk_pairs_* (mk_pairs.hip: the mates of a pair together) share.  tr_hend_k gives hlen[r];
+// record on its own) and mk_pairs_* (mk_pairs.hip: the mates of a pair together) share; mk_correct_* (mk_correct.hip)
+// takes tr_hend_k and tr_emit for records it writes whole.  tr_hend_k gives hlen[r];
 // tr_first_k is the walk of mk_screenwalk.h with a sink that keeps the first low window of every record; tr_decide_k
 // turns it into kept[r] and the record's output length; tr_gather_k / tr_edges_k write a record from its two sources and
 // tr_emit is the tail of a piece that launches them.  The kernels that are no templates are static: every file that
@@ -115,6 +116,7 @@ static __global__ void __launch_bounds__(256) tr_decide_k(const mk_screen_row_t*
 // What the gather knows of a record: where its output starts, its two sources and their lengths.
 struct TrRec {
   u64 at, hsrc, h, ssrc, body;  // dst[r]; start[r], hlen[r]; sstart[r], hlen[r] + kept[r]: the LF stands at offset body
+  u64 lf;                       // 1; 0 where kept[r] == 0: a header line alone, which only mk_correct_* emits
 };
 struct TrPlace {
   const uint8_t* __restrict__ text;
@@ -129,14 +131,15 @@ struct TrPlace {
   size_t nrows;
   __device__ __forceinline__ TrRec rec(size_t r) const {
     const u64 h = hlen[r];
-    return TrRec{dst[r], start[r], h, sstart[r], h + kept[r]};
+    const u64 kp = kept[r];
+    return TrRec{dst[r], start[r], h, sstart[r], h + kp, kp ? 1ull : 0ull};
   }
 };
 
 // Chunks, rounds and the search as in fl_gather_k.  A chunk is filled segment by segment: up to 16 bytes of the header
 // line (raw text), of the kept symbols (stream), or the LF, masked to what the segment still has and shifted to their
-// place; the record after an LF is r + 1, or the next emitted one.  An emitted record holds k + 1 bytes or more, so a
-// chunk sees at most sixteen segments.
+// place; the record after an LF is r + 1, or the next emitted one.  A record mk_trim_* emits holds k + 1 bytes or more;
+// mk_correct_* emits every record, a header line alone without the LF (lf == 0), and a chunk may hold several of them.
 #define TR_CHUNKS 4
 static __global__ void __launch_bounds__(256) tr_gather_k(TrPlace p, u64 head, u64 nbody, uint8_t* __restrict__ out) {
   const u64 g0 = fl_first_lane((((u64)blockIdx.x * 256 + threadIdx.x) >> 6) * (64 * TR_CHUNKS));
@@ -161,7 +164,7 @@ static __global__ void __launch_bounds__(256) tr_gather_k(TrPlace p, u64 head, u
       v |= seg << (8 * b);
       b += m;
       if (b == 16) break;
-      if (q + m <= c.body) continue;  // (the LF was not among them: the same record goes on)
+      if (q + m < c.body + c.lf) continue;  // (the record's last byte was not among them: the same record goes on)
       ++r;  // the record ended inside the chunk (bytes follow: an emitted record does)
       if (p.dst[r + 1] == p.dst[r]) r = fl_record_from(p.dst, r, p.nrows, o0 + b);
       c = p.rec(r);

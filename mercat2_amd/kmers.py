@@ -304,6 +304,46 @@ def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[
             "bytes_out": len(out)}
 
 
+def correct_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 2, rounds: int = 1,
+                  tsv_path: Union[str, Path, None] = None, mate_file: Union[str, Path, None] = None,
+                  out_path2: Union[str, Path, None] = None) -> Dict[str, int]:
+    """The records of a FASTA or FASTQ file with their isolated substitutions corrected against a table still on the GPU
+    (Counter.correct: a run of k-mers the table holds fewer than ``at_least`` times, shaped as one wrong base shapes it,
+    is repaired iff exactly one other base makes all of them solid), written to ``out_path`` -- gzip (level 1) if that
+    name ends in '.gz', plain bytes otherwise.  Every record is written.  The file is read as filter_reads reads it:
+    '.gz' inflated on the host, a FASTQ file first converted as MerCat2's fq2fa converts it (mk_fq2fa) -- so the output
+    is always FASTA: the header line as it stands, the characters on one line.  ``rounds`` > 1 corrects the output
+    again: a fix can free a neighbouring run.  A canonical table folds the windows.  Returns {"records", "runs", "fixed",
+    "ambiguous", "unfixable", "bases", "bytes_out"}: "runs" of the first round, the others summed over the rounds.  With
+    ``tsv_path`` every record's name, length and those four figures are written there too (report.write_correct_tsv).
+    With ``mate_file`` the two files are interleaved on the host (native.interleave), corrected as one text and split
+    again into ``out_path`` and ``out_path2`` (interleaved in ``out_path`` without the latter): every record is
+    written, so pairs stay pairs."""
+    if rounds < 1:
+        raise ValueError("correct_reads: rounds must be 1 or more")
+    if mate_file is None and out_path2 is not None:
+        raise ValueError("correct_reads: out_path2 goes with mate_file only")
+    first = text = _reads_text(file) if mate_file is None else _pairs_text(file, mate_file)
+    fix = None
+    for _ in range(rounds):
+        text, step, _ = table.correct(text, at_least)
+        if fix is None:
+            fix = step.copy()
+        else:
+            fix[:, 1:] += step[:, 1:]
+    if mate_file is None:
+        _write_reads(out_path, text)
+    else:
+        _write_pairs(text, None, out_path, out_path2, None)
+    lengths = record_lengths(first)
+    if tsv_path is not None:
+        from .report import write_correct_tsv
+        write_correct_tsv(tsv_path, record_names(first), lengths, fix)
+    total = [int(v) for v in fix.sum(axis=0, dtype="uint64")]
+    return {"records": int(fix.shape[0]), "runs": total[0], "fixed": total[1], "ambiguous": total[2], "unfixable": total[3],
+            "bases": int(sum(lengths)), "bytes_out": len(text)}
+
+
 def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], target: int = 20,
                     min_depth: int = 0, seed: int = 0, invert: bool = False, tsv_path: Union[str, Path, None] = None) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file thinned to depth ``target`` against a table still on the GPU that has been

@@ -36,7 +36,8 @@ ABI_SYMBOLS = [
     "mk_pair_stats", "mk_pair_stats_matrix", "mk_load_tsv", "mk_load_tsv_text", "mk_tsv_shape",
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
-    "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_norm_text", "mk_norm_device",
+    "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_correct_text", "mk_correct_device",
+    "mk_norm_text", "mk_norm_device",
     "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
@@ -46,6 +47,7 @@ SCREEN_FOLD = 1
 FILTER_FOLD, FILTER_INVERT = 1, 2
 TRACK_FOLD, TRACK_SAT32 = 1, 2
 TRIM_FOLD = 1
+CORRECT_FOLD = 1
 NORM_FOLD, NORM_INVERT = 1, 2
 PAIRS_FILTER, PAIRS_TRIM, PAIRS_NORM = 0, 1, 2  # mk_pairs_rule_t.op
 PAIRS_OPS = {"filter": PAIRS_FILTER, "trim": PAIRS_TRIM, "norm": PAIRS_NORM}
@@ -179,6 +181,29 @@ class Trim(C.Structure):
                 [(n, C.c_uint64) for n in ("records_out", "records_trimmed", "records_dropped", "bases_in", "bases_out",
                                            "bytes_out", "preamble")] +
                 [(n, C.c_double) for n in ("s_place", "s_first", "s_gather", "s_write")])
+
+    def as_dict(self):
+        d = self.screen.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+class CorrectRule(C.Structure):
+    """mk_correct_rule_t (include/mercat_hip.h)."""
+    _fields_ = [("at_least", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+# mk_correct_row_t: the columns of Counter.correct's ``fix`` array, and the same row as a structured dtype
+CORRECT_COLUMNS = ("runs", "fixed", "ambiguous", "unfixable")
+CorrectRow = np.dtype([(n, np.uint32) for n in CORRECT_COLUMNS])
+
+
+class Correct(C.Structure):
+    """mk_correct_t (include/mercat_hip.h)."""
+    _fields_ = ([("screen", Screen)] +
+                [(n, C.c_uint64) for n in ("records", "runs", "candidates", "fixed", "ambiguous", "unfixable", "bases",
+                                           "bytes_out", "preamble")] +
+                [(n, C.c_double) for n in ("s_place", "s_track", "s_runs", "s_try", "s_gather", "s_write")])
 
     def as_dict(self):
         d = self.screen.as_dict()
@@ -393,6 +418,10 @@ def lib() -> C.CDLL:
                                    C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
         "mk_trim_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(TrimRule), C.c_void_p, C.c_size_t, szp,
                                      C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
+        "mk_correct_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(CorrectRule), C.c_void_p, C.c_size_t, szp,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Correct)]),
+        "mk_correct_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(CorrectRule), C.c_void_p, C.c_size_t, szp,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Correct)]),
         "mk_norm_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Norm)]),
         "mk_norm_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
@@ -1250,6 +1279,49 @@ class Counter:
         self._check(self._L.mk_trim_device(self._h, ptr, int(nbytes), TRIM_FOLD if self._fold_flag(fold) else 0, C.byref(rule),
                                            out_ptr or None, int(out_cap), C.byref(out_len), kept_ptr or None, rows_ptr or None,
                                            int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
+    # -- correcting: FASTA text in, every record with its isolated substitutions put right out; the table is only read
+    def correct(self, path_or_bytes, at_least: int = 2, fold: Optional[bool] = None, piece_bytes: int = 0,
+                info: Optional[dict] = None):
+        """mk_correct_text: (out, fix, rows) of the FASTA text (a path to a plain file, or the text itself as bytes).  A
+        maximal run of k-mers the table holds fewer than ``at_least`` times that has the shape one substituted base
+        leaves -- k of them inside a record, up to k at either end -- names that base; it is replaced iff exactly one
+        other base of ACGT makes every k-mer of the run solid (include/mercat_hip.h has the rule).  ``out``: every record
+        in order, its header line as it stands, then its characters on one line and a newline.  ``fix``: a (records, 4)
+        uint32 array, CORRECT_COLUMNS a record (``fix.view(CorrectRow)`` names them): its weak runs and those fixed,
+        ambiguous and unfixable.  ``rows``: the (records, 5) uint64 array Counter.screen gives for the same, uncorrected
+        text and ``at_least``.  Nucleotide contexts with k <= 64 only.  ``fold`` None: fold iff the context is
+        canonical.  ``info``, if given, receives the mk_correct_t fields (those of mk_screen_t beside them)."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        cap = (int(np.count_nonzero(held == ord(">"))) if size else 0) + 1  # (a record is a header line, or the text in front)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        fix = np.zeros((cap, len(CORRECT_COLUMNS)), dtype=np.uint32)
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Correct()
+        rule = CorrectRule(int(at_least), 0)
+        self._check(self._L.mk_correct_text(self._h, addr, size, int(piece_bytes), CORRECT_FOLD if self._fold_flag(fold) else 0,
+                                            C.byref(rule), out.ctypes.data, size + 1, C.byref(out_len), fix.ctypes.data,
+                                            rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), fix[: n.value], rows[: n.value]
+
+    def correct_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, fix_ptr: int = 0, rows_ptr: int = 0, cap: int = 0,
+                       at_least: int = 2, fold: Optional[bool] = None) -> dict:
+        """mk_correct_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> the corrected records at
+        device address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) and, where given, four uint32 a
+        record at ``fix_ptr`` and the rows (five uint64 a record) at ``rows_ptr`` with room for ``cap`` records each --
+        all on this context's GPU, the last two aligned to 8.  Returns the mk_correct_t fields: "bytes_out" bytes were
+        written, "records" rows."""
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), Correct()
+        rule = CorrectRule(int(at_least), 0)
+        self._check(self._L.mk_correct_device(self._h, ptr, int(nbytes), CORRECT_FOLD if self._fold_flag(fold) else 0,
+                                              C.byref(rule), out_ptr or None, int(out_cap), C.byref(out_len), fix_ptr or None,
+                                              rows_ptr or None, int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
 
     # -- normalising: FASTA text in, the records thinned to a target depth out; the table is only read

@@ -212,6 +212,26 @@ def write_trim_tsv(path, names: Sequence[str], lengths, kept, keep=None) -> int:
     return len(names)
 
 
+def format_correct_tsv(names: Sequence[str], lengths, fix) -> bytes:
+    """``record\tlength\truns\tfixed\tambiguous\tunfixable``, then one line per record (kmers.correct_reads /
+    Counter.correct): its name, its characters and the four columns of its ``fix`` row."""
+    if len(names) != len(lengths) or len(names) != len(fix):
+        raise ValueError("format_correct_tsv: %d names for %d lengths and %d fix rows" % (len(names), len(lengths), len(fix)))
+    out = [b"record\tlength\truns\tfixed\tambiguous\tunfixable\n"]
+    for name, length, row in zip(names, lengths, fix):
+        runs, fixed, ambiguous, unfixable = (int(v) for v in row)
+        out.append(name.encode() + b"\t%d\t%d\t%d\t%d\t%d\n" % (int(length), runs, fixed, ambiguous, unfixable))
+    return b"".join(out)
+
+
+def write_correct_tsv(path, names: Sequence[str], lengths, fix) -> int:
+    """``format_correct_tsv`` written to ``path``; returns the number of records."""
+    text = format_correct_tsv(names, lengths, fix)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
 def format_norm_tsv(names: Sequence[str], windows, median, kept, paired: bool = False) -> bytes:
     """``record\twindows\tmedian\tkept``, then one line per record (kmers.normalize_reads / Counter.normalize): its name,
     its k-mers, the median of their counts and 1 where the record was written, 0 where not.  A ``paired`` run adds a last
