@@ -12,6 +12,8 @@ import pytest
 
 from mercat2_amd import cli, diversity, native
 
+import pair_moments as pm
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
@@ -20,52 +22,9 @@ INDEX = json.loads((GOLDEN / "pca" / "index.json").read_text())
 ALPHA = json.loads((GOLDEN / "diversity" / "alpha_cases.json").read_text())
 EXACT = {"euclidean", "sqeuclidean", "cityblock", "manhattan", "braycurtis", "chebyshev", "hamming", "matching",
          "jaccard", "dice", "rogerstanimoto", "russellrao", "sokalmichener", "sokalsneath", "yule"}
-INTS = ("dot", "l1", "cheb", "neq", "both", "sums", "rows", "constant_row")
 
 
-def _close_enough(got, want):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    return bool(np.all(np.abs(got - want) <= 1e-9 * np.maximum(1.0, np.abs(want))))
-
-
-def _exact(X):
-    """The statistics of a rows x n count matrix in exact integers (numpy int64 where nothing can overflow, else
-    Python ints), canb / seuc in float64."""
-    X = np.asarray(X, dtype=np.uint64)
-    rows, n = X.shape
-    top = int(X.max()) if X.size else 0
-    O = X.astype(np.int64) if top * top * max(rows, 1) < (1 << 62) else X.astype(object)
-    dot = O.T.dot(O) if rows else np.zeros((n, n), dtype=np.int64)
-    l1 = np.zeros((n, n), dtype=object)
-    cheb, neq, both = (np.zeros((n, n), dtype=np.uint64) for _ in range(3))
-    F = X.astype(np.float64)
-    canb, seuc = np.zeros((n, n)), np.zeros((n, n))
-    var = F.var(axis=1, ddof=1) if n > 1 and rows else np.ones(rows)
-    for i in range(n):
-        d = np.abs(O - O[:, i:i + 1])
-        l1[i] = [int(v) for v in d.sum(axis=0)] if rows else 0
-        cheb[i] = d.max(axis=0) if rows else 0
-        neq[i] = (X != X[:, i:i + 1]).sum(axis=0)
-        both[i] = ((X != 0) & (X[:, i:i + 1] != 0)).sum(axis=0)
-        with np.errstate(all="ignore"):
-            s = F + F[:, i:i + 1]
-            canb[i] = np.where(s > 0, np.abs(F - F[:, i:i + 1]) / np.where(s > 0, s, 1), 0).sum(axis=0)
-            seuc[i] = ((F - F[:, i:i + 1]) ** 2 / var[:, None]).sum(axis=0)
-    np.fill_diagonal(l1, 0)
-    np.fill_diagonal(canb, 0)
-    np.fill_diagonal(seuc, 0)
-    return {"dot": [[int(v) for v in r] for r in dot], "l1": [[int(v) for v in r] for r in l1], "cheb": cheb, "neq": neq,
-            "both": both, "canb": canb, "seuc": seuc, "sums": [int(v) for v in O.sum(axis=0)] if rows else [0] * n,
-            "rows": rows, "constant_row": bool(n and rows and (X == X[:, :1]).all(axis=1).any())}
-
-
-def _same_ints(got, want):
-    for key in INTS:
-        g, w = got[key], want[key]
-        if isinstance(g, np.ndarray):
-            assert np.array_equal(g, w), key
-        else:
-            assert g == w, key
+_close_enough, _exact, _same_ints = pm.close_enough, pm.exact, pm.same_ints  # (tests/pair_moments.py)
 
 
 def _check(ctxs, slab_rows=0):

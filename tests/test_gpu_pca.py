@@ -11,15 +11,15 @@ import pytest
 
 from mercat2_amd import cli, native, pca
 
+import pair_moments as pm
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 PCA = GOLDEN / "pca"
 
 
-def _xtx(matrix):
-    m = np.asarray(matrix, dtype=np.uint64).astype(object)
-    return (m.T.dot(m)).tolist() if m.size else [[0] * m.shape[1] for _ in range(m.shape[1])]
+_xtx = pm.xtx  # (tests/pair_moments.py: X^T X in Python ints)
 
 
 def _check(ctxs, slab_rows=0):
