@@ -36,7 +36,11 @@ extern "C" {
 #define MK_ERR_RANGE (-7)     /* caller buffer too small / value out of range */
 #define MK_ERR_UNSUPPORTED (-8) /* clean mode (mk_set_clean): the chunk holds text whose rewrite by removeN the GPU does not
                                  reproduce (a blank inside a sequence line, a '>' that does not start a header line, a
-                                 0x7F byte); nothing of the chunk was counted -- count the text mk_remove_n produces instead */
+                                 0x7F byte); nothing of the chunk was counted -- count the text mk_remove_n produces instead.
+                                 mk_fastq_select_* / mk_fq_interleave / mk_fq_split_pairs: a FASTQ record is malformed (its
+                                 first line lacks the '@', its third the '+', its sequence and quality lines differ in
+                                 length, its sequence line holds a blank or '*' while kept[] is given, or the text ends
+                                 inside it); the message names the record and the check, nothing was written */
 
 /* Alphabets select the packed fast path; they never restrict the input.  Windows holding a
  * symbol outside the alphabet are still counted, exactly, by the by-reference kernel
@@ -719,7 +723,70 @@ int mk_interleave(const uint8_t* text1, size_t n1, const uint8_t* text2, size_t 
                   size_t* npairs);
 int mk_split_pairs(const uint8_t* text, size_t n, uint8_t* out1, size_t cap1, size_t* len1, uint8_t* out2, size_t cap2,
                    size_t* len2, size_t* npairs);
-const char* mk_host_error(void); /* the message of this thread's last failed mk_interleave / mk_split_pairs */
+const char* mk_host_error(void); /* the message of this thread's last failed mk_interleave / mk_split_pairs / mk_fq_* */
+/* The FASTQ analogues, for the R1 / R2 files of reads whose qualities are to be kept (mk_fastq_select_*): records are the
+ * 4-line records defined there -- lines split on '\n' only, record i is lines 4i .. 4i + 3, nothing of a line is looked
+ * at.  mk_fq_interleave writes record i of text1, then record i of text2, byte for byte; a last record without '\n' gets
+ * one; empty lines behind the last complete record are dropped, 1 to 3 trailing lines that are not all empty are
+ * MK_ERR_UNSUPPORTED (the text ends inside a record).  Different record counts are MK_ERR_RANGE and mk_host_error gives
+ * both.  *out_len <= n1 + n2 + 2; with cap too small MK_ERR_RANGE and the needed size in *out_len (out = NULL, cap = 0 is
+ * the sizing call).  mk_fq_split_pairs is the inverse for an interleaved text with an even record count (odd:
+ * MK_ERR_RANGE): record 2p goes to out1, record 2p + 1 to out2; *len1, *len2 <= n + 1. */
+int mk_fq_interleave(const uint8_t* text1, size_t n1, const uint8_t* text2, size_t n2, uint8_t* out, size_t cap, size_t* out_len,
+                     size_t* npairs);
+int mk_fq_split_pairs(const uint8_t* text, size_t n, uint8_t* out1, size_t cap1, size_t* len1, uint8_t* out2, size_t cap2,
+                      size_t* len2, size_t* npairs);
+
+/* ---- a decision applied to the FASTQ text it was taken for: the records mk_filter_*, mk_norm_* and mk_pairs_* keep and
+ *      the lengths mk_trim_* leaves, written as FASTQ with their qualities (what khmer, BBDuk and BBNorm hand to an
+ *      assembler, a mapper or a second correction pass) ----
+ * Those calls read the FASTA view mk_fq2fa gives of a FASTQ text; record r there is record r here as long as every header
+ * line starts with '@' (the first check below).  The decision arrays may come from them or from the caller.  The tables
+ * are not read: the counting figures and the export stay untouched; an open chunk is MK_ERR_STATE as for the screen
+ * calls; the stream is idle afterwards.
+ * Lines and records: lines are fq2fa's -- split on '\n' only, numbered across the whole text; a last line without '\n' is
+ * a line.  Record r is lines 4r .. 4r + 3.  The text must hold exactly nrec records, else MK_ERR_RANGE and the message
+ * gives both counts (this is checked first).  The up to 3 lines behind the last complete record are tolerated only if
+ * they are all empty; otherwise they are a malformed record (the text ends inside it).
+ * Well-formedness, checked on the device for every record, emitted or not; a failure is MK_ERR_UNSUPPORTED, the message
+ * names the lowest offending record index (over the whole call) and the first check it fails, in this order:
+ *   line 4r starts with '@' (otherwise fq2fa drops that header and the FASTA view's record numbers no longer match);
+ *   line 4r + 2 starts with '+';
+ *   the sequence line 4r + 1 and the quality line 4r + 3 are equally long, one trailing '\r' not counted on either;
+ *   only when kept is given: the sequence line, without its trailing '\r', holds no '*' and none of the bytes str.strip()
+ *     removes (blank, tab, VT, FF, CR, 0x1C..0x1F) -- its bytes are then exactly the parser's kept characters that kept[r]
+ *     counts;
+ *   only when kept is given: kept[r] <= the sequence length L.  This one is MK_ERR_RANGE.
+ * Selection: record r is emitted iff (keep == NULL or keep[r] == which) and (kept == NULL or kept[r] > 0).  which = 1 is
+ * the main output, 2 the orphans of mk_pairs_*; any other value is MK_ERR_ARG; which is ignored when keep is NULL.  With
+ * both arrays NULL the call validates and copies the whole text.
+ * Output with kept == NULL: the emitted records in text order, each the bytes [start of line 4r, start of line 4r + 4)
+ * byte for byte (CR LF stays CR LF); a last record without its final '\n' gets one, so that outputs can always be
+ * concatenated.  Output with kept given: line 4r as it stands through its '\n'; the first kept[r] bytes of the sequence
+ * line and one '\n'; line 4r + 2 as it stands through its '\n'; the first kept[r] bytes of the quality line and one '\n'
+ * -- for an untrimmed LF-terminated record the input byte for byte.  *out_len <= n + 1 in both modes.
+ * out = NULL, out_cap = 0 is the sizing call.  With out_cap too small: MK_ERR_RANGE, the needed size in *out_len, nothing
+ * written past the buffer -- every piece is still walked to learn it.  On every other error *out_len = 0.  n == 0 with
+ * nrec == 0 is success with empty output.  st may be NULL.
+ * mk_fastq_select_text: host memory in and out, piece by piece: pieces end behind a line 4j once they hold piece_bytes
+ * (mk_fastq_cuts; 0: the default, and the limits, of the screen calls; a record longer than that makes its piece grow);
+ * each piece copies its own slice of keep and kept to the device.  Output, errors and the record indices in messages do
+ * not depend on piece_bytes.
+ * mk_fastq_select_device: everything in DEVICE memory of the context's GPU, one piece; text and out at any address,
+ * d_kept aligned to 8 (MK_ERR_ARG otherwise). */
+typedef struct mk_fastq_select_t {
+  uint64_t records, records_out, records_trimmed; /* of the text; emitted; emitted with kept[r] below the sequence length */
+  uint64_t bases_out, bytes_out, lines;           /* sequence bytes emitted; output bytes; lines of the text            */
+  /* seconds: host time in the copies to the device (text, keep, kept); HIP-event time of the line index; of the checks,
+   * the decision and its scan; of the gather; host time in the copies back */
+  double s_copy, s_index, s_place, s_gather, s_write;
+} mk_fastq_select_t;
+int mk_fastq_select_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes,
+                         const uint8_t* keep, const uint64_t* kept, size_t nrec, unsigned which,
+                         uint8_t* out, size_t out_cap, size_t* out_len, mk_fastq_select_t* st);
+int mk_fastq_select_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n,
+                           const uint8_t* d_keep, const uint64_t* d_kept, size_t nrec, unsigned which,
+                           uint8_t* d_out, size_t out_cap, size_t* out_len, mk_fastq_select_t* st);
 
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
@@ -943,6 +1010,12 @@ int mk_stream_cuts(const uint8_t* text, size_t n, uint64_t chunksize, size_t blo
  * find_kmers takes for a header (lib/mercat2_kmers.py:51-52); a line that merely contains '>' is not one.
  * Through the streaming scanner, `block` bytes at a time, self-checked like mk_stream_cuts. */
 int mk_record_cuts(const uint8_t* text, size_t n, uint64_t piece, size_t block, uint64_t* cuts, size_t cap, size_t* ncuts);
+/* Where mk_fastq_select_text cuts a FASTQ text into pieces: behind a line 4j (lines split on '\n' only, numbered across
+ * the text) once a piece holds `piece` bytes, so that no 4-line record is split and a record longer than `piece` makes
+ * its piece grow.  Only '\n' is counted; nothing else of the text is looked at.  cuts[0..*ncuts) ascending, strictly
+ * inside the text; piece i is [cuts[i-1], cuts[i]) with cuts[-1] = 0 and cuts[ncuts] = n.  MK_ERR_RANGE (and the needed
+ * size in *ncuts) if cap is short. */
+int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts);
 /* The file reader's own gzip decoder (csrc/mk_inflate.h) over a whole '.gz' file held in memory,
  * producing `block` bytes per step as the reader does, every member's CRC-32 and length checked.
  * A self-check for tests (against zlib): out must hold the whole text (cap bytes).

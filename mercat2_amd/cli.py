@@ -37,7 +37,8 @@ and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  P
 -filter, -trim and -norm is interleaved, with -filter_mate / -trim_mate / -norm_mate FILE2 the pair comes in two files
 (interleaved on the host, written back as ..._1 and ..._2); either way a pair is written or left out as a whole
 (mk_pairs_text), -filter_pair says whether one matching mate is enough, -singles also writes <sample>_singles.fna (.faa)
-and the per-record TSVs gain the pair's index.  -against FILE -op OP writes, for every sample of FILE's type,
+and the per-record TSVs gain the pair's index.  -fastq_out makes -filter, -trim and -norm of a FASTQ FILE write FASTQ with
+the qualities (.fastq in place of .fna; mk_fastq_select_text).  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
 (mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
@@ -67,12 +68,15 @@ FILTER_PAIR = ("either", "both")
 def paired_outputs(args, name: str, folder, stem: str, base: str, ext: str) -> dict:
     """The arguments of kmers.filter_reads / trim_reads / normalize_reads that say where the reads of call ``name`` go:
     ``folder/<stem>.<ext>`` for single reads and interleaved pairs, ``<stem>_1`` and ``<stem>_2`` with a mate file,
-    ``<base>_singles`` with -singles."""
+    ``<base>_singles`` with -singles.  With -fastq_out the extension is ``fastq`` and the call is told to write FASTQ."""
+    fastq = {"fastq_out": True} if getattr(args, "fastq_out", False) else {}
+    if fastq:
+        ext = "fastq"
     if not args.pairs_of[name]:
-        return {"out_path": folder / f"{stem}.{ext}"}
+        return {"out_path": folder / f"{stem}.{ext}", **fastq}
     mate = getattr(args, f"{name}_mate")
     kw = {"out_path": folder / (f"{stem}_1.{ext}" if mate else f"{stem}.{ext}"), "paired": True, "mate_file": mate,
-          "out_path2": folder / f"{stem}_2.{ext}" if mate else None}
+          "out_path2": folder / f"{stem}_2.{ext}" if mate else None, **fastq}
     if args.singles:
         kw["singles_path"] = folder / f"{base}_singles.{ext}"
     return kw
@@ -175,6 +179,10 @@ def parseargs(argv=None):
                    help="-filter on paired reads: a pair matches if either mate does, or only if both do [either]")
     p.add_argument("-singles", action="store_true",
                    help="paired reads: also write <sample>_singles.fna, the reads that pass on their own in a pair that does not")
+    p.add_argument("-fastq_out", action="store_true",
+                   help="-filter, -trim, -norm (with -paired, the mate options and -singles too): FILE is FASTQ and the reads are "
+                        "written as FASTQ with their qualities -- the quality line cut wherever -trim cuts the sequence -- to "
+                        "the same names with .fastq in place of .fna (mk_fastq_select_text).  Not with -correct")
     p.add_argument("-filter_min", type=int, default=None, metavar="N", help="-filter: a k-mer is a hit from this count on [1]")
     p.add_argument("-filter_hits", type=int, default=None, metavar="N", help="-filter: a record matches from this many hits on [1]")
     p.add_argument("-filter_frac", type=float, default=None, metavar="F",
@@ -367,6 +375,21 @@ def parseargs(argv=None):
             p.error("-singles with -filter needs -filter_keep matched: the pairs that do not pass have no orphans")
         if args.pairs_of["norm"] and args.norm_keep != "kept":
             p.error("-singles with -norm needs -norm_keep kept")
+    if args.fastq_out:  # refused before anything runs: the qualities must exist, and must still fit the bases
+        if not (args.filter or args.trim or args.norm):
+            p.error("-fastq_out needs -filter, -trim or -norm FILE")
+        if args.correct:
+            p.error("-fastq_out does not go with -correct: corrected bases no longer go with the qualities they came with")
+        for name in ("filter", "trim", "norm"):
+            file = getattr(args, name)
+            if not file:
+                continue
+            if getattr(args, f"{name}_kind") == "protein":
+                p.error(f"-fastq_out with -{name} {file}: a protein file has no qualities to keep")
+            for f in (file, mates[name]):
+                if f is not None and not str(f).lower().endswith(tuple(FILE_EXT_FASTQ)):
+                    p.error(f"-fastq_out with -{name} {f}: not a FASTQ file ({' / '.join(FILE_EXT_FASTQ)}); there are no "
+                            "qualities to write")
     args.against_kind = None
     if args.op and not args.against:
         p.error("-op needs -against FILE")
@@ -748,6 +771,10 @@ def main(argv=None) -> int:
                                                min_frac=args.filter_frac, invert=args.filter_keep == "unmatched", **where)
                         except native.MercatHipError as e:
                             raise SystemExit(f"-filter {args.filter}: {e}")
+                        except ValueError as e:  # (-fastq_out: a header line that fq2fa drops)
+                            if not args.fastq_out:
+                                raise
+                            raise SystemExit(f"-filter {args.filter}: {e}")
                         kept[base] = res["kept"]
                     print(f"filter_{kind}/: {res['records']} records of {os.path.basename(args.filter)} filtered against "
                           f"{len(tables)} sample(s), {args.filter_keep} records written: " +
@@ -778,6 +805,10 @@ def main(argv=None) -> int:
                                              **paired_outputs(args, "trim", out / f"trim_{kind}", f"{base}_trimmed", base, ext))
                         except native.MercatHipError as e:
                             raise SystemExit(f"-trim {args.trim}: {e}")
+                        except ValueError as e:  # (-fastq_out: a header line that fq2fa drops)
+                            if not args.fastq_out:
+                                raise
+                            raise SystemExit(f"-trim {args.trim}: {e}")
                         kept[base] = (res["kept"], res["trimmed"])
                     print(f"trim_{kind}/: {res['records']} records of {os.path.basename(args.trim)} trimmed against "
                           f"{len(tables)} sample(s), records written (of them cut): " +
@@ -801,7 +832,7 @@ def main(argv=None) -> int:
                           f"{len(tables)} sample(s), bases replaced (of weak runs): " +
                           ", ".join(f"{base} {n} ({t})" for base, (n, t) in fixed.items()))
                 if args.norm and args.norm_kind == kind:  # from the tables still on the GPU
-                    from .kmers import normalize_read_pairs, normalize_reads
+                    from .kmers import normalize_read_pairs, normalize_reads, normalize_reads_fastq
                     (out / f"norm_{kind}").mkdir(parents=True, exist_ok=True)
                     ext = "faa" if kind == "protein" else "fna"
                     kept = {}
@@ -809,10 +840,16 @@ def main(argv=None) -> int:
                         try:
                             where = paired_outputs(args, "norm", out / f"norm_{kind}", f"{base}_{args.norm_keep}", base, ext)
                             run = normalize_read_pairs if where.pop("paired", False) else normalize_reads
+                            if run is normalize_reads and where.pop("fastq_out", False):
+                                run = normalize_reads_fastq
                             res = run(tables[base], args.norm, target=args.norm_target, min_depth=args.norm_min,
                                       seed=args.norm_seed, invert=args.norm_keep == "tossed",
                                       tsv_path=out / f"norm_{kind}" / f"{base}_norm.tsv", **where)
                         except native.MercatHipError as e:
+                            raise SystemExit(f"-norm {args.norm}: {e}")
+                        except ValueError as e:  # (-fastq_out: a header line that fq2fa drops)
+                            if not args.fastq_out:
+                                raise
                             raise SystemExit(f"-norm {args.norm}: {e}")
                         kept[base] = (res["kept"], res["thinned"])
                     print(f"norm_{kind}/: {res['records']} records of {os.path.basename(args.norm)} thinned to depth "

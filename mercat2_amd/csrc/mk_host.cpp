@@ -105,6 +105,26 @@ static int stream_cuts(const uint8_t* text, size_t n, uint64_t chunksize, size_t
   return (sink.cuts.size() > cap && cuts) ? MK_ERR_RANGE : MK_OK;
 }
 
+// Where mk_fastq_select_text cuts a FASTQ text: a piece ends behind a line 4j (lines split on '\n' only, numbered
+// across the text) once it holds `piece` bytes.  Only '\n' is counted (memchr); nothing else of the text is looked at.
+extern "C" int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts) {
+  if (!ncuts || (n && !text)) return MK_ERR_ARG;
+  size_t found = 0, pos = 0, from = 0;
+  uint64_t line = 0;
+  while (pos < n) {
+    const uint8_t* nl = (const uint8_t*)memchr(text + pos, '\n', n - pos);
+    if (!nl) break;
+    pos = (size_t)(nl - text) + 1;
+    if ((++line & 3) == 0 && pos < n && pos - from >= piece) {
+      if (found < cap && cuts) cuts[found] = (uint64_t)pos;
+      ++found;
+      from = pos;
+    }
+  }
+  *ncuts = found;
+  return (found > cap && cuts) ? MK_ERR_RANGE : MK_OK;
+}
+
 // ------------------------------------------------------------------------------- gunzip
 // The reader's own gzip decoder (mk_inflate.h) over a whole file in memory, producing `block` bytes
 // per call as the file reader does, with every member's CRC-32 and length checked (zlib's crc32).
@@ -777,6 +797,95 @@ extern "C" int mk_split_pairs(const uint8_t* text, size_t n, uint8_t* out1, size
   if (npairs) *npairs = r / 2;
   if (a1 > cap1 || a2 > cap2) {
     g_host_err = "mk_split_pairs: the outputs hold " + std::to_string(a1) + " and " + std::to_string(a2) + " bytes, more than their room";
+    return MK_ERR_RANGE;
+  }
+  return MK_OK;
+}
+
+// ---- the same for two FASTQ files: records are lines 4i .. 4i + 3 of the text, lines split on '\n' only ------------
+namespace {
+// starts[i] = first byte of record i, starts[records] = the byte behind the last complete record.  False when what
+// trails behind it -- 1 to 3 lines -- is not empty lines only: the text ends inside a record.
+static bool fq_record_starts(const uint8_t* text, size_t n, std::vector<uint64_t>& starts) {
+  size_t pos = 0;
+  uint64_t line = 0;
+  while (pos < n) {
+    if ((line++ & 3) == 0) starts.push_back(pos);
+    const uint8_t* nl = (const uint8_t*)memchr(text + pos, '\n', n - pos);
+    pos = nl ? (size_t)(nl - text) + 1 : n;
+  }
+  if ((line & 3) == 0) starts.push_back(n);
+  for (size_t i = (size_t)starts.back(); i < n; ++i)
+    if (text[i] != '\n') return false;
+  return true;
+}
+// Appends record [a, b) of text at out + at where it fits in cap, with one LF if it does not end in one.
+static size_t put_fq_record(const uint8_t* text, uint64_t a, uint64_t b, uint8_t* out, size_t cap, size_t at) {
+  const size_t len = (size_t)(b - a);
+  const bool lf = len && text[b - 1] != '\n';
+  if (out && at + len + (lf ? 1 : 0) <= cap) {
+    memcpy(out + at, text + a, len);
+    if (lf) out[at + len] = '\n';
+  }
+  return at + len + (lf ? 1 : 0);
+}
+static int fq_incomplete(const char* what, const char* which, size_t records) {
+  g_host_err = std::string(what) + ": " + which + " ends inside record " + std::to_string(records) + " (a FASTQ record is 4 lines)";
+  return MK_ERR_UNSUPPORTED;
+}
+}  // namespace
+
+extern "C" int mk_fq_interleave(const uint8_t* text1, size_t n1, const uint8_t* text2, size_t n2, uint8_t* out, size_t cap,
+                                size_t* out_len, size_t* npairs) {
+  if (!out_len || (n1 && !text1) || (n2 && !text2) || (cap && !out)) { g_host_err = "mk_fq_interleave: NULL buffer"; return MK_ERR_ARG; }
+  *out_len = 0;
+  if (npairs) *npairs = 0;
+  std::vector<uint64_t> s1, s2;
+  const bool ok1 = fq_record_starts(text1, n1, s1), ok2 = fq_record_starts(text2, n2, s2);
+  const size_t r1 = s1.size() - 1, r2 = s2.size() - 1;
+  if (!ok1) return fq_incomplete("mk_fq_interleave", "text1", r1);
+  if (!ok2) return fq_incomplete("mk_fq_interleave", "text2", r2);
+  if (r1 != r2) {
+    g_host_err = "mk_fq_interleave: text1 holds " + std::to_string(r1) + " records, text2 holds " + std::to_string(r2);
+    return MK_ERR_RANGE;
+  }
+  size_t at = 0;
+  for (size_t i = 0; i < r1; ++i) {
+    at = put_fq_record(text1, s1[i], s1[i + 1], out, cap, at);
+    at = put_fq_record(text2, s2[i], s2[i + 1], out, cap, at);
+  }
+  *out_len = at;
+  if (npairs) *npairs = r1;
+  if (at > cap) {
+    g_host_err = "mk_fq_interleave: the output holds " + std::to_string(at) + " bytes, out has room for " + std::to_string(cap);
+    return MK_ERR_RANGE;
+  }
+  return MK_OK;
+}
+
+extern "C" int mk_fq_split_pairs(const uint8_t* text, size_t n, uint8_t* out1, size_t cap1, size_t* len1, uint8_t* out2, size_t cap2,
+                                 size_t* len2, size_t* npairs) {
+  if (!len1 || !len2 || (n && !text) || (cap1 && !out1) || (cap2 && !out2)) { g_host_err = "mk_fq_split_pairs: NULL buffer"; return MK_ERR_ARG; }
+  *len1 = *len2 = 0;
+  if (npairs) *npairs = 0;
+  std::vector<uint64_t> s;
+  const bool ok = fq_record_starts(text, n, s);
+  const size_t r = s.size() - 1;
+  if (!ok) return fq_incomplete("mk_fq_split_pairs", "the text", r);
+  if (r & 1) {
+    g_host_err = "mk_fq_split_pairs: the text holds " + std::to_string(r) + " records, an odd number";
+    return MK_ERR_RANGE;
+  }
+  size_t a1 = 0, a2 = 0;
+  for (size_t i = 0; i < r; i += 2) {
+    a1 = put_fq_record(text, s[i], s[i + 1], out1, cap1, a1);
+    a2 = put_fq_record(text, s[i + 1], s[i + 2], out2, cap2, a2);
+  }
+  *len1 = a1;
+  *len2 = a2;
+  if (npairs) *npairs = r / 2;
+  if (a1 > cap1 || a2 > cap2) {
+    g_host_err = "mk_fq_split_pairs: the outputs hold " + std::to_string(a1) + " and " + std::to_string(a2) + " bytes, more than their room";
     return MK_ERR_RANGE;
   }
   return MK_OK;

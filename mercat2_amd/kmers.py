@@ -218,10 +218,44 @@ def _is_paired(paired, mate_file, out_path2, singles_path) -> bool:
     return True
 
 
+def _fastq_texts(what: str, file, mate_file=None) -> Tuple[bytes, bytes]:
+    """(raw, fasta) of a ``fastq_out`` run: the raw FASTQ text -- with ``mate_file`` both raw texts interleaved on the host
+    (native.interleave_fastq) -- and the FASTA view mk_fq2fa gives of it, which the deciding call reads.  ValueError for
+    a file without a FASTQ suffix, and for a text in which fq2fa drops a header line: record r of the FASTA view would
+    no longer be record r of the FASTQ text."""
+    for f in (file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("%s: fastq_out needs FASTQ input (%s), not %s" % (what, " / ".join(FASTQ_SUFFIXES), f))
+    raw = read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    text, st = native.fq2fa(raw)
+    if st["headers_dropped"] > 0:
+        raise ValueError("%s: fastq_out needs every FASTQ record to start with '@'; %d header line(s) of %s do not, and "
+                         "fq2fa drops them" % (what, st["headers_dropped"], file))
+    return raw, text
+
+
+def _write_fastq(table: "native.Counter", raw: bytes, keep, kept, out_path, out_path2=None, singles_path=None) -> int:
+    """The decision of a call on the FASTA view applied to the raw FASTQ text (Counter.fastq_select) and written as
+    _write_pairs writes FASTA: ``out_path``, or split into ``out_path`` and ``out_path2``; the orphans (keep == 2) to
+    ``singles_path``.  Returns the bytes of the main output."""
+    out = table.fastq_select(raw, keep, kept, which=1)
+    if out_path2 is None:
+        _write_reads(out_path, out)
+    else:
+        first, second = native.split_pairs_fastq(out)
+        _write_reads(out_path, first)
+        _write_reads(out_path2, second)
+    if singles_path is not None:
+        _write_reads(singles_path, table.fastq_select(raw, keep, kept, which=2) if keep is not None else b"")
+    return len(out)
+
+
 def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 1, min_hits: int = 1,
                  min_frac: float = 0.0, invert: bool = False, paired: bool = False, mate_file: Union[str, Path, None] = None,
                  out_path2: Union[str, Path, None] = None, singles_path: Union[str, Path, None] = None,
-                 both: bool = False) -> Dict[str, int]:
+                 both: bool = False, fastq_out: bool = False) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file that match a table still on the GPU (Counter.filter), written to ``out_path``
     -- gzip (level 1) if that name ends in '.gz', plain bytes otherwise; with ``invert`` the records that do not match.  A
     record matches iff at least ``min_hits`` of its k-mers occur ``at_least`` times in the table and they are at least
@@ -233,8 +267,24 @@ def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Unio
     and interleaved with the first on the host): the pair is the unit (Counter.filter_pairs) -- it is written iff either
     mate matches, with ``both`` iff both do.  The output is interleaved in ``out_path``, or split into ``out_path`` and
     ``out_path2``; ``singles_path`` receives the matching mates of pairs that fail under ``both``.  The result gains
-    {"pairs", "pairs_kept", "singles"}."""
+    {"pairs", "pairs_kept", "singles"}.
+    ``fastq_out``: the input (and the mate file) must be FASTQ, and the same records are written as FASTQ, qualities
+    included, byte for byte (Counter.fastq_select applies the decision to the raw text); "bytes_out" counts those bytes.
+    The FASTA output of the deciding call is computed and thrown away."""
     min_ppm = native.ppm_of_fraction(min_frac)
+    if fastq_out:
+        is_paired = _is_paired(paired, mate_file, out_path2, singles_path)
+        raw, text = _fastq_texts("filter_reads", file, mate_file)
+        info = {}
+        if is_paired:
+            _, _, keep, _, _ = table.filter_pairs(text, at_least, min_hits, min_ppm, both, invert, singles=singles_path is not None, info=info)
+            done = {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "bytes_in": len(text), "bytes_out": 0,
+                    "pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]), "singles": int(info["singles_out"])}
+        else:
+            _, keep, _ = table.filter(text, at_least, min_hits, min_ppm, invert)
+            done = {"records": int(keep.shape[0]), "kept": int(keep.sum()), "bytes_in": len(text), "bytes_out": 0}
+        done["bytes_out"] = _write_fastq(table, raw, keep, None, out_path, out_path2, singles_path)
+        return done
     if _is_paired(paired, mate_file, out_path2, singles_path):
         text = _pairs_text(file, mate_file)
         info: Dict[str, int] = {}
@@ -259,7 +309,7 @@ def filter_reads(table: "native.Counter", file: Union[str, Path], out_path: Unio
 def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 2,
                min_len: int = 0, tsv_path: Union[str, Path, None] = None, paired: bool = False,
                mate_file: Union[str, Path, None] = None, out_path2: Union[str, Path, None] = None,
-               singles_path: Union[str, Path, None] = None) -> Dict[str, int]:
+               singles_path: Union[str, Path, None] = None, fastq_out: bool = False) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file, each cut in front of its first k-mer that a table still on the GPU holds fewer
     than ``at_least`` times (Counter.trim: khmer's trim_on_abundance), written to ``out_path`` -- gzip (level 1) if that
     name ends in '.gz', plain bytes otherwise.  A record of which fewer than max(``min_len``, k) characters remain is
@@ -272,7 +322,31 @@ def trim_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[
     and interleaved with the first on the host): the pair is the unit (Counter.trim_pairs) -- both mates are written,
     each at its own trimmed length, iff both keep something.  The output is interleaved in ``out_path``, or split into
     ``out_path`` and ``out_path2``; ``singles_path`` receives the mates that keep something while their mate does not.
-    "kept" then counts the records written in pairs and the result gains {"pairs", "pairs_kept", "singles"}."""
+    "kept" then counts the records written in pairs and the result gains {"pairs", "pairs_kept", "singles"}.
+    ``fastq_out``: the input (and the mate file) must be FASTQ, and the same records are written as FASTQ, the quality
+    line cut wherever the sequence line is (Counter.fastq_select applies the kept lengths to the raw text); "bytes_out"
+    counts those bytes.  The FASTA output of the deciding call is computed and thrown away; the TSV is unchanged."""
+    if fastq_out:
+        is_paired = _is_paired(paired, mate_file, out_path2, singles_path)
+        raw, text = _fastq_texts("trim_reads", file, mate_file)
+        info = {}
+        if is_paired:
+            _, _, keep, kept, _ = table.trim_pairs(text, at_least, min_len, singles=singles_path is not None, info=info)
+        else:
+            keep = None
+            _, kept, _ = table.trim(text, at_least, min_len, info=info)
+        if tsv_path is not None:
+            from .report import write_trim_tsv
+            if is_paired:
+                write_trim_tsv(tsv_path, record_names(text), record_lengths(text), kept, keep)
+            else:
+                write_trim_tsv(tsv_path, record_names(text), record_lengths(text), kept)
+        done = {"records": int(kept.shape[0]), "kept": int(info["records_out"]), "trimmed": int(info["records_trimmed"]),
+                "dropped": int(info["records_dropped"]), "bases_in": int(info["bases_in"]), "bases_out": int(info["bases_out"]),
+                "bytes_out": _write_fastq(table, raw, keep, kept, out_path, out_path2, singles_path)}
+        if is_paired:
+            done.update({"pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]), "singles": int(info["singles_out"])})
+        return done
     if _is_paired(paired, mate_file, out_path2, singles_path):
         text = _pairs_text(file, mate_file)
         info: Dict[str, int] = {}
@@ -355,7 +429,8 @@ def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: U
     first converted as MerCat2's fq2fa converts it (mk_fq2fa) -- so the output is always FASTA, the records byte for byte
     and in order, and the qualities are gone.  A canonical table folds the windows.  Returns {"records", "kept", "short",
     "low", "over", "thinned", "bytes_out"} ("kept": the records written).  With ``tsv_path`` every record's name,
-    k-mers, depth and fate are written there too (report.write_norm_tsv).  Paired reads: normalize_read_pairs."""
+    k-mers, depth and fate are written there too (report.write_norm_tsv).  Paired reads: normalize_read_pairs.  FASTQ
+    out, with the qualities: normalize_reads_fastq."""
     text = read_fasta_bytes(file)
     if str(file).lower().endswith(FASTQ_SUFFIXES):
         text, _ = native.fq2fa(text)
@@ -375,17 +450,48 @@ def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: U
             "bytes_out": len(out)}
 
 
+def normalize_reads_fastq(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], target: int = 20,
+                          min_depth: int = 0, seed: int = 0, invert: bool = False, tsv_path: Union[str, Path, None] = None) -> Dict[str, int]:
+    """normalize_reads with FASTQ out (what ``fastq_out=True`` is to filter_reads, trim_reads and normalize_read_pairs;
+    normalize_reads keeps the arguments it has).  The input must be FASTQ, and the records normalize_reads would write are
+    written as FASTQ, qualities included, byte for byte (Counter.fastq_select applies the decision to the raw text);
+    "bytes_out" counts those bytes.  The FASTA output of the deciding call is computed and thrown away; the figures and
+    the TSV are normalize_reads'."""
+    raw, text = _fastq_texts("normalize_reads_fastq", file)
+    info: Dict[str, int] = {}
+    _, keep, med, rows = table.normalize(text, target, min_depth, seed, invert, info=info)
+    if tsv_path is not None:
+        from .report import write_norm_tsv
+        write_norm_tsv(tsv_path, record_names(text), rows[:, 0], med, keep)
+    return {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "short": int(info["records_short"]),
+            "low": int(info["records_low"]), "over": int(info["records_over"]), "thinned": int(info["records_thinned"]),
+            "bytes_out": _write_fastq(table, raw, keep, None, out_path)}
+
+
 def normalize_read_pairs(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], target: int = 20,
                          min_depth: int = 0, seed: int = 0, invert: bool = False, tsv_path: Union[str, Path, None] = None,
                          mate_file: Union[str, Path, None] = None, out_path2: Union[str, Path, None] = None,
-                         singles_path: Union[str, Path, None] = None) -> Dict[str, int]:
+                         singles_path: Union[str, Path, None] = None, fastq_out: bool = False) -> Dict[str, int]:
     """normalize_reads for paired reads (the paired form of filter_reads and trim_reads is an argument of theirs;
     normalize_reads keeps the arguments it has).  ``file`` is interleaved, or -- with ``mate_file`` -- the first of two
     files that are read as normalize_reads reads one and interleaved on the host.  The pair is the unit
     (Counter.normalize_pairs): its depth is that of its shallowest mate that has k-mers and reaches ``min_depth``, its
     draw that of its first mate.  The output is interleaved in ``out_path``, or split into ``out_path`` and
     ``out_path2``; normalisation has no orphans, so a ``singles_path`` is written empty.  Returns normalize_reads' figures
-    ("kept": the records written) and {"pairs", "pairs_kept", "singles"}; the TSV gains the column ``pair``."""
+    ("kept": the records written) and {"pairs", "pairs_kept", "singles"}; the TSV gains the column ``pair``.
+    ``fastq_out``: FASTQ in (the mate file too), the same records out as FASTQ with their qualities (Counter.fastq_select
+    applies the decision to the raw text); the FASTA output of the deciding call is computed and thrown away."""
+    if fastq_out:
+        raw, text = _fastq_texts("normalize_read_pairs", file, mate_file)
+        info = {}
+        _, _, keep, med, rows = table.normalize_pairs(text, target, min_depth, seed, invert, info=info)
+        if tsv_path is not None:
+            from .report import write_norm_tsv
+            write_norm_tsv(tsv_path, record_names(text), rows[:, 0], med, keep, paired=True)
+        return {"records": int(keep.shape[0]), "kept": int(info["records_out"]), "short": int(info["records_short"]),
+                "low": int(info["records_low"]), "over": int(info["records_over"]), "thinned": int(info["records_thinned"]),
+                "bytes_out": _write_fastq(table, raw, keep, None, out_path, out_path2, singles_path),
+                "pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]), "singles": int(info["singles_out"])}
     text = _pairs_text(file, mate_file)
     info: Dict[str, int] = {}
     out, _, keep, med, rows = table.normalize_pairs(text, target, min_depth, seed, invert, info=info)

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_correct_text", "mk_correct_device",
     "mk_norm_text", "mk_norm_device",
     "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
+    "mk_fastq_select_text", "mk_fastq_select_device", "mk_fastq_cuts", "mk_fq_interleave", "mk_fq_split_pairs",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -248,6 +249,15 @@ class Pairs(C.Structure):
         return d
 
 
+class FastqSelect(C.Structure):
+    """mk_fastq_select_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("records", "records_out", "records_trimmed", "bases_out", "bytes_out", "lines")] +
+                [(n, C.c_double) for n in ("s_copy", "s_index", "s_place", "s_gather", "s_write")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def ppm_of_fraction(min_frac: float) -> int:
     """min_ppm of mk_filter_rule_t for "at least this fraction of the record's k-mers are hits": round(min_frac * 10^6);
     ValueError outside 0..1 (and for a NaN)."""
@@ -436,6 +446,13 @@ def lib() -> C.CDLL:
         "mk_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_host_error": (C.c_char_p, []),
+        "mk_fastq_select_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint,
+                                           C.c_void_p, C.c_size_t, szp, C.POINTER(FastqSelect)]),
+        "mk_fastq_select_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint,
+                                             C.c_void_p, C.c_size_t, szp, C.POINTER(FastqSelect)]),
+        "mk_fastq_cuts": (C.c_int, [u8p, C.c_size_t, C.c_uint64, u64p, C.c_size_t, szp]),
+        "mk_fq_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
+        "mk_fq_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
     }
     L.mk_version.restype = C.c_char_p
     ver = (L.mk_version() or b"").decode()
@@ -561,6 +578,61 @@ def split_pairs(text) -> Tuple[bytes, bytes]:
     if rc:
         raise _host_error(rc, "mk_split_pairs")
     return o1[: l1.value].tobytes(), o2[: l2.value].tobytes()
+
+
+def interleave_fastq(a, b) -> bytes:
+    """mk_fq_interleave: record i of FASTQ text ``a``, then record i of ``b`` (the R1 / R2 files of paired reads), on the
+    host.  Records are the 4-line records of Counter.fastq_select; a last record without a newline gets one.
+    MercatHipError (MK_ERR_RANGE) when the texts hold different numbers of records, (MK_ERR_UNSUPPORTED) when one ends
+    inside a record."""
+    L = lib()
+    a1, n1, k1 = _buf_ptr(a)
+    a2, n2, k2 = _buf_ptr(b)
+    out = np.empty(n1 + n2 + 2, dtype=np.uint8)
+    out_len, pairs = C.c_size_t(0), C.c_size_t(0)
+    rc = L.mk_fq_interleave(a1, n1, a2, n2, out.ctypes.data, out.size, C.byref(out_len), C.byref(pairs))
+    if rc:
+        raise _host_error(rc, "mk_fq_interleave")
+    return out[: out_len.value].tobytes()
+
+
+def split_pairs_fastq(text) -> Tuple[bytes, bytes]:
+    """mk_fq_split_pairs: (records 0, 2, 4, ...; records 1, 3, 5, ...) of an interleaved FASTQ text, on the host.
+    MercatHipError (MK_ERR_RANGE) for an odd number of records."""
+    L = lib()
+    addr, n, keep = _buf_ptr(text)
+    o1, o2 = np.empty(n + 1, dtype=np.uint8), np.empty(n + 1, dtype=np.uint8)
+    l1, l2, pairs = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    rc = L.mk_fq_split_pairs(addr, n, o1.ctypes.data, n + 1, C.byref(l1), o2.ctypes.data, n + 1, C.byref(l2), C.byref(pairs))
+    if rc:
+        raise _host_error(rc, "mk_fq_split_pairs")
+    return o1[: l1.value].tobytes(), o2[: l2.value].tobytes()
+
+
+def fastq_cuts(text, piece: int) -> np.ndarray:
+    """Where Counter.fastq_select cuts a FASTQ text into pieces (mk_fastq_cuts): behind a line 4j once a piece holds
+    ``piece`` bytes."""
+    L = lib()
+    addr, n, keep = _buf_ptr(text)
+    need = C.c_size_t(0)
+    cap = 64
+    while True:
+        cuts = np.empty(cap, dtype=np.uint64)
+        rc = L.mk_fastq_cuts(addr, n, int(piece), cuts.ctypes.data, cap, C.byref(need))
+        if rc == MK_OK:
+            return cuts[: need.value].copy()
+        if rc != -7:
+            raise MercatHipError(rc, "mk_fastq_cuts")
+        cap = need.value
+
+
+def _select_arrays(keep, kept) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], int]:
+    """keep as uint8, kept as uint64 (each or both None) and the number of records they speak of (-1: neither given)."""
+    keep = None if keep is None else np.ascontiguousarray(np.asarray(keep).astype(np.uint8, copy=False)).reshape(-1)
+    kept = None if kept is None else np.ascontiguousarray(np.asarray(kept).astype(np.uint64, copy=False)).reshape(-1)
+    if keep is not None and kept is not None and len(keep) != len(kept):
+        raise ValueError("keep speaks of %d records, kept of %d" % (len(keep), len(kept)))
+    return keep, kept, (len(keep) if keep is not None else len(kept) if kept is not None else -1)
 
 
 def textwrap_lines(text, width: int = 80) -> list:
@@ -1189,6 +1261,50 @@ class Counter:
         self._check(self._L.mk_filter_device(self._h, ptr, int(nbytes), self._filter_flags(fold, invert), C.byref(rule), out_ptr or None,
                                              int(out_cap), C.byref(out_len), rows_ptr or None, keep_ptr or None, int(cap), C.byref(n),
                                              C.byref(st)))
+        return st.as_dict()
+
+    # -- a decision applied to the FASTQ text it was taken for: the kept records out with their qualities; no table is read
+    def _check_select(self, rc: int):
+        if rc:
+            msg = self._L.mk_last_error(self._h)
+            raise MercatHipError(rc, msg.decode() if msg else "")
+
+    def fastq_select(self, path_or_bytes, keep=None, kept=None, which: int = 1, piece_bytes: int = 0,
+                     info: Optional[dict] = None) -> bytes:
+        """mk_fastq_select_text: the records of the FASTQ text (a path to a plain file, or the text itself as bytes) that a
+        decision keeps, as FASTQ.  ``keep``: one value per record (Counter.filter's / normalize's booleans, Counter.pairs'
+        0 / 1 / 2), a record is emitted iff keep[r] == ``which`` (1: the main output, 2: the orphans).  ``kept``: one
+        length per record (Counter.trim's), a record is emitted iff kept[r] > 0, its sequence and quality lines cut to
+        kept[r] bytes.  Either may be None; with both None the text is validated and copied.  The arrays are coerced to
+        uint8 / uint64 and must speak of exactly the text's 4-line records.  MercatHipError: MK_ERR_UNSUPPORTED for a
+        malformed record (the message names it), MK_ERR_RANGE for another record count or a kept[r] longer than its read.
+        ``info``, if given, receives the mk_fastq_select_t fields."""
+        keep, kept, nrec = _select_arrays(keep, kept)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        if nrec < 0:  # (neither array: the text's own count -- lines split on '\n', a last line without one is a line)
+            nl = int(np.count_nonzero(held == 10)) if size else 0
+            nrec = (nl + (1 if size and held[-1] != 10 else 0)) // 4
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        out_len, st = C.c_size_t(0), FastqSelect()
+        self._check_select(self._L.mk_fastq_select_text(
+            self._h, addr, size, int(piece_bytes), keep.ctypes.data if keep is not None else None,
+            kept.ctypes.data if kept is not None else None, nrec, int(which), out.ctypes.data, size + 1, C.byref(out_len), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes()
+
+    def fastq_select_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, nrec: int, keep_ptr: int = 0, kept_ptr: int = 0,
+                            which: int = 1) -> dict:
+        """mk_fastq_select_device: ``nbytes`` of FASTQ text (``nrec`` whole records) at device address ``ptr`` -> the
+        emitted records at device address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) under one
+        keep byte a record at ``keep_ptr`` and one uint64 length a record at ``kept_ptr`` (aligned to 8), each optional
+        -- all on this context's GPU.  Returns the mk_fastq_select_t fields: "bytes_out" bytes were written."""
+        out_len, st = C.c_size_t(0), FastqSelect()
+        self._check_select(self._L.mk_fastq_select_device(self._h, ptr, int(nbytes), keep_ptr or None, kept_ptr or None, int(nrec),
+                                                          int(which), out_ptr or None, int(out_cap), C.byref(out_len), C.byref(st)))
         return st.as_dict()
 
     # -- tracking: FASTA text in, the count under every window out (and the median a record); the table is only read
