@@ -40,7 +40,8 @@ extern "C" {
                                  mk_fastq_select_* / mk_fq_interleave / mk_fq_split_pairs: a FASTQ record is malformed (its
                                  first line lacks the '@', its third the '+', its sequence and quality lines differ in
                                  length, its sequence line holds a blank or '*' while kept[] is given, or the text ends
-                                 inside it); the message names the record and the check, nothing was written */
+                                 inside it); the message names the record and the check, nothing was written.
+                                 mk_correct_fastq_*: the same, and a sequence line the parser reads differently */
 
 /* Alphabets select the packed fast path; they never restrict the input.  Windows holding a
  * symbol outside the alphabet are still counted, exactly, by the by-reference kernel
@@ -593,6 +594,60 @@ int mk_correct_text(mk_ctx* ctx, const uint8_t* text, size_t n, size_t piece_byt
 int mk_correct_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags, const mk_correct_rule_t* rule,
                       uint8_t* d_out, size_t out_cap, size_t* out_len, mk_correct_row_t* d_fix, mk_screen_row_t* d_rows, size_t cap,
                       size_t* nrows, mk_correct_t* st);
+
+/* ---- FASTQ in, the same FASTQ out with the correction above applied and the qualities kept: the text is read on the
+ *      device as it stands, and because every record is emitted and a fix replaces one byte by one byte, the output is
+ *      the input with at most one byte per fixed run changed (what Lighter, Musket and BFC hand to an assembler, a mapper
+ *      or a second correction pass) ----
+ * Lines and records are mk_fastq_select_*'s, word for word: lines are split on '\n' only and numbered across the whole
+ * text, a last line without '\n' is a line, record r is lines 4r .. 4r + 3, and the up to 3 lines behind the last
+ * complete record are tolerated only if they are all empty (otherwise the text ends inside a record).  *nrows is the
+ * number of records.
+ * Record checks, on the device, for every record, before anything is parsed; a failure is MK_ERR_UNSUPPORTED and the
+ * message names the lowest failing record, numbered over the whole call, and the first check it fails, in this order:
+ *   line 4r starts with '@';  line 4r + 2 starts with '+';
+ *   the sequence line 4r + 1 and the quality line 4r + 3 are equally long, one trailing '\r' not counted on either;
+ *   the sequence line, without its trailing '\r', holds no '*' and none of the bytes str.strip() removes.
+ * Rule: the FASTA view of the text is mk_fq2fa's -- here the text copied on the device and rewritten in place ('@' of
+ * line 4r made '>', every byte of lines 4r + 2 and 4r + 3 made '\n', nothing moved) -- and mk_correct_*'s rule is
+ * applied to that view, word for word: fix, rows, MK_CORRECT_FOLD, the context restrictions (MK_ERR_ARG), MK_ERR_STATE
+ * and MK_ERR_NON_ASCII are as there, and fix[r] and rows[r] are exactly what mk_correct_text returns for
+ * mk_fq2fa(text).  st->correct is filled as there for the view, with bytes_out = n, preamble = 0 and s_gather = 0.
+ * View check: after the parse it is checked, per record, that the parser found exactly the text's records, each where
+ * its header line starts, and counted as record r's characters exactly the bytes of its sequence line.  A sequence line
+ * that the parser reads differently -- one that starts with '>', say, is a header line of the view -- is
+ * MK_ERR_UNSUPPORTED; the message names the lowest such record, or gives both record counts when only they differ.
+ * Nothing is patched before this check has been read back clean.
+ * Output: the n input bytes as they stand -- CR LF stays, a last record without '\n' stays open, trailing lines stay --
+ * but for every FIXED run the byte of its p, at offset p of the sequence line, is the fixing base, and where
+ * rule->new_qual != 0 the byte at the same offset of the quality line is new_qual (Lighter's -newQual).  st->patched
+ * counts the sequence bytes changed (= st->correct.fixed).  *out_len = n on success; on any error 0, except that
+ * out_cap < n is MK_ERR_RANGE with *out_len = n, decided before any work (out = NULL, out_cap = 0 is the sizing call)
+ * and that cap below the record count is MK_ERR_RANGE with *out_len = n and the count in *nrows, as for mk_correct_*.
+ * at_least >= 1, reserved == 0, new_qual 0 or in 33..126; a NULL rule, a value out of range or an unknown flag bit is
+ * MK_ERR_ARG.  The table is only read; the counting figures, the export and what mk_fastq_stats reports stay untouched.
+ * mk_correct_fastq_text: host memory in and out; pieces end behind a line 4j once they hold piece_bytes (mk_fastq_cuts;
+ * 0: the default, and the limits, of the screen calls).  out is written once, after the last piece has passed its
+ * checks: on an error it holds what it held.  Output, fix, rows and messages do not depend on piece_bytes for a text
+ * with at most one kind of fault; of a malformed record, a sequence line the parser reads differently and a byte
+ * >= 0x80 in different records, the one in the earliest piece is reported, so which it is may depend on piece_bytes.
+ * mk_correct_fastq_device: everything in DEVICE memory of the context's GPU, one piece; text and out at any address,
+ * d_fix and d_rows aligned to 8.  d_out == d_fastq corrects in place; any other overlap is MK_ERR_ARG.  d_out is not
+ * written before every check has passed. */
+typedef struct mk_correct_fastq_rule_t { uint64_t at_least; uint32_t new_qual; uint32_t reserved; } mk_correct_fastq_rule_t;
+typedef struct mk_correct_fastq_t {
+  mk_correct_t correct;                 /* as mk_correct_* fills it for the FASTA view of the same text */
+  uint64_t lines, patched;              /* lines of the text; bytes changed in sequence lines (= correct.fixed) */
+  /* seconds: host time in the copies to the device; HIP-event time of the line index and the record checks; of the view
+   * check and the patch */
+  double s_copy, s_index, s_patch;
+} mk_correct_fastq_t;
+int mk_correct_fastq_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes, unsigned flags,
+                          const mk_correct_fastq_rule_t* rule, uint8_t* out, size_t out_cap, size_t* out_len, mk_correct_row_t* fix,
+                          mk_screen_row_t* rows, size_t cap, size_t* nrows, mk_correct_fastq_t* st);
+int mk_correct_fastq_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, unsigned flags, const mk_correct_fastq_rule_t* rule,
+                            uint8_t* d_out, size_t out_cap, size_t* out_len, mk_correct_row_t* d_fix, mk_screen_row_t* d_rows,
+                            size_t cap, size_t* nrows, mk_correct_fastq_t* st);
 
 /* ---- sequences in, the reads thinned to a target depth out: digital normalisation by the median mk_track_* computes,
  *      decided and applied where the counts are (BBNorm's plan with khmer's normalize-by-median depth; with abundance

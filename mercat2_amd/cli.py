@@ -30,7 +30,10 @@ trim_<type>/<sample>_trim.tsv with every record's length and what it keeps.  -co
 sample, correct_<type>/<sample>_corrected.fna: every record of FILE with the single wrong bases put right that the sample's
 table can name -- a run of k-mers held fewer than -correct_min times, shaped as one substitution shapes it, and exactly one
 base that makes them all solid (mk_correct_text) -- and correct_<type>/<sample>_correct.tsv with every record's runs and what
-became of them; -correct_mate FILE2 corrects two files of mates together and writes ..._1 and ..._2.  -norm FILE writes, for every sample of FILE's
+became of them; -correct_mate FILE2 corrects two files of mates together and writes ..._1 and ..._2; -correct_fastq reads a
+FASTQ FILE on the GPU as it stands and writes correct_<type>/<sample>_corrected.fastq, the same text with the fixed bases and
+the qualities where they were (mk_correct_fastq_text), -correct_qual C writing C over the quality of every fixed base.
+-norm FILE writes, for every sample of FILE's
 type, norm_<type>/<sample>_<kept|tossed>.fna (.faa): the records of FILE thinned to depth -norm_target by the median of their
 k-mers' counts in the sample's table -- digital normalisation, BBNorm's count-first plan with khmer's depth (mk_norm_text) --
 and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  Paired reads: with -paired the FILE of
@@ -151,6 +154,13 @@ def parseargs(argv=None):
     p.add_argument("-correct_mate", type=str, default=None, metavar="FILE2",
                    help="-correct: the second file of paired reads (FILE the first); every record is written, to "
                         "..._corrected_1 and ..._corrected_2")
+    p.add_argument("-correct_fastq", action="store_true",
+                   help="-correct: FILE (and -correct_mate FILE2) is FASTQ and is written as FASTQ, byte for byte but for the "
+                        "corrected bases, the qualities kept: correct_<type>/<sample>_corrected.fastq (..._corrected_1.fastq and "
+                        "..._corrected_2.fastq with a mate) beside the same _correct.tsv (mk_correct_fastq_text)")
+    p.add_argument("-correct_qual", type=str, default=None, metavar="C",
+                   help="-correct_fastq: the quality character written under every corrected base, one of '!'..'~' "
+                        "(Lighter's -newQual) [the qualities stay]")
     p.add_argument("-norm", type=str, required=False, metavar="FILE",
                    help="a FASTA or FASTQ file (plain or .gz) of reads to thin against the tables on the GPU (digital "
                         "normalisation; the table should have been counted from these reads): for every sample of FILE's type, "
@@ -283,9 +293,11 @@ def parseargs(argv=None):
         args.trim_len = args.trim_len or 0  # (0: the k-mer length)
     args.correct_kind = None
     if not args.correct:
-        for flag in ("correct_min", "correct_rounds", "correct_mate"):
+        for flag in ("correct_min", "correct_rounds", "correct_mate", "correct_qual"):
             if getattr(args, flag) is not None:
                 p.error(f"-{flag} needs -correct FILE")
+        if args.correct_fastq:
+            p.error("-correct_fastq needs -correct FILE")
     else:
         if not os.path.isfile(args.correct):
             p.error(f"file '{args.correct}' is not valid.\n")
@@ -307,6 +319,16 @@ def parseargs(argv=None):
                 p.error(f"file '{args.correct_mate}' is not valid.\n")
             if classify(Path(args.correct_mate).expanduser().absolute(), True)[0] != args.correct_kind:
                 p.error(f"-correct_mate {args.correct_mate}: not the type of -correct {args.correct}")
+        if args.correct_fastq:
+            for f in (args.correct, args.correct_mate):
+                if f is not None and not str(f).lower().endswith(tuple(FILE_EXT_FASTQ)):
+                    p.error(f"-correct_fastq with {f}: not a FASTQ file ({' / '.join(FILE_EXT_FASTQ)}); there are no qualities "
+                            "to keep")
+        if args.correct_qual is not None:
+            if not args.correct_fastq:
+                p.error("-correct_qual needs -correct_fastq")
+            if len(args.correct_qual) != 1 or not "!" <= args.correct_qual <= "~":
+                p.error(f"-correct_qual {args.correct_qual!r}: one printable character in '!'..'~'")
     args.norm_kind = None
     if not args.norm:
         for flag in ("norm_target", "norm_min", "norm_seed", "norm_keep"):
@@ -814,13 +836,22 @@ def main(argv=None) -> int:
                           f"{len(tables)} sample(s), records written (of them cut): " +
                           ", ".join(f"{base} {n} ({t})" for base, (n, t) in kept.items()))
                 if args.correct and args.correct_kind == kind:  # from the tables still on the GPU
-                    from .kmers import correct_reads
+                    from .kmers import correct_reads, correct_reads_fastq
                     folder = out / f"correct_{kind}"
                     folder.mkdir(parents=True, exist_ok=True)
                     fixed = {}
                     for base in sorted(tables):
                         mate = args.correct_mate
                         try:
+                            if args.correct_fastq:
+                                res = correct_reads_fastq(tables[base], args.correct,
+                                                          folder / (f"{base}_corrected_1.fastq" if mate else f"{base}_corrected.fastq"),
+                                                          at_least=args.correct_min, rounds=args.correct_rounds,
+                                                          tsv_path=folder / f"{base}_correct.tsv", mate_file=mate,
+                                                          out_path2=folder / f"{base}_corrected_2.fastq" if mate else None,
+                                                          new_qual=args.correct_qual or 0)
+                                fixed[base] = (res["fixed"], res["runs"])
+                                continue
                             res = correct_reads(tables[base], args.correct, folder / (f"{base}_corrected_1.fna" if mate else f"{base}_corrected.fna"),
                                                 at_least=args.correct_min, rounds=args.correct_rounds,
                                                 tsv_path=folder / f"{base}_correct.tsv", mate_file=mate,

@@ -418,6 +418,54 @@ def correct_reads(table: "native.Counter", file: Union[str, Path], out_path: Uni
             "bases": int(sum(lengths)), "bytes_out": len(text)}
 
 
+def correct_reads_fastq(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], at_least: int = 2, rounds: int = 1,
+                        tsv_path: Union[str, Path, None] = None, mate_file: Union[str, Path, None] = None,
+                        out_path2: Union[str, Path, None] = None, new_qual=0) -> Dict[str, int]:
+    """correct_reads with FASTQ out, qualities included (correct_reads keeps the arguments it has).  The input -- and the
+    mate -- must be FASTQ ('.gz' inflated on the host); the text is read on the GPU as it stands (Counter.correct_fastq)
+    and written back byte for byte but for the fixed bases, so the FASTA output is never built.  ``new_qual`` (an int,
+    or one character; 0: none) is written over the quality of every fixed base.  ``rounds`` > 1 corrects the FASTQ
+    output again.  With ``mate_file`` the two files are interleaved on the host (native.interleave_fastq), corrected in
+    one call and split again (native.split_pairs_fastq) into ``out_path`` and ``out_path2`` (interleaved in ``out_path``
+    without the latter).  The returned figures and the TSV are correct_reads' for the same file: names and lengths are
+    those of the FASTA view mk_fq2fa gives of the reads; "bytes_out" counts the FASTQ bytes.  ValueError for input
+    without a FASTQ suffix; MercatHipError (MK_ERR_UNSUPPORTED) for a malformed record."""
+    if rounds < 1:
+        raise ValueError("correct_reads_fastq: rounds must be 1 or more")
+    if mate_file is None and out_path2 is not None:
+        raise ValueError("correct_reads_fastq: out_path2 goes with mate_file only")
+    for f in (file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("correct_reads_fastq: needs FASTQ input (%s), not %s" % (" / ".join(FASTQ_SUFFIXES), f))
+    qual = native.quality_byte(new_qual)
+    if qual and not 33 <= qual <= 126:
+        raise ValueError("correct_reads_fastq: new_qual %r is no printable quality character ('!'..'~')" % (new_qual,))
+    raw = read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    first, _ = native.fq2fa(raw)
+    fix = None
+    for _ in range(rounds):
+        raw, step, _ = table.correct_fastq(raw, at_least, qual)
+        if fix is None:
+            fix = step.copy()
+        else:
+            fix[:, 1:] += step[:, 1:]
+    if mate_file is None or out_path2 is None:
+        _write_reads(out_path, raw)
+    else:
+        one, two = native.split_pairs_fastq(raw)
+        _write_reads(out_path, one)
+        _write_reads(out_path2, two)
+    lengths = record_lengths(first)
+    if tsv_path is not None:
+        from .report import write_correct_tsv
+        write_correct_tsv(tsv_path, record_names(first), lengths, fix)
+    total = [int(v) for v in fix.sum(axis=0, dtype="uint64")]
+    return {"records": int(fix.shape[0]), "runs": total[0], "fixed": total[1], "ambiguous": total[2], "unfixable": total[3],
+            "bases": int(sum(lengths)), "bytes_out": len(raw)}
+
+
 def normalize_reads(table: "native.Counter", file: Union[str, Path], out_path: Union[str, Path], target: int = 20,
                     min_depth: int = 0, seed: int = 0, invert: bool = False, tsv_path: Union[str, Path, None] = None) -> Dict[str, int]:
     """The records of a FASTA or FASTQ file thinned to depth ``target`` against a table still on the GPU that has been

@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
     "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_correct_text", "mk_correct_device",
-    "mk_norm_text", "mk_norm_device",
+    "mk_correct_fastq_text", "mk_correct_fastq_device", "mk_norm_text", "mk_norm_device",
     "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
     "mk_fastq_select_text", "mk_fastq_select_device", "mk_fastq_cuts", "mk_fq_interleave", "mk_fq_split_pairs",
 ]
@@ -210,6 +210,33 @@ class Correct(C.Structure):
         d = self.screen.as_dict()
         d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
         return d
+
+
+class CorrectFastqRule(C.Structure):
+    """mk_correct_fastq_rule_t (include/mercat_hip.h)."""
+    _fields_ = [("at_least", C.c_uint64), ("new_qual", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CorrectFastq(C.Structure):
+    """mk_correct_fastq_t (include/mercat_hip.h)."""
+    _fields_ = ([("correct", Correct)] + [(n, C.c_uint64) for n in ("lines", "patched")] +
+                [(n, C.c_double) for n in ("s_copy", "s_index", "s_patch")])
+
+    def as_dict(self):
+        d = self.correct.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
+        return d
+
+
+def quality_byte(new_qual) -> int:
+    """new_qual of mk_correct_fastq_rule_t from an int or a one-character str / bytes (0: the qualities stay)."""
+    if isinstance(new_qual, str):
+        new_qual = new_qual.encode("latin-1")
+    if isinstance(new_qual, (bytes, bytearray)):
+        if len(new_qual) != 1:
+            raise ValueError("new_qual %r: one character" % (new_qual,))
+        return new_qual[0]
+    return int(new_qual)
 
 
 class NormRule(C.Structure):
@@ -432,6 +459,10 @@ def lib() -> C.CDLL:
                                       C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Correct)]),
         "mk_correct_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(CorrectRule), C.c_void_p, C.c_size_t, szp,
                                         C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Correct)]),
+        "mk_correct_fastq_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(CorrectFastqRule), C.c_void_p,
+                                            C.c_size_t, szp, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(CorrectFastq)]),
+        "mk_correct_fastq_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(CorrectFastqRule), C.c_void_p, C.c_size_t,
+                                              szp, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(CorrectFastq)]),
         "mk_norm_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Norm)]),
         "mk_norm_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(NormRule), C.c_void_p, C.c_size_t, szp,
@@ -1438,6 +1469,54 @@ class Counter:
         self._check(self._L.mk_correct_device(self._h, ptr, int(nbytes), CORRECT_FOLD if self._fold_flag(fold) else 0,
                                               C.byref(rule), out_ptr or None, int(out_cap), C.byref(out_len), fix_ptr or None,
                                               rows_ptr or None, int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
+    # -- correcting FASTQ: the text in, the same text out with the fixes in its sequence lines and the qualities kept
+    def _check_correct_fastq(self, rc: int):
+        if rc:
+            msg = self._L.mk_last_error(self._h)
+            raise (NonAsciiInput if rc == -5 else MercatHipError)(rc, msg.decode() if msg else "")
+
+    def correct_fastq(self, path_or_bytes, at_least: int = 2, new_qual=0, fold: Optional[bool] = None, piece_bytes: int = 0,
+                      info: Optional[dict] = None):
+        """mk_correct_fastq_text: (out, fix, rows) of the FASTQ text (a path to a plain file, or the text itself as bytes).
+        ``out`` is the text byte for byte -- CR LF, an open last record and trailing empty lines included -- but for the
+        base of every run Counter.correct would fix in the FASTA view native.fq2fa gives of it; ``fix`` and ``rows`` are
+        Counter.correct's for that view.  ``new_qual`` (an int, or one character as str or bytes; 0: none) is written
+        over the quality of every fixed base.  MercatHipError: MK_ERR_UNSUPPORTED for a malformed record or a sequence
+        line the parser reads differently (the message names the record).  Nucleotide contexts with k <= 64 only.
+        ``fold`` None: fold iff the context is canonical.  ``info``, if given, receives the mk_correct_fastq_t fields
+        (those of mk_correct_t and mk_screen_t beside them)."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        nl = int(np.count_nonzero(held == 10)) if size else 0
+        cap = (nl + 1) // 4 + 1  # (a record is four lines; a last line without '\n' is a line)
+        rows = np.zeros((cap, len(SCREEN_COLUMNS)), dtype=np.uint64)
+        fix = np.zeros((cap, len(CORRECT_COLUMNS)), dtype=np.uint32)
+        out = np.empty(max(size, 1), dtype=np.uint8)
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), CorrectFastq()
+        rule = CorrectFastqRule(int(at_least), quality_byte(new_qual), 0)
+        self._check_correct_fastq(self._L.mk_correct_fastq_text(
+            self._h, addr, size, int(piece_bytes), CORRECT_FOLD if self._fold_flag(fold) else 0, C.byref(rule), out.ctypes.data,
+            size, C.byref(out_len), fix.ctypes.data, rows.ctypes.data, cap, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), fix[: n.value], rows[: n.value]
+
+    def correct_fastq_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, fix_ptr: int = 0, rows_ptr: int = 0,
+                             cap: int = 0, at_least: int = 2, new_qual=0, fold: Optional[bool] = None) -> dict:
+        """mk_correct_fastq_device: ``nbytes`` of FASTQ text at device address ``ptr`` -> the corrected text (``nbytes``
+        bytes) at device address ``out_ptr`` (room for ``out_cap``; ``out_ptr`` == ``ptr`` corrects in place, any other
+        overlap is refused) and, where given, four uint32 a record at ``fix_ptr`` and the rows (five uint64 a record) at
+        ``rows_ptr`` with room for ``cap`` records each -- all on this context's GPU, the last two aligned to 8.  Returns
+        the mk_correct_fastq_t fields: "bytes_out" bytes were written, "records" rows."""
+        n, out_len, st = C.c_size_t(0), C.c_size_t(0), CorrectFastq()
+        rule = CorrectFastqRule(int(at_least), quality_byte(new_qual), 0)
+        self._check_correct_fastq(self._L.mk_correct_fastq_device(
+            self._h, ptr, int(nbytes), CORRECT_FOLD if self._fold_flag(fold) else 0, C.byref(rule), out_ptr or None, int(out_cap),
+            C.byref(out_len), fix_ptr or None, rows_ptr or None, int(cap), C.byref(n), C.byref(st)))
         return st.as_dict()
 
     # -- normalising: FASTA text in, the records thinned to a target depth out; the table is only read
