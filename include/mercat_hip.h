@@ -57,7 +57,7 @@ typedef struct mk_stats_t {
   uint64_t raw_bytes;      /* FASTA bytes fed                                               */
   uint64_t symbols;        /* sequence characters kept by the parser (the "bases")          */
   uint64_t windows;        /* length-k windows counted (all paths)                          */
-  uint64_t exotic_windows; /* of those, windows counted by the by-reference path            */
+  uint64_t exotic_windows; /* of those, windows no packed kernel takes: counted byte-wise    */
   uint64_t chunks;         /* chunks ended                                                  */
   uint64_t survivors;      /* chunk-table entries that passed their chunk's min_count       */
   uint64_t rows;           /* distinct k-mers now in the running (merged) table             */

@@ -57,7 +57,7 @@ struct MkChunkInfo {
   unsigned long long non_ascii;     // kept (sequence) bytes >= 0x80; header lines may hold any bytes
   unsigned long long bad_symbols;   // kept characters outside the alphabet
   unsigned long long windows;       // windows counted by the packed/dense path
-  unsigned long long exotic;        // windows counted by the by-reference path
+  unsigned long long exotic;        // windows counted by mk_count_byref_k: those no packed kernel takes (a character outside the alphabet; every window in MK_MODE_BYREF)
   unsigned long long survivors;     // packed entries passing min_count (this chunk)
   unsigned long long survivors_ref; // by-reference entries passing min_count
   unsigned long long side;          // count of the one key that equals MK_EMPTY (all-T 32-mer)

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void mk_count_ref128_k(const u64* __restrict__
       }
     }
   }
-  add_windows(info, mine, true);
+  add_windows(info, mine, false);  // (packed windows: `exotic` is for the windows mk_count_byref_k takes)
 }
 
 // The same for amino acids (13 <= k <= 25): one thread per packed word = 12 window starts.
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void mk_count_ref128aa_k(const u64* __restrict
       ++mine;
     }
   }
-  add_windows(info, mine, true);
+  add_windows(info, mine, false);
 }
 
 int mk_launch_count_ref128(mk_ctx* c, size_t seq_len) {
