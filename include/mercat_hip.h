@@ -37,7 +37,7 @@ extern "C" {
 #define MK_ERR_UNSUPPORTED (-8) /* clean mode (mk_set_clean): the chunk holds text whose rewrite by removeN the GPU does not
                                  reproduce (a blank inside a sequence line, a '>' that does not start a header line, a
                                  0x7F byte); nothing of the chunk was counted -- count the text mk_remove_n produces instead.
-                                 mk_fastq_select_* / mk_fq_interleave / mk_fq_split_pairs: a FASTQ record is malformed (its
+                                 mk_fastq_select_* / mk_fastq_qtrim_* / mk_fq_interleave / mk_fq_split_pairs: a FASTQ record is malformed (its
                                  first line lacks the '@', its third the '+', its sequence and quality lines differ in
                                  length, its sequence line holds a blank or '*' while kept[] is given, or the text ends
                                  inside it); the message names the record and the check, nothing was written.
@@ -843,6 +843,60 @@ int mk_fastq_select_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n,
                            const uint8_t* d_keep, const uint64_t* d_kept, size_t nrec, unsigned which,
                            uint8_t* d_out, size_t out_cap, size_t* out_len, mk_fastq_select_t* st);
 
+/* ---- quality trimming and read filtering of a FASTQ text: the step MerCat2 hands to fastp, here as a stated rule -- the
+ *      running-sum trimming of BWA -q and cutadapt -q 5',3' at both ends, then the span filters of fastp and cutadapt
+ *      (length, N count, share of low-quality bases, mean quality) -- read, decided, cut and gathered on the GPU ----
+ * Lines, records, the tolerated trailing empty lines and the checks are mk_fastq_select_*'s (no kept: the byte check of
+ * the sequence line is not made), in that order, with one more behind them (kind 5): a byte of the quality line, one
+ * trailing '\r' not counted, below phred_base ("its quality line holds a character below the phred base").  The lowest
+ * record wins, then the lowest kind; all are MK_ERR_UNSUPPORTED.  The tables are not read; an open chunk is MK_ERR_STATE.
+ * Trimming of a read of L bases, q[i] = qual[i] - phred_base, all sums signed 64-bit:
+ *   5': s = best = start = 0; for i = 0 .. L-1: s += cut_front - q[i]; stop at the first s < 0; whenever s > best
+ *       (strictly): best = s, start = i + 1.
+ *   3': on the same untrimmed read: s = best = 0, stop = L; for i = L-1 .. 0: s += cut_back - q[i]; stop at the first
+ *       s < 0; whenever s > best (strictly): best = s, stop = i.
+ *   start >= stop: start = stop = 0.  kept = stop - start.  (A cutoff of 0 never trims; ties cut less.)
+ * Filters over [start, stop), the first that applies names the reason: short: kept < max(min_len, 1); n: more than max_n
+ * of the span's bases are 'N' or 'n'; lowq: low * 1000000 > max_low_ppm * kept, low = span bases with q < low_q (0: off);
+ * meanq: qsum < min_mean_q * kept (0: off).  A record none drops passes.
+ * paired: records 2p and 2p + 1 are mates (an odd count is MK_ERR_RANGE): keep[r] = 1 if both pass, 2 if only r passes,
+ * 0 otherwise; unpaired keep[r] is the pass bit.  Record r is emitted iff keep[r] == which (1, or 2 with paired only).
+ * Output, in text order: a record with start == 0 and kept == L whole, byte for byte (a forced '\n' where the text ends
+ * without one); any other as the header line as it stands, seq[start:stop] and '\n', the '+' line as it stands,
+ * qual[start:stop] and '\n'.  rows[r] (every record): length, start, kept, n, low, qsum (the last three over the span).
+ * hist[v]: bases of quality value v over all records; hist[256 + v]: over the emitted spans.
+ * cap: the records keep and rows have room for; a text with more is MK_ERR_RANGE with the count in *nrec (checked first;
+ * not when both are NULL).  keep, rows, hist may each be NULL.  out = NULL, out_cap = 0 is the sizing call; out_cap too
+ * small is MK_ERR_RANGE with the needed size in *out_len (keep, rows and hist are then complete); on every other error
+ * *out_len = 0.  *out_len <= n + 1.
+ * mk_fastq_qtrim_text: host memory, piece by piece as mk_fastq_select_text (with paired a piece ends behind an even
+ * record: mk_fastq_pair_cuts); nothing depends on piece_bytes.  mk_fastq_qtrim_device: everything in DEVICE memory of
+ * the context's GPU, one piece of at most 2^32 - 1 bytes (more: MK_ERR_RANGE, before anything is read; the text call's
+ * pieces are smaller); text and out at any address, d_rows and d_hist aligned to 8 (MK_ERR_ARG otherwise). */
+typedef struct mk_qtrim_opt_t {
+  uint32_t phred_base;          /* 33 or 64 (else MK_ERR_ARG)                                                          */
+  uint32_t cut_front, cut_back; /* 0 .. 93; 0: that end is not trimmed                                                 */
+  uint32_t min_len, max_n;      /* max_n ~0: no limit                                                                  */
+  uint32_t low_q, max_low_ppm;  /* max_low_ppm 0 .. 1000000                                                            */
+  uint32_t min_mean_q;
+  uint32_t paired, which;
+} mk_qtrim_opt_t;
+typedef struct mk_fastq_qtrim_t {
+  uint64_t records, records_out, records_trimmed; /* of the text; emitted; emitted and cut                             */
+  uint64_t dropped_short, dropped_n, dropped_lowq, dropped_meanq; /* records by the filter that dropped them           */
+  uint64_t orphans;                               /* records with keep[r] == 2                                         */
+  uint64_t bases_in, bases_out, bytes_out, lines; /* sequence bytes of the text; emitted; output bytes; lines          */
+  /* seconds: host time in the copies to the device; HIP-event time of the line index; of the quality scan; of the
+   * decision and its prefix sum; of the gather; host time in the copies back */
+  double s_copy, s_index, s_scan, s_place, s_gather, s_write;
+} mk_fastq_qtrim_t;
+int mk_fastq_qtrim_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes, const mk_qtrim_opt_t* opt, size_t cap,
+                        uint8_t* keep, uint64_t* rows, uint64_t* hist, uint8_t* out, size_t out_cap, size_t* out_len, size_t* nrec,
+                        mk_fastq_qtrim_t* st);
+int mk_fastq_qtrim_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const mk_qtrim_opt_t* opt, size_t cap, uint8_t* d_keep,
+                          uint64_t* d_rows, uint64_t* d_hist, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec,
+                          mk_fastq_qtrim_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where
@@ -1071,6 +1125,9 @@ int mk_record_cuts(const uint8_t* text, size_t n, uint64_t piece, size_t block, 
  * inside the text; piece i is [cuts[i-1], cuts[i]) with cuts[-1] = 0 and cuts[ncuts] = n.  MK_ERR_RANGE (and the needed
  * size in *ncuts) if cap is short. */
 int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts);
+/* The same for mk_fastq_qtrim_text with paired reads: a piece ends behind a line 8j, so that the mates 2p and 2p + 1 stay
+ * in one piece; a pair longer than `piece` makes its piece grow. */
+int mk_fastq_pair_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts);
 /* The file reader's own gzip decoder (csrc/mk_inflate.h) over a whole '.gz' file held in memory,
  * producing `block` bytes per step as the reader does, every member's CRC-32 and length checked.
  * A self-check for tests (against zlib): out must hold the whole text (cap bytes).

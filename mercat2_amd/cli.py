@@ -9,7 +9,8 @@ tsv_<type>/<sample>_counts.tsv files) as they are: their tables are loaded onto 
 cohort grows by one sample, or gets its -pca / -union reports, without recounting.  FASTQ input (.fq, .fastq, plain or .gz) is taken with -skipclean: MerCat2 then
 converts it with fq2fa only (lib/mercat2_fasta.py:175-198) into clean/<base>.fna.gz and counts that as a
 nucleotide sample; here the GPU counts the raw reads the same way while the file is written.  Without
--skipclean MerCat2 trims the reads with fastp first, a tool this engine does not run: refused.  With -pca and
+-skipclean MerCat2 trims the reads with fastp first, a tool this engine does not run: refused, unless -qtrim puts the
+engine's own quality trimming in that place (below).  With -pca and
 more than three samples of a type, pca_<type>/pca.tsv is computed from the tables still on the GPU
 (bin/mercat2.py:170-181, lib/mercat2_figures.py:206-291; mercat2_amd/pca.py): exact PCA, no plots.  The diversity
 reports are written from the tables on the GPU too (mercat2_amd/diversity.py): the 21 beta-diversity matrices per
@@ -43,7 +44,12 @@ and norm_<type>/<sample>_norm.tsv with every record's k-mers, depth and fate.  P
 and the per-record TSVs gain the pair's index.  -fastq_out makes -filter, -trim and -norm of a FASTQ FILE write FASTQ with
 the qualities (.fastq in place of .fna; mk_fastq_select_text).  -against FILE -op OP writes, for every sample of FILE's type,
 against/tsv_<type>/<sample>_counts.tsv: the sample's table combined by key with the count table FILE on the GPU
-(mk_table_op) -- a folder a next run takes with -tsv.  FASTQ QC, ORF calling (-prod / -fgs), the HTML report and plots belong
+(mk_table_op) -- a folder a next run takes with -tsv.  -qtrim [Q] takes FASTQ input with or without -skipclean and, where
+MerCat2 would run fastp, trims and filters the reads on the GPU by a stated rule (mk_fastq_qtrim_text: the running-sum
+quality cut of BWA -q / cutadapt -q at the 3' end, with -qtrim_front at the 5' end too, then -qtrim_len, -qtrim_n,
+-qtrim_low / -qtrim_low_frac and -qtrim_mean): qtrim/<sample>_qtrim.fastq holds the reads that are then counted,
+qtrim/<sample>_qtrim.tsv every read's length, cut and verdict, qtrim/<sample>_summary.tsv reads, bases, Q20 / Q30 bases and
+mean quality before and after.  The result is that rule's, not fastp's: no adapters are removed.  Per-position QC plots, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -219,6 +225,19 @@ def parseargs(argv=None):
     p.add_argument("-o", type=str, default="mercat_results", required=False, help="Output folder")
     p.add_argument("-replace", action="store_true", help="Replace existing output directory [False]")
     p.add_argument("-skipclean", action="store_true", help="skip trimming of the sequences [False]")
+    p.add_argument("-qtrim", type=int, nargs="?", const=20, default=None, metavar="Q",
+                   help="FASTQ input, with or without -skipclean: trim and filter the reads on the GPU before they are counted. "
+                        "This stands where MerCat2 runs fastp, and its result is not fastp's: every read is cut at its 3' end "
+                        "by the running sum of Q - quality (BWA -q, cutadapt -q; no adapter removal, no sliding window) "
+                        "[Q = 20]; writes qtrim/<sample>_qtrim.fastq, _qtrim.tsv and _summary.tsv")
+    p.add_argument("-qtrim_front", type=int, default=None, metavar="Q", help="-qtrim: cut the 5' end the same way with this cutoff [0: not cut]")
+    p.add_argument("-qtrim_len", type=int, default=None, metavar="N", help="-qtrim: drop a read of which fewer than N bases remain [1]")
+    p.add_argument("-qtrim_n", type=int, default=None, metavar="N", help="-qtrim: drop a read whose remaining bases hold more than N 'N' [no limit]")
+    p.add_argument("-qtrim_low", type=int, default=None, metavar="Q", help="-qtrim: a remaining base below quality Q is low [0: off]")
+    p.add_argument("-qtrim_low_frac", type=float, default=None, metavar="F",
+                   help="-qtrim: drop a read of whose remaining bases more than this fraction (0..1) are low; needs -qtrim_low [1]")
+    p.add_argument("-qtrim_mean", type=int, default=None, metavar="Q", help="-qtrim: drop a read whose remaining bases average below Q [0: off]")
+    p.add_argument("-qtrim_phred", type=int, default=None, choices=(33, 64), help="-qtrim: the offset of the quality characters [33]")
     p.add_argument("-toupper", action="store_true", help="convert all input sequences to uppercase [False]")
     # flags of the reference's other layers (bin/mercat2.py:45-58)
     p.add_argument("-prod", action="store_true", help="(MerCat2: ORF calling with prodigal) not part of this engine")
@@ -254,6 +273,28 @@ def parseargs(argv=None):
         p.error(f"folder {args.f} is not valid.\n")
     if args.query and not os.path.isfile(args.query):
         p.error(f"file '{args.query}' is not valid.\n")
+    qtrim_flags = ("qtrim_front", "qtrim_len", "qtrim_n", "qtrim_low", "qtrim_low_frac", "qtrim_mean", "qtrim_phred")
+    if args.qtrim is None:
+        for flag in qtrim_flags:
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -qtrim")
+    else:
+        given = list(args.i)
+        if args.f and os.path.isdir(args.f):
+            given += sorted(os.listdir(args.f))
+        if not any(fastq_ext(Path(name)) for name in given):
+            p.error(f"-qtrim trims FASTQ reads ({' / '.join(FILE_EXT_FASTQ)}); no input is a FASTQ file")
+        for flag, value in (("qtrim", args.qtrim), ("qtrim_front", args.qtrim_front), ("qtrim_low", args.qtrim_low),
+                            ("qtrim_mean", args.qtrim_mean)):
+            if value is not None and not 0 <= value <= 93:
+                p.error(f"-{flag} {value}: must lie in 0..93")
+        for flag in ("qtrim_len", "qtrim_n"):
+            if getattr(args, flag) is not None and not 0 <= getattr(args, flag) < 1 << 32:
+                p.error(f"-{flag} {getattr(args, flag)}: must lie in 0..2^32 - 1")
+        if args.qtrim_low_frac is not None and not 0.0 <= args.qtrim_low_frac <= 1.0:
+            p.error(f"-qtrim_low_frac {args.qtrim_low_frac}: must lie in 0..1")
+        if args.qtrim_low_frac is not None and not args.qtrim_low:
+            p.error("-qtrim_low_frac needs -qtrim_low Q: no base is low without it")
     if args.histo is not None and not 1 <= args.histo <= 1 << 20:
         p.error(f"-histo {args.histo}: HIGH must lie in 1..{1 << 20}")
     args.screen_kind = None
@@ -516,6 +557,25 @@ def classify(path: Path, skipclean: bool = False):
     return ("protein" if ext in FILE_EXT_PROTEIN else "nucleotide"), base
 
 
+def qtrim_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
+    """-qtrim: the reads of FASTQ sample ``base`` (``raw``: its bytes if they are in memory already, else None and ``f``
+    is read) trimmed and filtered on GPU ``device`` by kmers.qtrim_reads, which writes qtrim/<base>_qtrim.fastq,
+    _qtrim.tsv and _summary.tsv; returns the trimmed text, which is counted in the raw reads' place."""
+    from . import kmers, native
+    folder = out / "qtrim"
+    folder.mkdir(parents=True, exist_ok=True)
+    try:
+        done = kmers.qtrim_reads(
+            f if raw is None else raw, folder / f"{base}_qtrim.fastq", cut_back=args.qtrim, cut_front=args.qtrim_front or 0,
+            min_len=args.qtrim_len or 0, max_n=args.qtrim_n, low_q=args.qtrim_low or 0,
+            max_low_frac=1.0 if args.qtrim_low_frac is None else args.qtrim_low_frac, min_mean_q=args.qtrim_mean or 0,
+            phred_base=args.qtrim_phred or 33, tsv_path=folder / f"{base}_qtrim.tsv", summary_path=folder / f"{base}_summary.tsv",
+            device=device, keep_text=True)
+    except native.MercatHipError as e:
+        raise SystemExit(f"-qtrim '{f.name}': {e}")
+    return done["text"]
+
+
 def count_converted(base: str, holder: dict, fut, tsv: Path, args, devices, home: int, lines: list, tables: dict, t: dict) -> None:
     """The table of a sample whose text a background job rewrites (removeN) or converts (fq2fa) and writes as a level-9
     .gz, counted from the text in memory: the reference cuts the REWRITTEN file, and its size on disk decides
@@ -597,7 +657,7 @@ def main(argv=None) -> int:
     samples = {"nucleotide": {}, "protein": {}}
     fastq = set()  # nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)
     for f in files:
-        kind, base = classify(f.expanduser().absolute(), args.skipclean)
+        kind, base = classify(f.expanduser().absolute(), args.skipclean or args.qtrim is not None)
         if kind:
             samples[kind][base] = f
             if fastq_ext(f):
@@ -621,6 +681,7 @@ def main(argv=None) -> int:
     cleaned = {}  # base -> [clean file, raw bytes (until counted), future of (.gz size, stats), holder of the cleaned text, timings]
     gz_writers = ThreadPoolExecutor(max(1, min(int(args.n), 16)))
     to_load = {b: f for b, f in samples["nucleotide"].items() if clean or b in fastq}
+    home_of = {b: devices[i % len(devices)] for i, b in enumerate(samples["nucleotide"])}  # (the GPU that counts the sample, below)
     if to_load:
         import threading
         budget = [8 << 30]  # bytes of input held in memory between loading and counting; samples beyond it are read when counted
@@ -637,6 +698,10 @@ def main(argv=None) -> int:
             t0 = timeit.default_timer()
             raw = read_fasta_bytes(f)
             t["read_s"] = timeit.default_timer() - t0
+            if base in fastq and args.qtrim is not None:
+                t0 = timeit.default_timer()
+                raw = qtrim_sample(args, f, raw, out, base, home_of[base])
+                t["qtrim_s"] = timeit.default_timer() - t0
             if base in fastq:
                 path, fut, holder = fq2fa_background(f, raw, out / "clean", base, gz_writers, timings=t, limit=args.s * 1024 * 1024)
             else:
@@ -676,7 +741,7 @@ def main(argv=None) -> int:
             if kind == "nucleotide" and base in fastq:
                 limit = args.s * 1024 * 1024
                 if cleaned[base] is None:  # (not loaded up front: the conversion, its file, then the count)
-                    text, _ = fq2fa_text(read_fasta_bytes(f))
+                    text, _ = fq2fa_text(qtrim_sample(args, f, None, out, base, home) if args.qtrim is not None else read_fasta_bytes(f))
                     os.makedirs(out / "clean", exist_ok=True)
                     size = _write_clean_gz(out / "clean" / f"{base}.fna.gz", text, t)
                     chunked = args.s > 0 and size >= limit

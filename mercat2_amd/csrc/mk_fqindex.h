@@ -1,6 +1,7 @@
 // mk_fqindex.h -- the line index of a FASTQ text and the check of its sequence lines, shared by mk_fastq_select_*
-// (mk_fqselect.hip, which has the scheme) and mk_correct_fastq_* (mk_correctfq.hip): fs_tiles_k, fs_scan_k, fs_lines_k,
-// the status word they leave, and the phrases of the record checks (fs_kind).
+// (mk_fqselect.hip, which has the scheme), mk_correct_fastq_* (mk_correctfq.hip) and mk_fastq_qtrim_* (mk_qtrim.hip):
+// fs_tiles_k, fs_scan_k, fs_lines_k, the status word they leave, the phrases of the record checks (fs_kind), and the
+// segment gather of the two calls that write records out (fs_gather_k, fs_edges_k).
 #pragma once
 #include "mk_recordplace.h"
 #include "mk_tableview.h"
@@ -112,6 +113,61 @@ static __global__ void __launch_bounds__(256) fs_lines_k(const uint8_t* __restri
     }
     if (bad != FS_NONE) atomicMin((unsigned long long*)&st->bad, (unsigned long long)bad);
   }
+}
+
+// The gather of mk_fqselect.hip's scheme, shared with mk_qtrim.hip (four segments a record there).
+// fl_gather_k over segments: segment s goes to [dst[s], dst[s + 1]) from seg_src[s] on; nseg of them.
+#define FS_CHUNKS 4
+static __global__ void __launch_bounds__(256) fs_gather_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ seg_src,
+                                                          const u64* __restrict__ dst, size_t nseg, u64 head, u64 nbody,
+                                                          uint8_t* __restrict__ out) {
+  const u64 g0 = fl_first_lane((((u64)blockIdx.x * 256 + threadIdx.x) >> 6) * (64 * FS_CHUNKS));
+  if (g0 >= nbody) return;
+  size_t s = fl_record_of(dst, 0, nseg - 1, head + 16 * g0);
+  for (int j = 0; j < FS_CHUNKS; ++j) {
+    const u64 g = g0 + j * 64 + (threadIdx.x & 63);
+    if (g >= nbody) break;
+    const u64 o0 = head + 16 * g;
+    s = fl_record_from(dst, s, nseg, o0);
+    u64 end = dst[s + 1];
+    u64 from = seg_src[s];
+    u64 src = (from & ~FS_FORCE) + (o0 - dst[s]);
+    unsigned __int128 v = 0;
+    for (unsigned b = 0;;) {  // b: bytes of the chunk filled
+      const u64 left = end - (o0 + b);  // (1 or more: the segment holds byte o0 + b)
+      const unsigned m = left < 16 - b ? (unsigned)left : 16 - b;
+      unsigned __int128 part = fl_load16(text, n, src);
+      if (m < 16) part &= (((unsigned __int128)1) << (8 * m)) - 1;
+      if ((from & FS_FORCE) && left <= 16 - b)  // the segment ends in this chunk: its last byte
+        part = (part & ~(((unsigned __int128)0xFF) << (8 * (m - 1)))) | (((unsigned __int128)10) << (8 * (m - 1)));
+      v |= part << (8 * b);
+      b += m;
+      if (b == 16) break;
+      ++s;  // the segment ended inside the chunk (bytes follow: an emitted segment does)
+      if (dst[s + 1] == dst[s]) s = fl_record_from(dst, s, nseg, o0 + b);
+      end = dst[s + 1];
+      from = seg_src[s];
+      src = from & ~FS_FORCE;
+    }
+    const u64 v0 = (u64)v, v1 = (u64)(v >> 64);
+    *reinterpret_cast<uint4*>(out + o0) = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
+  }
+}
+
+// The bytes in front of the first aligned 16 of the output (head of them) and behind the last (from tail_at on): a lane
+// a byte, at most 15 + 15.
+static __global__ void __launch_bounds__(64) fs_edges_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ seg_src,
+                                                        const u64* __restrict__ dst, size_t nseg, u64 head, u64 tail_at, u64 out_len,
+                                                        uint8_t* __restrict__ out) {
+  u64 o;
+  if (threadIdx.x < 16) o = threadIdx.x < head ? threadIdx.x : out_len;
+  else if (threadIdx.x < 32) o = tail_at + (threadIdx.x - 16);
+  else return;
+  if (o >= out_len) return;
+  const size_t s = fl_record_of(dst, 0, nseg - 1, o);
+  const u64 from = seg_src[s], at = (from & ~FS_FORCE) + (o - dst[s]);
+  const bool forced = (from & FS_FORCE) && o + 1 == dst[s + 1];
+  out[o] = forced ? (uint8_t)10 : (at < n ? text[at] : (uint8_t)0);
 }
 
 static const char* fs_kind(unsigned kind) {

@@ -17,7 +17,8 @@
 //                            force a '\n' as the last byte}.
 //   rocprim::exclusive_scan  dst[s], dst[2 * nrec] = the piece's output length.  The status is read back here, once, and
 //                            no address is made of a length before it has been seen to be clean.
-//   fs_gather_k (fs_edges_k) fl_gather_k's scheme (mk_recordplace.h) over segments: output-driven, a lane owns 16 aligned
+//   fs_gather_k (fs_edges_k) (in mk_fqindex.h: mk_qtrim.hip gathers with them too)
+//                            fl_gather_k's scheme (mk_recordplace.h) over segments: output-driven, a lane owns 16 aligned
 //                            output bytes a round, one search a wave, fl_record_from from there, fl_load16 / mask /
 //                            shift / OR per segment, and the last byte of a flagged segment that ends in the chunk
 //                            replaced by '\n' -- the base behind a trimmed prefix, the '\r' of CR LF, the 0 that
@@ -83,60 +84,6 @@ static __global__ void __launch_bounds__(256) fs_decide_k(const uint8_t* __restr
   block_add(&st->records_out, n_out);
   block_add(&st->records_trimmed, n_trimmed);
   block_add(&st->bases_out, n_bases);
-}
-
-// fl_gather_k over segments: segment s goes to [dst[s], dst[s + 1]) from seg_src[s] on; nseg of them.
-#define FS_CHUNKS 4
-static __global__ void __launch_bounds__(256) fs_gather_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ seg_src,
-                                                          const u64* __restrict__ dst, size_t nseg, u64 head, u64 nbody,
-                                                          uint8_t* __restrict__ out) {
-  const u64 g0 = fl_first_lane((((u64)blockIdx.x * 256 + threadIdx.x) >> 6) * (64 * FS_CHUNKS));
-  if (g0 >= nbody) return;
-  size_t s = fl_record_of(dst, 0, nseg - 1, head + 16 * g0);
-  for (int j = 0; j < FS_CHUNKS; ++j) {
-    const u64 g = g0 + j * 64 + (threadIdx.x & 63);
-    if (g >= nbody) break;
-    const u64 o0 = head + 16 * g;
-    s = fl_record_from(dst, s, nseg, o0);
-    u64 end = dst[s + 1];
-    u64 from = seg_src[s];
-    u64 src = (from & ~FS_FORCE) + (o0 - dst[s]);
-    unsigned __int128 v = 0;
-    for (unsigned b = 0;;) {  // b: bytes of the chunk filled
-      const u64 left = end - (o0 + b);  // (1 or more: the segment holds byte o0 + b)
-      const unsigned m = left < 16 - b ? (unsigned)left : 16 - b;
-      unsigned __int128 part = fl_load16(text, n, src);
-      if (m < 16) part &= (((unsigned __int128)1) << (8 * m)) - 1;
-      if ((from & FS_FORCE) && left <= 16 - b)  // the segment ends in this chunk: its last byte
-        part = (part & ~(((unsigned __int128)0xFF) << (8 * (m - 1)))) | (((unsigned __int128)10) << (8 * (m - 1)));
-      v |= part << (8 * b);
-      b += m;
-      if (b == 16) break;
-      ++s;  // the segment ended inside the chunk (bytes follow: an emitted segment does)
-      if (dst[s + 1] == dst[s]) s = fl_record_from(dst, s, nseg, o0 + b);
-      end = dst[s + 1];
-      from = seg_src[s];
-      src = from & ~FS_FORCE;
-    }
-    const u64 v0 = (u64)v, v1 = (u64)(v >> 64);
-    *reinterpret_cast<uint4*>(out + o0) = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
-  }
-}
-
-// The bytes in front of the first aligned 16 of the output (head of them) and behind the last (from tail_at on): a lane
-// a byte, at most 15 + 15.
-static __global__ void __launch_bounds__(64) fs_edges_k(const uint8_t* __restrict__ text, u64 n, const u64* __restrict__ seg_src,
-                                                        const u64* __restrict__ dst, size_t nseg, u64 head, u64 tail_at, u64 out_len,
-                                                        uint8_t* __restrict__ out) {
-  u64 o;
-  if (threadIdx.x < 16) o = threadIdx.x < head ? threadIdx.x : out_len;
-  else if (threadIdx.x < 32) o = tail_at + (threadIdx.x - 16);
-  else return;
-  if (o >= out_len) return;
-  const size_t s = fl_record_of(dst, 0, nseg - 1, o);
-  const u64 from = seg_src[s], at = (from & ~FS_FORCE) + (o - dst[s]);
-  const bool forced = (from & FS_FORCE) && o + 1 == dst[s + 1];
-  out[o] = forced ? (uint8_t)10 : (at < n ? text[at] : (uint8_t)0);
 }
 
 // ------------------------------------------------------------------------------------------ host side

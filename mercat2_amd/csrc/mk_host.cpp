@@ -107,7 +107,8 @@ static int stream_cuts(const uint8_t* text, size_t n, uint64_t chunksize, size_t
 
 // Where mk_fastq_select_text cuts a FASTQ text: a piece ends behind a line 4j (lines split on '\n' only, numbered
 // across the text) once it holds `piece` bytes.  Only '\n' is counted (memchr); nothing else of the text is looked at.
-extern "C" int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts) {
+// mk_fastq_qtrim_text with paired reads cuts behind a line 8j in the same way (mk_fastq_pair_cuts).
+static int fastq_cuts_every(const uint8_t* text, size_t n, uint64_t piece, uint64_t per, uint64_t* cuts, size_t cap, size_t* ncuts) {
   if (!ncuts || (n && !text)) return MK_ERR_ARG;
   size_t found = 0, pos = 0, from = 0;
   uint64_t line = 0;
@@ -115,7 +116,7 @@ extern "C" int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint
     const uint8_t* nl = (const uint8_t*)memchr(text + pos, '\n', n - pos);
     if (!nl) break;
     pos = (size_t)(nl - text) + 1;
-    if ((++line & 3) == 0 && pos < n && pos - from >= piece) {
+    if ((++line % per) == 0 && pos < n && pos - from >= piece) {
       if (found < cap && cuts) cuts[found] = (uint64_t)pos;
       ++found;
       from = pos;
@@ -123,6 +124,12 @@ extern "C" int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint
   }
   *ncuts = found;
   return (found > cap && cuts) ? MK_ERR_RANGE : MK_OK;
+}
+extern "C" int mk_fastq_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts) {
+  return fastq_cuts_every(text, n, piece, 4, cuts, cap, ncuts);
+}
+extern "C" int mk_fastq_pair_cuts(const uint8_t* text, size_t n, uint64_t piece, uint64_t* cuts, size_t cap, size_t* ncuts) {
+  return fastq_cuts_every(text, n, piece, 8, cuts, cap, ncuts);
 }
 
 // ------------------------------------------------------------------------------- gunzip

@@ -551,3 +551,64 @@ def normalize_read_pairs(table: "native.Counter", file: Union[str, Path], out_pa
             "low": int(info["records_low"]), "over": int(info["records_over"]), "thinned": int(info["records_thinned"]),
             "bytes_out": len(out), "pairs": int(info["pairs"]), "pairs_kept": int(info["pairs_out"]),
             "singles": int(info["singles_out"])}
+
+
+def fastq_names(raw: bytes) -> List[str]:
+    """The names of a FASTQ text's 4-line records, in order: the first word behind the '@' of line 4r ("" for none)."""
+    lines = raw.count(b"\n") + (1 if raw and not raw.endswith(b"\n") else 0)
+    heads = raw.split(b"\n")[0::4][: lines // 4]
+    return [(h[1:].split() or [b""])[0].decode("utf-8", "replace") for h in heads]
+
+
+def qtrim_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None], cut_back: int = 20, cut_front: int = 0, min_len: int = 0,
+                max_n: Optional[int] = None, low_q: int = 0, max_low_frac: float = 1.0, min_mean_q: int = 0, phred_base: int = 33,
+                paired: bool = False, tsv_path: Union[str, Path, None] = None, summary_path: Union[str, Path, None] = None,
+                mate_file: Union[str, Path, None] = None, out_path2: Union[str, Path, None] = None,
+                singles_path: Union[str, Path, None] = None, device: int = 0, keep_text: bool = False) -> Dict[str, object]:
+    """The reads of a FASTQ file ('.fq' / '.fastq', plain or '.gz'; or the FASTQ text itself as bytes, for a caller that
+    holds it already) quality-trimmed and filtered on the GPU
+    (Counter.fastq_qtrim has the rule and the options: BWA's / cutadapt's running-sum cut at both ends, then length, N,
+    low-quality share and mean quality), written as FASTQ to ``out_path`` -- gzip (level 1) if that name ends in '.gz'.
+    This stands where MerCat2 runs fastp; its result is this stated rule's, not fastp's (no adapter removal).  No table
+    is read: the call opens a small context of its own on ``device``.
+    Paired reads (``paired``: the file is interleaved; or ``mate_file``: the second file, interleaved with the first on
+    the host by native.interleave_fastq): a pair is written iff both mates pass, interleaved to ``out_path`` or split
+    into ``out_path`` and ``out_path2``; ``singles_path`` receives the reads that pass while their mate does not (a
+    second call with which = 2).  ``tsv_path``: every record's name, row and keep value (report.write_qtrim_tsv);
+    ``summary_path``: reads, bases, Q20 / Q30 bases and mean quality before and after, and the drop counts
+    (report.write_qtrim_summary).  Returns the mk_fastq_qtrim_t figures, "hist" (2 x 256) and, with ``keep_text``, the
+    main output under "text" (interleaved for pairs)."""
+    is_paired = _is_paired(paired, mate_file, out_path2, singles_path)
+    is_text = isinstance(file, (bytes, bytearray, memoryview))
+    for f in (None if is_text else file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("qtrim_reads: needs FASTQ input (%s), not %s" % (" / ".join(FASTQ_SUFFIXES), f))
+    raw = bytes(file) if is_text else read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    opts = dict(cut_back=cut_back, cut_front=cut_front, min_len=min_len, max_n=max_n, low_q=low_q, max_low_frac=max_low_frac,
+                min_mean_q=min_mean_q, phred_base=phred_base, paired=is_paired)
+    info: Dict[str, object] = {}
+    with native.Counter(5, native.ALPHABET_NT2, device=device) as ctx:
+        out, keep, rows, hist = ctx.fastq_qtrim(raw, which=1, info=info, **opts)
+        singles = ctx.fastq_qtrim(raw, which=2, **opts)[0] if singles_path is not None else None
+    if out_path is not None:
+        if out_path2 is None:
+            _write_reads(out_path, out)
+        else:
+            first, second = native.split_pairs_fastq(out)
+            _write_reads(out_path, first)
+            _write_reads(out_path2, second)
+    if singles_path is not None:
+        _write_reads(singles_path, singles or b"")
+    if tsv_path is not None:
+        from .report import write_qtrim_tsv
+        write_qtrim_tsv(tsv_path, fastq_names(raw), rows, keep)
+    if summary_path is not None:
+        from .report import write_qtrim_summary
+        write_qtrim_summary(summary_path, info, hist)
+    done: Dict[str, object] = {name: value for name, value in info.items() if not name.startswith("s_")}
+    done["hist"] = hist
+    if keep_text:
+        done["text"] = out
+    return done

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "mk_correct_fastq_text", "mk_correct_fastq_device", "mk_norm_text", "mk_norm_device",
     "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
     "mk_fastq_select_text", "mk_fastq_select_device", "mk_fastq_cuts", "mk_fq_interleave", "mk_fq_split_pairs",
+    "mk_fastq_qtrim_text", "mk_fastq_qtrim_device", "mk_fastq_pair_cuts",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -285,6 +286,39 @@ class FastqSelect(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class QtrimOpt(C.Structure):
+    """mk_qtrim_opt_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("phred_base", "cut_front", "cut_back", "min_len", "max_n", "low_q", "max_low_ppm",
+                                          "min_mean_q", "paired", "which")]
+
+
+class FastqQtrim(C.Structure):
+    """mk_fastq_qtrim_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("records", "records_out", "records_trimmed", "dropped_short", "dropped_n", "dropped_lowq",
+                                           "dropped_meanq", "orphans", "bases_in", "bases_out", "bytes_out", "lines")] +
+                [(n, C.c_double) for n in ("s_copy", "s_index", "s_scan", "s_place", "s_gather", "s_write")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+QTRIM_COLUMNS = ("length", "start", "kept", "n", "low", "qsum")  # the columns of Counter.fastq_qtrim's rows
+QTRIM_NO_LIMIT = 0xFFFFFFFF  # mk_qtrim_opt_t.max_n: no limit
+
+
+def qtrim_options(cut_back: int = 20, cut_front: int = 0, min_len: int = 0, max_n=None, low_q: int = 0, max_low_frac: float = 1.0,
+                  min_mean_q: int = 0, phred_base: int = 33, paired: bool = False, which: int = 1) -> "QtrimOpt":
+    """mk_qtrim_opt_t of Counter.fastq_qtrim's arguments; ValueError for one that no uint32 holds or a fraction outside
+    0..1 (the library checks the ranges the rule sets)."""
+    vals = dict(phred_base=phred_base, cut_front=cut_front, cut_back=cut_back, min_len=min_len,
+                max_n=QTRIM_NO_LIMIT if max_n is None else max_n, low_q=low_q, max_low_ppm=ppm_of_fraction(max_low_frac),
+                min_mean_q=min_mean_q, paired=1 if paired else 0, which=which)
+    for name, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s %r: must lie in 0..2^32-1" % (name, v))
+    return QtrimOpt(**{name: int(v) for name, v in vals.items()})
+
+
 def ppm_of_fraction(min_frac: float) -> int:
     """min_ppm of mk_filter_rule_t for "at least this fraction of the record's k-mers are hits": round(min_frac * 10^6);
     ValueError outside 0..1 (and for a NaN)."""
@@ -482,6 +516,11 @@ def lib() -> C.CDLL:
         "mk_fastq_select_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint,
                                              C.c_void_p, C.c_size_t, szp, C.POINTER(FastqSelect)]),
         "mk_fastq_cuts": (C.c_int, [u8p, C.c_size_t, C.c_uint64, u64p, C.c_size_t, szp]),
+        "mk_fastq_pair_cuts": (C.c_int, [u8p, C.c_size_t, C.c_uint64, u64p, C.c_size_t, szp]),
+        "mk_fastq_qtrim_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.POINTER(QtrimOpt), C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqQtrim)]),
+        "mk_fastq_qtrim_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(QtrimOpt), C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqQtrim)]),
         "mk_fq_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_fq_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
     }
@@ -640,16 +679,17 @@ def split_pairs_fastq(text) -> Tuple[bytes, bytes]:
     return o1[: l1.value].tobytes(), o2[: l2.value].tobytes()
 
 
-def fastq_cuts(text, piece: int) -> np.ndarray:
+def fastq_cuts(text, piece: int, pairs: bool = False) -> np.ndarray:
     """Where Counter.fastq_select cuts a FASTQ text into pieces (mk_fastq_cuts): behind a line 4j once a piece holds
-    ``piece`` bytes."""
+    ``piece`` bytes.  ``pairs``: where Counter.fastq_qtrim cuts paired reads (mk_fastq_pair_cuts): behind a line 8j."""
     L = lib()
+    scan = L.mk_fastq_pair_cuts if pairs else L.mk_fastq_cuts
     addr, n, keep = _buf_ptr(text)
     need = C.c_size_t(0)
     cap = 64
     while True:
         cuts = np.empty(cap, dtype=np.uint64)
-        rc = L.mk_fastq_cuts(addr, n, int(piece), cuts.ctypes.data, cap, C.byref(need))
+        rc = scan(addr, n, int(piece), cuts.ctypes.data, cap, C.byref(need))
         if rc == MK_OK:
             return cuts[: need.value].copy()
         if rc != -7:
@@ -1336,6 +1376,51 @@ class Counter:
         out_len, st = C.c_size_t(0), FastqSelect()
         self._check_select(self._L.mk_fastq_select_device(self._h, ptr, int(nbytes), keep_ptr or None, kept_ptr or None, int(nrec),
                                                           int(which), out_ptr or None, int(out_cap), C.byref(out_len), C.byref(st)))
+        return st.as_dict()
+
+    # -- quality trimming and read filtering of a FASTQ text (what MerCat2 leaves to fastp); no table is read
+    def fastq_qtrim(self, path_or_bytes, cut_back: int = 20, cut_front: int = 0, min_len: int = 0, max_n=None, low_q: int = 0,
+                    max_low_frac: float = 1.0, min_mean_q: int = 0, phred_base: int = 33, paired: bool = False, which: int = 1,
+                    piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_fastq_qtrim_text: (out, keep, rows, hist) of the FASTQ text (a path to a plain file, or the text itself as
+        bytes).  Every read is cut at its 3' end by the running sum of ``cut_back`` - q (BWA -q, cutadapt -q) and at its
+        5' end by that of ``cut_front`` - q (0: that end stays), then dropped if the span left is shorter than
+        max(``min_len``, 1), holds more than ``max_n`` N (None: no limit), more than ``max_low_frac`` of its bases below
+        ``low_q`` (0: off), or a mean quality below ``min_mean_q`` (0: off).  ``paired``: records 2p and 2p + 1 are mates;
+        keep is 1 where both pass, 2 for a read whose mate fails, else 0; ``which`` = 2 writes those orphans.  ``out``: the
+        emitted records as FASTQ bytes; ``keep``: uint8 a record; ``rows``: (records, 6) uint64, QTRIM_COLUMNS; ``hist``:
+        (2, 256) uint64, the bases of every quality value in the text and in the emitted spans.  MercatHipError:
+        MK_ERR_UNSUPPORTED for a malformed record (the message names it), MK_ERR_RANGE for an odd record count with
+        ``paired``.  ``info``, if given, receives the mk_fastq_qtrim_t fields."""
+        opt = qtrim_options(cut_back, cut_front, min_len, max_n, low_q, max_low_frac, min_mean_q, phred_base, paired, which)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        nl = int(np.count_nonzero(held == 10)) if size else 0
+        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        keep, rows, hist = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 6), dtype=np.uint64), np.zeros((2, 256), dtype=np.uint64)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqQtrim()
+        self._check_select(self._L.mk_fastq_qtrim_text(
+            self._h, addr, size, int(piece_bytes), C.byref(opt), cap, keep.ctypes.data, rows.ctypes.data, hist.ctypes.data,
+            out.ctypes.data, size + 1, C.byref(out_len), C.byref(nrec), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), keep[: nrec.value], rows[: nrec.value], hist
+
+    def fastq_qtrim_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, cap: int = 0, keep_ptr: int = 0, rows_ptr: int = 0,
+                           hist_ptr: int = 0, **options) -> dict:
+        """mk_fastq_qtrim_device: ``nbytes`` of FASTQ text at device address ``ptr`` -> the emitted records at device
+        address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) and, where given, one keep byte a
+        record at ``keep_ptr``, six uint64 a record at ``rows_ptr`` (room for ``cap`` records each) and 512 uint64 at
+        ``hist_ptr`` (both aligned to 8) -- all on this context's GPU.  ``options``: those of Counter.fastq_qtrim.
+        Returns the mk_fastq_qtrim_t fields: "bytes_out" bytes were written, "records" rows."""
+        opt = qtrim_options(**options)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqQtrim()
+        self._check_select(self._L.mk_fastq_qtrim_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), keep_ptr or None,
+                                                         rows_ptr or None, hist_ptr or None, out_ptr or None, int(out_cap),
+                                                         C.byref(out_len), C.byref(nrec), C.byref(st)))
         return st.as_dict()
 
     # -- tracking: FASTA text in, the count under every window out (and the median a record); the table is only read

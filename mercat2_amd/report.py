@@ -321,3 +321,47 @@ def _merge_files(tsv_list, out_file, device: int, transposed: bool) -> None:
     finally:
         for c in ctxs:
             c.close()
+
+
+def format_qtrim_tsv(names: Sequence[str], rows, keep) -> bytes:
+    """``record\tlength\tstart\tkept\tn\tlow\tqsum\tkeep``, then one line per record (kmers.qtrim_reads /
+    Counter.fastq_qtrim): its name, the six columns of its row and its keep value."""
+    if len(names) != len(rows) or len(names) != len(keep):
+        raise ValueError("format_qtrim_tsv: %d names for %d rows and %d keep values" % (len(names), len(rows), len(keep)))
+    out = [b"record\tlength\tstart\tkept\tn\tlow\tqsum\tkeep\n"]
+    for name, row, k in zip(names, rows, keep):
+        out.append(name.encode() + b"\t%d\t%d\t%d\t%d\t%d\t%d" % tuple(int(v) for v in row) + b"\t%d\n" % int(k))
+    return b"".join(out)
+
+
+def write_qtrim_tsv(path, names: Sequence[str], rows, keep) -> int:
+    """``format_qtrim_tsv`` written to ``path``; returns the number of records."""
+    text = format_qtrim_tsv(names, rows, keep)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
+def format_qtrim_summary(figures: Dict[str, int], hist) -> bytes:
+    """``metric\tbefore\tafter`` over reads, bases, q20_bases, q30_bases and mean_quality -- from the call's figures and
+    its two histograms (hist[0][v]: bases of quality v in the text, hist[1][v]: in the emitted spans) -- then the four
+    drop counts and the orphans, which have no "before".  The mean is written with four decimals."""
+    def side(h, reads):
+        bases = sum(int(c) for c in h)
+        q20 = sum(int(c) for v, c in enumerate(h) if v >= 20)
+        q30 = sum(int(c) for v, c in enumerate(h) if v >= 30)
+        mean = sum(v * int(c) for v, c in enumerate(h)) / bases if bases else 0.0
+        return [b"%d" % reads, b"%d" % bases, b"%d" % q20, b"%d" % q30, b"%.4f" % mean]
+    before, after = side(hist[0], int(figures["records"])), side(hist[1], int(figures["records_out"]))
+    out = [b"metric\tbefore\tafter\n"]
+    for name, b, a in zip((b"reads", b"bases", b"q20_bases", b"q30_bases", b"mean_quality"), before, after):
+        out.append(name + b"\t" + b + b"\t" + a + b"\n")
+    for name in ("dropped_short", "dropped_n", "dropped_lowq", "dropped_meanq", "orphans"):
+        out.append(name.encode() + b"\t\t%d\n" % int(figures[name]))
+    return b"".join(out)
+
+
+def write_qtrim_summary(path, figures: Dict[str, int], hist) -> None:
+    """``format_qtrim_summary`` written to ``path``."""
+    with open(path, "wb") as fh:
+        fh.write(format_qtrim_summary(figures, hist))
