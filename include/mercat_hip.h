@@ -897,6 +897,64 @@ int mk_fastq_qtrim_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const m
                           uint64_t* d_rows, uint64_t* d_hist, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec,
                           mk_fastq_qtrim_t* st);
 
+/* ---- 3' adapter removal from the reads of a FASTQ text: the first job of the fastp run MerCat2 starts, here as a stated
+ *      rule -- the 3' adapter search of cutadapt -a ... --no-indels, reduced to the leftmost admissible position -- read,
+ *      decided, cut and gathered on the GPU.  Qualities are carried along and never interpreted ----
+ * Lines, records, the tolerated trailing empty lines, the checks and their messages are mk_fastq_select_*'s without kept
+ * ('@', '+', equal lengths, a text that ends inside a record); all MK_ERR_UNSUPPORTED, the lowest record wins.  The tables
+ * are not read; an open chunk is MK_ERR_STATE.
+ * Adapters: A of them, 1 .. 1024, each of 1 .. 128 bases over ACGTN (lower case folded; any other byte is MK_ERR_ARG and
+ * the message names the adapter), bases[] their characters back to back, lengths[a] their lengths, mates[a] their mate
+ * class: 1 first mates and unpaired reads, 2 second mates, 3 both (mates == NULL: all 1).  Without paired every record
+ * is of class 1; with paired record 2p is of class 1 and record 2p + 1 of class 2.
+ * A read's sequence line content s has L bytes (one trailing '\r' taken off), a .. z folded to upper case; a byte that is
+ * then none of A, C, G, T mismatches every adapter base but N; an adapter N matches any byte.  For position i in 0 .. L-1
+ * and adapter a of m bases: ov = min(m, L - i); mism = the number of j < ov with adapter[j] != 'N' and adapter[j] !=
+ * fold(s[i + j]); a is admissible at i iff its class covers the record, ov >= min_overlap and mism * 1000000 <=
+ * max_err_ppm * ov (64-bit integers).  The hit is the smallest i that has an admissible adapter, and of those admissible
+ * there the lowest index.  cut = i, or L without a hit; the read keeps s[:cut] and qual[:cut].  A read with cut <
+ * max(min_len, 1) is dropped as short.  paired, which and keep[r] are mk_fastq_qtrim_*'s: keep[r] = 1 if both mates pass, 2
+ * if only r passes, 0 otherwise (unpaired: the pass bit); record r is emitted iff keep[r] == which; an odd record count
+ * with paired is MK_ERR_RANGE.
+ * Output, in text order: a record with cut == L whole, byte for byte (a forced '\n' where the text ends without one); any
+ * other as the header line as it stands, s[:cut] and '\n', the '+' line as it stands, qual[:cut] and '\n'.
+ * rows[r] (every record, five uint64): length, kept, adapter, overlap, mismatches -- adapter the index of the hit, or
+ * 0xFFFFFFFF with overlap = mismatches = 0.  hits[a] (A uint64): the records whose hit is adapter a, emitted or not.
+ * cap, the sizing call, out_cap too small, *nrec, *out_len, the order of the errors and NULL keep / rows / hits are
+ * mk_fastq_qtrim_*'s (options, then the panel, are checked first).  mk_fastq_adapt_device: one piece of at most 2^32 - 1
+ * bytes, text and out at any address, d_rows and d_hits aligned to 8 (MK_ERR_ARG otherwise); bases, lengths and mates are
+ * host memory in both calls.
+ * mk_adapters_pack: host code, no GPU: validates the adapters and writes the packed panel the scan kernel reads, 1 + 9 A
+ * 64-bit words (*nwords; words = NULL sizes; words_cap too small is MK_ERR_RANGE; err, if given, receives the message):
+ *   words[0] = A; adapter a is the nine words at 1 + 9 a:
+ *   [0]      length (bits 0 .. 7) | class << 8 | first << 32 -- first: the lowest index of an adapter with the same bases
+ *            (after folding) and the same class, a itself if there is none before it; the kernel compares only those with
+ *            first == a, which leaves the reported index the lowest
+ *   [1..4]   codes: base j is the two bits at 2 (j % 32) of word 1 + j / 32: A 0, C 1, G 2, T 3 (N: 0)
+ *   [5..8]   the wildcard plane, inverted ("care"): bit 2 (j % 32) of word 5 + j / 32 is set iff base j is not N
+ *   all bits behind the adapter's last base are 0. */
+typedef struct mk_adapt_opt_t {
+  uint32_t min_overlap; /* 1 .. 128 (else MK_ERR_ARG)                                                                  */
+  uint32_t max_err_ppm; /* 0 .. 1000000                                                                                */
+  uint32_t min_len, paired, which;
+} mk_adapt_opt_t;
+typedef struct mk_fastq_adapt_t {
+  uint64_t records, records_out, records_trimmed; /* of the text; emitted; emitted and cut                             */
+  uint64_t dropped_short, orphans;                /* records dropped as short; records with keep[r] == 2               */
+  uint64_t bases_in, bases_out, bytes_out, lines; /* sequence bytes of the text; emitted; output bytes; lines          */
+  /* seconds: host time in the copies to the device; HIP-event time of the line index; of the adapter scan; of the
+   * decision and its prefix sum; of the gather; host time in the copies back */
+  double s_copy, s_index, s_scan, s_place, s_gather, s_write;
+} mk_fastq_adapt_t;
+int mk_adapters_pack(const uint8_t* bases, const uint32_t* lengths, const uint8_t* mates, size_t A, uint64_t* words, size_t words_cap,
+                     size_t* nwords, char* err, size_t err_cap);
+int mk_fastq_adapt_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes, const uint8_t* bases, const uint32_t* lengths,
+                        const uint8_t* mates, size_t A, const mk_adapt_opt_t* opt, size_t cap, uint8_t* keep, uint64_t* rows,
+                        uint64_t* hits, uint8_t* out, size_t out_cap, size_t* out_len, size_t* nrec, mk_fastq_adapt_t* st);
+int mk_fastq_adapt_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const uint8_t* bases, const uint32_t* lengths,
+                          const uint8_t* mates, size_t A, const mk_adapt_opt_t* opt, size_t cap, uint8_t* d_keep, uint64_t* d_rows,
+                          uint64_t* d_hits, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec, mk_fastq_adapt_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

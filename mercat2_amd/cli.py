@@ -49,7 +49,13 @@ MerCat2 would run fastp, trims and filters the reads on the GPU by a stated rule
 quality cut of BWA -q / cutadapt -q at the 3' end, with -qtrim_front at the 5' end too, then -qtrim_len, -qtrim_n,
 -qtrim_low / -qtrim_low_frac and -qtrim_mean): qtrim/<sample>_qtrim.fastq holds the reads that are then counted,
 qtrim/<sample>_qtrim.tsv every read's length, cut and verdict, qtrim/<sample>_summary.tsv reads, bases, Q20 / Q30 bases and
-mean quality before and after.  The result is that rule's, not fastp's: no adapters are removed.  Per-position QC plots, ORF calling (-prod / -fgs), the HTML report and plots belong
+mean quality before and after.  The result is that rule's, not fastp's: no adapters are removed by it.  -adapt [FILE] does
+that, before -qtrim where both are given, again by a stated rule (mk_fastq_adapt_text: the 3' adapter search of cutadapt -a
+--no-indels at its leftmost admissible position, over -adapt_overlap bases within -adapt_err mismatches a base, reads left
+shorter than -adapt_len dropped) against the adapters of the FASTA FILE or, without one, Illumina's TruSeq, Nextera and
+small-RNA adapters: adapt/<sample>_adapt.fastq holds the reads that -qtrim and the count then see, adapt/<sample>_adapt.tsv
+every read's length, cut, adapter, overlap and mismatches, adapt/<sample>_summary.tsv reads and bases before and after and
+the hits of each adapter.  Indels, 5' and anchored adapters, mate-overlap detection and poly-G trimming stay out.  Per-position QC plots, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -238,6 +244,17 @@ def parseargs(argv=None):
                    help="-qtrim: drop a read of whose remaining bases more than this fraction (0..1) are low; needs -qtrim_low [1]")
     p.add_argument("-qtrim_mean", type=int, default=None, metavar="Q", help="-qtrim: drop a read whose remaining bases average below Q [0: off]")
     p.add_argument("-qtrim_phred", type=int, default=None, choices=(33, 64), help="-qtrim: the offset of the quality characters [33]")
+    p.add_argument("-adapt", type=str, nargs="?", const="", default=None, metavar="FILE",
+                   help="FASTQ input, with or without -skipclean: remove 3' adapters from the reads on the GPU before -qtrim and the "
+                        "count see them. The first job of the fastp run MerCat2 starts, as a stated rule that is not fastp's: a read "
+                        "is cut at the leftmost position where an adapter matches the rest of it, or runs off its end (no indels, no "
+                        "mate-overlap detection). FILE: a FASTA file of up to 1024 adapters of up to 128 bases [the Illumina TruSeq, "
+                        "Nextera and small-RNA adapters]; writes adapt/<sample>_adapt.fastq, _adapt.tsv and _summary.tsv")
+    p.add_argument("-adapt_overlap", type=int, default=None, metavar="N",
+                   help="-adapt: the fewest bases an adapter must cover [8: set for a panel of hundreds of adapters, which at "
+                        "cutadapt's 3 for one adapter would cut the end of most adapter-free reads by chance]")
+    p.add_argument("-adapt_err", type=float, default=None, metavar="F", help="-adapt: mismatches allowed, as a fraction (0..1) of the overlap [0.1]")
+    p.add_argument("-adapt_len", type=int, default=None, metavar="N", help="-adapt: drop a read of which fewer than N bases remain [1]")
     p.add_argument("-toupper", action="store_true", help="convert all input sequences to uppercase [False]")
     # flags of the reference's other layers (bin/mercat2.py:45-58)
     p.add_argument("-prod", action="store_true", help="(MerCat2: ORF calling with prodigal) not part of this engine")
@@ -295,6 +312,34 @@ def parseargs(argv=None):
             p.error(f"-qtrim_low_frac {args.qtrim_low_frac}: must lie in 0..1")
         if args.qtrim_low_frac is not None and not args.qtrim_low:
             p.error("-qtrim_low_frac needs -qtrim_low Q: no base is low without it")
+    args.adapters = None
+    if args.adapt is None:
+        for flag in ("adapt_overlap", "adapt_err", "adapt_len"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -adapt")
+    else:
+        given = list(args.i)
+        if args.f and os.path.isdir(args.f):
+            given += sorted(os.listdir(args.f))
+        if not any(fastq_ext(Path(name)) for name in given):
+            p.error(f"-adapt trims FASTQ reads ({' / '.join(FILE_EXT_FASTQ)}); no input is a FASTQ file")
+        if args.adapt_overlap is not None and not 1 <= args.adapt_overlap <= 128:
+            p.error(f"-adapt_overlap {args.adapt_overlap}: must lie in 1..128")
+        if args.adapt_err is not None and not 0.0 <= args.adapt_err <= 1.0:
+            p.error(f"-adapt_err {args.adapt_err}: must lie in 0..1")
+        if args.adapt_len is not None and not 0 <= args.adapt_len < 1 << 32:
+            p.error(f"-adapt_len {args.adapt_len}: must lie in 0..2^32 - 1")
+        if args.adapt:
+            if not os.path.isfile(args.adapt):
+                p.error(f"file '{args.adapt}' is not valid.\n")
+            from .native import read_adapters
+            try:
+                names, seqs = read_adapters(args.adapt)
+            except ValueError as e:
+                p.error(f"-adapt: {e}")
+            if len(set(seqs)) > 1024 or max(len(s) for s in seqs) > 128:
+                p.error(f"-adapt {args.adapt}: at most 1024 distinct adapters of at most 128 bases each")
+            args.adapters = list(zip(names, seqs))
     if args.histo is not None and not 1 <= args.histo <= 1 << 20:
         p.error(f"-histo {args.histo}: HIGH must lie in 1..{1 << 20}")
     args.screen_kind = None
@@ -576,6 +621,34 @@ def qtrim_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes
     return done["text"]
 
 
+def adapt_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
+    """-adapt: the reads of FASTQ sample ``base`` (``raw``: its bytes if they are in memory already, else None and ``f``
+    is read) with their 3' adapters removed on GPU ``device`` by kmers.adapt_reads, which writes
+    adapt/<base>_adapt.fastq, _adapt.tsv and _summary.tsv; returns the text that is left, which -qtrim and the count see
+    in the raw reads' place."""
+    from . import kmers, native
+    folder = out / "adapt"
+    folder.mkdir(parents=True, exist_ok=True)
+    try:
+        done = kmers.adapt_reads(
+            f if raw is None else raw, folder / f"{base}_adapt.fastq", adapters=args.adapters,
+            min_overlap=8 if args.adapt_overlap is None else args.adapt_overlap, max_err=0.1 if args.adapt_err is None else args.adapt_err,
+            min_len=args.adapt_len or 0, tsv_path=folder / f"{base}_adapt.tsv", summary_path=folder / f"{base}_summary.tsv",
+            device=device, keep_text=True)
+    except native.MercatHipError as e:
+        raise SystemExit(f"-adapt '{f.name}': {e}")
+    return done["text"]
+
+
+def prepared_reads(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
+    """The reads of FASTQ sample ``base`` as the count sees them: through -adapt, then through -qtrim, where given."""
+    if args.adapt is not None:
+        raw = adapt_sample(args, f, raw, out, base, device)
+    if args.qtrim is not None:
+        raw = qtrim_sample(args, f, raw, out, base, device)
+    return read_fasta_bytes(f) if raw is None else raw
+
+
 def count_converted(base: str, holder: dict, fut, tsv: Path, args, devices, home: int, lines: list, tables: dict, t: dict) -> None:
     """The table of a sample whose text a background job rewrites (removeN) or converts (fq2fa) and writes as a level-9
     .gz, counted from the text in memory: the reference cuts the REWRITTEN file, and its size on disk decides
@@ -657,7 +730,7 @@ def main(argv=None) -> int:
     samples = {"nucleotide": {}, "protein": {}}
     fastq = set()  # nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)
     for f in files:
-        kind, base = classify(f.expanduser().absolute(), args.skipclean or args.qtrim is not None)
+        kind, base = classify(f.expanduser().absolute(), args.skipclean or args.qtrim is not None or args.adapt is not None)
         if kind:
             samples[kind][base] = f
             if fastq_ext(f):
@@ -698,9 +771,9 @@ def main(argv=None) -> int:
             t0 = timeit.default_timer()
             raw = read_fasta_bytes(f)
             t["read_s"] = timeit.default_timer() - t0
-            if base in fastq and args.qtrim is not None:
+            if base in fastq and (args.qtrim is not None or args.adapt is not None):
                 t0 = timeit.default_timer()
-                raw = qtrim_sample(args, f, raw, out, base, home_of[base])
+                raw = prepared_reads(args, f, raw, out, base, home_of[base])
                 t["qtrim_s"] = timeit.default_timer() - t0
             if base in fastq:
                 path, fut, holder = fq2fa_background(f, raw, out / "clean", base, gz_writers, timings=t, limit=args.s * 1024 * 1024)
@@ -741,7 +814,7 @@ def main(argv=None) -> int:
             if kind == "nucleotide" and base in fastq:
                 limit = args.s * 1024 * 1024
                 if cleaned[base] is None:  # (not loaded up front: the conversion, its file, then the count)
-                    text, _ = fq2fa_text(qtrim_sample(args, f, None, out, base, home) if args.qtrim is not None else read_fasta_bytes(f))
+                    text, _ = fq2fa_text(prepared_reads(args, f, None, out, base, home))
                     os.makedirs(out / "clean", exist_ok=True)
                     size = _write_clean_gz(out / "clean" / f"{base}.fna.gz", text, t)
                     chunked = args.s > 0 and size >= limit

@@ -1,0 +1,340 @@
+// mk_fqpiece.h -- what the calls that read a FASTQ text, judge every record by a scan kernel of their own and write the
+// survivors cut share: mk_fastq_qtrim_* (mk_qtrim.hip) and mk_fastq_adapt_* (mk_adapt.hip).
+//   device side   QtLine (a line's content seen through aligned 16-byte granules), qt_record (the lines of a record and
+//                 its checks), fq_segments (the four segments of an emitted record from its span).
+//   host side     FqCall<P> (the state of a call), fq_piece<P> (one piece: line index, P::scan, P::decide, the prefix
+//                 sum, the gather, the copies back), fq_run (how a call checks, opens and ends), fq_device_body /
+//                 fq_text_body (the one piece of a device call, the piece loop of a text call).
+// A policy P names what differs:
+//   Opt, Status (device counters behind the FsStatus of a piece), Stats (the call's mk_fastq_*_t), Side (what the scan
+//   kernel reads or writes beside the text), ROW (uint64 a row),
+//   paired(o), kind(k) (the phrase of a failed check), scan(...), decide(...), add(stats, status).
+#pragma once
+#include "mk_fqindex.h"
+
+#define QT_GROUP 16u
+#define QT_PASS (QT_GROUP * 16u)
+
+// A line's content [a, a + L) seen through aligned granules: pass p, lane j owns the 16 bytes at (a & ~15) + 256 p + 16 j,
+// whose byte b is content index i0 + b.  A granule that holds no byte of the content is not loaded.
+struct QtLine {
+  u64 a, L;
+  __device__ __forceinline__ unsigned passes() const { return (unsigned)(((a & 15) + L + QT_PASS - 1) / QT_PASS); }
+  __device__ __forceinline__ long long i0(unsigned p, unsigned j) const { return (long long)p * QT_PASS + 16 * j - (long long)(a & 15); }
+  __device__ __forceinline__ FsSeg load(const uint8_t* __restrict__ text, u64 n, unsigned p, unsigned j) const {
+    const long long i = i0(p, j);
+    if (i + 16 <= 0 || i >= (long long)L) {
+      FsSeg s;
+      s.w[0] = s.w[1] = s.w[2] = s.w[3] = 0;
+      s.len = 0;
+      s.nlmask = 0;
+      return s;
+    }
+    return fs_load(text, n, (a & ~(u64)15) + (u64)p * QT_PASS + 16 * j);
+  }
+};
+#define QT_BYTE(c, b) (((c).w[(b) >> 2] >> (8 * ((b)&3))) & 0xFFu)
+
+// The lines of record r and what the checks on them say: the contents of the sequence line [l1, l1 + ls) and of the
+// quality line [l3, l3 + lq), one trailing '\r' taken off each.
+struct QtRecord {
+  u64 l0, l1, l2, l3, l4, ls, lq;
+  bool has_nl;  // the last line ends in '\n'
+  int fail;
+};
+__device__ __forceinline__ QtRecord qt_record(const uint8_t* __restrict__ text, const u64* __restrict__ line, size_t r) {
+  QtRecord q;
+  q.l0 = line[4 * r]; q.l1 = line[4 * r + 1]; q.l2 = line[4 * r + 2]; q.l3 = line[4 * r + 3]; q.l4 = line[4 * r + 4];
+  q.ls = q.l2 - 1 - q.l1;
+  const bool seq_cr = q.ls > 0 && text[q.l2 - 2] == 13u;
+  q.ls -= seq_cr ? 1 : 0;
+  q.has_nl = text[q.l4 - 1] == 10u;
+  q.lq = q.l4 - (q.has_nl ? 1 : 0) - q.l3;
+  const bool qual_cr = q.lq > 0 && text[q.l3 + q.lq - 1] == 13u;
+  q.lq -= qual_cr ? 1 : 0;
+  q.fail = text[q.l0] != '@' ? FS_AT : text[q.l2] != '+' ? FS_PLUS : q.ls != q.lq ? FS_LENGTH : -1;
+  return q;
+}
+
+// The four segments of an emitted record whose span is [start, start + kept) of its L bases: whole = {record, -, -, -},
+// cut = {header line, seq[span] '\n', plus line, qual[span] '\n'}; unused ones have length 0.  True for a cut record.
+__device__ __forceinline__ bool fq_segments(const QtRecord& q, u64 L, u64 start, u64 kept, u64 s[4], u64 m[4]) {
+  if (start == 0 && kept == L) {
+    s[0] = q.l0 | (q.has_nl ? 0 : FS_FORCE);
+    m[0] = q.l4 - q.l0 + (q.has_nl ? 0 : 1);
+    return false;
+  }
+  s[0] = q.l0;
+  m[0] = q.l1 - q.l0;
+  s[1] = (q.l1 + start) | FS_FORCE;
+  m[1] = kept + 1;
+  s[2] = q.l2;
+  m[2] = q.l3 - q.l2;
+  s[3] = (q.l3 + start) | FS_FORCE;
+  m[3] = kept + 1;
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------ host side
+template <class P>
+struct FqCall {
+  mk_ctx* c;
+  const char* what;
+  typename P::Opt o;
+  size_t limit;   // records the caller's arrays hold
+  uint8_t* keep;  // the caller's arrays (host memory for the text call, device memory for the device call), or nullptr
+  u64* rows;
+  uint8_t* out;
+  size_t out_cap;
+  bool device;
+  typename P::Side side;
+  MkDevBuf tiles, meta, scan_tmp, stage, side_buf;
+  MkTimed index, scan, place, gather;
+  typename P::Stats st{};
+  size_t records = 0, bytes_out = 0;  // of all pieces so far
+  int bad_rc = MK_OK;                 // the first record that failed a check (pieces come in text order)
+  std::string bad_msg;
+  FqCall(mk_ctx* c_, const char* w, const typename P::Opt& o_, size_t lim, uint8_t* kp, u64* rw, uint8_t* ot, size_t oc, bool dev)
+      : c(c_), what(w), o(o_), limit(lim), keep(kp), rows(rw), out(ot), out_cap(oc), device(dev), side{}, index(c_), scan(c_), place(c_),
+        gather(c_) {}
+  ~FqCall() {
+    for (MkDevBuf* b : {&tiles, &meta, &scan_tmp, &stage, &side_buf}) buf_free(*b);
+  }
+  bool counting_only() const { return bad_rc != MK_OK || records > limit; }
+};
+
+// One piece of n > 0 bytes at d_text (device memory, 16-byte aligned, whole records -- whole pairs with paired -- but for
+// what trails in the last piece).  Its records are added to f.records either way.  The stream is idle afterwards.
+template <class P>
+static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
+  typedef typename P::Status Status;
+  constexpr size_t ROW = P::ROW;
+  mk_ctx* c = f.c;
+  int rc;
+  const size_t ntiles = div_up(n, FS_TILE);
+  // tiles: FsStatus | Status | tile_pre[ntiles] | tile_cnt[ntiles]
+  if ((rc = mk_buf_reserve(c, f.tiles, sizeof(FsStatus) + sizeof(Status) + ntiles * (sizeof(u64) + sizeof(unsigned)))) != MK_OK) return rc;
+  FsStatus* d_st = (FsStatus*)f.tiles.p;
+  Status* d_qs = (Status*)(d_st + 1);
+  u64* tile_pre = (u64*)(d_qs + 1);
+  unsigned* tile_cnt = (unsigned*)(tile_pre + ntiles);
+  struct { FsStatus s; Status q; } h{};
+  h.s.bad = FS_NONE;
+  MK_HIP(hipMemcpyAsync(d_st, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+  if ((rc = f.index.begin()) != MK_OK) return rc;
+  hipLaunchKernelGGL(fs_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_text, (u64)n, tile_cnt);
+  hipLaunchKernelGGL(fs_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, d_st);
+  MK_HIP(hipGetLastError());
+  if ((rc = f.index.end()) != MK_OK) return rc;
+  uint8_t tail[4] = {0, 0, 0, 0};
+  const size_t ntail = std::min<size_t>(n, 4);
+  u64 newlines = 0;
+  MK_HIP(hipMemcpyAsync(&newlines, &d_st->newlines, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(tail + (4 - ntail), d_text + (n - ntail), ntail, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = f.index.add_to(f.st.s_index)) != MK_OK) return rc;
+  const u64 lines = newlines + (tail[3] != '\n' ? 1 : 0);
+  const size_t nrec = (size_t)(lines / 4), first = f.records;
+  const unsigned trailing = (unsigned)(lines & 3);
+  f.st.lines += lines;
+  f.records += nrec;
+  // what trails behind the last complete record: `trailing` empty lines are that many '\n' behind a '\n' (or the text's start)
+  bool trail_ok = true;
+  for (unsigned i = 0; i < trailing && trail_ok; ++i) trail_ok = tail[3 - i] == '\n';
+  if (trailing && trail_ok && n > trailing) trail_ok = tail[3 - trailing] == '\n';
+  if (f.counting_only()) return MK_OK;
+  const auto fail_trailing = [&]() {
+    f.bad_rc = MK_ERR_UNSUPPORTED;
+    f.bad_msg = std::string(f.what) + ": record " + std::to_string(first + nrec) + " is malformed: the text ends inside it (" +
+                std::to_string(trailing) + " of its 4 lines)";
+    return MK_OK;
+  };
+  if (!nrec) return trail_ok ? MK_OK : fail_trailing();
+
+  // meta: line[4 nrec + 1] | seg_src[nseg + 1] | len[nseg + 1] | dst[nseg + 1] | rows[ROW nrec] | verdict[nrec] | keep[nrec]
+  const size_t nseg = 4 * nrec, nidx = 4 * nrec;
+  if ((rc = mk_buf_reserve(c, f.meta, (nidx + 1 + 3 * (nseg + 1) + ROW * nrec) * sizeof(u64) + 2 * nrec)) != MK_OK) return rc;
+  u64* line = (u64*)f.meta.p;
+  u64* seg_src = line + nidx + 1;
+  u64* len = seg_src + nseg + 1;
+  u64* dst = len + nseg + 1;
+  u64* d_rows = dst + nseg + 1;
+  uint8_t* d_verdict = (uint8_t*)(d_rows + ROW * nrec);
+  uint8_t* d_keep = d_verdict + nrec;
+  if (f.device && f.rows) d_rows = f.rows + ROW * first;
+  if (f.device && f.keep) d_keep = f.keep + first;
+  size_t tmp = 0;
+  MK_HIP(rocprim::exclusive_scan((void*)nullptr, tmp, (const u64*)len, dst, 0ull, nseg + 1, rocprim::plus<u64>(), c->stream));
+  if ((rc = mk_buf_reserve(c, f.scan_tmp, tmp ? tmp : 16)) != MK_OK) return rc;
+
+  if ((rc = f.index.begin()) != MK_OK) return rc;
+  const int end_is_n = lines == nidx ? 1 : 0;  // (no line 4 nrec starts: the last record ends with the text)
+  hipLaunchKernelGGL(fs_lines_k<false>, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_text, (u64)n, (const u64*)tile_pre, (u64)nidx,
+                     end_is_n, line, d_st);
+  MK_HIP(hipGetLastError());
+  if ((rc = f.index.end()) != MK_OK) return rc;
+  if ((rc = f.scan.begin()) != MK_OK) return rc;
+  P::scan(f, d_text, n, (const u64*)line, nrec, d_rows, d_verdict, d_st);
+  MK_HIP(hipGetLastError());
+  if ((rc = f.scan.end()) != MK_OK) return rc;
+  if ((rc = f.place.begin()) != MK_OK) return rc;
+  // (the lengths are only added up before the status below has been read: no address is made of them)
+  P::decide(f, d_text, (const u64*)line, nrec, (const u64*)d_rows, (const uint8_t*)d_verdict, d_keep, seg_src, len, d_st, d_qs);
+  MK_HIP(hipGetLastError());
+  MK_HIP(rocprim::exclusive_scan(f.scan_tmp.p, tmp, (const u64*)len, dst, 0ull, nseg + 1, rocprim::plus<u64>(), c->stream));
+  if ((rc = f.place.end()) != MK_OK) return rc;
+  u64 piece_out = 0;
+  MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&piece_out, dst + nseg, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = f.index.add_to(f.st.s_index)) != MK_OK) return rc;
+  if ((rc = f.scan.add_to(f.st.s_scan)) != MK_OK) return rc;
+  if ((rc = f.place.add_to(f.st.s_place)) != MK_OK) return rc;
+  if (h.s.bad != FS_NONE) {
+    f.bad_rc = MK_ERR_UNSUPPORTED;
+    f.bad_msg = std::string(f.what) + ": record " + std::to_string(first + (size_t)(h.s.bad >> 3)) + " is malformed: " +
+                P::kind((unsigned)(h.s.bad & 7));
+    return MK_OK;
+  }
+  if (!trail_ok) return fail_trailing();
+  if (piece_out > (u64)n + 1) {
+    c->err = std::string(f.what) + ": the output of a piece is longer than its records (internal error)";
+    return MK_ERR_STATE;
+  }
+  f.st.records_out += h.s.records_out;
+  f.st.records_trimmed += h.s.records_trimmed;
+  f.st.bases_out += h.s.bases_out;
+  P::add(f.st, h.q);
+  if (!f.device && (f.keep || f.rows)) {
+    const auto t1 = MkClock::now();
+    if (f.keep) MK_HIP(hipMemcpyAsync(f.keep + first, d_keep, nrec, hipMemcpyDeviceToHost, c->stream));
+    if (f.rows) MK_HIP(hipMemcpyAsync(f.rows + ROW * first, d_rows, ROW * nrec * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    f.st.s_write += mk_since(t1);
+  }
+
+  // the gather: into the caller's device memory, or into a staging buffer that is copied to the host.  Without room the
+  // call goes on adding up and answers MK_ERR_RANGE at its end.
+  const size_t at = f.bytes_out;
+  f.bytes_out += (size_t)piece_out;
+  if (!piece_out || f.bytes_out > f.out_cap) return MK_OK;
+  uint8_t* d_out = f.out + at;
+  if (!f.device) {
+    if ((rc = mk_buf_reserve(c, f.stage, (size_t)piece_out)) != MK_OK) return rc;
+    d_out = (uint8_t*)f.stage.p;
+  }
+  const u64 head = std::min<u64>((16 - ((uintptr_t)d_out & 15)) & 15, piece_out);
+  const u64 nbody = (piece_out - head) / 16, tail_at = head + 16 * nbody;
+  if ((rc = f.gather.begin()) != MK_OK) return rc;
+  if (nbody)
+    hipLaunchKernelGGL(fs_gather_k, dim3((unsigned)div_up((size_t)nbody, 256 * FS_CHUNKS)), dim3(256), 0, c->stream, d_text, (u64)n,
+                       (const u64*)seg_src, (const u64*)dst, nseg, head, nbody, d_out);
+  if (head || tail_at < piece_out)
+    hipLaunchKernelGGL(fs_edges_k, dim3(1), dim3(64), 0, c->stream, d_text, (u64)n, (const u64*)seg_src, (const u64*)dst, nseg, head,
+                       tail_at, piece_out, d_out);
+  MK_HIP(hipGetLastError());
+  if ((rc = f.gather.end()) != MK_OK) return rc;
+  MK_HIP(hipStreamSynchronize(c->stream));
+  if ((rc = f.gather.add_to(f.st.s_gather)) != MK_OK) return rc;
+  if (!f.device) {
+    const auto t1 = MkClock::now();
+    MK_HIP(hipMemcpyAsync(f.out + at, d_out, (size_t)piece_out, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    f.st.s_write += mk_since(t1);
+  }
+  return MK_OK;
+}
+
+// How both kinds of call check their arguments, open and end; pre(): what the call sets up on the device before the first
+// piece; body(): the pieces; post(): what it copies back once the call is known to succeed.
+template <class P, class Pre, class Body, class Post>
+static int fq_run(FqCall<P>& f, size_t* out_len, size_t* nrec, typename P::Stats* st, Pre&& pre, Body&& body, Post&& post) {
+  mk_ctx* c = f.c;
+  MK_REFUSE_SPOILED(c, f.what);
+  if (c->in_chunk) { c->err = std::string(f.what) + ": a chunk is open"; return MK_ERR_STATE; }
+  if (!out_len) { c->err = std::string(f.what) + ": out_len is NULL"; return MK_ERR_ARG; }
+  *out_len = 0;
+  if (nrec) *nrec = 0;
+  MK_HIP(hipSetDevice(c->device));
+  MK_HIP(hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = pre()) != MK_OK) return rc;
+  rc = body();
+  (void)hipStreamSynchronize(c->stream);
+  if (rc != MK_OK) return rc;
+  if (nrec) *nrec = f.records;
+  if (f.records > f.limit) {
+    c->err = std::string(f.what) + ": the text holds " + std::to_string(f.records) + " records, keep and rows have room for " +
+             std::to_string(f.limit);
+    return MK_ERR_RANGE;
+  }
+  if (P::paired(f.o) && (f.records & 1)) {
+    c->err = std::string(f.what) + ": paired, but the text holds an odd number of records (" + std::to_string(f.records) + ")";
+    return MK_ERR_RANGE;
+  }
+  if (f.bad_rc != MK_OK) {
+    c->err = f.bad_msg;
+    return f.bad_rc;
+  }
+  if ((rc = post()) != MK_OK) return rc;
+  *out_len = f.bytes_out;
+  f.st.records = f.records;
+  f.st.bytes_out = f.bytes_out;
+  if (st) *st = f.st;
+  if (f.bytes_out > f.out_cap) {
+    c->err = std::string(f.what) + ": the output holds " + std::to_string(f.bytes_out) + " bytes, out has room for " + std::to_string(f.out_cap);
+    return MK_ERR_RANGE;
+  }
+  return MK_OK;
+}
+
+// The one piece of a device call: the text where it stands, or copied to c->raw where it is not aligned to 16 (the line
+// passes, the scans and fl_load16 load 16 aligned bytes at a time).
+template <class P>
+static int fq_device_body(FqCall<P>& f, const uint8_t* d_fastq, size_t n) {
+  mk_ctx* c = f.c;
+  if (!n) return MK_OK;
+  const uint8_t* d_text = d_fastq;
+  if ((uintptr_t)d_text & 15) {
+    int rc = mk_buf_reserve(c, c->raw, n + 64);
+    if (rc != MK_OK) return rc;
+    const auto t1 = MkClock::now();
+    MK_HIP(hipMemcpyAsync(c->raw.p, d_fastq, n, hipMemcpyDeviceToDevice, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    f.st.s_copy += mk_since(t1);
+    d_text = (const uint8_t*)c->raw.p;
+  }
+  return fq_piece(f, d_text, n);
+}
+
+// The pieces of a text call: they end behind a line 4j (8j: mates stay together) once they hold `piece` bytes: the default
+// and the limits of the screen calls.
+template <class P>
+static int fq_text_body(FqCall<P>& f, const uint8_t* fastq, size_t n, size_t piece_bytes) {
+  mk_ctx* c = f.c;
+  if (!n) return MK_OK;
+  size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
+  piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
+  std::vector<uint64_t> cuts(n / piece + 2, 0);
+  size_t ncuts = 0;
+  if ((P::paired(f.o) ? mk_fastq_pair_cuts : mk_fastq_cuts)(fastq, n, piece, cuts.data(), cuts.size(), &ncuts) != MK_OK) {
+    c->err = std::string(f.what) + ": the line scanner failed (internal error)";
+    return MK_ERR_STATE;
+  }
+  cuts.resize(ncuts);
+  cuts.push_back(n);
+  size_t at = 0;
+  for (const uint64_t end : cuts) {
+    const size_t len = (size_t)end - at;
+    if (!len) continue;
+    int rc = mk_buf_reserve(c, c->raw, len + 64);
+    if (rc != MK_OK) return rc;
+    const auto t1 = MkClock::now();
+    MK_HIP(hipMemcpyAsync(c->raw.p, fastq + at, len, hipMemcpyHostToDevice, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    f.st.s_copy += mk_since(t1);
+    if ((rc = fq_piece(f, (const uint8_t*)c->raw.p, len)) != MK_OK) return rc;
+    at = (size_t)end;
+  }
+  return MK_OK;
+}

@@ -612,3 +612,83 @@ def qtrim_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None],
     if keep_text:
         done["text"] = out
     return done
+
+
+def _named_adapters(adapters) -> Tuple[List[str], List[str]]:
+    """(names, seqs) of ``adapters``: None (native.ILLUMINA_ADAPTERS), a FASTA file (native.read_adapters), (name, seq)
+    pairs, or plain sequences, which are named by themselves."""
+    if adapters is None:
+        adapters = native.ILLUMINA_ADAPTERS
+    if isinstance(adapters, (str, Path)):
+        return native.read_adapters(adapters)
+    names, seqs = [], []
+    for a in adapters:
+        name, seq = a if isinstance(a, tuple) else (None, a)
+        seq = seq.decode("latin-1") if isinstance(seq, (bytes, bytearray)) else str(seq)
+        names.append(seq if name is None else str(name))
+        seqs.append(seq)
+    return names, seqs
+
+
+def adapt_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None], adapters=None, adapters2=None, min_overlap: int = 8,
+                max_err: float = 0.1, min_len: int = 0, paired: bool = False, tsv_path: Union[str, Path, None] = None,
+                summary_path: Union[str, Path, None] = None, mate_file: Union[str, Path, None] = None,
+                out_path2: Union[str, Path, None] = None, singles_path: Union[str, Path, None] = None, device: int = 0,
+                keep_text: bool = False) -> Dict[str, object]:
+    """The reads of a FASTQ file ('.fq' / '.fastq', plain or '.gz'; or the FASTQ text itself as bytes) with their 3'
+    adapters removed on the GPU (Counter.fastq_adapt has the rule: the leftmost position at which an adapter matches the
+    rest of the read, or runs off its end, over ``min_overlap`` bases within ``max_err`` mismatches a base; no indels),
+    written as FASTQ to ``out_path`` -- gzip (level 1) if that name ends in '.gz'.  This is the first job of the fastp
+    run MerCat2 starts; its result is this stated rule's, not fastp's.  ``adapters``: None (native.ILLUMINA_ADAPTERS:
+    TruSeq, Nextera, small RNA), a FASTA file, (name, sequence) pairs or sequences; ``adapters2``: the same for second
+    mates (pairs only).  The default overlap of 8 is set for a panel of hundreds of adapters, not for one.  No table is
+    read: the call opens a small context of its own on ``device``.
+    Paired reads (``paired``: the file is interleaved; or ``mate_file``: the second file): a pair is written iff both
+    mates keep max(``min_len``, 1) bases, interleaved to ``out_path`` or split into ``out_path`` and ``out_path2``;
+    ``singles_path`` receives the reads that pass while their mate does not.  ``tsv_path``: every record's name, row and
+    keep value (report.write_adapt_tsv); ``summary_path``: reads and bases before and after, reads trimmed and dropped,
+    and the hits of every adapter that has any (report.write_adapt_summary).  Returns the mk_fastq_adapt_t figures,
+    "hits", "adapter_names" and, with ``keep_text``, the main output under "text" (interleaved for pairs)."""
+    is_paired = _is_paired(paired, mate_file, out_path2, singles_path)
+    is_text = isinstance(file, (bytes, bytearray, memoryview))
+    for f in (None if is_text else file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("adapt_reads: needs FASTQ input (%s), not %s" % (" / ".join(FASTQ_SUFFIXES), f))
+    if adapters2 is not None and not is_paired:
+        raise ValueError("adapt_reads: adapters2 are searched in second mates: needs paired reads")
+    names, seqs = _named_adapters(adapters)
+    names2, seqs2 = _named_adapters(adapters2) if adapters2 is not None else ([], None)
+    raw = bytes(file) if is_text else read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    opts = dict(min_overlap=min_overlap, max_err=max_err, min_len=min_len, paired=is_paired)
+    info: Dict[str, object] = {}
+    with native.Counter(5, native.ALPHABET_NT2, device=device) as ctx:
+        out, keep, rows, hits = ctx.fastq_adapt(raw, seqs, seqs2, which=1, info=info, **opts)
+        singles = ctx.fastq_adapt(raw, seqs, seqs2, which=2, **opts)[0] if singles_path is not None else None
+    # the panel holds every distinct sequence once: its names are those of the first record that has it
+    first_name: Dict[str, str] = {}
+    for name, seq in zip(names + names2, seqs + (seqs2 or [])):
+        first_name.setdefault(seq, name)
+    panel_names = [first_name[seq] for seq in info.pop("adapters")]
+    if out_path is not None:
+        if out_path2 is None:
+            _write_reads(out_path, out)
+        else:
+            first, second = native.split_pairs_fastq(out)
+            _write_reads(out_path, first)
+            _write_reads(out_path2, second)
+    if singles_path is not None:
+        _write_reads(singles_path, singles or b"")
+    if tsv_path is not None:
+        from .report import write_adapt_tsv
+        write_adapt_tsv(tsv_path, fastq_names(raw), rows, keep, panel_names)
+    if summary_path is not None:
+        from .report import write_adapt_summary
+        write_adapt_summary(summary_path, info, hits, panel_names)
+    done: Dict[str, object] = {name: value for name, value in info.items() if not name.startswith("s_")}
+    done["hits"] = hits
+    done["adapter_names"] = panel_names
+    if keep_text:
+        done["text"] = out
+    return done

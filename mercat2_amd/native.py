@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
     "mk_fastq_select_text", "mk_fastq_select_device", "mk_fastq_cuts", "mk_fq_interleave", "mk_fq_split_pairs",
     "mk_fastq_qtrim_text", "mk_fastq_qtrim_device", "mk_fastq_pair_cuts",
+    "mk_adapters_pack", "mk_fastq_adapt_text", "mk_fastq_adapt_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -319,6 +320,107 @@ def qtrim_options(cut_back: int = 20, cut_front: int = 0, min_len: int = 0, max_
     return QtrimOpt(**{name: int(v) for name, v in vals.items()})
 
 
+class AdaptOpt(C.Structure):
+    """mk_adapt_opt_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("min_overlap", "max_err_ppm", "min_len", "paired", "which")]
+
+
+class FastqAdapt(C.Structure):
+    """mk_fastq_adapt_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("records", "records_out", "records_trimmed", "dropped_short", "orphans", "bases_in",
+                                           "bases_out", "bytes_out", "lines")] +
+                [(n, C.c_double) for n in ("s_copy", "s_index", "s_scan", "s_place", "s_gather", "s_write")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+ADAPT_COLUMNS = ("length", "kept", "adapter", "overlap", "mismatches")  # the columns of Counter.fastq_adapt's rows
+ADAPT_NO_HIT = 0xFFFFFFFF  # the adapter column of a read without a hit
+ADAPT_PANEL_STRIDE = 9  # 64-bit words an adapter in mk_adapters_pack's panel, behind the one word that holds A
+# the 3' adapters of the common Illumina library kits, as cutadapt's and fastp's manuals give them
+ILLUMINA_ADAPTERS = (("TruSeq", "AGATCGGAAGAGC"), ("Nextera", "CTGTCTCTTATACACATCT"), ("small_RNA", "TGGAATTCTCGGGTGCCAAGG"))
+
+
+def adapt_options(min_overlap: int = 8, max_err: float = 0.1, min_len: int = 0, paired: bool = False, which: int = 1) -> "AdaptOpt":
+    """mk_adapt_opt_t of Counter.fastq_adapt's arguments; ValueError for one that no uint32 holds or an error rate outside
+    0..1 (the library checks the ranges the rule sets)."""
+    vals = dict(min_overlap=min_overlap, max_err_ppm=ppm_of_fraction(max_err), min_len=min_len, paired=1 if paired else 0, which=which)
+    for name, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s %r: must lie in 0..2^32-1" % (name, v))
+    return AdaptOpt(**{name: int(v) for name, v in vals.items()})
+
+
+def read_adapters(path, check: bool = True) -> Tuple[list, list]:
+    """(names, seqs) of the FASTA file ``path`` (plain or '.gz', records of any number of lines): the first word behind
+    every '>' and the record's bases as str, blanks and tabs at line ends stripped.  A '>' line with no bases behind it
+    is no record.  ValueError for a file without records and, with ``check``, naming the first record that holds a byte
+    outside ACGTNacgtn (``check`` False: the records as they stand)."""
+    import gzip
+    with (gzip.open(path, "rb") if str(path).lower().endswith(".gz") else open(path, "rb")) as fh:
+        raw = fh.read()
+    names, seqs = [], []
+    for line in raw.split(b"\n"):
+        line = line.rstrip(b" \t\r")
+        if line.startswith(b">"):
+            if names and not seqs[-1]:
+                names.pop()
+                seqs.pop()
+            names.append((line[1:].split() or [b""])[0].decode("utf-8", "replace"))
+            seqs.append(b"")
+        elif line:
+            if not names:
+                raise ValueError("read_adapters: %s does not start with a '>' line" % (path,))
+            seqs[-1] += line
+    if names and not seqs[-1]:
+        names.pop()
+        seqs.pop()
+    if not names:
+        raise ValueError("read_adapters: %s holds no record" % (path,))
+    for i, (name, seq) in enumerate(zip(names, seqs)):
+        bad = seq.translate(None, b"ACGTNacgtn")
+        if bad and check:
+            raise ValueError("read_adapters: record %d ('%s') of %s holds the byte 0x%02X: adapters are of ACGTN" % (i, name, path, bad[0]))
+    return names, [s.decode("latin-1") for s in seqs]
+
+
+def adapter_arrays(adapters, adapters2=None):
+    """(bases, lengths, mates, seqs) as mk_fastq_adapt_* take them, of sequences (str or bytes) for first mates and
+    unpaired reads (``adapters``) and for second mates (``adapters2``): every distinct sequence once, in the order of
+    its first appearance, with class 1, 2 or -- where both lists hold it -- 3.  ``seqs``: those sequences as str."""
+    as_bytes = lambda a: a.encode() if isinstance(a, str) else bytes(a)
+    order, cls = [], {}
+    for group, bit in ((adapters or (), 1), (adapters2 or (), 2)):
+        for a in group:
+            a = as_bytes(a)
+            if a not in cls:
+                order.append(a)
+            cls[a] = cls.get(a, 0) | bit
+    bases = np.frombuffer(b"".join(order), dtype=np.uint8).copy() if order else np.zeros(0, np.uint8)
+    lengths = np.array([len(a) for a in order], dtype=np.uint32)
+    mates = np.array([cls[a] for a in order], dtype=np.uint8)
+    return bases, lengths, mates, [a.decode("latin-1") for a in order]
+
+
+def pack_adapters(bases, lengths, mates=None) -> np.ndarray:
+    """mk_adapters_pack: the packed panel (uint64 words; include/mercat_hip.h has the layout) of the adapters whose
+    characters stand back to back in ``bases`` (uint8) with ``lengths`` (uint32) and mate classes ``mates`` (uint8, None:
+    all 1).  Host code: no GPU is needed.  MercatHipError with the library's message for a refused panel."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    if mates is not None:
+        mates = np.ascontiguousarray(mates, dtype=np.uint8)
+    A = int(lengths.shape[0])
+    words = np.zeros(1 + ADAPT_PANEL_STRIDE * max(min(A, 1024), 1), dtype=np.uint64)
+    nwords, err = C.c_size_t(0), C.create_string_buffer(256)
+    rc = lib().mk_adapters_pack(bases.ctypes.data, lengths.ctypes.data, mates.ctypes.data if mates is not None else None, A,
+                                words.ctypes.data, words.shape[0], C.byref(nwords), err, 256)
+    if rc:
+        raise MercatHipError(rc, err.value.decode())
+    return words[: nwords.value]
+
+
 def ppm_of_fraction(min_frac: float) -> int:
     """min_ppm of mk_filter_rule_t for "at least this fraction of the record's k-mers are hits": round(min_frac * 10^6);
     ValueError outside 0..1 (and for a NaN)."""
@@ -521,6 +623,13 @@ def lib() -> C.CDLL:
                                           C.c_void_p, C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqQtrim)]),
         "mk_fastq_qtrim_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(QtrimOpt), C.c_size_t, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqQtrim)]),
+        "mk_adapters_pack": (C.c_int, [u8p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_char_p, C.c_size_t]),
+        "mk_fastq_adapt_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, u8p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AdaptOpt),
+                                          C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, szp,
+                                          C.POINTER(FastqAdapt)]),
+        "mk_fastq_adapt_device": (C.c_int, [vp, u8p, C.c_size_t, u8p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AdaptOpt),
+                                            C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, szp,
+                                            C.POINTER(FastqAdapt)]),
         "mk_fq_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_fq_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
     }
@@ -1420,6 +1529,63 @@ class Counter:
         out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqQtrim()
         self._check_select(self._L.mk_fastq_qtrim_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), keep_ptr or None,
                                                          rows_ptr or None, hist_ptr or None, out_ptr or None, int(out_cap),
+                                                         C.byref(out_len), C.byref(nrec), C.byref(st)))
+        return st.as_dict()
+
+    # -- 3' adapter removal from the reads of a FASTQ text (the first job of the fastp run MerCat2 starts); no table is read
+    def fastq_adapt(self, path_or_bytes, adapters, adapters2=None, min_overlap: int = 8, max_err: float = 0.1, min_len: int = 0,
+                    paired: bool = False, which: int = 1, piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_fastq_adapt_text: (out, keep, rows, hits) of the FASTQ text (a path to a plain file, or the text itself as
+        bytes).  Every read is cut at the leftmost position at which one of ``adapters`` (sequences over ACGTN, str or
+        bytes, each of 1..128 bases, at most 1024) matches what is left of the read, or runs off its end, over at least
+        ``min_overlap`` bases with at most ``max_err`` x overlap mismatches (no indels; an adapter N matches anything, a
+        read N nothing but that); of several adapters there, the first listed.  The default overlap of 8 is set for a
+        panel of hundreds of adapters: 3, cutadapt's for one adapter, would cut the end of most adapter-free reads by
+        chance.  A read of which fewer than max(``min_len``, 1) bases remain is dropped.  ``paired``: records 2p and 2p +
+        1 are mates, ``adapters`` are searched in first mates and ``adapters2`` (which needs ``paired``) in second mates;
+        keep is 1 where both pass, 2 for a read whose mate is dropped, else 0; ``which`` = 2 writes those orphans.
+        ``out``: the emitted records as FASTQ bytes; ``keep``: uint8 a record; ``rows``: (records, 5) uint64,
+        ADAPT_COLUMNS, the adapter column indexing info["adapters"] (ADAPT_NO_HIT without a hit); ``hits``: uint64 an
+        adapter, the records it cut.  MercatHipError: MK_ERR_ARG for a refused panel or option, MK_ERR_UNSUPPORTED for a
+        malformed record (the message names it), MK_ERR_RANGE for an odd record count with ``paired``.  ``info``, if
+        given, receives the mk_fastq_adapt_t fields and "adapters", the panel's sequences in index order."""
+        if adapters2 is not None and not paired:
+            raise ValueError("fastq_adapt: adapters2 are searched in second mates: needs paired")
+        opt = adapt_options(min_overlap, max_err, min_len, paired, which)
+        bases, lengths, mates, seqs = adapter_arrays(adapters, adapters2)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        nl = int(np.count_nonzero(held == 10)) if size else 0
+        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        keep, rows, hits = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 5), dtype=np.uint64), np.zeros(len(seqs), dtype=np.uint64)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqAdapt()
+        self._check_select(self._L.mk_fastq_adapt_text(
+            self._h, addr, size, int(piece_bytes), bases.ctypes.data, lengths.ctypes.data, mates.ctypes.data, len(seqs), C.byref(opt), cap,
+            keep.ctypes.data, rows.ctypes.data, hits.ctypes.data, out.ctypes.data, size + 1, C.byref(out_len), C.byref(nrec), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+            info["adapters"] = seqs
+        return out[: out_len.value].tobytes(), keep[: nrec.value], rows[: nrec.value], hits
+
+    def fastq_adapt_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, adapters, adapters2=None, cap: int = 0,
+                           keep_ptr: int = 0, rows_ptr: int = 0, hits_ptr: int = 0, **options) -> dict:
+        """mk_fastq_adapt_device: ``nbytes`` of FASTQ text at device address ``ptr`` -> the emitted records at device
+        address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) and, where given, one keep byte a
+        record at ``keep_ptr``, five uint64 a record at ``rows_ptr`` (room for ``cap`` records each) and one uint64 an
+        adapter at ``hits_ptr`` (both aligned to 8) -- all on this context's GPU.  ``adapters``, ``adapters2`` and
+        ``options``: those of Counter.fastq_adapt.  Returns the mk_fastq_adapt_t fields: "bytes_out" bytes were written,
+        "records" rows."""
+        if adapters2 is not None and not options.get("paired"):
+            raise ValueError("fastq_adapt_device: adapters2 are searched in second mates: needs paired")
+        opt = adapt_options(**options)
+        bases, lengths, mates, seqs = adapter_arrays(adapters, adapters2)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqAdapt()
+        self._check_select(self._L.mk_fastq_adapt_device(self._h, ptr, int(nbytes), bases.ctypes.data, lengths.ctypes.data,
+                                                         mates.ctypes.data, len(seqs), C.byref(opt), int(cap), keep_ptr or None,
+                                                         rows_ptr or None, hits_ptr or None, out_ptr or None, int(out_cap),
                                                          C.byref(out_len), C.byref(nrec), C.byref(st)))
         return st.as_dict()
 

@@ -365,3 +365,45 @@ def write_qtrim_summary(path, figures: Dict[str, int], hist) -> None:
     """``format_qtrim_summary`` written to ``path``."""
     with open(path, "wb") as fh:
         fh.write(format_qtrim_summary(figures, hist))
+
+
+def format_adapt_tsv(names: Sequence[str], rows, keep, adapter_names: Sequence[str]) -> bytes:
+    """``record\tlength\tkept\tadapter\toverlap\tmismatches\tkeep``, then one line per record (kmers.adapt_reads /
+    Counter.fastq_adapt): its name, its row -- the adapter by its name, ``-`` without a hit -- and its keep value."""
+    if len(names) != len(rows) or len(names) != len(keep):
+        raise ValueError("format_adapt_tsv: %d names for %d rows and %d keep values" % (len(names), len(rows), len(keep)))
+    out = [b"record\tlength\tkept\tadapter\toverlap\tmismatches\tkeep\n"]
+    for name, row, k in zip(names, rows, keep):
+        length, kept, adapter, overlap, mism = (int(v) for v in row)
+        which = "-" if adapter == 0xFFFFFFFF else adapter_names[adapter]
+        out.append(name.encode() + b"\t%d\t%d\t" % (length, kept) + which.encode() + b"\t%d\t%d\t%d\n" % (overlap, mism, int(k)))
+    return b"".join(out)
+
+
+def write_adapt_tsv(path, names: Sequence[str], rows, keep, adapter_names: Sequence[str]) -> int:
+    """``format_adapt_tsv`` written to ``path``; returns the number of records."""
+    text = format_adapt_tsv(names, rows, keep, adapter_names)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
+def format_adapt_summary(figures: Dict[str, int], hits, adapter_names: Sequence[str]) -> bytes:
+    """``metric\tbefore\tafter`` over reads and bases, then trimmed (emitted reads that were cut), dropped_short and
+    orphans, which have no "before", then ``adapter:<name>`` with the reads it cut (emitted or not) for every adapter
+    that cut any, in panel order."""
+    out = [b"metric\tbefore\tafter\n",
+           b"reads\t%d\t%d\n" % (int(figures["records"]), int(figures["records_out"])),
+           b"bases\t%d\t%d\n" % (int(figures["bases_in"]), int(figures["bases_out"]))]
+    for name, key in (("trimmed", "records_trimmed"), ("dropped_short", "dropped_short"), ("orphans", "orphans")):
+        out.append(name.encode() + b"\t\t%d\n" % int(figures[key]))
+    for name, h in zip(adapter_names, hits):
+        if int(h):
+            out.append(b"adapter:" + name.encode() + b"\t\t%d\n" % int(h))
+    return b"".join(out)
+
+
+def write_adapt_summary(path, figures: Dict[str, int], hits, adapter_names: Sequence[str]) -> None:
+    """``format_adapt_summary`` written to ``path``."""
+    with open(path, "wb") as fh:
+        fh.write(format_adapt_summary(figures, hits, adapter_names))
