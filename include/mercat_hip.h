@@ -955,6 +955,76 @@ int mk_fastq_adapt_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const u
                           const uint8_t* mates, size_t A, const mk_adapt_opt_t* opt, size_t cap, uint8_t* d_keep, uint64_t* d_rows,
                           uint64_t* d_hits, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec, mk_fastq_adapt_t* st);
 
+/* ---- mate-overlap detection in paired reads: the other half of the fastp run MerCat2 starts -- panel-free adapter removal
+ *      (mode 0) and merging of overlapping mates into one read (mode 1; fastp -m, PEAR, BBMerge) -- here as a stated rule,
+ *      which is not fastp's: read, decided, cut or merged and gathered on the GPU.  Quality bytes are compared as bytes: no
+ *      phred base is involved ----
+ * The text is interleaved FASTQ: records 2p and 2p + 1 are mates, by position; an odd count is MK_ERR_RANGE.  Lines,
+ * records, the tolerated trailing empty lines, the checks and their messages are mk_fastq_select_*'s without kept ('@',
+ * '+', equal lengths, a text that ends inside a record); all MK_ERR_UNSUPPORTED, the lowest record wins.  The tables are
+ * not read; an open chunk is MK_ERR_STATE.
+ * Notation: s1, q1 (L1 bytes) and s2, q2 (L2 bytes) are the contents of the mates' sequence and quality lines (one
+ * trailing '\r' taken off); fold maps a .. z to upper case; comp maps A <-> T and C <-> G on folded bytes and anything else
+ * to N; rc[j] = comp(fold(s2[L2 - 1 - j])), rq[j] = q2[L2 - 1 - j].
+ * Candidates: an offset d puts rc[j] under s1[d + j].  Fragment length F = d + L2; overlap = mate-1 positions [max(d, 0),
+ * min(L1, F)), ov of them; mm = the overlap positions p at which fold(s1[p]) and rc[p - d] are not both of ACGT and equal
+ * (an N in either mate is a mismatch).  d is admissible iff ov >= min_overlap and mm <= max_mismatch and mm * 1000000 <=
+ * max_err_ppm * ov (integers).  Order: d = 0, 1, 2, ... while ov >= min_overlap, then d = -1, -2, ... while ov >=
+ * min_overlap; the first admissible candidate is the hit (the order of fastp's overlap analysis: the longest overlap of
+ * mates that do not read through first, then read-through).  fastp's defaults are min_overlap 30, max_mismatch 5,
+ * max_err_ppm 200000.  A pair with L1 or L2 above MK_OVERLAP_MAX_BASES is not tested: it has no hit and counts in
+ * skipped_long.
+ * rows[r] (every record, five uint64, the same in both modes): length, kept, fragment, overlap, mismatches.  With a hit
+ * kept = min(length, F) and the last three are equal for both mates; without one kept = length, fragment = 0xFFFFFFFF,
+ * overlap = mismatches = 0.
+ * mode 0 (trim): with a hit each mate is cut to its first kept bases (mate 2's adapter is at its 3' end too).  A pair
+ * with a hit and F < max(min_len, 1) is dropped: keep = 0 for both mates (dropped_short); every other pair has keep = 1.
+ * which must be 1.  Output: both mates of every kept pair, in text order: an uncut record whole, byte for byte (a forced
+ * '\n' where the text ends without one), a cut record as mk_fastq_adapt_* emits one (the header line as it stands,
+ * s[:kept] and '\n', the '+' line as it stands, qual[:kept] and '\n').
+ * mode 1 (merge): a pair with a hit and F >= max(min_len, 1) is merged: keep = 1 for both mates; with a hit and a shorter
+ * F it is dropped: keep = 0 (dropped_short); without a hit keep = 2.  which = 1 writes one record a merged pair: mate 1's
+ * header line as it stands, the merged sequence and '\n', mate 1's '+' line as it stands, the merged quality and '\n'.
+ * which = 2 writes both mates of every keep == 2 pair, byte for byte (the forced '\n' as above).  The merged read covers
+ * positions p in [0, F):
+ *   p < d: s1[p], q1[p];   p >= L1: rc[p - d], rq[p - d];
+ *   in the overlap, the folded bytes equal and of ACGT: s1[p] as it stands with the larger of the two quality bytes;
+ *   in the overlap otherwise: a byte of ACGT (after folding) wins over one that is not, then the higher quality byte
+ *   wins, then mate 1; the winner's base (s1[p] as it stands, or rc[p - d]) goes out with its own quality.
+ * Figures: pairs = records / 2; pairs_hit; pairs_merged (mode 1: keep 1), pairs_trimmed (mode 0: kept pairs with a hit
+ * of which a mate was cut); dropped_short, skipped_long (pairs); records_out, records_trimmed (emitted; emitted and not
+ * byte for byte: cut, or merged), bases_in (all records), bases_out (emitted).
+ * cap, the sizing call (out = NULL, out_cap = 0), out_cap too small (MK_ERR_RANGE with the needed size in *out_len, keep
+ * and rows complete), *nrec, the order of the errors (options first) and NULL keep / rows are mk_fastq_adapt_*'s.
+ * *out_len <= n + 1 in both modes.  mk_fastq_overlap_text: host memory, piece by piece; pieces end behind a line 8j
+ * (mk_fastq_pair_cuts), nothing depends on piece_bytes.  mk_fastq_overlap_device: everything in DEVICE memory, one piece
+ * of at most 2^32 - 1 bytes (more: MK_ERR_RANGE before anything is read), text and out at any address, d_rows aligned to
+ * 8 (MK_ERR_ARG otherwise).  d_fastq is never modified: a merging call (mode 1, which 1) works on a copy of its own, whose
+ * time is in s_copy.
+ * MK_ERR_ARG: mode not 0 / 1; min_overlap outside 1 .. MK_OVERLAP_MAX_BASES; max_err_ppm above 1000000; which not 1,
+ * except 2 with mode 1. */
+#define MK_OVERLAP_MAX_BASES 512
+typedef struct mk_overlap_opt_t {
+  uint32_t mode;         /* 0 trim, 1 merge                                                                            */
+  uint32_t min_overlap;  /* 1 .. MK_OVERLAP_MAX_BASES                                                                  */
+  uint32_t max_mismatch; /* mismatches an overlap may hold                                                             */
+  uint32_t max_err_ppm;  /* 0 .. 1000000: and per million overlap bases                                                */
+  uint32_t min_len, which;
+} mk_overlap_opt_t;
+typedef struct mk_fastq_overlap_t {
+  uint64_t records, pairs, pairs_hit, pairs_merged, pairs_trimmed, dropped_short, skipped_long;
+  uint64_t records_out, records_trimmed, bases_in, bases_out, bytes_out, lines;
+  /* seconds: host time in the copies to the device (and the device call's own copy of a text it merges in); HIP-event
+   * time of the line index; of the pair scan; of the decision, the merge writer and the prefix sum; of the gather; host
+   * time in the copies back */
+  double s_copy, s_index, s_scan, s_place, s_gather, s_write;
+} mk_fastq_overlap_t;
+int mk_fastq_overlap_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes, const mk_overlap_opt_t* opt, size_t cap,
+                          uint8_t* keep, uint64_t* rows, uint8_t* out, size_t out_cap, size_t* out_len, size_t* nrec,
+                          mk_fastq_overlap_t* st);
+int mk_fastq_overlap_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const mk_overlap_opt_t* opt, size_t cap, uint8_t* d_keep,
+                            uint64_t* d_rows, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec, mk_fastq_overlap_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

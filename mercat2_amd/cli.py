@@ -55,7 +55,15 @@ that, before -qtrim where both are given, again by a stated rule (mk_fastq_adapt
 shorter than -adapt_len dropped) against the adapters of the FASTA FILE or, without one, Illumina's TruSeq, Nextera and
 small-RNA adapters: adapt/<sample>_adapt.fastq holds the reads that -qtrim and the count then see, adapt/<sample>_adapt.tsv
 every read's length, cut, adapter, overlap and mismatches, adapt/<sample>_summary.tsv reads and bases before and after and
-the hits of each adapter.  Indels, 5' and anchored adapters, mate-overlap detection and poly-G trimming stay out.  Per-position QC plots, ORF calling (-prod / -fgs), the HTML report and plots belong
+the hits of each adapter.  -overlap trim|merge does the paired-end half of that fastp run, before -adapt and -qtrim: every
+FASTQ input is interleaved pairs (or, with -overlap_mate FILE2, the first of two files), mate 1 is laid against the reverse
+complement of mate 2 (mk_fastq_overlap_text: the first offset, longest overlap first and read-through last, with -overlap_min
+bases within -overlap_diff mismatches and -overlap_err mismatches a base), and a pair that overlaps is cut to its fragment
+-- adapters gone without a panel -- or merged into one read with a consensus over the overlap; overlap/<sample>_overlap.fastq,
+or _merged.fastq and _unmerged.fastq, hold what -adapt, -qtrim and the count then see, overlap/<sample>_overlap.tsv every
+read's length, cut, fragment, overlap and mismatches, overlap/<sample>_summary.tsv the pair counts and the fragment lengths.
+Indels (in adapters and in the overlap), 5' and anchored adapters, quality-aware correction of unmerged mates (fastp -c) and
+poly-G trimming stay out.  Per-position QC plots, ORF calling (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -247,14 +255,29 @@ def parseargs(argv=None):
     p.add_argument("-adapt", type=str, nargs="?", const="", default=None, metavar="FILE",
                    help="FASTQ input, with or without -skipclean: remove 3' adapters from the reads on the GPU before -qtrim and the "
                         "count see them. The first job of the fastp run MerCat2 starts, as a stated rule that is not fastp's: a read "
-                        "is cut at the leftmost position where an adapter matches the rest of it, or runs off its end (no indels, no "
-                        "mate-overlap detection). FILE: a FASTA file of up to 1024 adapters of up to 128 bases [the Illumina TruSeq, "
+                        "is cut at the leftmost position where an adapter matches the rest of it, or runs off its end (no indels; "
+                        "-overlap finds adapters by the mates' overlap). FILE: a FASTA file of up to 1024 adapters of up to 128 bases [the Illumina TruSeq, "
                         "Nextera and small-RNA adapters]; writes adapt/<sample>_adapt.fastq, _adapt.tsv and _summary.tsv")
     p.add_argument("-adapt_overlap", type=int, default=None, metavar="N",
                    help="-adapt: the fewest bases an adapter must cover [8: set for a panel of hundreds of adapters, which at "
                         "cutadapt's 3 for one adapter would cut the end of most adapter-free reads by chance]")
     p.add_argument("-adapt_err", type=float, default=None, metavar="F", help="-adapt: mismatches allowed, as a fraction (0..1) of the overlap [0.1]")
     p.add_argument("-adapt_len", type=int, default=None, metavar="N", help="-adapt: drop a read of which fewer than N bases remain [1]")
+    p.add_argument("-overlap", type=str, default=None, choices=("trim", "merge"),
+                   help="FASTQ input, with or without -skipclean: every FASTQ input is taken as interleaved pairs, whose mates are "
+                        "laid over each other on the GPU before -adapt, -qtrim and the count see them. The paired-end half of the "
+                        "fastp run MerCat2 starts, as a stated rule that is not fastp's (indels in the overlap, quality-aware correction "
+                        "of unmerged mates -- fastp -c -- and poly-G trimming stay out). trim: a pair that overlaps is cut to its fragment (adapter removal without a panel); "
+                        "writes overlap/<sample>_overlap.fastq. merge: it becomes one read with a consensus over the overlap; "
+                        "writes overlap/<sample>_merged.fastq and _unmerged.fastq, and the count sees both. Either way "
+                        "overlap/<sample>_overlap.tsv and _summary.tsv")
+    p.add_argument("-overlap_min", type=int, default=None, metavar="N", help="-overlap: the fewest bases the mates must share [30]")
+    p.add_argument("-overlap_diff", type=int, default=None, metavar="N", help="-overlap: mismatches an overlap may hold [5]")
+    p.add_argument("-overlap_err", type=float, default=None, metavar="F",
+                   help="-overlap: and mismatches allowed as a fraction (0..1) of the overlap [0.2]")
+    p.add_argument("-overlap_len", type=int, default=None, metavar="N", help="-overlap: drop a pair whose fragment has fewer than N bases [1]")
+    p.add_argument("-overlap_mate", type=str, default=None, metavar="FILE2",
+                   help="-overlap with exactly one FASTQ input: that file holds the first mates and FILE2 the second")
     p.add_argument("-toupper", action="store_true", help="convert all input sequences to uppercase [False]")
     # flags of the reference's other layers (bin/mercat2.py:45-58)
     p.add_argument("-prod", action="store_true", help="(MerCat2: ORF calling with prodigal) not part of this engine")
@@ -340,6 +363,31 @@ def parseargs(argv=None):
             if len(set(seqs)) > 1024 or max(len(s) for s in seqs) > 128:
                 p.error(f"-adapt {args.adapt}: at most 1024 distinct adapters of at most 128 bases each")
             args.adapters = list(zip(names, seqs))
+    if args.overlap is None:
+        for flag in ("overlap_min", "overlap_diff", "overlap_err", "overlap_len", "overlap_mate"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -overlap")
+    else:
+        given = list(args.i)
+        if args.f and os.path.isdir(args.f):
+            given += sorted(os.listdir(args.f))
+        reads = [name for name in given if fastq_ext(Path(name))]
+        if not reads:
+            p.error(f"-overlap lays the mates of FASTQ pairs over each other ({' / '.join(FILE_EXT_FASTQ)}); no input is a FASTQ file")
+        if args.overlap_min is not None and not 1 <= args.overlap_min <= 512:
+            p.error(f"-overlap_min {args.overlap_min}: must lie in 1..512")
+        if args.overlap_err is not None and not 0.0 <= args.overlap_err <= 1.0:
+            p.error(f"-overlap_err {args.overlap_err}: must lie in 0..1")
+        for flag in ("overlap_diff", "overlap_len"):
+            if getattr(args, flag) is not None and not 0 <= getattr(args, flag) < 1 << 32:
+                p.error(f"-{flag} {getattr(args, flag)}: must lie in 0..2^32 - 1")
+        if args.overlap_mate is not None:
+            if len(reads) != 1:
+                p.error(f"-overlap_mate names the second file of exactly one FASTQ input; {len(reads)} are given (interleave them)")
+            if not os.path.isfile(args.overlap_mate):
+                p.error(f"file '{args.overlap_mate}' is not valid.\n")
+            if not fastq_ext(Path(args.overlap_mate)):
+                p.error(f"-overlap_mate {args.overlap_mate}: needs a FASTQ file ({' / '.join(FILE_EXT_FASTQ)})")
     if args.histo is not None and not 1 <= args.histo <= 1 << 20:
         p.error(f"-histo {args.histo}: HIGH must lie in 1..{1 << 20}")
     args.screen_kind = None
@@ -640,8 +688,33 @@ def adapt_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes
     return done["text"]
 
 
+def overlap_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
+    """-overlap: the pairs of FASTQ sample ``base`` (``raw``: its bytes if they are in memory already, else None and ``f``
+    is read; interleaved, or the first mates with -overlap_mate) trimmed or merged by the overlap of their mates on GPU
+    ``device`` by kmers.overlap_reads, which writes overlap/<base>_overlap.fastq (trim) or _merged.fastq and
+    _unmerged.fastq (merge), _overlap.tsv and _summary.tsv; returns the text that -adapt, -qtrim and the count see in the
+    raw reads' place: the trimmed pairs, or the merged reads followed by the unmerged pairs."""
+    from . import kmers, native
+    folder = out / "overlap"
+    folder.mkdir(parents=True, exist_ok=True)
+    merging = args.overlap == "merge"
+    try:
+        done = kmers.overlap_reads(
+            f if raw is None else raw, folder / (f"{base}_merged.fastq" if merging else f"{base}_overlap.fastq"), mode=args.overlap,
+            min_overlap=30 if args.overlap_min is None else args.overlap_min, max_mismatch=5 if args.overlap_diff is None else args.overlap_diff,
+            max_err=0.2 if args.overlap_err is None else args.overlap_err, min_len=args.overlap_len or 0, mate_file=args.overlap_mate,
+            unmerged_path=folder / f"{base}_unmerged.fastq" if merging else None, tsv_path=folder / f"{base}_overlap.tsv",
+            summary_path=folder / f"{base}_summary.tsv", device=device, keep_text=True)
+    except (native.MercatHipError, ValueError) as e:
+        raise SystemExit(f"-overlap '{f.name}': {e}")
+    return done["text"] + done["unmerged"] if merging else done["text"]
+
+
 def prepared_reads(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
-    """The reads of FASTQ sample ``base`` as the count sees them: through -adapt, then through -qtrim, where given."""
+    """The reads of FASTQ sample ``base`` as the count sees them: through -overlap, then -adapt, then -qtrim, where
+    given."""
+    if args.overlap is not None:
+        raw = overlap_sample(args, f, raw, out, base, device)
     if args.adapt is not None:
         raw = adapt_sample(args, f, raw, out, base, device)
     if args.qtrim is not None:
@@ -730,7 +803,8 @@ def main(argv=None) -> int:
     samples = {"nucleotide": {}, "protein": {}}
     fastq = set()  # nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)
     for f in files:
-        kind, base = classify(f.expanduser().absolute(), args.skipclean or args.qtrim is not None or args.adapt is not None)
+        kind, base = classify(f.expanduser().absolute(),
+                              args.skipclean or args.qtrim is not None or args.adapt is not None or args.overlap is not None)
         if kind:
             samples[kind][base] = f
             if fastq_ext(f):
@@ -771,7 +845,7 @@ def main(argv=None) -> int:
             t0 = timeit.default_timer()
             raw = read_fasta_bytes(f)
             t["read_s"] = timeit.default_timer() - t0
-            if base in fastq and (args.qtrim is not None or args.adapt is not None):
+            if base in fastq and (args.qtrim is not None or args.adapt is not None or args.overlap is not None):
                 t0 = timeit.default_timer()
                 raw = prepared_reads(args, f, raw, out, base, home_of[base])
                 t["qtrim_s"] = timeit.default_timer() - t0

@@ -1,5 +1,5 @@
 // mk_fqpiece.h -- what the calls that read a FASTQ text, judge every record by a scan kernel of their own and write the
-// survivors cut share: mk_fastq_qtrim_* (mk_qtrim.hip) and mk_fastq_adapt_* (mk_adapt.hip).
+// survivors cut share: mk_fastq_qtrim_* (mk_qtrim.hip), mk_fastq_adapt_* (mk_adapt.hip) and mk_fastq_overlap_* (mk_overlap.hip).
 //   device side   QtLine (a line's content seen through aligned 16-byte granules), qt_record (the lines of a record and
 //                 its checks), fq_segments (the four segments of an emitted record from its span).
 //   host side     FqCall<P> (the state of a call), fq_piece<P> (one piece: line index, P::scan, P::decide, the prefix
@@ -88,6 +88,7 @@ struct FqCall {
   size_t out_cap;
   bool device;
   typename P::Side side;
+  uint8_t* own = nullptr;  // the piece's text where it is the call's own copy (c->raw), which a policy may patch; else nullptr
   MkDevBuf tiles, meta, scan_tmp, stage, side_buf;
   MkTimed index, scan, place, gather;
   typename P::Stats st{};
@@ -289,13 +290,13 @@ static int fq_run(FqCall<P>& f, size_t* out_len, size_t* nrec, typename P::Stats
 }
 
 // The one piece of a device call: the text where it stands, or copied to c->raw where it is not aligned to 16 (the line
-// passes, the scans and fl_load16 load 16 aligned bytes at a time).
+// passes, the scans and fl_load16 load 16 aligned bytes at a time) or where the call patches its text (own_copy).
 template <class P>
-static int fq_device_body(FqCall<P>& f, const uint8_t* d_fastq, size_t n) {
+static int fq_device_body(FqCall<P>& f, const uint8_t* d_fastq, size_t n, bool own_copy = false) {
   mk_ctx* c = f.c;
   if (!n) return MK_OK;
   const uint8_t* d_text = d_fastq;
-  if ((uintptr_t)d_text & 15) {
+  if (((uintptr_t)d_text & 15) || own_copy) {
     int rc = mk_buf_reserve(c, c->raw, n + 64);
     if (rc != MK_OK) return rc;
     const auto t1 = MkClock::now();
@@ -303,6 +304,7 @@ static int fq_device_body(FqCall<P>& f, const uint8_t* d_fastq, size_t n) {
     MK_HIP(hipStreamSynchronize(c->stream));
     f.st.s_copy += mk_since(t1);
     d_text = (const uint8_t*)c->raw.p;
+    f.own = (uint8_t*)c->raw.p;
   }
   return fq_piece(f, d_text, n);
 }
@@ -333,6 +335,7 @@ static int fq_text_body(FqCall<P>& f, const uint8_t* fastq, size_t n, size_t pie
     MK_HIP(hipMemcpyAsync(c->raw.p, fastq + at, len, hipMemcpyHostToDevice, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));
     f.st.s_copy += mk_since(t1);
+    f.own = (uint8_t*)c->raw.p;
     if ((rc = fq_piece(f, (const uint8_t*)c->raw.p, len)) != MK_OK) return rc;
     at = (size_t)end;
   }

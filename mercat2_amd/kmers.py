@@ -692,3 +692,75 @@ def adapt_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None],
     if keep_text:
         done["text"] = out
     return done
+
+
+def overlap_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None], mode: str = "merge", min_overlap: int = 30,
+                  max_mismatch: int = 5, max_err: float = 0.2, min_len: int = 0, mate_file: Union[str, Path, None] = None,
+                  out_path2: Union[str, Path, None] = None, unmerged_path: Union[str, Path, None] = None,
+                  unmerged_path2: Union[str, Path, None] = None, tsv_path: Union[str, Path, None] = None,
+                  summary_path: Union[str, Path, None] = None, device: int = 0, keep_text: bool = False) -> Dict[str, object]:
+    """The paired reads of a FASTQ file ('.fq' / '.fastq', plain or '.gz'; or the FASTQ text itself as bytes) trimmed or
+    merged by the overlap of their mates on the GPU (Counter.fastq_overlap has the rule: mate 1 against the reverse
+    complement of mate 2, the first offset whose overlap has ``min_overlap`` bases within ``max_mismatch`` mismatches and
+    ``max_err`` mismatches a base; no indels).  ``file`` is interleaved, or -- with ``mate_file`` -- the first of two
+    files, interleaved on the host (native.interleave_fastq).  This is the paired-end half of the fastp run MerCat2
+    starts; its result is this stated rule's, not fastp's.  No table is read: the call opens a small context of its own
+    on ``device``.
+    ``mode`` "trim": every pair with an overlap is cut to its fragment -- adapter removal without a panel -- and written
+    with the others, interleaved to ``out_path`` or split into ``out_path`` and ``out_path2``; a pair whose fragment is
+    shorter than max(``min_len``, 1) is dropped.  ``mode`` "merge": every pair with an overlap becomes one read in
+    ``out_path``; the pairs without one are written as they stand (a second call with which = 2) to ``unmerged_path``,
+    interleaved, or split into ``unmerged_path`` and ``unmerged_path2``.  Outputs are gzip (level 1) where the name ends
+    in '.gz'.  ``tsv_path``: every record's name, row and keep value (report.write_overlap_tsv); ``summary_path``: pairs,
+    hits, merged / trimmed / dropped / skipped pairs, bases before and after and the pairs of every fragment length
+    (report.write_overlap_summary), counted on the host from the rows.  Returns the mk_fastq_overlap_t figures,
+    "fragments" ({fragment length: pairs}) and, with ``keep_text``, the main output under "text" and, in merge mode, the
+    unmerged pairs under "unmerged"."""
+    if mode not in native.OVERLAP_MODES:
+        raise ValueError("overlap_reads: mode %r: must be 'trim' or 'merge'" % (mode,))
+    merging = mode == "merge"
+    if merging and out_path2 is not None:
+        raise ValueError("overlap_reads: merged reads are one file: out_path2 goes with mode 'trim'")
+    if not merging and (unmerged_path is not None or unmerged_path2 is not None):
+        raise ValueError("overlap_reads: unmerged_path goes with mode 'merge': mode 'trim' writes every pair it keeps to out_path")
+    if unmerged_path2 is not None and unmerged_path is None:
+        raise ValueError("overlap_reads: unmerged_path2 needs unmerged_path")
+    is_text = isinstance(file, (bytes, bytearray, memoryview))
+    for f in (None if is_text else file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("overlap_reads: needs FASTQ input (%s), not %s" % (" / ".join(FASTQ_SUFFIXES), f))
+    opts = dict(mode=mode, min_overlap=min_overlap, max_mismatch=max_mismatch, max_err=max_err, min_len=min_len)
+    native.overlap_options(**opts)  # (a refused value is refused before a file is read)
+    raw = bytes(file) if is_text else read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    info: Dict[str, object] = {}
+    with native.Counter(5, native.ALPHABET_NT2, device=device) as ctx:
+        out, keep, rows = ctx.fastq_overlap(raw, which=1, info=info, **opts)
+        unmerged = ctx.fastq_overlap(raw, which=2, **opts)[0] if merging and (unmerged_path is not None or keep_text) else None
+
+    def write(text, path, path2):
+        if path is None:
+            return
+        if path2 is None:
+            _write_reads(path, text)
+        else:
+            first, second = native.split_pairs_fastq(text)
+            _write_reads(path, first)
+            _write_reads(path2, second)
+    write(out, out_path, out_path2)
+    if merging:
+        write(unmerged or b"", unmerged_path, unmerged_path2)
+    from .report import overlap_fragments, write_overlap_summary, write_overlap_tsv
+    fragments = overlap_fragments(rows)
+    if tsv_path is not None:
+        write_overlap_tsv(tsv_path, fastq_names(raw), rows, keep)
+    if summary_path is not None:
+        write_overlap_summary(summary_path, info, fragments)
+    done: Dict[str, object] = {name: value for name, value in info.items() if not name.startswith("s_")}
+    done["fragments"] = fragments
+    if keep_text:
+        done["text"] = out
+        if merging:
+            done["unmerged"] = unmerged or b""
+    return done

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "mk_fastq_select_text", "mk_fastq_select_device", "mk_fastq_cuts", "mk_fq_interleave", "mk_fq_split_pairs",
     "mk_fastq_qtrim_text", "mk_fastq_qtrim_device", "mk_fastq_pair_cuts",
     "mk_adapters_pack", "mk_fastq_adapt_text", "mk_fastq_adapt_device",
+    "mk_fastq_overlap_text", "mk_fastq_overlap_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -352,6 +353,44 @@ def adapt_options(min_overlap: int = 8, max_err: float = 0.1, min_len: int = 0, 
     return AdaptOpt(**{name: int(v) for name, v in vals.items()})
 
 
+class OverlapOpt(C.Structure):
+    """mk_overlap_opt_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "min_overlap", "max_mismatch", "max_err_ppm", "min_len", "which")]
+
+
+class FastqOverlap(C.Structure):
+    """mk_fastq_overlap_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("records", "pairs", "pairs_hit", "pairs_merged", "pairs_trimmed", "dropped_short", "skipped_long",
+                                           "records_out", "records_trimmed", "bases_in", "bases_out", "bytes_out", "lines")] +
+                [(n, C.c_double) for n in ("s_copy", "s_index", "s_scan", "s_place", "s_gather", "s_write")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+OVERLAP_COLUMNS = ("length", "kept", "fragment", "overlap", "mismatches")  # the columns of Counter.fastq_overlap's rows
+OVERLAP_NO_HIT = 0xFFFFFFFF  # the fragment column of a pair without a hit
+OVERLAP_MAX_BASES = 512  # MK_OVERLAP_MAX_BASES: a pair with a longer mate is not tested
+OVERLAP_MODES = {"trim": 0, "merge": 1}
+
+
+def overlap_options(mode="merge", min_overlap: int = 30, max_mismatch: int = 5, max_err: float = 0.2, min_len: int = 0,
+                    which: int = 1) -> "OverlapOpt":
+    """mk_overlap_opt_t of Counter.fastq_overlap's arguments; ValueError for a mode that is neither "trim" nor "merge" (0
+    and 1 are taken too), a value that no uint32 holds or an error rate outside 0..1 (the library checks the ranges the
+    rule sets)."""
+    if mode in OVERLAP_MODES:
+        mode = OVERLAP_MODES[mode]
+    elif isinstance(mode, str) or isinstance(mode, bool):
+        raise ValueError("mode %r: must be 'trim' or 'merge'" % (mode,))
+    vals = dict(mode=mode, min_overlap=min_overlap, max_mismatch=max_mismatch, max_err_ppm=ppm_of_fraction(max_err), min_len=min_len,
+                which=which)
+    for name, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s %r: must lie in 0..2^32-1" % (name, v))
+    return OverlapOpt(**{name: int(v) for name, v in vals.items()})
+
+
 def read_adapters(path, check: bool = True) -> Tuple[list, list]:
     """(names, seqs) of the FASTA file ``path`` (plain or '.gz', records of any number of lines): the first word behind
     every '>' and the record's bases as str, blanks and tabs at line ends stripped.  A '>' line with no bases behind it
@@ -630,6 +669,10 @@ def lib() -> C.CDLL:
         "mk_fastq_adapt_device": (C.c_int, [vp, u8p, C.c_size_t, u8p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AdaptOpt),
                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp, szp,
                                             C.POINTER(FastqAdapt)]),
+        "mk_fastq_overlap_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.POINTER(OverlapOpt), C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqOverlap)]),
+        "mk_fastq_overlap_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(OverlapOpt), C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqOverlap)]),
         "mk_fq_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_fq_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
     }
@@ -1587,6 +1630,56 @@ class Counter:
                                                          mates.ctypes.data, len(seqs), C.byref(opt), int(cap), keep_ptr or None,
                                                          rows_ptr or None, hits_ptr or None, out_ptr or None, int(out_cap),
                                                          C.byref(out_len), C.byref(nrec), C.byref(st)))
+        return st.as_dict()
+
+    # -- mate-overlap detection in interleaved pairs: panel-free adapter removal, or merging; no table is read
+    def fastq_overlap(self, path_or_bytes, mode="merge", min_overlap: int = 30, max_mismatch: int = 5, max_err: float = 0.2,
+                      min_len: int = 0, which: int = 1, piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_fastq_overlap_text: (out, keep, rows) of the interleaved FASTQ text (a path to a plain file, or the text
+        itself as bytes): records 2p and 2p + 1 are mates.  Mate 1 is laid against the reverse complement of mate 2 at
+        every offset -- mates that do not read through first, the longest overlap first, then read-through -- and the
+        first offset whose overlap has at least ``min_overlap`` bases, at most ``max_mismatch`` mismatches and at most
+        ``max_err`` x overlap of them is the hit; it gives the fragment length (include/mercat_hip.h has the rule in
+        full; the defaults are fastp's 30 / 5 / 20 %; a pair with a mate above OVERLAP_MAX_BASES is not tested).
+        ``mode`` "trim": both mates of a pair with a hit are cut to the fragment (adapter removal without a panel), a
+        pair whose fragment is shorter than max(``min_len``, 1) is dropped; keep is 1 or 0.  ``mode`` "merge": a pair
+        with a hit becomes one read, mate 1 then what mate 2 adds, with a consensus over the overlap (the base of the
+        higher quality byte, a base of ACGT before any other); keep is 1 for a merged pair, 0 for one dropped as short,
+        2 without a hit, and ``which`` = 2 writes those unmerged pairs as they stand.  ``out``: the emitted records as
+        FASTQ bytes; ``keep``: uint8 a record; ``rows``: (records, 5) uint64, OVERLAP_COLUMNS (fragment OVERLAP_NO_HIT
+        without a hit).  MercatHipError: MK_ERR_ARG for a refused option, MK_ERR_UNSUPPORTED for a malformed record (the
+        message names it), MK_ERR_RANGE for an odd record count.  ``info``, if given, receives the mk_fastq_overlap_t
+        fields."""
+        opt = overlap_options(mode, min_overlap, max_mismatch, max_err, min_len, which)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        nl = int(np.count_nonzero(held == 10)) if size else 0
+        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        keep, rows = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 5), dtype=np.uint64)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqOverlap()
+        self._check_select(self._L.mk_fastq_overlap_text(
+            self._h, addr, size, int(piece_bytes), C.byref(opt), cap, keep.ctypes.data, rows.ctypes.data, out.ctypes.data, size + 1,
+            C.byref(out_len), C.byref(nrec), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), keep[: nrec.value], rows[: nrec.value]
+
+    def fastq_overlap_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, cap: int = 0, keep_ptr: int = 0, rows_ptr: int = 0,
+                             **options) -> dict:
+        """mk_fastq_overlap_device: ``nbytes`` of interleaved FASTQ text at device address ``ptr`` -> the emitted records
+        at device address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) and, where given, one keep
+        byte a record at ``keep_ptr`` and five uint64 a record at ``rows_ptr`` (aligned to 8; room for ``cap`` records
+        each) -- all on this context's GPU.  The text is not modified: a merging call works on a copy.  ``options``:
+        those of Counter.fastq_overlap.  Returns the mk_fastq_overlap_t fields: "bytes_out" bytes were written,
+        "records" rows."""
+        opt = overlap_options(**options)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqOverlap()
+        self._check_select(self._L.mk_fastq_overlap_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), keep_ptr or None,
+                                                           rows_ptr or None, out_ptr or None, int(out_cap), C.byref(out_len),
+                                                           C.byref(nrec), C.byref(st)))
         return st.as_dict()
 
     # -- tracking: FASTA text in, the count under every window out (and the median a record); the table is only read

@@ -407,3 +407,56 @@ def write_adapt_summary(path, figures: Dict[str, int], hits, adapter_names: Sequ
     """``format_adapt_summary`` written to ``path``."""
     with open(path, "wb") as fh:
         fh.write(format_adapt_summary(figures, hits, adapter_names))
+
+
+def format_overlap_tsv(names: Sequence[str], rows, keep) -> bytes:
+    """``record\tlength\tkept\tfragment\toverlap\tmismatches\tkeep``, then one line per record (kmers.overlap_reads /
+    Counter.fastq_overlap): its name, its row -- the fragment ``-`` without a hit -- and its keep value."""
+    if len(names) != len(rows) or len(names) != len(keep):
+        raise ValueError("format_overlap_tsv: %d names for %d rows and %d keep values" % (len(names), len(rows), len(keep)))
+    out = [b"record\tlength\tkept\tfragment\toverlap\tmismatches\tkeep\n"]
+    for name, row, k in zip(names, rows, keep):
+        length, kept, fragment, overlap, mism = (int(v) for v in row)
+        frag = b"-" if fragment == 0xFFFFFFFF else b"%d" % fragment
+        out.append(name.encode() + b"\t%d\t%d\t" % (length, kept) + frag + b"\t%d\t%d\t%d\n" % (overlap, mism, int(k)))
+    return b"".join(out)
+
+
+def write_overlap_tsv(path, names: Sequence[str], rows, keep) -> int:
+    """``format_overlap_tsv`` written to ``path``; returns the number of records."""
+    text = format_overlap_tsv(names, rows, keep)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
+def overlap_fragments(rows) -> Dict[int, int]:
+    """{fragment length: pairs} over the pairs with a hit, in ascending order, from Counter.fastq_overlap's rows (the
+    row of every first mate)."""
+    counts: Dict[int, int] = {}
+    for row in rows[0::2]:
+        fragment = int(row[2])
+        if fragment != 0xFFFFFFFF:
+            counts[fragment] = counts.get(fragment, 0) + 1
+    return dict(sorted(counts.items()))
+
+
+def format_overlap_summary(figures: Dict[str, int], fragments: Dict[int, int]) -> bytes:
+    """``metric\tbefore\tafter`` over reads and bases, then the pair counts, which have no "before" -- pairs, hits, merged,
+    trimmed, dropped_short, skipped_long -- then ``fragment\tpairs`` and one line per fragment length that occurs."""
+    out = [b"metric\tbefore\tafter\n",
+           b"reads\t%d\t%d\n" % (int(figures["records"]), int(figures["records_out"])),
+           b"bases\t%d\t%d\n" % (int(figures["bases_in"]), int(figures["bases_out"]))]
+    for name, key in (("pairs", "pairs"), ("hits", "pairs_hit"), ("merged", "pairs_merged"), ("trimmed", "pairs_trimmed"),
+                      ("dropped_short", "dropped_short"), ("skipped_long", "skipped_long")):
+        out.append(name.encode() + b"\t\t%d\n" % int(figures[key]))
+    out.append(b"fragment\tpairs\n")
+    for fragment, pairs in fragments.items():
+        out.append(b"%d\t%d\n" % (int(fragment), int(pairs)))
+    return b"".join(out)
+
+
+def write_overlap_summary(path, figures: Dict[str, int], fragments: Dict[int, int]) -> None:
+    """``format_overlap_summary`` written to ``path``."""
+    with open(path, "wb") as fh:
+        fh.write(format_overlap_summary(figures, fragments))
