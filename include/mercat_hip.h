@@ -81,6 +81,8 @@ typedef struct mk_stats_t {
   uint64_t parse_retries; /* chunks parsed a second time by the general parser (a blank inside a sequence line)           */
   uint64_t split_exhausted; /* sub-ranges of the LDS count kernels that reached the last split level (every hash bit used):
                                counted by probing the whole table (ABI 5)                                                     */
+  uint64_t flat_chunks;  /* chunks counted through the flat parse lane (read files: packed in place, one kernel)              */
+  uint64_t flat_refused; /* flat launches refused (the text is not one line per record): parsed again by the fast parser     */
 } mk_stats_t;
 
 /* ---- lifetime ------------------------------------------------------------------------- */

@@ -273,6 +273,7 @@ static int reset_impl(mk_ctx* c, size_t expect_rows) {
   c->raw_len = 0;
   c->part_reuse_ok = false;  // (a new sample sizes its own bucket regions: nothing is inherited across samples)
   c->dup_known = false;
+  c->flat_lane = 0;  // (the next sample decides for itself, from the share of symbols this one's text had: flat_share stays)
   // (surv_hint stays, like dup_hint and nk_hint: a context that is reset counts the next sample, and the survivors of the
   // last sample's last full chunk are the best guess there is for its first chunk -- the fused launch spills what a wrong
   // guess leaves no room for.  Only a new context has no guess and hands its first chunk's survivors over through regions.)

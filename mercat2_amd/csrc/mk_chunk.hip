@@ -7,11 +7,20 @@
 // fallback of the first).  What both do alike is the steps below, each called by both.
 #include "mk_common.h"
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 
 typedef unsigned long long u64;
 
 #define MK_RETRY_GENERAL 1  // (internal) the speculative lane met input it does not handle: take the general path
+#define MK_RETRY_DENSE 2    // (internal) the flat parse was refused: the speculative lane again, with the three-kernel parser
+
+// The flat lane (mk_fparse.hip) is worth taking on read files: the scatter walks every raw position, header bytes
+// included, so long header lines cost it more than the parser saves.  symbols / raw bytes of the last full chunk below
+// this share: the lane is not taken (measured: profiles/fparse_flat.md; MK_FP_FLAT_SHARE overrides it).
+#define MK_FLAT_MIN_SHARE 0.70
+// share < 0: nothing is known about the input yet -- try the lane.
+static bool flat_lane_wanted(bool enabled, double share, double min_share) { return enabled && (share < 0.0 || share >= min_share); }
 
 // ------------------------------------------------------------------- steps of both lanes
 // seq / bad / codes for a chunk of n raw bytes (the kernels read the true seq_len on the device)
@@ -155,9 +164,16 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   MK_HIP(hipSetDevice(c->device));
   MK_HIP(hipMemsetAsync(c->info.p, 0, sizeof(MkChunkInfo), c->stream));
   if ((rc = reserve_chunk_buffers(c, n)) != MK_OK) return rc;
+  // The flat lane: decided at a sample's first chunk (the hints downstream then see one kind of length throughout) and
+  // given up until mk_reset by a refused launch.  MK_FP_FLAT=0 is the A/B switch.
+  const bool flat_on = mk_env_int("MK_FP_FLAT", 1) != 0;
+  if (c->flat_lane == 0) c->flat_lane = flat_lane_wanted(flat_on, c->flat_share, mk_env_double("MK_FP_FLAT_SHARE", MK_FLAT_MIN_SHARE)) ? 1 : -1;
+  const bool flat = flat_on && c->flat_lane > 0;
   // (the parsed stream itself is not written: only the by-reference kernel reads it, and that runs only when the chunk
   // holds characters outside the alphabet -- the chunk is then parsed once more with the stream, below)
-  if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/true, /*write_seq=*/false)) != MK_OK) return rc;
+  if ((rc = flat ? mk_launch_fparse_flat(c, d_al, begin, n)
+                 : mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/true, /*write_seq=*/false)) != MK_OK) return rc;
+  const size_t n_pos = flat ? begin + n : n;  // positions the kernels downstream walk at most
   const bool two = c->mode == MK_MODE_HASH128;
   c->rtab_chunk_slots = 0;
   c->surv_regions = 0;
@@ -192,35 +208,50 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
     mk_ctx* t = c->fuse_cap ? c->fuse_target : c;
     std::shared_lock<std::shared_mutex> rd(t->table_mu, std::defer_lock);
     if (t != c) rd.lock();
-    rc = two ? mk_launch_count_superkmer2(c, n, min_count) : mk_launch_count_superkmer(c, n, min_count);  // (seq_len <= n)
+    rc = two ? mk_launch_count_superkmer2(c, n_pos, min_count) : mk_launch_count_superkmer(c, n_pos, min_count);  // (seq_len <= n_pos)
   }
   c->fuse_cap = 0;
   if (rc) return rc;
   if ((rc = mk_pull_info(c)) != MK_OK) return rc;  // the one read-back
   MkChunkInfo* h = c->h_info;
+  if (flat && (h->parse_fallback & MK_FP_REFUSED)) {  // not one line per record: this sample is parsed densely from here on
+    c->st.flat_refused += 1;
+    c->flat_lane = -1;
+    // (a refused launch left the running table alone: the fused kernel returned at its abort test, which reads the whole
+    // word, and the survivors of an unfused one are imported further down.  A wave that found no state to start from
+    // may have taken a header line's blanks for a sequence line's: whether the text holds such blanks is the dense
+    // parser's to say)
+    return MK_RETRY_DENSE;
+  }
   if (h->parse_fallback) { c->st.parse_retries += 1; return MK_RETRY_GENERAL; }
   if ((rc = refuse_non_ascii(c)) != MK_OK) return rc;
-  const size_t seq_len = (size_t)h->seq_len;
-  if (h->bad_symbols) {  // windows holding a symbol outside the alphabet: by reference, now
-    // the by-reference kernel reads the parsed stream, which the first parse did not write: parse again (the raw text
-    // is still there), this time for the stream only -- the packed words, the bitmap and the chunk's counters stand
-    // (the second parse adds to the chunk's counters again -- kept bytes >= 0x80 -- so they are set aside and put back)
-    if ((rc = mk_buf_reserve(c, c->ex_tmp, sizeof(MkChunkInfo) + 64)) != MK_OK) return rc;
-    MK_HIP(hipMemcpyAsync(c->ex_tmp.p, c->info.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/false, /*write_seq=*/true)) != MK_OK) return rc;
-    MK_HIP(hipMemcpyAsync(c->info.p, c->ex_tmp.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
-    const u64 bound = std::min<u64>((u64)seq_len, h->bad_symbols * (u64)c->k);
-    c->rtab_chunk_slots = pow2_at_least(2 * (size_t)bound);
-    if ((rc = mk_buf_reserve(c, c->rtab_chunk, c->rtab_chunk_slots * sizeof(MkSlot))) != MK_OK) return rc;
-    if ((rc = mk_clear_table(c, MK_TABLE_REF, c->rtab_chunk.p, c->rtab_chunk_slots)) != MK_OK) return rc;
-    if ((rc = mk_launch_count_byref(c, seq_len, true)) != MK_OK) return rc;
-    if ((rc = mk_launch_count_survivors(c, min_count)) != MK_OK) return rc;
-    if ((rc = mk_pull_info(c)) != MK_OK) return rc;
-  }
+  const size_t seq_len = (size_t)h->seq_len;  // (flat lane: raw positions)
+  // (the exact passes read the packed words and the bitmap in the coordinates of the launch that overflowed: they run
+  // before the second parse below rewrites both)
   if ((rc = repartition_exactly(c, seq_len, min_count, two ? mk_launch_count_superkmer2 : mk_launch_count_superkmer)) != MK_OK) return rc;
   if ((rc = finish_count(c, seq_len, min_count, two)) != MK_OK) {
     if (h->errors && !two && c->fused_last) spoil(c, c->fuse_target ? c->fuse_target : c);
     return rc;
+  }
+  if (h->bad_symbols) {  // windows holding a symbol outside the alphabet: by reference, now
+    // the by-reference kernel reads the parsed stream, which the first parse did not write: parse again (the raw text
+    // is still there), this time with the stream -- the chunk's counters stand (the second parse adds to them again
+    // -- kept bytes >= 0x80 -- so they are set aside and put back).  It also writes the packed words and the bitmap,
+    // which nobody reads after it but the by-reference kernel: that needs the bitmap in the stream's coordinates, which
+    // the flat lane's is not, and the stream's own length on the device (MkChunkInfo's first word: not put back).
+    static_assert(offsetof(MkChunkInfo, seq_len) == 0, "the counters put back below are everything behind seq_len");
+    if ((rc = mk_buf_reserve(c, c->ex_tmp, sizeof(MkChunkInfo) + 64)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync(c->ex_tmp.p, c->info.p, sizeof(MkChunkInfo), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = mk_launch_fparse(c, d_al, begin, n, /*fuse_pack_nt=*/flat, /*write_seq=*/true)) != MK_OK) return rc;
+    MK_HIP(hipMemcpyAsync((char*)c->info.p + sizeof(u64), (const char*)c->ex_tmp.p + sizeof(u64), sizeof(MkChunkInfo) - sizeof(u64),
+                          hipMemcpyDeviceToDevice, c->stream));
+    const u64 bound = std::min<u64>((u64)seq_len, h->bad_symbols * (u64)c->k);
+    c->rtab_chunk_slots = pow2_at_least(2 * (size_t)bound);
+    if ((rc = mk_buf_reserve(c, c->rtab_chunk, c->rtab_chunk_slots * sizeof(MkSlot))) != MK_OK) return rc;
+    if ((rc = mk_clear_table(c, MK_TABLE_REF, c->rtab_chunk.p, c->rtab_chunk_slots)) != MK_OK) return rc;
+    if ((rc = mk_launch_count_byref(c, seq_len, true)) != MK_OK) return rc;  // (the grid covers seq_len; the kernel reads the stream's length)
+    if ((rc = mk_launch_count_survivors(c, min_count)) != MK_OK) return rc;
+    if ((rc = mk_pull_info(c)) != MK_OK) return rc;
   }
   const bool fused_done = !two && c->fused_last;  // (of the launch that counted: the exact pass is never fused)
   if (fused_done) {
@@ -253,6 +284,8 @@ static int process_chunk_fast(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min
   // windows per distinct key, a fraction of the survivors -- made the first chunk of the next sample plan two sub-range
   // passes per bucket, 480 instead of 305 us, and would size the fused launch's table for nothing)
   const bool full_chunk = !c->dup_known || seq_len * 4 >= c->part_prev_len * 3;
+  if (full_chunk && n >= ((size_t)1 << 20)) c->flat_share = (double)h->symbols / (double)n;  // (the flat lane's guard, next sample)
+  if (flat) c->st.flat_chunks += 1;
   if (!two && (full_chunk || !c->surv_hint_ok)) { c->surv_hint = h->survivors; c->surv_hint_ok = true; }
   note_hints(c, seq_len, full_chunk);
   if (mk_env_set("MK_VERBOSE"))
@@ -284,6 +317,7 @@ static int process_chunk(mk_ctx* c, const uint8_t* d_raw, size_t n, u64 min_coun
   if (!c->clean_mode && c->alphabet == MK_ALPHABET_NT2 && n && n < 0xFE000000ull &&
       ((c->mode == MK_MODE_HASH64 && c->k >= MK_SK_MIN_K && c->k <= 32) || c->mode == MK_MODE_HASH128)) {
     rc = process_chunk_fast(c, d_raw, n, min_count);
+    if (rc == MK_RETRY_DENSE) rc = process_chunk_fast(c, d_raw, n, min_count);  // (flat_lane is off now)
     if (rc != MK_RETRY_GENERAL) return rc;
     known_blank = true;  // (the fast parser has just said so: straight to the general one)
   }

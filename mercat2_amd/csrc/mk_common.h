@@ -65,13 +65,16 @@ struct MkChunkInfo {
   unsigned long long new_rows_ref;
   unsigned long long distinct;      // distinct packed keys seen in this chunk (partitioned path)
   unsigned long long errors;        // non-zero: a kernel hit a condition it cannot handle
-  unsigned long long parse_fallback;  // fast parser saw a blank in a sequence line: re-parse generally
+  unsigned long long parse_fallback;  // fast parser: MK_FP_BLANK (a blank in a sequence line: re-parse generally) | MK_FP_REFUSED
   unsigned long long records;       // super-k-mer records written (partitioned nt path)
   unsigned long long part_overflow; // a bucket region sized from a sampled histogram was too small: partition again, exactly
   unsigned long long spilled;       // fused upsert (mk_skcount.hip): survivors written to the spill list instead of the running table
   unsigned long long split_exhausted; // sub-ranges counted (or found void) with every split bit used: the whole LDS table probed
   unsigned long long pre_void;      // two-word pre-filter (mk_skmer2.hip): buckets it could not split far enough (count them exactly)
 };
+
+#define MK_FP_BLANK 1u    // MkChunkInfo::parse_fallback: the fast parsers' one assumption failed (mk_fparse.hip)
+#define MK_FP_REFUSED 2u  // ... the flat lane's rule failed: the text is not one line per record (mk_fparse_flat)
 
 enum MkMode { MK_MODE_DENSE = 0, MK_MODE_HASH64 = 1, MK_MODE_HASH128 = 2, MK_MODE_BYREF = 3 };
 enum MkKernelId { MK_K_PARSE = 0, MK_K_PACK, MK_K_COUNT, MK_K_EXOTIC, MK_K_FILTER, MK_K_EXPORT, MK_K_PART, MK_K_NUM };
@@ -203,6 +206,9 @@ struct mk_ctx {
   bool fused_last = false;            // the last count launch was a fused one
   unsigned long long surv_hint = 0;   // survivors of the previous chunk of this sample
   bool surv_hint_ok = false;
+  // flat lane (mk_fparse.hip mk_fparse_flat): decided at a sample's first chunk, kept until mk_reset
+  int flat_lane = 0;          // 0 not decided yet, 1 taken, -1 not taken (the guard said no, or a launch was refused)
+  double flat_share = -1.0;   // symbols per raw byte of the last full chunk; < 0: not known yet
   // one table for several contexts of a device (mk_share_table): the fused launches of this context upsert into the owner's
   mk_ctx* share_owner = nullptr;
   mk_ctx* fuse_target = nullptr;      // the context whose table the NEXT / last fused launch of this one upserts into (this or share_owner)
@@ -355,6 +361,8 @@ void mk_decode_row(const mk_ctx* c, const ExportView& v, size_t i, uint8_t* out)
 int mk_launch_parse(mk_ctx* c, const uint8_t* d_raw, size_t n);
 // fast parse (mk_fparse.hip): same output; sets info.parse_fallback when its assumption fails
 int mk_launch_fparse(mk_ctx* c, const uint8_t* d_raw, size_t begin, size_t len, bool fuse_pack_nt, bool write_seq = true);
+// flat lane: packed words and bad bitmap at raw-text positions; sets MK_FP_REFUSED when the text is not one line per record
+int mk_launch_fparse_flat(mk_ctx* c, const uint8_t* d_raw, size_t begin, size_t len);
 // pack: seq -> codes, bad (+ info.bad_symbols)
 int mk_launch_pack(mk_ctx* c, size_t seq_cap);
 // counting

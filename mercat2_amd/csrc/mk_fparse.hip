@@ -482,11 +482,163 @@ __global__ __launch_bounds__(FP_THREADS) void mk_fparse_emit(const uint8_t* __re
   // (without the fused pack nobody reads the sum: the pack kernel counts the bad symbols)
   for (int d = 32; d > 0; d >>= 1) nbad += __shfl_down(nbad, d);
   if (codes && lane == 0 && nbad > 0) atomicAdd(&info->bad_symbols, (u64)nbad);
-  if (__ballot(flag_low != 0) && lane == 0) atomicOr(&info->parse_fallback, 1ull);  // the host re-parses the chunk generally
+  if (__ballot(flag_low != 0) && lane == 0) atomicOr(&info->parse_fallback, (unsigned long long)MK_FP_BLANK);  // the host re-parses the chunk generally
   if (__ballot(nhi != 0)) {  // (never, for ASCII input)
     for (int d = 32; d > 0; d >>= 1) nhi += __shfl_down(nhi, d);
     if (lane == 0) atomicAdd(&info->non_ascii, (u64)nhi);
   }
+}
+
+// ------------------------------------------------------------------------------------------ the flat lane
+// Read files (one header line, one sequence line per record): the packed word and the bad bit of a symbol are written at
+// the symbol's position in the RAW text (counted from the 16-byte boundary below the chunk), header bytes and line ends
+// marked bad as a separator is in the dense stream.  No window spans a bad bit, so the kernels downstream count the same
+// windows as long as ONE rule holds: two symbols that are neighbours in the dense stream are neighbours in the text, i.e.
+// every run of dropped bytes between two kept symbols holds a header-line start.  That is a third carry chain, "a symbol
+// was kept since the last header-line start" (generate: a kept symbol; kill: a header-line start); a kept symbol that
+// begins a new run while the chain is set breaks the rule (a sequence on two lines, a '*' inside a sequence) and the
+// launch raises MK_FP_REFUSED in info->parse_fallback.  Positions are fixed, so there is no prefix sum, no compaction
+// and nothing to wait for: a wave takes its entry state from the 1 KiB of text in front of it, which must hold a
+// header-line start (or the chunk's first byte) -- otherwise the launch is refused as well.  So that a text is taken
+// or refused whatever its lines' places against the waves, the same is asked of EVERY whole 1 KiB sub-step of the text:
+// the lane is for records shorter than that (reads), not for contigs or long reads.  Every word is stored whole.
+struct FlState {
+  unsigned prev_nl;    // the byte in front is a line end (or the chunk starts here)
+  unsigned h;          // ... lies inside a header line
+  unsigned k;          // a symbol was kept since the last header-line start
+  unsigned prev_kept;  // the byte in front is a kept symbol
+  unsigned starts;     // the sub-step just taken holds a header-line start
+};
+
+// One 1 KiB sub-step: wave_step, then the kept-since-header chain over `kept` (the emitted bytes that are symbols).
+// viol: kept symbols that begin a run although the chain is set.
+__device__ __forceinline__ void flat_step(unsigned nl, unsigned gt, unsigned st, unsigned low, FlState& s, unsigned& kept,
+                                          unsigned& start, unsigned& bad_low, unsigned& viol) {
+  const int lane = threadIdx.x & 63;
+  unsigned out, last_nl;
+  const unsigned hout = wave_step(nl, gt, st, low, s.prev_nl, s.h, out, start, bad_low, last_nl);
+  kept = out & ~start;
+  unsigned kout0;
+  (void)lane_header(kept, start, 0u, kout0);
+  const u64 G = __ballot(kout0 != 0);  // a symbol kept behind the lane's last header-line start
+  const u64 P = __ballot(start == 0);  // no header-line start in the lane: passes its entry state on
+  const u64 A = G | P, B = G;
+  const u64 CI = (A + B + (u64)s.k) ^ A ^ B;
+  const unsigned kin = (unsigned)(CI >> lane) & 1u;
+  unsigned kout;
+  const unsigned K = lane_header(kept, start, kin, kout);
+  const unsigned my_last_kept = (kept >> 15) & 1u;
+  const unsigned pk = (unsigned)__builtin_amdgcn_update_dpp((int)s.prev_kept, (int)my_last_kept, 0x138, 0xf, 0xf, false);  // wave_shr:1
+  const unsigned before_kept = ((kept << 1) | pk) & 0xFFFFu, before_k = ((K << 1) | kin) & 0xFFFFu;
+  viol = kept & ~before_kept & before_k;
+  s.prev_nl = last_nl;
+  s.h = hout;
+  s.k = mk_wave_last(kout);
+  s.prev_kept = mk_wave_last(my_last_kept);
+  s.starts = P != ~0ull ? 1u : 0u;
+}
+
+#define FL_WINDOW 1024  // bytes of text in front of a wave that its entry state is taken from: one sub-step
+
+// code_words: u64 words of `codes` to write (two per word of `bad`); the last wave fills what lies behind the text.
+__global__ __launch_bounds__(FP_THREADS) void mk_fparse_flat(const uint8_t* __restrict__ raw, size_t begin, size_t n, size_t nwaves,
+                                                             MkChunkInfo* __restrict__ info, u64* __restrict__ codes,
+                                                             u64* __restrict__ bad, size_t code_words) {
+  const size_t wave = (size_t)blockIdx.x * FP_WAVES + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  unsigned nsym = 0, nbad = 0, nhi = 0;
+  if (wave < nwaves) {
+    const size_t base = wave * FP_WAVE_BYTES;
+    FlState s{1u, 0u, 0u, 0u, 0u};
+    unsigned refused = 0, flag_low = 0;
+    uint4 v_next = load16(raw, base + (size_t)lane * 16, begin, n);
+    if (base) {
+      // entry state: the chains run over the window from zero are right behind its last header-line start
+      const size_t wb = base - FL_WINDOW;
+      s.prev_nl = (wb <= begin) ? 1u : ((raw[wb - 1] == 10 || raw[wb - 1] == 13) ? 1u : 0u);
+      unsigned nl, gt, st, low, hi, kept, start, bl, viol;
+      classify16(load16(raw, wb + (size_t)lane * 16, begin, n), nl, gt, st, low, hi);
+      flat_step(nl, gt, st, low, s, kept, start, bl, viol);
+      if (wb > begin && !s.starts) {  // a header line or a sequence line longer than the window
+        refused = 1;
+        s.h = s.k = 0;
+      }
+    }
+    unsigned* __restrict__ bad32 = reinterpret_cast<unsigned*>(bad);
+#pragma unroll 1
+    for (int sub = 0; sub < FP_SUB; ++sub) {
+      const size_t pos = base + (size_t)sub * 1024 + (size_t)lane * 16;
+      const uint4 v = v_next;
+      if (sub + 1 < FP_SUB) v_next = load16(raw, pos + 1024, begin, n);
+      unsigned nl, gt, st, low, hi, kept, start, bl, viol;
+      classify16(v, nl, gt, st, low, hi);
+      flat_step(nl, gt, st, low, s, kept, start, bl, viol);
+      refused |= viol | ((!s.starts && base + (size_t)(sub + 1) * 1024 <= n) ? 1u : 0u);  // (the text's last, partial sub-step needs none)
+      flag_low |= bl;
+      // the 2-bit pack of mk_fparse_emit, on the lane's own 16 bytes: codes, first character on top, and the bytes
+      // that are not what their code stands for
+      unsigned g = 0, z0 = 0, z1 = 0;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const unsigned xd = d == 0 ? v.x : (d == 1 ? v.y : (d == 2 ? v.z : v.w));
+        const unsigned c = ((xd >> 1) & 0x03030303u) ^ ((xd >> 2) & 0x01010101u);
+        const unsigned df = __builtin_amdgcn_perm(0u, 0x54474341u, c) ^ xd;
+        const unsigned nz = (((df & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | df) & 0x80808080u;  // 0x80 in every byte outside ACGT
+        g |= __builtin_amdgcn_udot4(c, 0x01041040u, 0u, false) << (24 - 8 * d);
+        if (d < 2) z0 = __builtin_amdgcn_udot4(nz, (d & 1) ? 0x80402010u : 0x08040201u, z0, false);
+        else z1 = __builtin_amdgcn_udot4(nz, (d & 1) ? 0x80402010u : 0x08040201u, z1, false);
+      }
+      const unsigned other = (z0 >> 7) | ((z1 >> 7) << 8);  // bytes outside the alphabet
+      const unsigned good = kept & ~other;
+      // symbol j of the lane: bits 31-2j, 30-2j of its half word.  Everything but a good symbol has code 0.
+      unsigned m = __brev(good) >> 16;
+      m = (m | (m << 8)) & 0x00FF00FFu;
+      m = (m | (m << 4)) & 0x0F0F0F0Fu;
+      m = (m | (m << 2)) & 0x33333333u;
+      m = (m | (m << 1)) & 0x55555555u;
+      g &= m | (m << 1);
+      const unsigned b16 = ~good & 0xFFFFu;
+      nsym += __popc(kept);
+      nbad += __popc(kept & other);
+      nhi += __popc(kept & hi);
+      // whole words: the even lane of a pair stores both lanes' halves (quad_perm [1,0,3,2]: the pair's other lane)
+      const unsigned g_o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)g, 0xB1, 0xf, 0xf, false);
+      const unsigned b_o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)b16, 0xB1, 0xf, 0xf, false);
+      const size_t w = pos >> 5;
+      if (!(lane & 1) && w < code_words) {
+        codes[w] = ((u64)g << 32) | g_o;
+        bad32[w] = b16 | (b_o << 16);
+      }
+    }
+    if (wave + 1 == nwaves) {  // the padding the kernels downstream may read: bad, codes 0
+      for (size_t w = nwaves * (FP_WAVE_BYTES / 32) + (size_t)lane; w < code_words; w += 64) {
+        codes[w] = 0ull;
+        bad32[w] = ~0u;
+      }
+    }
+    const unsigned fb = (__ballot(flag_low != 0) ? MK_FP_BLANK : 0u) | (__ballot(refused != 0) ? MK_FP_REFUSED : 0u);
+    if (fb && lane == 0) atomicOr(&info->parse_fallback, (unsigned long long)fb);
+    if (wave == 0 && lane == 0) info->seq_len = n;
+  }
+  block_add(&info->symbols, (u64)nsym);  // (one add per workgroup; nothing to add is no add)
+  block_add(&info->bad_symbols, (u64)nbad);
+  block_add(&info->non_ascii, (u64)nhi);
+}
+
+// The flat lane's parser (process_chunk_fast): packed words and bad bitmap in raw-text positions, info->seq_len = begin + len.
+// info->parse_fallback & MK_FP_REFUSED afterwards: the text is not one line per record; parse it with mk_launch_fparse.
+int mk_launch_fparse_flat(mk_ctx* c, const uint8_t* d_raw, size_t begin, size_t len) {
+  if (len == 0) { c->err = "mk_launch_fparse_flat: empty chunk (internal error)"; return MK_ERR_STATE; }
+  const size_t n = begin + len;
+  const size_t bad_words = n / 64 + 4;  // (what reserve_chunk_buffers has room for, and mk_launch_fparse fills)
+  const size_t nwaves = (n + FP_WAVE_BYTES - 1) / FP_WAVE_BYTES;
+  const unsigned blocks = (unsigned)((nwaves + FP_WAVES - 1) / FP_WAVES);
+  mk_prof_begin(c, MK_K_PARSE);
+  hipLaunchKernelGGL(mk_fparse_flat, dim3(blocks), dim3(FP_THREADS), 0, c->stream, d_raw, begin, n, nwaves, (MkChunkInfo*)c->info.p,
+                     (u64*)c->codes.p, (u64*)c->bad.p, 2 * bad_words);
+  mk_prof_end(c);
+  MK_HIP(hipGetLastError());
+  return MK_OK;
 }
 
 // Returns MK_OK after enqueueing; info->parse_fallback != 0 afterwards means "re-parse with the general kernels".
