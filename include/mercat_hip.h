@@ -1027,6 +1027,64 @@ int mk_fastq_overlap_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t pi
 int mk_fastq_overlap_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const mk_overlap_opt_t* opt, size_t cap, uint8_t* d_keep,
                             uint64_t* d_rows, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec, mk_fastq_overlap_t* st);
 
+/* ---- per-cycle quality control of a FASTQ text: the figures MerCat2 asks fastqc for, before and after trimming -- where
+ *      along the read the quality falls and the base composition drifts, and per read its length, mean quality and GC
+ *      share -- reduced on the GPU from the text, as a stated rule.  No plots, no duplication or over-represented
+ *      sequences, no adapter or k-mer content, no position grouping and no verdicts: nothing here is fastqc's number ----
+ * Lines, records and the tolerated trailing empty lines are mk_fastq_qtrim_*'s; one trailing '\r' is taken off the
+ * sequence line and off the quality line, as there.  The checks are its own, in its order: '@', '+', equal lengths, a text
+ * that ends inside a record, and kind 5: a byte of the quality line below phred_base ("its quality line holds a character
+ * below the phred base").  The lowest record wins, then the lowest kind; all are MK_ERR_UNSUPPORTED with the same
+ * phrases.  No table is read; an open chunk is MK_ERR_STATE.
+ * Options: phred_base 33 or 64; max_pos = P in 1 .. MK_QC_MAX_POS; paired 0 or 1; anything else is MK_ERR_ARG.  With
+ * paired, record r belongs to class c = r & 1 and an odd record count is MK_ERR_RANGE; without, c = 0.  C = the number of
+ * classes, 1 or 2.
+ * Base i of a record of L bases has q[i] = qual[i] - phred_base (>= 0; a negative value is the kind-5 error), the bin
+ * v[i] = min(q[i], MK_QC_QBINS - 1), the base class b[i] of seq[i] | 0x20: 'a' 0, 'c' 1, 'g' 2, 't' 3, 'n' 4, anything
+ * else 5, and the row p[i] = min(i, P): row P collects every cycle from P on.
+ * The tables, all uint64, exact, zeroed by the call, all required (a NULL one is MK_ERR_ARG):
+ *   pos_qual[c][p][v]   C x (P + 1) x 96: bases of class c, row p, quality bin v
+ *   pos_base[c][p][k]   C x (P + 1) x 8: bases of class c, row p, base class k; columns 6 and 7 stay 0
+ *   read_len[c][l]      C x (P + 2): records of length l for l <= P; index P + 1: the records longer than P
+ *   read_qual[c][m]     C x 96: records with L > 0 by m = min(qsum / L, 95), integer division, qsum = the sum of the
+ *                       unclipped q[i]
+ *   read_gc[c][g]       C x 101: records with L > 0 by g = (200 gc + L) / (2 L), integer division (rounds half up), gc =
+ *                       the bases of class 1 or 2
+ * rows[r], optional (NULL: none): four uint64 a record: length, qsum, gc, n (the bases of class 4).  cap: the records rows
+ * has room for; a text with more is MK_ERR_RANGE with the count in *nrec (checked first; not when rows is NULL).
+ * mk_fastq_qc_t: min_len and max_len per class, both 0 for a class without records.
+ * mk_fastq_qc_text: host memory, piece by piece (with paired a piece ends behind an even record: mk_fastq_pair_cuts); the
+ * tables are accumulated on the device over all pieces and copied back once; nothing depends on piece_bytes.
+ * mk_fastq_qc_device: everything in DEVICE memory of the context's GPU (the mk_qc_out_t itself is host memory, its
+ * pointers device memory), one piece of at most 2^32 - 1 bytes (more: MK_ERR_RANGE, before anything is read); the text at
+ * any address, the tables and rows aligned to 8 (MK_ERR_ARG otherwise).  Both leave the tables unspecified on any error. */
+#define MK_QC_MAX_POS 16384
+#define MK_QC_QBINS 96
+typedef struct mk_qc_opt_t {
+  uint32_t phred_base; /* 33 or 64 (else MK_ERR_ARG) */
+  uint32_t max_pos;    /* P: 1 .. MK_QC_MAX_POS      */
+  uint32_t paired;     /* 0 or 1                     */
+} mk_qc_opt_t;
+typedef struct mk_qc_out_t {
+  uint64_t* pos_qual;
+  uint64_t* pos_base;
+  uint64_t* read_len;
+  uint64_t* read_qual;
+  uint64_t* read_gc;
+  uint64_t* rows; /* or NULL */
+} mk_qc_out_t;
+typedef struct mk_fastq_qc_t {
+  uint64_t records, lines, bases; /* of the text; bases: sequence bytes */
+  uint64_t min_len[2], max_len[2];
+  /* seconds: host time in the copies to the device; HIP-event time of the line index; of the per-read kernel; of the
+   * per-cycle kernel; host time in the copies back */
+  double s_copy, s_index, s_reads, s_cycles, s_write;
+} mk_fastq_qc_t;
+int mk_fastq_qc_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes, const mk_qc_opt_t* opt, size_t cap,
+                     const mk_qc_out_t* out, size_t* nrec, mk_fastq_qc_t* st);
+int mk_fastq_qc_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const mk_qc_opt_t* opt, size_t cap, const mk_qc_out_t* d_out,
+                       size_t* nrec, mk_fastq_qc_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

@@ -63,7 +63,16 @@ bases within -overlap_diff mismatches and -overlap_err mismatches a base), and a
 or _merged.fastq and _unmerged.fastq, hold what -adapt, -qtrim and the count then see, overlap/<sample>_overlap.tsv every
 read's length, cut, fragment, overlap and mismatches, overlap/<sample>_summary.tsv the pair counts and the fragment lengths.
 Indels (in adapters and in the overlap), 5' and anchored adapters, quality-aware correction of unmerged mates (fastp -c) and
-poly-G trimming stay out.  Per-position QC plots, ORF calling (-prod / -fgs), the HTML report and plots belong
+poly-G trimming stay out.  -qc [MAXPOS] stands where MerCat2 runs fastqc, on the reads as read and again on the trimmed
+reads: for every FASTQ sample (which still needs -skipclean or one of the steps above) the GPU reduces the text to per-cycle
+and per-read tables (mk_fastq_qc_text: at every cycle the bases of every quality value and of A, C, G, T, N and anything
+else, cycles from MAXPOS on in one row; per read its length, mean quality and GC share), written as
+qc/<sample>_raw_cycles.tsv (bases, mean, percentiles and composition a cycle), _quality.tsv, _gc.tsv, _length.tsv and
+_summary.tsv, and as qc/<sample>_clean_*.tsv from what the count sees where -overlap, -adapt or -qtrim ran.  -qc_paired or
+-overlap gives every figure per mate (the clean stage only while mates still alternate: not after -overlap merge, -adapt or
+-qtrim); -qc_phred sets the offset.  The figures are that stated rule's, not fastqc's: duplication levels,
+over-represented sequences, adapter and k-mer content, position grouping and verdicts stay out.  QC plots, ORF calling
+(-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -293,6 +302,15 @@ def parseargs(argv=None):
     p.add_argument("-gpus", type=int, default=None,
                    help="number of GPUs to use, devices 0..N-1 [all visible]: a sample that is chunked (-s) has its chunks spread "
                         "over them (chunk i on GPU i mod N, tables summed by peer copies); small samples go one per GPU")
+    p.add_argument("-qc", type=int, nargs="?", const=512, default=None, metavar="MAXPOS",
+                   help="FASTQ input: quality control of the reads on the GPU where MerCat2 runs fastqc -- per cycle the quality "
+                        "distribution and the base composition, per read the length, mean quality and GC share, as a stated rule "
+                        "that is not fastqc's (no plots, duplication levels, adapter or k-mer content, verdicts). Cycles from "
+                        "MAXPOS on share one row [512]. Writes qc/<sample>_raw_cycles.tsv, _quality.tsv, _gc.tsv, _length.tsv and "
+                        "_summary.tsv from the text as read and, where -overlap, -adapt or -qtrim ran, qc/<sample>_clean_*.tsv "
+                        "from the reads the count sees")
+    p.add_argument("-qc_phred", type=int, default=None, choices=(33, 64), help="-qc: the offset of the quality characters [33]")
+    p.add_argument("-qc_paired", action="store_true", help="-qc: the FASTQ inputs are interleaved pairs: every figure per mate")
     p.add_argument("-gpu", type=int, default=None, help="use exactly this one HIP device (overrides -gpus)")
     p.add_argument("-streams", type=int, default=None,
                    help="engine contexts counting chunks concurrently [2 for one-word keys, else 1]")
@@ -335,6 +353,19 @@ def parseargs(argv=None):
             p.error(f"-qtrim_low_frac {args.qtrim_low_frac}: must lie in 0..1")
         if args.qtrim_low_frac is not None and not args.qtrim_low:
             p.error("-qtrim_low_frac needs -qtrim_low Q: no base is low without it")
+    if args.qc is None:
+        if args.qc_phred is not None:
+            p.error("-qc_phred needs -qc")
+        if args.qc_paired:
+            p.error("-qc_paired needs -qc")
+    else:
+        given = list(args.i)
+        if args.f and os.path.isdir(args.f):
+            given += sorted(os.listdir(args.f))
+        if not any(fastq_ext(Path(name)) for name in given):
+            p.error(f"-qc looks at FASTQ reads ({' / '.join(FILE_EXT_FASTQ)}); no input is a FASTQ file")
+        if not 1 <= args.qc <= 16384:
+            p.error(f"-qc {args.qc}: must lie in 1..16384")
     args.adapters = None
     if args.adapt is None:
         for flag in ("adapt_overlap", "adapt_err", "adapt_len"):
@@ -710,16 +741,51 @@ def overlap_sample(args, f: Path, raw, out: Path, base: str, device: int) -> byt
     return done["text"] + done["unmerged"] if merging else done["text"]
 
 
-def prepared_reads(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
+def qc_sample(args, f: Path, text: bytes, out: Path, base: str, stage: str, paired: bool, device: int, timings=None) -> None:
+    """-qc: the quality-control tables of ``text``, the reads of FASTQ sample ``base`` at ``stage`` ("raw": as read;
+    "clean": as the count sees them), reduced on GPU ``device`` by kmers.qc_reads, which writes
+    qc/<base>_<stage>_cycles.tsv, _quality.tsv, _gc.tsv, _length.tsv and _summary.tsv.  ``timings``, if given, has the
+    seconds added to its "qc_s"."""
+    from . import kmers, native
+    folder = out / "qc"
+    folder.mkdir(parents=True, exist_ok=True)
+    t0 = timeit.default_timer()
+    try:
+        kmers.qc_reads(text, folder / f"{base}_{stage}", max_pos=args.qc, phred_base=args.qc_phred or 33, paired=paired, device=device)
+    except native.MercatHipError as e:
+        raise SystemExit(f"-qc '{f.name}' ({stage}): {e}")
+    if timings is not None:
+        timings["qc_s"] = timings.get("qc_s", 0.0) + timeit.default_timer() - t0
+
+
+def prepared_reads(args, f: Path, raw, out: Path, base: str, device: int, timings=None) -> bytes:
     """The reads of FASTQ sample ``base`` as the count sees them: through -overlap, then -adapt, then -qtrim, where
-    given."""
+    given.  With -qc the two places where MerCat2 runs fastqc: the text as read (with -overlap_mate both files,
+    interleaved), and, where one of those steps ran, what it left.  The raw stage is per mate with -qc_paired or
+    -overlap; the clean stage too, unless mates no longer alternate in it: after -overlap merge, and after -adapt or
+    -qtrim, which judge every read on its own."""
+    qc = args.qc is not None
+    steps = args.overlap is not None or args.adapt is not None or args.qtrim is not None
+    paired = qc and (args.qc_paired or args.overlap is not None)
+    if qc:
+        raw = read_fasta_bytes(f) if raw is None else raw
+        text = raw
+        if args.overlap is not None and args.overlap_mate is not None:
+            from . import native
+            text = native.interleave_fastq(raw, read_fasta_bytes(args.overlap_mate))
+        qc_sample(args, f, text, out, base, "raw", paired, device, timings)
+        del text
     if args.overlap is not None:
         raw = overlap_sample(args, f, raw, out, base, device)
     if args.adapt is not None:
         raw = adapt_sample(args, f, raw, out, base, device)
     if args.qtrim is not None:
         raw = qtrim_sample(args, f, raw, out, base, device)
-    return read_fasta_bytes(f) if raw is None else raw
+    raw = read_fasta_bytes(f) if raw is None else raw
+    if qc and steps:
+        qc_sample(args, f, raw, out, base, "clean", paired and args.overlap != "merge" and args.adapt is None and args.qtrim is None,
+                  device, timings)
+    return raw
 
 
 def count_converted(base: str, holder: dict, fut, tsv: Path, args, devices, home: int, lines: list, tables: dict, t: dict) -> None:
@@ -845,10 +911,12 @@ def main(argv=None) -> int:
             t0 = timeit.default_timer()
             raw = read_fasta_bytes(f)
             t["read_s"] = timeit.default_timer() - t0
-            if base in fastq and (args.qtrim is not None or args.adapt is not None or args.overlap is not None):
+            steps = args.qtrim is not None or args.adapt is not None or args.overlap is not None
+            if base in fastq and (steps or args.qc is not None):
                 t0 = timeit.default_timer()
-                raw = prepared_reads(args, f, raw, out, base, home_of[base])
-                t["qtrim_s"] = timeit.default_timer() - t0
+                raw = prepared_reads(args, f, raw, out, base, home_of[base], timings=t)
+                if steps:
+                    t["qtrim_s"] = timeit.default_timer() - t0 - t.get("qc_s", 0.0)
             if base in fastq:
                 path, fut, holder = fq2fa_background(f, raw, out / "clean", base, gz_writers, timings=t, limit=args.s * 1024 * 1024)
             else:
@@ -888,7 +956,7 @@ def main(argv=None) -> int:
             if kind == "nucleotide" and base in fastq:
                 limit = args.s * 1024 * 1024
                 if cleaned[base] is None:  # (not loaded up front: the conversion, its file, then the count)
-                    text, _ = fq2fa_text(prepared_reads(args, f, None, out, base, home))
+                    text, _ = fq2fa_text(prepared_reads(args, f, None, out, base, home, timings=t))
                     os.makedirs(out / "clean", exist_ok=True)
                     size = _write_clean_gz(out / "clean" / f"{base}.fna.gz", text, t)
                     chunked = args.s > 0 and size >= limit

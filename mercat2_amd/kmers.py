@@ -614,6 +614,35 @@ def qtrim_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None],
     return done
 
 
+def qc_reads(file: Union[str, Path, bytes], out_prefix: Union[str, Path, None] = None, max_pos: int = 512, phred_base: int = 33,
+             paired: bool = False, mate_file: Union[str, Path, None] = None, device: int = 0) -> Dict[str, object]:
+    """The quality-control tables of a FASTQ file ('.fq' / '.fastq', plain or '.gz'; or the FASTQ text itself as bytes,
+    for a caller that holds it already), reduced on the GPU (Counter.fastq_qc has the rule and the tables: per cycle the
+    bases of every quality value and of every base class, per read its length, mean quality and GC share).  This stands
+    where MerCat2 runs fastqc; the figures are that stated rule's, not fastqc's (no plots, no duplication levels, no
+    verdicts).  No table is read: the call opens a small context of its own on ``device``.
+    Paired reads (``paired``: the file is interleaved; or ``mate_file``: the second file, interleaved with the first on
+    the host by native.interleave_fastq): every table has a class a mate.  ``out_prefix``: the tables are also written as
+    ``<out_prefix>_cycles.tsv``, ``_quality.tsv``, ``_gc.tsv``, ``_length.tsv`` and ``_summary.tsv``
+    (report.write_qc_files).  Returns the tables and, under their names, the mk_fastq_qc_t figures."""
+    is_text = isinstance(file, (bytes, bytearray, memoryview))
+    for f in (None if is_text else file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("qc_reads: needs FASTQ input (%s), not %s" % (" / ".join(FASTQ_SUFFIXES), f))
+    raw = bytes(file) if is_text else read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    info: Dict[str, object] = {}
+    with native.Counter(5, native.ALPHABET_NT2, device=device) as ctx:
+        done: Dict[str, object] = ctx.fastq_qc(raw, max_pos=max_pos, phred_base=phred_base, paired=bool(paired or mate_file is not None),
+                                               info=info)
+    if out_prefix is not None:
+        from .report import write_qc_files
+        write_qc_files(out_prefix, done)
+    done.update({name: value for name, value in info.items() if not name.startswith("s_")})
+    return done
+
+
 def _named_adapters(adapters) -> Tuple[List[str], List[str]]:
     """(names, seqs) of ``adapters``: None (native.ILLUMINA_ADAPTERS), a FASTA file (native.read_adapters), (name, seq)
     pairs, or plain sequences, which are named by themselves."""

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "mk_fastq_qtrim_text", "mk_fastq_qtrim_device", "mk_fastq_pair_cuts",
     "mk_adapters_pack", "mk_fastq_adapt_text", "mk_fastq_adapt_device",
     "mk_fastq_overlap_text", "mk_fastq_overlap_device",
+    "mk_fastq_qc_text", "mk_fastq_qc_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -319,6 +320,49 @@ def qtrim_options(cut_back: int = 20, cut_front: int = 0, min_len: int = 0, max_
         if not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError("%s %r: must lie in 0..2^32-1" % (name, v))
     return QtrimOpt(**{name: int(v) for name, v in vals.items()})
+
+
+QC_MAX_POS, QC_QBINS, QC_GC_BINS = 16384, 96, 101  # MK_QC_MAX_POS, MK_QC_QBINS; the bins of read_gc
+QC_TABLES = ("pos_qual", "pos_base", "read_len", "read_qual", "read_gc")  # the tables of Counter.fastq_qc, in mk_qc_out_t's order
+QC_COLUMNS = ("length", "qsum", "gc", "n")  # the columns of Counter.fastq_qc's rows
+QC_BASES = ("A", "C", "G", "T", "N", "other")  # the base classes: columns 0 .. 5 of pos_base
+
+
+class QcOpt(C.Structure):
+    """mk_qc_opt_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("phred_base", "max_pos", "paired")]
+
+
+class QcOut(C.Structure):
+    """mk_qc_out_t (include/mercat_hip.h): host or device addresses, 0 for no rows."""
+    _fields_ = [(n, C.c_void_p) for n in QC_TABLES + ("rows",)]
+
+
+class FastqQc(C.Structure):
+    """mk_fastq_qc_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("records", "lines", "bases")] + [("min_len", C.c_uint64 * 2), ("max_len", C.c_uint64 * 2)] +
+                [(n, C.c_double) for n in ("s_copy", "s_index", "s_reads", "s_cycles", "s_write")])
+
+    def as_dict(self):
+        return {n: list(getattr(self, n)) if n in ("min_len", "max_len") else getattr(self, n) for n, _ in self._fields_}
+
+
+def qc_options(max_pos: int = 512, phred_base: int = 33, paired: bool = False) -> "QcOpt":
+    """mk_qc_opt_t of Counter.fastq_qc's arguments; ValueError for one that no uint32 holds (the library checks the
+    ranges the rule sets)."""
+    vals = dict(phred_base=phred_base, max_pos=max_pos, paired=1 if paired else 0)
+    for name, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s %r: must lie in 0..2^32-1" % (name, v))
+    return QcOpt(**{name: int(v) for name, v in vals.items()})
+
+
+def qc_shapes(max_pos: int, paired: bool) -> Dict[str, tuple]:
+    """The shapes of the five tables of Counter.fastq_qc (uint64 each) for ``max_pos`` = P and C = 2 classes with
+    ``paired``, else 1."""
+    c, p = (2 if paired else 1), int(max_pos)
+    return {"pos_qual": (c, p + 1, QC_QBINS), "pos_base": (c, p + 1, 8), "read_len": (c, p + 2), "read_qual": (c, QC_QBINS),
+            "read_gc": (c, QC_GC_BINS)}
 
 
 class AdaptOpt(C.Structure):
@@ -673,6 +717,9 @@ def lib() -> C.CDLL:
                                             C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqOverlap)]),
         "mk_fastq_overlap_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(OverlapOpt), C.c_size_t, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqOverlap)]),
+        "mk_fastq_qc_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.POINTER(QcOpt), C.c_size_t, C.POINTER(QcOut), szp,
+                                       C.POINTER(FastqQc)]),
+        "mk_fastq_qc_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(QcOpt), C.c_size_t, C.POINTER(QcOut), szp, C.POINTER(FastqQc)]),
         "mk_fq_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_fq_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
     }
@@ -1573,6 +1620,55 @@ class Counter:
         self._check_select(self._L.mk_fastq_qtrim_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), keep_ptr or None,
                                                          rows_ptr or None, hist_ptr or None, out_ptr or None, int(out_cap),
                                                          C.byref(out_len), C.byref(nrec), C.byref(st)))
+        return st.as_dict()
+
+    # -- per-cycle quality control of a FASTQ text (what MerCat2 asks fastqc for); no table is read
+    def fastq_qc(self, path_or_bytes, max_pos: int = 512, phred_base: int = 33, paired: bool = False, rows: bool = False,
+                 piece_bytes: int = 0, info: Optional[dict] = None) -> Dict[str, "np.ndarray"]:
+        """mk_fastq_qc_text: the quality-control tables of the FASTQ text (a path to a plain file, or the text itself as
+        bytes), uint64 arrays under their names: "pos_qual" (C, P + 1, 96): the bases of every quality value at every
+        cycle, row P = ``max_pos`` collecting the cycles from P on and bin 95 the values from 95 on; "pos_base" (C, P + 1,
+        8): the same for the base classes QC_BASES; "read_len" (C, P + 2): the reads of every length, the last bin those
+        longer than P; "read_qual" (C, 96): the reads by their mean quality, rounded down; "read_gc" (C, 101): the reads
+        by their GC share in percent, rounded half up.  ``paired``: records 2p and 2p + 1 are mates and C = 2 classes,
+        else C = 1.  ``rows``: also "rows", (records, 4) uint64, QC_COLUMNS.  MercatHipError: MK_ERR_UNSUPPORTED for a
+        malformed record (the message names it), MK_ERR_RANGE for an odd record count with ``paired``.  ``info``, if
+        given, receives the mk_fastq_qc_t fields."""
+        opt = qc_options(max_pos, phred_base, paired)
+        if not 1 <= opt.max_pos <= QC_MAX_POS:  # (before the tables are sized by it)
+            raise MercatHipError(-1, "mk_fastq_qc_text: max_pos must be 1 .. %d" % QC_MAX_POS)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        got = {name: np.zeros(shape, dtype=np.uint64) for name, shape in qc_shapes(opt.max_pos, bool(opt.paired)).items()}
+        cap = 0
+        if rows:
+            nl = int(np.count_nonzero(held == 10)) if size else 0
+            cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
+            got["rows"] = np.zeros((cap, 4), dtype=np.uint64)
+        out = QcOut(**{name: a.ctypes.data for name, a in got.items()})
+        nrec, st = C.c_size_t(0), FastqQc()
+        self._check_select(self._L.mk_fastq_qc_text(self._h, addr, size, int(piece_bytes), C.byref(opt), cap, C.byref(out),
+                                                    C.byref(nrec), C.byref(st)))
+        if rows:
+            got["rows"] = got["rows"][: nrec.value]
+        if info is not None:
+            info.update(st.as_dict())
+        return got
+
+    def fastq_qc_device(self, ptr: int, nbytes: int, pos_qual_ptr: int, pos_base_ptr: int, read_len_ptr: int, read_qual_ptr: int,
+                        read_gc_ptr: int, rows_ptr: int = 0, cap: int = 0, **options) -> dict:
+        """mk_fastq_qc_device: ``nbytes`` of FASTQ text at device address ``ptr`` -> the five tables of Counter.fastq_qc
+        at the device addresses given (uint64, the sizes of qc_shapes, zeroed by the call) and, where ``rows_ptr`` is
+        given, four uint64 a record there (room for ``cap`` records) -- all aligned to 8, all on this context's GPU.
+        ``options``: max_pos, phred_base, paired.  Returns the mk_fastq_qc_t fields."""
+        opt = qc_options(**options)
+        out = QcOut(pos_qual_ptr or None, pos_base_ptr or None, read_len_ptr or None, read_qual_ptr or None, read_gc_ptr or None,
+                    rows_ptr or None)
+        nrec, st = C.c_size_t(0), FastqQc()
+        self._check_select(self._L.mk_fastq_qc_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), C.byref(out), C.byref(nrec),
+                                                      C.byref(st)))
         return st.as_dict()
 
     # -- 3' adapter removal from the reads of a FASTQ text (the first job of the fastp run MerCat2 starts); no table is read

@@ -460,3 +460,114 @@ def write_overlap_summary(path, figures: Dict[str, int], fragments: Dict[int, in
     """``format_overlap_summary`` written to ``path``."""
     with open(path, "wb") as fh:
         fh.write(format_overlap_summary(figures, fragments))
+
+
+# ---- the quality-control tables of Counter.fastq_qc / kmers.qc_reads as TSVs: pure Python over the arrays.  ``mate``: 0 for
+# ---- a text read as one class, 1 and 2 for the mates of a paired one
+def _qc_mates(qc) -> list:
+    classes = len(qc["read_len"])
+    return [(c, c + 1 if classes == 2 else 0) for c in range(classes)]
+
+
+def qc_percentile(hist, x: int) -> int:
+    """The smallest value v with 100 * (hist[0] + .. + hist[v]) >= x * sum(hist); 0 for an empty histogram."""
+    total, cum = sum(int(n) for n in hist), 0
+    for v, n in enumerate(hist):
+        cum += int(n)
+        if total and 100 * cum >= x * total:
+            return v
+    return 0
+
+
+def qc_mean(hist) -> float:
+    """sum(v * hist[v]) / sum(hist); 0.0 for an empty histogram."""
+    total = sum(int(n) for n in hist)
+    return sum(v * int(n) for v, n in enumerate(hist)) / total if total else 0.0
+
+
+def format_qc_cycles(qc) -> bytes:
+    """``mate\tcycle\tbases\tmean\tp10\tq1\tmedian\tq3\tp90\tA\tC\tG\tT\tN\tother``, one line per mate and row of
+    pos_qual / pos_base that holds a base: the cycle counted from 1 (the row that collects the cycles behind max_pos = P
+    is written ``>P``), its bases, their mean quality with two decimals, the qualities at 10, 25, 50, 75 and 90 per cent
+    (qc_percentile) and the bases of each class."""
+    out = [b"mate\tcycle\tbases\tmean\tp10\tq1\tmedian\tq3\tp90\tA\tC\tG\tT\tN\tother\n"]
+    for c, mate in _qc_mates(qc):
+        P = len(qc["pos_qual"][c]) - 1
+        for p in range(P + 1):
+            hist = [int(n) for n in qc["pos_qual"][c][p]]
+            bases = sum(hist)
+            if not bases:
+                continue
+            cycle = b">%d" % P if p == P else b"%d" % (p + 1)
+            marks = tuple(qc_percentile(hist, x) for x in (10, 25, 50, 75, 90))
+            out.append(b"%d\t" % mate + cycle + b"\t%d\t%.2f" % (bases, qc_mean(hist)) + b"\t%d\t%d\t%d\t%d\t%d" % marks +
+                       b"\t%d\t%d\t%d\t%d\t%d\t%d\n" % tuple(int(n) for n in qc["pos_base"][c][p][:6]))
+    return b"".join(out)
+
+
+def format_qc_quality(qc) -> bytes:
+    """``mate\tmean_quality\treads``: the reads of every mean quality (rounded down) that occurs."""
+    out = [b"mate\tmean_quality\treads\n"]
+    for c, mate in _qc_mates(qc):
+        out += [b"%d\t%d\t%d\n" % (mate, m, int(n)) for m, n in enumerate(qc["read_qual"][c]) if int(n)]
+    return b"".join(out)
+
+
+def format_qc_gc(qc) -> bytes:
+    """``mate\tgc\treads``: the reads of every GC share in per cent (rounded half up), all 101 lines a mate."""
+    out = [b"mate\tgc\treads\n"]
+    for c, mate in _qc_mates(qc):
+        out += [b"%d\t%d\t%d\n" % (mate, g, int(n)) for g, n in enumerate(qc["read_gc"][c])]
+    return b"".join(out)
+
+
+def format_qc_length(qc) -> bytes:
+    """``mate\tlength\treads``: the reads of every length that occurs; the last bin, the reads longer than max_pos = P,
+    is written ``>P``."""
+    out = [b"mate\tlength\treads\n"]
+    for c, mate in _qc_mates(qc):
+        P = len(qc["read_len"][c]) - 2
+        for l, n in enumerate(qc["read_len"][c]):
+            if int(n):
+                out.append(b"%d\t" % mate + (b">%d" % P if l == P + 1 else b"%d" % l) + b"\t%d\n" % int(n))
+    return b"".join(out)
+
+
+def format_qc_summary(qc) -> bytes:
+    """``metric`` and a column a mate (``all`` for a text read as one class, else ``mate1`` and ``mate2``): reads, bases,
+    empty_reads, min_length, mean_length (two decimals), max_length (a length behind max_pos = P is written ``>P``),
+    gc_percent (two decimals, of all bases), n_bases, q20_bases, q30_bases, mean_quality (two decimals)."""
+    mates = _qc_mates(qc)
+    cols = []
+    for c, _ in mates:
+        lens = [int(n) for n in qc["read_len"][c]]
+        P = len(lens) - 2
+        name = lambda l: b">%d" % P if l == P + 1 else b"%d" % l
+        seen = [l for l, n in enumerate(lens) if n]
+        quals = [sum(int(row[v]) for row in qc["pos_qual"][c]) for v in range(len(qc["pos_qual"][c][0]))]
+        kinds = [sum(int(row[k]) for row in qc["pos_base"][c]) for k in range(6)]
+        reads, bases = sum(lens), sum(quals)
+        cols.append([b"%d" % reads, b"%d" % bases, b"%d" % lens[0], name(seen[0]) if seen else b"0",
+                     b"%.2f" % (bases / reads if reads else 0.0), name(seen[-1]) if seen else b"0",
+                     b"%.2f" % (100.0 * (kinds[1] + kinds[2]) / bases if bases else 0.0), b"%d" % kinds[4],
+                     b"%d" % sum(quals[20:]), b"%d" % sum(quals[30:]), b"%.2f" % qc_mean(quals)])
+    out = [b"metric\t" + (b"all" if len(mates) == 1 else b"mate1\tmate2") + b"\n"]
+    for i, metric in enumerate((b"reads", b"bases", b"empty_reads", b"min_length", b"mean_length", b"max_length", b"gc_percent",
+                                b"n_bases", b"q20_bases", b"q30_bases", b"mean_quality")):
+        out.append(metric + b"".join(b"\t" + col[i] for col in cols) + b"\n")
+    return b"".join(out)
+
+
+QC_FILES = {"cycles": format_qc_cycles, "quality": format_qc_quality, "gc": format_qc_gc, "length": format_qc_length,
+            "summary": format_qc_summary}
+
+
+def write_qc_files(prefix, qc) -> list:
+    """``<prefix>_cycles.tsv``, ``_quality.tsv``, ``_gc.tsv``, ``_length.tsv`` and ``_summary.tsv`` of the tables of
+    Counter.fastq_qc; returns the paths."""
+    paths = []
+    for name, fmt in QC_FILES.items():
+        paths.append("%s_%s.tsv" % (prefix, name))
+        with open(paths[-1], "wb") as fh:
+            fh.write(fmt(qc))
+    return paths
