@@ -1085,6 +1085,58 @@ int mk_fastq_qc_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_b
 int mk_fastq_qc_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const mk_qc_opt_t* opt, size_t cap, const mk_qc_out_t* d_out,
                        size_t* nrec, mk_fastq_qc_t* st);
 
+/* ---- duplicate reads of a FASTQ text: what fastp --dedup, clumpify dedupe and seqkit rmdup -s remove and fastqc's
+ *      duplication levels report, here as a stated rule -- reads (or pairs) whose key BYTES are equal form a cluster, the
+ *      one of lowest index stays -- found, decided and gathered on the GPU.  Exact: a hash only chooses where to look ----
+ * Lines, records, the tolerated trailing empty lines, the one trailing '\r' taken off the sequence and quality lines and
+ * the checks with their messages are mk_fastq_qtrim_*'s without kind 5 (qualities are never interpreted): '@', '+', equal
+ * lengths, a text that ends inside a record.  The lowest record wins, then the lowest kind; all are MK_ERR_UNSUPPORTED.
+ * The tables are not read; an open chunk is MK_ERR_STATE.
+ * Key of a read of L bases: the bytes seq[0 : L] with prefix = 0, else seq[0 : min(L, prefix)], as they stand ('a' is not
+ * 'A', 'N' is a byte like any other, no reverse complement).  An empty read has the empty key.
+ * Unit: unpaired the record, its key the read's; paired the pair (2p, 2p + 1), its key the ordered pair of the mates' keys
+ * (equal iff both first mates and both second mates are equal, lengths included; an odd record count is MK_ERR_RANGE).
+ * Units with equal keys form a cluster; its first is the unit of lowest index over the whole call, its copies its size.
+ * rows[r] = {L, first}: first = the record that plays r's part in the first unit of r's cluster (r itself for a first
+ * occurrence; paired 2p' + (r & 1)).  keep[r] = 1 iff first == r, else 0.  Record r is emitted iff keep[r] == 1 with
+ * which = 1 (the uniques) or keep[r] == 0 with which = 2 (the duplicates); any other which is MK_ERR_ARG.
+ * Output, in text order: the emitted records whole, byte for byte (a forced '\n' where the text ends without one).
+ * levels[high + 2], zeroed by the call: levels[i] = clusters of i copies for 1 <= i <= high, levels[high + 1] = those of
+ * more, levels[0] = 0.  high in 1 .. MK_DEDUP_MAX_HIGH (else MK_ERR_ARG).
+ * cap, *nrec, the sizing call (out = NULL, out_cap = 0), MK_ERR_RANGE with the needed size in *out_len, *out_len <= n + 1:
+ * mk_fastq_qtrim_*'s.  keep, rows and levels may each be NULL.
+ * mk_fastq_dedup_text: host memory, piece by piece (with paired a piece ends behind an even record); the text of all pieces
+ * stays on the device for the length of the call (a copy in the last piece may equal a read of the first), so the call
+ * needs about n bytes and 64 to 112 more a record of device memory; a failed allocation is MK_ERR_NOMEM and the message
+ * gives the bytes.  Nothing depends on piece_bytes, on scheduling or on the hash function: two runs give identical bytes.
+ * mk_fastq_dedup_device: everything in DEVICE memory of the context's GPU, one piece of at most 2^32 - 1 bytes (more:
+ * MK_ERR_RANGE, before anything is read); text and out at any address, d_rows and d_levels aligned to 8 (MK_ERR_ARG
+ * otherwise).  The text is never written. */
+#define MK_DEDUP_MAX_HIGH (1u << 20)
+typedef struct mk_dedup_opt_t {
+  uint32_t prefix; /* 0: whole reads; else the first `prefix` bases are the key */
+  uint32_t paired; /* 0 or 1                                                    */
+  uint32_t which;  /* 1: emit the uniques; 2: emit the duplicates               */
+  uint32_t high;   /* 1 .. MK_DEDUP_MAX_HIGH                                    */
+} mk_dedup_opt_t;
+typedef struct mk_fastq_dedup_t {
+  uint64_t records, records_out;  /* of the text; emitted                                                              */
+  uint64_t distinct, duplicates;  /* clusters (pairs with paired); records with keep[r] == 0                           */
+  uint64_t max_copies, slots;     /* the largest cluster, in units; slots of the call's table                          */
+  uint64_t probes, compares;      /* diagnostics: probe steps beyond the first; key bytes compared                     */
+  uint64_t bases_in, bases_out, bytes_out, lines; /* sequence bytes of the text; emitted; output bytes; lines          */
+  /* seconds: host time counting lines and sizing the call's state; host time in the copies to the device; HIP-event time
+   * of the line index; of keys and inserts together, and of each; of the decision and its prefix sum; of the gather; of
+   * the pass over the table; host time in the copies back */
+  double s_plan, s_copy, s_index, s_scan, s_key, s_insert, s_place, s_gather, s_levels, s_write;
+} mk_fastq_dedup_t;
+int mk_fastq_dedup_text(mk_ctx* ctx, const uint8_t* fastq, size_t n, size_t piece_bytes, const mk_dedup_opt_t* opt, size_t cap,
+                        uint8_t* keep, uint64_t* rows, uint64_t* levels, uint8_t* out, size_t out_cap, size_t* out_len, size_t* nrec,
+                        mk_fastq_dedup_t* st);
+int mk_fastq_dedup_device(mk_ctx* ctx, const uint8_t* d_fastq, size_t n, const mk_dedup_opt_t* opt, size_t cap, uint8_t* d_keep,
+                          uint64_t* d_rows, uint64_t* d_levels, uint8_t* d_out, size_t out_cap, size_t* out_len, size_t* nrec,
+                          mk_fastq_dedup_t* st);
+
 /* ---- several samples side by side: merge_tsv (lib/mercat2_report.py:98-156) from the tables --- */
 /* The combined table of n samples (contexts with the same k; each on its own GPU or all on one):
  * every k-mer present in any of them, in sorted(str) order, with its count in each sample (0 where

@@ -70,8 +70,16 @@ else, cycles from MAXPOS on in one row; per read its length, mean quality and GC
 qc/<sample>_raw_cycles.tsv (bases, mean, percentiles and composition a cycle), _quality.tsv, _gc.tsv, _length.tsv and
 _summary.tsv, and as qc/<sample>_clean_*.tsv from what the count sees where -overlap, -adapt or -qtrim ran.  -qc_paired or
 -overlap gives every figure per mate (the clean stage only while mates still alternate: not after -overlap merge, -adapt or
--qtrim); -qc_phred sets the offset.  The figures are that stated rule's, not fastqc's: duplication levels,
-over-represented sequences, adapter and k-mer content, position grouping and verdicts stay out.  QC plots, ORF calling
+-qtrim); -qc_phred sets the offset.  The figures are that stated rule's, not fastqc's: adapter and k-mer content, position
+grouping and verdicts stay out.  -dedup takes FASTQ input with or without -skipclean and removes duplicate reads on the GPU
+first of all, before -overlap, -adapt and -qtrim (trimming makes copies of one fragment differ in length): reads whose
+sequence bytes are equal -- with -dedup_prefix N their first N bases -- form a cluster and the first of it stays
+(mk_fastq_dedup_text: exact, case and N as they stand, no reverse complement; a hash only chooses where to look); with
+-dedup_paired, or whenever -overlap is given, the unit is the pair and both mates must be equal (-overlap_mate FILE2 is then
+interleaved once in front of -dedup).  dedup/<sample>_dedup.fastq holds what the later steps and the count see,
+dedup/<sample>_dedup.tsv every read's length, first, copies and keep value, _levels.tsv the clusters of 1 .. -dedup_high
+copies and of more (fastqc's duplication levels), _summary.tsv the duplication rate, _overrepresented.tsv the clusters that
+hold at least -dedup_over of the reads (at most 1000).  With -qc the raw stage is the text in front of -dedup.  QC plots, ORF calling
 (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
@@ -311,6 +319,17 @@ def parseargs(argv=None):
                         "from the reads the count sees")
     p.add_argument("-qc_phred", type=int, default=None, choices=(33, 64), help="-qc: the offset of the quality characters [33]")
     p.add_argument("-qc_paired", action="store_true", help="-qc: the FASTQ inputs are interleaved pairs: every figure per mate")
+    p.add_argument("-dedup", action="store_true",
+                   help="FASTQ input, with or without -skipclean: remove duplicate reads on the GPU before -overlap, -adapt, -qtrim "
+                        "and the count see them -- reads whose sequence bytes are equal form a cluster and the first stays (a "
+                        "stated rule: exact, case and N as they stand, no reverse complement). Writes dedup/<sample>_dedup.fastq, "
+                        "_dedup.tsv, _levels.tsv, _summary.tsv and _overrepresented.tsv")
+    p.add_argument("-dedup_prefix", type=int, default=None, metavar="N", help="-dedup: compare only the first N bases of a read [0: whole reads]")
+    p.add_argument("-dedup_paired", action="store_true",
+                   help="-dedup: the FASTQ inputs are interleaved pairs and a pair is a duplicate iff both mates are (implied by -overlap)")
+    p.add_argument("-dedup_high", type=int, default=None, metavar="N", help="-dedup: the duplication levels written one by one [100]")
+    p.add_argument("-dedup_over", type=float, default=None, metavar="F",
+                   help="-dedup: a sequence is over-represented from this fraction (0..1) of the reads on [0.001]")
     p.add_argument("-gpu", type=int, default=None, help="use exactly this one HIP device (overrides -gpus)")
     p.add_argument("-streams", type=int, default=None,
                    help="engine contexts counting chunks concurrently [2 for one-word keys, else 1]")
@@ -353,6 +372,24 @@ def parseargs(argv=None):
             p.error(f"-qtrim_low_frac {args.qtrim_low_frac}: must lie in 0..1")
         if args.qtrim_low_frac is not None and not args.qtrim_low:
             p.error("-qtrim_low_frac needs -qtrim_low Q: no base is low without it")
+    if not args.dedup:
+        for flag in ("dedup_prefix", "dedup_high", "dedup_over"):
+            if getattr(args, flag) is not None:
+                p.error(f"-{flag} needs -dedup")
+        if args.dedup_paired:
+            p.error("-dedup_paired needs -dedup")
+    else:
+        given = list(args.i)
+        if args.f and os.path.isdir(args.f):
+            given += sorted(os.listdir(args.f))
+        if not any(fastq_ext(Path(name)) for name in given):
+            p.error(f"-dedup removes duplicate FASTQ reads ({' / '.join(FILE_EXT_FASTQ)}); no input is a FASTQ file")
+        if args.dedup_prefix is not None and not 0 <= args.dedup_prefix < 1 << 32:
+            p.error(f"-dedup_prefix {args.dedup_prefix}: must lie in 0..2^32 - 1")
+        if args.dedup_high is not None and not 1 <= args.dedup_high <= 1 << 20:
+            p.error(f"-dedup_high {args.dedup_high}: must lie in 1..{1 << 20}")
+        if args.dedup_over is not None and not 0.0 <= args.dedup_over <= 1.0:
+            p.error(f"-dedup_over {args.dedup_over}: must lie in 0..1")
     if args.qc is None:
         if args.qc_phred is not None:
             p.error("-qc_phred needs -qc")
@@ -719,12 +756,13 @@ def adapt_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes
     return done["text"]
 
 
-def overlap_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
+def overlap_sample(args, f: Path, raw, out: Path, base: str, device: int, interleaved: bool = False) -> bytes:
     """-overlap: the pairs of FASTQ sample ``base`` (``raw``: its bytes if they are in memory already, else None and ``f``
     is read; interleaved, or the first mates with -overlap_mate) trimmed or merged by the overlap of their mates on GPU
     ``device`` by kmers.overlap_reads, which writes overlap/<base>_overlap.fastq (trim) or _merged.fastq and
     _unmerged.fastq (merge), _overlap.tsv and _summary.tsv; returns the text that -adapt, -qtrim and the count see in the
-    raw reads' place: the trimmed pairs, or the merged reads followed by the unmerged pairs."""
+    raw reads' place: the trimmed pairs, or the merged reads followed by the unmerged pairs.  ``interleaved``: ``raw`` holds
+    both files of -overlap_mate already."""
     from . import kmers, native
     folder = out / "overlap"
     folder.mkdir(parents=True, exist_ok=True)
@@ -733,12 +771,36 @@ def overlap_sample(args, f: Path, raw, out: Path, base: str, device: int) -> byt
         done = kmers.overlap_reads(
             f if raw is None else raw, folder / (f"{base}_merged.fastq" if merging else f"{base}_overlap.fastq"), mode=args.overlap,
             min_overlap=30 if args.overlap_min is None else args.overlap_min, max_mismatch=5 if args.overlap_diff is None else args.overlap_diff,
-            max_err=0.2 if args.overlap_err is None else args.overlap_err, min_len=args.overlap_len or 0, mate_file=args.overlap_mate,
+            max_err=0.2 if args.overlap_err is None else args.overlap_err, min_len=args.overlap_len or 0,
+            mate_file=None if interleaved else args.overlap_mate,
             unmerged_path=folder / f"{base}_unmerged.fastq" if merging else None, tsv_path=folder / f"{base}_overlap.tsv",
             summary_path=folder / f"{base}_summary.tsv", device=device, keep_text=True)
     except (native.MercatHipError, ValueError) as e:
         raise SystemExit(f"-overlap '{f.name}': {e}")
     return done["text"] + done["unmerged"] if merging else done["text"]
+
+
+def dedup_sample(args, f: Path, raw, out: Path, base: str, paired: bool, device: int, timings=None) -> bytes:
+    """-dedup: the reads of FASTQ sample ``base`` (``raw``: its bytes if they are in memory already, else None and ``f``
+    is read; with ``paired`` interleaved pairs) without their duplicates, found on GPU ``device`` by kmers.dedup_reads,
+    which writes dedup/<base>_dedup.fastq, _dedup.tsv, _levels.tsv, _summary.tsv and _overrepresented.tsv; returns the
+    text that is left, which the later steps and the count see in the raw reads' place.  ``timings``, if given, has the
+    seconds added to its "dedup_s"."""
+    from . import kmers, native
+    folder = out / "dedup"
+    folder.mkdir(parents=True, exist_ok=True)
+    t0 = timeit.default_timer()
+    try:
+        done = kmers.dedup_reads(
+            f if raw is None else raw, folder / f"{base}_dedup.fastq", prefix=args.dedup_prefix or 0, paired=paired,
+            high=100 if args.dedup_high is None else args.dedup_high, over_frac=0.001 if args.dedup_over is None else args.dedup_over,
+            tsv_path=folder / f"{base}_dedup.tsv", summary_path=folder / f"{base}_summary.tsv",
+            levels_path=folder / f"{base}_levels.tsv", over_path=folder / f"{base}_overrepresented.tsv", device=device, keep_text=True)
+    except native.MercatHipError as e:
+        raise SystemExit(f"-dedup '{f.name}': {e}")
+    if timings is not None:
+        timings["dedup_s"] = timings.get("dedup_s", 0.0) + timeit.default_timer() - t0
+    return done["text"]
 
 
 def qc_sample(args, f: Path, text: bytes, out: Path, base: str, stage: str, paired: bool, device: int, timings=None) -> None:
@@ -759,32 +821,42 @@ def qc_sample(args, f: Path, text: bytes, out: Path, base: str, stage: str, pair
 
 
 def prepared_reads(args, f: Path, raw, out: Path, base: str, device: int, timings=None) -> bytes:
-    """The reads of FASTQ sample ``base`` as the count sees them: through -overlap, then -adapt, then -qtrim, where
-    given.  With -qc the two places where MerCat2 runs fastqc: the text as read (with -overlap_mate both files,
-    interleaved), and, where one of those steps ran, what it left.  The raw stage is per mate with -qc_paired or
-    -overlap; the clean stage too, unless mates no longer alternate in it: after -overlap merge, and after -adapt or
-    -qtrim, which judge every read on its own."""
+    """The reads of FASTQ sample ``base`` as the count sees them: through -dedup, then -overlap, then -adapt, then
+    -qtrim, where given (duplicates are looked for in the reads as sequenced: trimming makes copies of one fragment
+    differ in length).  -dedup takes pairs with -dedup_paired or -overlap; with -overlap_mate both files are interleaved
+    once, on the host, in front of it, and -overlap then gets that text.  With -qc the two places where MerCat2 runs
+    fastqc: the text as read (with -overlap_mate both files, interleaved), and, where one of those steps ran, what it
+    left.  The raw stage is per mate with -qc_paired or -overlap; the clean stage too, unless mates no longer alternate in
+    it: after -overlap merge, and after -adapt or -qtrim, which judge every read on its own, and after a -dedup of single reads (one of pairs drops whole pairs)."""
     qc = args.qc is not None
-    steps = args.overlap is not None or args.adapt is not None or args.qtrim is not None
+    steps = args.dedup or args.overlap is not None or args.adapt is not None or args.qtrim is not None
     paired = qc and (args.qc_paired or args.overlap is not None)
+    interleaved = False
+    if args.dedup and args.overlap is not None and args.overlap_mate is not None:
+        from . import native
+        raw = native.interleave_fastq(read_fasta_bytes(f) if raw is None else raw, read_fasta_bytes(args.overlap_mate))
+        interleaved = True
     if qc:
         raw = read_fasta_bytes(f) if raw is None else raw
         text = raw
-        if args.overlap is not None and args.overlap_mate is not None:
+        if args.overlap is not None and args.overlap_mate is not None and not interleaved:
             from . import native
             text = native.interleave_fastq(raw, read_fasta_bytes(args.overlap_mate))
         qc_sample(args, f, text, out, base, "raw", paired, device, timings)
         del text
+    if args.dedup:
+        raw = dedup_sample(args, f, raw, out, base, args.dedup_paired or args.overlap is not None, device, timings)
     if args.overlap is not None:
-        raw = overlap_sample(args, f, raw, out, base, device)
+        raw = overlap_sample(args, f, raw, out, base, device, interleaved)
     if args.adapt is not None:
         raw = adapt_sample(args, f, raw, out, base, device)
     if args.qtrim is not None:
         raw = qtrim_sample(args, f, raw, out, base, device)
     raw = read_fasta_bytes(f) if raw is None else raw
     if qc and steps:
-        qc_sample(args, f, raw, out, base, "clean", paired and args.overlap != "merge" and args.adapt is None and args.qtrim is None,
-                  device, timings)
+        alternate = args.overlap != "merge" and args.adapt is None and args.qtrim is None and (
+            not args.dedup or args.dedup_paired or args.overlap is not None)  # (-dedup of single reads drops single reads)
+        qc_sample(args, f, raw, out, base, "clean", paired and alternate, device, timings)
     return raw
 
 
@@ -870,7 +942,7 @@ def main(argv=None) -> int:
     fastq = set()  # nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)
     for f in files:
         kind, base = classify(f.expanduser().absolute(),
-                              args.skipclean or args.qtrim is not None or args.adapt is not None or args.overlap is not None)
+                              args.skipclean or args.dedup or args.qtrim is not None or args.adapt is not None or args.overlap is not None)
         if kind:
             samples[kind][base] = f
             if fastq_ext(f):
@@ -912,11 +984,11 @@ def main(argv=None) -> int:
             raw = read_fasta_bytes(f)
             t["read_s"] = timeit.default_timer() - t0
             steps = args.qtrim is not None or args.adapt is not None or args.overlap is not None
-            if base in fastq and (steps or args.qc is not None):
+            if base in fastq and (steps or args.dedup or args.qc is not None):
                 t0 = timeit.default_timer()
                 raw = prepared_reads(args, f, raw, out, base, home_of[base], timings=t)
                 if steps:
-                    t["qtrim_s"] = timeit.default_timer() - t0 - t.get("qc_s", 0.0)
+                    t["qtrim_s"] = timeit.default_timer() - t0 - t.get("qc_s", 0.0) - t.get("dedup_s", 0.0)
             if base in fastq:
                 path, fut, holder = fq2fa_background(f, raw, out / "clean", base, gz_writers, timings=t, limit=args.s * 1024 * 1024)
             else:

@@ -8,7 +8,8 @@
 // A policy P names what differs:
 //   Opt, Status (device counters behind the FsStatus of a piece), Stats (the call's mk_fastq_*_t), Side (what the scan
 //   kernel reads or writes beside the text), ROW (uint64 a row),
-//   paired(o), kind(k) (the phrase of a failed check), scan(...), decide(...), add(stats, status).
+//   paired(o), kind(k) (the phrase of a failed check), scan(...), decide(...), add(stats, status); optionally ready(...)
+//   (what a piece sets up once its records are counted: mk_dedup.hip's table).
 #pragma once
 #include "mk_fqindex.h"
 
@@ -104,6 +105,15 @@ struct FqCall {
   bool counting_only() const { return bad_rc != MK_OK || records > limit; }
 };
 
+// P::ready(f, d_text, n, nrec), where a policy has one: what it sets up once a piece's record count is known and before
+// its kernels run (records f.records - nrec .. f.records - 1); an error ends the call.  A policy without one is not asked.
+template <class P>
+static auto fq_ready(FqCall<P>& f, const uint8_t* d_text, size_t n, size_t nrec, int) -> decltype(P::ready(f, d_text, n, nrec)) {
+  return P::ready(f, d_text, n, nrec);
+}
+template <class P>
+static int fq_ready(FqCall<P>&, const uint8_t*, size_t, size_t, long) { return MK_OK; }
+
 // One piece of n > 0 bytes at d_text (device memory, 16-byte aligned, whole records -- whole pairs with paired -- but for
 // what trails in the last piece).  Its records are added to f.records either way.  The stream is idle afterwards.
 template <class P>
@@ -151,6 +161,7 @@ static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
     return MK_OK;
   };
   if (!nrec) return trail_ok ? MK_OK : fail_trailing();
+  if ((rc = fq_ready(f, d_text, n, nrec, 0)) != MK_OK) return rc;
 
   // meta: line[4 nrec + 1] | seg_src[nseg + 1] | len[nseg + 1] | dst[nseg + 1] | rows[ROW nrec] | verdict[nrec] | keep[nrec]
   const size_t nseg = 4 * nrec, nidx = 4 * nrec;

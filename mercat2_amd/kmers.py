@@ -643,6 +643,83 @@ def qc_reads(file: Union[str, Path, bytes], out_prefix: Union[str, Path, None] =
     return done
 
 
+def fastq_keys(raw: bytes, prefix: int = 0) -> List[bytes]:
+    """The keys of a FASTQ text's 4-line records as Counter.fastq_dedup compares them: line 4r + 1 without one trailing
+    '\\r', cut to ``prefix`` bytes where that is not 0."""
+    lines = raw.count(b"\n") + (1 if raw and not raw.endswith(b"\n") else 0)
+    seqs = raw.split(b"\n")[1::4][: lines // 4]
+    seqs = [s[:-1] if s.endswith(b"\r") else s for s in seqs]
+    return [s[:prefix] for s in seqs] if prefix else seqs
+
+
+def dedup_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None], prefix: int = 0, paired: bool = False,
+                keep: str = "unique", high: int = 100, over_frac: float = 0.001, tsv_path: Union[str, Path, None] = None,
+                summary_path: Union[str, Path, None] = None, levels_path: Union[str, Path, None] = None,
+                over_path: Union[str, Path, None] = None, mate_file: Union[str, Path, None] = None,
+                out_path2: Union[str, Path, None] = None, device: int = 0, keep_text: bool = False) -> Dict[str, object]:
+    """The reads of a FASTQ file ('.fq' / '.fastq', plain or '.gz'; or the FASTQ text itself as bytes, for a caller that
+    holds it already) without their duplicates, found on the GPU (Counter.fastq_dedup has the rule: reads whose sequence
+    bytes -- with ``prefix`` their first ``prefix`` bases -- are equal form a cluster, and its first record over the
+    whole text stays), written as FASTQ to ``out_path`` -- gzip (level 1) if that name ends in '.gz'.  ``keep``:
+    "unique" writes the first of every cluster, "duplicate" the records a run removes.  This stands where fastp --dedup
+    or clumpify dedupe would; it is exact (no hash decides), case and N count as they stand, no reverse complement is
+    tried.  No table is read: the call opens a small context of its own on ``device``.
+    Paired reads (``paired``: the file is interleaved; or ``mate_file``: the second file, interleaved with the first on
+    the host by native.interleave_fastq): the unit is the pair, equal iff both mates are; the output is interleaved to
+    ``out_path`` or split into ``out_path`` and ``out_path2``.  ``tsv_path``: every record's name, length, first, copies
+    and keep value (report.write_dedup_tsv); ``levels_path``: the duplication levels; ``summary_path``: units, distinct,
+    duplicates, rate, largest cluster, bases before and after; ``over_path``: the clusters that hold at least
+    ``over_frac`` of the units (and two of them), by copies descending, then first ascending, at most 1000, with the
+    sequence read from the text at their first record -- host work on a handful of rows.  Returns the mk_fastq_dedup_t
+    figures, "levels", "over" and, with ``keep_text``, the output under "text" (interleaved for pairs)."""
+    if keep not in ("unique", "duplicate"):
+        raise ValueError("dedup_reads: keep must be 'unique' or 'duplicate', not %r" % (keep,))
+    is_paired = _is_paired(paired, mate_file, out_path2, None)
+    is_text = isinstance(file, (bytes, bytearray, memoryview))
+    for f in (None if is_text else file, mate_file):
+        if f is not None and not str(f).lower().endswith(FASTQ_SUFFIXES):
+            raise ValueError("dedup_reads: needs FASTQ input (%s), not %s" % (" / ".join(FASTQ_SUFFIXES), f))
+    raw = bytes(file) if is_text else read_fasta_bytes(file)
+    if mate_file is not None:
+        raw = native.interleave_fastq(raw, read_fasta_bytes(mate_file))
+    np = native.np
+    info: Dict[str, object] = {}
+    with native.Counter(5, native.ALPHABET_NT2, device=device) as ctx:
+        out, kept, rows, levels = ctx.fastq_dedup(raw, prefix=prefix, paired=is_paired, which=1, high=high, info=info)
+        if keep == "duplicate":
+            out = ctx.fastq_dedup(raw, prefix=prefix, paired=is_paired, which=2, high=high)[0]
+    if out_path is not None:
+        if out_path2 is None:
+            _write_reads(out_path, out)
+        else:
+            first, second = native.split_pairs_fastq(out)
+            _write_reads(out_path, first)
+            _write_reads(out_path2, second)
+    # cluster sizes per record: one integer a record, which left the GPU anyway
+    step = 2 if is_paired else 1
+    units = len(rows) // step
+    first = rows[:, 1].astype(np.int64)
+    unit_first = first[::step] // step
+    copies = np.repeat(np.bincount(unit_first, minlength=max(units, 1))[unit_first], step) if units else np.zeros(0, np.int64)
+    from . import report
+    over = report.dedup_over(copies, rows, is_paired, over_frac)
+    names = fastq_names(raw) if tsv_path is not None or over_path is not None else None
+    if tsv_path is not None:
+        report.write_dedup_tsv(tsv_path, names, rows, kept, copies)
+    if levels_path is not None:
+        report.write_dedup_levels(levels_path, levels, units)
+    if summary_path is not None:
+        report.write_dedup_summary(summary_path, info, is_paired)
+    if over_path is not None:
+        report.write_dedup_over(over_path, over, names, fastq_keys(raw, prefix), units, is_paired)
+    done: Dict[str, object] = {name: value for name, value in info.items() if not name.startswith("s_")}
+    done["levels"] = levels
+    done["over"] = over
+    if keep_text:
+        done["text"] = out
+    return done
+
+
 def _named_adapters(adapters) -> Tuple[List[str], List[str]]:
     """(names, seqs) of ``adapters``: None (native.ILLUMINA_ADAPTERS), a FASTA file (native.read_adapters), (name, seq)
     pairs, or plain sequences, which are named by themselves."""

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "mk_adapters_pack", "mk_fastq_adapt_text", "mk_fastq_adapt_device",
     "mk_fastq_overlap_text", "mk_fastq_overlap_device",
     "mk_fastq_qc_text", "mk_fastq_qc_device",
+    "mk_fastq_dedup_text", "mk_fastq_dedup_device",
 ]
 MK_ABI = 6  # the number mk_version() must announce: struct layouts and signatures of include/mercat_hip.h as bound below
 MERGE_RANGES, MERGE_GATHER, MERGE_BALANCED, MERGE_RCCL = 0, 1, 2, 4
@@ -363,6 +364,36 @@ def qc_shapes(max_pos: int, paired: bool) -> Dict[str, tuple]:
     c, p = (2 if paired else 1), int(max_pos)
     return {"pos_qual": (c, p + 1, QC_QBINS), "pos_base": (c, p + 1, 8), "read_len": (c, p + 2), "read_qual": (c, QC_QBINS),
             "read_gc": (c, QC_GC_BINS)}
+
+
+DEDUP_MAX_HIGH = 1 << 20  # MK_DEDUP_MAX_HIGH
+DEDUP_COLUMNS = ("length", "first")  # the columns of Counter.fastq_dedup's rows
+
+
+class DedupOpt(C.Structure):
+    """mk_dedup_opt_t (include/mercat_hip.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("prefix", "paired", "which", "high")]
+
+
+class FastqDedup(C.Structure):
+    """mk_fastq_dedup_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("records", "records_out", "distinct", "duplicates", "max_copies", "slots", "probes",
+                                           "compares", "bases_in", "bases_out", "bytes_out", "lines")] +
+                [(n, C.c_double) for n in ("s_plan", "s_copy", "s_index", "s_scan", "s_key", "s_insert", "s_place", "s_gather",
+                                           "s_levels", "s_write")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def dedup_options(prefix: int = 0, paired: bool = False, which: int = 1, high: int = 100) -> "DedupOpt":
+    """mk_dedup_opt_t of Counter.fastq_dedup's arguments; ValueError for one that no uint32 holds (the library checks the
+    ranges the rule sets)."""
+    vals = dict(prefix=prefix, paired=1 if paired else 0, which=which, high=high)
+    for name, v in vals.items():
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s %r: must lie in 0..2^32-1" % (name, v))
+    return DedupOpt(**{name: int(v) for name, v in vals.items()})
 
 
 class AdaptOpt(C.Structure):
@@ -720,6 +751,10 @@ def lib() -> C.CDLL:
         "mk_fastq_qc_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.POINTER(QcOpt), C.c_size_t, C.POINTER(QcOut), szp,
                                        C.POINTER(FastqQc)]),
         "mk_fastq_qc_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(QcOpt), C.c_size_t, C.POINTER(QcOut), szp, C.POINTER(FastqQc)]),
+        "mk_fastq_dedup_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.POINTER(DedupOpt), C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqDedup)]),
+        "mk_fastq_dedup_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(DedupOpt), C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, szp, szp, C.POINTER(FastqDedup)]),
         "mk_fq_interleave": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, szp]),
         "mk_fq_split_pairs": (C.c_int, [u8p, C.c_size_t, C.c_void_p, C.c_size_t, szp, C.c_void_p, C.c_size_t, szp, szp]),
     }
@@ -1669,6 +1704,51 @@ class Counter:
         nrec, st = C.c_size_t(0), FastqQc()
         self._check_select(self._L.mk_fastq_qc_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), C.byref(out), C.byref(nrec),
                                                       C.byref(st)))
+        return st.as_dict()
+
+    # -- duplicate reads of a FASTQ text (fastp --dedup, fastqc's duplication levels); no table is read
+    def fastq_dedup(self, path_or_bytes, prefix: int = 0, paired: bool = False, which: int = 1, high: int = 100, piece_bytes: int = 0,
+                    info: Optional[dict] = None):
+        """mk_fastq_dedup_text: (out, keep, rows, levels) of the FASTQ text (a path to a plain file, or the text itself as
+        bytes).  Reads whose sequence bytes are equal (``prefix`` > 0: whose first ``prefix`` bases are) form a cluster;
+        ``paired``: records 2p and 2p + 1 are mates and pairs equal in both mates do.  The first of a cluster, over the
+        whole text, is kept.  ``out``: the kept records (``which`` = 2: the others) as FASTQ bytes, whole; ``keep``:
+        uint8 a record; ``rows``: (records, 2) uint64, DEDUP_COLUMNS: the length and the record that stands for this one;
+        ``levels``: (high + 2,) uint64: the clusters of i copies, the last those of more than ``high``.  MercatHipError:
+        MK_ERR_UNSUPPORTED for a malformed record (the message names it), MK_ERR_RANGE for an odd record count with
+        ``paired``.  ``info``, if given, receives the mk_fastq_dedup_t fields."""
+        opt = dedup_options(prefix, paired, which, high)
+        if not 1 <= opt.high <= DEDUP_MAX_HIGH:  # (before levels is sized by it)
+            raise MercatHipError(-1, "mk_fastq_dedup_text: high must lie in 1 .. 2^20")
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        nl = int(np.count_nonzero(held == 10)) if size else 0
+        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
+        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        keep, rows = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 2), dtype=np.uint64)
+        levels = np.zeros(opt.high + 2, dtype=np.uint64)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqDedup()
+        self._check_select(self._L.mk_fastq_dedup_text(
+            self._h, addr, size, int(piece_bytes), C.byref(opt), cap, keep.ctypes.data, rows.ctypes.data, levels.ctypes.data,
+            out.ctypes.data, size + 1, C.byref(out_len), C.byref(nrec), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), keep[: nrec.value], rows[: nrec.value], levels
+
+    def fastq_dedup_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, cap: int = 0, keep_ptr: int = 0, rows_ptr: int = 0,
+                           levels_ptr: int = 0, **options) -> dict:
+        """mk_fastq_dedup_device: ``nbytes`` of FASTQ text at device address ``ptr`` -> the emitted records at device
+        address ``out_ptr`` (room for ``out_cap``; ``nbytes`` + 1 always suffice) and, where given, one keep byte a
+        record at ``keep_ptr``, two uint64 a record at ``rows_ptr`` (room for ``cap`` records each) and high + 2 uint64
+        at ``levels_ptr`` (both aligned to 8) -- all on this context's GPU.  ``options``: prefix, paired, which, high.
+        Returns the mk_fastq_dedup_t fields: "bytes_out" bytes were written, "records" rows."""
+        opt = dedup_options(**options)
+        out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqDedup()
+        self._check_select(self._L.mk_fastq_dedup_device(self._h, ptr, int(nbytes), C.byref(opt), int(cap), keep_ptr or None,
+                                                         rows_ptr or None, levels_ptr or None, out_ptr or None, int(out_cap),
+                                                         C.byref(out_len), C.byref(nrec), C.byref(st)))
         return st.as_dict()
 
     # -- 3' adapter removal from the reads of a FASTQ text (the first job of the fastp run MerCat2 starts); no table is read

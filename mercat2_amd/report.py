@@ -571,3 +571,109 @@ def write_qc_files(prefix, qc) -> list:
         with open(paths[-1], "wb") as fh:
             fh.write(fmt(qc))
     return paths
+
+
+# ---- -dedup: duplicate reads (kmers.dedup_reads / Counter.fastq_dedup) ----
+DEDUP_OVER_LIMIT = 1000  # rows of _overrepresented.tsv at most
+
+
+def dedup_copies(rows, paired: bool = False) -> list:
+    """copies[r]: the units (reads, or pairs with ``paired``) of the cluster of record r, from the ``first`` column of
+    Counter.fastq_dedup's rows (pure Python; kmers.dedup_reads counts with numpy)."""
+    firsts = [int(row[1]) for row in rows]
+    size: Dict[int, int] = {}
+    for r, f in enumerate(firsts):
+        if not paired or not r & 1:
+            size[f] = size.get(f, 0) + 1
+    return [size[f - (f & 1) if paired else f] for f in firsts]
+
+
+def dedup_over(copies, rows, paired: bool = False, over_frac: float = 0.001, limit: int = DEDUP_OVER_LIMIT) -> list:
+    """[(first record, copies)] of the over-represented clusters: those that hold at least ``over_frac`` of the units
+    and more than one of them, by copies descending, then by first ascending, ``limit`` of them at most.  With
+    ``paired`` the first record is the pair's first mate."""
+    step = 2 if paired else 1
+    units = len(rows) // step
+    found = [(int(rows[r][1]), int(copies[r])) for r in range(0, len(rows), step) if int(rows[r][1]) == r]
+    found = [(f, n) for f, n in found if n > 1 and n >= over_frac * units]
+    found.sort(key=lambda x: (-x[1], x[0]))
+    return found[:limit]
+
+
+def format_dedup_tsv(names: Sequence[str], rows, keep, copies) -> bytes:
+    """``record\tlength\tfirst\tcopies\tkeep``, then one line per record (kmers.dedup_reads / Counter.fastq_dedup): its
+    name, its length, the name of the record that stands for it, the size of its cluster and its keep value."""
+    if len(names) != len(rows) or len(names) != len(keep) or len(names) != len(copies):
+        raise ValueError("format_dedup_tsv: %d names for %d rows, %d keep values and %d copies" %
+                         (len(names), len(rows), len(keep), len(copies)))
+    out = [b"record\tlength\tfirst\tcopies\tkeep\n"]
+    for name, row, k, n in zip(names, rows, keep, copies):
+        out.append(name.encode() + b"\t%d\t" % int(row[0]) + names[int(row[1])].encode() + b"\t%d\t%d\n" % (int(n), int(k)))
+    return b"".join(out)
+
+
+def write_dedup_tsv(path, names: Sequence[str], rows, keep, copies) -> int:
+    """``format_dedup_tsv`` written to ``path``; returns the number of records."""
+    text = format_dedup_tsv(names, rows, keep, copies)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(names)
+
+
+def format_dedup_levels(levels, units: int) -> bytes:
+    """``copies\tsequences\treads\tpercent_of_reads``: for every level 1 .. high that occurs the clusters of that many
+    copies, the units they hold and their share of all ``units`` (reads, or pairs) with four decimals; the last row,
+    always written, is ``>high``: its units are those the other rows do not hold."""
+    high = len(levels) - 2
+    share = lambda n: b"%.4f" % (100.0 * n / units if units else 0.0)
+    out, held = [b"copies\tsequences\treads\tpercent_of_reads\n"], 0
+    for i in range(1, high + 1):
+        if int(levels[i]):
+            n = i * int(levels[i])
+            held += n
+            out.append(b"%d\t%d\t%d\t" % (i, int(levels[i]), n) + share(n) + b"\n")
+    out.append(b">%d\t%d\t%d\t" % (high, int(levels[high + 1]), int(units) - held) + share(int(units) - held) + b"\n")
+    return b"".join(out)
+
+
+def write_dedup_levels(path, levels, units: int) -> None:
+    """``format_dedup_levels`` written to ``path``."""
+    with open(path, "wb") as fh:
+        fh.write(format_dedup_levels(levels, units))
+
+
+def format_dedup_summary(figures: Dict[str, int], paired: bool = False) -> bytes:
+    """``metric\tvalue``: reads (``pairs`` with ``paired``), distinct, duplicates (units that are not the first of their
+    cluster), duplication_rate (duplicates / units, six decimals), largest_cluster, bases_before and bases_after -- from
+    the mk_fastq_dedup_t figures of a call with which = 1."""
+    units = int(figures["records"]) // (2 if paired else 1)
+    dup = units - int(figures["distinct"])
+    rows = [(b"pairs" if paired else b"reads", b"%d" % units), (b"distinct", b"%d" % int(figures["distinct"])),
+            (b"duplicates", b"%d" % dup), (b"duplication_rate", b"%.6f" % (dup / units if units else 0.0)),
+            (b"largest_cluster", b"%d" % int(figures["max_copies"])), (b"bases_before", b"%d" % int(figures["bases_in"])),
+            (b"bases_after", b"%d" % int(figures["bases_out"]))]
+    return b"metric\tvalue\n" + b"".join(k + b"\t" + v + b"\n" for k, v in rows)
+
+
+def write_dedup_summary(path, figures: Dict[str, int], paired: bool = False) -> None:
+    """``format_dedup_summary`` written to ``path``."""
+    with open(path, "wb") as fh:
+        fh.write(format_dedup_summary(figures, paired))
+
+
+def format_dedup_over(over, names: Sequence[str], seqs: Sequence[bytes], units: int, paired: bool = False) -> bytes:
+    """``first\tcopies\tpercent\tsequence`` (and ``sequence2`` with ``paired``): one line per (first record, copies) of
+    ``over`` (dedup_over, whose order is kept): the name of the first record, the copies, their share of all ``units``
+    with four decimals, and the key of that record (of both mates); ``seqs[r]`` is the key of record r."""
+    out = [b"first\tcopies\tpercent\tsequence" + (b"\tsequence2" if paired else b"") + b"\n"]
+    for first, n in over:
+        out.append(names[first].encode() + b"\t%d\t%.4f\t" % (n, 100.0 * n / units if units else 0.0) + bytes(seqs[first]) +
+                   (b"\t" + bytes(seqs[first + 1]) if paired else b"") + b"\n")
+    return b"".join(out)
+
+
+def write_dedup_over(path, over, names: Sequence[str], seqs: Sequence[bytes], units: int, paired: bool = False) -> int:
+    """``format_dedup_over`` written to ``path``; returns the number of rows."""
+    with open(path, "wb") as fh:
+        fh.write(format_dedup_over(over, names, seqs, units, paired))
+    return len(over)
