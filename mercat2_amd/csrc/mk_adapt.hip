@@ -2,7 +2,7 @@
 // mk_fastq_adapt_device; include/mercat_hip.h has the rule and the panel's layout): every read is cut at the leftmost
 // position at which an adapter of the panel matches its remainder (or runs off its end) within the error rate, the
 // survivors gathered as FASTQ -- on the GPU, by mk_qtrim.hip's scheme (mk_fqpiece.h has the shared parts):
-//   fs_tiles_k / fs_scan_k / fs_lines_k<false>   the line index (mk_fqindex.h), unchanged.
+//   fs_index_open / fs_index_lines<false>        the line index (mk_fqindex.h), unchanged.
 //   ad_scan_k                a wave a record, a lane a candidate position, 64 positions a block.  Lanes 0 .. 11 load the 12
 //                            aligned 16-byte granules that hold the block's positions and the 128 bases behind them
 //                            (QtLine: fs_load) and pack each into 32 bits of 2-bit codes and 32 bits of an "other" plane

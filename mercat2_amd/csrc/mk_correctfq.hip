@@ -6,8 +6,7 @@
 // raw bytes.
 //
 // A piece of n bytes (16-byte aligned, in c->raw):
-//   fs_tiles_k / fs_scan_k / fs_lines_k<true>   the line index of mk_fqselect.hip (mk_fqindex.h), line[L] for L <= 4 nrec,
-//                                               and the check of the sequence lines' bytes
+//   fs_index_open, fs_index_lines<true>         the line index (mk_fqindex.h) with the check of the sequence lines' bytes
 //   cq_check_k                                  a lane per record: '@', '+', the two lengths, from five line[] entries and
 //                                               a few bytes; atomicMin(record << 3 | check) as fs_decide_k.  Read back
 //                                               here: a text that fails is not parsed.
@@ -119,43 +118,19 @@ struct CqCall {
 static int cq_piece(ScCall& s, CrCall& f, CqCall& q, uint8_t* d_view, size_t n, uint8_t* d_dst, const uint8_t* d_src) {
   mk_ctx* c = s.c;
   int rc;
-  const size_t ntiles = div_up(n, FS_TILE);
-  // tiles: FsStatus (48) | tile_pre[ntiles] | tile_cnt[ntiles]
-  if ((rc = mk_buf_reserve(c, q.tiles, sizeof(FsStatus) + ntiles * (sizeof(u64) + sizeof(unsigned)))) != MK_OK) return rc;
-  FsStatus* d_st = (FsStatus*)q.tiles.p;
-  u64* tile_pre = (u64*)((char*)q.tiles.p + sizeof(FsStatus));
-  unsigned* tile_cnt = (unsigned*)(tile_pre + ntiles);
-  FsStatus h{};
-  h.bad = FS_NONE;
-  MK_HIP(hipMemcpyAsync(d_st, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-  if ((rc = q.index.begin()) != MK_OK) return rc;
-  hipLaunchKernelGGL(fs_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const uint8_t*)d_view, (u64)n, tile_cnt);
-  hipLaunchKernelGGL(fs_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, d_st);
-  MK_HIP(hipGetLastError());
-  if ((rc = q.index.end()) != MK_OK) return rc;
-  uint8_t tail[4] = {0, 0, 0, 0};
-  const size_t ntail = std::min<size_t>(n, 4);
-  u64 newlines = 0;
-  MK_HIP(hipMemcpyAsync(&newlines, &d_st->newlines, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  MK_HIP(hipMemcpyAsync(tail + (4 - ntail), d_view + (n - ntail), ntail, hipMemcpyDeviceToHost, c->stream));
-  MK_HIP(hipStreamSynchronize(c->stream));
-  if ((rc = q.index.add_to(q.st.s_index)) != MK_OK) return rc;
-  const u64 lines = newlines + (tail[3] != '\n' ? 1 : 0);
-  const size_t nrec = (size_t)(lines / 4), first = q.records;
-  const unsigned trailing = (unsigned)(lines & 3);
-  q.st.lines += lines;
+  FsIndex ix;
+  if ((rc = fs_index_open(c, q.tiles, q.index, q.st.s_index, d_view, n, nullptr, 0, ix)) != MK_OK) return rc;
+  FsStatus* d_st = ix.d_st;
+  const size_t nrec = ix.nrec, first = q.records;
+  q.st.lines += ix.lines;
   q.records += nrec;
-  // what trails behind the last complete record: `trailing` empty lines are that many '\n' behind a '\n' (or the text's start)
-  bool trail_ok = true;
-  for (unsigned i = 0; i < trailing && trail_ok; ++i) trail_ok = tail[3 - i] == '\n';
-  if (trailing && trail_ok && n > trailing) trail_ok = tail[3 - trailing] == '\n';
+  // (a failed check ends the call at once: no piece behind it is parsed)
   const auto fail_trailing = [&]() {
-    c->err = std::string(q.what) + ": record " + std::to_string(first + nrec) + " is malformed: the text ends inside it (" +
-             std::to_string(trailing) + " of its 4 lines)";
+    c->err = fs_msg_incomplete(q.what, first + nrec, ix.trailing);
     return MK_ERR_UNSUPPORTED;
   };
   if (!nrec) {  // (empty lines only: nothing to parse; the piece counts among the bytes read as any other)
-    if (!trail_ok) return fail_trailing();
+    if (!ix.trail_ok) return fail_trailing();
     s.out.bytes += n;
     s.out.pieces += 1;
     if (d_src) MK_HIP(hipMemcpyAsync(d_dst, d_src, n, hipMemcpyDeviceToDevice, c->stream));
@@ -166,23 +141,19 @@ static int cq_piece(ScCall& s, CrCall& f, CqCall& q, uint8_t* d_view, size_t n, 
   const size_t nidx = 4 * nrec;
   if ((rc = mk_buf_reserve(c, q.lines, (nidx + 1) * sizeof(u64))) != MK_OK) return rc;
   u64* line = (u64*)q.lines.p;
-  if ((rc = q.index.begin()) != MK_OK) return rc;
-  const int end_is_n = lines == nidx ? 1 : 0;  // (no line 4 nrec starts: the last record ends with the text)
-  hipLaunchKernelGGL(fs_lines_k<true>, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const uint8_t*)d_view, (u64)n,
-                     (const u64*)tile_pre, (u64)nidx, end_is_n, line, d_st);
-  hipLaunchKernelGGL(cq_check_k, dim3(grid_for(nrec, 256, 4096)), dim3(256), 0, c->stream, (const uint8_t*)d_view, (const u64*)line, nrec,
-                     d_st);
-  MK_HIP(hipGetLastError());
-  if ((rc = q.index.end()) != MK_OK) return rc;
+  rc = fs_index_lines<true>(c, q.index, d_view, n, ix, line, [&]() {
+    hipLaunchKernelGGL(cq_check_k, dim3(grid_for(nrec, 256, 4096)), dim3(256), 0, c->stream, (const uint8_t*)d_view, (const u64*)line, nrec, d_st);
+  });
+  if (rc != MK_OK) return rc;
+  FsStatus h;
   MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipStreamSynchronize(c->stream));
   if ((rc = q.index.add_to(q.st.s_index)) != MK_OK) return rc;
   if (h.bad != FS_NONE) {
-    c->err = std::string(q.what) + ": record " + std::to_string(first + (size_t)(h.bad >> 3)) + " is malformed: " +
-             fs_kind((unsigned)(h.bad & 7));
+    c->err = fs_msg_malformed(q.what, first + (size_t)(h.bad >> 3), fs_kind((unsigned)(h.bad & 7)));
     return MK_ERR_UNSUPPORTED;
   }
-  if (!trail_ok) return fail_trailing();
+  if (!ix.trail_ok) return fail_trailing();
 
   // the view, in place; its figures go to a word of the call: what mk_fastq_stats reports is the counting path's alone
   std::swap(c->fastq_stats, q.stats);
@@ -267,8 +238,7 @@ static int cq_run(mk_ctx* c, unsigned flags, const mk_correct_fastq_rule_t* rule
   }
   if (out_cap < n) {  // (the output has the input's length: known before any work)
     if (out_len) *out_len = n;
-    c->err = std::string(what) + ": the output holds " + std::to_string(n) + " bytes, out has room for " + std::to_string(out_cap);
-    return MK_ERR_RANGE;
+    return fs_out_room(c, what, n, out_cap);
   }
   f->cap = (f->rows || f->fix) ? f->cap : ~(size_t)0;
   f->apply = false;
@@ -303,13 +273,9 @@ extern "C" int mk_correct_fastq_device(mk_ctx* c, const uint8_t* d_fastq, size_t
   CqCall q(c, "mk_correct_fastq_device", rule ? rule->new_qual : 0);
   return cq_run(c, flags, rule, n, out_cap, &f, &q, out_len, nrows, st, [&](ScCall& s) -> int {
     if (!n) return MK_OK;
-    int rc = mk_buf_reserve(c, c->raw, n + 64);
-    if (rc != MK_OK) return rc;
-    const auto t1 = MkClock::now();
-    MK_HIP(hipMemcpyAsync(c->raw.p, d_fastq, n, hipMemcpyDeviceToDevice, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    q.st.s_copy += mk_since(t1);
-    return cq_piece(s, f, q, (uint8_t*)c->raw.p, n, d_out, d_out != d_fastq ? d_fastq : nullptr);
+    const uint8_t* d_view;  // (always the call's own copy: it becomes the view)
+    const int rc = fs_aligned_text(c, d_fastq, n, true, q.st.s_copy, &d_view);
+    return rc != MK_OK ? rc : cq_piece(s, f, q, (uint8_t*)c->raw.p, n, d_out, d_out != d_fastq ? d_fastq : nullptr);
   });
 }
 
@@ -324,19 +290,11 @@ extern "C" int mk_correct_fastq_text(mk_ctx* c, const uint8_t* fastq, size_t n, 
   CqCall q(c, "mk_correct_fastq_text", rule ? rule->new_qual : 0);
   return cq_run(c, flags, rule, n, out_cap, &f, &q, out_len, nrows, st, [&](ScCall& s) -> int {
     if (!n) return MK_OK;
-    // pieces end behind a line 4j once they hold `piece` bytes: the default and the limits of the screen calls.  The
-    // corrected pieces stay on the device until the last has passed its checks: out is written once, or not at all.
-    size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
-    piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
-    std::vector<uint64_t> cuts(n / piece + 2, 0);
-    size_t ncuts = 0;
-    if (mk_fastq_cuts(fastq, n, piece, cuts.data(), cuts.size(), &ncuts) != MK_OK) {
-      c->err = "mk_correct_fastq_text: the line scanner failed (internal error)";
-      return MK_ERR_STATE;
-    }
-    cuts.resize(ncuts);
-    cuts.push_back(n);
-    int rc = mk_buf_reserve(c, q.stage, n);
+    // The corrected pieces stay on the device until the last has passed its checks: out is written once, or not at all.
+    std::vector<uint64_t> cuts;
+    int rc = fs_piece_cuts(c, q.what, fastq, n, piece_bytes, false, cuts);
+    if (rc != MK_OK) return rc;
+    rc = mk_buf_reserve(c, q.stage, n);
     if (rc != MK_OK) return rc;
     uint8_t* stage = (uint8_t*)q.stage.p;
     size_t at = 0;

@@ -475,24 +475,16 @@ extern "C" int mk_fastq_dedup_text(mk_ctx* c, const uint8_t* fastq, size_t n, si
     DdSide& s = f.side;
     // the pieces of fq_text_body, and beside the pass that cuts them the line count that sizes ref[] and the table
     const auto t0 = MkClock::now();
-    size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
-    piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
-    std::vector<uint64_t> cuts(n / piece + 2, 0);
-    size_t ncuts = 0;
-    if ((o.paired ? mk_fastq_pair_cuts : mk_fastq_cuts)(fastq, n, piece, cuts.data(), cuts.size(), &ncuts) != MK_OK) {
-      c->err = "mk_fastq_dedup_text: the line scanner failed (internal error)";
-      return MK_ERR_STATE;
-    }
-    cuts.resize(ncuts);
-    cuts.push_back(n);
+    std::vector<uint64_t> cuts;
+    int rc = fs_piece_cuts(c, f.what, fastq, n, piece_bytes, o.paired, cuts);
+    if (rc != MK_OK) return rc;
     size_t newlines = 0;  // (a memchr walk: 33 ms for 314 MB where std::count, which this build does not vectorise, took 79)
     for (const uint8_t *p = fastq, *end = fastq + n; (p = (const uint8_t*)memchr(p, '\n', (size_t)(end - p))) != nullptr; ++p) ++newlines;
     s.expect = (newlines + (fastq[n - 1] != '\n' ? 1 : 0)) / 4;
     // every piece at an offset aligned to 16 of one buffer (the line kernels load aligned granules), 64 bytes of slack
     const size_t res_bytes = n + 16 * cuts.size() + 64;
     f.st.s_plan += mk_since(t0);
-    int rc = mk_buf_reserve(c, s.res, res_bytes);
-    if (rc != MK_OK) {
+    if ((rc = mk_buf_reserve(c, s.res, res_bytes)) != MK_OK) {
       if (rc == MK_ERR_NOMEM) c->err = "mk_fastq_dedup_text: the resident text (" + std::to_string(res_bytes) + " bytes): " + c->err;
       return rc;
     }

@@ -1,10 +1,12 @@
 // mk_fqpiece.h -- what the calls that read a FASTQ text, judge every record by a scan kernel of their own and write the
-// survivors cut share: mk_fastq_qtrim_* (mk_qtrim.hip), mk_fastq_adapt_* (mk_adapt.hip) and mk_fastq_overlap_* (mk_overlap.hip).
+// survivors, whole or cut, share: mk_fastq_qtrim_* (mk_qtrim.hip), mk_fastq_adapt_* (mk_adapt.hip), mk_fastq_overlap_*
+// (mk_overlap.hip) and mk_fastq_dedup_* (mk_dedup.hip).  mk_fastq_qc_* (mk_qc.hip) takes the device side only.
 //   device side   QtLine (a line's content seen through aligned 16-byte granules), qt_record (the lines of a record and
 //                 its checks), fq_segments (the four segments of an emitted record from its span).
-//   host side     FqCall<P> (the state of a call), fq_piece<P> (one piece: line index, P::scan, P::decide, the prefix
-//                 sum, the gather, the copies back), fq_run (how a call checks, opens and ends), fq_device_body /
-//                 fq_text_body (the one piece of a device call, the piece loop of a text call).
+//   host side     FqCall<P> (the state of a call), fq_piece<P> (one piece: mk_fqindex.h's steps -- fs_index_open,
+//                 fs_index_lines, fs_gather -- around P::scan, P::decide and the prefix sum), fq_run (fs_call, the check
+//                 of the record count, fs_call_end, fs_out_room), fq_device_body / fq_text_body (the one piece of a
+//                 device call over fs_aligned_text, the pieces of a text call over fs_piece_cuts).
 // A policy P names what differs:
 //   Opt, Status (device counters behind the FsStatus of a piece), Stats (the call's mk_fastq_*_t), Side (what the scan
 //   kernel reads or writes beside the text), ROW (uint64 a row),
@@ -78,11 +80,9 @@ __device__ __forceinline__ bool fq_segments(const QtRecord& q, u64 L, u64 start,
 
 // ------------------------------------------------------------------------------------------ host side
 template <class P>
-struct FqCall {
+struct FqCall : FsPieces {
   mk_ctx* c;
-  const char* what;
   typename P::Opt o;
-  size_t limit;   // records the caller's arrays hold
   uint8_t* keep;  // the caller's arrays (host memory for the text call, device memory for the device call), or nullptr
   u64* rows;
   uint8_t* out;
@@ -93,16 +93,13 @@ struct FqCall {
   MkDevBuf tiles, meta, scan_tmp, stage, side_buf;
   MkTimed index, scan, place, gather;
   typename P::Stats st{};
-  size_t records = 0, bytes_out = 0;  // of all pieces so far
-  int bad_rc = MK_OK;                 // the first record that failed a check (pieces come in text order)
-  std::string bad_msg;
+  size_t bytes_out = 0;  // of all pieces so far
   FqCall(mk_ctx* c_, const char* w, const typename P::Opt& o_, size_t lim, uint8_t* kp, u64* rw, uint8_t* ot, size_t oc, bool dev)
-      : c(c_), what(w), o(o_), limit(lim), keep(kp), rows(rw), out(ot), out_cap(oc), device(dev), side{}, index(c_), scan(c_), place(c_),
+      : FsPieces{w, lim}, c(c_), o(o_), keep(kp), rows(rw), out(ot), out_cap(oc), device(dev), side{}, index(c_), scan(c_), place(c_),
         gather(c_) {}
   ~FqCall() {
     for (MkDevBuf* b : {&tiles, &meta, &scan_tmp, &stage, &side_buf}) buf_free(*b);
   }
-  bool counting_only() const { return bad_rc != MK_OK || records > limit; }
 };
 
 // P::ready(f, d_text, n, nrec), where a policy has one: what it sets up once a piece's record count is known and before
@@ -122,45 +119,16 @@ static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
   constexpr size_t ROW = P::ROW;
   mk_ctx* c = f.c;
   int rc;
-  const size_t ntiles = div_up(n, FS_TILE);
-  // tiles: FsStatus | Status | tile_pre[ntiles] | tile_cnt[ntiles]
-  if ((rc = mk_buf_reserve(c, f.tiles, sizeof(FsStatus) + sizeof(Status) + ntiles * (sizeof(u64) + sizeof(unsigned)))) != MK_OK) return rc;
-  FsStatus* d_st = (FsStatus*)f.tiles.p;
-  Status* d_qs = (Status*)(d_st + 1);
-  u64* tile_pre = (u64*)(d_qs + 1);
-  unsigned* tile_cnt = (unsigned*)(tile_pre + ntiles);
-  struct { FsStatus s; Status q; } h{};
-  h.s.bad = FS_NONE;
-  MK_HIP(hipMemcpyAsync(d_st, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-  if ((rc = f.index.begin()) != MK_OK) return rc;
-  hipLaunchKernelGGL(fs_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_text, (u64)n, tile_cnt);
-  hipLaunchKernelGGL(fs_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, d_st);
-  MK_HIP(hipGetLastError());
-  if ((rc = f.index.end()) != MK_OK) return rc;
-  uint8_t tail[4] = {0, 0, 0, 0};
-  const size_t ntail = std::min<size_t>(n, 4);
-  u64 newlines = 0;
-  MK_HIP(hipMemcpyAsync(&newlines, &d_st->newlines, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  MK_HIP(hipMemcpyAsync(tail + (4 - ntail), d_text + (n - ntail), ntail, hipMemcpyDeviceToHost, c->stream));
-  MK_HIP(hipStreamSynchronize(c->stream));
-  if ((rc = f.index.add_to(f.st.s_index)) != MK_OK) return rc;
-  const u64 lines = newlines + (tail[3] != '\n' ? 1 : 0);
-  const size_t nrec = (size_t)(lines / 4), first = f.records;
-  const unsigned trailing = (unsigned)(lines & 3);
-  f.st.lines += lines;
-  f.records += nrec;
-  // what trails behind the last complete record: `trailing` empty lines are that many '\n' behind a '\n' (or the text's start)
-  bool trail_ok = true;
-  for (unsigned i = 0; i < trailing && trail_ok; ++i) trail_ok = tail[3 - i] == '\n';
-  if (trailing && trail_ok && n > trailing) trail_ok = tail[3 - trailing] == '\n';
-  if (f.counting_only()) return MK_OK;
-  const auto fail_trailing = [&]() {
-    f.bad_rc = MK_ERR_UNSUPPORTED;
-    f.bad_msg = std::string(f.what) + ": record " + std::to_string(first + nrec) + " is malformed: the text ends inside it (" +
-                std::to_string(trailing) + " of its 4 lines)";
-    return MK_OK;
-  };
-  if (!nrec) return trail_ok ? MK_OK : fail_trailing();
+  static_assert(sizeof(Status) <= FS_OWN_MAX && sizeof(Status) % 8 == 0, "the status block of a policy");
+  const Status zero{};
+  FsIndex ix;
+  if ((rc = fs_index_open(c, f.tiles, f.index, f.st.s_index, d_text, n, &zero, sizeof zero, ix)) != MK_OK) return rc;
+  FsStatus* d_st = ix.d_st;
+  Status* d_qs = (Status*)ix.d_own;
+  const size_t nrec = ix.nrec;
+  size_t first;
+  f.st.lines += ix.lines;
+  if (!f.take(ix, first)) return MK_OK;
   if ((rc = fq_ready(f, d_text, n, nrec, 0)) != MK_OK) return rc;
 
   // meta: line[4 nrec + 1] | seg_src[nseg + 1] | len[nseg + 1] | dst[nseg + 1] | rows[ROW nrec] | verdict[nrec] | keep[nrec]
@@ -179,12 +147,7 @@ static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
   MK_HIP(rocprim::exclusive_scan((void*)nullptr, tmp, (const u64*)len, dst, 0ull, nseg + 1, rocprim::plus<u64>(), c->stream));
   if ((rc = mk_buf_reserve(c, f.scan_tmp, tmp ? tmp : 16)) != MK_OK) return rc;
 
-  if ((rc = f.index.begin()) != MK_OK) return rc;
-  const int end_is_n = lines == nidx ? 1 : 0;  // (no line 4 nrec starts: the last record ends with the text)
-  hipLaunchKernelGGL(fs_lines_k<false>, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_text, (u64)n, (const u64*)tile_pre, (u64)nidx,
-                     end_is_n, line, d_st);
-  MK_HIP(hipGetLastError());
-  if ((rc = f.index.end()) != MK_OK) return rc;
+  if ((rc = fs_index_lines<false>(c, f.index, d_text, n, ix, line)) != MK_OK) return rc;
   if ((rc = f.scan.begin()) != MK_OK) return rc;
   P::scan(f, d_text, n, (const u64*)line, nrec, d_rows, d_verdict, d_st);
   MK_HIP(hipGetLastError());
@@ -196,19 +159,14 @@ static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
   MK_HIP(rocprim::exclusive_scan(f.scan_tmp.p, tmp, (const u64*)len, dst, 0ull, nseg + 1, rocprim::plus<u64>(), c->stream));
   if ((rc = f.place.end()) != MK_OK) return rc;
   u64 piece_out = 0;
+  struct { FsStatus s; Status q; } h;
   MK_HIP(hipMemcpyAsync(&h, d_st, sizeof h, hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipMemcpyAsync(&piece_out, dst + nseg, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipStreamSynchronize(c->stream));
   if ((rc = f.index.add_to(f.st.s_index)) != MK_OK) return rc;
   if ((rc = f.scan.add_to(f.st.s_scan)) != MK_OK) return rc;
   if ((rc = f.place.add_to(f.st.s_place)) != MK_OK) return rc;
-  if (h.s.bad != FS_NONE) {
-    f.bad_rc = MK_ERR_UNSUPPORTED;
-    f.bad_msg = std::string(f.what) + ": record " + std::to_string(first + (size_t)(h.s.bad >> 3)) + " is malformed: " +
-                P::kind((unsigned)(h.s.bad & 7));
-    return MK_OK;
-  }
-  if (!trail_ok) return fail_trailing();
+  if (f.failed(ix, first, h.s.bad, P::kind)) return MK_OK;
   if (piece_out > (u64)n + 1) {
     c->err = std::string(f.what) + ": the output of a piece is longer than its records (internal error)";
     return MK_ERR_STATE;
@@ -224,37 +182,8 @@ static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
     MK_HIP(hipStreamSynchronize(c->stream));
     f.st.s_write += mk_since(t1);
   }
-
-  // the gather: into the caller's device memory, or into a staging buffer that is copied to the host.  Without room the
-  // call goes on adding up and answers MK_ERR_RANGE at its end.
-  const size_t at = f.bytes_out;
-  f.bytes_out += (size_t)piece_out;
-  if (!piece_out || f.bytes_out > f.out_cap) return MK_OK;
-  uint8_t* d_out = f.out + at;
-  if (!f.device) {
-    if ((rc = mk_buf_reserve(c, f.stage, (size_t)piece_out)) != MK_OK) return rc;
-    d_out = (uint8_t*)f.stage.p;
-  }
-  const u64 head = std::min<u64>((16 - ((uintptr_t)d_out & 15)) & 15, piece_out);
-  const u64 nbody = (piece_out - head) / 16, tail_at = head + 16 * nbody;
-  if ((rc = f.gather.begin()) != MK_OK) return rc;
-  if (nbody)
-    hipLaunchKernelGGL(fs_gather_k, dim3((unsigned)div_up((size_t)nbody, 256 * FS_CHUNKS)), dim3(256), 0, c->stream, d_text, (u64)n,
-                       (const u64*)seg_src, (const u64*)dst, nseg, head, nbody, d_out);
-  if (head || tail_at < piece_out)
-    hipLaunchKernelGGL(fs_edges_k, dim3(1), dim3(64), 0, c->stream, d_text, (u64)n, (const u64*)seg_src, (const u64*)dst, nseg, head,
-                       tail_at, piece_out, d_out);
-  MK_HIP(hipGetLastError());
-  if ((rc = f.gather.end()) != MK_OK) return rc;
-  MK_HIP(hipStreamSynchronize(c->stream));
-  if ((rc = f.gather.add_to(f.st.s_gather)) != MK_OK) return rc;
-  if (!f.device) {
-    const auto t1 = MkClock::now();
-    MK_HIP(hipMemcpyAsync(f.out + at, d_out, (size_t)piece_out, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    f.st.s_write += mk_since(t1);
-  }
-  return MK_OK;
+  return fs_gather(c, f.gather, f.stage, d_text, n, seg_src, dst, nseg, piece_out, f.out, f.out_cap, f.device, f.bytes_out, f.st.s_gather,
+                   f.st.s_write);
 }
 
 // How both kinds of call check their arguments, open and end; pre(): what the call sets up on the device before the first
@@ -262,17 +191,18 @@ static int fq_piece(FqCall<P>& f, const uint8_t* d_text, size_t n) {
 template <class P, class Pre, class Body, class Post>
 static int fq_run(FqCall<P>& f, size_t* out_len, size_t* nrec, typename P::Stats* st, Pre&& pre, Body&& body, Post&& post) {
   mk_ctx* c = f.c;
-  MK_REFUSE_SPOILED(c, f.what);
-  if (c->in_chunk) { c->err = std::string(f.what) + ": a chunk is open"; return MK_ERR_STATE; }
-  if (!out_len) { c->err = std::string(f.what) + ": out_len is NULL"; return MK_ERR_ARG; }
-  *out_len = 0;
-  if (nrec) *nrec = 0;
-  MK_HIP(hipSetDevice(c->device));
-  MK_HIP(hipStreamSynchronize(c->stream));
-  int rc;
-  if ((rc = pre()) != MK_OK) return rc;
-  rc = body();
-  (void)hipStreamSynchronize(c->stream);
+  int rc = fs_call(
+      c, f.what,
+      [&]() -> int {
+        if (!out_len) { c->err = std::string(f.what) + ": out_len is NULL"; return MK_ERR_ARG; }
+        *out_len = 0;
+        if (nrec) *nrec = 0;
+        return MK_OK;
+      },
+      [&]() -> int {
+        const int r = pre();
+        return r != MK_OK ? r : body();
+      });
   if (rc != MK_OK) return rc;
   if (nrec) *nrec = f.records;
   if (f.records > f.limit) {
@@ -280,72 +210,39 @@ static int fq_run(FqCall<P>& f, size_t* out_len, size_t* nrec, typename P::Stats
              std::to_string(f.limit);
     return MK_ERR_RANGE;
   }
-  if (P::paired(f.o) && (f.records & 1)) {
-    c->err = std::string(f.what) + ": paired, but the text holds an odd number of records (" + std::to_string(f.records) + ")";
-    return MK_ERR_RANGE;
-  }
-  if (f.bad_rc != MK_OK) {
-    c->err = f.bad_msg;
-    return f.bad_rc;
-  }
+  if ((rc = fs_call_end(c, f.what, f.records, P::paired(f.o), f.bad_rc, f.bad_msg)) != MK_OK) return rc;
   if ((rc = post()) != MK_OK) return rc;
   *out_len = f.bytes_out;
   f.st.records = f.records;
   f.st.bytes_out = f.bytes_out;
   if (st) *st = f.st;
-  if (f.bytes_out > f.out_cap) {
-    c->err = std::string(f.what) + ": the output holds " + std::to_string(f.bytes_out) + " bytes, out has room for " + std::to_string(f.out_cap);
-    return MK_ERR_RANGE;
-  }
-  return MK_OK;
+  return fs_out_room(c, f.what, f.bytes_out, f.out_cap);
 }
 
-// The one piece of a device call: the text where it stands, or copied to c->raw where it is not aligned to 16 (the line
-// passes, the scans and fl_load16 load 16 aligned bytes at a time) or where the call patches its text (own_copy).
+// The one piece of a device call: the text where it stands or its aligned copy (own_copy: the call patches its text).
 template <class P>
 static int fq_device_body(FqCall<P>& f, const uint8_t* d_fastq, size_t n, bool own_copy = false) {
-  mk_ctx* c = f.c;
   if (!n) return MK_OK;
-  const uint8_t* d_text = d_fastq;
-  if (((uintptr_t)d_text & 15) || own_copy) {
-    int rc = mk_buf_reserve(c, c->raw, n + 64);
-    if (rc != MK_OK) return rc;
-    const auto t1 = MkClock::now();
-    MK_HIP(hipMemcpyAsync(c->raw.p, d_fastq, n, hipMemcpyDeviceToDevice, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    f.st.s_copy += mk_since(t1);
-    d_text = (const uint8_t*)c->raw.p;
-    f.own = (uint8_t*)c->raw.p;
-  }
+  const uint8_t* d_text;
+  int rc = fs_aligned_text(f.c, d_fastq, n, own_copy, f.st.s_copy, &d_text);
+  if (rc != MK_OK) return rc;
+  if (d_text != d_fastq) f.own = (uint8_t*)f.c->raw.p;
   return fq_piece(f, d_text, n);
 }
 
-// The pieces of a text call: they end behind a line 4j (8j: mates stay together) once they hold `piece` bytes: the default
-// and the limits of the screen calls.
+// The pieces of a text call (fs_piece_cuts), each uploaded to c->raw.
 template <class P>
 static int fq_text_body(FqCall<P>& f, const uint8_t* fastq, size_t n, size_t piece_bytes) {
   mk_ctx* c = f.c;
   if (!n) return MK_OK;
-  size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
-  piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
-  std::vector<uint64_t> cuts(n / piece + 2, 0);
-  size_t ncuts = 0;
-  if ((P::paired(f.o) ? mk_fastq_pair_cuts : mk_fastq_cuts)(fastq, n, piece, cuts.data(), cuts.size(), &ncuts) != MK_OK) {
-    c->err = std::string(f.what) + ": the line scanner failed (internal error)";
-    return MK_ERR_STATE;
-  }
-  cuts.resize(ncuts);
-  cuts.push_back(n);
+  std::vector<uint64_t> cuts;
+  int rc = fs_piece_cuts(c, f.what, fastq, n, piece_bytes, P::paired(f.o), cuts);
+  if (rc != MK_OK) return rc;
   size_t at = 0;
   for (const uint64_t end : cuts) {
     const size_t len = (size_t)end - at;
     if (!len) continue;
-    int rc = mk_buf_reserve(c, c->raw, len + 64);
-    if (rc != MK_OK) return rc;
-    const auto t1 = MkClock::now();
-    MK_HIP(hipMemcpyAsync(c->raw.p, fastq + at, len, hipMemcpyHostToDevice, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    f.st.s_copy += mk_since(t1);
+    if ((rc = fs_upload_raw(c, fastq + at, len, f.st.s_copy)) != MK_OK) return rc;
     f.own = (uint8_t*)c->raw.p;
     if ((rc = fq_piece(f, (const uint8_t*)c->raw.p, len)) != MK_OK) return rc;
     at = (size_t)end;

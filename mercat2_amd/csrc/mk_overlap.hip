@@ -3,7 +3,7 @@
 // offset, the first admissible one in the rule's order giving the fragment length; the pairs then cut to the fragment
 // (mode 0) or merged into one read with a consensus over the overlap (mode 1), the survivors gathered as FASTQ -- on the
 // GPU, by mk_qtrim.hip's scheme (mk_fqpiece.h has the shared parts):
-//   fs_tiles_k / fs_scan_k / fs_lines_k<false>   the line index (mk_fqindex.h), unchanged.
+//   fs_index_open / fs_index_lines<false>        the line index (mk_fqindex.h), unchanged.
 //   ov_scan_k     a wave (a workgroup of one) a pair, a lane a candidate offset, 64 candidates a block in the rule's order.
 //                 All 64 lanes load: lanes 0 .. 31 the first 32 aligned 16-byte granules of mate 1's sequence line, lanes
 //                 32 .. 63 those of mate 2's (QtLine: fs_load); lanes 31 and 63 also load the 33rd granule, which holds

@@ -2,8 +2,8 @@
 // has the rule): where along the read the quality falls and the base composition drifts, and per read its length, mean
 // quality and GC share -- the figures fastqc gives MerCat2 before and after trimming, reduced on the GPU from the text,
 // the line index and the record checks the trimming calls already have there.  Nothing is written out, so the decide /
-// prefix sum / gather of mk_fqpiece.h's piece have no part here; the piece below is its first half with two kernels:
-//   fs_tiles_k / fs_scan_k / fs_lines_k<false>   the line index (mk_fqindex.h), unchanged.
+// prefix sum / gather of mk_fqpiece.h's piece have no part here; the piece below is the line index of mk_fqindex.h
+// (fs_index_open, fs_index_lines) with two kernels behind it:
 //   qc_reads_k    qt_scan_k's layout: 16 lanes a record, four records a wave, a lane one aligned 16-byte granule of a
 //                 line a pass, DPP row sums.  The quality line gives qsum and the bytes below the phred base, the
 //                 sequence line on its own granules gc and n.  Lane 0 of the row names a failed record (atomicMin on the
@@ -252,27 +252,21 @@ static size_t qc_table_words(const QcOpt& o, size_t at[5]) {  // where the five 
   return total;
 }
 
-struct QcCall {
+struct QcCall : FsPieces {
   mk_ctx* c;
-  const char* what;
   QcOpt o;
-  size_t limit;  // records the caller's rows hold
   u64* rows;     // the caller's (host memory for the text call, device memory for the device call), or nullptr
   bool device;
   QcTables t{};
   MkDevBuf tiles, meta, tables;
   MkTimed index, reads, cycles;
   mk_fastq_qc_t st{};
-  size_t records = 0;
   u64 mn[2] = {~0ull, ~0ull}, mx[2] = {0, 0};
-  int bad_rc = MK_OK;  // the first record that failed a check (pieces come in text order)
-  std::string bad_msg;
   QcCall(mk_ctx* c_, const char* w, const QcOpt& o_, size_t lim, u64* rw, bool dev)
-      : c(c_), what(w), o(o_), limit(lim), rows(rw), device(dev), index(c_), reads(c_), cycles(c_) {}
+      : FsPieces{w, lim}, c(c_), o(o_), rows(rw), device(dev), index(c_), reads(c_), cycles(c_) {}
   ~QcCall() {
     for (MkDevBuf* b : {&tiles, &meta, &tables}) buf_free(*b);
   }
-  bool counting_only() const { return bad_rc != MK_OK || records > limit; }
 };
 
 // One piece of n > 0 bytes at d_text (device memory, 16-byte aligned, below 2^32 bytes, whole records -- whole pairs with
@@ -281,46 +275,17 @@ struct QcCall {
 static int qc_piece(QcCall& f, const uint8_t* d_text, size_t n) {
   mk_ctx* c = f.c;
   int rc;
-  const size_t ntiles = div_up(n, FS_TILE);
-  // tiles: FsStatus | QcStatus | tile_pre[ntiles] | tile_cnt[ntiles]
-  if ((rc = mk_buf_reserve(c, f.tiles, sizeof(FsStatus) + sizeof(QcStatus) + ntiles * (sizeof(u64) + sizeof(unsigned)))) != MK_OK) return rc;
-  FsStatus* d_st = (FsStatus*)f.tiles.p;
-  QcStatus* d_qs = (QcStatus*)(d_st + 1);
-  u64* tile_pre = (u64*)(d_qs + 1);
-  unsigned* tile_cnt = (unsigned*)(tile_pre + ntiles);
-  struct { FsStatus s; QcStatus q; } h{};
-  h.s.bad = h.q.bad = FS_NONE;
-  h.q.min_len[0] = h.q.min_len[1] = ~0ull;
-  MK_HIP(hipMemcpyAsync(d_st, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-  if ((rc = f.index.begin()) != MK_OK) return rc;
-  hipLaunchKernelGGL(fs_tiles_k, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_text, (u64)n, tile_cnt);
-  hipLaunchKernelGGL(fs_scan_k, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)tile_cnt, ntiles, tile_pre, d_st);
-  MK_HIP(hipGetLastError());
-  if ((rc = f.index.end()) != MK_OK) return rc;
-  uint8_t tail[4] = {0, 0, 0, 0};
-  const size_t ntail = std::min<size_t>(n, 4);
-  u64 newlines = 0;
-  MK_HIP(hipMemcpyAsync(&newlines, &d_st->newlines, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  MK_HIP(hipMemcpyAsync(tail + (4 - ntail), d_text + (n - ntail), ntail, hipMemcpyDeviceToHost, c->stream));
-  MK_HIP(hipStreamSynchronize(c->stream));
-  if ((rc = f.index.add_to(f.st.s_index)) != MK_OK) return rc;
-  const u64 lines = newlines + (tail[3] != '\n' ? 1 : 0);
-  const size_t nrec = (size_t)(lines / 4), first = f.records;
-  const unsigned trailing = (unsigned)(lines & 3);
-  f.st.lines += lines;
-  f.records += nrec;
-  // what trails behind the last complete record: `trailing` empty lines are that many '\n' behind a '\n' (or the text's start)
-  bool trail_ok = true;
-  for (unsigned i = 0; i < trailing && trail_ok; ++i) trail_ok = tail[3 - i] == '\n';
-  if (trailing && trail_ok && n > trailing) trail_ok = tail[3 - trailing] == '\n';
-  if (f.counting_only()) return MK_OK;
-  const auto fail_trailing = [&]() {
-    f.bad_rc = MK_ERR_UNSUPPORTED;
-    f.bad_msg = std::string(f.what) + ": record " + std::to_string(first + nrec) + " is malformed: the text ends inside it (" +
-                std::to_string(trailing) + " of its 4 lines)";
-    return MK_OK;
-  };
-  if (!nrec) return trail_ok ? MK_OK : fail_trailing();
+  static_assert(sizeof(QcStatus) <= FS_OWN_MAX && sizeof(QcStatus) % 8 == 0, "the status block of the call");
+  QcStatus hq{};
+  hq.bad = FS_NONE;
+  hq.min_len[0] = hq.min_len[1] = ~0ull;
+  FsIndex ix;
+  if ((rc = fs_index_open(c, f.tiles, f.index, f.st.s_index, d_text, n, &hq, sizeof hq, ix)) != MK_OK) return rc;
+  QcStatus* d_qs = (QcStatus*)ix.d_own;
+  const size_t nrec = ix.nrec;
+  size_t first;
+  f.st.lines += ix.lines;
+  if (!f.take(ix, first)) return MK_OK;
 
   // meta: line[4 nrec + 1] | rec[nrec] | rows[4 nrec] (the text call's, where the caller wants them)
   const size_t nidx = 4 * nrec;
@@ -331,36 +296,25 @@ static int qc_piece(QcCall& f, const uint8_t* d_text, size_t n) {
   QcRec* d_rec = (QcRec*)(line + nidx + 1);
   u64* d_rows = own_rows ? (u64*)(d_rec + nrec) : f.rows ? f.rows + 4 * first : nullptr;
 
-  if ((rc = f.index.begin()) != MK_OK) return rc;
-  const int end_is_n = lines == nidx ? 1 : 0;  // (no line 4 nrec starts: the last record ends with the text)
-  hipLaunchKernelGGL(fs_lines_k<false>, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_text, (u64)n, (const u64*)tile_pre, (u64)nidx,
-                     end_is_n, line, d_st);
-  MK_HIP(hipGetLastError());
-  if ((rc = f.index.end()) != MK_OK) return rc;
+  if ((rc = fs_index_lines<false>(c, f.index, d_text, n, ix, line)) != MK_OK) return rc;
   if ((rc = f.reads.begin()) != MK_OK) return rc;
   hipLaunchKernelGGL(qc_reads_k, dim3(grid_for(nrec, 256 / QT_GROUP, 1u << 16)), dim3(256), 0, c->stream, d_text, (u64)n, (const u64*)line,
                      nrec, f.o, f.t, d_rows, d_rec, d_qs);
   MK_HIP(hipGetLastError());
   if ((rc = f.reads.end()) != MK_OK) return rc;
-  MK_HIP(hipMemcpyAsync(&h.q, d_qs, sizeof h.q, hipMemcpyDeviceToHost, c->stream));
+  MK_HIP(hipMemcpyAsync(&hq, d_qs, sizeof hq, hipMemcpyDeviceToHost, c->stream));
   MK_HIP(hipStreamSynchronize(c->stream));
   if ((rc = f.index.add_to(f.st.s_index)) != MK_OK) return rc;
   if ((rc = f.reads.add_to(f.st.s_reads)) != MK_OK) return rc;
-  if (h.q.bad != FS_NONE) {
-    f.bad_rc = MK_ERR_UNSUPPORTED;
-    f.bad_msg = std::string(f.what) + ": record " + std::to_string(first + (size_t)(h.q.bad >> 3)) + " is malformed: " +
-                qc_kind((unsigned)(h.q.bad & 7));
-    return MK_OK;
-  }
-  if (!trail_ok) return fail_trailing();
-  f.st.bases += h.q.bases;
+  if (f.failed(ix, first, hq.bad, qc_kind)) return MK_OK;
+  f.st.bases += hq.bases;
   for (int k = 0; k < 2; ++k) {
-    f.mn[k] = std::min(f.mn[k], h.q.min_len[k]);
-    f.mx[k] = std::max(f.mx[k], h.q.max_len[k]);
+    f.mn[k] = std::min(f.mn[k], hq.min_len[k]);
+    f.mx[k] = std::max(f.mx[k], hq.max_len[k]);
   }
 
   // the cycles: as many tiles as the piece's longest read reaches, and the one behind them if it passes P
-  const u64 longest = std::max(h.q.max_len[0], h.q.max_len[1]);
+  const u64 longest = std::max(hq.max_len[0], hq.max_len[1]);
   if (longest) {
     const unsigned classes = f.o.paired ? 2u : 1u;
     const unsigned tiles = (unsigned)div_up((size_t)std::min<u64>(longest, f.o.P), QC_TILE);
@@ -388,29 +342,23 @@ static int qc_piece(QcCall& f, const uint8_t* d_text, size_t n) {
 template <class Pre, class Body, class Post>
 static int qc_run(QcCall& f, size_t* nrec, mk_fastq_qc_t* st, Pre&& pre, Body&& body, Post&& post) {
   mk_ctx* c = f.c;
-  MK_REFUSE_SPOILED(c, f.what);
-  if (c->in_chunk) { c->err = std::string(f.what) + ": a chunk is open"; return MK_ERR_STATE; }
-  if (nrec) *nrec = 0;
-  MK_HIP(hipSetDevice(c->device));
-  MK_HIP(hipStreamSynchronize(c->stream));
-  int rc;
-  if ((rc = pre()) != MK_OK) return rc;
-  rc = body();
-  (void)hipStreamSynchronize(c->stream);
+  int rc = fs_call(
+      c, f.what,
+      [&]() -> int {
+        if (nrec) *nrec = 0;
+        return MK_OK;
+      },
+      [&]() -> int {
+        const int r = pre();
+        return r != MK_OK ? r : body();
+      });
   if (rc != MK_OK) return rc;
   if (nrec) *nrec = f.records;
   if (f.records > f.limit) {
     c->err = std::string(f.what) + ": the text holds " + std::to_string(f.records) + " records, rows has room for " + std::to_string(f.limit);
     return MK_ERR_RANGE;
   }
-  if (f.o.paired && (f.records & 1)) {
-    c->err = std::string(f.what) + ": paired, but the text holds an odd number of records (" + std::to_string(f.records) + ")";
-    return MK_ERR_RANGE;
-  }
-  if (f.bad_rc != MK_OK) {
-    c->err = f.bad_msg;
-    return f.bad_rc;
-  }
+  if ((rc = fs_call_end(c, f.what, f.records, f.o.paired, f.bad_rc, f.bad_msg)) != MK_OK) return rc;
   if ((rc = post()) != MK_OK) return rc;
   f.st.records = f.records;
   for (int k = 0; k < 2; ++k) {
@@ -461,17 +409,9 @@ extern "C" int mk_fastq_qc_device(mk_ctx* c, const uint8_t* d_fastq, size_t n, c
       },
       [&]() -> int {
         if (!n) return MK_OK;
-        const uint8_t* d_text = d_fastq;
-        if ((uintptr_t)d_text & 15) {  // (the line passes and the granules load 16 aligned bytes at a time)
-          int rc = mk_buf_reserve(c, c->raw, n + 64);
-          if (rc != MK_OK) return rc;
-          const auto t1 = MkClock::now();
-          MK_HIP(hipMemcpyAsync(c->raw.p, d_fastq, n, hipMemcpyDeviceToDevice, c->stream));
-          MK_HIP(hipStreamSynchronize(c->stream));
-          f.st.s_copy += mk_since(t1);
-          d_text = (const uint8_t*)c->raw.p;
-        }
-        return qc_piece(f, d_text, n);
+        const uint8_t* d_text;
+        const int rc = fs_aligned_text(c, d_fastq, n, false, f.st.s_copy, &d_text);
+        return rc != MK_OK ? rc : qc_piece(f, d_text, n);
       },
       [&]() -> int { return MK_OK; });
 }
@@ -497,30 +437,17 @@ extern "C" int mk_fastq_qc_text(mk_ctx* c, const uint8_t* fastq, size_t n, size_
         return MK_OK;
       },
       [&]() -> int {
-        // the pieces of fq_text_body: they end behind a line 4j (8j: mates stay together) once they hold `piece` bytes
         if (!n) return MK_OK;
-        size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
-        piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
-        std::vector<uint64_t> cuts(n / piece + 2, 0);
-        size_t ncuts = 0;
-        if ((o.paired ? mk_fastq_pair_cuts : mk_fastq_cuts)(fastq, n, piece, cuts.data(), cuts.size(), &ncuts) != MK_OK) {
-          c->err = "mk_fastq_qc_text: the line scanner failed (internal error)";
-          return MK_ERR_STATE;
-        }
-        cuts.resize(ncuts);
-        cuts.push_back(n);
+        std::vector<uint64_t> cuts;
+        int rc = fs_piece_cuts(c, f.what, fastq, n, piece_bytes, o.paired, cuts);
+        if (rc != MK_OK) return rc;
         size_t from = 0;
         for (const uint64_t end : cuts) {
           const size_t len = (size_t)end - from;
           if (!len) continue;
           // (a record longer than the piece grows it: the kernels' 32-bit offsets and counters end at 2^32)
           if (len > 0xFFFFFFFFull) { c->err = "mk_fastq_qc_text: a piece holds at most 2^32 - 1 bytes"; return MK_ERR_RANGE; }
-          int rc = mk_buf_reserve(c, c->raw, len + 64);
-          if (rc != MK_OK) return rc;
-          const auto t1 = MkClock::now();
-          MK_HIP(hipMemcpyAsync(c->raw.p, fastq + from, len, hipMemcpyHostToDevice, c->stream));
-          MK_HIP(hipStreamSynchronize(c->stream));
-          f.st.s_copy += mk_since(t1);
+          if ((rc = fs_upload_raw(c, fastq + from, len, f.st.s_copy)) != MK_OK) return rc;
           if ((rc = qc_piece(f, (const uint8_t*)c->raw.p, len)) != MK_OK) return rc;
           from = (size_t)end;
         }

@@ -2,7 +2,7 @@
 // include/mercat_hip.h has the rule): the qualities that every other read call only carries along are read here, the
 // reads cut at both ends by the running sums of BWA -q / cutadapt -q, judged by length, N, low-quality share and mean
 // quality, and the survivors gathered as FASTQ -- on the GPU, by mk_fqselect.hip's scheme:
-//   fs_tiles_k / fs_scan_k / fs_lines_k<false>   the line index (mk_fqindex.h), unchanged.
+//   fs_index_open / fs_index_lines<false>        the line index (mk_fqindex.h), unchanged.
 //   qt_scan_k                16 lanes a record, four records a wave.  A lane owns one aligned 16-byte granule of the
 //                            quality line a pass (fs_load), a pass is the 256 bytes of its row of lanes.  The lane sums
 //                            its cut - q, a DPP row scan gives every lane the sum in front of it, the lane walks its 16

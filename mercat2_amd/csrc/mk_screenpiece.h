@@ -119,8 +119,7 @@ static int sc_run(mk_ctx* c, const char* what, unsigned flags, uint64_t at_least
 // The ends of those pieces for a text of n > 0 bytes, ascending; the last is n.
 static int sc_piece_ends(ScCall& s, const uint8_t* text, size_t n, size_t piece_bytes, std::vector<uint64_t>& cuts) {
   mk_ctx* c = s.c;
-  size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
-  piece = std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
+  const size_t piece = tl_piece_size(c, piece_bytes, n);
   cuts.assign(n / piece + 2, 0);
   size_t ncuts = 0;
   int r = mk_record_cuts(text, n, piece, (size_t)4 << 20, cuts.data(), cuts.size(), &ncuts);

@@ -256,8 +256,7 @@ int TlPieces::fail(int code, const std::string& msg) {
 
 int TlPieces::setup(size_t piece_bytes, size_t total_hint) {
   const size_t k = (size_t)c->k;
-  piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(total_hint + 2, 4096));
-  piece = std::min(std::max(piece, 2 * (k + 24)), TL_MAX_PIECE);
+  piece = tl_piece_size(c, piece_bytes, total_hint);
   if (2 * (k + 24) > TL_MAX_PIECE) return fail(MK_ERR_ARG, "k is too large for a table in text form");
   cap_rows = (piece + 64) / min_row() + 2;  // (a last line without its '\n' gets one: a piece may be one byte longer)
   MK_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));

@@ -13,6 +13,12 @@
 #define TL_NONE 0xFFFFFFFFu
 #define TL_MAX_PIECE ((size_t)1 << 30)  // positions inside a piece are 32-bit
 #define TL_DEFAULT_PIECE ((size_t)16 << 20)
+// The bytes a piece of a text of n bytes holds before it is cut: piece_bytes, or (0) the default, the whole of a small
+// text; never less than two of the longest rows of a table in text form, never more than 32-bit positions reach.
+static inline size_t tl_piece_size(const mk_ctx* c, size_t piece_bytes, size_t n) {
+  const size_t piece = piece_bytes ? piece_bytes : std::min(TL_DEFAULT_PIECE, std::max<size_t>(n + 2, 4096));
+  return std::min(std::max(piece, 2 * ((size_t)c->k + 24)), TL_MAX_PIECE);
+}
 
 // what the kernels of one piece tell the host (device memory, copied back once per piece)
 struct TlStatus {

@@ -795,6 +795,24 @@ def _big_u8(n: int) -> np.ndarray:
     return np.frombuffer(mmap.mmap(-1, n), dtype=np.uint8)
 
 
+def _fastq_in(path_or_bytes, count: bool = True) -> Tuple[int, int, object, int]:
+    """(address, nbytes, keepalive, records) of a FASTQ text given as a path to a plain file or as bytes: its 4-line
+    records, lines split on '\\n', a last line without one counting as a line (0 where ``count`` is off)."""
+    if isinstance(path_or_bytes, (str, os.PathLike)):
+        with open(path_or_bytes, "rb") as fh:
+            path_or_bytes = fh.read()
+    addr, size, held = _buf_ptr(path_or_bytes)
+    if not count:
+        return addr, size, held, 0
+    nl = int(np.count_nonzero(held == 10)) if size else 0
+    return addr, size, held, (nl + (1 if size and held[-1] != 10 else 0)) // 4
+
+
+def _fastq_out(size: int) -> np.ndarray:
+    """The output array of a call that writes records of a text of ``size`` bytes: at most one newline longer."""
+    return np.empty(size + 1, dtype=np.uint8)
+
+
 # ------------------------------------------------------------------------------ host helpers
 def chunk_cuts(text, chunksize: int) -> np.ndarray:
     """Offsets at which the reference Chunker would start chunks 1.. (lib/mercat2_Chunker.py:39-59)."""
@@ -1585,14 +1603,10 @@ class Counter:
         malformed record (the message names it), MK_ERR_RANGE for another record count or a kept[r] longer than its read.
         ``info``, if given, receives the mk_fastq_select_t fields."""
         keep, kept, nrec = _select_arrays(keep, kept)
-        if isinstance(path_or_bytes, (str, os.PathLike)):
-            with open(path_or_bytes, "rb") as fh:
-                path_or_bytes = fh.read()
-        addr, size, held = _buf_ptr(path_or_bytes)
-        if nrec < 0:  # (neither array: the text's own count -- lines split on '\n', a last line without one is a line)
-            nl = int(np.count_nonzero(held == 10)) if size else 0
-            nrec = (nl + (1 if size and held[-1] != 10 else 0)) // 4
-        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        addr, size, held, own = _fastq_in(path_or_bytes, count=nrec < 0)
+        if nrec < 0:  # (neither array: the text's own count)
+            nrec = own
+        out = _fastq_out(size)
         out_len, st = C.c_size_t(0), FastqSelect()
         self._check_select(self._L.mk_fastq_select_text(
             self._h, addr, size, int(piece_bytes), keep.ctypes.data if keep is not None else None,
@@ -1627,13 +1641,8 @@ class Counter:
         MK_ERR_UNSUPPORTED for a malformed record (the message names it), MK_ERR_RANGE for an odd record count with
         ``paired``.  ``info``, if given, receives the mk_fastq_qtrim_t fields."""
         opt = qtrim_options(cut_back, cut_front, min_len, max_n, low_q, max_low_frac, min_mean_q, phred_base, paired, which)
-        if isinstance(path_or_bytes, (str, os.PathLike)):
-            with open(path_or_bytes, "rb") as fh:
-                path_or_bytes = fh.read()
-        addr, size, held = _buf_ptr(path_or_bytes)
-        nl = int(np.count_nonzero(held == 10)) if size else 0
-        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
-        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        addr, size, held, cap = _fastq_in(path_or_bytes)
+        out = _fastq_out(size)
         keep, rows, hist = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 6), dtype=np.uint64), np.zeros((2, 256), dtype=np.uint64)
         out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqQtrim()
         self._check_select(self._L.mk_fastq_qtrim_text(
@@ -1672,15 +1681,9 @@ class Counter:
         opt = qc_options(max_pos, phred_base, paired)
         if not 1 <= opt.max_pos <= QC_MAX_POS:  # (before the tables are sized by it)
             raise MercatHipError(-1, "mk_fastq_qc_text: max_pos must be 1 .. %d" % QC_MAX_POS)
-        if isinstance(path_or_bytes, (str, os.PathLike)):
-            with open(path_or_bytes, "rb") as fh:
-                path_or_bytes = fh.read()
-        addr, size, held = _buf_ptr(path_or_bytes)
+        addr, size, held, cap = _fastq_in(path_or_bytes, count=rows)
         got = {name: np.zeros(shape, dtype=np.uint64) for name, shape in qc_shapes(opt.max_pos, bool(opt.paired)).items()}
-        cap = 0
         if rows:
-            nl = int(np.count_nonzero(held == 10)) if size else 0
-            cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
             got["rows"] = np.zeros((cap, 4), dtype=np.uint64)
         out = QcOut(**{name: a.ctypes.data for name, a in got.items()})
         nrec, st = C.c_size_t(0), FastqQc()
@@ -1720,13 +1723,8 @@ class Counter:
         opt = dedup_options(prefix, paired, which, high)
         if not 1 <= opt.high <= DEDUP_MAX_HIGH:  # (before levels is sized by it)
             raise MercatHipError(-1, "mk_fastq_dedup_text: high must lie in 1 .. 2^20")
-        if isinstance(path_or_bytes, (str, os.PathLike)):
-            with open(path_or_bytes, "rb") as fh:
-                path_or_bytes = fh.read()
-        addr, size, held = _buf_ptr(path_or_bytes)
-        nl = int(np.count_nonzero(held == 10)) if size else 0
-        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
-        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        addr, size, held, cap = _fastq_in(path_or_bytes)
+        out = _fastq_out(size)
         keep, rows = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 2), dtype=np.uint64)
         levels = np.zeros(opt.high + 2, dtype=np.uint64)
         out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqDedup()
@@ -1772,13 +1770,8 @@ class Counter:
             raise ValueError("fastq_adapt: adapters2 are searched in second mates: needs paired")
         opt = adapt_options(min_overlap, max_err, min_len, paired, which)
         bases, lengths, mates, seqs = adapter_arrays(adapters, adapters2)
-        if isinstance(path_or_bytes, (str, os.PathLike)):
-            with open(path_or_bytes, "rb") as fh:
-                path_or_bytes = fh.read()
-        addr, size, held = _buf_ptr(path_or_bytes)
-        nl = int(np.count_nonzero(held == 10)) if size else 0
-        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
-        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        addr, size, held, cap = _fastq_in(path_or_bytes)
+        out = _fastq_out(size)
         keep, rows, hits = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 5), dtype=np.uint64), np.zeros(len(seqs), dtype=np.uint64)
         out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqAdapt()
         self._check_select(self._L.mk_fastq_adapt_text(
@@ -1827,13 +1820,8 @@ class Counter:
         message names it), MK_ERR_RANGE for an odd record count.  ``info``, if given, receives the mk_fastq_overlap_t
         fields."""
         opt = overlap_options(mode, min_overlap, max_mismatch, max_err, min_len, which)
-        if isinstance(path_or_bytes, (str, os.PathLike)):
-            with open(path_or_bytes, "rb") as fh:
-                path_or_bytes = fh.read()
-        addr, size, held = _buf_ptr(path_or_bytes)
-        nl = int(np.count_nonzero(held == 10)) if size else 0
-        cap = (nl + (1 if size and held[-1] != 10 else 0)) // 4
-        out = np.empty(size + 1, dtype=np.uint8)  # (the output is at most one newline longer than the text)
+        addr, size, held, cap = _fastq_in(path_or_bytes)
+        out = _fastq_out(size)
         keep, rows = np.zeros(cap, dtype=np.uint8), np.zeros((cap, 5), dtype=np.uint64)
         out_len, nrec, st = C.c_size_t(0), C.c_size_t(0), FastqOverlap()
         self._check_select(self._L.mk_fastq_overlap_text(
