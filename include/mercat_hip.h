@@ -536,6 +536,57 @@ int mk_trim_device(mk_ctx* ctx, const uint8_t* d_text, size_t n, unsigned flags,
                    uint8_t* d_out, size_t out_cap, size_t* out_len, uint64_t* d_kept, mk_screen_row_t* d_rows, size_t cap,
                    size_t* nrows, mk_trim_t* st);
 
+/* ---- nucleotide sequences in, their open reading frames out as protein FASTA: six-frame stop-to-stop ORF calling (what
+ *      OrfM and getorf do in front of a protein k-mer profile), optionally from the first start codon.  No gene model, no
+ *      RBS, no scoring: this is not prodigal. ----
+ * Text, records and kept characters are mk_screen_*'s: same parser, lines stripped and joined, '*' removed, a header
+ * line without sequence is a record, a leading headless record is allowed, MK_ERR_NON_ASCII as there, pieces cut by
+ * mk_record_cuts (nothing depends on piece_bytes).  Any context of the device serves: alphabet and k do not matter, the
+ * table is neither read nor changed, the chunk buffers are scratch, a spoiled context or an open chunk is MK_ERR_STATE,
+ * the stream is idle afterwards and the counting figures are untouched.
+ * Rule: s[0..L) are a record's kept characters; A a -> 0, C c -> 1, G g -> 2, T t U u -> 3, every other byte "other".
+ * For t = s and then its reverse complement (complementing keeps "other") and each class c in 0, 1, 2, codon i covers
+ * t[c + 3i, c + 3i + 3) for i < (L - c) / 3.  A codon with an "other" byte translates to X and is neither stop nor
+ * start; any other by the standard code, index 16 c1 + 4 c2 + c3 in
+ *   KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF
+ * Stops are TAA TAG TGA.  A stretch is a maximal run of non-stop codons of one class; the record's ends close stretches
+ * too.  Default: the ORF is the stretch.  MK_ORF_START: the stretch from its first ATG on (with MK_ORF_ALT also GTG and
+ * TTG, translated as they stand); a stretch without a start yields nothing.  An ORF of fewer than min_aa codons is
+ * dropped.  Coordinates are on the forward strand, half open: an ORF [a', b') of the reverse complement is
+ * [L - b', L - a').  begin is the left end, aa the number of codons, frame 1 + c forward and 4 + c reverse.  Order: by
+ * (record, right end in forward coordinates of the stretch the ORF was cut from, forward before reverse); n is the ORF's
+ * 1-based rank within its record in that order.  MK_ORF_PLUS / MK_ORF_MINUS restrict the strand; ranks count what is
+ * emitted.
+ * Output, per ORF: '>' name '_' begin+1 '_' frame '_' n LF, the aa amino acids on one line, LF.  name: the bytes of the
+ * record's header line behind its '>' up to the first byte <= 0x20 or the end of the line; empty for the headless
+ * record.  No stop character is written.  rows[i] = {record (numbered over the whole call), begin, aa, frame}.
+ * A NULL opt, min_aa == 0, an unknown flag, MK_ORF_ALT without MK_ORF_START, or MK_ORF_PLUS with MK_ORF_MINUS is
+ * MK_ERR_ARG and the message names it.  out and rows may each be NULL (cap is ignored without rows).  With out_cap or
+ * cap too small: MK_ERR_RANGE, the needed sizes in *out_len and *norfs, nothing written past either -- every piece is
+ * still walked to learn them (out = NULL, out_cap = 0 is the sizing call; the output can be longer than the input).
+ * mk_orf_text: host memory in and out, piece by piece.  mk_orf_device: text, out and rows in DEVICE memory of the
+ * context's GPU, one piece; text and out at any address, d_rows aligned to 8 (MK_ERR_ARG otherwise). */
+#define MK_ORF_START 1u
+#define MK_ORF_ALT   2u   /* only with START, else MK_ERR_ARG */
+#define MK_ORF_PLUS  4u
+#define MK_ORF_MINUS 8u
+typedef struct mk_orf_opt_t { uint32_t min_aa, flags; } mk_orf_opt_t;
+typedef struct mk_orf_row_t { uint64_t record, begin; uint32_t aa, frame; } mk_orf_row_t;   /* 24 bytes */
+typedef struct mk_orf_t {
+  /* input bytes, records, kept characters; ORFs, their amino acids, output bytes, the longest ORF's codons, ORFs per
+   * frame 1..6; bytes in front of the first header line of a text that is not headless */
+  uint64_t bytes, records, bases, orfs, residues, bytes_out, longest, per_frame[6], preamble;
+  int32_t headless, pieces;
+  /* seconds: host time in the copies in; HIP-event time of the parse and record scan; of the ORF scan (tile summaries,
+   * carries, count, rows); of the record starts, names, lengths and their scan; of the gather; host time in the copies
+   * back; wall time of the call */
+  double s_read, s_parse, s_find, s_place, s_emit, s_write, s_total;
+} mk_orf_t;
+int mk_orf_text  (mk_ctx* ctx, const uint8_t* text,   size_t n, size_t piece_bytes, const mk_orf_opt_t* opt,
+                  uint8_t* out,   size_t out_cap, size_t* out_len, mk_orf_row_t* rows,   size_t cap, size_t* norfs, mk_orf_t* st);
+int mk_orf_device(mk_ctx* ctx, const uint8_t* d_text, size_t n,                     const mk_orf_opt_t* opt,
+                  uint8_t* d_out, size_t out_cap, size_t* out_len, mk_orf_row_t* d_rows, size_t cap, size_t* norfs, mk_orf_t* st);
+
 /* ---- sequences in, every isolated substitution the table can name put right out: k-mer-spectrum error correction
  *      where the counts are (the conservative "spectral alignment" step of Musket, Lighter, BFC and Quake; with
  *      abundance trimming and normalisation the third standard step in front of an assembly or a second count) ----

@@ -79,8 +79,14 @@ sequence bytes are equal -- with -dedup_prefix N their first N bases -- form a c
 interleaved once in front of -dedup).  dedup/<sample>_dedup.fastq holds what the later steps and the count see,
 dedup/<sample>_dedup.tsv every read's length, first, copies and keep value, _levels.tsv the clusters of 1 .. -dedup_high
 copies and of more (fastqc's duplication levels), _summary.tsv the duplication rate, _overrepresented.tsv the clusters that
-hold at least -dedup_over of the reads (at most 1000).  With -qc the raw stage is the text in front of -dedup.  QC plots, ORF calling
-(-prod / -fgs), the HTML report and plots belong
+hold at least -dedup_over of the reads (at most 1000).  With -qc the raw stage is the text in front of -dedup.  -orf stands where MerCat2
+runs -prod / -fgs: the six-frame stop-to-stop ORFs (mk_orf_text: at least MIN_AA codons; -orf_start from the first ATG,
+-orf_alt GTG and TTG too; -orf_strand) of the text the nucleotide count sees -- the cleaned text, the raw text with
+-skipclean, fq2fa's text for FASTQ after -dedup / -overlap / -adapt / -qtrim -- are called on the GPU, written to
+orf/<sample>_orf.faa and orf/<sample>_orf.tsv, and counted as the protein sample <sample>_orf with everything a protein
+sample gets.  It is a stated rule, not a gene caller: gene models, RBS scoring, other translation tables, M for alternative
+starts, partial-gene flags, the resolution of nested or overlapping ORFs and frameshift-aware calling stay out, and so does
+a separate k for the ORFs.  QC plots, prodigal and FragGeneScanRs themselves (-prod / -fgs), the HTML report and plots belong
 to the reference's other layers: their flags are accepted where they change nothing here (-lowmem, -debug,
 -category_file) and refused with a clear message where the run would need that layer's output (-prod, -fgs).
 """
@@ -248,7 +254,9 @@ def parseargs(argv=None):
                         "where FILE lacks it; diff: a - b where that is positive -- and no row where that is 0")
     p.add_argument("-against_min", type=int, default=1, metavar="N",
                    help="-against: a count of FILE below N is taken as absent [1]")
-    p.add_argument("-k", type=int, required=True, help="kmer length")
+    p.add_argument("-k", type=int, required=True,
+                   help="kmer length (with -orf the same k serves the nucleotide samples and their ORFs, as with MerCat2's -prod: "
+                        "a protein k such as 3 to 7 is meant then)")
     p.add_argument("-n", type=int, default=os.cpu_count() or 1,
                    help="no of cores [auto detect]: samples read (inflated) and counted concurrently, at most 8")
     p.add_argument("-c", type=int, default=10, help="minimum kmer count [10]")
@@ -299,6 +307,14 @@ def parseargs(argv=None):
     # flags of the reference's other layers (bin/mercat2.py:45-58)
     p.add_argument("-prod", action="store_true", help="(MerCat2: ORF calling with prodigal) not part of this engine")
     p.add_argument("-fgs", action="store_true", help="(MerCat2: ORF calling with FragGeneScanRs) not part of this engine")
+    p.add_argument("-orf", type=int, nargs="?", const=32, default=None, metavar="MIN_AA",
+                   help="nucleotide input: call the six-frame stop-to-stop ORFs of at least MIN_AA codons [32] of the text the "
+                        "count sees on the GPU, where MerCat2 runs prodigal (-prod) or FragGeneScanRs (-fgs) -- a stated rule, what "
+                        "OrfM and getorf do, not a gene caller; writes orf/<sample>_orf.faa and orf/<sample>_orf.tsv and counts "
+                        "the protein sample <sample>_orf with the same -k (a protein k such as 3 to 7 is meant)")
+    p.add_argument("-orf_start", action="store_true", help="-orf: an ORF begins at the first ATG of its stop-to-stop stretch")
+    p.add_argument("-orf_alt", action="store_true", help="-orf_start: GTG and TTG start too (translated as they stand, not as M)")
+    p.add_argument("-orf_strand", choices=["both", "plus", "minus"], default=None, help="-orf: the strand(s) to call [both]")
     p.add_argument("-lowmem", action="store_true",
                    help="(MerCat2: incremental PCA beyond 1000 samples) accepted, no effect: the PCA here is exact, and is not "
                         "computed for more than 1000 samples")
@@ -647,6 +663,19 @@ def parseargs(argv=None):
             k = native.tsv_shape(path)["k"]
             if k and k != args.k:
                 p.error(f"-k {args.k}: '{path}' holds {k}-mers")
+    if args.orf is None and (args.orf_start or args.orf_alt or args.orf_strand is not None):
+        p.error("-orf_start / -orf_alt / -orf_strand need -orf")
+    if args.orf is not None and args.orf < 1:
+        p.error("-orf MIN_AA must be 1 or more")
+    if args.orf_alt and not args.orf_start:
+        p.error("-orf_alt needs -orf_start")
+    if args.orf is not None:  # refused here, before anything runs
+        samples, _ = input_samples(args)
+        if not samples["nucleotide"]:
+            p.error("-orf calls the ORFs of nucleotide samples: no nucleotide input file is given")
+        for base in samples["nucleotide"]:
+            if f"{base}_orf" in samples["protein"] or f"{base}_orf" in args.loaded["protein"]:
+                p.error(f"-orf: the ORFs of '{base}' are counted as the protein sample '{base}_orf', which is given as an input already")
     if args.prod or args.fgs:
         p.error("-prod / -fgs call ORFs with prodigal / FragGeneScanRs before counting amino-acid k-mers; that layer is "
                 "not part of this engine: run the ORF caller and pass its .faa output with -i / -f")
@@ -716,6 +745,53 @@ def classify(path: Path, skipclean: bool = False):
         return None, None
     base = path.name[: -len(ext)]
     return ("protein" if ext in FILE_EXT_PROTEIN else "nucleotide"), base
+
+
+def orf_samples(args, samples: dict, cleaned: dict, clean_paths: dict, out: Path, devices) -> None:
+    """-orf: for every nucleotide sample the ORFs of the text its count saw -- the file under clean/ (once its writer has
+    finished), or with -skipclean the FASTA file itself -- called by kmers.orf_reads, which writes orf/<sample>_orf.faa and
+    orf/<sample>_orf.tsv; the .faa joins ``samples["protein"]`` as <sample>_orf."""
+    from . import kmers, native
+    folder = out / "orf"
+    folder.mkdir(parents=True, exist_ok=True)
+    start = timeit.default_timer()
+    total = 0
+    for idx, (base, f) in enumerate(samples["nucleotide"].items()):
+        job = cleaned.get(base)
+        if job is not None:
+            job[2].result()  # (the clean file is complete)
+        faa = folder / f"{base}_orf.faa"
+        try:
+            done = kmers.orf_reads(read_fasta_bytes(clean_paths.get(base, f)), faa, min_aa=args.orf, start=args.orf_start,
+                                   alt_starts=args.orf_alt, strand=args.orf_strand or "both", tsv_path=folder / f"{base}_orf.tsv",
+                                   device=devices[idx % len(devices)])
+        except native.MercatHipError as e:
+            raise SystemExit(f"-orf '{f.name}': {e}")
+        total += done["orfs"]
+        samples["protein"][f"{base}_orf"] = faa
+    print(f"orf/: {total} ORFs of at least {args.orf} codons in {len(samples['nucleotide'])} sample(s): "
+          f"{round(timeit.default_timer() - start, 2)} seconds")
+
+
+def input_samples(args):
+    """(samples, fastq) of the input files: {"nucleotide": {sample: file}, "protein": {...}} by ``classify``, and the
+    nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)."""
+    files = [Path(f) for f in args.i]
+    if args.f:
+        folder = Path(os.path.abspath(os.path.expanduser(args.f)))
+        files += [folder / name for name in sorted(os.listdir(folder)) if (folder / name).is_file()]
+    samples = {"nucleotide": {}, "protein": {}}
+    fastq = set()
+    for f in files:
+        kind, base = classify(f.expanduser().absolute(),
+                              args.skipclean or args.dedup or args.qtrim is not None or args.adapt is not None or args.overlap is not None)
+        if kind:
+            samples[kind][base] = f
+            if fastq_ext(f):
+                fastq.add(base)
+            else:
+                fastq.discard(base)
+    return samples, fastq
 
 
 def qtrim_sample(args, f: Path, raw, out: Path, base: str, device: int) -> bytes:
@@ -934,22 +1010,7 @@ def main(argv=None) -> int:
                 empty.lookup_text(args.query)
         except native.MercatHipError as e:
             raise SystemExit(f"-query {args.query}: {e}")
-    files = [Path(f) for f in args.i]
-    if args.f:
-        folder = Path(os.path.abspath(os.path.expanduser(args.f)))
-        files += [folder / name for name in sorted(os.listdir(folder)) if (folder / name).is_file()]
-    samples = {"nucleotide": {}, "protein": {}}
-    fastq = set()  # nucleotide samples given as FASTQ (-skipclean: fq2fa, then counted)
-    for f in files:
-        kind, base = classify(f.expanduser().absolute(),
-                              args.skipclean or args.dedup or args.qtrim is not None or args.adapt is not None or args.overlap is not None)
-        if kind:
-            samples[kind][base] = f
-            if fastq_ext(f):
-                fastq.add(base)
-            else:
-                fastq.discard(base)
-
+    samples, fastq = input_samples(args)
     for kind in samples:
         both = sorted(set(samples[kind]) & set(args.loaded[kind]))
         if both:
@@ -963,6 +1024,7 @@ def main(argv=None) -> int:
     print("Loading files")
     load_start = timeit.default_timer()
     clean = not args.skipclean
+    clean_paths = {}  # base -> the file under clean/ that holds the text the count saw (-orf reads it back)
     cleaned = {}  # base -> [clean file, raw bytes (until counted), future of (.gz size, stats), holder of the cleaned text, timings]
     gz_writers = ThreadPoolExecutor(max(1, min(int(args.n), 16)))
     to_load = {b: f for b, f in samples["nucleotide"].items() if clean or b in fastq}
@@ -1001,6 +1063,8 @@ def main(argv=None) -> int:
     print(f"Time to load {len(samples['nucleotide']) + len(samples['protein'])} files: {round(timeit.default_timer() - load_start, 2)} seconds")
 
     for kind in ("nucleotide", "protein"):
+        if kind == "protein" and args.orf is not None:  # the ORFs of the nucleotide samples join the protein samples
+            orf_samples(args, samples, cleaned, clean_paths, out, devices)
         if not samples[kind] and not args.loaded[kind]:
             continue
         print("Processing Nucleotides" if kind == "nucleotide" else "Processing protein")
@@ -1031,12 +1095,14 @@ def main(argv=None) -> int:
                     text, _ = fq2fa_text(prepared_reads(args, f, None, out, base, home, timings=t))
                     os.makedirs(out / "clean", exist_ok=True)
                     size = _write_clean_gz(out / "clean" / f"{base}.fna.gz", text, t)
+                    clean_paths[base] = out / "clean" / f"{base}.fna.gz"
                     chunked = args.s > 0 and size >= limit
                     run_text(base, text, tsv, args.k, args.c, args.s, chunked, device=home, devices=devices if chunked else None,
                              streams=args.streams, canonical=args.canonical, report=lines.append, keep=tables, timings=t)
                     del text
                 else:
                     clean_file, raw, fut, holder, t_load = cleaned[base]
+                    clean_paths[base] = clean_file
                     # the table straight from the raw reads, counted as fq2fa leaves them (rewritten in place on the GPU),
                     # while the conversion and the level-9 gzip of clean/<base>.fna.gz run in the background
                     done = run_raw_fastq(base, raw, tsv, args.k, args.c, limit, device=home, canonical=args.canonical,
@@ -1051,6 +1117,7 @@ def main(argv=None) -> int:
                 limit = args.s * 1024 * 1024
                 if cleaned[base] is None:  # (not loaded up front: the rewrite, its file, then the count, one after the other)
                     clean_file, _gc, text = removeN_text(f, out / "clean", args.toupper, timings=t)
+                    clean_paths[base] = clean_file
                     chunked = args.s > 0 and os.stat(clean_file).st_size >= limit
                     run_text(base, text, tsv, args.k, args.c, args.s, chunked, device=home, devices=devices if chunked else None,
                              streams=args.streams, canonical=args.canonical, report=lines.append, keep=tables, timings=t)
@@ -1058,6 +1125,7 @@ def main(argv=None) -> int:
                     t_load = {}
                 else:
                     clean_file, raw, fut, holder, t_load = cleaned[base]
+                    clean_paths[base] = clean_file
                     # the table straight from the raw text, counted as removeN leaves it (N runs cut records: the GPU finds
                     # them in the parser's pass), while the rewrite and the level-9 gzip of the clean file run in the background
                     done = run_raw_clean(base, raw, tsv, args.k, args.c, args.toupper, limit, device=home, canonical=args.canonical,

@@ -187,15 +187,16 @@ int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows
   if (h.headless) s.out.headless = 1;
   s.last.nrows = nrows;
   s.last.headless = h.headless != 0;
+  // (what the parse and the scan left is the caller's with or without rows: room 0 is the call that wants no probe)
+  s.last.tile_pre = tile_pre;
+  s.last.seq_len = (size_t)info.seq_len;
+  s.last.row_base = h.headless ? 0 : 1;
   if (!nrows || nrows > room) return MK_OK;  // (too many: the call goes on counting records and answers MK_ERR_RANGE)
   if (!d_rows) {
     if ((rc = mk_buf_reserve(c, *own, nrows * sizeof(mk_screen_row_t))) != MK_OK) return rc;
     d_rows = (mk_screen_row_t*)own->p;
   }
   s.last.d_rows = d_rows;
-  s.last.tile_pre = tile_pre;
-  s.last.seq_len = (size_t)info.seq_len;
-  s.last.row_base = h.headless ? 0 : 1;
   if ((rc = s.probe.begin()) != MK_OK) return rc;
   hipLaunchKernelGGL(sc_rows_init_k, dim3(grid_for(nrows, 256, 4096)), dim3(256), 0, c->stream, d_rows, nrows);
   if (info.seq_len && (rc = sc_launch_probe(s, (size_t)info.seq_len, tile_pre, h.headless ? 0 : 1, d_rows, d_st)) != MK_OK) return rc;

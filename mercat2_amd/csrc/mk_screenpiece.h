@@ -85,7 +85,9 @@ struct ScCall {
 
 // One piece of n bytes at d_text (device memory, whole records): parsed, scanned, and -- where there is room for all its
 // rows -- probed into d_rows (room rows; nullptr: the call's own buffer `own`, copied to h_rows if that is given).  The
-// piece's records are added to s.rows_seen either way.  The stream is idle afterwards.
+// piece's records are added to s.rows_seen either way, and s.last holds what the parse and the scan left (text, nrows,
+// headless, tile_pre, seq_len, row_base) with or without rows: room 0 is the call that wants no probe (mk_orf.hip).  The
+// stream is idle afterwards.
 int sc_piece(ScCall& s, const uint8_t* d_text, size_t n, mk_screen_row_t* d_rows, size_t room, MkDevBuf* own, mk_screen_row_t* h_rows);
 
 // How the calls open (lk_open's rules) and end; body: the pieces.  cap: rows the caller has room for.

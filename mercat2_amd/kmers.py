@@ -172,6 +172,45 @@ def track_reads(table: "native.Counter", file: Union[str, Path], at_least: int =
     return names, counts, offsets, rows, med
 
 
+def orf_names(text: bytes) -> List[bytes]:
+    """The names of a FASTA text's records as Counter.orfs writes them in front of an ORF's coordinates: per header line
+    (``record_names``' test) the bytes behind its '>' up to the first byte <= 0x20, and a leading b"" when sequence
+    stands in front of the first header line."""
+    names: List[bytes] = []
+    headless = False
+    for line in bytes(text).replace(b"\r\n", b"\n").replace(b"\r", b"\n").split(b"\n"):
+        line = line.strip(_BLANKS)
+        if line.startswith(b">"):
+            end = 1
+            while end < len(line) and line[end] > 0x20:
+                end += 1
+            names.append(line[1:end])
+        elif not names and not headless and line.replace(b"*", b""):
+            headless = True
+    return ([b""] if headless else []) + names
+
+
+def orf_reads(file: Union[str, Path, bytes], out_path: Union[str, Path, None], min_aa: int = 32, start: bool = False,
+              alt_starts: bool = False, strand: str = "both", tsv_path: Union[str, Path, None] = None, device: int = 0) -> Dict[str, object]:
+    """The open reading frames of a nucleotide FASTA or FASTQ file ('.gz' inflated, FASTQ converted by mk_fq2fa; or the
+    FASTA text itself as bytes, for a caller that holds it already), called on the GPU and written as protein FASTA to
+    ``out_path`` (gzip level 1 if it ends in '.gz'; None: not written).  Counter.orfs has the rule: six-frame
+    stop-to-stop ORFs of ``min_aa`` codons or more, from the first ATG with ``start`` (GTG and TTG too with
+    ``alt_starts``), ``strand`` "both", "plus" or "minus".  This stands where MerCat2 runs prodigal or FragGeneScan; it
+    is that stated rule, not a gene caller.  ``tsv_path``: one line per ORF (report.write_orf_tsv).  No table is read: the
+    call opens a small context of its own on ``device``.  Returns the mk_orf_t figures, without the timings."""
+    text = bytes(file) if isinstance(file, (bytes, bytearray, memoryview)) else _reads_text(file)
+    info: Dict[str, object] = {}
+    with native.Counter(5, native.ALPHABET_NT2, device=device) as ctx:
+        out, rows = ctx.orfs(text, min_aa=min_aa, start=start, alt_starts=alt_starts, strand=strand, info=info)
+    if out_path is not None:
+        _write_reads(out_path, out)
+    if tsv_path is not None:
+        from .report import write_orf_tsv
+        write_orf_tsv(tsv_path, orf_names(text), rows)
+    return {name: value for name, value in info.items() if not name.startswith("s_")}
+
+
 def _reads_text(file: Union[str, Path]) -> bytes:
     """A FASTA or FASTQ file as the read-writing calls read it: '.gz' inflated, FASTQ converted by mk_fq2fa."""
     text = read_fasta_bytes(file)

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "mk_lookup", "mk_lookup_device", "mk_lookup_text", "mk_lookup_file", "mk_histo", "mk_histo_device",
     "mk_screen_text", "mk_screen_device", "mk_table_op", "mk_filter_text", "mk_filter_device",
     "mk_track_text", "mk_track_device", "mk_trim_text", "mk_trim_device", "mk_correct_text", "mk_correct_device",
+    "mk_orf_text", "mk_orf_device",
     "mk_correct_fastq_text", "mk_correct_fastq_device", "mk_norm_text", "mk_norm_device",
     "mk_pairs_text", "mk_pairs_device", "mk_interleave", "mk_split_pairs", "mk_host_error",
     "mk_fastq_select_text", "mk_fastq_select_device", "mk_fastq_cuts", "mk_fq_interleave", "mk_fq_split_pairs",
@@ -192,6 +193,51 @@ class Trim(C.Structure):
         d = self.screen.as_dict()
         d.update({n: getattr(self, n) for n, _ in self._fields_[1:]})
         return d
+
+
+ORF_START, ORF_ALT, ORF_PLUS, ORF_MINUS = 1, 2, 4, 8  # MK_ORF_*
+ORF_STRANDS = {"both": 0, "plus": ORF_PLUS, "minus": ORF_MINUS}
+ORF_COLUMNS = ("record", "begin", "aa", "frame")  # the columns of Counter.orfs' rows
+# the standard code, index 16 c1 + 4 c2 + c3 with A 0, C 1, G 2, T 3 (include/mercat_hip.h)
+CODON_TABLE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
+ORF_ROW_DTYPE = np.dtype([("record", "<u8"), ("begin", "<u8"), ("aa", "<u4"), ("frame", "<u4")])  # mk_orf_row_t
+
+
+class OrfOpt(C.Structure):
+    """mk_orf_opt_t (include/mercat_hip.h)."""
+    _fields_ = [("min_aa", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Orf(C.Structure):
+    """mk_orf_t (include/mercat_hip.h)."""
+    _fields_ = ([(n, C.c_uint64) for n in ("bytes", "records", "bases", "orfs", "residues", "bytes_out", "longest")] +
+                [("per_frame", C.c_uint64 * 6), ("preamble", C.c_uint64), ("headless", C.c_int32), ("pieces", C.c_int32)] +
+                [(n, C.c_double) for n in ("s_read", "s_parse", "s_find", "s_place", "s_emit", "s_write", "s_total")])
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["per_frame"] = [int(v) for v in self.per_frame]
+        return d
+
+
+def orf_options(min_aa: int = 32, start: bool = False, alt_starts: bool = False, strand: str = "both") -> "OrfOpt":
+    """mk_orf_opt_t of Counter.orfs' arguments; ValueError for a min_aa no uint32 holds, a strand that is none of
+    "both", "plus", "minus", or alt_starts without start."""
+    if strand not in ORF_STRANDS:
+        raise ValueError("strand %r: must be 'both', 'plus' or 'minus'" % (strand,))
+    if alt_starts and not start:
+        raise ValueError("alt_starts needs start")
+    if not 0 <= int(min_aa) <= 0xFFFFFFFF:
+        raise ValueError("min_aa %r does not fit mk_orf_opt_t" % (min_aa,))
+    return OrfOpt(int(min_aa), (ORF_START if start else 0) | (ORF_ALT if alt_starts else 0) | ORF_STRANDS[strand])
+
+
+def orf_rows(raw: np.ndarray) -> np.ndarray:
+    """mk_orf_row_t records as the (n, 4) uint64 array Counter.orfs returns: record, begin, aa, frame."""
+    out = np.empty((raw.size, 4), dtype=np.uint64)
+    for j, name in enumerate(ORF_COLUMNS):
+        out[:, j] = raw[name]
+    return out
 
 
 class CorrectRule(C.Structure):
@@ -705,6 +751,10 @@ def lib() -> C.CDLL:
                                    C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
         "mk_trim_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(TrimRule), C.c_void_p, C.c_size_t, szp,
                                      C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Trim)]),
+        "mk_orf_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.POINTER(OrfOpt), C.c_void_p, C.c_size_t, szp,
+                                  C.c_void_p, C.c_size_t, szp, C.POINTER(Orf)]),
+        "mk_orf_device": (C.c_int, [vp, u8p, C.c_size_t, C.POINTER(OrfOpt), C.c_void_p, C.c_size_t, szp,
+                                    C.c_void_p, C.c_size_t, szp, C.POINTER(Orf)]),
         "mk_correct_text": (C.c_int, [vp, u8p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(CorrectRule), C.c_void_p, C.c_size_t, szp,
                                       C.c_void_p, C.c_void_p, C.c_size_t, szp, C.POINTER(Correct)]),
         "mk_correct_device": (C.c_int, [vp, u8p, C.c_size_t, C.c_uint, C.POINTER(CorrectRule), C.c_void_p, C.c_size_t, szp,
@@ -1934,6 +1984,52 @@ class Counter:
         self._check(self._L.mk_trim_device(self._h, ptr, int(nbytes), TRIM_FOLD if self._fold_flag(fold) else 0, C.byref(rule),
                                            out_ptr or None, int(out_cap), C.byref(out_len), kept_ptr or None, rows_ptr or None,
                                            int(cap), C.byref(n), C.byref(st)))
+        return st.as_dict()
+
+    # -- ORF calling: nucleotide FASTA text in, its six-frame ORFs out as protein FASTA; no table is read
+    def orfs(self, path_or_bytes, min_aa: int = 32, start: bool = False, alt_starts: bool = False, strand: str = "both",
+             piece_bytes: int = 0, info: Optional[dict] = None):
+        """mk_orf_text: (out, rows) of the FASTA text (a path to a plain file, or the text itself as bytes).  ``out``: one
+        protein record per ORF of ``min_aa`` codons or more -- '>' name '_' begin+1 '_' frame '_' rank, then the amino
+        acids on one line -- in the order (record, right end, forward before reverse).  Stop-to-stop by default;
+        ``start``: from the first ATG of a stretch on (``alt_starts``: GTG and TTG too).  ``strand`` "both", "plus" or
+        "minus".  ``rows``: (n, 4) uint64: record, begin (0-based, forward strand), aa, frame (1-3 forward, 4-6
+        reverse).  The sizes come from a sizing call first.  ``info``, if given, receives the mk_orf_t fields."""
+        opt = orf_options(min_aa, start, alt_starts, strand)
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as fh:
+                path_or_bytes = fh.read()
+        addr, size, held = _buf_ptr(path_or_bytes)
+        out_len, n, st = C.c_size_t(0), C.c_size_t(0), Orf()
+        rc = self._L.mk_orf_text(self._h, addr, size, int(piece_bytes), C.byref(opt), None, 0, C.byref(out_len), None, 0,
+                                 C.byref(n), C.byref(st))
+        if rc != -7:
+            self._check(rc)  # (MK_OK: nothing to write)
+        out = np.empty(max(out_len.value, 1), dtype=np.uint8)
+        raw = np.zeros(max(n.value, 1), dtype=ORF_ROW_DTYPE)
+        if rc:
+            self._check(self._L.mk_orf_text(self._h, addr, size, int(piece_bytes), C.byref(opt), out.ctypes.data, out_len.value,
+                                            C.byref(out_len), raw.ctypes.data, n.value, C.byref(n), C.byref(st)))
+        if info is not None:
+            info.update(st.as_dict())
+        return out[: out_len.value].tobytes(), orf_rows(raw[: n.value])
+
+    def orfs_device(self, ptr: int, nbytes: int, out_ptr: int, out_cap: int, rows_ptr: int = 0, cap: int = 0, **options) -> dict:
+        """mk_orf_device: ``nbytes`` of FASTA text (whole records) at device address ``ptr`` -> the protein records at
+        device address ``out_ptr`` (room for ``out_cap``) and, where given, the mk_orf_row_t rows (24 bytes each) at
+        ``rows_ptr`` (aligned to 8) with room for ``cap`` -- all on this context's GPU.  ``options``: those of
+        orf_options.  Returns the mk_orf_t fields; with too little room MercatHipError (MK_ERR_RANGE) whose ``needed``
+        holds the sizes (out_len, norfs)."""
+        opt = orf_options(**options)
+        out_len, n, st = C.c_size_t(0), C.c_size_t(0), Orf()
+        rc = self._L.mk_orf_device(self._h, ptr, int(nbytes), C.byref(opt), out_ptr or None, int(out_cap), C.byref(out_len),
+                                   rows_ptr or None, int(cap), C.byref(n), C.byref(st))
+        if rc == -7:
+            msg = self._L.mk_last_error(self._h)
+            err = MercatHipError(rc, msg.decode() if msg else "")
+            err.needed = (out_len.value, n.value)
+            raise err
+        self._check(rc)
         return st.as_dict()
 
     # -- correcting: FASTA text in, every record with its isolated substitutions put right out; the table is only read

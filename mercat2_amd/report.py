@@ -212,6 +212,30 @@ def write_trim_tsv(path, names: Sequence[str], lengths, kept, keep=None) -> int:
     return len(names)
 
 
+def format_orf_tsv(names: Sequence[str], rows) -> bytes:
+    """``record\tname\tbegin\tend\tstrand\tframe\taa``, then one line per ORF (kmers.orf_reads / Counter.orfs): the number
+    of its record in the text, that record's name (``names[record]``), where it lies on the forward strand -- 0-based,
+    half open, ``end - begin == 3 * aa`` --, ``+`` for frames 1 to 3 and ``-`` for 4 to 6, the frame and its amino
+    acids."""
+    out = [b"record\tname\tbegin\tend\tstrand\tframe\taa\n"]
+    for row in rows:
+        record, begin, aa, frame = (int(v) for v in row)
+        if not 0 <= record < len(names):
+            raise ValueError("format_orf_tsv: record %d of %d names" % (record, len(names)))
+        name = names[record]
+        name = name if isinstance(name, bytes) else name.encode()
+        out.append(b"%d\t%s\t%d\t%d\t%s\t%d\t%d\n" % (record, name, begin, begin + 3 * aa, b"+" if frame < 4 else b"-", frame, aa))
+    return b"".join(out)
+
+
+def write_orf_tsv(path, names: Sequence[str], rows) -> int:
+    """``format_orf_tsv`` written to ``path``; returns the number of ORFs."""
+    text = format_orf_tsv(names, rows)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return len(rows)
+
+
 def format_correct_tsv(names: Sequence[str], lengths, fix) -> bytes:
     """``record\tlength\truns\tfixed\tambiguous\tunfixable``, then one line per record (kmers.correct_reads /
     Counter.correct): its name, its characters and the four columns of its ``fix`` row."""
